@@ -11,8 +11,14 @@ Default workload (N=1): BASELINE.json configs[2] = "C3": 1e8 samples, 3 observab
 shift+scale+resolution_scale floated, 20^3 bins, 1e5 data events.  Inputs are synthetic, generated on
 the GPU and resident in HBM before the timed region.
 
-  python bench.py [--gpus N] [--steps K] [--warmup W]
+  python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]
   python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...
+
+A plain run sets up, warms up, times the K steps and prints the result line (metric, value, unit, ms_per_step, ...).
+--full adds everything else the bench measures and checks after the timed steps: the roofline sample of the fill
+kernel, parity against the CPU oracle and its timing (cpu_baseline), the ensemble leg of whole fake experiments, the
+gather of the intervals and the sub-records (--also).  --dump-outputs DIR writes what the timed steps computed as
+DIR/<name>.npy (dump_outputs below).
 
 N>1: fake experiments shard over the GPUs (sxmc.cpp:59 is an independent-iteration loop); every rank
 holds a replica of the MC tables and walks its own chain with its own seed -- no data-path
@@ -33,6 +39,7 @@ if ROOT not in sys.path:
 
 HBM_PEAK_GBS = 8000.0      # MI355X HBM3E peak (MI355X_MICROARCH.md: 8.0 TB/s spec)
 ROOFLINE_LAUNCHES = 100    # event-timed fill launches behind `roofline` (after the timed region, whatever --steps is)
+DUMP_LIMIT_BYTES = 64 << 20   # --dump-outputs: all files together
 
 
 def source_fingerprints():
@@ -204,6 +211,46 @@ def chain_intervals(chain, nparameters):
     return out
 
 
+def step_outputs(leg, chain, accepted):
+    """What a caller of the timed path holds after its last timed step, by name: the chain's rows of the timed steps
+    (one per step: the parameter vector the chain stands at, then its NLL), the accepted count, the chain's current
+    vector and NLL, and the last step's proposal with the NLL evaluated at it.  The `pdfz` form walks no chain: its
+    caller receives every evaluator's histogram and normalisation."""
+    m = leg.m
+    if leg.form == "pdfz":
+        return {"histograms": np.concatenate([p.GetBins().reshape(-1) for p in m.pdfs]).astype(np.float64),
+                "normalizations": m.normalizations.get().astype(np.float64)}
+    return {"chain": np.asarray(chain, np.float32), "accepted": np.array([accepted], np.float64),
+            "current_vector": m.current_vector.get().astype(np.float64),
+            "current_nll": m.current_nll.get().astype(np.float64),
+            "proposed_vector": m.proposed_vector.get().astype(np.float64),
+            "proposed_nll": m.proposed_nll.get().astype(np.float64)}
+
+
+def dump_outputs(outdir, arrays, limit=DUMP_LIMIT_BYTES):
+    """--dump-outputs: every array as outdir/<name>.npy (float32 or float64).  Should they exceed `limit` bytes in all,
+    the largest is cut to a fixed sample of its rows (seed 0, in order, its last row always kept) until they fit, so
+    that two builds run with the same arguments can be compared output for output.  Returns {name: shape}."""
+    os.makedirs(outdir, exist_ok=True)
+    arrays = {k: np.ascontiguousarray(v) for k, v in arrays.items()}
+    for k, v in arrays.items():
+        if v.dtype not in (np.float32, np.float64):
+            raise TypeError("%s: %s is not float32 or float64" % (k, v.dtype))
+    while sum(v.nbytes for v in arrays.values()) > limit:
+        k = max(arrays, key=lambda n: arrays[n].nbytes)
+        v = arrays[k]
+        others = sum(a.nbytes for n, a in arrays.items() if n != k)
+        row_bytes = max(1, v.nbytes // max(v.shape[0], 1))
+        keep = max(1, min(v.shape[0] - 1, (limit - others) // row_bytes))
+        if v.shape[0] <= 1:
+            raise ValueError("--dump-outputs: %s alone exceeds %d bytes" % (k, limit))
+        rows = np.random.default_rng(0).choice(v.shape[0] - 1, keep - 1, replace=False)
+        arrays[k] = v[np.append(np.sort(rows), v.shape[0] - 1)]
+    for k, v in arrays.items():
+        np.save(os.path.join(outdir, k + ".npy"), v)
+    return {k: list(v.shape) for k, v in arrays.items()}
+
+
 FORMS = {"step": "step", "fused": True, "graph": True, "reference": False, "pdfz": True, "dropin": "dropin"}
 K40_SAMPLES_PER_SEC = 2.99546e9     # /root/reference/README.md:322, `bench_sxmc pdfz` on an Nvidia Tesla K40 (the table's best)
 
@@ -367,15 +414,19 @@ class Leg:
         m.group.Profile(False, 0)
         self._launches = m.group.LastStepLaunches() if (m.consume and m.tail and self.form != "pdfz") else None
         self.elapsed, self.steps = elapsed, steps
-        # ---- the roofline sample, decoupled from --steps: AFTER the timed region (ms_per_step comes from the timed
-        # steps alone) the walk goes on for ROOFLINE_LAUNCHES more steps launched one by one, each fill bracketed by
-        # HIP events on the stream it is launched on, from the state the chain has reached
-        n = max(ROOFLINE_LAUNCHES, 0)
         self.fill_ms_total, self.nfill = self.fill_ms_region, self.nfill_region
         self.roofline_sample = "inside the timed region: the %d steps launched one by one" % self.nfill_region
-        self.region_chain = None
+        self.event_bracket_ms = None
+        self.region_chain = m.flush()              # (rows kept, accepted) of the timed steps: what the line reports
+        return elapsed
+
+    def post_timed_sample(self):
+        """The roofline sample (--full), decoupled from --steps: AFTER the timed region (ms_per_step comes from the
+        timed steps alone) the walk goes on for ROOFLINE_LAUNCHES more steps launched one by one, each fill bracketed
+        by HIP events on the stream it is launched on, from the state the chain has reached."""
+        m, torch = self.m, self.torch
+        n = max(ROOFLINE_LAUNCHES, 0)
         if n > 0:
-            self.region_chain = m.flush()          # (rows kept, accepted) of the timed steps: what the line reports
             m.group.Profile(True, 2 * n + 8)
             if self.la is not None:
                 self.la.steps(2 * n, graph_passes=0)      # (one or two steps per pass: at least n passes)
@@ -390,7 +441,6 @@ class Leg:
                 self.fill_ms_total, self.nfill = post_ms, post_n
                 self.roofline_sample = "post-timed, %d launches" % post_n
         self.event_bracket_ms = self.empty_bracket_ms()
-        return elapsed
 
     def empty_bracket_ms(self, n=50):
         """What two hipEventRecord calls measure with NOTHING between them, on the walk's stream (mean of n).  The fill's
@@ -648,6 +698,7 @@ def also_record(args, torch, dev, name, form, lut_output, steps, warmup, exp_see
               lookahead=lookahead, overrides=overrides)
     leg.setup(steps, warmup)
     elapsed = leg.timed(steps, collective=False)
+    leg.post_timed_sample()
     rf = leg.roofline()
     par, cpu = leg.parity(time_evals=1)
     rec = {"value": steps / elapsed, "unit": "steps/s (each one NLL evaluation the walk uses)" if lookahead else "evals/s",
@@ -792,6 +843,7 @@ def pdfz_record(args, torch, dev, name, exp_seed):
               keep_host="all", overrides={"prewarm": 1})
     leg.setup(100, 1)
     elapsed = leg.timed(100, collective=False)
+    leg.post_timed_sample()
     rf = leg.roofline()
     par, cpu = leg.parity(time_evals=1)
     n = int(leg.w.nsamples_total)
@@ -869,8 +921,15 @@ def parse_args(argv=None):
     """The command line (argv None: sys.argv) -- also what tools/ use to build the same legs as the bench."""
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
-    ap.add_argument("--steps", type=int, default=1000)
+    ap.add_argument("--steps", type=int, default=1000, help="timed steps (ms_per_step is their mean)")
     ap.add_argument("--warmup", type=int, default=100)
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also measure and check everything else: the roofline sample, parity "
+                         "against the CPU oracle and its timing, the ensemble leg, the gather of the intervals and the "
+                         "sub-records (--also).  Off: set up, warm up, time the steps, print the result line")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the timed steps computed (the chain's rows, its state and the last step's proposal "
+                         "with its NLL; rank 0's at N > 1) as DIR/<name>.npy, float32 / float64, 64 MB at most")
     ap.add_argument("--workload", default="c3", help="c3 (default, the metric's config), c1, c2, c5, bench_pdfz, bench_pdfz_group")
     ap.add_argument("--scale", type=float, default=1.0, help="shrink the sample counts (testing only)")
     ap.add_argument("--events", type=int, default=100000)
@@ -892,11 +951,11 @@ def parse_args(argv=None):
                     help="untimed steps before the --warmup steps (GPU clocks and graph replay settle)")
     ap.add_argument("--graph-steps", type=int, default=10, help="steps recorded per HIP graph (--form graph)")
     ap.add_argument("--launch", default="0,0", help="bin_threads,bin_blocks_per_cu (0 = default)")
-    ap.add_argument("--no-cpu-baseline", action="store_true", help="skip the oracle legs (timing AND parity)")
-    ap.add_argument("--cpu-evals", type=int, default=2)
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: skip the oracle legs (timing AND parity)")
+    ap.add_argument("--cpu-evals", type=int, default=2, help="--full: timed oracle evaluations (cpu_baseline)")
     ap.add_argument("--seed", type=int, default=3)
     ap.add_argument("--experiments", type=int, default=-1,
-                    help="fake experiments for the ensemble leg (fake data + MCMC + intervals), sharded k mod N; "
+                    help="--full: fake experiments for the ensemble leg (fake data + MCMC + intervals), sharded k mod N; "
                          "-1 = eight per rank, 0 = skip")
     ap.add_argument("--exp-steps", type=int, default=2000, help="MCMC steps per fake experiment in the ensemble leg")
     ap.add_argument("--exp-lockstep", type=int, default=2,
@@ -906,10 +965,10 @@ def parse_args(argv=None):
     ap.add_argument("--exp-concurrent", type=int, default=4,
                     help="fake experiments in flight per GPU in the ensemble leg (one stream each, shared MC tables)")
     ap.add_argument("--also", default="auto",
-                    help="sub-records measured after the headline: comma list of c3_float_stream, c3_lookahead, c3_lut_materialized, c2, c5, "
+                    help="--full: sub-records measured after the headline: comma list of c3_float_stream, c3_lookahead, c3_lut_materialized, c2, c5, "
                          "c2_float_columns, bench_pdfz, bench_pdfz_group, cpp_host, c3_dropin, c3_1e5_walk, c4_per_gpu, cpp_multi_gpu; auto = the single-GPU ones when the headline is the full-size C3 on one "
                          "GPU, cpp_multi_gpu (sxmc::ensemble_multi_gpu over the same cards) at N > 1; none = skip")
-    ap.add_argument("--also-steps", type=int, default=200, help="timed steps of each sub-record (C5: a quarter)")
+    ap.add_argument("--also-steps", type=int, default=200, help="--full: timed steps of each sub-record (C5: a quarter)")
     ap.add_argument("--partition", type=int, default=0, help="0 auto, 1 sliced, 2 interleaved")
     ap.add_argument("--no-sparse", action="store_true", help="fill HBM-resident histograms densely (global atomics)")
     ap.add_argument("--no-prebin", action="store_true", help="bin every observable in the kernel (no pre-binned column)")
@@ -958,6 +1017,10 @@ def main():
         raise SystemExit(dist.spawn_ranks(args.gpus, [sys.executable, os.path.abspath(__file__)] + sys.argv[1:]))
     if world != args.gpus:
         raise SystemExit("WORLD_SIZE=%d does not match --gpus %d" % (world, args.gpus))
+    if args.steps < 1:
+        raise SystemExit("--steps must be at least 1")
+    if not args.full and (args.also not in ("auto", "none") or args.experiments > 0):
+        raise SystemExit("--also and --experiments choose what --full measures after the timed steps: add --full")
 
     # the job's stdout carries ONE line, the JSON record: whatever libraries print on fd 1 meanwhile (gloo and RCCL
     # announce themselves there) goes to stderr
@@ -985,11 +1048,12 @@ def main():
     dist.init()
     info = capi.device_info(device_index)
     # what the collectives of this job really run on (backend, RCCL's own rank count, every rank's card)
-    collective, rccl = dist.collective_record(device_index, info)
+    collective, rccl = dist.collective_record(device_index, info) if args.full else (None, None)
 
     # ---- inputs: same MC tables on every rank (replica), own data events + chain seed per rank
     exp_seed = dist.experiment_seed(args.seed, rank)
-    want_cpu = (not args.no_cpu_baseline) and rank == 0 and not args.debug_mode   # parity: rank 0 at every N
+    # parity (--full): rank 0 at every N
+    want_cpu = args.full and not args.no_cpu_baseline and rank == 0 and not args.debug_mode
     big = args.workload.lower() == "c5" and args.scale >= 0.2
     leg = Leg(args, torch, dev, args.workload, args.form, args.lut_output, args.seed, exp_seed,
               keep_host=("ends" if big else "all") if want_cpu else "none",
@@ -1003,21 +1067,27 @@ def main():
     # ---- timed region: exactly K steps between barrier + synchronize on both sides
     elapsed = leg.timed(args.steps)
 
-    chain, accepted = leg.region_chain if leg.region_chain is not None else m.flush()
+    chain, accepted = leg.region_chain
+    dumped = None
+    if args.dump_outputs and rank == 0:       # (at N > 1: rank 0's chain)
+        dumped = dump_outputs(args.dump_outputs, step_outputs(leg, chain, accepted))
     if chain.shape[0] == 0:
         chain = np.zeros((1, w.nparameters + 1), np.float32)
-    mine_iv = chain_intervals(chain, w.nparameters)[None]
-    intervals = dist.gather_intervals(mine_iv, world, w.nparameters)
-    if rccl is not None:
-        # the same exchange on librccl through the C ABI (what sxmc::ensemble_multi_gpu calls); NaN-free payload
-        via_abi = dist.gather_intervals(mine_iv, world, w.nparameters, comm=rccl)
-        collective["intervals_through_c_abi_match_torch"] = bool(np.array_equal(via_abi, intervals))
+    intervals = None
+    if args.full:
+        leg.post_timed_sample()
+        mine_iv = chain_intervals(chain, w.nparameters)[None]
+        intervals = dist.gather_intervals(mine_iv, world, w.nparameters)
+        if rccl is not None:
+            # the same exchange on librccl through the C ABI (what sxmc::ensemble_multi_gpu calls); NaN-free payload
+            via_abi = dist.gather_intervals(mine_iv, world, w.nparameters, comm=rccl)
+            collective["intervals_through_c_abi_match_torch"] = bool(np.array_equal(via_abi, intervals))
 
     # ---- ensemble leg (sxmc.cpp:59-145): whole fake experiments, experiment k on rank k mod N, the MC
     # tables stay resident; one RCCL all_gather of the per-experiment intervals at the end.  Outside the
     # timed region of the headline metric; reported beside it.
     experiments = None
-    nexp = 8 * world if args.experiments < 0 else args.experiments
+    nexp = 0 if not args.full else 8 * world if args.experiments < 0 else args.experiments
     # (fake data sets are drawn from 1-3 D histograms only, as in the reference: pdfz.cpp:499-501)
     if nexp > 0 and not args.debug_mode and args.form != "pdfz" and w.nobs <= 3:
         from sxmc_amd import ensemble
@@ -1174,13 +1244,14 @@ def main():
         "dtype_filter": "f32-on-u16-codes" if "+codes" in m.group.LaunchInfo() else None,
         "data": "synthetic",
         "config": cfg,
-        "roofline": leg.roofline(world),
+        "roofline": leg.roofline(world) if args.full else None,
         "cpu_baseline": None,
         "parity": None,
         "collective": collective,
-        "intervals_gathered": [int(x) for x in intervals.shape],
+        "intervals_gathered": [int(x) for x in intervals.shape] if intervals is not None else None,
         "experiments": experiments,
         "also": None,
+        "outputs_dumped": dumped,
     }
 
     if want_cpu:
@@ -1194,7 +1265,7 @@ def main():
 
     # ---- sub-records: the other single-GPU configurations and the lookup-table-materialising step form,
     # measured in the same run so that their numbers carry the driver's clock too
-    also = args.also
+    also = args.also if args.full else "none"
     if also == "auto":
         full_c3 = args.workload.lower() == "c3" and args.scale == 1.0 and not args.debug_mode
         also = "none"

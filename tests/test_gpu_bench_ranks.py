@@ -17,7 +17,7 @@ def test_bare_two_rank_bench_over_gloo(tmp_path):
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_PORT")}
     env["SXMC_DIST_BACKEND"] = "gloo"
     env["SXMC_BENCH_FULL"] = str(tmp_path / "full.json")      # the full record (the stdout line is the compact one)
-    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "20", "--warmup", "5",
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--full", "--steps", "20", "--warmup", "5",
                         "--prewarm", "20", "--scale", "0.02", "--events", "5000", "--experiments", "4", "--exp-steps", "300",
                         "--also", "cpp_multi_gpu"], capture_output=True, text=True, env=env, timeout=900)
     assert r.returncode == 0, r.stderr[-4000:]
@@ -53,7 +53,7 @@ def test_six_rank_rehearsal_of_the_node_run(tmp_path):
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_PORT")}
     env["SXMC_DIST_BACKEND"] = "gloo"
     env["SXMC_BENCH_FULL"] = str(tmp_path / "full.json")
-    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "6", "--steps", "20", "--warmup", "5",
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "6", "--full", "--steps", "20", "--warmup", "5",
                         "--prewarm", "20", "--scale", "0.002", "--events", "3000", "--experiments", "256",
                         "--exp-steps", "50", "--also", "none"], capture_output=True, text=True, env=env, timeout=1100)
     assert r.returncode == 0, r.stderr[-4000:]

@@ -4,7 +4,7 @@
 out=${1:-gpurun_out/boxed_ab.log}
 run() {
   label=$1; lib=$2; shift; shift
-  SXMC_HIP_LIB=$lib python bench.py --also none --experiments 0 --steps 300 --no-cpu-baseline "$@" 2>/dev/null | python -c "
+  SXMC_HIP_LIB=$lib python bench.py --full --also none --experiments 0 --steps 300 --no-cpu-baseline "$@" 2>/dev/null | python -c "
 import json,sys
 r=json.loads(sys.stdin.readlines()[-1]); f=r['roofline']
 print('%-34s %8.1f evals/s  fill %.2f us  step %.2f us  %s' % ('$label', r['value'], 1e3*f['avg_launch_ms'], 1e3*r['ms_per_step'], r['config']['launch_plan'][-40:]))" >> $out
