@@ -238,6 +238,44 @@ int sxmc_hist_launch_info(sxmc_hist_t h, char* out, size_t n);
  * is sized analytically from the device; 0 keeps the default.  threads: a multiple of 64 up to 1024. */
 int sxmc_hist_set_launch_config(sxmc_hist_t h, int bin_threads, int bin_blocks_per_cu);
 
+/* ---------------------------------------------------------------- pdfz::EvalKernel ---------- */
+/* The kernel-density PDF (pdfz.h:578-625; the reference declares it and leaves it unimplemented): a Gaussian kernel
+ * on every Monte Carlo sample, after the systematics have moved it, truncated to the domain and renormalised there.
+ * Contract (sxmc_amd/include/sxmc/pdfz.h, class EvalKernel, says it in full):
+ *   h_d = bandwidth_scale_d * sigma_d * n^(-1/(D+4)) (Scott's rule), fixed at creation, sigma_d the sample standard
+ *   deviation (n - 1) of observable d over the n untransformed samples inside the domain;
+ *   norm = the in-domain count after the systematics (equal to EvalHist's on the same inputs);
+ *   pdf(x) = 1/norm sum_i w_i prod_d phi((x_d - s_id)/h_d)/h_d, w_i = 1 / prod_d [Phi((upper_d - s_id)/h_d) -
+ *   Phi((lower_d - s_id)/h_d)] for in-domain samples, 0 otherwise; points outside the domain NaN, points of another
+ *   data set 0, norm 0 NaN.  At most 4 observables.  Cost: O(points x samples) per evaluation.
+ * Validation as sxmc_hist_create (pdfz.cpp:64-82, MAX_NFIELDS), then the bandwidth scales (count, positive and
+ * finite), at most 4 observables, upper > lower, at least 2 in-domain samples and no zero spread. */
+typedef struct sxmc_kde* sxmc_kde_t;     /* one pdfz::EvalKernel */
+int sxmc_kde_create(const float* samples, size_t nsamples_floats, int samples_on_device,
+                    int nfields, int nobservables,
+                    const double* lower, size_t n_lower,
+                    const double* upper, size_t n_upper,
+                    const double* bandwidth_scale, size_t n_bandwidth_scale,
+                    unsigned dataset, sxmc_kde_t* out);
+int sxmc_kde_destroy(sxmc_kde_t k);
+/* As sxmc_hist_add_systematic.  SXMC_ERR_INVALID beyond 7 columns (observables + fields systematics read) or 64
+ * polynomial coefficients in all. */
+int sxmc_kde_add_systematic(sxmc_kde_t k, int type, int obs, int extra_field, int npars, const short* pars);
+/* As sxmc_hist_set_eval_points: rows of nobservables + 1 floats (last = dataset id), host memory. */
+int sxmc_kde_set_eval_points(sxmc_kde_t k, const float* points, size_t npoints_floats);
+int sxmc_kde_set_pdf_value_buffer(sxmc_kde_t k, float* d_output, int offset, int stride);
+int sxmc_kde_set_normalization_buffer(sxmc_kde_t k, unsigned* d_norm, int offset);
+int sxmc_kde_set_parameter_buffer(sxmc_kde_t k, const double* d_params, int offset, int stride);
+/* Launches on the evaluator's own stream and returns before completion; do_eval_pdf = 0 computes the norm only.
+ * eval_finished waits for the evaluator's stream. */
+int sxmc_kde_eval_async(sxmc_kde_t k, int do_eval_pdf);
+int sxmc_kde_eval_finished(sxmc_kde_t k);
+int sxmc_kde_get_stream(sxmc_kde_t k, sxmc_stream_t* s);
+/* h[0 .. nobservables): the bandwidths fixed at creation. */
+int sxmc_kde_bandwidths(sxmc_kde_t k, double* h, size_t n);
+int sxmc_kde_nsamples(sxmc_kde_t k, size_t* nsamples);
+int sxmc_kde_npoints(sxmc_kde_t k, size_t* npoints);
+
 /* ---------------------------------------------------------------- evaluator group ----------- */
 /* The "EvalAsync on all signals, then EvalFinished on all" of mcmc.cpp:264-271 and
  * bench_sxmc.cpp:193-200 as ONE batched launch sequence (zero, fill, evaluate) over all

@@ -105,6 +105,19 @@ SIGNATURES = {
     "sxmc_hist_set_optimize": [_vp, _i],
     "sxmc_hist_optimize": [_vp],
     "sxmc_hist_launch_info": [_vp, C.c_char_p, _sz],
+    "sxmc_kde_create": [_vp, _sz, _i, _i, _i, _vp, _sz, _vp, _sz, _vp, _sz, _u, _pvp],
+    "sxmc_kde_destroy": [_vp],
+    "sxmc_kde_add_systematic": [_vp, _i, _i, _i, _i, _vp],
+    "sxmc_kde_set_eval_points": [_vp, _vp, _sz],
+    "sxmc_kde_set_pdf_value_buffer": [_vp, _vp, _i, _i],
+    "sxmc_kde_set_normalization_buffer": [_vp, _vp, _i],
+    "sxmc_kde_set_parameter_buffer": [_vp, _vp, _i, _i],
+    "sxmc_kde_eval_async": [_vp, _i],
+    "sxmc_kde_eval_finished": [_vp],
+    "sxmc_kde_get_stream": [_vp, _pvp],
+    "sxmc_kde_bandwidths": [_vp, _vp, _sz],
+    "sxmc_kde_nsamples": [_vp, _psz],
+    "sxmc_kde_npoints": [_vp, _psz],
     "sxmc_group_create": [_vp, _i, _pvp],
     "sxmc_group_destroy": [_vp],
     "sxmc_group_set_launch_config": [_vp, _i, _i],

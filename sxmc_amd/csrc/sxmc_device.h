@@ -197,3 +197,24 @@ hipError_t sx_launch_transpose(const float* aos, float* cols, unsigned long long
 hipError_t sx_launch_untranspose_obs(const float* cols, float* out, unsigned long long nsamples,
                                      int nobs, unsigned long long col_pitch, float dataset,
                                      hipStream_t s);
+
+// pdfz::EvalKernel (kde_kernels.hip, sxmc_kde.cpp)
+#define SXMC_KDE_MAX_DIM 4   // observables of a kernel-density evaluator
+#define SXMC_KDE_TILE 256    // samples per f32 partial sum of the pair kernel; sample rows are padded to a multiple
+// The prepass's geometry: rows = [npad][nobs + 1] floats (scaled coordinates, weight), norm = the in-domain counter.
+struct SxKdeArgs {
+  float* rows;
+  unsigned long long npad;
+  unsigned* norm;
+  double lower[SXMC_KDE_MAX_DIM];
+  double upper[SXMC_KDE_MAX_DIM];
+  double cscale[SXMC_KDE_MAX_DIM];       // sqrt(log2(e) / 2) / h
+  double inv_h_sqrt2[SXMC_KDE_MAX_DIM];  // 1 / (h sqrt 2)
+};
+hipError_t sx_kde_prepass(const SxSignalDesc& d, const SxKdeArgs& a, hipStream_t s);
+// pts: [D][pitch] scaled point coordinates, pitch a multiple of 256; part: [nsplit][pitch]
+hipError_t sx_kde_pairs(int D, const float* pts, unsigned long long pitch, const float* rows, unsigned tiles_per_split,
+                        unsigned ntiles, int nsplit, double* part, hipStream_t s);
+hipError_t sx_kde_combine(const double* part, unsigned long long pitch, int nsplit, unsigned long long npoints,
+                          const int* codes, const unsigned* norm, double prefactor, float* out, long stride,
+                          hipStream_t s);

@@ -9,6 +9,7 @@
 //   sxmc_group.cpp        the group entry points: configuration, autotune, evaluation, the step and its step-end forms
 //   sxmc_multigroup.cpp   lockstep chains and the look-ahead pass
 //   sxmc_nll_api.cpp      the NLL launch points with the reference's argument lists; the measurement build's test hooks
+//   sxmc_kde.cpp          the kernel-density evaluator (sxmc_kde_*) behind pdfz::EvalKernel
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -421,6 +422,7 @@ namespace sxhost {
 using sxplan::ordered_queue_bytes;
 constexpr unsigned kMinQueueLog = 9;     // the smallest queues of ambiguous rows a fill over codes works with: 2^9 entries
 void member_slots(const sxmc_hist* h, std::vector<int>& slot_col);
+int fill_desc(const sxmc_hist* h, SxSignalDesc& d);   // a member's descriptor: table, slots, systematics, bindings
 void free_sparse(sxmc_hist* h);
 int build_sparse(sxmc_hist* h, const std::vector<int>& rb);
 unsigned ordered_queue_log(size_t room, int cap = 0);

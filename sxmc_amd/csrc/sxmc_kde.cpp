@@ -1,0 +1,330 @@
+// sxmc_kde.cpp -- the evaluator behind pdfz::EvalKernel (sxmc_kde_*): the kernel-density PDF.  The contract is written
+// out in include/sxmc_hip.h and sxmc_amd/include/sxmc/pdfz.h; the kernels are in kde_kernels.hip.
+//
+// The sample table, the constructor's validation and the systematics are an EvalHist's: the evaluator holds an
+// internal histogram evaluator with one bin per observable that is never evaluated itself -- it uploads the table
+// column-major, checks and packs the systematics, and gives the fill's descriptor (fill_desc), which the prepass reads
+// with the fill's own arithmetic.  So the norm is the histogram's, bit for bit.
+#include "sxmc_host.h"
+
+using namespace sxhost;
+
+struct sxmc_kde {
+  sxmc_hist* h = nullptr;          // table, geometry, systematics and stream (one bin per observable)
+  int D = 0;
+  size_t nsamples = 0;
+  size_t npad = 0;                 // sample rows, a multiple of SXMC_KDE_TILE
+  double bw[SXMC_KDE_MAX_DIM] = {0};
+  double prefactor = 0;            // 1 / ((2 pi)^(D/2) prod h)
+  float* d_rows = nullptr;         // [npad][D + 1]: scaled coordinates, weight
+  // evaluation points
+  bool has_points = false;
+  size_t npoints = 0, pitch = 0, cap_pitch = 0;
+  float* d_pts = nullptr;          // [D][pitch] scaled coordinates (0 where the point's code is not 0)
+  int* d_codes = nullptr;          // [pitch] EvalHist's point codes: 0 in domain, -1 outside, -2 another data set
+  int nsplit = 1;
+  unsigned tiles_per_split = 1;
+  double* d_part = nullptr;        // [nsplit][pitch] partial sums
+  size_t cap_part = 0;
+  // bindings
+  float* pdf = nullptr;
+  int pdf_off = 0, pdf_stride = 1;
+  unsigned* norm = nullptr;
+  int norm_off = 0;
+  const double* params = nullptr;
+  int par_off = 0, par_stride = 1;
+  int cus = 256;
+};
+
+namespace {
+
+constexpr double kLog2eHalfSqrt = 0.84932180028801907;   // sqrt(log2(e) / 2): exp(-z^2 / 2) = exp2(-(z * this)^2)
+
+// How the pair sum is split over workgroups: s splits of the sample tiles, each a workgroup per 256 points.  Of the
+// splits that keep every workgroup's share whole, the one with the fewest rounds of `slots` resident workgroups times
+// tiles per workgroup (the smallest on a tie).
+void choose_split(size_t pitch, size_t ntiles, int cus, int& nsplit, unsigned& tiles_per_split) {
+  const unsigned long long pblocks = pitch / 256, slots = (unsigned long long)cus * 8;
+  unsigned long long best = ~0ull;
+  nsplit = 1;
+  tiles_per_split = (unsigned)ntiles;
+  const unsigned long long smax = std::min<unsigned long long>(ntiles, std::max<unsigned long long>(1, 64 * slots / pblocks));
+  for (unsigned long long s = 1; s <= smax; s++) {
+    const unsigned long long tps = (ntiles + s - 1) / s;
+    const unsigned long long used = (ntiles + tps - 1) / tps;
+    const unsigned long long cost = (pblocks * used + slots - 1) / slots * tps;
+    if (cost < best) {
+      best = cost;
+      nsplit = (int)used;
+      tiles_per_split = (unsigned)tps;
+    }
+  }
+}
+
+}  // namespace
+
+extern "C" {
+
+int sxmc_kde_create(const float* samples, size_t nsamples_floats, int samples_on_device, int nfields, int nobservables,
+                    const double* lower, size_t n_lower, const double* upper, size_t n_upper,
+                    const double* bandwidth_scale, size_t n_bandwidth_scale, unsigned dataset, sxmc_kde_t* out) {
+  SX_REQUIRE(out, "null argument");
+  *out = nullptr;
+  // Eval::Eval validation, pdfz.cpp:64-82 (same order, same messages, as sxmc_hist_create)
+  SX_REQUIRE(nfields > 0 && nsamples_floats % (size_t)nfields == 0,
+             "Length of samples array is not divisible by number of fields.");
+  SX_REQUIRE(nobservables != 0, "Number of observables in PDF is zero.");
+  SX_REQUIRE(nobservables > 0 && nobservables <= nfields,
+             "Number of observables cannot be greater than number of fields.");
+  SX_REQUIRE((int)n_upper == nobservables, "Number of upper bounds must be same as number of observables.");
+  SX_REQUIRE((int)n_lower == nobservables, "Number of lower bounds must be same as number of observables.");
+  SX_REQUIRE((int)n_bandwidth_scale == nobservables, "Number of bandwidth scales must be same as number of observables.");
+  SX_REQUIRE(nfields <= SXMC_MAX_NFIELDS,
+             "Exceeded maximum number of fields per sample. Edit MAX_NFIELDS in pdfz.cpp to fix this!");
+  SX_REQUIRE(nobservables <= SXMC_KDE_MAX_DIM, "EvalKernel supports at most 4 observables.");
+  SX_REQUIRE(lower && upper && bandwidth_scale, "null argument");
+  for (int d = 0; d < nobservables; d++) {
+    SX_REQUIRE(std::isfinite(bandwidth_scale[d]) && bandwidth_scale[d] > 0,
+               "Bandwidth scales must be positive and finite.");
+  }
+  for (int d = 0; d < nobservables; d++) {
+    SX_REQUIRE(upper[d] > lower[d], "Upper bound must be greater than lower bound.");
+  }
+  SX_REQUIRE(nsamples_floats == 0 || samples, "null samples");
+
+  // Scott's rule over the untransformed samples inside the domain, in f64 on the host (before anything is allocated on
+  // the device: a table that cannot set its bandwidths is refused without a GPU)
+  std::vector<float> copy;
+  const float* rows = samples;
+  if (samples_on_device && nsamples_floats) {
+    copy.resize(nsamples_floats);
+    SX_HIP(hipMemcpy(copy.data(), samples, sizeof(float) * nsamples_floats, hipMemcpyDeviceToHost));
+    rows = copy.data();
+  }
+  const int D = nobservables;
+  const size_t nrows = nsamples_floats / (size_t)nfields;
+  std::vector<size_t> inside;
+  for (size_t i = 0; i < nrows; i++) {
+    bool in = true;
+    for (int d = 0; d < D; d++) {
+      const double x = rows[i * (size_t)nfields + (size_t)d];
+      in = in && x >= lower[d] && x < upper[d];
+    }
+    if (in) inside.push_back(i);
+  }
+  const size_t n = inside.size();
+  SX_REQUIRE(n >= 2, "EvalKernel needs at least 2 samples inside the domain to set its bandwidths.");
+  double bw[SXMC_KDE_MAX_DIM] = {0}, prod_h = 1.0;
+  for (int d = 0; d < D; d++) {
+    double mean = 0.0, ss = 0.0;
+    for (size_t i : inside) mean += rows[i * (size_t)nfields + (size_t)d];
+    mean /= (double)n;
+    for (size_t i : inside) {
+      const double dx = rows[i * (size_t)nfields + (size_t)d] - mean;
+      ss += dx * dx;
+    }
+    const double sigma = std::sqrt(ss / (double)(n - 1));
+    SX_REQUIRE(sigma > 0, "EvalKernel bandwidth is zero: observable " + std::to_string(d) +
+                              " has no spread inside the domain.");
+    bw[d] = bandwidth_scale[d] * sigma * std::pow((double)n, -1.0 / (D + 4));
+    prod_h *= bw[d];
+  }
+
+  const std::vector<int> nbins((size_t)nobservables, 1);
+  sxmc_hist_t h = nullptr;
+  int rc = sxmc_hist_create(samples, nsamples_floats, samples_on_device, nfields, nobservables, lower, n_lower, upper,
+                            n_upper, nbins.data(), nbins.size(), dataset, &h);
+  if (rc) return rc;
+  std::unique_ptr<sxmc_kde> k(new sxmc_kde);
+  k->h = h;
+  k->D = D;
+  k->nsamples = h->nsamples;
+  for (int d = 0; d < D; d++) k->bw[d] = bw[d];
+  k->prefactor = 1.0 / (std::pow(2.0 * M_PI, 0.5 * D) * prod_h);
+  auto failed = [&](int code) {
+    if (k->d_rows) (void)hipFree(k->d_rows);
+    sxmc_hist_destroy(k->h);
+    return code;
+  };
+
+  k->npad = std::max<size_t>(SXMC_KDE_TILE, (k->nsamples + SXMC_KDE_TILE - 1) / SXMC_KDE_TILE * SXMC_KDE_TILE);
+  const size_t bytes = sizeof(float) * k->npad * (size_t)(D + 1);
+  hipError_t e = hipMalloc((void**)&k->d_rows, bytes);
+  if (e == hipSuccess) e = hipMemset(k->d_rows, 0, bytes);
+  if (e != hipSuccess) return failed(fail(SXMC_ERR_HIP, std::string("hipMalloc sample rows: ") + hipGetErrorString(e)));
+  DeviceProps props;
+  if (get_props(props) == SXMC_OK && props.cus > 0) k->cus = props.cus;
+  *out = k.release();
+  return SXMC_OK;
+}
+
+int sxmc_kde_destroy(sxmc_kde_t k) {
+  if (!k) return SXMC_OK;
+  if (k->h && k->h->stream) (void)hipStreamSynchronize(k->h->stream);
+  if (k->d_rows) (void)hipFree(k->d_rows);
+  if (k->d_pts) (void)hipFree(k->d_pts);
+  if (k->d_codes) (void)hipFree(k->d_codes);
+  if (k->d_part) (void)hipFree(k->d_part);
+  sxmc_hist_destroy(k->h);
+  delete k;
+  return SXMC_OK;
+}
+
+int sxmc_kde_add_systematic(sxmc_kde_t k, int type, int obs, int extra_field, int npars, const short* pars) {
+  SX_REQUIRE(k, "null evaluator");
+  int rc = sxmc_hist_add_systematic(k->h, type, obs, extra_field, npars, pars);
+  if (rc) return rc;
+  // the prepass runs the fill's run-time decoded program: up to 7 columns, one coefficient per lane
+  std::vector<int> slots;
+  member_slots(k->h, slots);
+  int ncoef = 0;
+  for (const HostSyst& s : k->h->systs) ncoef += (int)s.pars.size();
+  if (slots.size() > 7 || ncoef > 64) {
+    k->h->systs.pop_back();
+    return fail(SXMC_ERR_INVALID, "EvalKernel: the systematics read more than 7 fields or have more than 64 "
+                                  "coefficients in all");
+  }
+  return SXMC_OK;
+}
+
+int sxmc_kde_set_eval_points(sxmc_kde_t k, const float* points, size_t npoints_floats) {
+  SX_REQUIRE(k, "null evaluator");
+  const int D = k->D;
+  const size_t row = (size_t)D + 1;
+  SX_REQUIRE(npoints_floats % row == 0,
+             "Number of entries in evaluation points array not divisible by number of observables.");
+  SX_REQUIRE(npoints_floats == 0 || points, "null points");
+  const size_t n = npoints_floats / row;
+  SX_REQUIRE(n <= (size_t)INT_MAX, "too many evaluation points");
+  // EvalHist's point codes (pdfz.cpp:264-301) with one bin of zero scale per observable: every point inside the
+  // domain of this data set lands in bin 0
+  const std::vector<double> zero((size_t)D, 0.0);
+  const std::vector<int> unit((size_t)D, 1);
+  std::vector<int> codes;
+  sxplan::eval_point_bins(points, n, D, k->h->lower.data(), k->h->upper.data(), zero.data(), unit.data(), 1,
+                          k->h->dataset, codes);
+  const size_t pitch = std::max<size_t>(256, (n + 255) / 256 * 256);
+  std::vector<float> pts(pitch * (size_t)D, 0.0f);
+  codes.resize(pitch, -1);
+  for (size_t i = 0; i < n; i++) {
+    if (codes[i] != 0) continue;
+    for (int d = 0; d < D; d++) {
+      const double c = ((double)points[i * row + (size_t)d] - k->h->lower[(size_t)d]) * (kLog2eHalfSqrt / k->bw[d]);
+      pts[(size_t)d * pitch + i] = (float)c;
+    }
+  }
+  int nsplit = 1;
+  unsigned tps = 1;
+  choose_split(pitch, k->npad / SXMC_KDE_TILE, k->cus, nsplit, tps);
+  SX_HIP(hipStreamSynchronize(k->h->stream));   // (an evaluation in flight reads the arrays replaced here)
+  if (pitch > k->cap_pitch) {
+    if (k->d_pts) SX_HIP(hipFree(k->d_pts));
+    if (k->d_codes) SX_HIP(hipFree(k->d_codes));
+    k->d_pts = nullptr;
+    k->d_codes = nullptr;
+    k->cap_pitch = 0;
+    SX_HIP(hipMalloc((void**)&k->d_pts, sizeof(float) * pitch * (size_t)D));
+    SX_HIP(hipMalloc((void**)&k->d_codes, sizeof(int) * pitch));
+    k->cap_pitch = pitch;
+  }
+  const size_t part = (size_t)nsplit * pitch;
+  if (part > k->cap_part) {
+    if (k->d_part) SX_HIP(hipFree(k->d_part));
+    k->d_part = nullptr;
+    k->cap_part = 0;
+    SX_HIP(hipMalloc((void**)&k->d_part, sizeof(double) * part));
+    k->cap_part = part;
+  }
+  SX_HIP(hipMemcpy(k->d_pts, pts.data(), sizeof(float) * pts.size(), hipMemcpyHostToDevice));
+  SX_HIP(hipMemcpy(k->d_codes, codes.data(), sizeof(int) * pitch, hipMemcpyHostToDevice));
+  k->npoints = n;
+  k->pitch = pitch;
+  k->nsplit = nsplit;
+  k->tiles_per_split = tps;
+  k->has_points = true;
+  return SXMC_OK;
+}
+
+int sxmc_kde_set_pdf_value_buffer(sxmc_kde_t k, float* d_output, int offset, int stride) {
+  SX_REQUIRE(k, "null evaluator");
+  k->pdf = d_output;
+  k->pdf_off = offset;
+  k->pdf_stride = stride;
+  return SXMC_OK;
+}
+int sxmc_kde_set_normalization_buffer(sxmc_kde_t k, unsigned* d_norm, int offset) {
+  SX_REQUIRE(k, "null evaluator");
+  k->norm = d_norm;
+  k->norm_off = offset;
+  return SXMC_OK;
+}
+int sxmc_kde_set_parameter_buffer(sxmc_kde_t k, const double* d_params, int offset, int stride) {
+  SX_REQUIRE(k, "null evaluator");
+  k->params = d_params;
+  k->par_off = offset;
+  k->par_stride = stride;
+  return SXMC_OK;
+}
+
+int sxmc_kde_eval_async(sxmc_kde_t k, int do_eval_pdf) {
+  SX_REQUIRE(k, "null evaluator");
+  if (!k->norm) return fail(SXMC_ERR_STATE, "evaluation before SetNormalizationBuffer");
+  if (!k->h->systs.empty() && !k->params) return fail(SXMC_ERR_STATE, "evaluation before SetParameterBuffer");
+  const bool lookup = do_eval_pdf && k->has_points && k->npoints > 0;
+  if (lookup && !k->pdf) return fail(SXMC_ERR_STATE, "evaluation before SetPDFValueBuffer");
+  const hipStream_t s = k->h->stream;
+  SxSignalDesc d;
+  fill_desc(k->h, d);
+  d.params = k->params ? k->params + k->par_off : nullptr;
+  d.param_stride = k->par_stride;
+  SxKdeArgs a;
+  std::memset(&a, 0, sizeof a);
+  a.rows = k->d_rows;
+  a.npad = k->npad;
+  a.norm = k->norm + k->norm_off;
+  for (int i = 0; i < k->D; i++) {
+    a.lower[i] = k->h->lower[(size_t)i];
+    a.upper[i] = k->h->upper[(size_t)i];
+    a.cscale[i] = kLog2eHalfSqrt / k->bw[i];
+    a.inv_h_sqrt2[i] = 1.0 / (k->bw[i] * M_SQRT2);
+  }
+  SX_HIP(hipMemsetAsync(a.norm, 0, sizeof(unsigned), s));
+  SX_HIP(sx_kde_prepass(d, a, s));
+  if (lookup) {
+    SX_HIP(sx_kde_pairs(k->D, k->d_pts, k->pitch, k->d_rows, k->tiles_per_split,
+                        (unsigned)(k->npad / SXMC_KDE_TILE), k->nsplit, k->d_part, s));
+    SX_HIP(sx_kde_combine(k->d_part, k->pitch, k->nsplit, k->npoints, k->d_codes, a.norm, k->prefactor,
+                          k->pdf + k->pdf_off, (long)k->pdf_stride, s));
+  }
+  return SXMC_OK;
+}
+
+int sxmc_kde_eval_finished(sxmc_kde_t k) {
+  SX_REQUIRE(k, "null evaluator");
+  SX_HIP(hipStreamSynchronize(k->h->stream));
+  return SXMC_OK;
+}
+
+int sxmc_kde_get_stream(sxmc_kde_t k, sxmc_stream_t* s) {
+  SX_REQUIRE(k && s, "null argument");
+  *s = k->h->stream;
+  return SXMC_OK;
+}
+int sxmc_kde_bandwidths(sxmc_kde_t k, double* h, size_t n) {
+  SX_REQUIRE(k && h, "null argument");
+  SX_REQUIRE(n == (size_t)k->D, "bandwidth buffer size mismatch");
+  for (int d = 0; d < k->D; d++) h[d] = k->bw[d];
+  return SXMC_OK;
+}
+int sxmc_kde_nsamples(sxmc_kde_t k, size_t* v) {
+  SX_REQUIRE(k && v, "null argument");
+  *v = k->nsamples;
+  return SXMC_OK;
+}
+int sxmc_kde_npoints(sxmc_kde_t k, size_t* v) {
+  SX_REQUIRE(k && v, "null argument");
+  *v = k->has_points ? k->npoints : 0;
+  return SXMC_OK;
+}
+
+}  // extern "C"

@@ -96,11 +96,19 @@ inline void build_pdfz(Signal& sig, const std::vector<float>& samples, int nfiel
   }
 }
 
+/** The signal's evaluator as the histogram evaluator it must be for `what`; a signal with another kind of evaluator (a
+ *  pdfz::EvalKernel) throws a pdfz::Error that names it instead of dereferencing a failed cast. */
+inline pdfz::EvalHist& histogram_of(const Signal& s, const std::string& what) {
+  pdfz::EvalHist* h = dynamic_cast<pdfz::EvalHist*>(s.histogram);
+  if (!h) throw pdfz::Error("signal '" + s.name + "': cannot " + what + ": its evaluator is not a pdfz::EvalHist");
+  return *h;
+}
+
 /** A copy of `base` whose evaluator shares base's sample table (pdfz::EvalHist::SharedSamples): what each
  *  additional concurrent chain on a GPU works with.  The caller deletes .histogram, as for build_pdfz. */
 inline Signal share_pdfz(const Signal& base) {
   Signal s = base;
-  s.histogram = new pdfz::EvalHist(*dynamic_cast<pdfz::EvalHist*>(base.histogram), pdfz::EvalHist::SharedSamples{});
+  s.histogram = new pdfz::EvalHist(histogram_of(base, "share its sample table"), pdfz::EvalHist::SharedSamples{});
   return s;
 }
 

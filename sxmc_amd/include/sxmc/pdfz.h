@@ -1,7 +1,7 @@
 // pdfz.h -- the reference's pdfz interface (src/pdfz.h:87-627) on MI355X.
 //
 // Same names, constructor arguments, defaults, virtuals and throw behaviour as pdfz::Eval /
-// pdfz::EvalHist, so that callers written against the reference (mcmc.cpp:233-242, 264-271,
+// pdfz::EvalHist / pdfz::EvalKernel, so that callers written against the reference (mcmc.cpp:233-242, 264-271,
 // signal.cpp:131-146, 192-196, bench_sxmc.cpp:58-96) compile against this header.  Everything is a
 // thin layer over the C ABI of libsxmc_hip.so (include/sxmc_hip.h); the arithmetic runs in
 // hand-written gfx950 kernels.  Differences, all forced by what is absent here:
@@ -271,6 +271,104 @@ class EvalHist : public Eval {
 
  protected:
   sxmc_hist_t handle = nullptr;
+};
+
+/** pdfz::EvalKernel (pdfz.h:578-625; declared by the reference, implemented here): the kernel-density PDF, the unbinned
+ *  alternative to EvalHist for signals whose Monte Carlo sample is too small to fill a fine histogram.
+ *
+ *  Constructor: (samples, nfields, nobservables, lower, upper, bandwidth_scale) as the reference declares it, plus
+ *  the optional `dataset` EvalHist has.  Validation needs no GPU: Eval::Eval's checks with the reference's messages in
+ *  its order (pdfz.cpp:64-82), then "Number of bandwidth scales must be same as number of observables.", the
+ *  MAX_NFIELDS check, at most 4 observables (this class's limit), every scale positive and finite, upper > lower.
+ *  Bandwidths (Scott's rule), fixed at construction and computed on the host in f64:
+ *    h_d = bandwidth_scale_d * sigma_d * n^(-1/(D+4)), sigma_d the sample standard deviation (n - 1) of observable d
+ *    over the n untransformed samples whose observables all lie in [lower, upper); n < 2 or a zero sigma throws.
+ *  Per evaluation:
+ *    - every attached systematic moves every sample, with the f64 arithmetic of EvalHist's fill;
+ *    - a sample is in the domain when lower <= x < upper for every observable (NaN is outside); norm = their count,
+ *      written to the normalization buffer: EvalHist's norm on the same inputs, bit for bit;
+ *    - an in-domain sample s_i carries w_i = 1 / prod_d [Phi((upper_d - s_id)/h_d) - Phi((lower_d - s_id)/h_d)], the
+ *      kernel truncated to the domain and renormalised; the others weigh 0;
+ *    - pdf(x) = (1/norm) sum_i w_i prod_d phi((x_d - s_id)/h_d)/h_d, whose integral over the domain is 1;
+ *    - points as EvalHist::SetEvalPoints: any observable outside the domain NaN (whatever the data set), inside and
+ *      of another data set 0, norm == 0 NaN; values go as float to pdf_out[offset + stride * i];
+ *    - EvalAsync(false) computes the norm only.  EvalAsync returns before completion, EvalFinished waits.
+ *  Deterministic: the same inputs give the same bits (no floating-point atomics).  Cost O(points x samples). */
+class EvalKernel : public Eval {
+ public:
+  EvalKernel(const std::vector<float>& samples, int nfields, int nobservables, const std::vector<double>& lower,
+             const std::vector<double>& upper, const std::vector<double>& bandwidth_scale, unsigned dataset = 0)
+      : Eval(samples, nfields, nobservables, lower, upper, dataset) {
+    throw_on(sxmc_kde_create(samples.data(), samples.size(), 0, nfields, nobservables, lower.data(), lower.size(),
+                             upper.data(), upper.size(), bandwidth_scale.data(), bandwidth_scale.size(), dataset,
+                             &handle));
+  }
+  EvalKernel(const EvalKernel&) = delete;
+  EvalKernel& operator=(const EvalKernel&) = delete;
+  virtual ~EvalKernel() { sxmc_kde_destroy(handle); }
+
+  virtual void SetEvalPoints(const std::vector<float>& points) {
+    throw_on(sxmc_kde_set_eval_points(handle, points.data(), points.size()));
+  }
+
+  virtual void AddSystematic(const Systematic& syst) {
+    int obs = 0, extra = 0;
+    Array<short>* pars = nullptr;
+    if (syst.type == Systematic::SHIFT) {
+      const ShiftSystematic& s = dynamic_cast<const ShiftSystematic&>(syst);
+      obs = s.obs;
+      pars = s.pars;
+    } else if (syst.type == Systematic::SCALE) {
+      const ScaleSystematic& s = dynamic_cast<const ScaleSystematic&>(syst);
+      obs = s.obs;
+      pars = s.pars;
+    } else if (syst.type == Systematic::CTSCALE) {
+      const CosThetaScaleSystematic& s = dynamic_cast<const CosThetaScaleSystematic&>(syst);
+      obs = s.obs;
+      pars = s.pars;
+    } else if (syst.type == Systematic::RESOLUTION_SCALE) {
+      const ResolutionScaleSystematic& s = dynamic_cast<const ResolutionScaleSystematic&>(syst);
+      obs = s.obs;
+      extra = s.true_obs;
+      pars = s.pars;
+    } else {
+      throw Error("Unknown systematic type");
+    }
+    throw_on(sxmc_kde_add_systematic(handle, (int)syst.type, obs, extra, (int)pars->size(), pars->readOnlyHostPtr()));
+  }
+
+  /** Bind the caller's buffers (device side) and launch prepass (+ pair sum + combine) on this evaluator's stream;
+   *  returns before completion. */
+  virtual void EvalAsync(bool do_eval_pdf = true) {
+    Bind();
+    throw_on(sxmc_kde_eval_async(handle, do_eval_pdf ? 1 : 0));
+  }
+  virtual void EvalFinished() { throw_on(sxmc_kde_eval_finished(handle)); }
+
+  void ForgetBuffers() override {
+    Eval::ForgetBuffers();
+    throw_on(sxmc_kde_set_pdf_value_buffer(handle, nullptr, 0, 1));
+    throw_on(sxmc_kde_set_normalization_buffer(handle, nullptr, 0));
+    throw_on(sxmc_kde_set_parameter_buffer(handle, nullptr, 0, 1));
+  }
+
+  void Bind() {
+    if (pdf_buffer) throw_on(sxmc_kde_set_pdf_value_buffer(handle, pdf_buffer->writeOnlyPtr(), pdf_offset, pdf_stride));
+    if (norm_buffer) throw_on(sxmc_kde_set_normalization_buffer(handle, norm_buffer->writeOnlyPtr(), norm_offset));
+    if (param_buffer) throw_on(sxmc_kde_set_parameter_buffer(handle, param_buffer->readOnlyPtr(), param_offset, param_stride));
+  }
+
+  /** The bandwidths h_d fixed at construction (Scott's rule). */
+  std::vector<double> Bandwidths() const {
+    std::vector<double> h((size_t)nobservables);
+    throw_on(sxmc_kde_bandwidths(handle, h.data(), h.size()));
+    return h;
+  }
+
+  sxmc_kde_t Handle() const { return handle; }
+
+ protected:
+  sxmc_kde_t handle = nullptr;
 };
 
 }  // namespace pdfz

@@ -209,3 +209,92 @@ class EvalHist:
             self.close()
         except Exception:
             pass
+
+
+class EvalKernel:
+    """pdfz::EvalKernel (pdfz.h:578-625): the kernel-density PDF, contract in sxmc_amd/include/sxmc/pdfz.h.
+    Same method names as EvalHist, plus Bandwidths(); at most 4 observables; O(points x samples) per evaluation."""
+
+    def __init__(self, samples, nfields, nobservables, lower, upper, bandwidth_scale, dataset=0):
+        lib = capi.load()
+        self._h = None
+        on_device = hasattr(samples, "data_ptr")
+        if on_device:
+            nfloats = int(samples.numel())
+        else:
+            samples = np.ascontiguousarray(samples, dtype=np.float32).reshape(-1)
+            nfloats = samples.size
+        lower = np.ascontiguousarray(lower, dtype=np.float64)
+        upper = np.ascontiguousarray(upper, dtype=np.float64)
+        scale = np.ascontiguousarray(bandwidth_scale, dtype=np.float64).reshape(-1)
+        h = C.c_void_p(0)
+        _raise(lib.sxmc_kde_create(capi.ptr(samples), nfloats, int(on_device), int(nfields), int(nobservables),
+                                   capi.ptr(lower), lower.size, capi.ptr(upper), upper.size, capi.ptr(scale),
+                                   scale.size, int(dataset), C.byref(h)))
+        self._h = h
+        self.nfields, self.nobservables, self.dataset = int(nfields), int(nobservables), int(dataset)
+        self._keep = {}
+
+    def SetEvalPoints(self, points):
+        points = np.ascontiguousarray(points, dtype=np.float32).reshape(-1)
+        _raise(capi.load().sxmc_kde_set_eval_points(self._h, capi.ptr(points), points.size))
+
+    def SetPDFValueBuffer(self, output, offset=0, stride=1):
+        self._keep["pdf"] = output
+        _raise(capi.load().sxmc_kde_set_pdf_value_buffer(self._h, capi.ptr(output), int(offset), int(stride)))
+
+    def SetNormalizationBuffer(self, norm, offset=0):
+        self._keep["norm"] = norm
+        _raise(capi.load().sxmc_kde_set_normalization_buffer(self._h, capi.ptr(norm), int(offset)))
+
+    def SetParameterBuffer(self, params, offset=0, stride=1):
+        self._keep["params"] = params
+        _raise(capi.load().sxmc_kde_set_parameter_buffer(self._h, capi.ptr(params), int(offset), int(stride)))
+
+    def AddSystematic(self, syst):
+        pars = np.asarray(syst.pars, dtype=np.int16)
+        extra = getattr(syst, "true_obs", 0)
+        _raise(capi.load().sxmc_kde_add_systematic(self._h, int(syst.type), int(syst.obs), int(extra),
+                                                   pars.size, capi.ptr(pars)))
+
+    def EvalAsync(self, do_eval_pdf=True):
+        _raise(capi.load().sxmc_kde_eval_async(self._h, int(bool(do_eval_pdf))))
+
+    def EvalFinished(self):
+        _raise(capi.load().sxmc_kde_eval_finished(self._h))
+
+    def Optimize(self):
+        pass
+
+    def Bandwidths(self):
+        """h_d = bandwidth_scale_d * sigma_d * n^(-1/(D+4)) (Scott's rule), fixed at construction."""
+        out = np.empty(self.nobservables, dtype=np.float64)
+        _raise(capi.load().sxmc_kde_bandwidths(self._h, capi.ptr(out), out.size))
+        return out
+
+    @property
+    def nsamples(self):
+        v = C.c_size_t(0)
+        _raise(capi.load().sxmc_kde_nsamples(self._h, C.byref(v)))
+        return v.value
+
+    @property
+    def npoints(self):
+        v = C.c_size_t(0)
+        _raise(capi.load().sxmc_kde_npoints(self._h, C.byref(v)))
+        return v.value
+
+    @property
+    def handle(self):
+        return self._h
+
+    def close(self):
+        if getattr(self, "_h", None):
+            capi.load().sxmc_kde_destroy(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass

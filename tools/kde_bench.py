@@ -1,0 +1,99 @@
+"""Measures pdfz::EvalKernel, the kernel-density PDF, and prints one JSON line.
+
+Default shape: N = 2^17 samples, D = 2 observables, nfields = 3 (the third a true value), shift + scale + resolution
+systematics, E = 10^5 evaluation points.  ms_per_eval: host clock around EvalAsync + EvalFinished (which waits for
+the device), warmed up, over a window of at least --seconds.  pairs_per_s = E x N / that time.
+
+The bound is the pair kernel's vector issue, read from its inner loop (kde_kernels.hip, --save-temps ISA): per sample
+and wave, D v_sub_f32, one v_mul_f32, D - 1 v_fmac_f32 for the distance, one v_exp_f32 and one v_fmac_f32 to
+accumulate; the sample row comes through scalar loads as SGPR operands.  At the issue costs of one wave's stream
+(4 cycles, 8 for v_exp_f32) that is 4 (2D + 1) + 8 cycles per 64 pairs per SIMD (28 at D = 2), over 4 SIMDs per CU at
+the clock the device reports.  cpu_numpy_pairs_per_s: the same sum in numpy f64 on a subset of the points.
+Usage: python tools/kde_bench.py [--samples N] [--points E] [--seconds S] [--cpu-points K]"""
+import argparse
+import json
+import math
+import os
+import sys
+import time
+
+import numpy as np
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+
+from sxmc_amd import capi, pdfz  # noqa: E402
+from sxmc_amd.capi import DeviceArray  # noqa: E402
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--samples", type=int, default=1 << 17)
+    ap.add_argument("--points", type=int, default=100000)
+    ap.add_argument("--seconds", type=float, default=1.0)
+    ap.add_argument("--cpu-points", type=int, default=200)
+    a = ap.parse_args()
+    if capi.device_count() < 1:
+        raise SystemExit("kde_bench.py needs a GPU")
+    D, F = 2, 3
+    rng = np.random.default_rng(11)
+    n, e = a.samples, a.points
+    t = rng.normal(5.0, 1.5, n)
+    samples = np.stack([t + rng.normal(0, 0.4, n), rng.uniform(-1, 1, n), t], axis=1).astype(np.float32)
+    lower, upper = [0.0, -1.0], [10.0, 1.0]
+    ev = pdfz.EvalKernel(samples.ravel(), F, D, lower, upper, [1.0, 1.0])
+    ev.AddSystematic(pdfz.ShiftSystematic(1, [0]))
+    ev.AddSystematic(pdfz.ScaleSystematic(0, [1]))
+    ev.AddSystematic(pdfz.ResolutionScaleSystematic(0, 2, [2]))
+    pts = np.stack([rng.uniform(0, 10, e), rng.uniform(-1, 1, e), np.zeros(e)], axis=1).astype(np.float32)
+    ev.SetEvalPoints(pts.ravel())
+    params = np.array([0.01, 0.02, 0.05])
+    pdf, norm, par = DeviceArray.zeros(e, np.float32), DeviceArray.zeros(1, np.uint32), DeviceArray(params)
+    ev.SetPDFValueBuffer(pdf)
+    ev.SetNormalizationBuffer(norm)
+    ev.SetParameterBuffer(par)
+    for _ in range(3):
+        ev.EvalAsync()
+        ev.EvalFinished()
+    calls, t0 = 0, time.perf_counter()
+    while True:
+        ev.EvalAsync()
+        ev.EvalFinished()
+        calls += 1
+        el = time.perf_counter() - t0
+        if el >= a.seconds and calls >= 3:
+            break
+    ms = 1e3 * el / calls
+    pairs = float(e) * n
+    rate = pairs / (ms * 1e-3)
+    info = capi.device_info(0)
+    cycles = 4 * (2 * D + 1) + 8
+    bound = info["compute_units"] * 4 * info["clock_khz"] * 1e3 * 64.0 / cycles
+    values = pdf.get()
+
+    # numpy f64 on a subset of the points (the bandwidths as the evaluator fixed them, parameters applied)
+    h = ev.Bandwidths()
+    x = samples.astype(np.float64)
+    x[:, 1] = x[:, 1] + params[0]
+    x[:, 0] = x[:, 0] * (1 + params[1])
+    x[:, 0] = x[:, 0] + params[2] * (x[:, 0] - x[:, 2])
+    s = x[:, :D]
+    s = s[np.all((s >= lower) & (s < upper), axis=1)]
+    k = min(a.cpu_points, e)
+    sub = pts[:k, :D].astype(np.float64)
+    c0 = time.perf_counter()
+    for i in range(k):
+        z = (sub[i] - s) / h
+        np.exp(-0.5 * (z * z).sum(axis=1)).sum()
+    cpu_rate = k * float(n) / (time.perf_counter() - c0)
+
+    print(json.dumps(dict(tool="kde_bench", samples=n, points=e, observables=D, nfields=F,
+                          systematics=["shift", "scale", "resolution_scale"], evaluations=calls,
+                          ms_per_eval=round(ms, 4), pairs_per_s=rate, bound_pairs_per_s=bound,
+                          bound_cycles_per_64_pairs_per_simd=cycles, clock_mhz=info["clock_khz"] / 1e3,
+                          compute_units=info["compute_units"], fraction_of_bound=round(rate / bound, 4),
+                          cpu_numpy_pairs_per_s=cpu_rate, norm=int(norm.get()[0]),
+                          finite_values=int(np.isfinite(values).sum()), device=info["name"])))
+
+
+if __name__ == "__main__":
+    main()
