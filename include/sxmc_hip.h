@@ -257,6 +257,10 @@ int sxmc_kde_create(const float* samples, size_t nsamples_floats, int samples_on
                     const double* upper, size_t n_upper,
                     const double* bandwidth_scale, size_t n_bandwidth_scale,
                     unsigned dataset, sxmc_kde_t* out);
+/* A second evaluator over the SAME sample table as `base` (as sxmc_hist_create_shared: the table is shared and reference
+ * counted, nothing is copied): systematics, bandwidths and prefactor copied from `base`; own rows, evaluation points,
+ * bindings, partial sums and stream.  For concurrent experiments on one GPU.  May outlive `base`. */
+int sxmc_kde_create_shared(sxmc_kde_t base, sxmc_kde_t* out);
 int sxmc_kde_destroy(sxmc_kde_t k);
 /* As sxmc_hist_add_systematic.  SXMC_ERR_INVALID beyond 7 columns (observables + fields systematics read) or 64
  * polynomial coefficients in all. */
@@ -275,6 +279,21 @@ int sxmc_kde_get_stream(sxmc_kde_t k, sxmc_stream_t* s);
 int sxmc_kde_bandwidths(sxmc_kde_t k, double* h, size_t n);
 int sxmc_kde_nsamples(sxmc_kde_t k, size_t* nsamples);
 int sxmc_kde_npoints(sxmc_kde_t k, size_t* npoints);
+/* The counterpart of sxmc_hist_random_sample: nobserved events drawn from the PDF of the evaluator's LAST evaluation
+ * (eval_async with do_eval_pdf 0 or 1; before any: SXMC_ERR_STATE).  Let S be that evaluation's in-domain moved samples
+ * (n = |S| = its norm; n == 0: SXMC_ERR_STATE).  An event picks s_i from S uniformly (the mixture weight 1/n; w_i only
+ * renormalises the truncated kernel), then each x_d from N(s_id, h_d^2) truncated to [lower_d, upper_d), by the inverse
+ * CDF in f64; a value that rounds to upper_d as a float becomes the float below it, so every event passes the
+ * evaluator's domain test lower <= x < upper.  Outside [lowers, uppers] (inclusive, host float arrays, both or
+ * neither) the event is redrawn, a new sample and new coordinates, up to 1024 attempts; then SXMC_ERR_STATE with the
+ * count.  h_events: nobserved rows of nobservables + 1 floats (last = dataset id).  Counter-based: Philox4x32-10 keyed
+ * by `seed`, counters (event, 2 attempt) and (event, 2 attempt + 1) -- the same seed and parameters give the same
+ * bits, on a shared evaluator too.  nobserved == 0 does nothing.  1 to 4 observables. */
+int sxmc_kde_random_sample(sxmc_kde_t k, size_t nobserved, unsigned long long seed, const float* lowers,
+                           const float* uppers, float* h_events);
+/* n: how many samples the last evaluation left inside the domain, counted by the sampler's own compaction (its norm;
+ * for tests).  SXMC_ERR_STATE before an evaluation. */
+int sxmc_kde_sample_pool(sxmc_kde_t k, size_t* n);
 
 /* ---------------------------------------------------------------- evaluator group ----------- */
 /* The "EvalAsync on all signals, then EvalFinished on all" of mcmc.cpp:264-271 and

@@ -118,6 +118,9 @@ SIGNATURES = {
     "sxmc_kde_bandwidths": [_vp, _vp, _sz],
     "sxmc_kde_nsamples": [_vp, _psz],
     "sxmc_kde_npoints": [_vp, _psz],
+    "sxmc_kde_create_shared": [_vp, _pvp],
+    "sxmc_kde_random_sample": [_vp, _sz, _ull, _vp, _vp, _vp],
+    "sxmc_kde_sample_pool": [_vp, _psz],
     "sxmc_group_create": [_vp, _i, _pvp],
     "sxmc_group_destroy": [_vp],
     "sxmc_group_set_launch_config": [_vp, _i, _i],

@@ -13,9 +13,10 @@
 //   kde_combine   per point the partials added in split order, times 1 / (norm (2 pi)^(D/2) prod h) in f64; the point
 //                 codes of EvalHist::SetEvalPoints (-1 NaN, -2 zero); norm == 0 gives NaN.
 // No floating-point atomics and no order that depends on timing: two evaluations give the same bits.
+// Sampling (sxmc_kde_random_sample) is at the end of the file.
 #include <hip/hip_runtime.h>
 
-#include "sxmc_device.h"
+#include "nll_device.h"
 
 #include "fill_kernels.inc.h"
 
@@ -169,5 +170,118 @@ hipError_t sx_kde_combine(const double* part, unsigned long long pitch, int nspl
   const unsigned grid = (unsigned)((npoints + kKdeBlock - 1) / kKdeBlock);
   hipLaunchKernelGGL(kde_combine_kernel, dim3(grid), dim3(kKdeBlock), 0, s, part, pitch, nsplit, npoints, codes, norm,
                      prefactor, out, stride);
+  return hipGetLastError();
+}
+
+// ------------------------------------------------------------------------------------ sampling (sxmc_kde_random_sample)
+// Draws from the PDF of the evaluator's last evaluation, which the rows the prepass left describe: an in-domain sample
+// has weight > 0, every other row 0.  (1) kde_flag + an inclusive scan (sx_inclusive_sum_u32) + kde_scatter list the in-domain rows in table
+// order; (2) kde_sample, one lane per event: a row picked uniformly from that list, then per observable a Gaussian
+// around its centre truncated to [lower, upper), drawn by the inverse CDF in f64.
+namespace {
+
+__global__ __launch_bounds__(kKdeBlock) void kde_flag_kernel(const float* __restrict__ rows, int D,
+                                                             unsigned long long npad, unsigned* __restrict__ flag) {
+  const unsigned long long i = (unsigned long long)blockIdx.x * kKdeBlock + threadIdx.x;
+  if (i >= npad) return;
+  flag[i] = rows[i * (unsigned long long)(D + 1) + (unsigned long long)D] > 0.0f ? 1u : 0u;
+}
+
+__global__ __launch_bounds__(kKdeBlock) void kde_scatter_kernel(const unsigned* __restrict__ flag,
+                                                                const unsigned* __restrict__ pos,
+                                                                unsigned long long npad, unsigned* __restrict__ idx) {
+  const unsigned long long i = (unsigned long long)blockIdx.x * kKdeBlock + threadIdx.x;
+  if (i >= npad) return;
+  if (flag[i]) idx[pos[i] - 1u] = (unsigned)i;   // pos: inclusive prefix sum of flag, so pos[i] >= 1 here
+}
+
+// Phi(z) = erfc(-z / sqrt 2) / 2, accurate in the lower tail; Phi^-1(p) = -sqrt 2 erfcinv(2 p), accurate for small p
+__device__ __forceinline__ double kde_phi(double z) { return 0.5 * erfc(-z * 0.70710678118654752); }
+__device__ __forceinline__ double kde_phi_inv(double p) { return -1.4142135623730950 * erfcinv(2.0 * p); }
+
+template <int D>
+__global__ __launch_bounds__(kKdeBlock) void kde_sample_kernel(const float* __restrict__ rows,
+                                                               const unsigned* __restrict__ idx, unsigned n,
+                                                               const SxKdeSampleArgs g, unsigned long long seed,
+                                                               unsigned long long nevents, float* __restrict__ out,
+                                                               unsigned* __restrict__ exhausted) {
+  const unsigned long long step = (unsigned long long)gridDim.x * kKdeBlock;
+  for (unsigned long long e = (unsigned long long)blockIdx.x * kKdeBlock + threadIdx.x; e < nevents; e += step) {
+    float x[D];
+    for (unsigned attempt = 0; attempt < 1024; attempt++) {
+      // five words per attempt: two Philox blocks, counters (e, 2 attempt) and (e, 2 attempt + 1)
+      const sxdev::Philox4 r0 = sxdev::philox4x32_10(e, 2ull * attempt, seed);
+      const sxdev::Philox4 r1 = sxdev::philox4x32_10(e, 2ull * attempt + 1ull, seed);
+      const unsigned u[4] = {r0.y, r0.z, r0.w, r1.x};
+      const unsigned i = idx[(unsigned)(((unsigned long long)r0.x * n) >> 32)];   // uniform over the n rows
+      const float* row = rows + (unsigned long long)i * (D + 1);
+      bool ok = true;
+#pragma unroll
+      for (int k = 0; k < D; k++) {
+        const double s = g.lower[k] + (double)row[k] * g.inv_cscale[k];   // the moved sample, from its scaled row
+        const double h = g.h[k];
+        // truncated to [lower, upper): alpha = (lower - s) / h <= 0 < beta = (upper - s) / h.  The lower tail mass
+        // pa = Phi(alpha), the upper tail mass qb = Phi(-beta), both accurate; a draw left of the median inverts
+        // p = pa + u m, one right of it q = qb + (1 - u) m, so that neither tail is taken as 1 - (a number near 1)
+        const double pa = kde_phi((g.lower[k] - s) / h);
+        const double qb = kde_phi((s - g.upper[k]) / h);
+        const double m = (0.5 - pa) + (0.5 - qb);
+        const double uu = ((double)u[k] + 0.5) * 2.3283064365386963e-10;            // (0, 1)
+        const double p = pa + uu * m;
+        double z;
+        if (p <= 0.5) {
+          z = kde_phi_inv(p);
+        } else {
+          const double q = qb + ((double)(0xFFFFFFFFu - u[k]) + 0.5) * 2.3283064365386963e-10 * m;   // 1 - p
+          z = -kde_phi_inv(q);
+        }
+        const double xd = s + h * z;
+        float xf = (float)xd;
+        // the evaluator's domain test in f64 on the float value: lower <= x < upper
+        if (!((double)xf >= g.lower[k])) xf = g.bottom[k];
+        if (!((double)xf < g.upper[k])) xf = g.top[k];
+        x[k] = xf;
+        if (g.has_cuts) ok = ok && !(xf > g.cut_hi[k] || xf < g.cut_lo[k]);
+      }
+      if (ok) break;
+      // redrawn while outside the cuts (a new row and new coordinates); after 1024 attempts the host fails the call
+      if (attempt == 1023) atomicAdd(exhausted, 1u);
+    }
+    float* o = out + e * (unsigned long long)(D + 1);
+#pragma unroll
+    for (int k = 0; k < D; k++) o[k] = x[k];
+    o[D] = g.dataset;
+  }
+}
+
+}  // namespace
+
+// the in-domain rows of the last evaluation, in table order: idx[0 .. pos[npad - 1])
+hipError_t sx_kde_compact(const float* rows, int D, unsigned long long npad, unsigned* flag, unsigned* pos,
+                          unsigned* idx, void* temp, size_t temp_bytes, hipStream_t s) {
+  if (npad == 0) return hipSuccess;
+  const unsigned grid = (unsigned)((npad + kKdeBlock - 1) / kKdeBlock);
+  hipLaunchKernelGGL(kde_flag_kernel, dim3(grid), dim3(kKdeBlock), 0, s, rows, D, npad, flag);
+  hipError_t e = hipGetLastError();
+  if (e != hipSuccess) return e;
+  e = sx_inclusive_sum_u32(flag, pos, (int)npad, temp, temp_bytes, s);
+  if (e != hipSuccess) return e;
+  hipLaunchKernelGGL(kde_scatter_kernel, dim3(grid), dim3(kKdeBlock), 0, s, flag, pos, npad, idx);
+  return hipGetLastError();
+}
+
+hipError_t sx_kde_sample(int D, const float* rows, const unsigned* idx, unsigned n, const SxKdeSampleArgs& g,
+                         unsigned long long seed, unsigned long long nevents, float* out, unsigned* exhausted,
+                         hipStream_t s) {
+  if (nevents == 0) return hipSuccess;
+  const unsigned long long b = (nevents + kKdeBlock - 1) / kKdeBlock;
+  const dim3 grid((unsigned)(b < 4096 ? b : 4096));
+  switch (D) {
+    case 1: hipLaunchKernelGGL(kde_sample_kernel<1>, grid, dim3(kKdeBlock), 0, s, rows, idx, n, g, seed, nevents, out, exhausted); break;
+    case 2: hipLaunchKernelGGL(kde_sample_kernel<2>, grid, dim3(kKdeBlock), 0, s, rows, idx, n, g, seed, nevents, out, exhausted); break;
+    case 3: hipLaunchKernelGGL(kde_sample_kernel<3>, grid, dim3(kKdeBlock), 0, s, rows, idx, n, g, seed, nevents, out, exhausted); break;
+    case 4: hipLaunchKernelGGL(kde_sample_kernel<4>, grid, dim3(kKdeBlock), 0, s, rows, idx, n, g, seed, nevents, out, exhausted); break;
+    default: return hipErrorInvalidValue;
+  }
   return hipGetLastError();
 }

@@ -523,6 +523,13 @@ hipError_t sx_hist_cdf(const unsigned* d_bins, unsigned* d_cdf, int nbins_total,
   return e != hipSuccess ? e : e2;
 }
 
+// the same scan on the caller's stream and scratch (temp == nullptr: temp_bytes receives the size it needs); one
+// instantiation of hipcub's scan for the library
+hipError_t sx_inclusive_sum_u32(const unsigned* d_in, unsigned* d_out, int n, void* temp, size_t& temp_bytes,
+                                hipStream_t s) {
+  return hipcub::DeviceScan::InclusiveSum(temp, temp_bytes, d_in, d_out, n, s);
+}
+
 hipError_t sx_random_sample(const unsigned* d_cdf, int nbins_total, int nobs, const int* nbins, const double* lower,
                             const double* upper, const float* cut_lo, const float* cut_hi, unsigned long long seed,
                             unsigned long long n, float dataset, float* d_out, unsigned* d_exhausted, hipStream_t s) {

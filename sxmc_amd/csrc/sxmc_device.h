@@ -218,3 +218,25 @@ hipError_t sx_kde_pairs(int D, const float* pts, unsigned long long pitch, const
 hipError_t sx_kde_combine(const double* part, unsigned long long pitch, int nsplit, unsigned long long npoints,
                           const int* codes, const unsigned* norm, double prefactor, float* out, long stride,
                           hipStream_t s);
+// Sampling from the last evaluation (sxmc_kde_random_sample): the in-domain rows listed by a flag, an inclusive scan
+// (temp: the scan's scratch, temp_bytes of it) and a scatter into idx; then one lane per event.
+struct SxKdeSampleArgs {
+  double lower[SXMC_KDE_MAX_DIM];
+  double upper[SXMC_KDE_MAX_DIM];
+  double h[SXMC_KDE_MAX_DIM];            // bandwidths
+  double inv_cscale[SXMC_KDE_MAX_DIM];   // h / sqrt(log2(e) / 2): scaled row coordinate -> x - lower
+  float bottom[SXMC_KDE_MAX_DIM];        // the smallest float >= lower
+  float top[SXMC_KDE_MAX_DIM];           // the largest float < upper
+  float cut_lo[SXMC_KDE_MAX_DIM];
+  float cut_hi[SXMC_KDE_MAX_DIM];
+  int has_cuts;
+  float dataset;
+};
+hipError_t sx_kde_compact(const float* rows, int D, unsigned long long npad, unsigned* flag, unsigned* pos,
+                          unsigned* idx, void* temp, size_t temp_bytes, hipStream_t s);
+// inclusive prefix sum of n unsigned (layout_kernels.hip); temp == nullptr: temp_bytes receives the scratch it needs
+hipError_t sx_inclusive_sum_u32(const unsigned* d_in, unsigned* d_out, int n, void* temp, size_t& temp_bytes,
+                                hipStream_t s);
+hipError_t sx_kde_sample(int D, const float* rows, const unsigned* idx, unsigned n, const SxKdeSampleArgs& g,
+                         unsigned long long seed, unsigned long long nevents, float* out, unsigned* exhausted,
+                         hipStream_t s);

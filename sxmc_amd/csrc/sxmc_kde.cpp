@@ -7,6 +7,8 @@
 // with the fill's own arithmetic.  So the norm is the histogram's, bit for bit.
 #include "sxmc_host.h"
 
+#include <limits>
+
 using namespace sxhost;
 
 struct sxmc_kde {
@@ -34,6 +36,14 @@ struct sxmc_kde {
   const double* params = nullptr;
   int par_off = 0, par_stride = 1;
   int cus = 256;
+  // sampling (sxmc_kde_random_sample): the rows hold an evaluation once one has been launched
+  bool evaluated = false;
+  unsigned* d_flag = nullptr;      // [npad] in-domain flags, then [npad] their inclusive prefix sum, then [npad] the
+                                   // in-domain row numbers (one allocation, made at the first draw)
+  void* d_scan_temp = nullptr;
+  size_t scan_temp_bytes = 0;
+  float* d_sample = nullptr;       // grow-only: drawn events + the count of events never accepted
+  size_t cap_sample = 0;
 };
 
 namespace {
@@ -158,9 +168,38 @@ int sxmc_kde_create(const float* samples, size_t nsamples_floats, int samples_on
   return SXMC_OK;
 }
 
+int sxmc_kde_create_shared(sxmc_kde_t base, sxmc_kde_t* out) {
+  SX_REQUIRE(base && out, "null argument");
+  *out = nullptr;
+  sxmc_hist_t h = nullptr;
+  int rc = sxmc_hist_create_shared(base->h, &h);   // the table (reference counted), the systematics, a stream
+  if (rc) return rc;
+  std::unique_ptr<sxmc_kde> k(new sxmc_kde);
+  k->h = h;
+  k->D = base->D;
+  k->nsamples = base->nsamples;
+  k->npad = base->npad;
+  for (int d = 0; d < SXMC_KDE_MAX_DIM; d++) k->bw[d] = base->bw[d];
+  k->prefactor = base->prefactor;
+  k->cus = base->cus;
+  const size_t bytes = sizeof(float) * k->npad * (size_t)(k->D + 1);
+  hipError_t e = hipMalloc((void**)&k->d_rows, bytes);
+  if (e == hipSuccess) e = hipMemset(k->d_rows, 0, bytes);
+  if (e != hipSuccess) {
+    if (k->d_rows) (void)hipFree(k->d_rows);
+    sxmc_hist_destroy(k->h);
+    return fail(SXMC_ERR_HIP, std::string("create_shared: ") + hipGetErrorString(e));
+  }
+  *out = k.release();
+  return SXMC_OK;
+}
+
 int sxmc_kde_destroy(sxmc_kde_t k) {
   if (!k) return SXMC_OK;
   if (k->h && k->h->stream) (void)hipStreamSynchronize(k->h->stream);
+  if (k->d_flag) (void)hipFree(k->d_flag);
+  if (k->d_scan_temp) (void)hipFree(k->d_scan_temp);
+  if (k->d_sample) (void)hipFree(k->d_sample);
   if (k->d_rows) (void)hipFree(k->d_rows);
   if (k->d_pts) (void)hipFree(k->d_pts);
   if (k->d_codes) (void)hipFree(k->d_codes);
@@ -296,6 +335,7 @@ int sxmc_kde_eval_async(sxmc_kde_t k, int do_eval_pdf) {
     SX_HIP(sx_kde_combine(k->d_part, k->pitch, k->nsplit, k->npoints, k->d_codes, a.norm, k->prefactor,
                           k->pdf + k->pdf_off, (long)k->pdf_stride, s));
   }
+  k->evaluated = true;
   return SXMC_OK;
 }
 
@@ -324,6 +364,110 @@ int sxmc_kde_nsamples(sxmc_kde_t k, size_t* v) {
 int sxmc_kde_npoints(sxmc_kde_t k, size_t* v) {
   SX_REQUIRE(k && v, "null argument");
   *v = k->has_points ? k->npoints : 0;
+  return SXMC_OK;
+}
+
+}  // extern "C"
+
+namespace {
+
+// Lists the in-domain rows of the last evaluation on the evaluator's stream and returns their count n (= the norm of
+// that evaluation): after it, d_flag + 2 npad holds their row numbers in table order.
+int kde_compact(sxmc_kde_t k, unsigned& n) {
+  if (!k->evaluated) {
+    return fail(SXMC_ERR_STATE, "EvalKernel: nothing to draw from before an evaluation (EvalAsync first)");
+  }
+  SX_REQUIRE(k->npad <= 0x7FFFFFFFull, "EvalKernel: too many samples to draw from");
+  const hipStream_t s = k->h->stream;
+  if (!k->d_flag) {
+    SX_HIP(hipStreamSynchronize(s));   // (allocation next to queued work: settle it first)
+    if (!k->d_scan_temp) {
+      size_t temp = 0;
+      SX_HIP(sx_inclusive_sum_u32(nullptr, nullptr, (int)k->npad, nullptr, temp, s));
+      SX_HIP(hipMalloc((void**)&k->d_scan_temp, std::max<size_t>(temp, 16)));
+      k->scan_temp_bytes = temp;
+    }
+    SX_HIP(hipMalloc((void**)&k->d_flag, sizeof(unsigned) * 3 * k->npad));
+  }
+  unsigned* flag = k->d_flag;
+  unsigned* pos = flag + k->npad;
+  unsigned* idx = pos + k->npad;
+  SX_HIP(sx_kde_compact(k->d_rows, k->D, k->npad, flag, pos, idx, k->d_scan_temp, k->scan_temp_bytes, s));
+  SX_HIP(hipMemcpyAsync(&n, pos + (k->npad - 1), sizeof(unsigned), hipMemcpyDeviceToHost, s));
+  SX_HIP(hipStreamSynchronize(s));
+  return SXMC_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int sxmc_kde_sample_pool(sxmc_kde_t k, size_t* n) {
+  SX_REQUIRE(k && n, "null argument");
+  unsigned c = 0;
+  const int rc = kde_compact(k, c);
+  if (rc) return rc;
+  *n = c;
+  return SXMC_OK;
+}
+
+int sxmc_kde_random_sample(sxmc_kde_t k, size_t nobserved, unsigned long long seed, const float* lowers,
+                           const float* uppers, float* h_events) {
+  SX_REQUIRE(k && (h_events || nobserved == 0), "null argument");
+  SX_REQUIRE((lowers == nullptr) == (uppers == nullptr), "give both cut arrays or neither");
+  if (!k->evaluated) {
+    return fail(SXMC_ERR_STATE, "EvalKernel: nothing to draw from before an evaluation (EvalAsync first)");
+  }
+  if (nobserved == 0) return SXMC_OK;
+  unsigned n = 0;
+  int rc = kde_compact(k, n);
+  if (rc) return rc;
+  if (n == 0) {
+    return fail(SXMC_ERR_STATE, "EvalKernel: the last evaluation left no sample inside the domain: nothing to draw from");
+  }
+  const int D = k->D;
+  SxKdeSampleArgs g;
+  std::memset(&g, 0, sizeof g);
+  for (int d = 0; d < D; d++) {
+    const double lo = k->h->lower[(size_t)d], hi = k->h->upper[(size_t)d];
+    g.lower[d] = lo;
+    g.upper[d] = hi;
+    g.h[d] = k->bw[d];
+    g.inv_cscale[d] = k->bw[d] / kLog2eHalfSqrt;
+    float b = (float)lo, t = (float)hi;
+    if ((double)b < lo) b = std::nextafter(b, std::numeric_limits<float>::infinity());
+    while (!((double)t < hi)) t = std::nextafter(t, -std::numeric_limits<float>::infinity());
+    g.bottom[d] = b;
+    g.top[d] = t;
+    g.cut_lo[d] = lowers ? lowers[d] : 0.0f;
+    g.cut_hi[d] = uppers ? uppers[d] : 0.0f;
+  }
+  g.has_cuts = lowers ? 1 : 0;
+  g.dataset = (float)k->h->dataset;
+  const size_t row = (size_t)D + 1;
+  const hipStream_t s = k->h->stream;
+  const size_t need = sizeof(float) * nobserved * row + sizeof(unsigned);   // + the count of events never accepted
+  if (need > k->cap_sample) {
+    if (k->d_sample) SX_HIP(hipFree(k->d_sample));
+    k->d_sample = nullptr;
+    k->cap_sample = 0;
+    SX_HIP(hipMalloc((void**)&k->d_sample, need + need / 4));
+    k->cap_sample = need + need / 4;
+  }
+  float* const d_out = k->d_sample;
+  unsigned* d_exhausted = reinterpret_cast<unsigned*>(d_out + nobserved * row);
+  SX_HIP(hipMemsetAsync(d_exhausted, 0, sizeof(unsigned), s));
+  const unsigned* idx = k->d_flag + 2 * k->npad;
+  SX_HIP(sx_kde_sample(D, k->d_rows, idx, n, g, seed, nobserved, d_out, d_exhausted, s));
+  SX_HIP(hipStreamSynchronize(s));
+  unsigned exhausted = 0;
+  SX_HIP(hipMemcpy(&exhausted, d_exhausted, sizeof(unsigned), hipMemcpyDeviceToHost));
+  if (exhausted) {
+    return fail(SXMC_ERR_STATE, std::to_string(exhausted) + " of " + std::to_string(nobserved) +
+                                    " events could not be drawn inside the cuts in 1024 attempts each: the cuts leave "
+                                    "(almost) none of the kernel-density PDF's mass");
+  }
+  SX_HIP(hipMemcpy(h_events, d_out, sizeof(float) * nobserved * row, hipMemcpyDeviceToHost));
   return SXMC_OK;
 }
 

@@ -20,9 +20,9 @@ import math
 
 import numpy as np
 
-from . import capi
+from . import capi, pdfz
 from .capi import DeviceArray
-from .mcmc import MCMC
+from .mcmc import MCMC, make_systematic
 
 INTERVAL_FIELDS = ("point_estimate", "lower", "upper", "coverage")
 
@@ -63,21 +63,39 @@ def random_sample(rng, bins, lower, upper, nbins, nobserved):
     return pts.astype(np.float32)
 
 
+def make_evaluators(workload):
+    """One evaluator per signal with every systematic attached: pdfz.EvalHist, or pdfz.EvalKernel for a signal whose
+    pdf is "kernel" (what make_fake_dataset draws from; signal.cpp:112-133 build_pdfz)."""
+    w = workload
+    out = []
+    for s in w.signals:
+        if getattr(s, "pdf", "hist") == "kernel":
+            scale = s.bandwidth_scale if s.bandwidth_scale is not None else [1.0] * w.nobs
+            ev = pdfz.EvalKernel(s.samples, s.nfields, w.nobs, w.lower, w.upper, scale, dataset=s.dataset)
+        else:
+            ev = pdfz.EvalHist(s.samples, s.nfields, w.nobs, w.lower, w.upper, w.nbins, dataset=s.dataset)
+        for d in w.systematics:
+            ev.AddSystematic(make_systematic(d))
+        out.append(ev)
+    return out
+
+
 def make_fake_dataset(rng, workload, evaluators, poisson=True):
     """generator.cpp:10-48: per signal nexpected x efficiency events (Poisson fluctuated), drawn from
-    the signal's histogram at the mean systematics; rows of nobs + 1 floats (last = dataset id)."""
+    the signal's PDF at the mean systematics (a histogram's bins, or a pdfz.EvalKernel's moved samples);
+    rows of nobs + 1 floats (last = dataset id)."""
     w = workload
     syst_means = w.parameter_means()[w.nsources:]
     rows, observed = [], []
     for sig, ev in zip(w.signals, evaluators):
-        if w.nobs > 3:
+        if w.nobs > 3 and not isinstance(ev, pdfz.EvalKernel):
             raise ValueError("Cannot sample histograms of more than 3 dimensions")   # pdfz.cpp:499-501
         eff, _, indomain = get_efficiency(ev, w.nsyst_pars, syst_means, sig.n_mc, want_bins=False)
         nevents = sig.nexpected * eff
         n = int(rng.poisson(nevents)) if poisson else int(math.floor(nevents + 0.5))
         if indomain == 0:
-            n = 0                                        # an empty histogram yields no events
-        # drawn on the device from the histogram get_efficiency just filled: it never leaves HBM
+            n = 0                                        # an empty PDF yields no events
+        # drawn on the device from the evaluation get_efficiency just made: it never leaves HBM
         rows.append(ev.RandomSample(n, int(rng.integers(0, 2 ** 63 - 1))) if n else
                     np.zeros((0, w.nobs + 1), np.float32))
         observed.append(n)

@@ -740,6 +740,35 @@ inline Systematic systematic_from_json(const std::string& name, const json::Valu
   s.fixed = c.get("fixed", false);
   return s;
 }
+/** A signal's "pdf" ("hist", the default, or "kernel": pdfz::EvalKernel) and, for "kernel" only, "bandwidth_scale":
+ *  one number for every fit observable or one per fit observable in fit-observable order, each positive and finite;
+ *  absent: 1.0 each.  A histogram signal keeps an empty bandwidth_scale. */
+inline void signal_pdf_from_json(Signal& s, const json::Value& c, size_t nobservables) {
+  const std::string who = "signal '" + s.name + "': ";
+  s.pdf = c.isMember("pdf") ? c["pdf"].asString("pdf") : std::string("hist");
+  if (s.pdf != "hist" && s.pdf != "kernel") {
+    throw ConfigError(who + "unknown \"pdf\" \"" + s.pdf + "\" (\"hist\" or \"kernel\")");
+  }
+  s.bandwidth_scale.clear();
+  if (c.isMember("bandwidth_scale")) {
+    if (s.pdf != "kernel") throw ConfigError(who + "\"bandwidth_scale\" is only for \"pdf\": \"kernel\"");
+    const json::Value& b = c["bandwidth_scale"];
+    if (b.kind == json::Value::Array) {
+      if (b.size() != nobservables) {
+        throw ConfigError(who + "\"bandwidth_scale\" has " + std::to_string(b.size()) + " values for " +
+                          std::to_string(nobservables) + " fit observables");
+      }
+      for (size_t i = 0; i < b.size(); i++) s.bandwidth_scale.push_back(b[i].asDouble("bandwidth_scale"));
+    } else {
+      s.bandwidth_scale.assign(nobservables, b.asDouble("bandwidth_scale"));
+    }
+    for (double v : s.bandwidth_scale) {
+      if (!(std::isfinite(v) && v > 0)) throw ConfigError(who + "\"bandwidth_scale\" must be positive and finite");
+    }
+  } else if (s.pdf == "kernel") {
+    s.bandwidth_scale.assign(nobservables, 1.0);
+  }
+}
 template <typename T>
 size_t index_with_append(std::vector<T>& v, const T& x) {   // utils.h get_index_with_append
   const size_t i = std::find(v.begin(), v.end(), x) - v.begin();
@@ -860,6 +889,7 @@ inline FitConfig parse_config(const std::string& text, const std::string& base_d
     // (-) tells Signal to scale by the total number of samples (config.cpp:216-222)
     double nexpected = c.isMember("rate") ? (double)c["rate"].asFloat("rate") : (double)(-1.0f / c["scale"].asFloat("scale"));
     for (const json::Value& sv : c["systematics"].items) s.systematic_names.push_back(sv.asString("systematics[]"));
+    detail::signal_pdf_from_json(s, c, fc.observables.size());
     const std::string source_name = c.get("source", name.c_str());
     for (const Source& src : fc.sources)
       if (src.name == source_name) {

@@ -401,6 +401,7 @@ inline std::vector<float> make_fake_dataset(std::mt19937_64& rng, std::vector<Si
                                             std::vector<unsigned>* observed_out = nullptr) {
   std::vector<float> events;
   for (Signal& s : signals) {
+    pdfz::EvalKernel* kde = dynamic_cast<pdfz::EvalKernel*>(s.histogram);
     const double eff = get_efficiency(s, systematics);
     const double nevents = s.nexpected * eff;
     size_t observed;
@@ -409,10 +410,12 @@ inline std::vector<float> make_fake_dataset(std::mt19937_64& rng, std::vector<Si
     } else {
       observed = (size_t)std::floor(nevents + 0.5);
     }
-    if (observables.size() > 3) throw pdfz::Error("Cannot EvalHist::CreateHistogram for dimensions greater than 3!");
+    if (!kde && observables.size() > 3) throw pdfz::Error("Cannot EvalHist::CreateHistogram for dimensions greater than 3!");
     if (eff <= 0) observed = 0;   // an empty histogram yields no events
-    // drawn on the device from the histogram get_efficiency just filled: it never leaves HBM
-    if (observed) histogram_of(s, "draw fake data").SampleEvents(events, observed, rng());
+    // drawn on the device from the evaluation get_efficiency just made (a histogram's bins, or a kernel-density PDF's
+    // moved samples): it never leaves HBM
+    if (observed && kde) kde->SampleEvents(events, observed, rng());
+    else if (observed) histogram_of(s, "draw fake data").SampleEvents(events, observed, rng());
     if (observed_out) observed_out->push_back((unsigned)observed);
   }
   return events;
@@ -840,6 +843,9 @@ struct MultiGpuEnsemble {
     unsigned long long acquisitions;
   };
   std::vector<LockUse> setup_locks;
+  /** how each device ran its experiments: "lockstep" (ensemble_lockstep) or "concurrent" (ensemble_concurrent) --
+   *  also when lockstep was asked for and a kernel-density signal ruled it out (lockstep batches histogram fills) */
+  std::string device_mode;
 };
 
 /** The ensemble of sxmc.cpp:44-145 over the GPUs of one node, driven from one process: a host thread per
@@ -889,6 +895,12 @@ inline MultiGpuEnsemble ensemble_multi_gpu(const std::vector<int>& devices, unsi
       }
     }
   }
+  // lockstep sets batch the chains' histogram fills: a kernel-density signal runs its device's experiments as
+  // ensemble_concurrent lanes instead
+  bool any_kernel = false;
+  for (const Signal& s : signals) any_kernel = any_kernel || s.pdf == "kernel";
+  const bool lockstep = opt.lockstep_chains >= 2 && !any_kernel;
+  out.device_mode = lockstep ? "lockstep" : "concurrent";
   std::vector<float> rank0((size_t)G * block, std::numeric_limits<float>::quiet_NaN());
   std::vector<std::exception_ptr> errors(G);
   // one lock for the process, or one per card (ranks rehearsed on one card share theirs); key -1 = the process's
@@ -933,9 +945,9 @@ inline MultiGpuEnsemble ensemble_multi_gpu(const std::vector<int>& devices, unsi
         std::vector<unsigned> ks;
         for (unsigned k = (unsigned)r; k < nexperiments; k += (unsigned)G) ks.push_back(k);
         // per device: experiments in flight either as lockstep sets (one pass over the tables per step and set)
-        // or each with its own fill
+        // or each with its own evaluation (ensemble_concurrent, nconcurrent in flight)
         std::vector<ExperimentResult> res =
-            opt.lockstep_chains >= 2
+            lockstep
                 ? ensemble_lockstep(ks, base_seed, src, mine, sys, obs, nsteps, burnin_fraction, opt.lockstep_chains,
                                     opt.lockstep_sets, opt.cl, opt.sync_interval,
                                     opt.graph_steps ? opt.graph_steps : 10, devices[r], &exclusive, opt.error_type)

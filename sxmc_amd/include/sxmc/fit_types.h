@@ -60,13 +60,16 @@ struct Signal {
   Source source;
   double nexpected = 0;
   size_t n_mc = 0;  //!< number of MC samples BEFORE cuts (signal.cpp:28); build_pdfz fills it in when it is 0
+  std::string pdf = "hist";                   //!< "hist": pdfz::EvalHist; "kernel": pdfz::EvalKernel (kernel density)
+  std::vector<double> bandwidth_scale;        //!< "kernel": one per fit observable, in fit-observable order (empty: 1.0)
   pdfz::Eval* histogram = nullptr;  //!< borrowed by the driver, as in the reference
   // keeps the parameter-index arrays alive (the reference leaks them, signal.cpp:139)
   std::vector<std::shared_ptr<pdfz::Array<short>>> par_arrays;
 };
 
-/** Signal::build_pdfz (signal.cpp:112-170): histogram evaluator of one signal with every systematic
- *  attached.  `samples` is the row-major [n][nfields] table, observables first. */
+/** Signal::build_pdfz (signal.cpp:112-170): the evaluator of one signal with every systematic attached -- a
+ *  pdfz::EvalHist, or a pdfz::EvalKernel when sig.pdf is "kernel" (bandwidth scales from sig.bandwidth_scale).
+ *  `samples` is the row-major [n][nfields] table, observables first. */
 inline void build_pdfz(Signal& sig, const std::vector<float>& samples, int nfields,
                        const std::vector<Observable>& observables, std::vector<Systematic>& systematics) {
   std::vector<double> lower(observables.size()), upper(observables.size());
@@ -76,7 +79,21 @@ inline void build_pdfz(Signal& sig, const std::vector<float>& samples, int nfiel
     upper.at(o.field_index) = o.upper;
     nbins.at(o.field_index) = (int)o.bins;
   }
-  pdfz::EvalHist* h = new pdfz::EvalHist(samples, nfields, (int)observables.size(), lower, upper, nbins, sig.dataset);
+  pdfz::Eval* h = nullptr;
+  if (sig.pdf == "kernel") {
+    const size_t D = observables.size();
+    if (!sig.bandwidth_scale.empty() && sig.bandwidth_scale.size() != D) {
+      throw pdfz::Error("signal '" + sig.name + "': " + std::to_string(sig.bandwidth_scale.size()) +
+                        " bandwidth scales for " + std::to_string(D) + " observables");
+    }
+    std::vector<double> scale(D, 1.0);
+    for (size_t i = 0; i < D && !sig.bandwidth_scale.empty(); i++) scale.at(observables[i].field_index) = sig.bandwidth_scale[i];
+    h = new pdfz::EvalKernel(samples, nfields, (int)D, lower, upper, scale, sig.dataset);
+  } else if (sig.pdf == "hist") {
+    h = new pdfz::EvalHist(samples, nfields, (int)observables.size(), lower, upper, nbins, sig.dataset);
+  } else {
+    throw pdfz::Error("signal '" + sig.name + "': unknown pdf \"" + sig.pdf + "\" (\"hist\" or \"kernel\")");
+  }
   sig.histogram = h;
   // (a table loaded through load_config has been cut: n_mc is then the row count before the cuts, set by the loader)
   if (sig.n_mc == 0) sig.n_mc = samples.size() / (size_t)nfields;
@@ -104,11 +121,15 @@ inline pdfz::EvalHist& histogram_of(const Signal& s, const std::string& what) {
   return *h;
 }
 
-/** A copy of `base` whose evaluator shares base's sample table (pdfz::EvalHist::SharedSamples): what each
+/** A copy of `base` whose evaluator shares base's sample table (EvalHist's or EvalKernel's SharedSamples): what each
  *  additional concurrent chain on a GPU works with.  The caller deletes .histogram, as for build_pdfz. */
 inline Signal share_pdfz(const Signal& base) {
   Signal s = base;
-  s.histogram = new pdfz::EvalHist(histogram_of(base, "share its sample table"), pdfz::EvalHist::SharedSamples{});
+  if (const pdfz::EvalKernel* k = dynamic_cast<const pdfz::EvalKernel*>(base.histogram)) {
+    s.histogram = new pdfz::EvalKernel(*k, pdfz::EvalKernel::SharedSamples{});
+  } else {
+    s.histogram = new pdfz::EvalHist(histogram_of(base, "share its sample table"), pdfz::EvalHist::SharedSamples{});
+  }
   return s;
 }
 

@@ -293,7 +293,12 @@ class EvalHist : public Eval {
  *    - points as EvalHist::SetEvalPoints: any observable outside the domain NaN (whatever the data set), inside and
  *      of another data set 0, norm == 0 NaN; values go as float to pdf_out[offset + stride * i];
  *    - EvalAsync(false) computes the norm only.  EvalAsync returns before completion, EvalFinished waits.
- *  Deterministic: the same inputs give the same bits (no floating-point atomics).  Cost O(points x samples). */
+ *  Deterministic: the same inputs give the same bits (no floating-point atomics).  Cost O(points x samples).
+ *  Fake data: SampleEvents draws from the PDF of the last evaluation (EvalAsync(false) or (true) first): a moved
+ *  in-domain sample chosen uniformly, then per observable its Gaussian truncated to [lower, upper); every event passes
+ *  the domain test above.  Counter-based (Philox4x32-10 keyed by the seed): the same seed gives the same events.
+ *  Concurrent experiments: EvalKernel(base, SharedSamples{}) shares base's sample table (systematics, bandwidths
+ *  copied; own rows, points, bindings and stream) and may outlive it. */
 class EvalKernel : public Eval {
  public:
   EvalKernel(const std::vector<float>& samples, int nfields, int nobservables, const std::vector<double>& lower,
@@ -302,6 +307,11 @@ class EvalKernel : public Eval {
     throw_on(sxmc_kde_create(samples.data(), samples.size(), 0, nfields, nobservables, lower.data(), lower.size(),
                              upper.data(), upper.size(), bandwidth_scale.data(), bandwidth_scale.size(), dataset,
                              &handle));
+  }
+  /** A second evaluator over the SAME sample table as `base` (sxmc_kde_create_shared): one per concurrent chain. */
+  typedef EvalHist::SharedSamples SharedSamples;
+  EvalKernel(const EvalKernel& base, SharedSamples) : Eval(base.nfields, base.nobservables, base.dataset) {
+    throw_on(sxmc_kde_create_shared(base.handle, &handle));
   }
   EvalKernel(const EvalKernel&) = delete;
   EvalKernel& operator=(const EvalKernel&) = delete;
@@ -363,6 +373,19 @@ class EvalKernel : public Eval {
     std::vector<double> h((size_t)nobservables);
     throw_on(sxmc_kde_bandwidths(handle, h.data(), h.size()));
     return h;
+  }
+
+  /** EvalHist::SampleEvents for the kernel-density PDF (sxmc_kde_random_sample): appends `observed` events (rows of
+   *  nobservables + 1 floats, last = dataset id) drawn from the PDF of the last evaluation, redrawn while outside
+   *  [lowers, uppers] when given. */
+  void SampleEvents(std::vector<float>& events, size_t observed, unsigned long long seed,
+                    const std::vector<float>& uppers = std::vector<float>(),
+                    const std::vector<float>& lowers = std::vector<float>()) {
+    const size_t row = (size_t)nobservables + 1, old = events.size();
+    events.resize(old + observed * row);
+    const bool cuts = !uppers.empty() && !lowers.empty();
+    throw_on(sxmc_kde_random_sample(handle, observed, seed, cuts ? lowers.data() : nullptr,
+                                    cuts ? uppers.data() : nullptr, events.data() + old));
   }
 
   sxmc_kde_t Handle() const { return handle; }

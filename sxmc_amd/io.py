@@ -15,6 +15,7 @@ schema can be run end to end (run_config; `fit.samples` re-loads a saved chain i
 does).  Plots and ROOT files are not supported.
 """
 import json
+import math
 import os
 import re
 
@@ -109,6 +110,40 @@ class FitConfig:
     """What FitConfig::FitConfig (config.cpp:19-297) extracts, as plain Python data."""
 
 
+def _number(v, what):
+    """json::Value::asDouble of config.h: a JSON number or boolean, else "<what>: not a number"."""
+    if not isinstance(v, (int, float)):
+        raise ValueError("%s: not a number" % what)
+    return float(v)
+
+
+def signal_pdf(name, c, nobservables):
+    """A signal's "pdf" ("hist", the default, or "kernel": pdfz.EvalKernel) and, for "kernel" only, "bandwidth_scale":
+    one number for every fit observable or one per fit observable in fit-observable order, each positive and finite;
+    absent: 1.0 each.  -> (pdf, bandwidth_scale list; empty for a histogram signal).  Same rules and messages as
+    sxmc::detail::signal_pdf_from_json (config.h)."""
+    who = "signal '%s': " % name
+    pdf = c.get("pdf", "hist")
+    if not isinstance(pdf, str):
+        raise ValueError("pdf: not a string")
+    if pdf not in ("hist", "kernel"):
+        raise ValueError(who + 'unknown "pdf" "%s" ("hist" or "kernel")' % pdf)
+    if "bandwidth_scale" not in c:
+        return pdf, ([1.0] * nobservables if pdf == "kernel" else [])
+    if pdf != "kernel":
+        raise ValueError(who + '"bandwidth_scale" is only for "pdf": "kernel"')
+    b = c["bandwidth_scale"]
+    if isinstance(b, list):
+        if len(b) != nobservables:
+            raise ValueError(who + '"bandwidth_scale" has %d values for %d fit observables' % (len(b), nobservables))
+        scale = [_number(v, "bandwidth_scale") for v in b]
+    else:
+        scale = [_number(b, "bandwidth_scale")] * nobservables
+    if not all(math.isfinite(v) and v > 0 for v in scale):
+        raise ValueError(who + '"bandwidth_scale" must be positive and finite')
+    return pdf, scale
+
+
 def load_config(path_or_text, base_dir=None):
     if os.path.exists(path_or_text):
         base_dir = base_dir or os.path.dirname(os.path.abspath(path_or_text))
@@ -198,13 +233,15 @@ def load_config(path_or_text, base_dir=None):
         c = sig_params[name]
         assert ("rate" in c) != ("scale" in c)
         src_name = c.get("source", name)
+        pdf, bandwidth_scale = signal_pdf(name, c, len(fc.observables))
         fc.signals.append(dict(
             name=name, dataset=int(c["dataset"]), filename=c["filename"],
             # config.cpp:216-222: both go through a float
             rate=float(np.float32(c["rate"])) if "rate" in c else None,
             scale=float(np.float32(c["scale"])) if "scale" in c else None,
             systematics=[s for s in c.get("systematics", [])],
-            source=next(s for s in fc.sources if s["name"] == src_name)))
+            source=next(s for s in fc.sources if s["name"] == src_name),
+            pdf=pdf, bandwidth_scale=bandwidth_scale))
     fc.data = {int(k): [dict(filename=row["filename"], title=row.get("title", "")) for row in rows]
                for k, rows in root.get("data", {}).items()}
     fc.base_dir = base_dir or "."
@@ -217,6 +254,7 @@ def build_workload(fc):
     nobs = len(fc.observables)
     nfields = len(fc.sample_fields)
     cuts = [(c["field"], c["lower"], c["upper"]) for c in fc.cuts]
+    order = sorted(range(nobs), key=lambda i: fc.observables[i]["field_index"])
     signals = []
     for s in fc.signals:
         table, fields = read_table(os.path.join(fc.base_dir, s["filename"]))
@@ -225,13 +263,15 @@ def build_workload(fc):
         nexpected = s["rate"] if s["rate"] is not None else \
             float(np.float32(-1.0) / np.float32(s["scale"])) * (-1.0 * n_mc)
         samples = read_dataset_to_samples(table, fields, s["dataset"], fc.sample_fields, cuts)
-        sig = workloads.Signal(samples, nfields, nexpected, s["source"]["index"], dataset=s["dataset"])
+        # (bandwidth scales in the workload's observable order, that of lower / upper)
+        scale = [s["bandwidth_scale"][i] for i in order] if s.get("bandwidth_scale") else None
+        sig = workloads.Signal(samples, nfields, nexpected, s["source"]["index"], dataset=s["dataset"],
+                               pdf=s.get("pdf", "hist"), bandwidth_scale=scale)
         sig.n_mc_total = n_mc
         sig.name = s["name"]
         signals.append(sig)
     systs = [dict(type=s["type"], obs=s["observable_field_index"], true_obs=s["truth_field_index"],
                   pars=s["pidx"]) for s in fc.systematics]
-    order = sorted(range(nobs), key=lambda i: fc.observables[i]["field_index"])
     lower = [float(fc.observables[i]["lower"]) for i in order]
     upper = [float(fc.observables[i]["upper"]) for i in order]
     nbins = [fc.observables[i]["bins"] for i in order]

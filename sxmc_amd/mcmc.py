@@ -53,6 +53,13 @@ class MCMC:
         consume=True (fused form): the step end also clears histograms and normalisations for the next step
         (3 launches per step; they cannot be read between steps: sxmc_group_finish_step_async)."""
         w = workload
+        for j, s in enumerate(w.signals):
+            # the walk batches histogram evaluators (nll.EvalGroup); a kernel-density signal is walked by sxmc::MCMC
+            pdf = getattr(s, "pdf", "hist")
+            if pdf != "hist":
+                raise ValueError("signal %r (signal %d) has pdf %r: the Python MCMC walks histogram signals only; walk "
+                                 "kernel-density signals with the C++ layer (sxmc::MCMC, sxmc_amd/include/sxmc/mcmc.h)"
+                                 % (getattr(s, "name", str(j)), j, pdf))
         self.w = w
         self.stream = stream
         self.fused = fused

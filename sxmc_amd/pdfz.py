@@ -213,7 +213,8 @@ class EvalHist:
 
 class EvalKernel:
     """pdfz::EvalKernel (pdfz.h:578-625): the kernel-density PDF, contract in sxmc_amd/include/sxmc/pdfz.h.
-    Same method names as EvalHist, plus Bandwidths(); at most 4 observables; O(points x samples) per evaluation."""
+    Same method names as EvalHist (RandomSample and Shared included), plus Bandwidths(); at most 4 observables;
+    O(points x samples) per evaluation."""
 
     def __init__(self, samples, nfields, nobservables, lower, upper, bandwidth_scale, dataset=0):
         lib = capi.load()
@@ -234,6 +235,19 @@ class EvalKernel:
         self._h = h
         self.nfields, self.nobservables, self.dataset = int(nfields), int(nobservables), int(dataset)
         self._keep = {}
+
+    @classmethod
+    def Shared(cls, base):
+        """A second evaluator over the SAME sample table as `base` (sxmc_kde_create_shared: nothing copied but the
+        systematics and bandwidths; own rows, points, bindings and stream).  It may outlive `base`."""
+        self = cls.__new__(cls)
+        self._h = None
+        h = C.c_void_p(0)
+        _raise(capi.load().sxmc_kde_create_shared(base._h, C.byref(h)))
+        self._h = h
+        self.nfields, self.nobservables, self.dataset = base.nfields, base.nobservables, base.dataset
+        self._keep = {}
+        return self
 
     def SetEvalPoints(self, points):
         points = np.ascontiguousarray(points, dtype=np.float32).reshape(-1)
@@ -271,6 +285,22 @@ class EvalKernel:
         out = np.empty(self.nobservables, dtype=np.float64)
         _raise(capi.load().sxmc_kde_bandwidths(self._h, capi.ptr(out), out.size))
         return out
+
+    def RandomSample(self, nobserved, seed, lowers=None, uppers=None):
+        """nobserved events drawn from the PDF of the last evaluation (EvalAsync first; sxmc_kde_random_sample), rows
+        of nobservables + 1 floats (last = dataset id); redrawn while outside [lowers, uppers] when given."""
+        out = np.empty((int(nobserved), self.nobservables + 1), dtype=np.float32)
+        lo = None if lowers is None else np.ascontiguousarray(lowers, dtype=np.float32)
+        hi = None if uppers is None else np.ascontiguousarray(uppers, dtype=np.float32)
+        _raise(capi.load().sxmc_kde_random_sample(self._h, int(nobserved), int(seed) & 0xFFFFFFFFFFFFFFFF,
+                                                  capi.ptr(lo), capi.ptr(hi), capi.ptr(out)))
+        return out
+
+    def SamplePool(self):
+        """How many samples the last evaluation left inside the domain, as the sampler counts them (= the norm)."""
+        v = C.c_size_t(0)
+        _raise(capi.load().sxmc_kde_sample_pool(self._h, C.byref(v)))
+        return v.value
 
     @property
     def nsamples(self):

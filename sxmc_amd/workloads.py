@@ -10,13 +10,16 @@ import numpy as np
 class Signal:
     """One signal's MC sample table + how it enters the fit."""
 
-    def __init__(self, samples, nfields, nexpected, source_id, dataset=0):
+    def __init__(self, samples, nfields, nexpected, source_id, dataset=0, pdf="hist", bandwidth_scale=None):
         self.samples = samples              # float32 [n, nfields] row-major
         self.nfields = nfields
         self.nexpected = float(nexpected)
         self.source_id = int(source_id)
         self.dataset = dataset
         self.n_mc_total = None              # simulated events BEFORE cuts, when they differ (signal.cpp:28)
+        self.pdf = pdf                      # "hist" (pdfz.EvalHist) or "kernel" (pdfz.EvalKernel)
+        # "kernel": one scale per observable in the workload's observable order (None: 1.0 each)
+        self.bandwidth_scale = None if bandwidth_scale is None else [float(v) for v in bandwidth_scale]
 
     @property
     def n_mc(self):

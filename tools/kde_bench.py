@@ -9,7 +9,9 @@ and wave, D v_sub_f32, one v_mul_f32, D - 1 v_fmac_f32 for the distance, one v_e
 accumulate; the sample row comes through scalar loads as SGPR operands.  At the issue costs of one wave's stream
 (4 cycles, 8 for v_exp_f32) that is 4 (2D + 1) + 8 cycles per 64 pairs per SIMD (28 at D = 2), over 4 SIMDs per CU at
 the clock the device reports.  cpu_numpy_pairs_per_s: the same sum in numpy f64 on a subset of the points.
-Usage: python tools/kde_bench.py [--samples N] [--points E] [--seconds S] [--cpu-points K]"""
+ms_per_sample_call: host clock around RandomSample(--sample-events) from the last evaluation (compaction of the
+in-domain rows, the draw, the copy of the events to the host), median of 5 calls after one warm-up.
+Usage: python tools/kde_bench.py [--samples N] [--points E] [--seconds S] [--cpu-points K] [--sample-events M]"""
 import argparse
 import json
 import math
@@ -31,6 +33,7 @@ def main():
     ap.add_argument("--points", type=int, default=100000)
     ap.add_argument("--seconds", type=float, default=1.0)
     ap.add_argument("--cpu-points", type=int, default=200)
+    ap.add_argument("--sample-events", type=int, default=1000000)
     a = ap.parse_args()
     if capi.device_count() < 1:
         raise SystemExit("kde_bench.py needs a GPU")
@@ -70,6 +73,16 @@ def main():
     bound = info["compute_units"] * 4 * info["clock_khz"] * 1e3 * 64.0 / cycles
     values = pdf.get()
 
+    # fake data: --sample-events events drawn from the last evaluation
+    ev.RandomSample(a.sample_events, 1)
+    sample_ms = []
+    for k in range(5):
+        c0 = time.perf_counter()
+        drawn = ev.RandomSample(a.sample_events, 2 + k)
+        sample_ms.append(1e3 * (time.perf_counter() - c0))
+    sample_ms = float(np.median(sample_ms))
+    drawn_in_domain = bool(np.all((drawn[:, :D] >= lower) & (drawn[:, :D] < upper)))
+
     # numpy f64 on a subset of the points (the bandwidths as the evaluator fixed them, parameters applied)
     h = ev.Bandwidths()
     x = samples.astype(np.float64)
@@ -92,7 +105,9 @@ def main():
                           bound_cycles_per_64_pairs_per_simd=cycles, clock_mhz=info["clock_khz"] / 1e3,
                           compute_units=info["compute_units"], fraction_of_bound=round(rate / bound, 4),
                           cpu_numpy_pairs_per_s=cpu_rate, norm=int(norm.get()[0]),
-                          finite_values=int(np.isfinite(values).sum()), device=info["name"])))
+                          finite_values=int(np.isfinite(values).sum()), sample_events=a.sample_events,
+                          ms_per_sample_call=round(sample_ms, 4), sampled_in_domain=drawn_in_domain,
+                          device=info["name"])))
 
 
 if __name__ == "__main__":
