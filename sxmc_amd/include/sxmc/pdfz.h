@@ -294,6 +294,9 @@ class EvalHist : public Eval {
  *      of another data set 0, norm == 0 NaN; values go as float to pdf_out[offset + stride * i];
  *    - EvalAsync(false) computes the norm only.  EvalAsync returns before completion, EvalFinished waits.
  *  Deterministic: the same inputs give the same bits (no floating-point atomics).  Cost O(points x samples).
+ *  Accuracy: a value's relative error is at most about 2^-24 (128 + 2.8 c_max), c_max the largest (x - lower) / h over
+ *  the points and samples (f32 coordinates measured from lower, f32 sums over 256-sample tiles): measured 2e-6 at
+ *  c_max ~ 20, 1e-5 at ~ 100 and 9e-5 at ~ 900 (tests/kde_reference.py has the bound, tests/test_gpu_kde_dims.py).
  *  Fake data: SampleEvents draws from the PDF of the last evaluation (EvalAsync(false) or (true) first): a moved
  *  in-domain sample chosen uniformly, then per observable its Gaussian truncated to [lower, upper); every event passes
  *  the domain test above.  Counter-based (Philox4x32-10 keyed by the seed): the same seed gives the same events.

@@ -3,19 +3,47 @@
 // path (EvalAsync / EvalFinished on every evaluator, then the NLL kernels).  Prints one JSON line; exit status 0 when
 // the walk took every step, its acceptance lies in (0, 1) and every recorded NLL is finite.  Without a GPU it says so
 // and exits 0.  Built and run by tests/test_kde_cpu.py (no device) and tests/test_gpu_kde.py.
+//
+// test_kde_walk [nsteps [outdir]]: with outdir, also writes what a host recomputation of the recorded NLLs needs
+// (tests/test_gpu_kde_walk.py) as raw little-endian arrays -- flat.f32 and line.f32 (the two tables, rows of F floats),
+// data.f32 (the events, rows of value + data set), chain.f32 (the recorded rows: parameters, then the NLL) -- and
+// index.json, which names them with their shapes and gives the parameter layout (names, means, sigmas), the
+// systematics, the signals (nexpected, n_mc, source), the domain and binning, and the kernel signal's bandwidth.
 #include <sxmc/pdfz.h>
 
 #include <cmath>
 #include <cstdio>
 #include <cstdlib>
+#include <fstream>
 #include <random>
 #include <string>
 #include <vector>
 
 #include "../../sxmc_amd/include/sxmc/mcmc.h"
 
+namespace {
+
+void write_raw(const std::string& path, const std::vector<float>& v) {
+  std::ofstream f(path, std::ios::binary);
+  f.write(reinterpret_cast<const char*>(v.data()), (std::streamsize)(v.size() * sizeof(float)));
+  if (!f) throw std::runtime_error("cannot write " + path);
+}
+
+std::string json_list(const std::vector<double>& v) {
+  std::string s = "[";
+  char buf[64];
+  for (size_t i = 0; i < v.size(); i++) {
+    std::snprintf(buf, sizeof buf, "%s%.17g", i ? ", " : "", v[i]);
+    s += buf;
+  }
+  return s + "]";
+}
+
+}  // namespace
+
 int main(int argc, char** argv) {
   const unsigned nsteps = argc > 1 ? (unsigned)std::atoi(argv[1]) : 3000u;
+  const std::string outdir = argc > 2 ? argv[2] : "";
   int ndev = 0;
   if (sxmc_device_count(&ndev) != SXMC_OK || ndev < 1) {
     std::printf("test_kde_walk: no GPU device, nothing to walk\n");
@@ -98,15 +126,51 @@ int main(int argc, char** argv) {
     }
 
     size_t rows = 0, finite = 0, accepted = 0;
+    sxmc::Chain chain;
     {
       sxmc::MCMC mcmc(sources, signals, systematics, observables, 4321, nullptr);
-      sxmc::Chain chain = mcmc(data, nsteps, 0.1f, false, 1000);
+      chain = mcmc(data, nsteps, 0.1f, false, 1000);
       rows = chain.nrows();
       accepted = chain.accepted;
       const size_t col = chain.names.size() - 1;   // "likelihood"
       for (size_t r = 0; r < rows; r++) finite += std::isfinite(chain.at(r, col)) ? 1 : 0;
     }
     std::vector<double> h = kde->Bandwidths();
+    if (!outdir.empty()) {
+      write_raw(outdir + "/flat.f32", flat);
+      write_raw(outdir + "/line.f32", line);
+      write_raw(outdir + "/data.f32", data);
+      write_raw(outdir + "/chain.f32", chain.rows);
+      std::vector<double> means, sigmas;
+      for (const sxmc::Source& s : sources) {
+        means.push_back(s.mean);
+        sigmas.push_back(s.sigma);
+      }
+      std::string names = "[", systs = "[";
+      for (const std::string& n : chain.names) names += std::string(names.size() > 1 ? ", " : "") + "\"" + n + "\"";
+      for (size_t q = 0; q < systematics.size(); q++) {
+        const sxmc::Systematic& s = systematics[q];
+        means.insert(means.end(), s.means.begin(), s.means.end());
+        sigmas.insert(sigmas.end(), s.sigmas.begin(), s.sigmas.end());
+        const bool res = s.type == pdfz::Systematic::RESOLUTION_SCALE;
+        systs += std::string(q ? ", " : "") + "{\"type\": \"" + (res ? "resolution_scale" : "scale") +
+                 "\", \"obs\": " + std::to_string(s.observable_field_index) +
+                 ", \"true_obs\": " + std::to_string(res ? s.truth_field_index : 0) +
+                 ", \"pars\": [" + std::to_string(s.pidx[0]) + "]}";
+      }
+      std::ofstream f(outdir + "/index.json");
+      f << "{\"arrays\": {\"flat\": [\"flat.f32\", " << flat.size() / F << ", " << F << "], "
+        << "\"line\": [\"line.f32\", " << line.size() / F << ", " << F << "], "
+        << "\"data\": [\"data.f32\", " << data.size() / 2 << ", 2], "
+        << "\"chain\": [\"chain.f32\", " << rows << ", " << chain.names.size() << "]}, "
+        << "\"names\": " << names << "], \"means\": " << json_list(means) << ", \"sigmas\": "
+        << json_list(sigmas) << ", \"systematics\": " << systs << "], "
+        << "\"nexpected\": " << json_list({signals[0].nexpected, signals[1].nexpected}) << ", "
+        << "\"n_mc\": [" << signals[0].n_mc << ", " << signals[1].n_mc << "], \"source_id\": [0, 1], "
+        << "\"nsources\": " << sources.size() << ", \"lower\": [0.0], \"upper\": [10.0], \"bins\": [25], "
+        << "\"bandwidth_scale\": [1.0], \"bandwidth\": " << json_list(h) << ", \"nfields\": " << F << "}\n";
+      if (!f) throw std::runtime_error("cannot write " + outdir + "/index.json");
+    }
     for (sxmc::Signal& s : signals) delete s.histogram;
     const double acceptance = (double)accepted / nsteps;
     const bool ok = rows > 0 && finite == rows && acceptance > 0.0 && acceptance < 1.0;

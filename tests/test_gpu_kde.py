@@ -1,5 +1,5 @@
 """GPU tests of pdfz::EvalKernel, the kernel-density PDF, against a numpy f64 restatement of its contract
-(sxmc_amd/include/sxmc/pdfz.h, class EvalKernel): values, norm, special points, normalisation, bandwidths,
+(sxmc_amd/include/sxmc/pdfz.h, class EvalKernel; tests/kde_reference.py): values, norm, special points, normalisation, bandwidths,
 determinism, fill-only evaluation, launch shapes, the NLL over a mixed lookup table, the C++ walk and the tool."""
 import json
 import math
@@ -14,69 +14,12 @@ from oracle import oracle
 from sxmc_amd import nll, pdfz
 from sxmc_amd.capi import DeviceArray
 from sxmc_amd.mcmc import make_systematic
+from tests.kde_reference import check_values, ref_bandwidths, ref_kde
 from tests.test_kde_cpu import build_kde_walk
 
 pytestmark = pytest.mark.gpu
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-
-try:
-    from scipy.special import erfc as _erfc
-except ImportError:   # (plain libm, one value at a time)
-    _erfc = np.vectorize(math.erfc, otypes=[np.float64])
-
-
-# ------------------------------------------------------------------ the contract in numpy (f64)
-def ref_transform(samples, nfields, systs, params):
-    """Every systematic on every sample, in order (apply_systematic, pdfz.cpp:306-331); p = sum_i c_i x^i."""
-    f = np.asarray(samples, np.float32).reshape(-1, nfields).astype(np.float64)
-    for s in systs:
-        k = s["obs"]
-        x = f[:, k]
-        p = np.zeros_like(x)
-        for i, q in enumerate(s["pars"]):
-            p = p + params[q] * (x ** i)
-        if s["type"] == "shift":
-            f[:, k] = x + p
-        elif s["type"] == "scale":
-            f[:, k] = x * (1 + p)
-        elif s["type"] == "ctscale":
-            f[:, k] = 1 + (x - 1) * (1 + p)
-        else:
-            f[:, k] = x + p * (x - f[:, s["true_obs"]])
-    return f
-
-
-def ref_bandwidths(samples, nfields, nobs, lower, upper, scale):
-    x = np.asarray(samples, np.float32).reshape(-1, nfields)[:, :nobs].astype(np.float64)
-    inside = np.all((x >= lower) & (x < upper), axis=1)
-    n = int(inside.sum())
-    return np.asarray(scale) * x[inside].std(axis=0, ddof=1) * n ** (-1.0 / (nobs + 4))
-
-
-def ref_kde(samples, nfields, nobs, lower, upper, scale, systs, params, points, dataset=0):
-    """(pdf values as float32, norm) of the contract."""
-    lower, upper = np.asarray(lower, np.float64), np.asarray(upper, np.float64)
-    h = ref_bandwidths(samples, nfields, nobs, lower, upper, scale)
-    s = ref_transform(samples, nfields, systs, params)[:, :nobs]
-    inside = np.all((s >= lower) & (s < upper), axis=1)
-    s = s[inside]
-    norm = int(inside.sum())
-    mass = np.prod(0.5 * (_erfc((s - upper) / (h * math.sqrt(2))) - _erfc((s - lower) / (h * math.sqrt(2)))), axis=1)
-    w = 1.0 / mass
-    pts = np.asarray(points, np.float32).reshape(-1, nobs + 1)
-    x = pts[:, :nobs].astype(np.float64)
-    out = np.zeros(len(pts), np.float64)
-    c = 1.0 / ((2 * math.pi) ** (nobs / 2) * np.prod(h))
-    step = max(1, 2 ** 24 // max(len(s), 1))
-    for a in range(0, len(x), step):
-        z = (x[a:a + step, None, :] - s[None, :, :]) / h
-        out[a:a + step] = (np.exp(-0.5 * (z * z).sum(axis=2)) @ w) * c / norm if norm else np.nan
-    in_dom = np.all((x >= lower) & (x < upper), axis=1)
-    out[in_dom & (pts[:, nobs] != np.float32(dataset))] = 0.0
-    out[~in_dom] = np.nan
-    return out, norm, h
-
 
 def gpu_kde(samples, nfields, nobs, lower, upper, scale, systs, params, points, dataset=0, par_off=0, par_stride=1,
             pdf_off=0, pdf_stride=1, norm_off=0, do_eval_pdf=True, repeat=1, ev=None):
@@ -106,17 +49,6 @@ def gpu_kde(samples, nfields, nobs, lower, upper, scale, systs, params, points, 
     return dict(ev=ev, values=vals, raw=raw, norm=int(nv[norm_off]), norms=nv, outs=outs)
 
 
-def check_values(got, want, label):
-    got, want = np.asarray(got, np.float64), np.asarray(want, np.float64)
-    assert np.array_equal(np.isnan(got), np.isnan(want)), label
-    ok = ~np.isnan(want)
-    err = np.abs(got[ok] - want[ok])
-    tol = 1e-4 * np.abs(want[ok]) + 1e-6 * np.max(np.abs(want[ok]))
-    worst = float(np.max(err / np.maximum(tol, 1e-300))) if err.size else 0.0
-    print("%s: worst |gpu - ref| = %.3g (%.3f of the tolerance)" % (label, float(err.max(initial=0.0)), worst))
-    assert np.all(err <= tol), label
-
-
 SYSTS_2D = [dict(type="shift", obs=0, pars=[0]), dict(type="scale", obs=1, pars=[1, 2]),
             dict(type="resolution_scale", obs=0, true_obs=2, pars=[3]), dict(type="ctscale", obs=1, pars=[4])]
 PARAMS_2D = {0: 0.05, 1: 0.02, 2: -0.003, 3: 0.1, 4: -0.04}
@@ -141,11 +73,11 @@ def test_values_1d_shift_scale():
     systs = [dict(type="scale", obs=0, pars=[0]), dict(type="resolution_scale", obs=0, true_obs=1, pars=[1])]
     params = {0: 0.03, 1: -0.2}
     pts = np.stack([rng.uniform(-0.2, 6.2, 500), np.zeros(500)], axis=1).astype(np.float32).ravel()
-    want, wnorm, _ = ref_kde(samples, 2, 1, [0.0], [6.0], [0.8], systs, params, pts)
+    ref = ref_kde(samples, 2, 1, [0.0], [6.0], [0.8], systs, params, pts)
     got = gpu_kde(samples, 2, 1, [0.0], [6.0], [0.8], systs, params, pts, par_off=2, par_stride=3, pdf_off=5,
                   pdf_stride=2, norm_off=1)
-    assert got["norm"] == wnorm
-    check_values(got["values"], want, "1-D")
+    assert got["norm"] == ref.norm
+    check_values(got["values"], ref, "1-D")
     assert np.all(got["raw"][:5] == 12345.0) and np.all(got["raw"][6::2] == 12345.0)   # only the strided slots
 
 
@@ -153,11 +85,11 @@ def test_values_2d_all_systematics():
     rng = np.random.default_rng(2)
     samples = table_2d(rng, 4000)
     pts = points_2d(rng, 400)
-    want, wnorm, _ = ref_kde(samples, 3, 2, [0.0, -1.0], [4.0, 1.0], [1.0, 0.7], SYSTS_2D, PARAMS_2D, pts)
+    ref = ref_kde(samples, 3, 2, [0.0, -1.0], [4.0, 1.0], [1.0, 0.7], SYSTS_2D, PARAMS_2D, pts)
     got = gpu_kde(samples, 3, 2, [0.0, -1.0], [4.0, 1.0], [1.0, 0.7], SYSTS_2D, PARAMS_2D, pts, par_off=1,
                   par_stride=2, pdf_off=3, pdf_stride=3, norm_off=1)
-    assert got["norm"] == wnorm
-    check_values(got["values"], want, "2-D")
+    assert got["norm"] == ref.norm
+    check_values(got["values"], ref, "2-D")
 
 
 def test_norm_bit_equal_to_evalhist():
@@ -250,10 +182,10 @@ def test_shapes(npoints, nsamples):
     rng = np.random.default_rng(npoints + nsamples)
     samples = rng.normal(0.5, 0.2, nsamples).astype(np.float32)
     pts = np.stack([rng.uniform(-0.1, 1.1, npoints), np.zeros(npoints)], axis=1).astype(np.float32).ravel()
-    want, wnorm, _ = ref_kde(samples, 1, 1, [0.0], [1.0], [1.0], [], {}, pts)
+    ref = ref_kde(samples, 1, 1, [0.0], [1.0], [1.0], [], {}, pts)
     got = gpu_kde(samples, 1, 1, [0.0], [1.0], [1.0], [], {}, pts)
-    assert got["norm"] == wnorm
-    check_values(got["values"], want, "E=%d N=%d" % (npoints, nsamples))
+    assert got["norm"] == ref.norm
+    check_values(got["values"], ref, "E=%d N=%d" % (npoints, nsamples))
 
 
 def test_nll_over_mixed_lut():
@@ -281,10 +213,10 @@ def test_nll_over_mixed_lut():
     for ev in (hist, kde):
         ev.EvalFinished()
     host_lut = lut.get().reshape(2, ne)
-    want_kde, wnorm, _ = ref_kde(small, 1, 1, [0.0], [4.0], [1.0], [dict(type="scale", obs=0, pars=[0])],
-                                 {0: 0.01}, events.ravel())
-    check_values(host_lut[1], want_kde, "KDE row of the mixed LUT")
-    assert int(norms.get()[1]) == wnorm
+    ref = ref_kde(small, 1, 1, [0.0], [4.0], [1.0], [dict(type="scale", obs=0, pars=[0])], {0: 0.01},
+                  events.ravel())
+    check_values(host_lut[1], ref, "KDE row of the mixed LUT")
+    assert int(norms.get()[1]) == ref.norm
     nexp = np.array([1000.0, 1000.0])
     n_mc = np.array([100000, 800], np.uint32)
     sid = np.array([0, 1], np.int16)

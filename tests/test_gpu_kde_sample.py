@@ -3,7 +3,7 @@
 domain -- checked in 1-D (KS against the exact mixture CDF, edge fractions), 2-D with every systematic (chi-square
 over a grid of separable truncated CDFs) and 4-D (moments); the domain, cuts, errors, determinism, shared evaluators
 (sxmc_kde_create_shared), fake data sets over a mixed workload and the C++ ensemble drivers with a kernel-density
-signal.  The numpy restatement of the evaluator is tests/test_gpu_kde.py's."""
+signal.  The numpy restatement of the evaluator is tests/kde_reference.py."""
 import json
 import math
 import os
@@ -14,7 +14,8 @@ import pytest
 
 from sxmc_amd import capi, ensemble, io, pdfz, workloads
 from sxmc_amd.capi import DeviceArray
-from tests.test_gpu_kde import PARAMS_2D, SYSTS_2D, _erfc, gpu_kde, ref_bandwidths, ref_transform, table_2d
+from tests.kde_reference import component_cdf, mixture_cdf, moved_in_domain, phi, ref_bandwidths
+from tests.test_gpu_kde import PARAMS_2D, SYSTS_2D, gpu_kde, table_2d
 from tests.test_kde_sample_cpu import build_cpp
 
 pytestmark = pytest.mark.gpu
@@ -23,28 +24,6 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
 # ------------------------------------------------------------------ the law in numpy (f64)
-def moved_in_domain(samples, nfields, nobs, lower, upper, systs, params):
-    s = ref_transform(samples, nfields, systs, params)[:, :nobs]
-    return s[np.all((s >= np.asarray(lower)) & (s < np.asarray(upper)), axis=1)]
-
-
-def phi(z):
-    return 0.5 * _erfc(-np.asarray(z, np.float64) / math.sqrt(2.0))
-
-
-def component_cdf(x, s, h, lo, hi):
-    """[len(x), len(s)]: the truncated Gaussian CDF of every component at every x (one observable)."""
-    pa, pb = phi((lo - s) / h), phi((hi - s) / h)
-    return (phi((np.asarray(x)[:, None] - s[None, :]) / h) - pa[None, :]) / (pb - pa)[None, :]
-
-
-def mixture_cdf(x, s, h, lo, hi, chunk=512):
-    out = np.empty(len(x))
-    for a in range(0, len(x), chunk):
-        out[a:a + chunk] = component_cdf(x[a:a + chunk], s, h, lo, hi).mean(axis=1)
-    return out
-
-
 def evaluated(samples, nfields, nobs, lower, upper, scale, systs=(), params=None, dataset=0):
     """An evaluator that has evaluated (norm and pdf at a few points) at `params`."""
     pts = np.zeros((4, nobs + 1), np.float32)
