@@ -197,6 +197,36 @@ void forget_evaluator(sxmc_hist* h) {
   for (sxmc_group* g : doomed) sxmc_group_destroy(g);
 }
 
+// The evaluator's own grow-only buffer of drawn events: an allocation and a hipFree per draw would each wait for the
+// device to drain, i.e. for whatever other chains have queued.
+int sample_buffer(sxmc_hist* h, size_t nobserved, size_t row, float*& d_events, unsigned*& d_exhausted) {
+  const size_t need = sizeof(float) * nobserved * row + sizeof(unsigned);   // + the count of events never accepted
+  if (need > h->cap_sample) {
+    if (h->d_sample) SX_HIP(hipFree(h->d_sample));
+    h->d_sample = nullptr;
+    h->cap_sample = 0;
+    SX_HIP(hipMalloc((void**)&h->d_sample, need + need / 4));
+    h->cap_sample = need + need / 4;
+  }
+  d_events = h->d_sample;
+  d_exhausted = reinterpret_cast<unsigned*>(d_events + nobserved * row);
+  SX_HIP(hipMemsetAsync(d_exhausted, 0, sizeof(unsigned), h->stream));
+  return SXMC_OK;
+}
+
+int sample_read_back(sxmc_hist* h, size_t nobserved, size_t row, const char* why, float* h_events) {
+  const unsigned* d_exhausted = reinterpret_cast<const unsigned*>(h->d_sample + nobserved * row);
+  SX_HIP(hipStreamSynchronize(h->stream));
+  unsigned exhausted = 0;
+  SX_HIP(hipMemcpy(&exhausted, d_exhausted, sizeof(unsigned), hipMemcpyDeviceToHost));
+  if (exhausted) {
+    return fail(SXMC_ERR_STATE, std::to_string(exhausted) + " of " + std::to_string(nobserved) +
+                                    " events could not be drawn inside the cuts in 1024 attempts each" + why);
+  }
+  SX_HIP(hipMemcpy(h_events, h->d_sample, sizeof(float) * nobserved * row, hipMemcpyDeviceToHost));
+  return SXMC_OK;
+}
+
 }  // namespace sxhost
 
 extern "C" {
@@ -629,32 +659,14 @@ int sxmc_hist_random_sample(sxmc_hist_t h, size_t nobserved, unsigned long long 
   SX_HIP(hipMemcpy(&total, h->d_cdf + (h->total_nbins - 1), sizeof(unsigned), hipMemcpyDeviceToHost));
   SX_REQUIRE(total > 0, "cannot sample an empty histogram");
   const size_t row = (size_t)h->nobs + 1;
-  // (the evaluator's own grow-only buffer: an allocation and a hipFree per draw would each wait for the device to
-  //  drain, i.e. for whatever other chains have queued)
-  const size_t need = sizeof(float) * nobserved * row + sizeof(unsigned);   // + the count of points never accepted
-  if (need > h->cap_sample) {
-    if (h->d_sample) SX_HIP(hipFree(h->d_sample));
-    h->d_sample = nullptr;
-    h->cap_sample = 0;
-    SX_HIP(hipMalloc((void**)&h->d_sample, need + need / 4));
-    h->cap_sample = need + need / 4;
-  }
-  float* const d_rows = h->d_sample;
-  unsigned* d_exhausted = reinterpret_cast<unsigned*>(d_rows + nobserved * row);
-  SX_HIP(hipMemsetAsync(d_exhausted, 0, sizeof(unsigned), h->stream));
+  float* d_rows = nullptr;
+  unsigned* d_exhausted = nullptr;
+  int rc = sample_buffer(h, nobserved, row, d_rows, d_exhausted);
+  if (rc) return rc;
   SX_HIP(sx_random_sample(h->d_cdf, h->total_nbins, h->nobs, h->nbins.data(), h->lower.data(), h->upper.data(), lowers,
                           uppers, seed, nobserved, (float)h->dataset, d_rows, d_exhausted, h->stream));
-  SX_HIP(hipStreamSynchronize(h->stream));
-  unsigned exhausted = 0;
-  SX_HIP(hipMemcpy(&exhausted, d_exhausted, sizeof(unsigned), hipMemcpyDeviceToHost));
-  if (exhausted) {
-    return fail(SXMC_ERR_STATE, std::to_string(exhausted) + " of " + std::to_string(nobserved) +
-                                    " events could not be drawn inside the cuts in 1024 attempts each (the reference "
-                                    "would redraw for ever, pdfz.cpp:838-905): the cuts leave (almost) none of the "
-                                    "histogram's content");
-  }
-  SX_HIP(hipMemcpy(h_events, d_rows, sizeof(float) * nobserved * row, hipMemcpyDeviceToHost));
-  return SXMC_OK;
+  return sample_read_back(h, nobserved, row, " (the reference would redraw for ever, pdfz.cpp:838-905): the cuts leave "
+                                            "(almost) none of the histogram's content", h_events);
 }
 
 int sxmc_hist_get_stream(sxmc_hist_t h, sxmc_stream_t* s) {

@@ -230,8 +230,8 @@ struct sxmc_hist {
   size_t read_bins_cap = 0;        // (grow-only: a new data set of about the same size re-uses the buffer)
   std::vector<void*> retired;      // outgrown device buffers, freed with the evaluator
   unsigned* d_cdf = nullptr;       // prefix sums of the histogram, for sxmc_hist_random_sample
-  float* d_sample = nullptr;       // ... and the rows it draws (grow-only: a fake experiment per walk draws about as many)
-  size_t cap_sample = 0;           // bytes
+  float* d_sample = nullptr;       // ... and the events drawn, a kernel-density evaluator's too (sxhost::sample_buffer;
+  size_t cap_sample = 0;           // grow-only: a fake experiment per walk draws about as many), bytes
   bool has_points = false;
   size_t npoints = 0;
   float* pdf = nullptr;
@@ -453,6 +453,12 @@ bool lazy_finish_enabled();
 bool host_can_read(const void* p);
 int settle();
 int settle_for(hipStream_t s);
+// (the buffer sxmc_hist_random_sample and sxmc_kde_random_sample draw into, h->d_sample: `nobserved` rows of `row`
+//  floats, then the count of events never accepted)
+// room for a draw, the count cleared on h->stream:
+int sample_buffer(sxmc_hist* h, size_t nobserved, size_t row, float*& d_events, unsigned*& d_exhausted);
+// waits for the draw, then fails with "<count> of <nobserved> events could not be drawn ... each" + why, or copies out:
+int sample_read_back(sxmc_hist* h, size_t nobserved, size_t row, const char* why, float* h_events);
 
 // ---- the step and its end (sxmc_group.cpp)
 extern std::atomic<int> g_stepping_groups;       // groups of this process that have stepped a chain (see note_stepping)

@@ -42,8 +42,6 @@ struct sxmc_kde {
                                    // in-domain row numbers (one allocation, made at the first draw)
   void* d_scan_temp = nullptr;
   size_t scan_temp_bytes = 0;
-  float* d_sample = nullptr;       // grow-only: drawn events + the count of events never accepted
-  size_t cap_sample = 0;
 };
 
 namespace {
@@ -69,6 +67,18 @@ void choose_split(size_t pitch, size_t ntiles, int cus, int& nsplit, unsigned& t
       tiles_per_split = (unsigned)tps;
     }
   }
+}
+
+// The cleared sample rows of a new evaluator that has its table (k->h) and npad.  On failure the table goes too: the
+// caller only drops k.
+int alloc_rows(sxmc_kde* k, const char* what) {
+  const size_t bytes = sizeof(float) * k->npad * (size_t)(k->D + 1);
+  hipError_t e = hipMalloc((void**)&k->d_rows, bytes);
+  if (e == hipSuccess) e = hipMemset(k->d_rows, 0, bytes);
+  if (e == hipSuccess) return SXMC_OK;
+  if (k->d_rows) (void)hipFree(k->d_rows);
+  sxmc_hist_destroy(k->h);
+  return fail(SXMC_ERR_HIP, std::string(what) + hipGetErrorString(e));
 }
 
 }  // namespace
@@ -151,17 +161,9 @@ int sxmc_kde_create(const float* samples, size_t nsamples_floats, int samples_on
   k->nsamples = h->nsamples;
   for (int d = 0; d < D; d++) k->bw[d] = bw[d];
   k->prefactor = 1.0 / (std::pow(2.0 * M_PI, 0.5 * D) * prod_h);
-  auto failed = [&](int code) {
-    if (k->d_rows) (void)hipFree(k->d_rows);
-    sxmc_hist_destroy(k->h);
-    return code;
-  };
-
   k->npad = std::max<size_t>(SXMC_KDE_TILE, (k->nsamples + SXMC_KDE_TILE - 1) / SXMC_KDE_TILE * SXMC_KDE_TILE);
-  const size_t bytes = sizeof(float) * k->npad * (size_t)(D + 1);
-  hipError_t e = hipMalloc((void**)&k->d_rows, bytes);
-  if (e == hipSuccess) e = hipMemset(k->d_rows, 0, bytes);
-  if (e != hipSuccess) return failed(fail(SXMC_ERR_HIP, std::string("hipMalloc sample rows: ") + hipGetErrorString(e)));
+  rc = alloc_rows(k.get(), "hipMalloc sample rows: ");
+  if (rc) return rc;
   DeviceProps props;
   if (get_props(props) == SXMC_OK && props.cus > 0) k->cus = props.cus;
   *out = k.release();
@@ -182,14 +184,8 @@ int sxmc_kde_create_shared(sxmc_kde_t base, sxmc_kde_t* out) {
   for (int d = 0; d < SXMC_KDE_MAX_DIM; d++) k->bw[d] = base->bw[d];
   k->prefactor = base->prefactor;
   k->cus = base->cus;
-  const size_t bytes = sizeof(float) * k->npad * (size_t)(k->D + 1);
-  hipError_t e = hipMalloc((void**)&k->d_rows, bytes);
-  if (e == hipSuccess) e = hipMemset(k->d_rows, 0, bytes);
-  if (e != hipSuccess) {
-    if (k->d_rows) (void)hipFree(k->d_rows);
-    sxmc_hist_destroy(k->h);
-    return fail(SXMC_ERR_HIP, std::string("create_shared: ") + hipGetErrorString(e));
-  }
+  rc = alloc_rows(k.get(), "create_shared: ");
+  if (rc) return rc;
   *out = k.release();
   return SXMC_OK;
 }
@@ -199,7 +195,6 @@ int sxmc_kde_destroy(sxmc_kde_t k) {
   if (k->h && k->h->stream) (void)hipStreamSynchronize(k->h->stream);
   if (k->d_flag) (void)hipFree(k->d_flag);
   if (k->d_scan_temp) (void)hipFree(k->d_scan_temp);
-  if (k->d_sample) (void)hipFree(k->d_sample);
   if (k->d_rows) (void)hipFree(k->d_rows);
   if (k->d_pts) (void)hipFree(k->d_pts);
   if (k->d_codes) (void)hipFree(k->d_codes);
@@ -445,30 +440,14 @@ int sxmc_kde_random_sample(sxmc_kde_t k, size_t nobserved, unsigned long long se
   g.has_cuts = lowers ? 1 : 0;
   g.dataset = (float)k->h->dataset;
   const size_t row = (size_t)D + 1;
-  const hipStream_t s = k->h->stream;
-  const size_t need = sizeof(float) * nobserved * row + sizeof(unsigned);   // + the count of events never accepted
-  if (need > k->cap_sample) {
-    if (k->d_sample) SX_HIP(hipFree(k->d_sample));
-    k->d_sample = nullptr;
-    k->cap_sample = 0;
-    SX_HIP(hipMalloc((void**)&k->d_sample, need + need / 4));
-    k->cap_sample = need + need / 4;
-  }
-  float* const d_out = k->d_sample;
-  unsigned* d_exhausted = reinterpret_cast<unsigned*>(d_out + nobserved * row);
-  SX_HIP(hipMemsetAsync(d_exhausted, 0, sizeof(unsigned), s));
+  float* d_out = nullptr;
+  unsigned* d_exhausted = nullptr;
+  rc = sample_buffer(k->h, nobserved, row, d_out, d_exhausted);   // (the histogram evaluator's, on the same stream)
+  if (rc) return rc;
   const unsigned* idx = k->d_flag + 2 * k->npad;
-  SX_HIP(sx_kde_sample(D, k->d_rows, idx, n, g, seed, nobserved, d_out, d_exhausted, s));
-  SX_HIP(hipStreamSynchronize(s));
-  unsigned exhausted = 0;
-  SX_HIP(hipMemcpy(&exhausted, d_exhausted, sizeof(unsigned), hipMemcpyDeviceToHost));
-  if (exhausted) {
-    return fail(SXMC_ERR_STATE, std::to_string(exhausted) + " of " + std::to_string(nobserved) +
-                                    " events could not be drawn inside the cuts in 1024 attempts each: the cuts leave "
-                                    "(almost) none of the kernel-density PDF's mass");
-  }
-  SX_HIP(hipMemcpy(h_events, d_out, sizeof(float) * nobserved * row, hipMemcpyDeviceToHost));
-  return SXMC_OK;
+  SX_HIP(sx_kde_sample(D, k->d_rows, idx, n, g, seed, nobserved, d_out, d_exhausted, k->h->stream));
+  return sample_read_back(k->h, nobserved, row, ": the cuts leave (almost) none of the kernel-density PDF's mass",
+                          h_events);
 }
 
 }  // extern "C"

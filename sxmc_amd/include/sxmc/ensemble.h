@@ -401,7 +401,6 @@ inline std::vector<float> make_fake_dataset(std::mt19937_64& rng, std::vector<Si
                                             std::vector<unsigned>* observed_out = nullptr) {
   std::vector<float> events;
   for (Signal& s : signals) {
-    pdfz::EvalKernel* kde = dynamic_cast<pdfz::EvalKernel*>(s.histogram);
     const double eff = get_efficiency(s, systematics);
     const double nevents = s.nexpected * eff;
     size_t observed;
@@ -410,12 +409,13 @@ inline std::vector<float> make_fake_dataset(std::mt19937_64& rng, std::vector<Si
     } else {
       observed = (size_t)std::floor(nevents + 0.5);
     }
-    if (!kde && observables.size() > 3) throw pdfz::Error("Cannot EvalHist::CreateHistogram for dimensions greater than 3!");
+    if (observables.size() > 3 && dynamic_cast<pdfz::EvalHist*>(s.histogram)) {
+      throw pdfz::Error("Cannot EvalHist::CreateHistogram for dimensions greater than 3!");
+    }
     if (eff <= 0) observed = 0;   // an empty histogram yields no events
     // drawn on the device from the evaluation get_efficiency just made (a histogram's bins, or a kernel-density PDF's
     // moved samples): it never leaves HBM
-    if (observed && kde) kde->SampleEvents(events, observed, rng());
-    else if (observed) histogram_of(s, "draw fake data").SampleEvents(events, observed, rng());
+    if (observed) s.histogram->SampleEvents(events, observed, rng());
     if (observed_out) observed_out->push_back((unsigned)observed);
   }
   return events;

@@ -121,15 +121,11 @@ inline pdfz::EvalHist& histogram_of(const Signal& s, const std::string& what) {
   return *h;
 }
 
-/** A copy of `base` whose evaluator shares base's sample table (EvalHist's or EvalKernel's SharedSamples): what each
+/** A copy of `base` whose evaluator shares base's sample table (pdfz::Eval::Share): what each
  *  additional concurrent chain on a GPU works with.  The caller deletes .histogram, as for build_pdfz. */
 inline Signal share_pdfz(const Signal& base) {
   Signal s = base;
-  if (const pdfz::EvalKernel* k = dynamic_cast<const pdfz::EvalKernel*>(base.histogram)) {
-    s.histogram = new pdfz::EvalKernel(*k, pdfz::EvalKernel::SharedSamples{});
-  } else {
-    s.histogram = new pdfz::EvalHist(histogram_of(base, "share its sample table"), pdfz::EvalHist::SharedSamples{});
-  }
+  s.histogram = base.histogram->Share();
   return s;
 }
 

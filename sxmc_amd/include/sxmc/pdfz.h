@@ -116,6 +116,16 @@ class Eval {
     norm_buffer = nullptr;
     param_buffer = nullptr;
   }
+  /** The sampling step of RandomSample (pdfz.cpp:843-918) on the device: appends `observed` events (rows of
+   *  nobservables + 1 floats, last = dataset id) drawn from the PDF of the last evaluation -- a histogram's bins
+   *  (EvalAsync(false) first, as CreateHistogram does) or a kernel-density PDF's moved samples -- redrawn while
+   *  outside [lowers, uppers] when given. */
+  virtual void SampleEvents(std::vector<float>& events, size_t observed, unsigned long long seed,
+                            const std::vector<float>& uppers = std::vector<float>(),
+                            const std::vector<float>& lowers = std::vector<float>()) = 0;
+  /** A new evaluator of the same kind over the SAME sample table (the SharedSamples constructors); the caller
+   *  deletes it. */
+  virtual Eval* Share() const = 0;
 
  protected:
   int nfields;
@@ -131,81 +141,147 @@ class Eval {
   int param_stride = 1;
 };
 
+namespace detail {
+
+/** A systematic of any of the four kinds as sxmc_*_add_systematic takes it. */
+struct SystematicFields {
+  int type, obs, extra;
+  Array<short>* pars;
+};
+inline SystematicFields unpack(const Systematic& syst) {
+  switch (syst.type) {
+    case Systematic::SHIFT: {
+      const ShiftSystematic& s = dynamic_cast<const ShiftSystematic&>(syst);
+      return {syst.type, s.obs, 0, s.pars};
+    }
+    case Systematic::SCALE: {
+      const ScaleSystematic& s = dynamic_cast<const ScaleSystematic&>(syst);
+      return {syst.type, s.obs, 0, s.pars};
+    }
+    case Systematic::CTSCALE: {
+      const CosThetaScaleSystematic& s = dynamic_cast<const CosThetaScaleSystematic&>(syst);
+      return {syst.type, s.obs, 0, s.pars};
+    }
+    case Systematic::RESOLUTION_SCALE: {
+      const ResolutionScaleSystematic& s = dynamic_cast<const ResolutionScaleSystematic&>(syst);
+      return {syst.type, s.obs, s.true_obs, s.pars};
+    }
+  }
+  throw Error("Unknown systematic type");
+}
+
+/** Tag of the sharing constructors: EvalHist(base, SharedSamples{}), EvalKernel(base, SharedSamples{}). */
+struct SharedSamples {};
+
+/** The entry points of include/sxmc_hip.h that the two families of evaluators have in common. */
+struct HistApi {
+  typedef sxmc_hist_t Handle;
+  static constexpr auto create_shared = sxmc_hist_create_shared;
+  static constexpr auto destroy = sxmc_hist_destroy;
+  static constexpr auto set_eval_points = sxmc_hist_set_eval_points;
+  static constexpr auto add_systematic = sxmc_hist_add_systematic;
+  static constexpr auto set_pdf_value_buffer = sxmc_hist_set_pdf_value_buffer;
+  static constexpr auto set_normalization_buffer = sxmc_hist_set_normalization_buffer;
+  static constexpr auto set_parameter_buffer = sxmc_hist_set_parameter_buffer;
+  static constexpr auto eval_async = sxmc_hist_eval_async;
+  static constexpr auto eval_finished = sxmc_hist_eval_finished;
+  static constexpr auto random_sample = sxmc_hist_random_sample;
+};
+struct KernelApi {
+  typedef sxmc_kde_t Handle;
+  static constexpr auto create_shared = sxmc_kde_create_shared;
+  static constexpr auto destroy = sxmc_kde_destroy;
+  static constexpr auto set_eval_points = sxmc_kde_set_eval_points;
+  static constexpr auto add_systematic = sxmc_kde_add_systematic;
+  static constexpr auto set_pdf_value_buffer = sxmc_kde_set_pdf_value_buffer;
+  static constexpr auto set_normalization_buffer = sxmc_kde_set_normalization_buffer;
+  static constexpr auto set_parameter_buffer = sxmc_kde_set_parameter_buffer;
+  static constexpr auto eval_async = sxmc_kde_eval_async;
+  static constexpr auto eval_finished = sxmc_kde_eval_finished;
+  static constexpr auto random_sample = sxmc_kde_random_sample;
+};
+
+/** What EvalHist and EvalKernel share: an evaluator of the library behind a handle, driven through Api's entry
+ *  points.  The concrete class's constructor creates the handle. */
+template <class Api>
+class EvalOver : public Eval {
+ public:
+  typedef detail::SharedSamples SharedSamples;
+  EvalOver(const EvalOver&) = delete;
+  EvalOver& operator=(const EvalOver&) = delete;
+  virtual ~EvalOver() { Api::destroy(handle); }
+
+  virtual void SetEvalPoints(const std::vector<float>& points) {
+    throw_on(Api::set_eval_points(handle, points.data(), points.size()));
+  }
+
+  virtual void AddSystematic(const Systematic& syst) {
+    const SystematicFields f = unpack(syst);
+    throw_on(Api::add_systematic(handle, f.type, f.obs, f.extra, (int)f.pars->size(), f.pars->readOnlyHostPtr()));
+  }
+
+  /** Bind the three caller buffers (device side) and launch the evaluation on this evaluator's stream -- zero + fill
+   *  (+ lookup) for a histogram (pdfz.cpp:441-488), prepass (+ pair sum + combine) for a kernel density; returns
+   *  before completion. */
+  virtual void EvalAsync(bool do_eval_pdf = true) {
+    Bind();
+    throw_on(Api::eval_async(handle, do_eval_pdf ? 1 : 0));
+  }
+  virtual void EvalFinished() { throw_on(Api::eval_finished(handle)); }
+
+  void ForgetBuffers() override {
+    Eval::ForgetBuffers();
+    throw_on(Api::set_pdf_value_buffer(handle, nullptr, 0, 1));
+    throw_on(Api::set_normalization_buffer(handle, nullptr, 0));
+    throw_on(Api::set_parameter_buffer(handle, nullptr, 0, 1));
+  }
+
+  /** The accessor calls of pdfz.cpp:457-470, 484-487: outputs become device-valid (host copies are
+   *  stale until read back), parameters are uploaded if the host side is newer. */
+  void Bind() {
+    if (pdf_buffer) throw_on(Api::set_pdf_value_buffer(handle, pdf_buffer->writeOnlyPtr(), pdf_offset, pdf_stride));
+    if (norm_buffer) throw_on(Api::set_normalization_buffer(handle, norm_buffer->writeOnlyPtr(), norm_offset));
+    if (param_buffer) throw_on(Api::set_parameter_buffer(handle, param_buffer->readOnlyPtr(), param_offset, param_stride));
+  }
+
+  void SampleEvents(std::vector<float>& events, size_t observed, unsigned long long seed,
+                    const std::vector<float>& uppers = std::vector<float>(),
+                    const std::vector<float>& lowers = std::vector<float>()) override {
+    const size_t row = (size_t)nobservables + 1, old = events.size();
+    events.resize(old + observed * row);
+    const bool cuts = !uppers.empty() && !lowers.empty();
+    throw_on(Api::random_sample(handle, observed, seed, cuts ? lowers.data() : nullptr,
+                                cuts ? uppers.data() : nullptr, events.data() + old));
+  }
+
+  typename Api::Handle Handle() const { return handle; }
+
+ protected:
+  EvalOver(int _nfields, int _nobservables, unsigned _dataset) : Eval(_nfields, _nobservables, _dataset) {}
+  /** A second evaluator over the SAME sample table as `base` (nothing copied; own histogram or rows, event bins or
+   *  points, bindings and stream; systematics as attached to `base` so far): one per concurrent chain on a GPU. */
+  EvalOver(const EvalOver& base, SharedSamples) : Eval(base.nfields, base.nobservables, base.dataset) {
+    throw_on(Api::create_shared(base.handle, &handle));
+  }
+  typename Api::Handle handle = nullptr;
+};
+
+}  // namespace detail
+
 /** pdfz::EvalHist (pdfz.h:402-574): N-dimensional histogram PDF. */
-class EvalHist : public Eval {
+class EvalHist : public detail::EvalOver<detail::HistApi> {
  public:
   EvalHist(const std::vector<float>& samples, int nfields, int nobservables, const std::vector<double>& lower,
            const std::vector<double>& upper, const std::vector<int>& nbins, unsigned dataset = 0,
            bool optimize = true)
-      : Eval(samples, nfields, nobservables, lower, upper, dataset) {
+      : EvalOver(nfields, nobservables, dataset) {
     throw_on(sxmc_hist_create(samples.data(), samples.size(), 0, nfields, nobservables, lower.data(),
                               lower.size(), upper.data(), upper.size(), nbins.data(), nbins.size(), dataset,
                               &handle));
     throw_on(sxmc_hist_set_optimize(handle, optimize ? 1 : 0));   // needs_optimization(optimize), pdfz.cpp:188
   }
-  /** A second evaluator over the SAME sample table as `base` (nothing copied; own histogram, event bins
-   *  and bindings; systematics as attached to `base` so far): one per concurrent chain on a GPU. */
-  struct SharedSamples {};
-  EvalHist(const EvalHist& base, SharedSamples) : Eval(base.nfields, base.nobservables, base.dataset) {
-    throw_on(sxmc_hist_create_shared(base.handle, &handle));
-  }
-  EvalHist(const EvalHist&) = delete;
-  EvalHist& operator=(const EvalHist&) = delete;
-  virtual ~EvalHist() { sxmc_hist_destroy(handle); }
-
-  virtual void SetEvalPoints(const std::vector<float>& points) {
-    throw_on(sxmc_hist_set_eval_points(handle, points.data(), points.size()));
-  }
-
-  virtual void AddSystematic(const Systematic& syst) {
-    int obs = 0, extra = 0;
-    Array<short>* pars = nullptr;
-    if (syst.type == Systematic::SHIFT) {
-      const ShiftSystematic& s = dynamic_cast<const ShiftSystematic&>(syst);
-      obs = s.obs;
-      pars = s.pars;
-    } else if (syst.type == Systematic::SCALE) {
-      const ScaleSystematic& s = dynamic_cast<const ScaleSystematic&>(syst);
-      obs = s.obs;
-      pars = s.pars;
-    } else if (syst.type == Systematic::CTSCALE) {
-      const CosThetaScaleSystematic& s = dynamic_cast<const CosThetaScaleSystematic&>(syst);
-      obs = s.obs;
-      pars = s.pars;
-    } else if (syst.type == Systematic::RESOLUTION_SCALE) {
-      const ResolutionScaleSystematic& s = dynamic_cast<const ResolutionScaleSystematic&>(syst);
-      obs = s.obs;
-      extra = s.true_obs;
-      pars = s.pars;
-    } else {
-      throw Error("Unknown systematic type");
-    }
-    throw_on(sxmc_hist_add_systematic(handle, (int)syst.type, obs, extra, (int)pars->size(),
-                                      pars->readOnlyHostPtr()));
-  }
-
-  /** Bind the three caller buffers (device side) and launch zero + fill (+ lookup) on this evaluator's
-   *  stream; returns before completion (pdfz.cpp:441-488). */
-  virtual void EvalAsync(bool do_eval_pdf = true) {
-    Bind();
-    throw_on(sxmc_hist_eval_async(handle, do_eval_pdf ? 1 : 0));
-  }
-  virtual void EvalFinished() { throw_on(sxmc_hist_eval_finished(handle)); }
-
-  /** The accessor calls of pdfz.cpp:457-470, 484-487: outputs become device-valid (host copies are
-   *  stale until read back), parameters are uploaded if the host side is newer. */
-  void ForgetBuffers() override {
-    Eval::ForgetBuffers();
-    throw_on(sxmc_hist_set_pdf_value_buffer(handle, nullptr, 0, 1));
-    throw_on(sxmc_hist_set_normalization_buffer(handle, nullptr, 0));
-    throw_on(sxmc_hist_set_parameter_buffer(handle, nullptr, 0, 1));
-  }
-
-  void Bind() {
-    if (pdf_buffer) throw_on(sxmc_hist_set_pdf_value_buffer(handle, pdf_buffer->writeOnlyPtr(), pdf_offset, pdf_stride));
-    if (norm_buffer) throw_on(sxmc_hist_set_normalization_buffer(handle, norm_buffer->writeOnlyPtr(), norm_offset));
-    if (param_buffer) throw_on(sxmc_hist_set_parameter_buffer(handle, param_buffer->readOnlyPtr(), param_offset, param_stride));
-  }
+  EvalHist(const EvalHist& base, SharedSamples s) : EvalOver(base, s) {}
+  Eval* Share() const override { return new EvalHist(*this, SharedSamples{}); }
 
   /** pdfz.cpp:622-628: trial launches choose the launch shape -- here at the next lookup evaluation of the batch this
    *  evaluator is evaluated in (they need an evaluation's bindings).  OptimizeBin (:630-727) is that choice for the fill;
@@ -253,24 +329,6 @@ class EvalHist : public Eval {
       for (size_t i = 0; i < bins.size(); i++) out[i] = bins[i] / vol / norm;
     return out;
   }
-
-  /** The sampling step of RandomSample (pdfz.cpp:843-918) on the device: appends `observed` events (rows of
-   *  nobservables + 1 floats, last = dataset id) drawn from the histogram of the last evaluation
-   *  (EvalAsync(false) first, as CreateHistogram does), redrawn while outside [lowers, uppers] when given. */
-  void SampleEvents(std::vector<float>& events, size_t observed, unsigned long long seed,
-                    const std::vector<float>& uppers = std::vector<float>(),
-                    const std::vector<float>& lowers = std::vector<float>()) {
-    const size_t row = (size_t)nobservables + 1, old = events.size();
-    events.resize(old + observed * row);
-    const bool cuts = !uppers.empty() && !lowers.empty();
-    throw_on(sxmc_hist_random_sample(handle, observed, seed, cuts ? lowers.data() : nullptr,
-                                     cuts ? uppers.data() : nullptr, events.data() + old));
-  }
-
-  sxmc_hist_t Handle() const { return handle; }
-
- protected:
-  sxmc_hist_t handle = nullptr;
 };
 
 /** pdfz::EvalKernel (pdfz.h:578-625; declared by the reference, implemented here): the kernel-density PDF, the unbinned
@@ -302,74 +360,17 @@ class EvalHist : public Eval {
  *  the domain test above.  Counter-based (Philox4x32-10 keyed by the seed): the same seed gives the same events.
  *  Concurrent experiments: EvalKernel(base, SharedSamples{}) shares base's sample table (systematics, bandwidths
  *  copied; own rows, points, bindings and stream) and may outlive it. */
-class EvalKernel : public Eval {
+class EvalKernel : public detail::EvalOver<detail::KernelApi> {
  public:
   EvalKernel(const std::vector<float>& samples, int nfields, int nobservables, const std::vector<double>& lower,
              const std::vector<double>& upper, const std::vector<double>& bandwidth_scale, unsigned dataset = 0)
-      : Eval(samples, nfields, nobservables, lower, upper, dataset) {
+      : EvalOver(nfields, nobservables, dataset) {
     throw_on(sxmc_kde_create(samples.data(), samples.size(), 0, nfields, nobservables, lower.data(), lower.size(),
                              upper.data(), upper.size(), bandwidth_scale.data(), bandwidth_scale.size(), dataset,
                              &handle));
   }
-  /** A second evaluator over the SAME sample table as `base` (sxmc_kde_create_shared): one per concurrent chain. */
-  typedef EvalHist::SharedSamples SharedSamples;
-  EvalKernel(const EvalKernel& base, SharedSamples) : Eval(base.nfields, base.nobservables, base.dataset) {
-    throw_on(sxmc_kde_create_shared(base.handle, &handle));
-  }
-  EvalKernel(const EvalKernel&) = delete;
-  EvalKernel& operator=(const EvalKernel&) = delete;
-  virtual ~EvalKernel() { sxmc_kde_destroy(handle); }
-
-  virtual void SetEvalPoints(const std::vector<float>& points) {
-    throw_on(sxmc_kde_set_eval_points(handle, points.data(), points.size()));
-  }
-
-  virtual void AddSystematic(const Systematic& syst) {
-    int obs = 0, extra = 0;
-    Array<short>* pars = nullptr;
-    if (syst.type == Systematic::SHIFT) {
-      const ShiftSystematic& s = dynamic_cast<const ShiftSystematic&>(syst);
-      obs = s.obs;
-      pars = s.pars;
-    } else if (syst.type == Systematic::SCALE) {
-      const ScaleSystematic& s = dynamic_cast<const ScaleSystematic&>(syst);
-      obs = s.obs;
-      pars = s.pars;
-    } else if (syst.type == Systematic::CTSCALE) {
-      const CosThetaScaleSystematic& s = dynamic_cast<const CosThetaScaleSystematic&>(syst);
-      obs = s.obs;
-      pars = s.pars;
-    } else if (syst.type == Systematic::RESOLUTION_SCALE) {
-      const ResolutionScaleSystematic& s = dynamic_cast<const ResolutionScaleSystematic&>(syst);
-      obs = s.obs;
-      extra = s.true_obs;
-      pars = s.pars;
-    } else {
-      throw Error("Unknown systematic type");
-    }
-    throw_on(sxmc_kde_add_systematic(handle, (int)syst.type, obs, extra, (int)pars->size(), pars->readOnlyHostPtr()));
-  }
-
-  /** Bind the caller's buffers (device side) and launch prepass (+ pair sum + combine) on this evaluator's stream;
-   *  returns before completion. */
-  virtual void EvalAsync(bool do_eval_pdf = true) {
-    Bind();
-    throw_on(sxmc_kde_eval_async(handle, do_eval_pdf ? 1 : 0));
-  }
-  virtual void EvalFinished() { throw_on(sxmc_kde_eval_finished(handle)); }
-
-  void ForgetBuffers() override {
-    Eval::ForgetBuffers();
-    throw_on(sxmc_kde_set_pdf_value_buffer(handle, nullptr, 0, 1));
-    throw_on(sxmc_kde_set_normalization_buffer(handle, nullptr, 0));
-    throw_on(sxmc_kde_set_parameter_buffer(handle, nullptr, 0, 1));
-  }
-
-  void Bind() {
-    if (pdf_buffer) throw_on(sxmc_kde_set_pdf_value_buffer(handle, pdf_buffer->writeOnlyPtr(), pdf_offset, pdf_stride));
-    if (norm_buffer) throw_on(sxmc_kde_set_normalization_buffer(handle, norm_buffer->writeOnlyPtr(), norm_offset));
-    if (param_buffer) throw_on(sxmc_kde_set_parameter_buffer(handle, param_buffer->readOnlyPtr(), param_offset, param_stride));
-  }
+  EvalKernel(const EvalKernel& base, SharedSamples s) : EvalOver(base, s) {}
+  Eval* Share() const override { return new EvalKernel(*this, SharedSamples{}); }
 
   /** The bandwidths h_d fixed at construction (Scott's rule). */
   std::vector<double> Bandwidths() const {
@@ -377,24 +378,6 @@ class EvalKernel : public Eval {
     throw_on(sxmc_kde_bandwidths(handle, h.data(), h.size()));
     return h;
   }
-
-  /** EvalHist::SampleEvents for the kernel-density PDF (sxmc_kde_random_sample): appends `observed` events (rows of
-   *  nobservables + 1 floats, last = dataset id) drawn from the PDF of the last evaluation, redrawn while outside
-   *  [lowers, uppers] when given. */
-  void SampleEvents(std::vector<float>& events, size_t observed, unsigned long long seed,
-                    const std::vector<float>& uppers = std::vector<float>(),
-                    const std::vector<float>& lowers = std::vector<float>()) {
-    const size_t row = (size_t)nobservables + 1, old = events.size();
-    events.resize(old + observed * row);
-    const bool cuts = !uppers.empty() && !lowers.empty();
-    throw_on(sxmc_kde_random_sample(handle, observed, seed, cuts ? lowers.data() : nullptr,
-                                    cuts ? uppers.data() : nullptr, events.data() + old));
-  }
-
-  sxmc_kde_t Handle() const { return handle; }
-
- protected:
-  sxmc_kde_t handle = nullptr;
 };
 
 }  // namespace pdfz
