@@ -215,9 +215,28 @@ int sxmc_hist_get_samples(sxmc_hist_t h, float* h_out, size_t n);
  * GetRandom's rule) -- redrawn while outside [lowers, uppers] when those are given (pdfz.cpp:853-857).  The
  * histogram stays in HBM (the reference, and round 1 of this library, copied every signal's histogram to the
  * host per fake experiment); only the events come back: h_events receives nobserved rows of nobservables + 1
- * floats (last = the evaluator's dataset id), the layout sxmc_hist_set_eval_points takes.  Counter-based
- * generator (Philox4x32-10 keyed by `seed`): the same seed gives the same events.  The Poisson fluctuation of
- * the event count (pdfz.cpp:836-841) is the caller's, on the host: it decides array sizes. */
+ * floats (last = the evaluator's dataset id), the layout sxmc_hist_set_eval_points takes.  The Poisson fluctuation
+ * of the event count (pdfz.cpp:836-841) is the caller's, on the host: it decides array sizes.  The contract, which
+ * tests/hist_sample_reference.py restates and the device output equals bit for bit:
+ *   words    event e, attempt t (from 0): Philox4x32-10 with counter words (e low, e high, t, 0) and key
+ *            (seed low, seed high) gives x, y, z, w -- the same seed and histogram give the same bits, on a shared
+ *            evaluator too
+ *   bin      cdf = the inclusive uint32 prefix sum of the flat row-major histogram, total = its last entry (0:
+ *            SXMC_ERR_INVALID); target = (x * total) >> 32; the bin is the first with cdf > target, so an empty bin
+ *            is never drawn; it is unravelled with the last observable fastest
+ *   point    observable k of index idx takes the next word of y, z, w:
+ *            xd = lower + (idx + (word + 0.5) * 2^-32) * ((upper - lower) / nbins), every operation rounded in f64
+ *   float    xf = (float)xd.  Rounding can carry xf out of the bin or of the domain, so xf is then moved one float at
+ *            a time, at most 4, towards the bin until the evaluator's own look-up of it -- lower <= xf < upper and
+ *            (int)((xf - lower) * (nbins / (upper - lower))), in f64 on the float, with the evaluator's lower, upper
+ *            and quotient -- gives idx.  Every event therefore looks up into the bin it was drawn from.  Only a bin that
+ *            holds no float at all (it is narrower than the float spacing at its position) cannot be met: the event is
+ *            then the in-domain float nearest to xd
+ *   cuts     lowers / uppers (host float arrays, both or neither), inclusive, tested on xf: while xf > upper cut or
+ *            xf < lower cut in any observable the event is redrawn with the next attempt, bin and point; after 1024
+ *            attempts SXMC_ERR_STATE with the count of such events -- none is handed out
+ * nobserved == 0 does nothing; more than 3 observables: SXMC_ERR_INVALID with the reference's message; after an
+ * evaluation that left the histogram unfilled (sparse look-up, a consuming step): SXMC_ERR_STATE. */
 int sxmc_hist_random_sample(sxmc_hist_t h, size_t nobserved, unsigned long long seed, const float* lowers,
                             const float* uppers, float* h_events);
 int sxmc_hist_get_stream(sxmc_hist_t h, sxmc_stream_t* s);

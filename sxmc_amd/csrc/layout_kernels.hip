@@ -16,7 +16,9 @@
 
 #include <hipcub/hipcub.hpp>
 
+#include <cmath>
 #include <cstring>
+#include <limits>
 
 #pragma clang fp contract(off)
 
@@ -289,13 +291,44 @@ __global__ __launch_bounds__(256) void column_codes16_kernel(const float* __rest
 // proportional to its content (inverse CDF: `cdf` is the inclusive prefix sum of the histogram), then a point
 // uniform inside the bin (what TH1::GetRandom does); redrawn while it falls outside the cuts, as the reference
 // does (:853-857).  Counter-based generator: event e, attempt t -> Philox4x32-10(counter = (e, t), key = seed).
+// The contract, word for word, is in include/sxmc_hip.h (sxmc_hist_random_sample).
 struct SampleGeom {
   int nobs;
   int has_cuts;
   int nbins[3];
-  double lower[3], width[3];
+  double lower[3], upper[3], width[3];
+  double scale[3];                  // the look-up's nbins / (upper - lower): the evaluator's own, not derived again
+  float bottom[3], top[3];          // the smallest float >= lower, the largest float < upper
   float cut_lo[3], cut_hi[3];
 };
+
+// where the float lies under the evaluator's look-up (SetEvalPoints: the domain test and the index, in f64 on the
+// float value) relative to bin idx: -1 below, +1 above, 0 inside
+__device__ __forceinline__ int sample_side(float xf, unsigned idx, double lower, double upper, double scale) {
+  const double x = (double)xf;
+  if (!(x >= lower)) return -1;
+  if (!(x < upper)) return 1;
+  const long long j = (long long)((x - lower) * scale);
+  return j < (long long)idx ? -1 : j > (long long)idx ? 1 : 0;
+}
+
+// (float)xd, moved one float at a time towards bin idx while it does not look up into it: rounding to f32 can leave
+// the bin, and the domain.  One step is enough wherever the bin holds a float; a bin that holds none (it is narrower
+// than the float spacing there) gets the in-domain float nearest to xd.
+__device__ __forceinline__ float sample_float(double xd, unsigned idx, const SampleGeom& g, int k) {
+  const float x0 = (float)xd;
+  float xf = x0;
+  for (int step = 0; step < 4; step++) {
+    const int s = sample_side(xf, idx, g.lower[k], g.upper[k], g.scale[k]);
+    if (s == 0) return xf;
+    xf = nextafterf(xf, s < 0 ? __builtin_inff() : -__builtin_inff());
+  }
+  if (sample_side(xf, idx, g.lower[k], g.upper[k], g.scale[k]) == 0) return xf;
+  xf = x0;
+  if (!((double)xf >= g.lower[k])) xf = g.bottom[k];
+  if (!((double)xf < g.upper[k])) xf = g.top[k];
+  return xf;
+}
 
 __global__ __launch_bounds__(256) void random_sample_kernel(const unsigned* __restrict__ cdf, unsigned nbins_total,
                                                             SampleGeom g, unsigned long long seed,
@@ -319,7 +352,8 @@ __global__ __launch_bounds__(256) void random_sample_kernel(const unsigned* __re
       for (int k = g.nobs - 1; k >= 0; k--) {
         const unsigned idx = flat % (unsigned)g.nbins[k];
         flat /= (unsigned)g.nbins[k];
-        x[k] = (float)(g.lower[k] + ((double)idx + ((double)u[k] + 0.5) * 2.3283064365386963e-10) * g.width[k]);
+        const double xd = g.lower[k] + ((double)idx + ((double)u[k] + 0.5) * 2.3283064365386963e-10) * g.width[k];
+        x[k] = sample_float(xd, idx, g, k);
         if (g.has_cuts) ok = ok && !(x[k] > g.cut_hi[k] || x[k] < g.cut_lo[k]);
       }
       if (ok) break;
@@ -531,8 +565,9 @@ hipError_t sx_inclusive_sum_u32(const unsigned* d_in, unsigned* d_out, int n, vo
 }
 
 hipError_t sx_random_sample(const unsigned* d_cdf, int nbins_total, int nobs, const int* nbins, const double* lower,
-                            const double* upper, const float* cut_lo, const float* cut_hi, unsigned long long seed,
-                            unsigned long long n, float dataset, float* d_out, unsigned* d_exhausted, hipStream_t s) {
+                            const double* upper, const double* scale, const float* cut_lo, const float* cut_hi,
+                            unsigned long long seed, unsigned long long n, float dataset, float* d_out,
+                            unsigned* d_exhausted, hipStream_t s) {
   if (n == 0) return hipSuccess;
   SampleGeom g{};
   g.nobs = nobs;
@@ -540,7 +575,14 @@ hipError_t sx_random_sample(const unsigned* d_cdf, int nbins_total, int nobs, co
   for (int k = 0; k < nobs && k < 3; k++) {
     g.nbins[k] = nbins[k];
     g.lower[k] = lower[k];
+    g.upper[k] = upper[k];
+    g.scale[k] = scale[k];
     g.width[k] = (upper[k] - lower[k]) / nbins[k];
+    float b = (float)lower[k], t = (float)upper[k];
+    if ((double)b < lower[k]) b = std::nextafter(b, std::numeric_limits<float>::infinity());
+    while (!((double)t < upper[k])) t = std::nextafter(t, -std::numeric_limits<float>::infinity());
+    g.bottom[k] = b;
+    g.top[k] = t;
     g.cut_lo[k] = cut_lo ? cut_lo[k] : 0.0f;
     g.cut_hi[k] = cut_hi ? cut_hi[k] : 0.0f;
   }

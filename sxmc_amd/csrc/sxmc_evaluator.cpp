@@ -663,8 +663,9 @@ int sxmc_hist_random_sample(sxmc_hist_t h, size_t nobserved, unsigned long long 
   unsigned* d_exhausted = nullptr;
   int rc = sample_buffer(h, nobserved, row, d_rows, d_exhausted);
   if (rc) return rc;
-  SX_HIP(sx_random_sample(h->d_cdf, h->total_nbins, h->nobs, h->nbins.data(), h->lower.data(), h->upper.data(), lowers,
-                          uppers, seed, nobserved, (float)h->dataset, d_rows, d_exhausted, h->stream));
+  SX_HIP(sx_random_sample(h->d_cdf, h->total_nbins, h->nobs, h->nbins.data(), h->lower.data(), h->upper.data(),
+                          h->scale.data(), lowers, uppers, seed, nobserved, (float)h->dataset, d_rows, d_exhausted,
+                          h->stream));
   return sample_read_back(h, nobserved, row, " (the reference would redraw for ever, pdfz.cpp:838-905): the cuts leave "
                                             "(almost) none of the histogram's content", h_events);
 }

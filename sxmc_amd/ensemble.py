@@ -44,9 +44,39 @@ def get_efficiency(ev, nsyst_pars, syst_means, n_mc=None, want_bins=True):
     return n / float(ev.nsamples if n_mc is None else n_mc), (ev.GetBins() if want_bins else None), n
 
 
+def sample_float(xd, idx, lower, upper, scale):
+    """The float step of the histogram samplers (include/sxmc_hip.h, sxmc_hist_random_sample), over arrays of one
+    observable: (float)xd, moved one float at a time (at most 4) towards bin idx while the evaluator's look-up of the
+    float -- lower <= x < upper and int((x - lower) * scale), in f64 -- does not give idx; where the bin holds no
+    float at all, the in-domain float nearest to xd."""
+    up, down = np.float32(np.inf), np.float32(-np.inf)
+
+    def side(xf):
+        x = xf.astype(np.float64)
+        j = ((x - lower) * scale).astype(np.int64)
+        s = np.where(j < idx, -1, np.where(j > idx, 1, 0))
+        return np.where(x >= lower, np.where(x < upper, s, 1), -1)
+    x0 = xd.astype(np.float32)
+    xf = x0.copy()
+    for _ in range(4):
+        s = side(xf)
+        if not s.any():
+            return xf
+        xf = np.where(s < 0, np.nextafter(xf, up), np.where(s > 0, np.nextafter(xf, down), xf))
+    bottom, top = np.float32(lower), np.float32(upper)
+    if float(bottom) < lower:
+        bottom = np.nextafter(bottom, up)
+    while not float(top) < upper:
+        top = np.nextafter(top, down)
+    near = np.where(x0.astype(np.float64) >= lower, x0, bottom)
+    near = np.where(near.astype(np.float64) < upper, near, top)
+    return np.where(side(xf) != 0, near, xf)
+
+
 def random_sample(rng, bins, lower, upper, nbins, nobserved):
     """TH1::GetRandom (1-3 D): pick a bin with probability proportional to its content, then a point
-    uniform inside the bin.  bins: flat row-major counts."""
+    uniform inside the bin, rounded to a float that the evaluator looks up into that bin (sample_float: the
+    device sampler's contract; the deviates here are numpy's).  bins: flat row-major counts."""
     nbins = np.asarray(nbins)
     D = nbins.size
     if D > 3:
@@ -58,9 +88,11 @@ def random_sample(rng, bins, lower, upper, nbins, nobserved):
     flat = np.searchsorted(cdf, rng.random(nobserved), side="right")
     flat = np.minimum(flat, bins.size - 1)
     idx = np.stack(np.unravel_index(flat, nbins), axis=1)
-    width = (np.asarray(upper, np.float64) - np.asarray(lower, np.float64)) / nbins
-    pts = np.asarray(lower, np.float64) + (idx + rng.random((nobserved, D))) * width
-    return pts.astype(np.float32)
+    lower, upper = np.asarray(lower, np.float64), np.asarray(upper, np.float64)
+    width = (upper - lower) / nbins
+    pts = lower + (idx + rng.random((nobserved, D))) * width
+    scale = nbins / (upper - lower)                      # the look-up's (pdfz.cpp:366-368)
+    return np.stack([sample_float(pts[:, k], idx[:, k], lower[k], upper[k], scale[k]) for k in range(D)], axis=1)
 
 
 def make_evaluators(workload):

@@ -368,7 +368,41 @@ inline void print_correlations(std::ostream& os, const Chain& chain) {
   }
 }
 
-/** RandomSample on a flat row-major histogram (1-3 D). */
+/** The float step of the histogram samplers (sxmc_hip.h, sxmc_hist_random_sample): (float)xd, moved one float at a time
+ *  (at most 4) towards bin idx while the evaluator's look-up of the float -- lower <= x < upper and
+ *  (int)((x - lower) * scale), in double -- does not give idx; a bin that holds no float at all: the in-domain float
+ *  nearest to xd. */
+inline float sample_float(double xd, size_t idx, double lower, double upper, double scale) {
+  auto side = [&](float xf) {
+    const double x = (double)xf;
+    if (!(x >= lower)) return -1;
+    if (!(x < upper)) return 1;
+    const long long j = (long long)((x - lower) * scale);
+    return j < (long long)idx ? -1 : j > (long long)idx ? 1 : 0;
+  };
+  const float inf = std::numeric_limits<float>::infinity();
+  float xf = (float)xd;
+  for (int step = 0; step < 4; step++) {
+    const int s = side(xf);
+    if (s == 0) return xf;
+    xf = std::nextafter(xf, s < 0 ? inf : -inf);
+  }
+  if (side(xf) == 0) return xf;
+  xf = (float)xd;
+  if (!((double)xf >= lower)) {
+    xf = (float)lower;
+    if ((double)xf < lower) xf = std::nextafter(xf, inf);
+  }
+  if (!((double)xf < upper)) {
+    xf = (float)upper;
+    while (!((double)xf < upper)) xf = std::nextafter(xf, -inf);
+  }
+  return xf;
+}
+
+/** RandomSample on a flat row-major histogram (1-3 D): a bin in proportion to its content, a point uniform inside it,
+ *  rounded to a float that the evaluator looks up into that bin (the device sampler's contract; the deviates here
+ *  are the host generator's). */
 inline void random_sample(std::mt19937_64& rng, const std::vector<unsigned>& bins, const std::vector<Observable>& obs,
                           size_t nobserved, unsigned dataset, std::vector<float>& events) {
   const size_t D = obs.size();
@@ -387,8 +421,10 @@ inline void random_sample(std::mt19937_64& rng, const std::vector<unsigned>& bin
       flat /= obs[k].bins;
     }
     for (size_t k = 0; k < D; k++) {
-      const double width = ((double)obs[k].upper - (double)obs[k].lower) / (double)obs[k].bins;
-      events.push_back((float)((double)obs[k].lower + ((double)idx[k] + uni(rng)) * width));
+      const double lower = (double)obs[k].lower, upper = (double)obs[k].upper;
+      const double width = (upper - lower) / (double)obs[k].bins;
+      const double scale = (int)obs[k].bins / (upper - lower);   // the look-up's (pdfz.cpp:366-368)
+      events.push_back(sample_float(lower + ((double)idx[k] + uni(rng)) * width, idx[k], lower, upper, scale));
     }
     events.push_back((float)dataset);
   }
