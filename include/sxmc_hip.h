@@ -207,6 +207,16 @@ int sxmc_hist_nsamples(sxmc_hist_t h, size_t* nsamples);
 int sxmc_hist_npoints(sxmc_hist_t h, size_t* npoints);
 int sxmc_hist_get_bins(sxmc_hist_t h, unsigned* h_bins, size_t n);       /* after eval_finished */
 int sxmc_hist_get_read_bins(sxmc_hist_t h, int* h_read_bins, size_t n);
+/* The histogram of the evaluator's LAST evaluation projected onto observable `obs` (TH2D::ProjectionX and its kin, as
+ * plot_fit uses them, plots.cpp:226-241; CreateHistogramProjection, pdfz.h:505-518): h_counts[j] = the sum of the bins
+ * whose index along `obs` is j, exact integers in 64 bits; n must be that observable's bin count.  The bins are summed
+ * where they are -- one pass over the histogram with integer atomics, partial marginals in LDS up to 2048 bins of the
+ * asked observable, one HBM atomic per non-empty bin beyond -- and only the n totals come back (sxmc_hist_get_bins
+ * copies the whole histogram: 512 MB at BASELINE config 5).  The histogram is left untouched.  Runs on the evaluator's
+ * stream after whatever is queued there; returns when h_counts is filled.  SXMC_ERR_INVALID (before the device is
+ * touched): a null argument, obs outside [0, nobservables), a wrong n.  SXMC_ERR_STATE, with sxmc_hist_get_bins'
+ * message: the histogram is not filled (a sparse look-up, a consuming step). */
+int sxmc_hist_project(sxmc_hist_t h, int obs, unsigned long long* h_counts, size_t n);
 /* GetSamples: rows of nobservables+1 floats (observables, dataset id); n = nsamples*(nobs+1). */
 int sxmc_hist_get_samples(sxmc_hist_t h, float* h_out, size_t n);
 /* EvalHist::RandomSample's sampling step (pdfz.cpp:817-922; 1-3 observables, as there) on the device: nobserved
@@ -313,6 +323,19 @@ int sxmc_kde_random_sample(sxmc_kde_t k, size_t nobserved, unsigned long long se
 /* n: how many samples the last evaluation left inside the domain, counted by the sampler's own compaction (its norm;
  * for tests).  SXMC_ERR_STATE before an evaluation. */
 int sxmc_kde_sample_pool(sxmc_kde_t k, size_t* n);
+/* The PDF of the evaluator's LAST evaluation projected onto observable `obs`: h_prob[j] = its share in bin j of nbins
+ * equal bins of [lower, upper).  The kernel of a sample is a product over the observables, the others integrate to
+ * their own truncation mass and cancel, so with (c_i, w_i) the rows the evaluation left (c the sample's scaled
+ * coordinate along `obs`, a float: (s - lower) sqrt(log2(e) / 2) / h), n the rows with w_i > 0 (the norm),
+ * u_i = c_i / sqrt(log2(e) / 2) in f64 (so u = (s - lower) / h), T = (upper - lower) / h, edges e_j = lower + j ((upper - lower) / nbins) (e_0 = lower
+ * and e_nbins = upper themselves) and t_j = (e_j - lower) / h:
+ *   h_prob[j] = (1/n) sum_i [Phi(t_j+1 - u_i) - Phi(t_j - u_i)] / [Phi(T - u_i) - Phi(-u_i)]
+ * over those rows; the shares sum to 1; all 0 when n = 0.  f64 throughout, Phi(z) = erfc(-z / sqrt 2) / 2; the samples
+ * are split across workgroups in a way that depends on their number alone and the splits are added in order, without
+ * floating-point atomics: two calls give the same bits.  Cost O(samples x nbins).  Runs on the evaluator's stream;
+ * returns when h_prob is filled; the rows are left untouched.  SXMC_ERR_INVALID: a null argument, obs outside
+ * [0, nobservables), nbins < 1.  SXMC_ERR_STATE before any evaluation. */
+int sxmc_kde_project(sxmc_kde_t k, int obs, int nbins, double* h_prob);
 
 /* ---------------------------------------------------------------- evaluator group ----------- */
 /* The "EvalAsync on all signals, then EvalFinished on all" of mcmc.cpp:264-271 and

@@ -98,6 +98,7 @@ SIGNATURES = {
     "sxmc_hist_npoints": [_vp, _psz],
     "sxmc_hist_get_bins": [_vp, _vp, _sz],
     "sxmc_hist_get_read_bins": [_vp, _vp, _sz],
+    "sxmc_hist_project": [_vp, _i, _vp, _sz],
     "sxmc_hist_get_samples": [_vp, _vp, _sz],
     "sxmc_hist_random_sample": [_vp, _sz, _ull, _vp, _vp, _vp],
     "sxmc_hist_get_stream": [_vp, _pvp],
@@ -121,6 +122,7 @@ SIGNATURES = {
     "sxmc_kde_create_shared": [_vp, _pvp],
     "sxmc_kde_random_sample": [_vp, _sz, _ull, _vp, _vp, _vp],
     "sxmc_kde_sample_pool": [_vp, _psz],
+    "sxmc_kde_project": [_vp, _i, _i, _vp],
     "sxmc_group_create": [_vp, _i, _pvp],
     "sxmc_group_destroy": [_vp],
     "sxmc_group_set_launch_config": [_vp, _i, _i],

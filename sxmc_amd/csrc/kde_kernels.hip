@@ -13,7 +13,7 @@
 //   kde_combine   per point the partials added in split order, times 1 / (norm (2 pi)^(D/2) prod h) in f64; the point
 //                 codes of EvalHist::SetEvalPoints (-1 NaN, -2 zero); norm == 0 gives NaN.
 // No floating-point atomics and no order that depends on timing: two evaluations give the same bits.
-// Sampling (sxmc_kde_random_sample) is at the end of the file.
+// Sampling (sxmc_kde_random_sample) and the projection onto one observable (sxmc_kde_project) follow the evaluation.
 #include <hip/hip_runtime.h>
 
 #include "nll_device.h"
@@ -283,5 +283,105 @@ hipError_t sx_kde_sample(int D, const float* rows, const unsigned* idx, unsigned
     case 4: hipLaunchKernelGGL(kde_sample_kernel<4>, grid, dim3(kKdeBlock), 0, s, rows, idx, n, g, seed, nevents, out, exhausted); break;
     default: return hipErrorInvalidValue;
   }
+  return hipGetLastError();
+}
+
+// ------------------------------------------------------------------------------------ projection (sxmc_kde_project)
+// The share of the PDF of the last evaluation in each of nbins equal bins of one observable: the kernel of an in-domain
+// sample is a product of truncated Gaussians, the other observables integrate to their own truncation mass, and what is
+// left is analytic, [Phi(t_j+1 - u) - Phi(t_j - u)] / [Phi(T - u) - Phi(-u)] per sample and bin.  Three launches:
+//   kde_project_prep     one lane per sample row: u = c / sqrt(log2(e) / 2) and the reciprocal mass in f64 (0 for a row outside the
+//                        domain) into scratch, once per sample instead of once per lane below; the in-domain count
+//   kde_project_kernel   the pair kernel's shape: one lane per bin, the samples wave-uniform (scalar loads of u and the
+//                        reciprocal mass), split across workgroups (blockIdx.y) so that a hundred bins fill the card
+//   kde_project_combine  per bin the partials in split order, over the count
+// f64 throughout, Phi through erfc as kde_prepass and kde_sample write it; no floating-point atomics.
+namespace {
+
+__global__ __launch_bounds__(kKdeBlock) void kde_project_prep_kernel(const float* __restrict__ rows,
+                                                                     const SxKdeProjectArgs a,
+                                                                     double* __restrict__ scratch,
+                                                                     unsigned* __restrict__ count) {
+  const unsigned long long i = (unsigned long long)blockIdx.x * kKdeBlock + threadIdx.x;
+  unsigned in = 0u;
+  if (i < a.npad) {
+    const float* row = rows + i * (unsigned long long)(a.D + 1);
+    double u = 0.0, inv = 0.0;
+    if (row[a.D] > 0.0f) {
+      in = 1u;
+      u = (double)row[a.obs] / a.cunit;
+      const double T = (a.upper - a.lower) / a.h;
+      inv = 1.0 / (kde_phi(T - u) - kde_phi(-u));
+    }
+    scratch[2ull * i] = u;
+    scratch[2ull * i + 1ull] = inv;
+  }
+  // (every lane of the wave gets here)
+#pragma unroll
+  for (int off = kWave / 2; off > 0; off >>= 1) in += __shfl_down(in, off, kWave);
+  if ((threadIdx.x & (kWave - 1)) == 0 && in != 0u) {
+    __hip_atomic_fetch_add(count, in, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+  }
+}
+
+// edge j of nbins equal bins as a distance from lower in bandwidths; the two ends are lower and upper themselves
+__device__ __forceinline__ double kde_project_edge(const SxKdeProjectArgs& a, unsigned long long j) {
+  if (j == 0ull) return 0.0;
+  if (j >= (unsigned long long)a.nbins) return (a.upper - a.lower) / a.h;
+  const double e = a.lower + (double)j * ((a.upper - a.lower) / (double)a.nbins);
+  return (e - a.lower) / a.h;
+}
+
+__global__ __launch_bounds__(SXMC_KDE_PROJ_LANES) void kde_project_kernel(const SxKdeProjectArgs a,
+                                                                          const double* __restrict__ scratch,
+                                                                          double* __restrict__ part) {
+  const unsigned long long lane = (unsigned long long)blockIdx.x * SXMC_KDE_PROJ_LANES + threadIdx.x;
+  // lanes past the last bin do the last bin's work (uniform trip count; their partial is never read)
+  const unsigned long long j = lane < (unsigned long long)a.nbins ? lane : (unsigned long long)a.nbins - 1ull;
+  const double t0 = kde_project_edge(a, j), t1 = kde_project_edge(a, j + 1ull);
+  const unsigned long long r0 = (unsigned long long)blockIdx.y * a.rows_per_split;
+  const unsigned long long r1 = r0 + a.rows_per_split < a.npad ? r0 + a.rows_per_split : a.npad;
+  double sum = 0.0;
+  for (unsigned long long i = r0; i < r1; i++) {
+    const double u = scratch[2ull * i];
+    const double inv = scratch[2ull * i + 1ull];
+    if (inv == 0.0) continue;   // (wave-uniform: a row outside the domain)
+    sum += (kde_phi(t1 - u) - kde_phi(t0 - u)) * inv;
+  }
+  part[(unsigned long long)blockIdx.y * a.pitch + lane] = sum;
+}
+
+__global__ __launch_bounds__(kKdeBlock) void kde_project_combine_kernel(const SxKdeProjectArgs a,
+                                                                        const double* __restrict__ part,
+                                                                        const unsigned* __restrict__ count,
+                                                                        double* __restrict__ prob) {
+  const unsigned long long j = (unsigned long long)blockIdx.x * kKdeBlock + threadIdx.x;
+  if (j >= (unsigned long long)a.nbins) return;
+  double s = 0.0;
+  for (unsigned k = 0; k < a.nsplit; k++) s += part[(unsigned long long)k * a.pitch + j];
+  const unsigned n = *count;
+  prob[j] = n == 0u ? 0.0 : s / (double)n;
+}
+
+}  // namespace
+
+hipError_t sx_kde_project(const float* rows, const SxKdeProjectArgs& a, double* scratch, unsigned* count, double* d_prob,
+                          hipStream_t s) {
+  if (a.nbins < 1 || a.npad == 0 || a.obs < 0 || a.obs >= a.D || a.rows_per_split == 0 ||
+      (unsigned long long)a.nsplit * a.rows_per_split < a.npad || a.pitch % SXMC_KDE_PROJ_LANES != 0 ||
+      a.pitch < (unsigned long long)a.nbins) {
+    return hipErrorInvalidValue;
+  }
+  double* part = scratch + 2ull * a.npad;
+  hipLaunchKernelGGL(kde_project_prep_kernel, dim3((unsigned)((a.npad + kKdeBlock - 1) / kKdeBlock)), dim3(kKdeBlock), 0,
+                     s, rows, a, scratch, count);
+  hipError_t e = hipGetLastError();
+  if (e != hipSuccess) return e;
+  hipLaunchKernelGGL(kde_project_kernel, dim3((unsigned)(a.pitch / SXMC_KDE_PROJ_LANES), a.nsplit),
+                     dim3(SXMC_KDE_PROJ_LANES), 0, s, a, scratch, part);
+  e = hipGetLastError();
+  if (e != hipSuccess) return e;
+  hipLaunchKernelGGL(kde_project_combine_kernel, dim3((unsigned)(((unsigned long long)a.nbins + kKdeBlock - 1) / kKdeBlock)),
+                     dim3(kKdeBlock), 0, s, a, part, count, d_prob);
   return hipGetLastError();
 }

@@ -186,6 +186,9 @@ hipError_t sx_random_sample(const unsigned* d_cdf, int nbins_total, int nobs, co
                             const double* upper, const double* scale, const float* cut_lo, const float* cut_hi,
                             unsigned long long seed, unsigned long long n, float dataset, float* d_out,
                             unsigned* d_exhausted, hipStream_t s);
+// the marginal of a histogram along one observable (project_kernels.hip): d_out[0 .. nb) 64-bit totals, zero on entry
+hipError_t sx_hist_project(const unsigned* d_bins, unsigned long long total, unsigned stride, unsigned nb,
+                           unsigned long long* d_out, unsigned max_blocks, hipStream_t s);
 hipError_t sx_launch_eval_pdf(const SxSignalDesc* d_descs, int nsig, unsigned long long max_points,
                               hipStream_t s);
 hipError_t sx_launch_eval_nll(const SxSignalDesc* d_descs, int nsig, unsigned long long npoints,
@@ -241,3 +244,19 @@ hipError_t sx_inclusive_sum_u32(const unsigned* d_in, unsigned* d_out, int n, vo
 hipError_t sx_kde_sample(int D, const float* rows, const unsigned* idx, unsigned n, const SxKdeSampleArgs& g,
                          unsigned long long seed, unsigned long long nevents, float* out, unsigned* exhausted,
                          hipStream_t s);
+// Projection onto one observable (sxmc_kde_project; the arithmetic is written out in include/sxmc_hip.h).  scratch:
+// [2 npad] doubles (u and the reciprocal mass of every sample row), then [nsplit][pitch] partial sums, pitch = the bins
+// rounded up to SXMC_KDE_PROJ_LANES; count: the in-domain rows, zero on entry.  rows_per_split sample rows to a
+// workgroup, whatever the device, and the splits are added in their order: the same bits everywhere.
+#define SXMC_KDE_PROJ_LANES 64
+struct SxKdeProjectArgs {
+  int D, obs, nbins;
+  unsigned long long npad;
+  unsigned rows_per_split, nsplit;
+  unsigned long long pitch;
+  double lower, upper;      // of the observable
+  double h;                 // its bandwidth
+  double cunit;             // sqrt(log2(e) / 2): a row's coordinate is (s - lower) / h times this
+};
+hipError_t sx_kde_project(const float* rows, const SxKdeProjectArgs& a, double* scratch, unsigned* count, double* d_prob,
+                          hipStream_t s);

@@ -393,6 +393,7 @@ int sxmc_hist_destroy(sxmc_hist_t h) {
   for (void* p : h->retired) (void)hipFree(p);
   if (h->d_cdf) (void)hipFree(h->d_cdf);
   if (h->d_sample) (void)hipFree(h->d_sample);
+  if (h->d_marginal) (void)hipFree(h->d_marginal);
   free_sparse(h);
   if (h->stream) (void)hipStreamDestroy(h->stream);
   delete h;
@@ -620,6 +621,34 @@ int sxmc_hist_get_bins(sxmc_hist_t h, unsigned* out, size_t n) {
                 "sxmc_group_finish_step_async cleared it): evaluate with do_eval_pdf = 0");
   }
   SX_HIP(hipMemcpy(out, h->d_bins, sizeof(unsigned) * n, hipMemcpyDeviceToHost));
+  return SXMC_OK;
+}
+int sxmc_hist_project(sxmc_hist_t h, int obs, unsigned long long* h_counts, size_t n) {
+  SX_FLUSH();
+  SX_REQUIRE(h && h_counts, "null argument");
+  SX_REQUIRE(obs >= 0 && obs < h->nobs, "no such observable to project onto");
+  SX_REQUIRE(n == (size_t)h->nbins[(size_t)obs], "projection buffer size mismatch");
+  if (!h->bins_valid) {
+    return fail(SXMC_ERR_STATE,
+                "the histogram is not filled (the last evaluation counted only the event bins, or "
+                "sxmc_group_finish_step_async cleared it): evaluate with do_eval_pdf = 0");
+  }
+  if (n == 0) return SXMC_OK;
+  if (n > h->cap_marginal) {
+    SX_HIP(hipStreamSynchronize(h->stream));   // (allocation next to queued work: settle it first)
+    if (h->d_marginal) SX_HIP(hipFree(h->d_marginal));
+    h->d_marginal = nullptr;
+    h->cap_marginal = 0;
+    SX_HIP(hipMalloc((void**)&h->d_marginal, sizeof(unsigned long long) * n));
+    h->cap_marginal = n;
+  }
+  DeviceProps props;
+  const unsigned cus = get_props(props) == SXMC_OK && props.cus > 0 ? (unsigned)props.cus : 256u;
+  SX_HIP(hipMemsetAsync(h->d_marginal, 0, sizeof(unsigned long long) * n, h->stream));
+  SX_HIP(sx_hist_project(h->d_bins, (unsigned long long)h->total_nbins, (unsigned)h->stride[(size_t)obs], (unsigned)n,
+                         h->d_marginal, cus * 8u, h->stream));
+  SX_HIP(hipMemcpyAsync(h_counts, h->d_marginal, sizeof(unsigned long long) * n, hipMemcpyDeviceToHost, h->stream));
+  SX_HIP(hipStreamSynchronize(h->stream));
   return SXMC_OK;
 }
 int sxmc_hist_get_read_bins(sxmc_hist_t h, int* out, size_t n) {

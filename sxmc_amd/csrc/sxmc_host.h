@@ -232,6 +232,8 @@ struct sxmc_hist {
   unsigned* d_cdf = nullptr;       // prefix sums of the histogram, for sxmc_hist_random_sample
   float* d_sample = nullptr;       // ... and the events drawn, a kernel-density evaluator's too (sxhost::sample_buffer;
   size_t cap_sample = 0;           // grow-only: a fake experiment per walk draws about as many), bytes
+  unsigned long long* d_marginal = nullptr;   // sxmc_hist_project's totals along one observable (grow-only)
+  size_t cap_marginal = 0;
   bool has_points = false;
   size_t npoints = 0;
   float* pdf = nullptr;

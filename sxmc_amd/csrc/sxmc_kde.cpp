@@ -42,6 +42,9 @@ struct sxmc_kde {
                                    // in-domain row numbers (one allocation, made at the first draw)
   void* d_scan_temp = nullptr;
   size_t scan_temp_bytes = 0;
+  // projection (sxmc_kde_project): per-row scratch, partial sums, the result and the in-domain count (grow-only)
+  double* d_proj = nullptr;
+  size_t cap_proj = 0;             // doubles
 };
 
 namespace {
@@ -195,6 +198,7 @@ int sxmc_kde_destroy(sxmc_kde_t k) {
   if (k->h && k->h->stream) (void)hipStreamSynchronize(k->h->stream);
   if (k->d_flag) (void)hipFree(k->d_flag);
   if (k->d_scan_temp) (void)hipFree(k->d_scan_temp);
+  if (k->d_proj) (void)hipFree(k->d_proj);
   if (k->d_rows) (void)hipFree(k->d_rows);
   if (k->d_pts) (void)hipFree(k->d_pts);
   if (k->d_codes) (void)hipFree(k->d_codes);
@@ -448,6 +452,49 @@ int sxmc_kde_random_sample(sxmc_kde_t k, size_t nobserved, unsigned long long se
   SX_HIP(sx_kde_sample(D, k->d_rows, idx, n, g, seed, nobserved, d_out, d_exhausted, k->h->stream));
   return sample_read_back(k->h, nobserved, row, ": the cuts leave (almost) none of the kernel-density PDF's mass",
                           h_events);
+}
+
+int sxmc_kde_project(sxmc_kde_t k, int obs, int nbins, double* h_prob) {
+  SX_REQUIRE(k && h_prob, "null argument");
+  SX_REQUIRE(obs >= 0 && obs < k->D, "EvalKernel: no such observable to project onto");
+  SX_REQUIRE(nbins >= 1, "EvalKernel: a projection needs at least one bin");
+  if (!k->evaluated) {
+    return fail(SXMC_ERR_STATE, "EvalKernel: nothing to project before an evaluation (EvalAsync first)");
+  }
+  SxKdeProjectArgs a;
+  std::memset(&a, 0, sizeof a);
+  a.D = k->D;
+  a.obs = obs;
+  a.nbins = nbins;
+  a.npad = k->npad;
+  // the sample rows are cut the same way on every device: at most 1024 splits of whole tiles
+  const unsigned long long tile = SXMC_KDE_TILE;
+  a.rows_per_split = (unsigned)(((k->npad + 1023) / 1024 + tile - 1) / tile * tile);
+  a.nsplit = (unsigned)((k->npad + a.rows_per_split - 1) / a.rows_per_split);
+  a.pitch = ((unsigned long long)nbins + SXMC_KDE_PROJ_LANES - 1) / SXMC_KDE_PROJ_LANES * SXMC_KDE_PROJ_LANES;
+  a.lower = k->h->lower[(size_t)obs];
+  a.upper = k->h->upper[(size_t)obs];
+  a.h = k->bw[obs];
+  a.cunit = kLog2eHalfSqrt;
+  const hipStream_t s = k->h->stream;
+  // [2 npad] per-row scratch, [nsplit][pitch] partials, [nbins] result, the count
+  const size_t off_prob = 2 * k->npad + (size_t)a.nsplit * a.pitch;
+  const size_t need = off_prob + (size_t)nbins + 1;
+  if (need > k->cap_proj) {
+    SX_HIP(hipStreamSynchronize(s));   // (allocation next to queued work: settle it first)
+    if (k->d_proj) SX_HIP(hipFree(k->d_proj));
+    k->d_proj = nullptr;
+    k->cap_proj = 0;
+    SX_HIP(hipMalloc((void**)&k->d_proj, sizeof(double) * need));
+    k->cap_proj = need;
+  }
+  double* d_prob = k->d_proj + off_prob;
+  unsigned* d_count = reinterpret_cast<unsigned*>(d_prob + nbins);
+  SX_HIP(hipMemsetAsync(d_count, 0, sizeof(unsigned), s));
+  SX_HIP(sx_kde_project(k->d_rows, a, k->d_proj, d_count, d_prob, s));
+  SX_HIP(hipMemcpyAsync(h_prob, d_prob, sizeof(double) * (size_t)nbins, hipMemcpyDeviceToHost, s));
+  SX_HIP(hipStreamSynchronize(s));
+  return SXMC_OK;
 }
 
 }  // extern "C"

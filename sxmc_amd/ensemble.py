@@ -439,3 +439,69 @@ def run_experiments_concurrently(workload, seeds, nsteps, chains, burnin_fractio
         chain, accepted = m.walk_end()
         out.append((contour_intervals(chain, cl), chain, accepted))
     return out
+
+
+# ------------------------------------------------------------------------------------ fit spectra
+def data_histogram(x, lower, upper, bins):
+    """TH1::Fill over one observable's values (TAxis::FindBin): an event with lower <= x < upper goes to bin
+    int(bins * (x - lower) / (upper - lower)), in f64 on the float; under- and overflow are not counted (nor is a value
+    whose quotient rounds up to `bins`: ROOT's overflow bin).  int64 [bins]."""
+    x = np.asarray(x, np.float32).astype(np.float64)
+    x = x[(x >= lower) & (x < upper)]
+    idx = (bins * (x - lower) / (upper - lower)).astype(np.int64)
+    return np.bincount(idx[idx < bins], minlength=bins).astype(np.int64)
+
+
+def fit_spectra(workload, evaluators, params, events):
+    """plot_fit without ROOT (plots.cpp:150-302): every signal's PDF at `params` (the P parameter values to show -- the
+    intervals' point estimates -- held as floats, as there), scaled to its fitted number of events and projected onto
+    each observable; their sum per data set ("fit"); the data histogrammed beside them.
+
+    Per signal (plots.cpp:205-227): parameters (double)(float)params[p] bound at offset nsources, EvalAsync(False),
+    eff = norm / n_mc, nexp = nexpected * eff * params[source], then per observable spectrum = Project(...) * nexp --
+    for a histogram signal counts * (nexp / sum of counts), TH1::Scale's arithmetic, computed from the integers;
+    all zeros when the PDF is empty.  The projections are made on the device (pdfz.EvalHist.ProjectCounts,
+    pdfz.EvalKernel.Project): no histogram is copied to the host.  Leaves the evaluators bound to scratch buffers.
+    events: rows of nobs + 1 floats (last = dataset id).
+
+    Returns a list, data sets ascending and per data set the observables in order, of dicts: observable (name),
+    dataset, lower, upper, bins, signals [{name, nexp, spectrum}] (that data set's, in signal order), fit, data."""
+    w = workload
+    pf = np.asarray(params, np.float32).reshape(-1)
+    if pf.size != w.nparameters:
+        raise ValueError("fit_spectra: %d parameter values for %d parameters" % (pf.size, w.nparameters))
+    pbuf = DeviceArray(pf.astype(np.float64))
+    nbuf = DeviceArray.zeros(len(evaluators), np.uint32)
+    names = getattr(w, "observable_names", None) or ["obs%d" % k for k in range(w.nobs)]
+    per_signal = []
+    for i, (sig, ev) in enumerate(zip(w.signals, evaluators)):
+        ev.SetParameterBuffer(pbuf, w.nsources)
+        ev.SetNormalizationBuffer(nbuf, i)
+        ev.EvalAsync(False)
+        ev.EvalFinished()
+        eff = float(nbuf.get()[i]) / float(sig.n_mc)
+        nexp = sig.nexpected * eff * float(pf[sig.source_id])
+        spectra = []
+        for k in range(w.nobs):
+            if isinstance(ev, pdfz.EvalHist):
+                counts = ev.ProjectCounts(k)
+                total = int(counts.sum())
+                spectra.append(counts.astype(np.float64) * (nexp / float(total)) if total else np.zeros(counts.size))
+            else:
+                spectra.append(ev.Project(k, w.nbins[k]) * nexp)
+        per_signal.append(dict(name=getattr(sig, "name", "signal%d" % i), nexp=float(nexp), spectra=spectra))
+    events = np.asarray(events, np.float32).reshape(-1, w.nobs + 1)
+    out = []
+    for ds in sorted({int(s.dataset) for s in w.signals}):
+        mine = [p for p, s in zip(per_signal, w.signals) if int(s.dataset) == ds]
+        rows = events[events[:, w.nobs].astype(np.int64) == ds]
+        for k in range(w.nobs):
+            fit = np.zeros(int(w.nbins[k]))
+            for p in mine:
+                fit = fit + p["spectra"][k]
+            out.append(dict(observable=names[k], dataset=ds, lower=float(w.lower[k]), upper=float(w.upper[k]),
+                            bins=int(w.nbins[k]),
+                            signals=[dict(name=p["name"], nexp=p["nexp"], spectrum=p["spectra"][k]) for p in mine],
+                            fit=fit, data=data_histogram(rows[:, k], float(w.lower[k]), float(w.upper[k]),
+                                                         int(w.nbins[k]))))
+    return out

@@ -6,7 +6,7 @@
 // thin layer over the C ABI of libsxmc_hip.so (include/sxmc_hip.h); the arithmetic runs in
 // hand-written gfx950 kernels.  Differences, all forced by what is absent here:
 //   * ROOT-returning methods (CreateHistogram, CreateHistogramProjection, DefaultHistogram,
-//     RandomSample) are replaced by plain-array accessors (GetBins, GetNormalizedHistogram);
+//     RandomSample) are replaced by plain-array accessors (GetBins, GetNormalizedHistogram, Project, SampleEvents);
 //   * Optimize/OptimizeBin/OptimizeEval (brute-force launch autotuning, pdfz.cpp:622-814): the constructor's
 //     `optimize` flag and Optimize() keep their meaning -- trial launches at the first evaluation with evaluation
 //     points -- but the trials are those of the BATCH the library forms behind the per-evaluator calls
@@ -126,6 +126,12 @@ class Eval {
   /** A new evaluator of the same kind over the SAME sample table (the SharedSamples constructors); the caller
    *  deletes it. */
   virtual Eval* Share() const = 0;
+  /** The share of the PDF of the last evaluation in each of `nbins` equal bins of observable `obs` (what
+   *  CreateHistogramProjection, pdfz.h:505-518, hands to plot_fit, normalised): the shares sum to 1, or are all 0 when
+   *  the norm is 0.  Computed on the device; the evaluation's results stay as they are. */
+  virtual std::vector<double> Project(int /*obs*/, int /*nbins*/) {
+    throw Error("Project is not implemented by this evaluator");
+  }
 
  protected:
   int nfields;
@@ -279,8 +285,9 @@ class EvalHist : public detail::EvalOver<detail::HistApi> {
                               lower.size(), upper.data(), upper.size(), nbins.data(), nbins.size(), dataset,
                               &handle));
     throw_on(sxmc_hist_set_optimize(handle, optimize ? 1 : 0));   // needs_optimization(optimize), pdfz.cpp:188
+    axis_nbins = nbins;
   }
-  EvalHist(const EvalHist& base, SharedSamples s) : EvalOver(base, s) {}
+  EvalHist(const EvalHist& base, SharedSamples s) : EvalOver(base, s), axis_nbins(base.axis_nbins) {}
   Eval* Share() const override { return new EvalHist(*this, SharedSamples{}); }
 
   /** pdfz.cpp:622-628: trial launches choose the launch shape -- here at the next lookup evaluation of the batch this
@@ -315,6 +322,30 @@ class EvalHist : public detail::EvalOver<detail::HistApi> {
     return out;
   }
 
+  /** The bins of the last evaluation summed over every observable but `obs`, on the device (sxmc_hist_project): exact
+   *  integers, and only the marginal is copied to the host. */
+  std::vector<unsigned long long> ProjectCounts(int obs) {
+    if (obs < 0 || obs >= nobservables) throw Error("no such observable to project onto");
+    std::vector<unsigned long long> out((size_t)axis_nbins[(size_t)obs], 0ull);
+    throw_on(sxmc_hist_project(handle, obs, out.data(), out.size()));
+    return out;
+  }
+
+  /** counts / sum of counts along `obs`; nbins must be the evaluator's own bin count there. */
+  std::vector<double> Project(int obs, int nbins) override {
+    if (obs < 0 || obs >= nobservables || nbins != axis_nbins[(size_t)obs]) {
+      throw Error("EvalHist projects onto its own bins: " + std::to_string(nbins) + " asked along observable " +
+                  std::to_string(obs));
+    }
+    const std::vector<unsigned long long> counts = ProjectCounts(obs);
+    unsigned long long total = 0;
+    for (unsigned long long c : counts) total += c;
+    std::vector<double> out(counts.size(), 0.0);
+    if (total > 0)
+      for (size_t j = 0; j < counts.size(); j++) out[j] = (double)counts[j] / (double)total;
+    return out;
+  }
+
   /** ROOT-free CreateHistogram (pdfz.cpp:498-594): fill only (EvalAsync(false)), then
    *  content = bins / bin_volume / norm, or 0 when norm == 0; row-major. */
   std::vector<double> GetNormalizedHistogram() {
@@ -329,6 +360,9 @@ class EvalHist : public detail::EvalOver<detail::HistApi> {
       for (size_t i = 0; i < bins.size(); i++) out[i] = bins[i] / vol / norm;
     return out;
   }
+
+ protected:
+  std::vector<int> axis_nbins;   //!< bins per observable, as constructed
 };
 
 /** pdfz::EvalKernel (pdfz.h:578-625; declared by the reference, implemented here): the kernel-density PDF, the unbinned
@@ -377,6 +411,15 @@ class EvalKernel : public detail::EvalOver<detail::KernelApi> {
     std::vector<double> h((size_t)nobservables);
     throw_on(sxmc_kde_bandwidths(handle, h.data(), h.size()));
     return h;
+  }
+
+  /** sxmc_kde_project: per bin the analytic integral of every in-domain sample's truncated Gaussian, in f64; two
+   *  calls give the same bits. */
+  std::vector<double> Project(int obs, int nbins) override {
+    std::vector<double> out((size_t)(nbins > 0 ? nbins : 0), 0.0);
+    double none = 0.0;
+    throw_on(sxmc_kde_project(handle, obs, nbins, out.empty() ? &none : out.data()));
+    return out;
   }
 };
 

@@ -281,6 +281,7 @@ def build_workload(fc):
     w.source_means = [float(s["mean"]) for s in fc.sources]
     w.source_sigmas = [float(s["sigma"]) for s in fc.sources]
     w.syst_means = [x for s in fc.systematics for x in s["means"]]
+    w.observable_names = [fc.observables[i]["name"] for i in order]
     w.parameter_names = [s["name"] for s in fc.sources] + \
         ["%s_%d" % (s["name"], j) for s in fc.systematics for j in range(s["npars"])] + ["likelihood"]
     nsrc = len(fc.sources)
@@ -315,10 +316,43 @@ def write_chain(path, names, chain):
     np.savez(path, **{n: np.asarray(chain)[:, i] for i, n in enumerate(names)})
 
 
-def run_config(path, out_dir=None, nexperiments=None, nsteps=None, report=None):
+def _g17(v):
+    return "%.17g" % float(v)
+
+
+def write_fit_spectra(directory, spectra):
+    """The result of ensemble.fit_spectra as one <observable name>_<dataset>.json per observable and data set in
+    `directory` (created if missing) -- the file names of plot_fit (plots.cpp:297-299).  Each file is one object:
+      observable, dataset, lower, upper, bins
+      signals: [{name, nexp, spectrum: [bins numbers]}]   that data set's signals, in signal order
+      fit: [bins numbers]      their sum
+      data: [bins integers]    the data set's events, histogrammed
+    Numbers are printed with 17 significant digits, so a double survives the round trip.  Returns the paths."""
+    os.makedirs(directory, exist_ok=True)
+    paths = []
+    for sp in spectra:
+        def arr(v):
+            return "[" + ", ".join(_g17(x) for x in v) + "]"
+        sigs = ",\n    ".join('{"name": %s, "nexp": %s, "spectrum": %s}'
+                              % (json.dumps(str(g["name"])), _g17(g["nexp"]), arr(g["spectrum"])) for g in sp["signals"])
+        text = ('{\n  "observable": %s,\n  "dataset": %d,\n  "lower": %s,\n  "upper": %s,\n  "bins": %d,\n'
+                '  "signals": [\n    %s\n  ],\n  "fit": %s,\n  "data": [%s]\n}\n'
+                % (json.dumps(str(sp["observable"])), int(sp["dataset"]), _g17(sp["lower"]), _g17(sp["upper"]),
+                   int(sp["bins"]), sigs, arr(sp["fit"]), ", ".join(str(int(c)) for c in sp["data"])))
+        path = os.path.join(directory, "%s_%d.json" % (sp["observable"], int(sp["dataset"])))
+        with open(path, "w") as f:
+            f.write(text)
+        paths.append(path)
+    return paths
+
+
+def run_config(path, out_dir=None, nexperiments=None, nsteps=None, report=None, spectra_dir=None):
     """ensemble() of sxmc.cpp:44-145 for a config in the reference's schema: per experiment fake data
     (or the configured data sets), MCMC, contour intervals; chains written as <prefix>_<i>.npz.
     report: a text stream that receives, per experiment, what sxmc.cpp:100-101 prints (best fit + correlation matrix).
+    spectra_dir: when given, experiment i's fit spectra at its point estimates (ensemble.fit_spectra: plot_fit,
+    sxmc.cpp:104-107) are written to spectra_dir/<i>/ (write_fit_spectra); nothing is written otherwise, whatever the
+    configuration's "plots" key says.
     Returns (intervals [nexp, P, 4], limits of fit.signal_name, parameter names)."""
     from . import ensemble
 
@@ -365,4 +399,6 @@ def run_config(path, out_dir=None, nexperiments=None, nsteps=None, report=None):
             limits.append(float(iv[w.parameter_names.index(fc.signal_name), 2]))
         if out_dir:
             write_chain(os.path.join(out_dir, "%s_%d.npz" % (fc.output_prefix, i)), w.parameter_names, chain)
+        if spectra_dir:
+            write_fit_spectra(os.path.join(spectra_dir, str(i)), ensemble.fit_spectra(w, m.pdfs, iv[:, 0], events))
     return np.array(allint), limits, w.parameter_names

@@ -4,7 +4,7 @@ Same class names, method names, argument order and error behaviour as pdfz::Eval
 pdfz::EvalHist (pdfz.h:246-574): constructor validation raises `Error` where the reference
 throws pdfz::Error; buffers are device arrays (capi.DeviceArray, or anything with data_ptr());
 EvalAsync returns before completion and EvalFinished waits.  ROOT-returning methods
-(CreateHistogram, RandomSample) are replaced by plain-array accessors (GetBins).
+(CreateHistogram, CreateHistogramProjection, RandomSample) are replaced by plain-array accessors (GetBins, Project).
 """
 import ctypes as C
 
@@ -149,6 +149,12 @@ class _Eval:
     def Optimize(self):
         pass
 
+    def Project(self, obs, nbins):
+        """The share of the PDF of the last evaluation in each of `nbins` equal bins of observable `obs` (float64; sums
+        to 1, or all 0 when the norm is 0) -- CreateHistogramProjection (pdfz.h:505-518) without ROOT, computed on the
+        device."""
+        raise Error("Project is not implemented by this evaluator")
+
     def RandomSample(self, nobserved, seed, lowers=None, uppers=None):
         """EvalHist::RandomSample's sampling step on the device (pdfz.cpp:817-922): nobserved events drawn from the
         PDF of the last evaluation -- a histogram's bins (EvalAsync(False) first) or a kernel density's moved samples
@@ -193,12 +199,33 @@ class EvalHist(_Eval):
     def __init__(self, samples, nfields, nobservables, lower, upper, nbins, dataset=0, optimize=True):
         nbins = np.ascontiguousarray(nbins, dtype=np.int32)
         self._create(capi.load().sxmc_hist_create, samples, nfields, nobservables, lower, upper, nbins, dataset)
+        self._nbins = [int(b) for b in nbins]
 
     @classmethod
     def Shared(cls, base):
         self = super().Shared(base)
         self._keep["base"] = base
+        self._nbins = list(base._nbins)
         return self
+
+    def ProjectCounts(self, obs):
+        """The bins of the last evaluation summed over every observable but `obs` (uint64, exact), on the device:
+        only the marginal comes back (sxmc_hist_project)."""
+        obs = int(obs)
+        if not 0 <= obs < self.nobservables:
+            raise Error("no such observable to project onto")
+        out = np.zeros(self._nbins[obs], dtype=np.uint64)
+        self._call("project", obs, capi.ptr(out), out.size)
+        return out
+
+    def Project(self, obs, nbins):
+        """counts / sum of counts along `obs`; nbins must be the evaluator's own bin count there."""
+        if not 0 <= int(obs) < self.nobservables or int(nbins) != self._nbins[int(obs)]:
+            raise Error("EvalHist projects onto its own bins: observable %d has %s, not %d"
+                        % (obs, self._nbins[int(obs)] if 0 <= int(obs) < self.nobservables else "no bins", nbins))
+        counts = self.ProjectCounts(obs)
+        total = int(counts.sum())
+        return counts / float(total) if total else np.zeros(counts.size)
 
     # -- replaces Optimize*: analytic launch sizing, optionally overridden -------------------
     def SetLaunchConfig(self, bin_threads=0, bin_blocks_per_cu=0):
@@ -251,3 +278,9 @@ class EvalKernel(_Eval):
     def SamplePool(self):
         """How many samples the last evaluation left inside the domain, as the sampler counts them (= the norm)."""
         return self._get("sample_pool", C.c_size_t)
+
+    def Project(self, obs, nbins):
+        """sxmc_kde_project: per bin the analytic integral of every in-domain sample's truncated Gaussian, in f64."""
+        out = np.zeros(max(int(nbins), 0), dtype=np.float64)
+        self._call("project", int(obs), int(nbins), capi.ptr(out))
+        return out

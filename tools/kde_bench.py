@@ -11,7 +11,11 @@ accumulate; the sample row comes through scalar loads as SGPR operands.  At the 
 the clock the device reports.  cpu_numpy_pairs_per_s: the same sum in numpy f64 on a subset of the points.
 ms_per_sample_call: host clock around RandomSample(--sample-events) from the last evaluation (compaction of the
 in-domain rows, the draw, the copy of the events to the host), median of 5 calls after one warm-up.
-Usage: python tools/kde_bench.py [--samples N] [--points E] [--seconds S] [--cpu-points K] [--sample-events M]"""
+ms_per_projection: host clock around one Project(obs, --project-bins) of the last evaluation (the per-row scratch, the
+sum over samples x bins, the combine, the copy of the shares to the host), both observables in turn, mean per call over
+a window of at least half of --seconds after one warm-up each.
+Usage: python tools/kde_bench.py [--samples N] [--points E] [--seconds S] [--cpu-points K] [--sample-events M]
+                                 [--project-bins B]"""
 import argparse
 import json
 import math
@@ -34,6 +38,7 @@ def main():
     ap.add_argument("--seconds", type=float, default=1.0)
     ap.add_argument("--cpu-points", type=int, default=200)
     ap.add_argument("--sample-events", type=int, default=1000000)
+    ap.add_argument("--project-bins", type=int, default=100)
     a = ap.parse_args()
     if capi.device_count() < 1:
         raise SystemExit("kde_bench.py needs a GPU")
@@ -83,6 +88,19 @@ def main():
     sample_ms = float(np.median(sample_ms))
     drawn_in_domain = bool(np.all((drawn[:, :D] >= lower) & (drawn[:, :D] < upper)))
 
+    # the projections of the last evaluation onto both observables
+    shares = [ev.Project(k, a.project_bins) for k in range(D)]
+    pcalls, p0 = 0, time.perf_counter()
+    while True:
+        for k in range(D):
+            shares[k] = ev.Project(k, a.project_bins)
+        pcalls += D
+        pel = time.perf_counter() - p0
+        if pel >= a.seconds / 2 and pcalls >= 3 * D:
+            break
+    projection_ms = 1e3 * pel / pcalls
+    projection_sums = [float(m.sum()) for m in shares]
+
     # numpy f64 on a subset of the points (the bandwidths as the evaluator fixed them, parameters applied)
     h = ev.Bandwidths()
     x = samples.astype(np.float64)
@@ -107,6 +125,8 @@ def main():
                           cpu_numpy_pairs_per_s=cpu_rate, norm=int(norm.get()[0]),
                           finite_values=int(np.isfinite(values).sum()), sample_events=a.sample_events,
                           ms_per_sample_call=round(sample_ms, 4), sampled_in_domain=drawn_in_domain,
+                          project_bins=a.project_bins, ms_per_projection=round(projection_ms, 4),
+                          projection_sums=projection_sums,
                           device=info["name"])))
 
 
