@@ -131,7 +131,7 @@ int flush_deferred() {
   // A plan with a boxed and an ordered form of the fill (sxmc_group_adapt_fill_form): the unchanged caller has no flush
   // to ask at, so its batches ask themselves -- the first one and every 256th after it wait for the batch's stream and
   // read the parameters back (a few hundred microseconds per 256 steps of ~100 us each).
-  if (m.size() >= 2 && g->cfg_box < 0 && (g->adapt_tick++ & 255u) == 0u) {
+  if (m.size() >= 2 && g->plan_cfg.box < 0 && (g->adapt_tick++ & 255u) == 0u) {
     int form = 0, changed = 0;
     g->last_stream = fl->stream;
     rc = sxmc_group_adapt_fill_form(g, &form, &changed);
@@ -140,8 +140,8 @@ int flush_deferred() {
   bool want = do_eval_pdf != 0;
   for (sxmc_hist* h : m) want = want && h->want_optimize && h->has_points;
   if (m.size() == 1 || m[0]->cfg_threads > 0 || m[0]->cfg_bpc > 0) {
-    g->cfg_threads = m[0]->cfg_threads;   // (a launch shape set by hand on the evaluators)
-    g->cfg_bpc = m[0]->cfg_bpc;
+    g->plan_cfg.threads = m[0]->cfg_threads;   // (a launch shape set by hand on the evaluators)
+    g->plan_cfg.bpc = m[0]->cfg_bpc;
   } else if (rc == SXMC_OK && m.size() >= 2 && !g->tuned && want) {
     g->tuned = true;
     rc = sxmc_group_optimize(g, fl->stream, nullptr);
@@ -514,8 +514,8 @@ int sxmc_hist_eval_async(sxmc_hist_t h, int do_eval_pdf) {
       int rc = sxmc_group_create(&h, 1, &h->self);
       if (rc) return rc;
     }
-    h->self->cfg_threads = h->cfg_threads;
-    h->self->cfg_bpc = h->cfg_bpc;
+    h->self->plan_cfg.threads = h->cfg_threads;
+    h->self->plan_cfg.bpc = h->cfg_bpc;
     h->inflight.reset();
     return sxmc_group_eval_async(h->self, do_eval_pdf, h->stream);
   }
@@ -722,8 +722,8 @@ int sxmc_hist_optimize(sxmc_hist_t h) {
   for (AutoGroup& a : g_auto_groups) {
     if (std::find(a.members.begin(), a.members.end(), h) != a.members.end()) {
       a.g->tuned = false;
-      a.g->cfg_threads = a.g->cfg_bpc = a.g->cfg_teams = 0;   // (what earlier trials chose)
-      a.g->cfg_codes = -1;
+      a.g->plan_cfg.threads = a.g->plan_cfg.bpc = a.g->plan_cfg.teams = 0;   // (what earlier trials chose)
+      a.g->plan_cfg.codes = -1;
     }
   }
   return SXMC_OK;

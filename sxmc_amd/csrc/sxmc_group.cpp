@@ -68,8 +68,8 @@ int sxmc_group_set_launch_config(sxmc_group_t g, int bin_threads, int bin_blocks
   SX_REQUIRE(bin_threads == 0 || (bin_threads >= 64 && bin_threads <= 1024 && bin_threads % 64 == 0),
              "bin_threads must be 0 or a multiple of 64 up to 1024");
   SX_REQUIRE(bin_blocks_per_cu >= 0 && bin_blocks_per_cu <= 16, "bin_blocks_per_cu out of range");
-  g->cfg_threads = bin_threads;
-  g->cfg_bpc = bin_blocks_per_cu;
+  g->plan_cfg.threads = bin_threads;
+  g->plan_cfg.bpc = bin_blocks_per_cu;
   return SXMC_OK;
 }
 
@@ -85,7 +85,7 @@ int sxmc_group_optimize(sxmc_group_t g, sxmc_stream_t s, int* chosen_threads) {
   if (rc) return rc;
   // only the pure-stream launches have anything to choose: how many lanes per CU keep HBM busiest differs
   // by a few per cent from one box to the next
-  if (g->classes.empty() || g->cfg_threads > 0 || g->cfg_bpc > 0) return SXMC_OK;
+  if (g->classes.empty() || g->plan_cfg.threads > 0 || g->plan_cfg.bpc > 0) return SXMC_OK;
   for (const LaunchClass& c : g->classes)
     if (!c.light) return SXMC_OK;
   hipStream_t st = (hipStream_t)s;
@@ -95,7 +95,7 @@ int sxmc_group_optimize(sxmc_group_t g, sxmc_stream_t s, int* chosen_threads) {
   // (over codes a lane has half the bytes per unit in flight: the larger shapes are the candidates there)
   bool has_codes = false;
   for (const LaunchClass& c : g->classes) has_codes = has_codes || c.codes;
-  // (threads, workgroups per CU; the first is what group_rebuild takes where nothing is asked for)
+  // (threads, workgroups per CU; the first is what class_codes_shape / class_waves_per_cu take where nothing is asked for)
   typedef std::pair<int, int> Shape;
   const std::vector<Shape> candidates =
       has_codes ? std::vector<Shape>{{512, 2}, {768, 1}, {1024, 1}, {896, 1}, {640, 1}}
@@ -121,8 +121,8 @@ int sxmc_group_optimize(sxmc_group_t g, sxmc_stream_t s, int* chosen_threads) {
   };
   for (const Shape& shape : candidates) {
     const int cand = shape.first;
-    g->cfg_threads = cand;
-    g->cfg_bpc = shape.second;
+    g->plan_cfg.threads = cand;
+    g->plan_cfg.bpc = shape.second;
     if ((failure = group_refresh(g)) != SXMC_OK) break;
     const float ms = timed_fill();
     if (failure != SXMC_OK) break;
@@ -134,34 +134,34 @@ int sxmc_group_optimize(sxmc_group_t g, sxmc_stream_t s, int* chosen_threads) {
   }
   // the default shape is what 0, 0 means: keep the configuration "automatic" when it won
   const bool is_auto = best_threads == candidates[0].first && best_bpc == candidates[0].second;
-  g->cfg_threads = (failure == SXMC_OK && !is_auto) ? best_threads : 0;
-  g->cfg_bpc = (failure == SXMC_OK && !is_auto) ? best_bpc : 0;
-  // second choice, for bucketed tables: one team of workgroups per member or three (see group_rebuild: which is
+  g->plan_cfg.threads = (failure == SXMC_OK && !is_auto) ? best_threads : 0;
+  g->plan_cfg.bpc = (failure == SXMC_OK && !is_auto) ? best_bpc : 0;
+  // second choice, for bucketed tables: one team of workgroups per member or three (see class_partition: which is
   // faster differs from box to box by ~3 % either way); three must win by 1.5 % to be taken
   bool has_bucketed = false;
   for (const LaunchClass& c : g->classes) has_bucketed = has_bucketed || ((c.shape.pre_width == 3 || c.shape.pre_width == 5 || c.shape.pre_width == 6) && c.shape.lds_hist);
-  if (failure == SXMC_OK && has_bucketed && g->cfg_teams == 0) {
+  if (failure == SXMC_OK && has_bucketed && g->plan_cfg.teams == 0) {
     float ms_of[2] = {best_ms, 1e30f};
     for (int pass = 0; pass < 2 && failure == SXMC_OK; pass++) {
-      g->cfg_teams = pass == 0 ? 0 : 3;
+      g->plan_cfg.teams = pass == 0 ? 0 : 3;
       if ((failure = group_refresh(g)) != SXMC_OK) break;
       const float ms = timed_fill();
       ms_of[pass] = ms;
     }
-    g->cfg_teams = (failure == SXMC_OK && ms_of[1] < 0.985f * ms_of[0]) ? 3 : 0;
+    g->plan_cfg.teams = (failure == SXMC_OK && ms_of[1] < 0.985f * ms_of[0]) ? 3 : 0;
   }
   // third choice, where the plan streams codes by default: the codes against the float columns, at the parameters
   // that are bound now.  Whether they pay was estimated from the binning (get_bucket_codes); this is the measurement:
   // the float stream is taken if it wins by 3 %.
-  if (failure == SXMC_OK && has_codes && g->cfg_codes < 0) {
+  if (failure == SXMC_OK && has_codes && g->plan_cfg.codes < 0) {
     float ms_of[2] = {1e30f, 1e30f};
     for (int pass = 0; pass < 2 && failure == SXMC_OK; pass++) {
-      g->cfg_codes = pass == 0 ? -1 : 0;
+      g->plan_cfg.codes = pass == 0 ? -1 : 0;
       if ((failure = group_refresh(g)) != SXMC_OK) break;
       const float ms = timed_fill();
       ms_of[pass] = ms;
     }
-    g->cfg_codes = (failure == SXMC_OK && ms_of[1] < 0.97f * ms_of[0]) ? 0 : -1;
+    g->plan_cfg.codes = (failure == SXMC_OK && ms_of[1] < 0.97f * ms_of[0]) ? 0 : -1;
   }
   (void)hipEventDestroy(e0);
   (void)hipEventDestroy(e1);
@@ -173,14 +173,14 @@ int sxmc_group_optimize(sxmc_group_t g, sxmc_stream_t s, int* chosen_threads) {
 int sxmc_group_set_partition_teams(sxmc_group_t g, int teams) {
   SX_REQUIRE(g, "null group");
   SX_REQUIRE(teams >= 0 && teams <= 64, "teams must be 0 (default: one) to 64");
-  g->cfg_teams = teams;
+  g->plan_cfg.teams = teams;
   return SXMC_OK;
 }
 
 int sxmc_group_set_partition(sxmc_group_t g, int mode) {
   SX_REQUIRE(g, "null group");
   SX_REQUIRE(mode >= 0 && mode <= 2, "partition mode must be 0 (auto), 1 (sliced) or 2 (interleaved)");
-  g->cfg_partition = mode;
+  g->plan_cfg.partition = mode;
   return SXMC_OK;
 }
 
@@ -192,25 +192,25 @@ int sxmc_group_set_sparse(sxmc_group_t g, int enable) {
 
 int sxmc_group_set_prebinning(sxmc_group_t g, int enable) {
   SX_REQUIRE(g, "null group");
-  g->cfg_prebin = enable ? 1 : 0;
+  g->plan_cfg.prebin = enable ? 1 : 0;
   return SXMC_OK;
 }
 
 int sxmc_group_set_bucketing(sxmc_group_t g, int enable) {
   SX_REQUIRE(g, "null group");
-  g->cfg_bucket = enable ? 1 : 0;
+  g->plan_cfg.bucket = enable ? 1 : 0;
   return SXMC_OK;
 }
 
 int sxmc_group_set_ordering(sxmc_group_t g, int enable) {
   SX_REQUIRE(g, "null group");
-  g->cfg_order = enable == 2 ? 2 : enable ? 1 : 0;
+  g->plan_cfg.order = enable == 2 ? 2 : enable ? 1 : 0;
   return SXMC_OK;
 }
 
 int sxmc_group_set_boxes(sxmc_group_t g, int enable) {
   SX_REQUIRE(g, "null group");
-  g->cfg_box = enable < 0 ? -1 : enable ? 1 : 0;
+  g->plan_cfg.box = enable < 0 ? -1 : enable ? 1 : 0;
   g->box_blocked = false;
   return SXMC_OK;
 }
@@ -226,7 +226,7 @@ int sxmc_group_set_fill_form(sxmc_group_t g, int form) {
   SX_FLUSH();
   int rc = group_refresh(g);
   if (rc) return rc;
-  SX_REQUIRE(g->twin && !g->twin->classes.empty() && g->cfg_box < 0, "the group's plan has one form only");
+  SX_REQUIRE(g->twin && !g->twin->classes.empty() && g->plan_cfg.box < 0, "the group's plan has one form only");
   g->fill_form = form;
   return SXMC_OK;
 }
@@ -291,7 +291,7 @@ int sxmc_group_adapt_fill_form(sxmc_group_t g, int* form, int* changed) {
   if (t_capturing) return fail(SXMC_ERR_STATE, "the form of the fill is not chosen while a graph is being recorded");
   int rc = group_refresh(g);
   if (rc) return rc;
-  if (!(g->twin && !g->twin->classes.empty() && g->cfg_box < 0)) return SXMC_OK;   // (one form only)
+  if (!(g->twin && !g->twin->classes.empty() && g->plan_cfg.box < 0)) return SXMC_OK;   // (one form only)
   SX_HIP(hipStreamSynchronize(g->last_stream));
   double width = HUGE_VAL;
   rc = box_image_width(g, &width);
@@ -309,13 +309,13 @@ int sxmc_group_fill_form(sxmc_group_t g, int* form) {
   SX_FLUSH();
   int rc = group_refresh(g);
   if (rc) return rc;
-  *form = (g->twin && !g->twin->classes.empty() && g->cfg_box < 0) ? g->fill_form : 0;
+  *form = (g->twin && !g->twin->classes.empty() && g->plan_cfg.box < 0) ? g->fill_form : 0;
   return SXMC_OK;
 }
 
 int sxmc_group_set_codes(sxmc_group_t g, int enable) {
   SX_REQUIRE(g, "null group");
-  g->cfg_codes = enable < 0 ? -1 : enable ? 1 : 0;
+  g->plan_cfg.codes = enable < 0 ? -1 : enable ? 1 : 0;
   return SXMC_OK;
 }
 
@@ -323,7 +323,7 @@ int sxmc_group_set_codes_queue_log(sxmc_group_t g, int log2_entries) {
   SX_REQUIRE(g, "null group");
   SX_REQUIRE(log2_entries == 0 || (log2_entries >= (int)kMinQueueLog && log2_entries <= 11),
              "the queues of ambiguous rows hold 2^9 .. 2^11 entries (0: as many as fit)");
-  g->cfg_queue_log = log2_entries;
+  g->plan_cfg.queue_log = log2_entries;
   return SXMC_OK;
 }
 
@@ -371,7 +371,7 @@ int sxmc_group_codes_windows(sxmc_group_t g, int member, int* nfields, double* b
 
 int sxmc_group_set_runtime_kernels(sxmc_group_t g, int enable) {
   SX_REQUIRE(g, "null group");
-  g->cfg_rtc = enable ? 1 : 0;
+  g->plan_cfg.rtc = enable ? 1 : 0;
   return SXMC_OK;
 }
 
@@ -381,20 +381,20 @@ int sxmc_group_launch_info(sxmc_group_t g, char* out, size_t n) {
   if (rc) return rc;
   std::string text;
   // (a plan with two forms: the launches of the form that runs now, its table named with the other form beside it)
-  const bool two = g->twin && !g->twin->classes.empty() && g->cfg_box < 0;
+  const bool two = g->twin && !g->twin->classes.empty() && g->plan_cfg.box < 0;
   const sxmc_group* plan = (two && g->fill_form == 2) ? g->twin : g;
   for (size_t i = 0; i < plan->classes.size(); i++) {
     const LaunchClass& c = plan->classes[i];
     char line[512];
     const char* kind = c.shape.rtc_fill ? "runtime" : c.shape.static_prog >= 0 ? "builtin" : c.shape.nobs ? "decoded" : "generic";
     std::snprintf(line, sizeof line,
-                  "launch %zu: members=%zu nobs=%d nslot=%d hist=%s program=%s table=%s%s threads=%d grid=%d partition=%d teams=%d\n",
+                  "launch %zu: members=%zu nobs=%d nslot=%d hist=%s program=%s table=%s%s threads=%d grid=%d partition=%d teams=%d lds=%zu layout=0x%08X\n",
                   i, c.member_idx.size(), c.shape.nobs, c.shape.nslot, c.shape.lds_hist ? "lds" : "global", kind,
                   c.shape.pre_width == 6 ? (c.dual ? "boxed+codes(now)|ordered+codes" : "boxed+codes")
                   : (two && plan == g->twin && c.shape.pre_width == 5) ? (c.codes ? "boxed+codes|ordered+codes(now)" : "boxed+codes|ordered(now)")
                   : c.shape.pre_width == 5 ? (c.codes ? "ordered+codes" : "ordered") : c.shape.pre_width == 3 ? "bucketed" : c.shape.pre_width ? "prebinned" : "rows",
                   c.runs_mode ? (c.shape.rtc_sparse ? "+runs(runtime)" : "+runs(builtin)") : "", c.shape.threads,
-                  c.shape.grid, c.partition, c.teams);
+                  c.shape.grid, c.partition, c.teams, (size_t)c.shape.lds_bytes, c.shape.lds_layout);
     text += line;
   }
   if (!g->rtc_note.empty()) text += "runtime specialisation failed: " + g->rtc_note.substr(0, 300) + "\n";
@@ -855,7 +855,7 @@ int sxmc_group_set_cooperative_step_end(sxmc_group_t g, int enable) {
 
 int sxmc_group_set_fused_step(sxmc_group_t g, int enable) {
   SX_REQUIRE(g, "null group");
-  g->cfg_fused = enable ? 1 : 0;
+  g->plan_cfg.fused = enable ? 1 : 0;
   return SXMC_OK;
 }
 
@@ -964,7 +964,7 @@ int sxmc_group_algorithmic_bytes(sxmc_group_t g, double* fill_read, double* hist
   SX_REQUIRE(g && fill_read && hist && event, "null argument");
   int rc = group_refresh(g);
   if (rc) return rc;
-  if (g->twin && !g->twin->classes.empty() && g->cfg_box < 0 && g->fill_form == 2) {
+  if (g->twin && !g->twin->classes.empty() && g->plan_cfg.box < 0 && g->fill_form == 2) {
     // (the ordered twin's tables are what the fill streams now; histogram and event bytes do not depend on the form)
     double fr2 = 0, hb2 = 0, ev2 = 0, fr1 = 0;
     rc = sxmc_group_algorithmic_bytes(g->twin, &fr2, &hb2, &ev2);

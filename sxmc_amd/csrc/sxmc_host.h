@@ -307,7 +307,7 @@ struct LaunchClass {
   unsigned* d_blk_off = nullptr;
   unsigned long long total_vec = 0;
   int partition = 0;  // 1 sliced, 2 interleaved (what build_partition chose)
-  bool light = false; // a pure stream: runs best with few waves per CU (see group_rebuild)
+  bool light = false; // a pure stream: runs best with few waves per CU (see class_waves_per_cu)
   bool runs_mode = false;  // bucketed tables laid out in per-wave runs; the sparse flavour runs fill_sparse_kernel
   int teams = 1;           // teams of workgroups per member over a bucketed table (sxplan::interleaved_segments)
   bool codes = false;      // ordered tables: the streamed columns go as 16-bit codes (fill_ordered_body's CODES)
@@ -315,10 +315,30 @@ struct LaunchClass {
   float box_dx = 0, box_dt = 0;   // ... mean extents of the members' granule boxes, what the choice is made from
   int box_obs = -1, box_truth = -1;   // ... the boxed observable and its truth field, as slots of the members' full descriptors
   unsigned padded_rstride = 0;  // ... with the LDS histogram in the padded form: words between its replicas (0: not)
-  unsigned plain_rstride = 0;   // ordered tables: words between the replicas of the LDS histogram in its swizzled form
+  int max_bins = 0;             // the largest histogram of the members
 };
 
 void free_class(LaunchClass& c);
+
+// The settings a group's launch plan depends on: a plan built with other values than these is out of date (group_refresh).
+struct PlanConfig {
+  int threads = 0, bpc = 0;   // launch shape set by hand (0: the plan's own)
+  int partition = 0;          // 0 auto, 1 sliced, 2 interleaved
+  int teams = 0;              // teams per member over a bucketed table (0 = 1, the default)
+  int prebin = 1;             // pre-bin the observables no systematic writes
+  int bucket = 1;             // stream a bucketed copy of the table where that pays
+  int order = 1;              // ... with the rows of a bucket ordered by a monotonically written observable
+  int box = -1;               // ... or grouped into boxes of a two-field observable (-1: where it pays, 1: wherever it applies)
+  int rtc = 1;                // specialise the fill kernel at run time for programs not built in
+  int codes = -1;             // ordered tables streamed as 16-bit codes (-1: SXMC_CODES, default on)
+  int queue_log = 0;          // ... cap on the queues of ambiguous rows, log2(entries) (0: what fits)
+  int fused = -1;             // the whole step in ONE launch where the fill has that form (-1: SXMC_FUSED_STEP, default OFF: measured slower)
+  bool operator==(const PlanConfig& o) const {
+    return threads == o.threads && bpc == o.bpc && partition == o.partition && teams == o.teams && prebin == o.prebin &&
+           bucket == o.bucket && order == o.order && box == o.box && rtc == o.rtc && codes == o.codes &&
+           queue_log == o.queue_log && fused == o.fused;
+  }
+};
 }  // namespace sxhost
 
 struct sxmc_group {
@@ -332,26 +352,16 @@ struct sxmc_group {
   int max_bins_sparse = 0;
   int cfg_sparse = 1;               // count only the event bins when evaluating for lookup
   std::vector<sxhost::LaunchClass> classes;
-  int cfg_threads = 0, cfg_bpc = 0;
-  int cfg_seen_threads = -1, cfg_seen_bpc = -1;
-  int cfg_partition = 0, cfg_seen_partition = -1;  // 0 auto, 1 sliced, 2 interleaved
-  int cfg_teams = 0, cfg_seen_teams = -1;          // teams per member over a bucketed table (0 = 1, the default)
-  int cfg_prebin = 1, cfg_seen_prebin = -1;        // pre-bin the observables no systematic writes
-  int cfg_bucket = 1, cfg_seen_bucket = -1;        // stream a bucketed copy of the table where that pays
+  sxhost::PlanConfig plan_cfg, plan_cfg_seen;      // the settings the plan depends on, and those the current plan was built with
   bool order_blocked = false;                      // a plan with ordered tables beyond LDS could not be laid out in runs
-  int cfg_order = 1, cfg_seen_order = -1;          // ... with the rows of a bucket ordered by a monotonically written observable
-  int cfg_box = -1, cfg_seen_box = -2;             // ... or grouped into boxes of a two-field observable (-1: where it pays, 1: wherever it applies)
   bool box_blocked = false;                        // a plan with boxed tables found no room for its codes / LDS form: planned again without
-  sxmc_group* twin = nullptr;                      // boxed plan, cfg_box < 0: the same members planned in the ORDERED form (owned);
+  sxmc_group* twin = nullptr;                      // boxed plan, plan_cfg.box < 0: the same members planned in the ORDERED form (owned);
                                                    // group_fill launches the one or the other (fill_form)
   bool is_twin = false;
   int fill_form = 2;                               // 1: the boxed plan's launches, 2: the twin's (where there is a twin)
   double* h_pin = nullptr;                         // pinned host words sxmc_group_adapt_fill_form reads the parameters into
   unsigned adapt_tick = 0;                         // deferred batches launched for this group (every 256th asks for the form)
   float box_limit = 0.12f;                         // sxmc_group_adapt_fill_form: boxed while the image of a mean box is narrower (bins)
-  int cfg_rtc = 1, cfg_seen_rtc = -1;              // specialise the fill kernel at run time for programs not built in
-  int cfg_codes = -1, cfg_seen_codes = -2;         // ordered tables streamed as 16-bit codes (-1: SXMC_CODES, default on)
-  int cfg_queue_log = 0, cfg_seen_queue_log = -1;  // ... cap on the queues of ambiguous rows, log2(entries) (0: what fits)
   std::string rtc_note;                            // why a run-time specialisation could not be had (last failure)
   std::string plan_note;                           // why a launch of the plan took a slower general path (for launch_info)
   int cfg_tail = 1;                                // sxmc_group_step_async: the one-workgroup step end where it fits
@@ -396,8 +406,6 @@ struct sxmc_group {
   unsigned* d_ticket = nullptr;  // arrival counter of the fused step end, zeroed by the zero kernel
   double* d_step_sums = nullptr; // 1024 partial sums of the fused step
   std::vector<char> h_tail;          // fused step (fill_step_kernel): the step end's arguments, passed to the kernel by value
-  int cfg_seen_fused = -2;
-  int cfg_fused = -1;                // the whole step in ONE launch where the fill has that form (-1: SXMC_FUSED_STEP, default OFF: measured slower)
   unsigned long long* d_coop_slots = nullptr;  // cooperative step end: one hand-over slot per worker (step_end_kernel)
   double* d_coop_last = nullptr;               // ... and the last partial of each that was not NaN
   // profiling of the fill kernel
@@ -421,13 +429,12 @@ struct sxmc_multigroup {
 namespace sxhost {
 
 // ---- the launch plan (sxmc_launch_plan.cpp)
+using sxplan::kMinQueueLog;
 using sxplan::ordered_queue_bytes;
-constexpr unsigned kMinQueueLog = 9;     // the smallest queues of ambiguous rows a fill over codes works with: 2^9 entries
 void member_slots(const sxmc_hist* h, std::vector<int>& slot_col);
 int fill_desc(const sxmc_hist* h, SxSignalDesc& d);   // a member's descriptor: table, slots, systematics, bindings
 void free_sparse(sxmc_hist* h);
 int build_sparse(sxmc_hist* h, const std::vector<int>& rb);
-unsigned ordered_queue_log(size_t room, int cap = 0);
 bool fused_step_requested(const sxmc_group* g);
 int group_refresh(sxmc_group* g);
 int group_check_bound(sxmc_group* g, bool need_pdf);

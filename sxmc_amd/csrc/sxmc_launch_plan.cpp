@@ -6,24 +6,14 @@ using namespace sxhost;
 
 namespace sxhost {
 
-// Who reads which units: sxmc_plan.h (apportion_workgroups, interleaved_segments, build_partition), here as thin
-// adapters from descriptors to their unit counts.
 using sxplan::apportion_workgroups;
-std::vector<unsigned long long> unit_counts(const std::vector<SxSignalDesc>& descs) {
-  std::vector<unsigned long long> nvec;
-  for (const SxSignalDesc& d : descs) nvec.push_back(d.nvec);
-  return nvec;
-}
-void interleaved_segments(const std::vector<SxSignalDesc>& descs, const std::vector<int>& K, int threads, int grid,
-                          std::vector<SxSegment>& segs, std::vector<unsigned>& blk_off) {
-  sxplan::interleaved_segments(unit_counts(descs), K, threads, grid, segs, blk_off);
-}
-void build_partition(const std::vector<SxSignalDesc>& descs, int grid, int threads, int want_mode,
-                     std::vector<SxSegment>& segs, std::vector<unsigned>& blk_off, int& mode_out,
-                     unsigned long long align = 1, int groups = 1) {
-  sxplan::build_partition(unit_counts(descs), grid, threads, want_mode, segs, blk_off, mode_out, align, groups);
-}
 
+// a host vector's copy on the device, allocated for at least `room` elements
+template <typename T>
+hipError_t upload(const std::vector<T>& v, T** d, size_t room = 0) {
+  const hipError_t e = hipMalloc((void**)d, sizeof(T) * std::max(v.size(), room));
+  return (e != hipSuccess || v.empty()) ? e : hipMemcpy(*d, v.data(), sizeof(T) * v.size(), hipMemcpyHostToDevice);
+}
 
 // Slot assignment: observables first (slot k = field k), then every other field a systematic
 // references, ascending.
@@ -84,14 +74,10 @@ int build_sparse(sxmc_hist* h, const std::vector<int>& rb) {
   const int cbits = st.cbits, fbits = st.fbits, tbits = st.tbits;
   SX_HIP(hipMalloc((void**)&h->d_cnt, sizeof(unsigned) * std::max<size_t>(T, 4)));
   SX_HIP(hipMemset(h->d_cnt, 0, sizeof(unsigned) * std::max<size_t>(T, 4)));
-  SX_HIP(hipMalloc((void**)&h->d_read_slot, sizeof(int) * std::max<size_t>(slot.size(), 1)));
-  if (!slot.empty()) SX_HIP(hipMemcpy(h->d_read_slot, slot.data(), sizeof(int) * slot.size(), hipMemcpyHostToDevice));
-  SX_HIP(hipMalloc((void**)&h->d_filter, sizeof(unsigned) * filter.size()));
-  SX_HIP(hipMemcpy(h->d_filter, filter.data(), sizeof(unsigned) * filter.size(), hipMemcpyHostToDevice));
-  SX_HIP(hipMalloc((void**)&h->d_table, sizeof(unsigned) * table.size()));
-  SX_HIP(hipMemcpy(h->d_table, table.data(), sizeof(unsigned) * table.size(), hipMemcpyHostToDevice));
-  SX_HIP(hipMalloc((void**)&h->d_coarse, sizeof(unsigned) * coarse.size()));
-  SX_HIP(hipMemcpy(h->d_coarse, coarse.data(), sizeof(unsigned) * coarse.size(), hipMemcpyHostToDevice));
+  SX_HIP(upload(slot, &h->d_read_slot, 1));
+  SX_HIP(upload(filter, &h->d_filter));
+  SX_HIP(upload(table, &h->d_table));
+  SX_HIP(upload(coarse, &h->d_coarse));
   h->h_read_slot = slot;
   h->coarse_shift = 32 - cbits;
   h->ntargets = (int)T;
@@ -326,7 +312,7 @@ int get_bucketed(sxmc_hist* h, const SampleStore::BucketSort* bs, const std::vec
   SX_HIP(sx_bucket_gather(st.d_cols, h->pitch, (int)fields.size(), fields.data(), bs->d_rows, dsrc.as<unsigned>(),
                           dvalid.as<unsigned>(), P, b->d_cols, b->pitch, nullptr));
   if (bs->ordered >= 0 && bs->box_truth >= 0) {
-    // the boxed observable's column is the last of `fields`, its truth field the one before (group_rebuild)
+    // the boxed observable's column is the last of `fields`, its truth field the one before (sxplan::compact_slots)
     SX_REQUIRE(fields.size() >= 2, "a boxed layout streams its observable and the truth field");
     SX_HIP(hipMalloc((void**)&b->d_gbox, sizeof(float) * 4 * A));
     SX_HIP(hipMemset(b->d_gbox, 0xFF, sizeof(float) * 4 * A));   // (NaN: a granule never written is left to the float columns)
@@ -356,7 +342,7 @@ int get_bucketed(sxmc_hist* h, const SampleStore::BucketSort* bs, const std::vec
       b->box_dt = trimmed(et);
     }
   } else if (bs->ordered >= 0) {
-    // the ordered observable's column is the last of `fields` (group_rebuild)
+    // the ordered observable's column is the last of `fields` (sxplan::compact_slots)
     SX_HIP(hipMalloc((void**)&b->d_gedge, sizeof(float) * 2 * A));
     SX_HIP(hipMemset(b->d_gedge, 0, sizeof(float) * 2 * A));
     SX_HIP(sx_bucket_edges(b->d_cols + (fields.size() - 1) * b->pitch, dvalid.as<unsigned>(), P, b->d_gedge, nullptr));
@@ -376,7 +362,7 @@ int get_bucketed(sxmc_hist* h, const SampleStore::BucketSort* bs, const std::vec
 // observables' windows when they overlap at all.  Built once per copy; left out (d_qcol stays null) when more than
 // 2 % of the rows would ask the exact columns: such a table gains nothing.
 bool codes_enabled(const sxmc_group* g) {
-  if (g->cfg_codes >= 0) return g->cfg_codes != 0;
+  if (g->plan_cfg.codes >= 0) return g->plan_cfg.codes != 0;
   static const bool on = [] {
     const char* e = std::getenv("SXMC_CODES");
     return !e || std::atoi(e) != 0;
@@ -443,18 +429,6 @@ int get_bucket_codes(sxmc_hist* h, const SampleStore::Bucketed* bkc, const SxSig
   return SXMC_OK;
 }
 
-using sxplan::ordered_rstride_padded;
-using sxplan::ordered_queue_bytes;
-// the largest set of queues (512 .. 2048 entries: every wave of the workgroup owns an equal slice) that fits `room`
-// bytes, as log2(entries); 0: none, the launch then streams the float columns
-unsigned ordered_queue_log(size_t room, int cap) {
-  unsigned qlog = 11;
-  // (sxmc_group_set_codes_queue_log caps the queues at 2^9 .. 2^11 entries -- smaller queues fill up and are emptied in
-  // the middle of the stream, and whole granules are handed to the float columns; the results do not depend on it)
-  if (cap > 0) qlog = (unsigned)std::min(std::max(cap, (int)kMinQueueLog), 11);
-  while (qlog >= kMinQueueLog && ordered_queue_bytes(qlog) > room) qlog--;
-  return qlog >= kMinQueueLog ? qlog : 0;
-}
 
 // The evaluator's event bins grouped by the buckets of a sort (fill_sparse_kernel): per bucket key an
 // open-addressing table keyed by the event bin's index contribution of the WRITTEN observables (flat index minus
@@ -466,61 +440,15 @@ int build_bucket_tables(sxmc_hist* h, const SampleStore::BucketSort* bs) {
   sxplan::BucketTables bt;   // directory + per-bucket tables of the event bins (sxmc_plan.h)
   sxplan::bucket_tables(bs->nkeys_total, bs->mask, bs->radix, h->nbins.data(), h->stride.data(), h->nobs, h->targets, bt);
   const std::vector<unsigned>&dir = bt.dir, &tkeys = bt.tkeys, &tslot = bt.tslot;
-  SX_HIP(hipMalloc((void**)&h->d_bdir, sizeof(unsigned) * dir.size()));
-  SX_HIP(hipMemcpy(h->d_bdir, dir.data(), sizeof(unsigned) * dir.size(), hipMemcpyHostToDevice));
-  SX_HIP(hipMalloc((void**)&h->d_btkeys, sizeof(unsigned) * std::max<size_t>(tkeys.size(), 4)));
-  SX_HIP(hipMalloc((void**)&h->d_btslot, sizeof(unsigned) * std::max<size_t>(tkeys.size(), 4)));
-  if (!tkeys.empty()) {
-    SX_HIP(hipMemcpy(h->d_btkeys, tkeys.data(), sizeof(unsigned) * tkeys.size(), hipMemcpyHostToDevice));
-    SX_HIP(hipMemcpy(h->d_btslot, tslot.data(), sizeof(unsigned) * tslot.size(), hipMemcpyHostToDevice));
-  }
+  SX_HIP(upload(dir, &h->d_bdir));
+  SX_HIP(upload(tkeys, &h->d_btkeys, 4));
+  SX_HIP(upload(tslot, &h->d_btslot, 4));
   h->btab_mask = bs->mask;
   h->btab_points_version = h->points_version;
   h->btab_valid = true;
   return SXMC_OK;
 }
 
-// LDS of fill_ordered_body: per chain 2^rlog replicas of the histogram, each padded to whole 64-word blocks (the
-// swizzle permutes inside a block) + 16 words (replicas of a bin in different banks), + header and trash words.
-unsigned ordered_rstride(int max_bins) { return (((unsigned)max_bins + 63u) & ~63u) + 16u; }
-size_t ordered_lds_bytes(int max_bins, int nchain, unsigned rlog) {
-  return (4 + ((size_t)nchain * ordered_rstride(max_bins) << rlog) + 64) * 4;
-}
-
-// The member's problem as the fill sees it once its table is bucketed: only the observables some systematic
-// writes (+ the extra fields), slots renumbered, columns = the bucketed copy.  `keep`: full slot -> new slot or -1.
-// `ordered` >= 0: that observable rides in the last slot and its geometry at index nobs2 (fill_ordered_kernel).
-void compact_desc(const SxSignalDesc& full, const std::vector<int>& keep, int nobs2, SxSignalDesc& cd, int ordered = -1) {
-  cd = full;
-  if (ordered >= 0) {
-    cd.bin_stride[nobs2] = full.bin_stride[ordered];
-    cd.nbins[nobs2] = full.nbins[ordered];
-    cd.lower[nobs2] = full.lower[ordered];
-    cd.upper[nobs2] = full.upper[ordered];
-    cd.scale[nobs2] = full.scale[ordered];
-  }
-  int nslot = 0;
-  for (int k = 0; k < full.nslot; k++) {
-    if (keep[(size_t)k] < 0) continue;
-    const int q = keep[(size_t)k];
-    cd.slot_col[q] = q;  // the copy holds exactly the streamed fields, in slot order
-    if (q < nobs2) {     // an observable the fill still bins (the others it keeps are read-only inputs)
-      cd.bin_stride[q] = full.bin_stride[k];
-      cd.nbins[q] = full.nbins[k];
-      cd.lower[q] = full.lower[k];
-      cd.upper[q] = full.upper[k];
-      cd.scale[q] = full.scale[k];
-    }
-    nslot++;
-  }
-  cd.nobs = nobs2;
-  cd.nslot = nslot;
-  for (int q = 0; q < full.nsyst; q++) {
-    cd.syst[q].obs_slot = (short)keep[(size_t)full.syst[q].obs_slot];
-    cd.syst[q].extra_slot =
-        (short)(full.syst[q].type == SXMC_SYST_RESOLUTION_SCALE ? keep[(size_t)full.syst[q].extra_slot] : 0);
-  }
-}
 
 // The whole step in one launch (fill_step_kernel), when asked for: its role workgroups carry the fill's LDS allotment
 // and need 16 KB of their own beside it, which the plan of an ordered fill then leaves free.
@@ -529,358 +457,186 @@ bool fused_step_requested(const sxmc_group* g) {
     const char* e = std::getenv("SXMC_FUSED_STEP");
     return (e && e[0] == '1') ? 1 : 0;
   }();
-  return (g->cfg_fused < 0 ? env_default : g->cfg_fused) != 0;
+  return (g->plan_cfg.fused < 0 ? env_default : g->plan_cfg.fused) != 0;
 }
 
-int group_rebuild(sxmc_group* g) {
-  TraceRange trace("sxmc: launch plan (tables, partitions, kernels)");
-  // Descriptors may still be read by kernels in flight on another stream: rebuilds are rare
-  // (bindings change only during setup), so a device-wide sync is the simple safe choice.
-  SX_HIP(hipDeviceSynchronize());
-  DeviceProps props;
-  int rc = get_props(props);
-  if (rc) return rc;
+int group_rebuild(sxmc_group* g);
 
-  const int n = (int)g->members.size();
-  g->h_descs.assign((size_t)n, SxSignalDesc{});
-  for (LaunchClass& c : g->classes) free_class(c);
-  g->classes.clear();
-  g->max_bins = 0;
-  g->max_points = 0;
-  g->same_points = n > 0;
-  g->plan_note.clear();
+// ---- the launch plan, step by step.  What a step decides without the device is in sxmc_plan.h (syst_use, choose_ordered,
+// choose_boxed, compact_slots, prebin_columns, ordered_lds_layout); here: the kernel tables, the device's tables, uploads.
 
-  int threads = g->cfg_threads > 0 ? g->cfg_threads : 512;
-  if (threads < 64 || threads > 1024 || threads % 64) threads = 512;
+// What a step of the plan found it cannot lay out: group_rebuild runs the pass again without that form.
+enum class Blocked { none, order, box };
 
-  for (int i = 0; i < n; i++) fill_desc(g->members[i], g->h_descs[i]);
-  if (!g->d_descs) SX_HIP(hipMalloc((void**)&g->d_descs, sizeof(SxSignalDesc) * std::max(n, 1)));
-  if (n) SX_HIP(hipMemcpy(g->d_descs, g->h_descs.data(), sizeof(SxSignalDesc) * n, hipMemcpyHostToDevice));
+inline bool is_boxed(const LaunchClass& c) { return c.shape.pre_width == 6; }
+inline bool is_ordered(const LaunchClass& c) { return c.shape.pre_width == 5 || is_boxed(c); }   // (the LDS layout, shapes and partition of the ordered form)
+inline bool is_bucketed(const LaunchClass& c) { return c.shape.pre_width == 3 || is_ordered(c); }
 
-  std::vector<SxSignalDesc> fill_descs((size_t)n);  // each member as its fill launch sees it
-  struct BucketPlan {                               // bucketed members: what to lay out once the class's shape is known
-    const SampleStore::BucketSort* sort = nullptr;
-    std::vector<int> fields;
-  };
-  std::vector<BucketPlan> plans((size_t)n);
-  g->member_bucket.assign((size_t)n, nullptr);
-  for (int i = 0; i < n; i++) {
-    sxmc_hist* h = g->members[i];
-    const SxSignalDesc& d = g->h_descs[i];
-    fill_descs[(size_t)i] = d;
-    g->max_bins = std::max(g->max_bins, h->total_nbins);
-    g->max_points = std::max<unsigned long long>(g->max_points, d.npoints);
-    if (!h->has_points || h->npoints != g->members[0]->npoints) g->same_points = false;
+// One member's part of the plan: the form its table takes and the kernel that runs it.
+struct MemberPlan {
+  // the key of its launch class (find_class): shape.nobs / nslot / lds_hist / pre_width / rtc_fill / rtc_sparse, prog,
+  // prog_simple, pre_mask, runs_mode; with it shape.static_prog and the boxed form's slots.  find_class copies it as
+  // the new class: set nothing else on it.
+  LaunchClass cls;
+  // bucketed forms: what to lay out once the class's shape is known
+  const SampleStore::BucketSort* sort = nullptr;
+  std::vector<int> fields;
+  SxSignalDesc desc;                  // the member as its fill launch sees it
+};
 
-    const int lds_hist = h->total_nbins <= kLdsMaxBins ? 1 : 0;
-    int key_nobs = 0, key_nslot = 0, static_prog = -1, pre_width = 0;
-    unsigned pre_mask = 0;
-    bool runs_mode = false;
-    std::vector<unsigned> prog;
-    bool prog_simple = false;
-
-    // A program every systematic of which is a short polynomial can run as straight-line code: from the table of
-    // kernels built into the library, or specialised now through hiprtc (sxmc_rtc.cpp).
-    int prog_ncoef = 0;
-    bool specialisable = d.nsyst <= 8;
-    for (int q = 0; q < d.nsyst; q++) {
-      prog_ncoef += d.syst[q].npars;
-      specialisable = specialisable && d.syst[q].npars >= 1 && d.syst[q].npars <= SXMC_MAX_SYST_PARS;
-    }
-    specialisable = specialisable && prog_ncoef <= 16;
-    auto prog_words = [](const SxSignalDesc& x) {
-      std::vector<unsigned> w;
-      for (int q = 0; q < x.nsyst; q++) {
-        w.push_back((unsigned)x.syst[q].type | ((unsigned)x.syst[q].obs_slot << 4) |
-                    ((unsigned)x.syst[q].extra_slot << 8) | (x.syst[q].npars > 1 ? (unsigned)x.syst[q].npars << 12 : 0u));
-      }
-      return w;
-    };
-    // is there a kernel for this specialisation?  *fn: the run-time one, or null for a built-in one
-    auto have_kernel = [&](int nobs_, int nslot_, int prew, int runs, const std::vector<unsigned>& words, int sp,
-                           void** fn) {
-      *fn = nullptr;
-      if (prew == 5 || prew == 6) {   // (sp: index into the ordered / boxed programs built in: histograms in LDS, no runs)
-        if (sp >= 0 && lds_hist && !runs) return true;
-      } else if (runs ? sx_fill_static_supports_sparse_runs(sp) : sx_fill_static_supports(sp, lds_hist, prew)) {
-        return true;
-      }
-      if (!g->cfg_rtc) return false;
-      SxRtcSpec k{};
-      k.nobs = nobs_;
-      k.nslot = nslot_;
-      k.lds_hist = lds_hist;
-      k.pre_width = prew;
-      k.sparse_runs = runs;
-      k.nops = (int)words.size();
-      for (size_t q = 0; q < words.size(); q++) k.ops[q] = words[q];
-      std::string err;
-      *fn = sx_rtc_get(k, &err);
-      if (!*fn) g->rtc_note = err;
-      return *fn != nullptr;
-    };
-    void *rtc_fill = nullptr, *rtc_sparse = nullptr;
-
-    // ---- bucketed table: the observables no systematic writes become a per-granule bin offset and the
-    // fill sees the lower-dimensional problem of the ones that are written.  With an ORDERED observable (written
-    // only by monotone one-coefficient systematics, read by nothing): that one too is a per-granule constant,
-    // worked out per evaluation from the granule's end values, except in the granules that straddle a bin edge.
-    bool bucketed = false;
-    int box_obs_of = -1, box_truth_of = -1;
-    // box_truth >= 0: `ordered` is a BOXED observable (fill_boxed_kernel) and box_truth the slot of its truth field
-    auto try_bucket = [&](int ordered, int box_truth = -1) -> int {
-      unsigned touched = 0, read = 0;
-      for (int q = 0; q < d.nsyst; q++) {
-        touched |= 1u << d.syst[q].obs_slot;
-        if (d.syst[q].type == SXMC_SYST_RESOLUTION_SCALE) read |= 1u << d.syst[q].extra_slot;
-      }
-      // compacted slots: the observables that are written (still binned by the fill), then everything that is only
-      // read -- the extra fields, and an untouched observable that serves as some systematic's truth field (its own
-      // bin index is the bucket's; its VALUE is still an input) --, then the ordered observable
-      unsigned mask = 0;
-      std::vector<int> keep((size_t)d.nslot, -1), fields;
-      int nobs2 = 0;
-      for (int k = 0; k < d.nobs; k++) {
-        if (k == ordered) continue;
-        if ((touched >> k) & 1u) {
-          keep[(size_t)k] = (int)fields.size();
-          fields.push_back(d.slot_col[k]);
-          nobs2++;
-        } else {
-          mask |= 1u << k;
-        }
-      }
-      for (int k = 0; k < d.nslot; k++) {
-        if (keep[(size_t)k] >= 0 || k == ordered) continue;
-        if (k >= d.nobs || ((read >> k) & 1u)) {
-          keep[(size_t)k] = (int)fields.size();
-          fields.push_back(d.slot_col[k]);
-        }
-      }
-      if (ordered >= 0) {
-        keep[(size_t)ordered] = (int)fields.size();
-        fields.push_back(d.slot_col[ordered]);
-      }
-      // (beyond LDS the granule word has no room for the row count: something must be binned per sample)
-      const bool shape_ok = box_truth >= 0 ? (nobs2 == 1 && fields.size() == 3 && lds_hist &&
-                                              fields[1] == d.slot_col[box_truth])
-                            : ordered >= 0 ? (nobs2 <= 5 && fields.size() <= 7 && (lds_hist || nobs2 >= 1))
-                                           : (mask && nobs2 >= 1 && sx_fill_has_specialization(nobs2, (int)fields.size()));
-      if (!shape_ok) return SXMC_OK;
-      SxSignalDesc cd;
-      compact_desc(d, keep, nobs2, cd, ordered);
-      const std::vector<unsigned> prog2 = prog_words(cd);
-      const int prew = box_truth >= 0 ? 6 : ordered >= 0 ? 5 : 3;
-      const int sp = box_truth >= 0 ? sx_fill_find_boxed_program(cd.nobs, cd.nslot, (int)prog2.size(), prog2.data())
-                     : ordered >= 0 ? sx_fill_find_ordered_program(cd.nobs, cd.nslot, (int)prog2.size(), prog2.data())
-                                    : sx_fill_find_static_program(cd.nobs, cd.nslot, (int)prog2.size(), prog2.data());
-      if (!have_kernel(cd.nobs, cd.nslot, prew, 0, prog2, sp, &rtc_fill)) return SXMC_OK;
-      const SampleStore::BucketSort* bs = nullptr;
-      int rc2 = get_bucket_sort(h, g->d_descs + i, mask, ordered, &bs,
-                                box_truth >= 0 ? d.slot_col[box_truth] : -1);
-      if (rc2) return rc2;
-      if (!bs) {
-        rtc_fill = nullptr;
-        return SXMC_OK;
-      }
-      fill_descs[(size_t)i] = cd;     // (columns, unit count and granule table: once the layout is chosen)
-      plans[(size_t)i].sort = bs;
-      plans[(size_t)i].fields = fields;
-      bucketed = true;
-      // histograms beyond LDS, evaluated at data events: per-wave runs + event bins grouped by bucket
-      bool narrow = true;   // (the runs kernel forms idx * stride + bin with ONE signed 24-bit multiply-add)
-      for (int k = 0; k < h->nobs; k++) {
-        narrow = narrow && h->nbins[(size_t)k] < (1 << 23) && h->stride[(size_t)k] < (1 << 23);
-      }
-      runs_mode = !lds_hist && narrow && h->has_points && h->d_table && box_truth < 0 &&
-                  have_kernel(cd.nobs, cd.nslot, prew, 1, prog2, sp, &rtc_sparse);
-      if (!lds_hist && !narrow && h->has_points && h->d_table) {
-        // (a regression on very large histograms must be visible: sxmc_group_launch_info prints this)
-        g->plan_note = "histogram with a bin count or stride of 2^23 or more: the sparse counting over runs (one signed "
-                       "24-bit multiply-add per index) does not apply, the general sparse path runs instead";
-      }
-      if (runs_mode) {
-        rc2 = build_bucket_tables(h, bs);
-        if (rc2) return rc2;
-      }
-      key_nobs = cd.nobs;
-      key_nslot = cd.nslot;
-      prog = prog2;
-      prog_simple = true;
-      static_prog = rtc_fill ? -1 : sp;
-      pre_mask = mask | (ordered >= 0 ? 1u << (16 + ordered) : 0u);
-      pre_width = prew;
-      box_obs_of = box_truth >= 0 ? ordered : -1;
-      box_truth_of = box_truth;
-      return SXMC_OK;
-    };
-    if (g->cfg_bucket && d.nsyst > 0 && specialisable) {
-      // the ordered observable: written by one-coefficient shift / scale / cos-theta scale only and read by
-      // nothing; of several, the one with the fewest bins (fewest granules that straddle an edge)
-      int ordered = -1;
-      // (a histogram beyond LDS: only with the event-bin counters over runs; the round-1 filter path of a table
-      // left in sorted order has no ordered form)
-      bool narrow_o = true;
-      for (int k = 0; k < h->nobs; k++) {
-        narrow_o = narrow_o && h->nbins[(size_t)k] < (1 << 23) && h->stride[(size_t)k] < (1 << 23);
-      }
-      const bool beyond_ok = !lds_hist && !g->order_blocked && narrow_o && h->has_points && h->d_table && n <= props.cus;
-      if (g->cfg_order && ((lds_hist && h->total_nbins < (1 << 24)) || beyond_ok)) {
-        for (int k = 0; k < d.nobs; k++) {
-          bool written = false, ok = true;
-          for (int q = 0; q < d.nsyst; q++) {
-            const SxSystOp& op = d.syst[q];
-            if (op.obs_slot == k) {
-              written = true;
-              ok = ok && op.npars == 1 &&
-                   (op.type == SXMC_SYST_SHIFT || op.type == SXMC_SYST_SCALE || op.type == SXMC_SYST_CTSCALE);
-            }
-            if (op.type == SXMC_SYST_RESOLUTION_SCALE && op.extra_slot == k) ok = false;
-          }
-          if (written && ok && (ordered < 0 || h->nbins[(size_t)k] < h->nbins[(size_t)ordered])) ordered = k;
-        }
-        // Does it pay?  Up to nbins + 1 granules per bucket straddle an edge and stream everything; with fewer
-        // than twice that many granules in all, most do (BASELINE config 5: 61 granules per bucket against 200
-        // bins of r) and the ordered form only adds work.  cfg_order == 2 (tests): wherever it applies.
-        if (ordered >= 0 && g->cfg_order == 1) {
-          double buckets = 1.0;
-          for (int k = 0; k < d.nobs; k++) {
-            bool written = false;
-            for (int q = 0; q < d.nsyst; q++) written = written || d.syst[q].obs_slot == k;
-            if (!written) buckets *= (double)h->nbins[(size_t)k];
-          }
-          const double straddling = buckets * ((double)h->nbins[(size_t)ordered] + 1.0);
-          if ((double)h->nsamples / 256.0 < 2.0 * straddling) ordered = -1;
-        }
-      }
-      // The BOXED observable (fill_boxed_kernel): written by one-coefficient shift / scale / cos-theta scale and at least
-      // one resolution scale, all of those against ONE field that nothing writes, and read by nothing; beside it exactly one
-      // other written observable, with one-coefficient shift / scale / cos-theta scale only (one streamed field, as 16-bit
-      // codes).  Histogram in LDS, codes on.  Where the ordered form also applies this one streams half the bytes.
-      int boxed = -1, box_truth = -1;
-      if (g->cfg_box != 0 && !g->box_blocked && g->cfg_order && lds_hist && h->total_nbins < (1 << 22) && codes_enabled(g)) {
-        int nwritten = 0;
-        bool others_ok = true;
-        for (int k = 0; k < d.nobs; k++) {
-          bool written = false, ok = true, has_res = false;
-          int truth = -1;
-          for (int q = 0; q < d.nsyst; q++) {
-            const SxSystOp& op = d.syst[q];
-            if (op.obs_slot == k) {
-              written = true;
-              ok = ok && op.npars == 1;
-              if (op.type == SXMC_SYST_RESOLUTION_SCALE) {
-                has_res = true;
-                ok = ok && (truth < 0 || truth == op.extra_slot) && op.extra_slot != k;
-                truth = op.extra_slot;
-              }
-            }
-            if (op.type == SXMC_SYST_RESOLUTION_SCALE && op.extra_slot == k) ok = false;   // (read by a systematic)
-          }
-          if (!written) continue;
-          nwritten++;
-          if (has_res && ok && boxed < 0) {
-            boxed = k;
-            box_truth = truth;
-          } else {
-            others_ok = others_ok && ok && !has_res;
-          }
-        }
-        bool truth_written = false;
-        for (int q = 0; q < d.nsyst && box_truth >= 0; q++) truth_written = truth_written || d.syst[q].obs_slot == box_truth;
-        if (boxed < 0 || nwritten != 2 || !others_ok || truth_written || d.nsyst > 8) boxed = -1;
-        // Does it pay?  A box straddles an edge of the observable when it is not small against a bin: with fewer than a
-        // few granules per bin, stratum and bucket most do.  cfg_box == 1 (tests): wherever it applies.
-        if (boxed >= 0 && g->cfg_box < 0) {
-          double buckets = 1.0;
-          for (int k = 0; k < d.nobs; k++) {
-            bool written = false;
-            for (int q = 0; q < d.nsyst; q++) written = written || d.syst[q].obs_slot == k;
-            if (!written) buckets *= (double)h->nbins[(size_t)k];
-          }
-          const double per = (double)h->nsamples / 256.0 / (buckets * box_strata());
-          if (per < 4.0 * ((double)h->nbins[(size_t)boxed] + 1.0)) boxed = -1;
-        }
-      }
-      if (boxed >= 0) {
-        rc = try_bucket(boxed, box_truth);
-        if (rc) return rc;
-      }
-      if (!bucketed && ordered >= 0) {
-        rc = try_bucket(ordered);
-        if (rc) return rc;
-        if (bucketed && !lds_hist && !runs_mode) {   // (no kernel for the runs: the unordered layout has the filter path)
-          bucketed = false;
-          rtc_fill = rtc_sparse = nullptr;
-          fill_descs[(size_t)i] = d;
-          plans[(size_t)i] = BucketPlan{};
-        }
-      }
-      if (!bucketed) {
-        rc = try_bucket(-1);
-        if (rc) return rc;
-      }
-    }
-    if (!bucketed) {
-      const bool spec = sx_fill_has_specialization(d.nobs, d.nslot) && d.ncoef <= 64;
-      key_nobs = spec ? d.nobs : 0;
-      key_nslot = spec ? d.nslot : 0;
-      prog = prog_words(d);
-      const int sp = (spec && specialisable)
-                         ? sx_fill_find_static_program(key_nobs, key_nslot, (int)prog.size(), prog.data())
-                         : -1;
-      prog_simple = spec && specialisable && have_kernel(key_nobs, key_nslot, 0, 0, prog, sp, &rtc_fill);
-      static_prog = (prog_simple && !rtc_fill) ? sp : -1;
-      // pre-binning: observables that no systematic writes (built-in programs only; bucketing covers the rest)
-      if (g->cfg_prebin && sx_fill_static_supports(static_prog, lds_hist, 1)) {
-        unsigned touched = 0;
-        for (int q = 0; q < d.nsyst; q++) touched |= 1u << d.syst[q].obs_slot;
-        long long bound = 0;  // largest value the partial index can take (index == nbins included)
-        for (int k = 0; k < d.nobs; k++) {
-          if (!((touched >> k) & 1u)) {
-            pre_mask |= 1u << k;
-            bound += (long long)h->nbins[(size_t)k] * h->stride[(size_t)k];
-          }
-        }
-        pre_width = bound < 0xFF ? 1 : 2;
-        if (!pre_mask || bound >= 0xFFFF) {
-          pre_mask = 0;
-          pre_width = 0;
-        }
-      }
-    }
-    LaunchClass* cls = nullptr;
-    for (LaunchClass& c : g->classes) {
-      if (c.shape.nobs == key_nobs && c.shape.nslot == key_nslot && c.shape.lds_hist == lds_hist &&
-          c.prog_simple == prog_simple && (!prog_simple || c.prog == prog) && c.pre_mask == pre_mask &&
-          c.shape.pre_width == pre_width && c.runs_mode == runs_mode && c.shape.rtc_fill == rtc_fill &&
-          c.shape.rtc_sparse == rtc_sparse) {
-        cls = &c;
-      }
-    }
-    if (!cls) {
-      g->classes.push_back(LaunchClass{});
-      cls = &g->classes.back();
-      cls->shape.nobs = key_nobs;
-      cls->shape.nslot = key_nslot;
-      cls->shape.lds_hist = lds_hist;
-      cls->shape.threads = threads;
-      cls->shape.debug_mode = 0;
-      cls->prog = prog;
-      cls->prog_simple = prog_simple;
-      cls->shape.static_prog = static_prog;
-      cls->shape.pre_width = pre_width;
-      cls->pre_mask = pre_mask;
-      cls->runs_mode = runs_mode;
-      cls->shape.rtc_fill = rtc_fill;
-      cls->shape.rtc_sparse = rtc_sparse;
-      cls->box_obs = pre_width == 6 ? box_obs_of : -1;
-      cls->box_truth = pre_width == 6 ? box_truth_of : -1;
-    }
-    cls->member_idx.push_back(i);
+// is there a kernel for this specialisation?  *fn: the run-time one, or null for a built-in one
+bool have_kernel(sxmc_group* g, int lds_hist, int nobs, int nslot, int prew, int runs, const std::vector<unsigned>& words,
+                 int sp, void** fn) {
+  *fn = nullptr;
+  if (prew == 5 || prew == 6) {   // (sp: index into the ordered / boxed programs built in: histograms in LDS, no runs)
+    if (sp >= 0 && lds_hist && !runs) return true;
+  } else if (runs ? sx_fill_static_supports_sparse_runs(sp) : sx_fill_static_supports(sp, lds_hist, prew)) {
+    return true;
   }
+  if (!g->plan_cfg.rtc) return false;
+  SxRtcSpec k{};
+  k.nobs = nobs;
+  k.nslot = nslot;
+  k.lds_hist = lds_hist;
+  k.pre_width = prew;
+  k.sparse_runs = runs;
+  k.nops = (int)words.size();
+  for (size_t q = 0; q < words.size(); q++) k.ops[q] = words[q];
+  std::string err;
+  *fn = sx_rtc_get(k, &err);
+  if (!*fn) g->rtc_note = err;
+  return *fn != nullptr;
+}
 
-  // sparse flavour: members whose histogram exceeds LDS count into per-event-bin counters
+// ---- bucketed table: the observables no systematic writes become a per-granule bin offset and the
+// fill sees the lower-dimensional problem of the ones that are written.  With an ORDERED observable (written
+// only by monotone one-coefficient systematics, read by nothing): that one too is a per-granule constant,
+// worked out per evaluation from the granule's end values, except in the granules that straddle a bin edge.
+// box_truth >= 0: `ordered` is a BOXED observable (fill_boxed_kernel) and box_truth the slot of its truth field.
+// mp.sort stays null where the form does not apply: no such shape, no kernel, or bucketing does not pay for the table.
+int plan_bucketed(sxmc_group* g, int i, const sxplan::SystUse& use, int ordered, int box_truth, MemberPlan& mp) {
+  mp = MemberPlan{};
+  LaunchClass& k = mp.cls;
+  sxmc_hist* h = g->members[(size_t)i];
+  const SxSignalDesc& d = g->h_descs[(size_t)i];
+  const int lds_hist = k.shape.lds_hist = h->total_nbins <= kLdsMaxBins ? 1 : 0;
+  const sxplan::CompactSlots cs = sxplan::compact_slots(d, use, ordered, box_truth, lds_hist != 0);
+  if (!cs.shape_ok || (ordered < 0 && !sx_fill_has_specialization(cs.nobs2, (int)cs.fields.size()))) return SXMC_OK;
+  SxSignalDesc cd;
+  sxplan::compact_desc(d, cs.keep, cs.nobs2, cd, ordered);
+  const std::vector<unsigned> prog2 = sxplan::prog_words(cd);
+  const int prew = box_truth >= 0 ? 6 : ordered >= 0 ? 5 : 3;
+  const int sp = box_truth >= 0 ? sx_fill_find_boxed_program(cd.nobs, cd.nslot, (int)prog2.size(), prog2.data())
+                 : ordered >= 0 ? sx_fill_find_ordered_program(cd.nobs, cd.nslot, (int)prog2.size(), prog2.data())
+                                : sx_fill_find_static_program(cd.nobs, cd.nslot, (int)prog2.size(), prog2.data());
+  if (!have_kernel(g, lds_hist, cd.nobs, cd.nslot, prew, 0, prog2, sp, &k.shape.rtc_fill)) return SXMC_OK;
+  const SampleStore::BucketSort* bs = nullptr;
+  int rc = get_bucket_sort(h, g->d_descs + i, cs.mask, ordered, &bs, box_truth >= 0 ? d.slot_col[box_truth] : -1);
+  if (rc) return rc;
+  if (!bs) {
+    k.shape.rtc_fill = nullptr;
+    return SXMC_OK;
+  }
+  mp.desc = cd;     // (columns, unit count and granule table: once the layout is chosen)
+  mp.sort = bs;
+  mp.fields = cs.fields;
+  // histograms beyond LDS, evaluated at data events: per-wave runs + event bins grouped by bucket
+  const bool narrow = sxplan::narrow_for_runs(d);
+  k.runs_mode = !lds_hist && narrow && h->has_points && h->d_table && box_truth < 0 &&
+                have_kernel(g, lds_hist, cd.nobs, cd.nslot, prew, 1, prog2, sp, &k.shape.rtc_sparse);
+  if (!lds_hist && !narrow && h->has_points && h->d_table) {
+    // (a regression on very large histograms must be visible: sxmc_group_launch_info prints this)
+    g->plan_note = "histogram with a bin count or stride of 2^23 or more: the sparse counting over runs (one signed "
+                   "24-bit multiply-add per index) does not apply, the general sparse path runs instead";
+  }
+  if (k.runs_mode) {
+    rc = build_bucket_tables(h, bs);
+    if (rc) return rc;
+  }
+  k.shape.nobs = cd.nobs;
+  k.shape.nslot = cd.nslot;
+  k.prog = prog2;
+  k.prog_simple = true;
+  k.shape.static_prog = k.shape.rtc_fill ? -1 : sp;
+  k.pre_mask = cs.pre_mask;
+  k.shape.pre_width = prew;
+  k.box_obs = box_truth >= 0 ? ordered : -1;
+  k.box_truth = box_truth;
+  return SXMC_OK;
+}
+
+// The table as it is: rows, or with the observables no systematic writes pre-binned.
+MemberPlan plan_rows(sxmc_group* g, const SxSignalDesc& d, const sxplan::SystUse& use, int lds_hist) {
+  MemberPlan mp{};
+  LaunchClass& k = mp.cls;
+  mp.desc = d;
+  k.shape.lds_hist = lds_hist;
+  const bool spec = sx_fill_has_specialization(d.nobs, d.nslot) && d.ncoef <= 64;
+  k.shape.nobs = spec ? d.nobs : 0;
+  k.shape.nslot = spec ? d.nslot : 0;
+  k.prog = sxplan::prog_words(d);
+  const int sp = (spec && use.specialisable)
+                     ? sx_fill_find_static_program(k.shape.nobs, k.shape.nslot, (int)k.prog.size(), k.prog.data())
+                     : -1;
+  k.prog_simple = spec && use.specialisable &&
+                  have_kernel(g, lds_hist, k.shape.nobs, k.shape.nslot, 0, 0, k.prog, sp, &k.shape.rtc_fill);
+  k.shape.static_prog = (k.prog_simple && !k.shape.rtc_fill) ? sp : -1;
+  // pre-binning: observables that no systematic writes (built-in programs only; bucketing covers the rest)
+  if (g->plan_cfg.prebin && sx_fill_static_supports(k.shape.static_prog, lds_hist, 1)) {
+    const sxplan::PrebinColumns pre = sxplan::prebin_columns(d, use);
+    k.pre_mask = pre.mask;
+    k.shape.pre_width = pre.width;
+  }
+  return mp;
+}
+
+// The form member i's table takes: boxed, ordered, bucketed, pre-binned or rows -- the first that applies, pays and
+// has a kernel.
+int plan_member(sxmc_group* g, const DeviceProps& props, int i, MemberPlan& mp) {
+  sxmc_hist* h = g->members[(size_t)i];
+  const SxSignalDesc& d = g->h_descs[(size_t)i];
+  const PlanConfig& cfg = g->plan_cfg;
+  const int lds_hist = h->total_nbins <= kLdsMaxBins ? 1 : 0;
+  const sxplan::SystUse use = sxplan::syst_use(d);
+  if (cfg.bucket && d.nsyst > 0 && use.specialisable) {
+    const bool runs_possible = !g->order_blocked && h->has_points && h->d_table && (int)g->members.size() <= props.cus;
+    const int ordered = sxplan::choose_ordered(d, use, cfg.order, lds_hist != 0, runs_possible);
+    // (the boxed form: beside the ordered one, codes on)
+    const bool box_on = cfg.box != 0 && !g->box_blocked && cfg.order && lds_hist && codes_enabled(g);
+    const sxplan::BoxChoice box = sxplan::choose_boxed(d, use, box_on ? cfg.box : 0, box_strata(), lds_hist != 0);
+    int rc = SXMC_OK;
+    mp = MemberPlan{};
+    if (box.obs >= 0) rc = plan_bucketed(g, i, use, box.obs, box.truth, mp);
+    if (!rc && !mp.sort && ordered >= 0) {
+      rc = plan_bucketed(g, i, use, ordered, -1, mp);
+      if (mp.sort && !lds_hist && !mp.cls.runs_mode) mp = MemberPlan{};   // (no kernel for the runs: the unordered layout has the filter path)
+    }
+    if (!rc && !mp.sort) rc = plan_bucketed(g, i, use, -1, -1, mp);
+    if (rc || mp.sort) return rc;
+  }
+  mp = plan_rows(g, d, use, lds_hist);
+  return SXMC_OK;
+}
+
+// The launch class of a member's plan: members with the same kernel and table form share a launch.
+LaunchClass& find_class(sxmc_group* g, const MemberPlan& mp, int threads) {
+  const LaunchClass& k = mp.cls;
+  for (LaunchClass& c : g->classes) {
+    if (c.shape.nobs == k.shape.nobs && c.shape.nslot == k.shape.nslot && c.shape.lds_hist == k.shape.lds_hist &&
+        c.prog_simple == k.prog_simple && (!k.prog_simple || c.prog == k.prog) && c.pre_mask == k.pre_mask &&
+        c.shape.pre_width == k.shape.pre_width && c.runs_mode == k.runs_mode && c.shape.rtc_fill == k.shape.rtc_fill &&
+        c.shape.rtc_sparse == k.shape.rtc_sparse) {
+      return c;
+    }
+  }
+  g->classes.push_back(k);
+  g->classes.back().shape.threads = threads;
+  return g->classes.back();
+}
+
+// sparse flavour: members whose histogram exceeds LDS count into per-event-bin counters
+int build_sparse_descs(sxmc_group* g) {
+  const int n = (int)g->members.size();
   std::vector<SxSignalDesc> sparse_descs = g->h_descs;
   g->sparse_ready = false;
   g->max_bins_sparse = 0;
@@ -914,378 +670,421 @@ int group_rebuild(sxmc_group* g) {
   g->prezeroed = 0;
   if (!g->d_descs_sparse) SX_HIP(hipMalloc((void**)&g->d_descs_sparse, sizeof(SxSignalDesc) * std::max(n, 1)));
   if (n) SX_HIP(hipMemcpy(g->d_descs_sparse, sparse_descs.data(), sizeof(SxSignalDesc) * n, hipMemcpyHostToDevice));
+  return SXMC_OK;
+}
 
-  for (LaunchClass& c : g->classes) {
-    const bool boxed = c.shape.pre_width == 6;
-    const bool bucketed = c.shape.pre_width == 3 || c.shape.pre_width == 5 || boxed;
-    const bool ordered = c.shape.pre_width == 5 || boxed;   // (the LDS layout, shapes and partition of the ordered form)
-    // ---- threads per workgroup, LDS
-    int cls_max_bins = 0, cls_nsyst = 0;
-    for (int idx : c.member_idx) {
-      cls_max_bins = std::max(cls_max_bins, g->h_descs[(size_t)idx].total_nbins);
-      cls_nsyst = std::max(cls_nsyst, g->h_descs[(size_t)idx].nsyst);
-    }
-    c.shape.lds_bytes = c.shape.lds_hist ? ((size_t)cls_max_bins + 4 + 64) * 4 : 64;
-    if (ordered && c.shape.lds_hist) c.shape.lds_bytes = ordered_lds_bytes(cls_max_bins, 1, 0);   // (replicas: below)
-    c.shape.sparse_runs = 0;
-    c.shape.sparse_lds_bytes = 0;
-    std::vector<int> K;   // runs mode: workgroups per member
-    if (c.runs_mode) {
-      // every wave owns 2 x 512 words of LDS (table keys + counts) and walks its own run of consecutive granules:
-      // member j gets K_j workgroups (in proportion to its granules) = K_j x waves runs.  Three workgroups of
-      // 512 per CU measured best at BASELINE config 5 (2.14 ms; one of 1024: 2.29 ms; thread counts that are not
-      // powers of two 2.4 ms); the kernel is bound by vector-instruction issue and HBM together, and 24 waves
-      // per CU is what its registers allow.
-      const int rthreads = g->cfg_threads > 0 ? c.shape.threads : 512;
-      const size_t need = (size_t)(rthreads / 64) * 2u * ((size_t)4 << SXMC_SPARSE_SMAX_LOG2);
-      std::vector<unsigned long long> sizes;
-      for (int idx : c.member_idx) sizes.push_back((unsigned long long)plans[(size_t)idx].sort->lsrc.size() * 64ull);
-      const int rbpc = std::min(g->cfg_bpc > 0 ? g->cfg_bpc : std::max(1, 1536 / rthreads),
-                                std::max(1, (int)((size_t)props.lds_per_cu / need)));
-      if (need > (size_t)props.lds_per_cu || !apportion_workgroups(sizes, props.cus * rbpc, rthreads, K)) {
-        if (ordered && !g->order_blocked) {   // the ordered layout needs the runs: plan again without it
-          g->order_blocked = true;
-          return group_rebuild(g);
-        }
-        c.runs_mode = false;   // (more such members than workgroups: the table stays in sorted order)
-      } else {
-        c.shape.threads = rthreads;
-        c.shape.sparse_lds_bytes = need;
+// ---- threads per workgroup and LDS of a class, before its tables are laid out.  K (runs mode): workgroups per member.
+void class_threads_and_lds(sxmc_group* g, const DeviceProps& props, const std::vector<MemberPlan>& plans, LaunchClass& c,
+                           std::vector<int>& K, Blocked& blocked) {
+  const PlanConfig& cfg = g->plan_cfg;
+  c.max_bins = 0;
+  for (int idx : c.member_idx) c.max_bins = std::max(c.max_bins, g->h_descs[(size_t)idx].total_nbins);
+  c.shape.lds_bytes = c.shape.lds_hist ? ((size_t)c.max_bins + 4 + 64) * 4 : 64;
+  if (is_ordered(c) && c.shape.lds_hist) {   // (replicas: class_lds_layout)
+    c.shape.lds_bytes = sxplan::ordered_lds_bytes(sxplan::ordered_rstride_plain(c.max_bins), 1, 0);
+  }
+  c.shape.sparse_runs = 0;
+  c.shape.sparse_lds_bytes = 0;
+  if (c.runs_mode) {
+    // every wave owns 2 x 512 words of LDS (table keys + counts) and walks its own run of consecutive granules:
+    // member j gets K_j workgroups (in proportion to its granules) = K_j x waves runs.  Three workgroups of
+    // 512 per CU measured best at BASELINE config 5 (2.14 ms; one of 1024: 2.29 ms; thread counts that are not
+    // powers of two 2.4 ms); the kernel is bound by vector-instruction issue and HBM together, and 24 waves
+    // per CU is what its registers allow.
+    const int rthreads = cfg.threads > 0 ? c.shape.threads : 512;
+    const size_t need = (size_t)(rthreads / 64) * 2u * ((size_t)4 << SXMC_SPARSE_SMAX_LOG2);
+    std::vector<unsigned long long> sizes;
+    for (int idx : c.member_idx) sizes.push_back((unsigned long long)plans[(size_t)idx].sort->lsrc.size() * 64ull);
+    const int rbpc = std::min(cfg.bpc > 0 ? cfg.bpc : std::max(1, 1536 / rthreads),
+                              std::max(1, (int)((size_t)props.lds_per_cu / need)));
+    if (need > (size_t)props.lds_per_cu || !apportion_workgroups(sizes, props.cus * rbpc, rthreads, K)) {
+      if (is_ordered(c) && !g->order_blocked) {   // the ordered layout needs the runs: plan again without it
+        blocked = Blocked::order;
+        return;
       }
-    }
-    if (!c.shape.lds_hist && g->sparse_ready && !c.runs_mode) {
-      int cshift = 32;
-      for (int idx : c.member_idx) cshift = std::min(cshift, g->members[idx]->coarse_shift);
-      c.shape.lds_bytes = ((size_t)4 + ((size_t)1 << (32 - cshift - 5))) * 4;   // header + largest coarse filter
-      // a filter of more than half the LDS leaves room for one workgroup per CU: make it a full one
-      if (g->cfg_threads <= 0 && c.shape.lds_bytes * 2 > (size_t)props.lds_per_cu) c.shape.threads = 1024;
-    }
-    if (g->cfg_threads <= 0 && g->cfg_bpc <= 0 && c.shape.lds_hist && !bucketed && !c.runs_mode) {
-      // A SHORT launch with its histograms in LDS (BASELINE config 2: 80 MB, ~10 units per lane): the launch's fixed
-      // cost is most of it, and a large part of that is the flush -- every workgroup sends its private histogram
-      // to HBM with memory-side atomics.  ONE workgroup of 1024 per CU instead of two of 512 keeps the lanes and
-      // halves the histograms to flush: config 2, same box, 17.6 us against 21.0 (35 700 against 33 200 evals/s;
-      // 768 x 1: 18.0, 512 x 1: 21.5, 256 x 4: 27.5, 1024 x 2: 19.6; profiles/r03_c2_sweep_policy_x_shape.log).
-      double bytes = 0;
-      for (int idx : c.member_idx) bytes += (double)g->h_descs[(size_t)idx].nvec * SXMC_VEC * 4.0 * std::max(1, c.shape.nslot);
-      if (bytes < 2.0e8) {
-        c.shape.threads = 1024;
-      }
-    }
-    int threads = c.shape.threads;  // (shadows the group-wide default above)
-
-    // ---- the members' descriptors; bucketed members: lay the table out now that the shape is known
-    std::vector<SxSignalDesc> descs;
-    unsigned long long prefix = 0;
-    for (size_t q = 0; q < c.member_idx.size(); q++) {
-      const int idx = c.member_idx[q];
-      SxSignalDesc d = fill_descs[(size_t)idx];
-      sxmc_hist* h = g->members[idx];
-      if (c.shape.pre_width == 1 || c.shape.pre_width == 2) {
-        SampleStore& st = *h->store;
-        std::lock_guard<std::mutex> lock(st.pre_mutex);
-        void* pre = st.find_pre(c.pre_mask, c.shape.pre_width);
-        if (!pre) {
-          const size_t npad = h->nvec * SXMC_VEC;
-          SX_HIP(hipMalloc(&pre, std::max<size_t>(npad * (size_t)c.shape.pre_width, 16)));
-          st.pre.push_back({c.pre_mask, c.shape.pre_width, pre});
-          SX_HIP(sx_launch_prebin(g->d_descs + idx, npad, c.pre_mask, c.shape.pre_width, pre, nullptr));
-          SX_HIP(hipDeviceSynchronize());
-        }
-        d.pre = pre;
-      }
-      if (bucketed) {
-        const int runs = c.runs_mode ? std::max(1, K[q]) * (threads / 64) : 1;
-        const SampleStore::Bucketed* bk = nullptr;
-        rc = get_bucketed(h, plans[(size_t)idx].sort, plans[(size_t)idx].fields, runs, &bk);
-        if (rc) return rc;
-        d.cols = bk->d_cols;
-        d.col_pitch = bk->pitch;
-        d.nsamples = bk->ngranules * 256;
-        d.nvec = bk->ngranules * 64;
-        d.pre = bk->d_gpre;
-        d.edges = bk->d_gedge;
-        d.boxes = bk->d_gbox;
-        if (boxed) {   // (launch-wide: the largest of the members' mean extents)
-          c.box_dx = std::max(c.box_dx, (float)bk->box_dx);
-          c.box_dt = std::max(c.box_dt, (float)bk->box_dt);
-        }
-        g->member_bucket[(size_t)idx] = bk;
-        // CODES: ordered table, histogram in LDS, 2 to 4 streamed fields, every systematic on them affine (one
-        // coefficient) -- the conditions fill_ordered_body's kCodes states at compile time
-        // (Histograms beyond LDS, counted at the event bins over run-walked tables -- BASELINE config 5 -- were given
-        // codes too and measured: bit-identical, and SLOWER, 4.0 ms against 2.1-2.6.  With 200 bins per written
-        // observable a code step is 1/220 of a bin, 0.8 % of the samples are ambiguous and 87 % of the 256-sample
-        // units hold one; the fix-up then runs almost everywhere.  Codes pay where bins are coarse against 2^-16 of
-        // the window: not offered there.)
-        bool affine = ordered && c.shape.lds_hist && c.shape.nobs >= 1 && (boxed || c.shape.nslot - 1 >= 2) &&
-                      c.shape.nslot - 1 <= SXMC_MAX_QSLOTS && !c.runs_mode && codes_enabled(g);
-        for (unsigned w : c.prog) affine = affine && ((int)((w >> 4) & 15u) == c.shape.nslot - 1 || ((w >> 12) & 15u) == 0u);
-        if (affine) {
-          rc = get_bucket_codes(h, bk, d);
-          if (rc) return rc;
-          if (bk->d_qcol) {
-            d.qcol = bk->d_qcol;
-            for (int m = 0; m < bk->nq; m++) {
-              d.qbase[m] = bk->qbase[m];
-              d.qstep[m] = bk->qstep[m];
-            }
-            c.codes = true;
-          }
-        }
-        if (boxed && !d.qcol) {   // (no table of codes -- too many ambiguous rows, rows outside the window, no memory: the
-                                  //  boxed form has no float stream of its own.  Planned again without it.)
-          g->box_blocked = true;
-          return group_rebuild(g);
-        }
-      }
-      d.vec_start = prefix;
-      prefix += d.nvec;
-      d.step_gate = g->d_ticket + 8;     // (read by the measurement build's gated fill only)
-      descs.push_back(d);
-    }
-    c.total_vec = prefix;
-    // Over codes, where nothing was asked for: TWO workgroups of 512 lanes per CU, each with half the replicas of the
-    // LDS histogram.  One of 768 or 1024 with all four replicas is as fast alone (config 3, alternating on one box:
-    // 81.0-81.6 us against 81.3-81.4 and 79.6-82.8), but with other chains' launches in flight -- the fake experiments
-    // of an ensemble -- two workgroups per CU let one launch's tail run under the next one's start: 13 280 chain-steps/s
-    // against 12 430 and 12 840 (profiles/r04b_codes_shapes_ab.log).  A histogram too large for two workgroups' LDS:
-    // one of 768.  sxmc_group_optimize times these shapes on the box it runs on.
-    const bool codes_auto = c.codes && g->cfg_threads <= 0 && g->cfg_bpc <= 0;
-    bool codes_two = false;
-    if (codes_auto) {
-      const size_t one = std::max(c.shape.lds_bytes, ordered_lds_bytes(cls_max_bins, 1, 0)) + ordered_queue_bytes(kMinQueueLog);
-      codes_two = 2 * (one + 2048) <= (size_t)props.lds_per_cu && c.shape.nobs == 1;   // (+ the padded form's guard rows)
-      threads = c.shape.threads = codes_two ? 512 : 768;
-      // (boxed form: one workgroup of 1024 lanes.  Config 3, one box, alternating: 64.6-66.4 us against 68.3 for 768 x 1
-      // and 73.0-73.3 for 512 x 2 -- profiles/r05_boxed_ab.log)
-      if (boxed) {
-        static const int forced = [] {   // (SXMC_BOX_LANES, measurement build: 512 = two workgroups of 512 per CU, 768, 1024)
-          const char* e = measure_env("SXMC_BOX_LANES");
-          return e ? std::atoi(e) : 0;
-        }();
-        codes_two = forced == 512 && codes_two;
-        threads = c.shape.threads = forced == 512 ? 512 : forced == 768 ? 768 : 1024;
-      }
-    }
-    // Waves per CU.  The fill is a stream: HBM delivers most with about 32 KiB of loads in flight per CU,
-    // which is 512 lanes with one unit (3-4 columns x 16 bytes) each; more waves only queue up (measured
-    // -8 % at BASELINE config 3).  Members whose per-sample arithmetic is long (a run-time decoded program
-    // of two or more systematics, the shape-agnostic kernel) or that probe L2 per sample (histograms
-    // beyond LDS) need the second set of waves to hide it.
-    const double stream_bytes = (double)c.total_vec * SXMC_VEC * 4.0 * std::max(1, c.shape.nslot - (ordered ? 1 : 0));
-    const bool light = c.shape.lds_hist && (c.shape.nobs > 0 || ordered) &&
-                       (c.shape.static_prog >= 0 || c.shape.rtc_fill || cls_nsyst <= 1) &&
-                       stream_bytes >= 2.0e8;  // (short launches are ramp-bound: they take all the waves)
-    c.light = light;
-    int bpc = g->cfg_bpc > 0 ? g->cfg_bpc : codes_auto ? (codes_two ? 2 : 1) : std::max(1, (light ? 512 : 1024) / threads);
-    const size_t lds_need = std::max(c.shape.lds_bytes, c.shape.sparse_lds_bytes);
-    const int lds_limit = std::max(1, (int)((size_t)props.lds_per_cu / std::max<size_t>(lds_need, 1)));
-    bpc = std::min(bpc, lds_limit);
-    c.shape.lds_layout = 0;
-    if (ordered && c.shape.lds_hist) {
-      // replicas of the LDS histogram (fill_ordered_body): as many as the workgroup's share of LDS holds, up to 4
-      unsigned rlog = 0;
-      // (SXMC_LDS_RESERVE, measurement build: bytes of the CU's LDS the fill leaves to other kernels' workgroups)
-      static const size_t lds_reserve = [] {
-        const char* e = measure_env("SXMC_LDS_RESERVE");
-        return e ? (size_t)std::max(0, std::atoi(e)) : (size_t)0;
-      }();
-      const size_t share = ((size_t)props.lds_per_cu - lds_reserve) / (size_t)std::max(1, bpc) -
-                           (fused_step_requested(g) ? 16 * 1024 : 0);
-      const size_t qreserve = c.codes ? ordered_queue_bytes(kMinQueueLog) : 0;   // (room for the smallest queues)
-      // (SXMC_ORDERED_REPLICAS_LOG2, measurement: fewer replicas leave LDS for a second workgroup per CU -- of another
-      // chain's launch, say)
-      static const unsigned rlog_max = [] {
-        const char* e = measure_env("SXMC_ORDERED_REPLICAS_LOG2");
-        return e ? (unsigned)std::min(std::max(std::atoi(e), 0), 2) : 2u;
-      }();
-      while (rlog < rlog_max && ordered_lds_bytes(cls_max_bins, 1, rlog + 1) + qreserve <= share) rlog++;
-      c.shape.lds_layout = ordered_rstride(cls_max_bins) | (rlog << 24);
-      c.shape.lds_bytes = ordered_lds_bytes(cls_max_bins, 1, rlog);
-      c.plain_rstride = ordered_rstride(cls_max_bins);
-      if (c.codes) {
-        // the padded form of the histogram where every member qualifies (one observable binned per sample, the
-        // outermost dimension) and it fits with room for the smallest queue; then the queues of ambiguous rows, in
-        // what the replicas leave of the workgroup's share
-        c.padded_rstride = 0;
-        if (c.shape.nobs == 1) {
-          unsigned rs = 0;
-          bool all = true;
-          for (size_t q = 0; q < c.member_idx.size(); q++) {
-            const sxmc_hist* h = g->members[(size_t)c.member_idx[q]];
-            const long long nb = descs[q].nbins[0];   // (slot 0 of the compacted problem)
-            // (ordered form: the observable binned per sample must be the histogram's outermost dimension; the boxed
-            // form makes it the outermost dimension of the LDS copy wherever it sits)
-            const long long S = boxed ? (nb >= 1 ? (long long)h->total_nbins / nb : 0) : descs[q].bin_stride[0];
-            all = all && S >= 1 && nb >= 1 && S * nb == (long long)h->total_nbins && S * (nb + 2) < (1ll << 22);
-            if (boxed) all = all && descs[q].bin_stride[0] >= 1 && (long long)h->total_nbins % ((long long)descs[q].bin_stride[0] * nb) == 0;
-            if (all) rs = std::max(rs, ordered_rstride_padded(h->total_nbins, (int)nb));
-          }
-          if (all && rs) {
-            unsigned prl = 0;
-            auto bytes = [&](unsigned rl) { return (4 + ((size_t)rs << rl) + 64) * 4 + ordered_queue_bytes(kMinQueueLog); };
-            if (bytes(0) <= share) {
-              while (prl < rlog_max && bytes(prl + 1) <= share) prl++;
-              c.padded_rstride = rs;
-              c.shape.lds_layout = rs | (prl << 24) | (1u << 27);
-              c.shape.lds_bytes = (4 + ((size_t)rs << prl) + 64) * 4;
-            }
-          }
-        }
-        const unsigned qlog = share > c.shape.lds_bytes ? ordered_queue_log(share - c.shape.lds_bytes, g->cfg_queue_log) : 0;
-        c.shape.lds_layout |= qlog << 28;
-        c.shape.lds_bytes += ordered_queue_bytes(qlog);
-        if (!qlog) c.codes = false;   // (no room for queues: the kernel streams the float columns)
-        if (boxed && (!qlog || !c.padded_rstride)) {   // (the boxed form exists only in the padded form with queues)
-          for (LaunchClass& cc : g->classes) free_class(cc);   // (what this pass has allocated so far)
-          g->box_blocked = true;
-          return group_rebuild(g);
-        }
-      } else if (boxed) {
-        for (LaunchClass& cc : g->classes) free_class(cc);
-        g->box_blocked = true;
-        return group_rebuild(g);
-      }
-    }
-    unsigned long long grid = (unsigned long long)props.cus * bpc;
-    const unsigned long long want = (c.total_vec + threads - 1) / threads;  // >= 1 unit per lane
-    grid = std::max<unsigned long long>(1, std::min(grid, want));
-    c.shape.grid = c.total_vec ? (int)grid : 0;
-    if (c.runs_mode) {
-      int used = 0;
-      for (int k : K) used += k;
-      c.shape.grid = used;
-      c.shape.sparse_runs = 1;
-    }
-    SX_HIP(hipMalloc((void**)&c.d_descs, sizeof(SxSignalDesc) * descs.size()));
-    SX_HIP(hipMemcpy(c.d_descs, descs.data(), sizeof(SxSignalDesc) * descs.size(), hipMemcpyHostToDevice));
-    if (g->sparse_ready && !c.shape.lds_hist) {
-      std::vector<SxSignalDesc> sd = descs;
-      for (size_t q = 0; q < sd.size(); q++) {
-        sxmc_hist* h = g->members[c.member_idx[q]];
-        make_sparse_desc(h, sd[q]);
-        sd[q].sparse_filter = sparse_descs[(size_t)c.member_idx[q]].sparse_filter;  // shared tables
-        sd[q].sparse_table = sparse_descs[(size_t)c.member_idx[q]].sparse_table;
-        sd[q].sparse_coarse = sparse_descs[(size_t)c.member_idx[q]].sparse_coarse;
-        if (c.runs_mode) {
-          // members that look up the same set of bins share ONE set of bucket tables (one data set, one binning)
-          const sxmc_hist* owner = h;
-          for (size_t k = 0; k < q; k++) {
-            const sxmc_hist* o = g->members[c.member_idx[k]];
-            if (o->btab_valid && o->btab_mask == h->btab_mask && o->total_nbins == h->total_nbins &&
-                o->targets == h->targets) {
-              owner = o;
-              break;
-            }
-          }
-          sd[q].sparse_dir = owner->d_bdir;
-          sd[q].sparse_tkeys = owner->d_btkeys;
-          sd[q].sparse_tslot = owner->d_btslot;
-          sd[q].pre = g->member_bucket[(size_t)c.member_idx[q]]->d_gkp;   // {bucket key, bin offset} per granule
-        }
-      }
-      SX_HIP(hipMalloc((void**)&c.d_descs_sparse, sizeof(SxSignalDesc) * sd.size()));
-      SX_HIP(hipMemcpy(c.d_descs_sparse, sd.data(), sizeof(SxSignalDesc) * sd.size(), hipMemcpyHostToDevice));
-    }
-    if (c.shape.grid > 0) {
-      std::vector<SxSegment> segs;
-      std::vector<unsigned> blk_off;
-      if (c.runs_mode) {
-        interleaved_segments(descs, K, threads, c.shape.grid, segs, blk_off);
-        c.partition = 2;
-      } else {
-        // Bucketed tables are sorted by bin, so a member's workgroups can work as TEAMS over contiguous parts of it
-        // (sxplan::interleaved_segments): a workgroup of a team of 7 sees a third of the histogram's bins, and the
-        // flush -- one memory-side atomic per non-zero bin of every workgroup, 1.3 M per launch at config 3 -- sends
-        // a third of the atomics, against a coarser interleaving of the stream.  Which wins depends on the BOX
-        // (profiles/r03_c3_teams_sweep.log: 3 teams 129.4 us against 133.4-134.4 on one,
-        // 128.4 against 124.9 on another, each consistently over alternating runs), so the default is one team and
-        // sxmc_group_optimize tries three on the box it runs on (SXMC_PART_GROUPS forces a count for A/B runs).
-        static const int forced_groups = [] {
-          const char* e = measure_env("SXMC_PART_GROUPS");
-          return e ? std::atoi(e) : 0;
-        }();
-        // (the boxed form, where nothing was asked for: 20 teams -- a workgroup then sees a twentieth of the sorted order,
-        // its bucket or two, and flushes as few bins.  One box, alternating, two rounds (profiles/r05_boxed_teams_ab.log):
-        // fill 63.4-63.5 us and step 77.9 against 65.0-65.1 and 79.9-80.0 for one team; 3-10 teams in between.)
-        const int groups = (bucketed && c.shape.lds_hist)
-                               ? (forced_groups > 0 ? forced_groups : g->cfg_teams > 0 ? g->cfg_teams : boxed ? 20 : 1) : 1;
-        c.teams = groups;
-        build_partition(descs, c.shape.grid, threads, g->cfg_partition, segs, blk_off, c.partition, bucketed ? 64 : 1,
-                        groups);
-      }
-      SX_HIP(hipMalloc((void**)&c.d_segs, sizeof(SxSegment) * std::max<size_t>(segs.size(), 1)));
-      SX_HIP(hipMalloc((void**)&c.d_blk_off, sizeof(unsigned) * blk_off.size()));
-      if (!segs.empty()) {
-        SX_HIP(hipMemcpy(c.d_segs, segs.data(), sizeof(SxSegment) * segs.size(), hipMemcpyHostToDevice));
-      }
-      SX_HIP(hipMemcpy(c.d_blk_off, blk_off.data(), sizeof(unsigned) * blk_off.size(), hipMemcpyHostToDevice));
+      c.runs_mode = false;   // (more such members than workgroups: the table stays in sorted order)
+    } else {
+      c.shape.threads = rthreads;
+      c.shape.sparse_lds_bytes = need;
     }
   }
+  if (!c.shape.lds_hist && g->sparse_ready && !c.runs_mode) {
+    int cshift = 32;
+    for (int idx : c.member_idx) cshift = std::min(cshift, g->members[idx]->coarse_shift);
+    c.shape.lds_bytes = ((size_t)4 + ((size_t)1 << (32 - cshift - 5))) * 4;   // header + largest coarse filter
+    // a filter of more than half the LDS leaves room for one workgroup per CU: make it a full one
+    if (cfg.threads <= 0 && c.shape.lds_bytes * 2 > (size_t)props.lds_per_cu) c.shape.threads = 1024;
+  }
+  if (cfg.threads <= 0 && cfg.bpc <= 0 && c.shape.lds_hist && !is_bucketed(c) && !c.runs_mode) {
+    // A SHORT launch with its histograms in LDS (BASELINE config 2: 80 MB, ~10 units per lane): the launch's fixed
+    // cost is most of it, and a large part of that is the flush -- every workgroup sends its private histogram
+    // to HBM with memory-side atomics.  ONE workgroup of 1024 per CU instead of two of 512 keeps the lanes and
+    // halves the histograms to flush: config 2, same box, 17.6 us against 21.0 (35 700 against 33 200 evals/s;
+    // 768 x 1: 18.0, 512 x 1: 21.5, 256 x 4: 27.5, 1024 x 2: 19.6; profiles/r03_c2_sweep_policy_x_shape.log).
+    double bytes = 0;
+    for (int idx : c.member_idx) bytes += (double)g->h_descs[(size_t)idx].nvec * SXMC_VEC * 4.0 * std::max(1, c.shape.nslot);
+    if (bytes < 2.0e8) {
+      c.shape.threads = 1024;
+    }
+  }
+}
 
-  // BOXED plans, cfg_box < 0 (the default): the boxed form is fast only while few boxes straddle an edge, which depends on
-  // the parameters of the evaluation.  The same members are therefore planned a second time in the ORDERED form (a twin
-  // group: its own tables, partition, launch shape), group_fill launches the plan `fill_form` names, and the host moves
-  // that between flushes of a walk (sxmc_group_adapt_fill_form).  Until it is asked to, the ordered form runs: a caller
-  // that never asks gets round 4's kernel.  No twin (the ordered form does not apply): the plan is built again without boxes.
-  if (!g->is_twin) {
-    bool any_boxed = false;
-    for (const LaunchClass& c : g->classes) any_boxed = any_boxed || c.shape.pre_width == 6;
-    if (any_boxed && g->cfg_box < 0) {
-      if (!g->twin) {
-        g->twin = new sxmc_group;
-        g->twin->is_twin = true;
+// ---- the tables of a class's members, now that the shape is known (pre-binned column, bucketed copy, codes), and their
+// descriptors as the fill reads them
+int class_tables(sxmc_group* g, const std::vector<MemberPlan>& plans, const std::vector<int>& K, LaunchClass& c,
+                 std::vector<SxSignalDesc>& descs, Blocked& blocked) {
+  const bool boxed = is_boxed(c);
+  unsigned long long prefix = 0;
+  for (size_t q = 0; q < c.member_idx.size(); q++) {
+    const int idx = c.member_idx[q];
+    SxSignalDesc d = plans[(size_t)idx].desc;
+    sxmc_hist* h = g->members[idx];
+    if (c.shape.pre_width == 1 || c.shape.pre_width == 2) {
+      SampleStore& st = *h->store;
+      std::lock_guard<std::mutex> lock(st.pre_mutex);
+      void* pre = st.find_pre(c.pre_mask, c.shape.pre_width);
+      if (!pre) {
+        const size_t npad = h->nvec * SXMC_VEC;
+        SX_HIP(hipMalloc(&pre, std::max<size_t>(npad * (size_t)c.shape.pre_width, 16)));
+        st.pre.push_back({c.pre_mask, c.shape.pre_width, pre});
+        SX_HIP(sx_launch_prebin(g->d_descs + idx, npad, c.pre_mask, c.shape.pre_width, pre, nullptr));
+        SX_HIP(hipDeviceSynchronize());
       }
-      sxmc_group* t = g->twin;
-      t->members = g->members;
-      t->cfg_box = 0;
-      t->cfg_threads = g->cfg_threads;
-      t->cfg_bpc = g->cfg_bpc;
-      t->cfg_partition = g->cfg_partition;
-      t->cfg_teams = g->cfg_teams;
-      t->cfg_queue_log = g->cfg_queue_log;
-      t->cfg_rtc = g->cfg_rtc;
-      t->cfg_codes = g->cfg_codes;
-      t->cfg_order = g->cfg_order;
-      t->cfg_prebin = g->cfg_prebin;
-      t->cfg_bucket = g->cfg_bucket;
-      t->cfg_fused = g->cfg_fused;
-      rc = group_rebuild(t);
+      d.pre = pre;
+    }
+    if (is_bucketed(c)) {
+      const int runs = c.runs_mode ? std::max(1, K[q]) * (c.shape.threads / 64) : 1;
+      const SampleStore::Bucketed* bk = nullptr;
+      int rc = get_bucketed(h, plans[(size_t)idx].sort, plans[(size_t)idx].fields, runs, &bk);
       if (rc) return rc;
-      bool ok = !t->classes.empty();
-      for (const LaunchClass& c : t->classes) ok = ok && c.shape.pre_width != 6;
-      if (!ok) {
-        g->box_blocked = true;
-        return group_rebuild(g);
+      d.cols = bk->d_cols;
+      d.col_pitch = bk->pitch;
+      d.nsamples = bk->ngranules * 256;
+      d.nvec = bk->ngranules * 64;
+      d.pre = bk->d_gpre;
+      d.edges = bk->d_gedge;
+      d.boxes = bk->d_gbox;
+      if (boxed) {   // (launch-wide: the largest of the members' mean extents)
+        c.box_dx = std::max(c.box_dx, (float)bk->box_dx);
+        c.box_dt = std::max(c.box_dt, (float)bk->box_dt);
       }
-      for (LaunchClass& c : g->classes) c.dual = c.shape.pre_width == 6;
-    } else if (g->twin && !any_boxed) {
-      for (LaunchClass& c : g->twin->classes) free_class(c);
-      g->twin->classes.clear();
+      g->member_bucket[(size_t)idx] = bk;
+      // CODES: ordered table, histogram in LDS, 2 to 4 streamed fields, every systematic on them affine (one
+      // coefficient) -- the conditions fill_ordered_body's kCodes states at compile time
+      // (Histograms beyond LDS, counted at the event bins over run-walked tables -- BASELINE config 5 -- were given
+      // codes too and measured: bit-identical, and SLOWER, 4.0 ms against 2.1-2.6.  With 200 bins per written
+      // observable a code step is 1/220 of a bin, 0.8 % of the samples are ambiguous and 87 % of the 256-sample
+      // units hold one; the fix-up then runs almost everywhere.  Codes pay where bins are coarse against 2^-16 of
+      // the window: not offered there.)
+      bool affine = is_ordered(c) && c.shape.lds_hist && c.shape.nobs >= 1 && (boxed || c.shape.nslot - 1 >= 2) &&
+                    c.shape.nslot - 1 <= SXMC_MAX_QSLOTS && !c.runs_mode && codes_enabled(g);
+      for (unsigned w : c.prog) affine = affine && ((int)((w >> 4) & 15u) == c.shape.nslot - 1 || ((w >> 12) & 15u) == 0u);
+      if (affine) {
+        rc = get_bucket_codes(h, bk, d);
+        if (rc) return rc;
+        if (bk->d_qcol) {
+          d.qcol = bk->d_qcol;
+          for (int m = 0; m < bk->nq; m++) {
+            d.qbase[m] = bk->qbase[m];
+            d.qstep[m] = bk->qstep[m];
+          }
+          c.codes = true;
+        }
+      }
+      if (boxed && !d.qcol) {   // (no table of codes -- too many ambiguous rows, rows outside the window, no memory: the
+                                //  boxed form has no float stream of its own.  Planned again without it.)
+        blocked = Blocked::box;
+        return SXMC_OK;
+      }
     }
-    if (!(any_boxed && g->cfg_box < 0)) g->fill_form = 1;   // (no twin: the plan's own launches)
-    else if (g->fill_form != 1) g->fill_form = 2;
+    d.vec_start = prefix;
+    prefix += d.nvec;
+    d.step_gate = g->d_ticket + 8;     // (read by the measurement build's gated fill only)
+    descs.push_back(d);
   }
+  c.total_vec = prefix;
+  return SXMC_OK;
+}
 
-  g->seen.resize((size_t)n);
-  g->seen_points.resize((size_t)n);
+// Over codes, where nothing was asked for: TWO workgroups of 512 lanes per CU, each with half the replicas of the
+// LDS histogram.  One of 768 or 1024 with all four replicas is as fast alone (config 3, alternating on one box:
+// 81.0-81.6 us against 81.3-81.4 and 79.6-82.8), but with other chains' launches in flight -- the fake experiments
+// of an ensemble -- two workgroups per CU let one launch's tail run under the next one's start: 13 280 chain-steps/s
+// against 12 430 and 12 840 (profiles/r04b_codes_shapes_ab.log).  A histogram too large for two workgroups' LDS:
+// one of 768.  sxmc_group_optimize times these shapes on the box it runs on.
+// Sets the class's threads; returns its workgroups per CU, or 0 where the shape is not this function's to choose.
+int class_codes_shape(const sxmc_group* g, const DeviceProps& props, LaunchClass& c) {
+  if (!(c.codes && g->plan_cfg.threads <= 0 && g->plan_cfg.bpc <= 0)) return 0;
+  const size_t one = std::max(c.shape.lds_bytes, sxplan::ordered_lds_bytes(sxplan::ordered_rstride_plain(c.max_bins), 1, 0)) +
+                     ordered_queue_bytes(kMinQueueLog);
+  bool codes_two = 2 * (one + 2048) <= (size_t)props.lds_per_cu && c.shape.nobs == 1;   // (+ the padded form's guard rows)
+  c.shape.threads = codes_two ? 512 : 768;
+  // (boxed form: one workgroup of 1024 lanes.  Config 3, one box, alternating: 64.6-66.4 us against 68.3 for 768 x 1
+  // and 73.0-73.3 for 512 x 2 -- profiles/r05_boxed_ab.log)
+  if (is_boxed(c)) {
+    static const int forced = [] {   // (SXMC_BOX_LANES, measurement build: 512 = two workgroups of 512 per CU, 768, 1024)
+      const char* e = measure_env("SXMC_BOX_LANES");
+      return e ? std::atoi(e) : 0;
+    }();
+    codes_two = forced == 512 && codes_two;
+    c.shape.threads = forced == 512 ? 512 : forced == 768 ? 768 : 1024;
+  }
+  return codes_two ? 2 : 1;
+}
+
+// Waves per CU.  The fill is a stream: HBM delivers most with about 32 KiB of loads in flight per CU,
+// which is 512 lanes with one unit (3-4 columns x 16 bytes) each; more waves only queue up (measured
+// -8 % at BASELINE config 3).  Members whose per-sample arithmetic is long (a run-time decoded program
+// of two or more systematics, the shape-agnostic kernel) or that probe L2 per sample (histograms
+// beyond LDS) need the second set of waves to hide it.  codes_bpc: class_codes_shape's answer.
+int class_waves_per_cu(const sxmc_group* g, const DeviceProps& props, LaunchClass& c, int codes_bpc) {
+  int cls_nsyst = 0;
+  for (int idx : c.member_idx) cls_nsyst = std::max(cls_nsyst, g->h_descs[(size_t)idx].nsyst);
+  const bool ordered = is_ordered(c);
+  const double stream_bytes = (double)c.total_vec * SXMC_VEC * 4.0 * std::max(1, c.shape.nslot - (ordered ? 1 : 0));
+  c.light = c.shape.lds_hist && (c.shape.nobs > 0 || ordered) &&
+            (c.shape.static_prog >= 0 || c.shape.rtc_fill || cls_nsyst <= 1) &&
+            stream_bytes >= 2.0e8;  // (short launches are ramp-bound: they take all the waves)
+  int bpc = g->plan_cfg.bpc > 0 ? g->plan_cfg.bpc : codes_bpc ? codes_bpc : std::max(1, (c.light ? 512 : 1024) / c.shape.threads);
+  const size_t lds_need = std::max(c.shape.lds_bytes, c.shape.sparse_lds_bytes);
+  const int lds_limit = std::max(1, (int)((size_t)props.lds_per_cu / std::max<size_t>(lds_need, 1)));
+  return std::min(bpc, lds_limit);
+}
+
+// The LDS of an ordered or boxed class with its histograms in LDS: replicas, padded or plain form, queues
+// (sxplan::ordered_lds_layout) in the workgroup's share of the CU's LDS.
+void class_lds_layout(sxmc_group* g, const DeviceProps& props, LaunchClass& c, const std::vector<SxSignalDesc>& descs,
+                      int bpc, Blocked& blocked) {
+  c.shape.lds_layout = 0;
+  if (!(is_ordered(c) && c.shape.lds_hist)) return;
+  // (SXMC_LDS_RESERVE, measurement build: bytes of the CU's LDS the fill leaves to other kernels' workgroups)
+  static const size_t lds_reserve = [] {
+    const char* e = measure_env("SXMC_LDS_RESERVE");
+    return e ? (size_t)std::max(0, std::atoi(e)) : (size_t)0;
+  }();
+  // (SXMC_ORDERED_REPLICAS_LOG2, measurement: fewer replicas leave LDS for a second workgroup per CU -- of another
+  // chain's launch, say)
+  static const unsigned rlog_max = [] {
+    const char* e = measure_env("SXMC_ORDERED_REPLICAS_LOG2");
+    return e ? (unsigned)std::min(std::max(std::atoi(e), 0), 2) : 2u;
+  }();
+  sxplan::OrderedLdsIn in;
+  in.max_bins = c.max_bins;
+  in.codes = c.codes;
+  in.share = ((size_t)props.lds_per_cu - lds_reserve) / (size_t)std::max(1, bpc) - (fused_step_requested(g) ? 16 * 1024 : 0);
+  in.rlog_max = rlog_max;
+  in.queue_cap = g->plan_cfg.queue_log;
+  // the padded form of the histogram where every member qualifies (one observable binned per sample, the
+  // outermost dimension) and it fits with room for the smallest queue; then the queues of ambiguous rows, in
+  // what the replicas leave of the workgroup's share
+  if (c.codes && c.shape.nobs == 1) in.padded_rstride = sxplan::padded_rstride_of(descs, is_boxed(c));
+  // (lds.fits is deliberately not consulted: a layout beyond the share was never refused here, and refusing it now
+  // would change which plans exist)
+  const sxplan::OrderedLds lds = sxplan::ordered_lds_layout(in);
+  c.shape.lds_layout = lds.word;
+  c.shape.lds_bytes = lds.bytes;
+  if (c.codes) {
+    c.padded_rstride = lds.padded ? in.padded_rstride : 0;
+    if (!lds.qlog) c.codes = false;   // (no room for queues: the kernel streams the float columns)
+  }
+  // (the boxed form exists only over codes, in the padded form with queues)
+  if (is_boxed(c) && (!in.codes || !lds.qlog || !lds.padded)) blocked = Blocked::box;
+}
+
+// The class's descriptors on the device, in both flavours.
+int class_upload_descs(sxmc_group* g, LaunchClass& c, const std::vector<SxSignalDesc>& descs) {
+  SX_HIP(upload(descs, &c.d_descs));
+  if (!(g->sparse_ready && !c.shape.lds_hist)) return SXMC_OK;
+  std::vector<SxSignalDesc> sd = descs;
+  for (size_t q = 0; q < sd.size(); q++) {
+    sxmc_hist* h = g->members[c.member_idx[q]];
+    const SxSignalDesc& shared = g->h_descs_sparse[(size_t)c.member_idx[q]];
+    make_sparse_desc(h, sd[q]);
+    sd[q].sparse_filter = shared.sparse_filter;  // shared tables
+    sd[q].sparse_table = shared.sparse_table;
+    sd[q].sparse_coarse = shared.sparse_coarse;
+    if (c.runs_mode) {
+      // members that look up the same set of bins share ONE set of bucket tables (one data set, one binning)
+      const sxmc_hist* owner = h;
+      for (size_t k = 0; k < q; k++) {
+        const sxmc_hist* o = g->members[c.member_idx[k]];
+        if (o->btab_valid && o->btab_mask == h->btab_mask && o->total_nbins == h->total_nbins &&
+            o->targets == h->targets) {
+          owner = o;
+          break;
+        }
+      }
+      sd[q].sparse_dir = owner->d_bdir;
+      sd[q].sparse_tkeys = owner->d_btkeys;
+      sd[q].sparse_tslot = owner->d_btslot;
+      sd[q].pre = g->member_bucket[(size_t)c.member_idx[q]]->d_gkp;   // {bucket key, bin offset} per granule
+    }
+  }
+  SX_HIP(upload(sd, &c.d_descs_sparse));
+  return SXMC_OK;
+}
+
+// Who reads which units of the class's members.
+int class_partition(sxmc_group* g, LaunchClass& c, const std::vector<SxSignalDesc>& descs, const std::vector<int>& K) {
+  if (c.shape.grid <= 0) return SXMC_OK;
+  std::vector<SxSegment> segs;
+  std::vector<unsigned> blk_off;
+  std::vector<unsigned long long> nvec;
+  for (const SxSignalDesc& d : descs) nvec.push_back(d.nvec);
+  if (c.runs_mode) {
+    sxplan::interleaved_segments(nvec, K, c.shape.threads, c.shape.grid, segs, blk_off);
+    c.partition = 2;
+  } else {
+    // Bucketed tables are sorted by bin, so a member's workgroups can work as TEAMS over contiguous parts of it
+    // (sxplan::interleaved_segments): a workgroup of a team of 7 sees a third of the histogram's bins, and the
+    // flush -- one memory-side atomic per non-zero bin of every workgroup, 1.3 M per launch at config 3 -- sends
+    // a third of the atomics, against a coarser interleaving of the stream.  Which wins depends on the BOX
+    // (profiles/r03_c3_teams_sweep.log: 3 teams 129.4 us against 133.4-134.4 on one,
+    // 128.4 against 124.9 on another, each consistently over alternating runs), so the default is one team and
+    // sxmc_group_optimize tries three on the box it runs on (SXMC_PART_GROUPS forces a count for A/B runs).
+    static const int forced_groups = [] {
+      const char* e = measure_env("SXMC_PART_GROUPS");
+      return e ? std::atoi(e) : 0;
+    }();
+    // (the boxed form, where nothing was asked for: 20 teams -- a workgroup then sees a twentieth of the sorted order,
+    // its bucket or two, and flushes as few bins.  One box, alternating, two rounds (profiles/r05_boxed_teams_ab.log):
+    // fill 63.4-63.5 us and step 77.9 against 65.0-65.1 and 79.9-80.0 for one team; 3-10 teams in between.)
+    const bool bucketed = is_bucketed(c);
+    const int groups = (bucketed && c.shape.lds_hist)
+                           ? (forced_groups > 0 ? forced_groups : g->plan_cfg.teams > 0 ? g->plan_cfg.teams : is_boxed(c) ? 20 : 1) : 1;
+    c.teams = groups;
+    sxplan::build_partition(nvec, c.shape.grid, c.shape.threads, g->plan_cfg.partition, segs, blk_off, c.partition,
+                            bucketed ? 64 : 1, groups);
+  }
+  SX_HIP(upload(segs, &c.d_segs, 1));
+  SX_HIP(upload(blk_off, &c.d_blk_off));
+  return SXMC_OK;
+}
+
+// One class from its members' plans to a launch: shape, tables, LDS, grid, descriptors, partition.
+int plan_class(sxmc_group* g, const DeviceProps& props, const std::vector<MemberPlan>& plans, LaunchClass& c, Blocked& blocked) {
+  std::vector<int> K;   // runs mode: workgroups per member
+  class_threads_and_lds(g, props, plans, c, K, blocked);
+  if (blocked != Blocked::none) return SXMC_OK;
+  std::vector<SxSignalDesc> descs;
+  int rc = class_tables(g, plans, K, c, descs, blocked);
+  if (rc || blocked != Blocked::none) return rc;
+  const int codes_bpc = class_codes_shape(g, props, c);   // (sets shape.threads, which the next line reads)
+  const int bpc = class_waves_per_cu(g, props, c, codes_bpc);
+  class_lds_layout(g, props, c, descs, bpc, blocked);
+  if (blocked != Blocked::none) return SXMC_OK;
+  const unsigned long long want = (c.total_vec + c.shape.threads - 1) / c.shape.threads;  // >= 1 unit per lane
+  const unsigned long long grid = std::max<unsigned long long>(1, std::min((unsigned long long)props.cus * bpc, want));
+  c.shape.grid = c.total_vec ? (int)grid : 0;
+  if (c.runs_mode) {
+    int used = 0;
+    for (int k : K) used += k;
+    c.shape.grid = used;
+    c.shape.sparse_runs = 1;
+  }
+  rc = class_upload_descs(g, c, descs);
+  return rc ? rc : class_partition(g, c, descs, K);
+}
+
+// BOXED plans, plan_cfg.box < 0 (the default): the boxed form is fast only while few boxes straddle an edge, which depends on
+// the parameters of the evaluation.  The same members are therefore planned a second time in the ORDERED form (a twin
+// group: its own tables, partition, launch shape), group_fill launches the plan `fill_form` names, and the host moves
+// that between flushes of a walk (sxmc_group_adapt_fill_form).  Until it is asked to, the ordered form runs: a caller
+// that never asks gets round 4's kernel.  No twin (the ordered form does not apply): the plan is built again without boxes.
+int plan_twin(sxmc_group* g, Blocked& blocked) {
+  if (g->is_twin) return SXMC_OK;
+  bool any_boxed = false;
+  for (const LaunchClass& c : g->classes) any_boxed = any_boxed || is_boxed(c);
+  const bool two = any_boxed && g->plan_cfg.box < 0;
+  if (two) {
+    if (!g->twin) {
+      g->twin = new sxmc_group;
+      g->twin->is_twin = true;
+    }
+    sxmc_group* t = g->twin;
+    t->members = g->members;
+    t->plan_cfg = g->plan_cfg;
+    t->plan_cfg.box = 0;
+    int rc = group_rebuild(t);
+    if (rc) return rc;
+    bool ok = !t->classes.empty();
+    for (const LaunchClass& c : t->classes) ok = ok && !is_boxed(c);
+    if (!ok) {
+      blocked = Blocked::box;
+      return SXMC_OK;
+    }
+    for (LaunchClass& c : g->classes) c.dual = is_boxed(c);
+  } else if (g->twin && !any_boxed) {
+    for (LaunchClass& c : g->twin->classes) free_class(c);
+    g->twin->classes.clear();
+  }
+  if (!two) g->fill_form = 1;   // (no twin: the plan's own launches)
+  else if (g->fill_form != 1) g->fill_form = 2;
+  return SXMC_OK;
+}
+
+// One pass over the plan, from the members' descriptors to the classes' launches.  `blocked`: a step found the ordered or
+// the boxed form cannot be laid out; what the pass has allocated is freed by the next one's start.
+int plan_pass(sxmc_group* g, const DeviceProps& props, Blocked& blocked) {
+  // Descriptors may still be read by kernels in flight on another stream: rebuilds are rare
+  // (bindings change only during setup), so a device-wide sync is the simple safe choice.
+  SX_HIP(hipDeviceSynchronize());
+  const int n = (int)g->members.size();
+  g->h_descs.assign((size_t)n, SxSignalDesc{});
+  for (LaunchClass& c : g->classes) free_class(c);
+  g->classes.clear();
+  g->max_bins = 0;
+  g->max_points = 0;
+  g->same_points = n > 0;
+  g->plan_note.clear();
+
+  int threads = g->plan_cfg.threads > 0 ? g->plan_cfg.threads : 512;
+  if (threads < 64 || threads > 1024 || threads % 64) threads = 512;
+
+  for (int i = 0; i < n; i++) fill_desc(g->members[i], g->h_descs[i]);
+  if (!g->d_descs) SX_HIP(hipMalloc((void**)&g->d_descs, sizeof(SxSignalDesc) * std::max(n, 1)));
+  if (n) SX_HIP(hipMemcpy(g->d_descs, g->h_descs.data(), sizeof(SxSignalDesc) * n, hipMemcpyHostToDevice));
+
+  std::vector<MemberPlan> plans((size_t)n);
+  g->member_bucket.assign((size_t)n, nullptr);
   for (int i = 0; i < n; i++) {
+    const sxmc_hist* h = g->members[i];
+    g->max_bins = std::max(g->max_bins, h->total_nbins);
+    g->max_points = std::max<unsigned long long>(g->max_points, g->h_descs[i].npoints);
+    if (!h->has_points || h->npoints != g->members[0]->npoints) g->same_points = false;
+    int rc = plan_member(g, props, i, plans[(size_t)i]);
+    if (rc) return rc;
+    find_class(g, plans[(size_t)i], threads).member_idx.push_back(i);
+  }
+  int rc = build_sparse_descs(g);
+  if (rc) return rc;
+  for (LaunchClass& c : g->classes) {
+    rc = plan_class(g, props, plans, c, blocked);
+    if (rc || blocked != Blocked::none) return rc;
+  }
+  return plan_twin(g, blocked);
+}
+
+int group_rebuild(sxmc_group* g) {
+  TraceRange trace("sxmc: launch plan (tables, partitions, kernels)");
+  DeviceProps props;
+  int rc = get_props(props);
+  if (rc) return rc;
+  for (;;) {   // (at most three passes: each of the two flags is set once)
+    Blocked blocked = Blocked::none;
+    rc = plan_pass(g, props, blocked);
+    if (rc) return rc;
+    if (blocked == Blocked::none) break;
+    (blocked == Blocked::order ? g->order_blocked : g->box_blocked) = true;
+  }
+  const size_t n = g->members.size();
+  g->seen.resize(n);
+  g->seen_points.resize(n);
+  for (size_t i = 0; i < n; i++) {
     g->seen[i] = g->members[i]->version;
     g->seen_points[i] = g->members[i]->points_version;
   }
-  g->cfg_seen_threads = g->cfg_threads;
-  g->cfg_seen_bpc = g->cfg_bpc;
-  g->cfg_seen_partition = g->cfg_partition;
-  g->cfg_seen_teams = g->cfg_teams;
-  g->cfg_seen_prebin = g->cfg_prebin;
-  g->cfg_seen_bucket = g->cfg_bucket;
-  g->cfg_seen_order = g->cfg_order;
-  g->cfg_seen_box = g->cfg_box;
-  g->cfg_seen_rtc = g->cfg_rtc;
-  g->cfg_seen_codes = g->cfg_codes;
-  g->cfg_seen_queue_log = g->cfg_queue_log;
-  g->cfg_seen_fused = g->cfg_fused;
+  g->plan_cfg_seen = g->plan_cfg;
   g->plan_generation++;
   g->built = true;
   return SXMC_OK;
@@ -1318,12 +1117,7 @@ int group_update_points(sxmc_group* g) {
 }
 
 int group_refresh(sxmc_group* g) {
-  bool stale = !g->built || g->cfg_seen_threads != g->cfg_threads || g->cfg_seen_bpc != g->cfg_bpc ||
-               g->cfg_seen_partition != g->cfg_partition || g->cfg_seen_teams != g->cfg_teams ||
-               g->cfg_seen_prebin != g->cfg_prebin ||
-               g->cfg_seen_bucket != g->cfg_bucket || g->cfg_seen_rtc != g->cfg_rtc ||
-               g->cfg_seen_order != g->cfg_order || g->cfg_seen_codes != g->cfg_codes || g->cfg_seen_box != g->cfg_box ||
-               g->cfg_seen_queue_log != g->cfg_queue_log || g->cfg_seen_fused != g->cfg_fused;
+  bool stale = !g->built || !(g->plan_cfg_seen == g->plan_cfg);
   bool points = false;
   for (size_t i = 0; !stale && i < g->members.size(); i++) {
     if (g->seen[i] != g->members[i]->version) stale = true;
@@ -1448,7 +1242,7 @@ int group_fill(sxmc_group* g, hipStream_t s, bool sparse) {
   int rc = group_prepare_fill(g, s, sparse);
   if (rc) return rc;
   // (a boxed plan with an ordered twin: the launches of the plan fill_form names -- sxmc_group_adapt_fill_form)
-  sxmc_group* plan = (g->twin && !g->twin->classes.empty() && g->fill_form == 2 && g->cfg_box < 0) ? g->twin : g;
+  sxmc_group* plan = (g->twin && !g->twin->classes.empty() && g->fill_form == 2 && g->plan_cfg.box < 0) ? g->twin : g;
   for (LaunchClass& c : plan->classes) {
     // profiled launches (sxmc_group_profile) carry two events stamped with the dispatch's own begin and end
     const bool rec = g->prof && !t_capturing && g->prof_n < (int)g->ev0.size() && c.shape.grid > 0;

@@ -52,25 +52,17 @@ bool multigroup_prepare(sxmc_multigroup* mg) {
       // ordered fill: the kernel argument is the replica layout; as many replicas as fit beside the other chains'
       // (codes: the padded form of the histograms if the chains' histograms fit that way with the smallest queues; a plan
       // with two workgroups per CU leaves each of them half the CU's LDS)
+      sxplan::OrderedLdsIn in;
+      in.max_bins = c0.max_bins;
+      in.nchain = (int)C;
+      in.padded_rstride = c0.padded_rstride;
+      in.codes = c0.codes;   // (the queues of ambiguous rows, fill_ordered_body's CODES, are shared by the chains)
       const size_t per_cu = (size_t)std::max(1, c0.shape.grid / std::max(1, props.cus));
-      const size_t lds_share = (size_t)props.lds_per_cu / std::min<size_t>(per_cu, 2);
-      size_t rstride = c0.plain_rstride;
-      bool padded = false;
-      if (c0.codes && c0.padded_rstride &&
-          (4 + C * (size_t)c0.padded_rstride + 64) * 4 + ordered_queue_bytes(kMinQueueLog) <= lds_share) {
-        rstride = c0.padded_rstride;
-        padded = true;
-      }
-      const size_t reserve = c0.codes ? ordered_queue_bytes(kMinQueueLog) : 0;
-      unsigned rlog = 0;
-      while (rlog < 2 && (4 + (C * rstride << (rlog + 1)) + 64) * 4 + reserve <= lds_share) rlog++;
-      lds = (4 + (C * rstride << rlog) + 64) * 4;
-      hist_words = rstride | ((size_t)rlog << 24) | (padded ? (size_t)1 << 27 : 0);
-      if (c0.codes) {   // the queues of ambiguous rows (fill_ordered_body's CODES), shared by the chains
-        const unsigned qlog = lds_share > lds ? ordered_queue_log(lds_share - lds, g0->cfg_queue_log) : 0;
-        lds += ordered_queue_bytes(qlog);
-        hist_words |= (size_t)qlog << 28;
-      }
+      in.share = (size_t)props.lds_per_cu / std::min<size_t>(per_cu, 2);
+      in.queue_cap = g0->plan_cfg.queue_log;
+      const sxplan::OrderedLds o = sxplan::ordered_lds_layout(in);
+      lds = o.bytes;
+      hist_words = o.word;
     }
     if (lds > (size_t)props.lds_per_cu) {
       mg->why_not = "the chains' histograms do not fit LDS together";
@@ -132,7 +124,7 @@ int sxmc_multigroup_step_async(sxmc_multigroup_t mg, sxmc_stream_t s, const sxmc
                    a.d_v_proposed && a.d_accepted && a.d_counter && a.d_jump_buffer && a.d_jump_width &&
                    a.d_nexpected && a.d_n_mc && a.d_source_id && a.d_norms && a.nparameters > 0,
                "null argument");
-    g->cfg_box = 0;   // (several chains per pass: the ordered form; the boxed one has no such kernel)
+    g->plan_cfg.box = 0;   // (several chains per pass: the ordered form; the boxed one has no such kernel)
     int rc = group_refresh(g);
     if (rc) return rc;
     if (!replan && mg->seen[c] != g->plan_generation) replan = true;
@@ -266,7 +258,7 @@ int sxmc_multigroup_lookahead_step_async(sxmc_multigroup_t mg, sxmc_stream_t s, 
   bool replan = mg->seen.size() != 2;
   for (size_t c = 0; c < 2; c++) {
     sxmc_group* g = mg->groups[c];
-    g->cfg_box = 0;   // (several chains per pass: the ordered form; the boxed one has no such kernel)
+    g->plan_cfg.box = 0;   // (several chains per pass: the ordered form; the boxed one has no such kernel)
     int rc = group_refresh(g);
     if (rc) return rc;
     if (!replan && mg->seen[c] != g->plan_generation) replan = true;
@@ -373,7 +365,7 @@ int sxmc_multigroup_lookahead_step_async(sxmc_multigroup_t mg, sxmc_stream_t s, 
 int sxmc_group_lookahead_supported(sxmc_group_t g, int* ok) {
   SX_REQUIRE(g && ok, "null argument");
   *ok = 0;
-  g->cfg_box = 0;   // (the look-ahead pass runs over the ordered form: the question is asked of that plan)
+  g->plan_cfg.box = 0;   // (the look-ahead pass runs over the ordered form: the question is asked of that plan)
   int rc = group_refresh(g);
   if (rc) return rc;
   if (!g->same_points || g->cfg_lut || (g->sparse_ready && g->cfg_sparse) || g->members.empty()) return SXMC_OK;

@@ -10,6 +10,8 @@
 //   bucket_granules / bucket_key_offsets / bucketed_layout   bucketed copies of a sample table (layout_kernels.hip)
 //   bucket_tables          per-bucket event-bin tables of fill_sparse_kernel
 //   event_classes          distinct tuples of event bins, weighted by multiplicity (eval_nll_kernel)
+//   code_windows / ordered_lds_layout / padded_rstride_of   codes and LDS of the ordered and boxed fills
+//   syst_use / choose_ordered / choose_boxed / compact_slots / prebin_columns   the form a member's table takes
 #pragma once
 
 #include <algorithm>
@@ -501,5 +503,295 @@ inline unsigned ordered_rstride_padded(int total_bins, int outer_bins) {
   return ((words + 63u) & ~63u) + 16u;
 }
 inline size_t ordered_queue_bytes(unsigned qlog) { return qlog ? (4 + ((size_t)2 << qlog)) * 4 : 0; }
+inline size_t ordered_lds_bytes(unsigned rstride, int nchain, unsigned rlog) {
+  return (4 + ((size_t)nchain * rstride << rlog) + 64) * 4;
+}
+constexpr unsigned kMinQueueLog = 9;     // the smallest queues of ambiguous rows a fill over codes works with: 2^9 entries
+// the largest set of queues (512 .. 2048 entries: every wave of the workgroup owns an equal slice) that fits `room`
+// bytes, as log2(entries); 0: none, the launch then streams the float columns
+inline unsigned ordered_queue_log(size_t room, int cap = 0) {
+  unsigned qlog = 11;
+  // (sxmc_group_set_codes_queue_log caps the queues at 2^9 .. 2^11 entries -- smaller queues fill up and are emptied in
+  // the middle of the stream, and whole granules are handed to the float columns; the results do not depend on it)
+  if (cap > 0) qlog = (unsigned)std::min(std::max(cap, (int)kMinQueueLog), 11);
+  while (qlog >= kMinQueueLog && ordered_queue_bytes(qlog) > room) qlog--;
+  return qlog >= kMinQueueLog ? qlog : 0;
+}
+
+// The padded form's stride where every member of a launch qualifies (`descs`: the members as their fill sees them, one
+// observable binned per sample in slot 0), else 0.  Ordered form: that observable must be the histogram's outermost
+// dimension; the boxed form makes it the outermost dimension of the LDS copy wherever it sits.
+inline unsigned padded_rstride_of(const std::vector<SxSignalDesc>& descs, bool boxed) {
+  unsigned rs = 0;
+  for (const SxSignalDesc& d : descs) {
+    const long long nb = d.nbins[0], total = d.total_nbins;
+    const long long S = boxed ? (nb >= 1 ? total / nb : 0) : d.bin_stride[0];
+    bool ok = S >= 1 && nb >= 1 && S * nb == total && S * (nb + 2) < (1ll << 22);
+    if (boxed) ok = ok && d.bin_stride[0] >= 1 && total % ((long long)d.bin_stride[0] * nb) == 0;
+    if (!ok) return 0;
+    rs = std::max(rs, ordered_rstride_padded((int)total, (int)nb));
+  }
+  return rs;
+}
+
+// The LDS of one workgroup of fill_ordered_body / fill_boxed_body, which decode `word` blindly: rstride | rlog << 24 |
+// padded << 27 | qlog << 28.  As many replicas (up to 2^rlog_max) of the chains' histograms as `share` bytes hold; over
+// codes the padded form where one was offered and fits with the smallest queues, then the queues of ambiguous rows in
+// what the replicas leave (`queue_cap`: sxmc_group_set_codes_queue_log).  fits == false: not even one replica does.
+struct OrderedLdsIn {
+  int max_bins = 0, nchain = 1;  // the largest histogram of the launch; chains per pass (1 .. 4)
+  unsigned padded_rstride = 0;   // padded_rstride_of(...); 0: not eligible
+  bool codes = false;
+  size_t share = 0;              // the workgroup's share of the CU's LDS, bytes
+  unsigned rlog_max = 2;
+  int queue_cap = 0;
+};
+struct OrderedLds {
+  unsigned word = 0, rlog = 0, qlog = 0;
+  bool padded = false, fits = false;
+  size_t bytes = 0;
+};
+inline OrderedLds ordered_lds_layout(const OrderedLdsIn& in) {
+  OrderedLds o;
+  const size_t qreserve = in.codes ? ordered_queue_bytes(kMinQueueLog) : 0;   // (room for the smallest queues)
+  unsigned rstride = ordered_rstride_plain(in.max_bins);
+  if (in.codes && in.padded_rstride && ordered_lds_bytes(in.padded_rstride, in.nchain, 0) + qreserve <= in.share) {
+    rstride = in.padded_rstride;
+    o.padded = true;
+  }
+  while (o.rlog < in.rlog_max && ordered_lds_bytes(rstride, in.nchain, o.rlog + 1) + qreserve <= in.share) o.rlog++;
+  o.bytes = ordered_lds_bytes(rstride, in.nchain, o.rlog);
+  if (in.codes) {
+    o.qlog = in.share > o.bytes ? ordered_queue_log(in.share - o.bytes, in.queue_cap) : 0;
+    o.bytes += ordered_queue_bytes(o.qlog);
+  }
+  o.word = rstride | (o.rlog << 24) | (o.padded ? 1u << 27 : 0u) | (o.qlog << 28);
+  o.fits = o.bytes <= in.share;
+  return o;
+}
+
+// ------------------------------------------------------------------------------------- which form a table takes
+// What the systematics of a member do to its slots (`d` as fill_desc fills it: slot k is observable k, the extra
+// fields after them).  Worked out once; every choice below reads it.
+struct SystUse {
+  unsigned written = 0;   // slots some systematic writes
+  unsigned truth = 0;     // slots read as a resolution scale's truth field
+  // per observable: some systematic on it has more than one coefficient; ... or is not a shift, scale or cos-theta
+  // scale; some resolution scale writes it; against which slot (-1: none, -2: more than one)
+  bool many_coef[SXMC_MAX_NFIELDS] = {}, not_affine[SXMC_MAX_NFIELDS] = {}, has_res[SXMC_MAX_NFIELDS] = {};
+  int truth_slot[SXMC_MAX_NFIELDS];
+  // A program every systematic of which is a short polynomial can run as straight-line code: from the table of
+  // kernels built into the library, or specialised at run time (sxmc_rtc.cpp).
+  bool specialisable = false;
+  bool is_written(int k) const { return (written >> k) & 1u; }
+  bool is_truth(int k) const { return (truth >> k) & 1u; }
+  // written by one-coefficient shift / scale / cos-theta scale only
+  bool affine_only(int k) const { return is_written(k) && !many_coef[k] && !not_affine[k]; }
+};
+inline SystUse syst_use(const SxSignalDesc& d) {
+  SystUse u;
+  std::fill(u.truth_slot, u.truth_slot + SXMC_MAX_NFIELDS, -1);
+  int ncoef = 0;
+  u.specialisable = d.nsyst <= 8;
+  for (int q = 0; q < d.nsyst; q++) {
+    const SxSystOp& op = d.syst[q];
+    const int k = op.obs_slot;
+    ncoef += op.npars;
+    u.specialisable = u.specialisable && op.npars >= 1 && op.npars <= SXMC_MAX_SYST_PARS;
+    u.written |= 1u << k;
+    u.many_coef[k] = u.many_coef[k] || op.npars != 1;
+    u.not_affine[k] = u.not_affine[k] || !(op.type == SXMC_SYST_SHIFT || op.type == SXMC_SYST_SCALE || op.type == SXMC_SYST_CTSCALE);
+    if (op.type == SXMC_SYST_RESOLUTION_SCALE) {
+      u.truth |= 1u << op.extra_slot;
+      u.truth_slot[k] = (!u.has_res[k] || u.truth_slot[k] == op.extra_slot) ? op.extra_slot : -2;
+      u.has_res[k] = true;
+    }
+  }
+  u.specialisable = u.specialisable && ncoef <= 16;
+  return u;
+}
+
+// the program as words, one per systematic (the key of a launch class and of the kernel tables)
+inline std::vector<unsigned> prog_words(const SxSignalDesc& x) {
+  std::vector<unsigned> w;
+  for (int q = 0; q < x.nsyst; q++) {
+    w.push_back((unsigned)x.syst[q].type | ((unsigned)x.syst[q].obs_slot << 4) |
+                ((unsigned)x.syst[q].extra_slot << 8) | (x.syst[q].npars > 1 ? (unsigned)x.syst[q].npars << 12 : 0u));
+  }
+  return w;
+}
+
+// buckets of a bucketed table: the bins of the observables no systematic writes
+inline double unwritten_buckets(const SxSignalDesc& d, const SystUse& u) {
+  double buckets = 1.0;
+  for (int k = 0; k < d.nobs; k++) {
+    if (!u.is_written(k)) buckets *= (double)d.nbins[k];
+  }
+  return buckets;
+}
+
+// (the runs kernel forms idx * stride + bin with ONE signed 24-bit multiply-add)
+inline bool narrow_for_runs(const SxSignalDesc& d) {
+  bool narrow = true;
+  for (int k = 0; k < d.nobs; k++) narrow = narrow && d.nbins[k] < (1 << 23) && d.bin_stride[k] < (1 << 23);
+  return narrow;
+}
+
+// The ORDERED observable: written by one-coefficient shift / scale / cos-theta scale only and read by nothing; of
+// several, the one with the fewest bins (fewest granules that straddle an edge).  -1: none.  mode: 0 off, 1 where it
+// pays, 2 wherever it applies.  A histogram beyond LDS (lds_hist false): only with the event-bin counters over runs
+// (`runs_possible`: the caller's side of that -- evaluation points, room for the members' workgroups); the round-1
+// filter path of a table left in sorted order has no ordered form.
+inline int choose_ordered(const SxSignalDesc& d, const SystUse& u, int mode, bool lds_hist, bool runs_possible) {
+  if (!mode || !(lds_hist ? d.total_nbins < (1 << 24) : (runs_possible && narrow_for_runs(d)))) return -1;
+  int ordered = -1;
+  for (int k = 0; k < d.nobs; k++) {
+    if (u.affine_only(k) && !u.is_truth(k) && (ordered < 0 || d.nbins[k] < d.nbins[ordered])) ordered = k;
+  }
+  // Does it pay?  Up to nbins + 1 granules per bucket straddle an edge and stream everything; with fewer
+  // than twice that many granules in all, most do (BASELINE config 5: 61 granules per bucket against 200
+  // bins of r) and the ordered form only adds work.  mode == 2 (tests): wherever it applies.
+  if (ordered >= 0 && mode == 1) {
+    const double straddling = unwritten_buckets(d, u) * ((double)d.nbins[ordered] + 1.0);
+    if ((double)d.nsamples / 256.0 < 2.0 * straddling) ordered = -1;
+  }
+  return ordered;
+}
+
+// The BOXED observable (fill_boxed_kernel): written by one-coefficient shift / scale / cos-theta scale and at least
+// one resolution scale, all of those against ONE field that nothing writes, and read by nothing; beside it exactly one
+// other written observable, with one-coefficient shift / scale / cos-theta scale only (one streamed field, as 16-bit
+// codes).  Histogram in LDS.  Where the ordered form also applies this one streams half the bytes.  mode: 0 off, < 0
+// where it pays, 1 wherever it applies; `strata`: strata of x - t inside a bucket.
+struct BoxChoice {
+  int obs = -1, truth = -1;   // the observable and the slot of its truth field; obs < 0: none
+};
+inline BoxChoice choose_boxed(const SxSignalDesc& d, const SystUse& u, int mode, int strata, bool lds_hist) {
+  BoxChoice b;
+  if (!mode || !lds_hist || d.total_nbins >= (1 << 22)) return b;
+  int nwritten = 0;
+  bool others_ok = true;
+  for (int k = 0; k < d.nobs; k++) {
+    if (!u.is_written(k)) continue;
+    const bool ok = !u.many_coef[k] && u.truth_slot[k] != -2 && !u.is_truth(k);   // (is_truth: read by a systematic, itself included)
+    nwritten++;
+    if (u.has_res[k] && ok && b.obs < 0) {
+      b.obs = k;
+      b.truth = u.truth_slot[k];
+    } else {
+      others_ok = others_ok && ok && !u.has_res[k];
+    }
+  }
+  const bool truth_written = b.truth >= 0 && u.is_written(b.truth);
+  if (b.obs < 0 || nwritten != 2 || !others_ok || truth_written || d.nsyst > 8) return BoxChoice{};
+  // Does it pay?  A box straddles an edge of the observable when it is not small against a bin: with fewer than a
+  // few granules per bin, stratum and bucket most do.  mode == 1 (tests): wherever it applies.
+  if (mode < 0) {
+    const double per = (double)d.nsamples / 256.0 / (unwritten_buckets(d, u) * strata);
+    if (per < 4.0 * ((double)d.nbins[b.obs] + 1.0)) return BoxChoice{};
+  }
+  return b;
+}
+
+// The member's problem as the fill sees it once its table is bucketed: only the observables some systematic
+// writes (+ the extra fields), slots renumbered, columns = the bucketed copy.  `keep`: full slot -> new slot or -1.
+// `ordered` >= 0: that observable rides in the last slot and its geometry at index nobs2 (fill_ordered_kernel).
+inline void compact_desc(const SxSignalDesc& full, const std::vector<int>& keep, int nobs2, SxSignalDesc& cd, int ordered = -1) {
+  cd = full;
+  if (ordered >= 0) {
+    cd.bin_stride[nobs2] = full.bin_stride[ordered];
+    cd.nbins[nobs2] = full.nbins[ordered];
+    cd.lower[nobs2] = full.lower[ordered];
+    cd.upper[nobs2] = full.upper[ordered];
+    cd.scale[nobs2] = full.scale[ordered];
+  }
+  int nslot = 0;
+  for (int k = 0; k < full.nslot; k++) {
+    if (keep[(size_t)k] < 0) continue;
+    const int q = keep[(size_t)k];
+    cd.slot_col[q] = q;  // the copy holds exactly the streamed fields, in slot order
+    if (q < nobs2) {     // an observable the fill still bins (the others it keeps are read-only inputs)
+      cd.bin_stride[q] = full.bin_stride[k];
+      cd.nbins[q] = full.nbins[k];
+      cd.lower[q] = full.lower[k];
+      cd.upper[q] = full.upper[k];
+      cd.scale[q] = full.scale[k];
+    }
+    nslot++;
+  }
+  cd.nobs = nobs2;
+  cd.nslot = nslot;
+  for (int q = 0; q < full.nsyst; q++) {
+    cd.syst[q].obs_slot = (short)keep[(size_t)full.syst[q].obs_slot];
+    cd.syst[q].extra_slot =
+        (short)(full.syst[q].type == SXMC_SYST_RESOLUTION_SCALE ? keep[(size_t)full.syst[q].extra_slot] : 0);
+  }
+}
+
+// Compacted slots of a bucketed table: the observables that are written (still binned by the fill), then everything
+// that is only read -- the extra fields, and an untouched observable that serves as some systematic's truth field (its
+// own bin index is the bucket's; its VALUE is still an input) --, then the ordered observable.  box_truth >= 0:
+// `ordered` is a BOXED observable and box_truth the slot of its truth field.
+struct CompactSlots {
+  unsigned mask = 0;         // the observables the buckets are made of (those no systematic writes)
+  unsigned pre_mask = 0;     // ... | 1 << (16 + ordered): the launch class's key
+  std::vector<int> keep;     // full slot -> compacted slot or -1
+  std::vector<int> fields;   // the table columns the copy streams, in compacted slot order
+  int nobs2 = 0;             // observables the fill still bins per sample
+  // a shape the ordered / boxed form takes.  The plain bucketed form (ordered < 0): one that has buckets and something
+  // to bin; whether a kernel is specialised for (nobs2, fields.size()) is the caller's to ask.
+  bool shape_ok = false;
+};
+inline CompactSlots compact_slots(const SxSignalDesc& d, const SystUse& u, int ordered, int box_truth, bool lds_hist) {
+  CompactSlots c;
+  c.keep.assign((size_t)d.nslot, -1);
+  for (int k = 0; k < d.nobs; k++) {
+    if (k == ordered) continue;
+    if (u.is_written(k)) {
+      c.keep[(size_t)k] = (int)c.fields.size();
+      c.fields.push_back(d.slot_col[k]);
+      c.nobs2++;
+    } else {
+      c.mask |= 1u << k;
+    }
+  }
+  for (int k = 0; k < d.nslot; k++) {
+    if (c.keep[(size_t)k] >= 0 || k == ordered) continue;
+    if (k >= d.nobs || u.is_truth(k)) {
+      c.keep[(size_t)k] = (int)c.fields.size();
+      c.fields.push_back(d.slot_col[k]);
+    }
+  }
+  if (ordered >= 0) {
+    c.keep[(size_t)ordered] = (int)c.fields.size();
+    c.fields.push_back(d.slot_col[ordered]);
+  }
+  c.pre_mask = c.mask | (ordered >= 0 ? 1u << (16 + ordered) : 0u);
+  // (beyond LDS the granule word has no room for the row count: something must be binned per sample)
+  c.shape_ok = box_truth >= 0 ? (c.nobs2 == 1 && c.fields.size() == 3 && lds_hist && c.fields[1] == d.slot_col[box_truth])
+               : ordered >= 0 ? (c.nobs2 <= 5 && c.fields.size() <= 7 && (lds_hist || c.nobs2 >= 1))
+                              : (c.mask && c.nobs2 >= 1);
+  return c;
+}
+
+// pre-binning: the observables that no systematic writes as ONE narrow column of partial bin indices (1 or 2 bytes wide;
+// width 0: none to pre-bin, or the index does not fit 16 bits)
+struct PrebinColumns {
+  unsigned mask = 0;
+  int width = 0;
+};
+inline PrebinColumns prebin_columns(const SxSignalDesc& d, const SystUse& u) {
+  PrebinColumns p;
+  long long bound = 0;  // largest value the partial index can take (index == nbins included)
+  for (int k = 0; k < d.nobs; k++) {
+    if (!u.is_written(k)) {
+      p.mask |= 1u << k;
+      bound += (long long)d.nbins[k] * d.bin_stride[k];
+    }
+  }
+  p.width = bound < 0xFF ? 1 : 2;
+  if (!p.mask || bound >= 0xFFFF) return PrebinColumns{};
+  return p;
+}
 
 }  // namespace sxplan

@@ -517,4 +517,244 @@ TEST(Plan, PaddedHistogramRowsDoNotOverlapAndFitTheirReplica) {
   }
 }
 
+// ---- the form a member's table takes (syst_use, choose_ordered, choose_boxed, compact_slots, prebin_columns) and the LDS
+// of the ordered / boxed fill (ordered_lds_layout).  Descriptors as fill_desc fills them: slot k is observable k, the
+// extra fields after them, ascending.
+namespace {
+struct Op {
+  int type, obs, extra, npars;
+};
+const int SHIFT = SXMC_SYST_SHIFT, SCALE = SXMC_SYST_SCALE, RES = SXMC_SYST_RESOLUTION_SCALE, CT = SXMC_SYST_CTSCALE;
+SxSignalDesc make_desc(const std::vector<int>& nbins, int nslot, unsigned long long nsamples, const std::vector<Op>& ops) {
+  SxSignalDesc d{};
+  d.nobs = (int)nbins.size();
+  d.nslot = nslot;
+  d.nsamples = nsamples;
+  d.nvec = (nsamples + 3) / 4;
+  long long total = 1;
+  for (int k = d.nobs - 1; k >= 0; k--) {
+    d.nbins[k] = nbins[(size_t)k];
+    d.bin_stride[k] = (int)total;
+    d.lower[k] = 0;
+    d.upper[k] = 1;
+    d.scale[k] = nbins[(size_t)k];
+    total *= nbins[(size_t)k];
+  }
+  d.total_nbins = (int)total;
+  for (int k = 0; k < nslot; k++) d.slot_col[k] = k;
+  d.nsyst = (int)ops.size();
+  for (size_t q = 0; q < ops.size(); q++) {
+    d.syst[q].type = (short)ops[q].type;
+    d.syst[q].obs_slot = (short)ops[q].obs;
+    d.syst[q].extra_slot = (short)(ops[q].type == RES ? ops[q].extra : 0);
+    d.syst[q].npars = (short)ops[q].npars;
+    d.syst[q].coef_start = (short)d.ncoef;
+    d.ncoef += ops[q].npars;
+  }
+  return d;
+}
+const std::vector<Op> kC3 = {{SHIFT, 1, 0, 1}, {SCALE, 0, 0, 1}, {RES, 0, 3, 1}};
+SxSignalDesc config3(unsigned long long n, std::vector<Op> ops = kC3, int nslot = 4) { return make_desc({20, 20, 20}, nslot, n, ops); }
+int ordered_of(const SxSignalDesc& d, int mode, bool lds = true) { return sxplan::choose_ordered(d, sxplan::syst_use(d), mode, lds, true); }
+int boxed_of(const SxSignalDesc& d, int mode, bool lds = true) { return sxplan::choose_boxed(d, sxplan::syst_use(d), mode, 2, lds).obs; }
+}  // namespace
+
+TEST(Plan, Config3OrderedAndBoxedObservablesAndWhereTheyPay) {
+  const SxSignalDesc d = config3(215040);
+  const sxplan::SystUse u = sxplan::syst_use(d);
+  EXPECT_EQ(0b0011u, u.written);
+  EXPECT_EQ(0b1000u, u.truth);
+  EXPECT_TRUE(u.specialisable && u.affine_only(1) && !u.affine_only(0) && !u.affine_only(2) && u.has_res[0] && !u.has_res[1]);
+  EXPECT_EQ(3, u.truth_slot[0]);
+  EXPECT_EQ(20.0, sxplan::unwritten_buckets(d, u));
+  EXPECT_TRUE(sxplan::narrow_for_runs(d));
+  EXPECT_EQ(std::vector<unsigned>({0x10u, 0x01u, 0x302u}), sxplan::prog_words(d));
+  // ordered: r, kept while nsamples / 256 >= 2 * 20 buckets * 21 edges
+  EXPECT_EQ(1, ordered_of(config3(215040), 1));
+  EXPECT_EQ(-1, ordered_of(config3(215039), 1));
+  EXPECT_EQ(1, ordered_of(config3(1), 2));
+  EXPECT_EQ(-1, ordered_of(config3(1u << 30), 0));
+  // boxed, 2 strata: e against e_true, kept while nsamples / 256 / (20 * 2) >= 4 * 21
+  const sxplan::BoxChoice b = sxplan::choose_boxed(config3(860160), sxplan::syst_use(d), -1, 2, true);
+  EXPECT_EQ(0, b.obs);
+  EXPECT_EQ(3, b.truth);
+  EXPECT_EQ(-1, boxed_of(config3(860159), -1));
+  EXPECT_EQ(0, boxed_of(config3(1), 1));
+  EXPECT_EQ(-1, boxed_of(config3(1u << 30), 0));
+  EXPECT_EQ(-1, boxed_of(config3(1u << 30), 1, false));   // (histogram beyond LDS)
+  // the slots of the two forms
+  const sxplan::CompactSlots bx = sxplan::compact_slots(d, u, 0, 3, true);
+  EXPECT_EQ(std::vector<int>({2, 0, -1, 1}), bx.keep);
+  EXPECT_EQ(std::vector<int>({1, 3, 0}), bx.fields);      // r, e_true, e
+  EXPECT_TRUE(bx.shape_ok && bx.nobs2 == 1 && bx.mask == 0b100u && bx.pre_mask == 0x10004u);
+  const sxplan::CompactSlots od = sxplan::compact_slots(d, u, 1, -1, true);
+  EXPECT_EQ(std::vector<int>({0, 2, -1, 1}), od.keep);
+  EXPECT_EQ(std::vector<int>({0, 3, 1}), od.fields);      // e, e_true, r
+  EXPECT_TRUE(od.shape_ok && od.nobs2 == 1 && od.mask == 0b100u && od.pre_mask == 0x20004u);
+  EXPECT_TRUE(!sxplan::compact_slots(d, u, 0, 3, false).shape_ok);   // (the boxed form: histograms in LDS only)
+  const sxplan::CompactSlots pl = sxplan::compact_slots(d, u, -1, -1, true);
+  EXPECT_EQ(std::vector<int>({0, 1, -1, 2}), pl.keep);
+  EXPECT_TRUE(pl.shape_ok && pl.nobs2 == 2 && pl.pre_mask == 0b100u);
+  // the member as the boxed fill sees it: r in slot 0, e's geometry at index nobs
+  SxSignalDesc cd;
+  sxplan::compact_desc(d, bx.keep, bx.nobs2, cd, 0);
+  EXPECT_TRUE(cd.nobs == 1 && cd.nslot == 3 && cd.bin_stride[0] == 20 && cd.bin_stride[1] == 400);
+  EXPECT_EQ(std::vector<unsigned>({0x00u, 0x21u, 0x122u}), sxplan::prog_words(cd));
+}
+
+TEST(Plan, Config5AtFullSizeHasNoOrderedObservable) {
+  // 5e7 samples: 195 312 granules against 2 * 3200 buckets * 201 edges
+  const SxSignalDesc d = make_desc({200, 200, 200, 4, 4}, 6, 50000000ull, {{SHIFT, 1, 0, 1}, {SCALE, 0, 0, 1}, {RES, 0, 5, 1}});
+  EXPECT_EQ(128000000, d.total_nbins);
+  EXPECT_EQ(3200.0, sxplan::unwritten_buckets(d, sxplan::syst_use(d)));
+  EXPECT_EQ(-1, ordered_of(d, 1, false));
+  EXPECT_EQ(1, ordered_of(d, 2, false));
+  EXPECT_EQ(-1, sxplan::choose_ordered(d, sxplan::syst_use(d), 2, false, false));   // (no runs: no ordered form beyond LDS)
+  SxSignalDesc wide = make_desc({100, 2900, 2900}, 4, 3000001, kC3);                 // a stride of 2^23 or more
+  EXPECT_TRUE(!sxplan::narrow_for_runs(wide));
+  EXPECT_EQ(-1, ordered_of(wide, 2, false));
+}
+
+TEST(Plan, EveryWayACandidateIsRefused) {
+  // a second coefficient
+  EXPECT_EQ(-1, ordered_of(config3(1, {{SHIFT, 1, 0, 2}, {SCALE, 0, 0, 1}, {RES, 0, 3, 1}}), 2));
+  EXPECT_EQ(-1, boxed_of(config3(1, {{SHIFT, 1, 0, 2}, {SCALE, 0, 0, 1}, {RES, 0, 3, 1}}), 1));
+  EXPECT_EQ(-1, boxed_of(config3(1, {{SHIFT, 1, 0, 1}, {SCALE, 0, 0, 2}, {RES, 0, 3, 1}}), 1));
+  EXPECT_EQ(1, ordered_of(config3(1, {{SHIFT, 1, 0, 1}, {SCALE, 0, 0, 2}, {RES, 0, 3, 1}}), 2));
+  // the observable read as some resolution scale's truth field
+  EXPECT_EQ(-1, ordered_of(config3(1, {{SHIFT, 1, 0, 1}, {RES, 0, 1, 1}}), 2));
+  EXPECT_EQ(-1, boxed_of(config3(1, {{SHIFT, 1, 0, 1}, {RES, 0, 3, 1}, {RES, 2, 0, 1}}), 1));
+  // a resolution scale on it: no order
+  EXPECT_EQ(-1, ordered_of(config3(1, {{SCALE, 0, 0, 1}, {RES, 0, 3, 1}}), 2));
+  // two truth fields for one observable
+  EXPECT_EQ(-2, sxplan::syst_use(config3(1, {{SHIFT, 1, 0, 1}, {RES, 0, 3, 1}, {RES, 0, 4, 1}}, 5)).truth_slot[0]);
+  EXPECT_EQ(-1, boxed_of(config3(1, {{SHIFT, 1, 0, 1}, {RES, 0, 3, 1}, {RES, 0, 4, 1}}, 5), 1));
+  EXPECT_EQ(0, boxed_of(config3(1, {{SHIFT, 1, 0, 1}, {RES, 0, 3, 1}, {RES, 0, 3, 1}}), 1));
+  // the truth field itself written
+  EXPECT_EQ(-1, boxed_of(config3(1, {{SHIFT, 1, 0, 1}, {RES, 0, 3, 1}, {SHIFT, 3, 0, 1}}), 1));
+  // three written observables (boxed), one (boxed: nothing to stream as codes)
+  EXPECT_EQ(-1, boxed_of(config3(1, {{SHIFT, 1, 0, 1}, {SCALE, 0, 0, 1}, {RES, 0, 3, 1}, {CT, 2, 0, 1}}), 1));
+  EXPECT_EQ(-1, boxed_of(config3(1, {{SCALE, 0, 0, 1}, {RES, 0, 3, 1}}), 1));
+  // more than 8 systematics (boxed)
+  std::vector<Op> many = kC3;
+  for (int q = 0; q < 6; q++) many.push_back({SHIFT, 1, 0, 1});
+  EXPECT_EQ(-1, boxed_of(config3(1, many), 1));
+  EXPECT_TRUE(!sxplan::syst_use(config3(1, many)).specialisable);
+  // a histogram of 2^24 bins or more (ordered), 2^22 or more (boxed)
+  SxSignalDesc big = config3(1);
+  big.total_nbins = (1 << 24) - 1;
+  EXPECT_EQ(1, ordered_of(big, 2));
+  big.total_nbins = 1 << 24;
+  EXPECT_EQ(-1, ordered_of(big, 2));
+  big.total_nbins = (1 << 22) - 1;
+  EXPECT_EQ(0, boxed_of(big, 1));
+  big.total_nbins = 1 << 22;
+  EXPECT_EQ(-1, boxed_of(big, 1));
+  // programs that cannot be specialised: no coefficient, more than SXMC_MAX_SYST_PARS, more than 16 in all
+  EXPECT_TRUE(!sxplan::syst_use(config3(1, {{SHIFT, 1, 0, 0}})).specialisable);
+  EXPECT_TRUE(!sxplan::syst_use(config3(1, {{SHIFT, 1, 0, SXMC_MAX_SYST_PARS + 1}})).specialisable);
+  EXPECT_TRUE(sxplan::syst_use(config3(1, {{SHIFT, 1, 0, 8}, {SCALE, 0, 0, 8}})).specialisable);
+  EXPECT_TRUE(!sxplan::syst_use(config3(1, {{SHIFT, 1, 0, 8}, {SCALE, 0, 0, 8}, {CT, 2, 0, 1}})).specialisable);
+}
+
+TEST(Plan, PrebinnedColumnWidths) {
+  const std::vector<Op> ops = {{SCALE, 0, 0, 1}};
+  auto pre = [&](int nb) {
+    const SxSignalDesc d = make_desc({3, nb}, 2, 1000, ops);   // (observable 1: stride 1, bound = nb)
+    return sxplan::prebin_columns(d, sxplan::syst_use(d));
+  };
+  EXPECT_TRUE(pre(254).width == 1 && pre(254).mask == 0b10u);
+  EXPECT_TRUE(pre(255).width == 2 && pre(255).mask == 0b10u);
+  EXPECT_TRUE(pre(65534).width == 2);
+  EXPECT_TRUE(pre(65535).width == 0 && pre(65535).mask == 0u);
+  const SxSignalDesc all = make_desc({3, 4}, 2, 1000, {{SCALE, 0, 0, 1}, {SHIFT, 1, 0, 1}});
+  EXPECT_TRUE(sxplan::prebin_columns(all, sxplan::syst_use(all)).width == 0);   // (every observable written)
+}
+
+TEST(Plan, OrderedLdsLayoutKnownAnswersOfConfig3) {
+  sxplan::OrderedLdsIn in;
+  in.max_bins = 8000;
+  in.padded_rstride = sxplan::ordered_rstride_padded(8000, 20);
+  EXPECT_EQ(8848u, in.padded_rstride);
+  in.codes = true;
+  in.share = 163840;            // the boxed class: one workgroup per CU
+  sxplan::OrderedLds o = sxplan::ordered_lds_layout(in);
+  EXPECT_EQ(0xBA002290u, o.word);
+  EXPECT_EQ((size_t)158240, o.bytes);
+  EXPECT_TRUE(o.fits && o.padded && o.rlog == 2 && o.qlog == 11);
+  in.share = 81920;             // its ordered twin: two workgroups per CU
+  o = sxplan::ordered_lds_layout(in);
+  EXPECT_EQ(0xA9002290u, o.word);
+  EXPECT_EQ((size_t)79264, o.bytes);
+  in.codes = false;             // float columns: the plain form, no queues
+  o = sxplan::ordered_lds_layout(in);
+  EXPECT_EQ(sxplan::ordered_rstride_plain(8000) | (1u << 24), o.word);
+  in.share = 1000;              // nothing fits: said, not wrapped around
+  o = sxplan::ordered_lds_layout(in);
+  EXPECT_TRUE(!o.fits && o.rlog == 0 && o.qlog == 0 && o.bytes > in.share);
+}
+
+TEST(Plan, OrderedLdsLayoutCoversWhatTheKernelLaysOut) {
+  // fill_ordered_body: 4 header words, chains * (rstride << rlog) words of histograms, 64 spare words; with queues 4
+  // header words and per wave 2 * ((1 << qlog) / waves) words
+  Rng r(14);
+  int with_queues = 0, padded = 0, nothing = 0;
+  for (int trial = 0; trial < 20000; trial++) {
+    const int nb = 1 + (int)r.below(200), bins = nb * (1 + (int)r.below((uint64_t)(40832 / nb)));
+    const int threads = 512 + 256 * (int)r.below(3), waves = threads / 64;
+    sxplan::OrderedLdsIn in;
+    in.max_bins = bins;
+    in.nchain = 1 + (int)r.below(4);
+    in.codes = r.below(2) != 0;
+    in.padded_rstride = r.below(2) ? sxplan::ordered_rstride_padded(bins, nb) : 0u;
+    in.share = 16384 + (size_t)r.below(160 * 1024 - 16384 + 1);
+    in.rlog_max = (unsigned)r.below(3);
+    in.queue_cap = r.below(2) ? 0 : 9 + (int)r.below(3);
+    const sxplan::OrderedLds o = sxplan::ordered_lds_layout(in);
+    const unsigned rstride = o.word & 0xFFFFFFu, rlog = (o.word >> 24) & 7u, qlog = o.word >> 28;
+    EXPECT_TRUE(rlog == o.rlog && qlog == o.qlog && ((o.word >> 27) & 1u) == (o.padded ? 1u : 0u) && rlog <= in.rlog_max);
+    const size_t hist = (4 + (size_t)in.nchain * ((size_t)rstride << rlog) + 64) * 4;
+    const size_t q9 = sxplan::ordered_queue_bytes(9);
+    // the padded bit: only where a padded stride was offered and fits with the smallest queues
+    const bool padded_fits = in.codes && in.padded_rstride && (4 + (size_t)in.nchain * in.padded_rstride + 64) * 4 + q9 <= in.share;
+    EXPECT_EQ(padded_fits, o.padded);
+    EXPECT_EQ(o.padded ? in.padded_rstride : sxplan::ordered_rstride_plain(bins), rstride);
+    EXPECT_TRUE(rstride >= (unsigned)bins);
+    size_t kernel = hist;
+    if (qlog) {
+      EXPECT_TRUE(in.codes && qlog >= 9 && qlog <= 11 && (in.queue_cap == 0 || (int)qlog <= in.queue_cap));
+      const unsigned slice = (1u << qlog) / (unsigned)waves;
+      kernel += (4 + (size_t)waves * 2 * slice) * 4;
+      // every wave's slice leaves 8 row entries after its granule part (the kernel's rq_cap >= 8, with its ring of 4)
+      const unsigned granules = std::max(slice / 8u, 4u * (unsigned)in.nchain + 1u);
+      EXPECT_TRUE(slice >= granules + 8u);
+      with_queues++;
+    } else if (in.codes) {
+      EXPECT_TRUE(hist + q9 > in.share);   // (no queues: only because the smallest do not fit)
+    }
+    EXPECT_TRUE(o.bytes >= kernel);
+    EXPECT_EQ(o.fits, o.bytes <= in.share);
+    if (!o.fits) {   // nothing fits: one replica, no queues, and the caller is told
+      EXPECT_TRUE(rlog == 0 && qlog == 0 && !o.padded);
+      nothing++;
+    }
+    padded += o.padded;
+  }
+  EXPECT_TRUE(with_queues > 1000 && padded > 1000 && nothing > 100);
+}
+
+TEST(Plan, PaddedStrideNeedsEveryMemberToQualify) {
+  // ordered form: slot 0 of the compacted problem must be the histogram's outermost dimension
+  SxSignalDesc a = make_desc({20, 20, 20}, 3, 1000, {});
+  EXPECT_EQ(sxplan::ordered_rstride_padded(8000, 20), sxplan::padded_rstride_of({a}, false));
+  SxSignalDesc b = a;
+  b.bin_stride[0] = 20;          // (e.g. r of config 3: not the outermost dimension)
+  EXPECT_EQ(0u, sxplan::padded_rstride_of({a, b}, false));
+  EXPECT_EQ(sxplan::ordered_rstride_padded(8000, 20), sxplan::padded_rstride_of({a, b}, true));   // boxed: wherever it sits
+  SxSignalDesc c = make_desc({40, 30}, 2, 1000, {});
+  EXPECT_EQ(std::max(sxplan::ordered_rstride_padded(8000, 20), sxplan::ordered_rstride_padded(1200, 40)),
+            sxplan::padded_rstride_of({c, a}, false));
+  EXPECT_EQ(0u, sxplan::padded_rstride_of({}, false));
+}
+
 int main(int argc, char** argv) { return mini::run_all(argc > 1 ? argv[1] : nullptr); }

@@ -2,7 +2,8 @@
 not available on the pool).
 
 * tests/cpp/test_plan.cpp -- the host planners of libsxmc_hip.so (sxmc_amd/csrc/sxmc_plan.h: work partitions, sparse
-  tables, bucket layouts, per-bucket event tables, event classes, SetEvalPoints' loop) built from randomized shapes
+  tables, bucket layouts, per-bucket event tables, event classes, SetEvalPoints' loop, the form a member's table takes, the
+  LDS layout of the ordered fill) built from randomized shapes
   and walked the way the kernels index them; a plain build and one under AddressSanitizer + UndefinedBehaviorSanitizer.
 * the CPU oracle's own known-answer tests re-run against oracle/libsxmc_oracle_asan.so (same sources, -fsanitize=
   address,undefined), so that the checker everything else is compared with is itself free of out-of-bounds reads and
@@ -28,20 +29,22 @@ def test_host_planners_device_free(exe):
     env = dict(os.environ, ASAN_OPTIONS="detect_leaks=1:abort_on_error=0", UBSAN_OPTIONS="halt_on_error=1:print_stacktrace=1")
     r = subprocess.run([os.path.join(CPP, exe)], capture_output=True, text=True, env=env, timeout=600)
     assert r.returncode == 0, (r.stdout[-3000:], r.stderr[-3000:])
-    assert "9 tests, 0 failed" in r.stdout
+    assert "16 tests, 0 failed" in r.stdout
     assert "runtime error" not in r.stderr and "AddressSanitizer" not in r.stderr
 
 
 def test_planner_header_needs_no_hip():
-    """sxmc_plan.h is what the library's host side (sxmc_launch_plan.cpp, sxmc_evaluator.cpp) uploads from: it must stay free of HIP and of library state, or the
+    """sxmc_plan.h is what the library's host side (sxmc_launch_plan.cpp, sxmc_evaluator.cpp, sxmc_multigroup.cpp) plans and uploads from: it must stay free of HIP and of library state, or the
     device-free test above stops covering what runs in production."""
     text = open(os.path.join(ROOT, "sxmc_amd", "csrc", "sxmc_plan.h")).read()
     code = "\n".join(line.split("//")[0] for line in text.splitlines())      # (comments may name HIP)
     assert "hip" not in code.lower() and "#include <hip" not in text
     src = "".join(open(os.path.join(ROOT, "sxmc_amd", "csrc", f)).read()
-                  for f in ("sxmc_launch_plan.cpp", "sxmc_evaluator.cpp", "sxmc_host.h"))
+                  for f in ("sxmc_launch_plan.cpp", "sxmc_evaluator.cpp", "sxmc_host.h", "sxmc_multigroup.cpp"))
     for fn in ("build_partition", "interleaved_segments", "apportion_workgroups", "build_sparse_tables", "eval_point_bins",
-               "bucket_granules", "bucket_key_offsets", "bucketed_layout", "bucket_tables", "event_classes"):
+               "bucket_granules", "bucket_key_offsets", "bucketed_layout", "bucket_tables", "event_classes", "syst_use",
+               "prog_words", "narrow_for_runs", "choose_ordered", "choose_boxed", "compact_slots", "compact_desc",
+               "prebin_columns", "padded_rstride_of", "ordered_lds_layout", "ordered_lds_bytes", "ordered_rstride_plain"):
         assert "sxplan::" + fn in src, fn + " is not what the library calls"
 
 
