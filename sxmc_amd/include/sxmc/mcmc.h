@@ -10,6 +10,17 @@
 // reference's own sequence of entry points instead (per-evaluator EvalAsync/EvalFinished,
 // nll_event_chunks, finish_nll_jump_pick_combo); both forms give the same numbers up to the
 // summation order of the event partial sums.
+//
+// The walk's SCHEDULE -- which steps end a run of steps, where the widths are re-tuned, how a run splits into graph
+// replays and a remainder, how many passes a round of the look-ahead walk launches,
+// which form the steps take (choose_form) -- is walk_plan.h: pure functions, tested without a device.  The walk and
+// LockstepSet::launch call them and hold no copy of those rules.
+//
+// The walk's STRUCTURE: MCMC::operator() sets up, chooses the form, walks run by run and finishes, over a Walk object
+// (private to MCMC) that holds the walk's arrays, its one argument block, its graph, its stream and the set-up lock;
+// every part is a member of Walk that says which lock it needs.  ~Walk is the scope guard: on every way out the
+// evaluators are un-bound from the arrays, the lockstep set is left and graph and stream are released under the lock,
+// before the arrays die.  Handles are owned (Owned<>); record_graph is the one recorder of launches into a graph.
 #pragma once
 
 #include <algorithm>
@@ -28,6 +39,7 @@
 
 #include "fit_types.h"
 #include "nll_kernels.h"
+#include "walk_plan.h"
 
 namespace sxmc {
 
@@ -113,6 +125,79 @@ struct RecordingScope {
   RecordingScope& operator=(const RecordingScope&) = delete;
 };
 
+/** A library handle that is destroyed with its owner: move-only.  reset() passes the library's answer on. */
+template <typename H, int (*Destroy)(H)>
+class Owned {
+ public:
+  Owned() = default;
+  explicit Owned(H h_) : h(h_) {}
+  ~Owned() { reset(); }
+  Owned(Owned&& o) noexcept : h(o.h) { o.h = nullptr; }
+  Owned& operator=(Owned&& o) noexcept {
+    if (this != &o) {
+      reset();
+      h = o.h;
+      o.h = nullptr;
+    }
+    return *this;
+  }
+  Owned(const Owned&) = delete;
+  Owned& operator=(const Owned&) = delete;
+  int reset() {
+    const int rc = h ? Destroy(h) : SXMC_OK;
+    h = nullptr;
+    return rc;
+  }
+  H get() const { return h; }
+  H* put() {   //!< for a `create(..., &out)` call: what was owned goes first
+    reset();
+    return &h;
+  }
+  explicit operator bool() const { return h != nullptr; }
+
+ private:
+  H h = nullptr;
+};
+typedef Owned<sxmc_graph_t, sxmc_graph_destroy> OwnedGraph;
+typedef Owned<sxmc_multigroup_t, sxmc_multigroup_destroy> OwnedMultigroup;
+typedef Owned<sxmc_group_t, sxmc_group_destroy> OwnedGroup;
+typedef Owned<sxmc_stream_t, sxmc_stream_destroy> OwnedStream;   //!< a stream its holder created itself
+
+/** Records n calls of launch_one (which returns the library's rc, or throws) on `stream` into `graph`, replacing what
+ *  it held.  `lock`, when `held`, trades its side of the recording gate for the exclusive one meanwhile.  The capture is
+ *  ALWAYS ended; after a failure the partial graph is destroyed, `graph` is empty, and the FIRST error is what comes
+ *  back: as the rc, with its text in *why when given (ending the capture may fail in turn and overwrite the library's
+ *  last error), or as launch_one's exception. */
+template <typename F>
+int record_graph(sxmc_stream_t stream, SetupLock* lock, bool held, unsigned n, OwnedGraph& graph, F&& launch_one,
+                 std::string* why = nullptr) {
+  RecordingScope recording(lock, held);
+  graph.reset();
+  int rc = sxmc_graph_begin_capture(stream);
+  if (rc) {
+    if (why) *why = sxmc_last_error();
+    return rc;
+  }
+  auto end = [&]() {
+    sxmc_graph_t recorded = nullptr;
+    const int rc2 = sxmc_graph_end_capture(stream, &recorded);
+    graph = OwnedGraph(recorded);
+    return rc2;
+  };
+  try {
+    for (unsigned k = 0; k < n && rc == SXMC_OK; k++) rc = launch_one();
+  } catch (...) {
+    end();
+    graph.reset();
+    throw;
+  }
+  if (rc && why) *why = sxmc_last_error();
+  const int rc2 = end();
+  if (rc == SXMC_OK && rc2 && why) *why = sxmc_last_error();
+  if (rc || rc2) graph.reset();
+  return rc ? rc : rc2;
+}
+
 /** Chains advanced TOGETHER (sxmc_multigroup_step_async): one fill pass over the shared sample tables per step for
  *  all of them, then every chain's own step end.  Shared by the MCMC objects of one lockstep set, each walking on
  *  its own host thread and on the set's ONE stream: a chain that is ready for its next run of steps leaves its
@@ -124,10 +209,6 @@ class LockstepSet {
   /** exclusive: the mutex that serialises set-up, graph recording and tear-down in this process (may be null). */
   LockstepSet(size_t nchains, sxmc_stream_t stream_, SetupLock* exclusive_ = nullptr)
       : stream(stream_), exclusive(exclusive_), groups(nchains, nullptr), args(nchains) {}
-  ~LockstepSet() {
-    if (graph) sxmc_graph_destroy(graph);
-    if (mg) sxmc_multigroup_destroy(mg);
-  }
   LockstepSet(const LockstepSet&) = delete;
   LockstepSet& operator=(const LockstepSet&) = delete;
 
@@ -145,7 +226,7 @@ class LockstepSet {
       generation++;
       if (rc != SXMC_OK) {
         broken = true;
-        why = sxmc_last_error();
+        if (why.empty()) why = sxmc_last_error();   // (a failed recording has left its first error there)
       }
       cv.notify_all();
       if (broken) throw std::runtime_error("lockstep set: " + why);
@@ -172,47 +253,33 @@ class LockstepSet {
  private:
   int launch(unsigned nsteps, unsigned graph_steps) {
     if (dirty) {
-      if (graph) sxmc_graph_destroy(graph);
-      graph = nullptr;
-      if (mg) sxmc_multigroup_destroy(mg);
-      mg = nullptr;
-      int rc = sxmc_multigroup_create(groups.data(), (int)groups.size(), &mg);
+      graph.reset();
+      int rc = sxmc_multigroup_create(groups.data(), (int)groups.size(), mg.put());
       if (rc) return rc;
       dirty = false;
       stepped = false;
     }
-    if (graph_steps > 0 && stepped && nsteps >= graph_steps) {
+    const RunSplit run = split_run(nsteps, graph_steps, !stepped);
+    if (run.replays > 0) {
       if (!graph || recorded != graph_steps) {
         // recording does not tolerate another thread's allocations: under the process's set-up mutex
         std::unique_lock<SetupLock> excl;
         if (exclusive) excl = std::unique_lock<SetupLock>(*exclusive);
-        RecordingScope recording(exclusive, exclusive != nullptr);
-        if (graph) sxmc_graph_destroy(graph);
-        graph = nullptr;
-        int rc = sxmc_graph_begin_capture(stream);
+        int rc = record_graph(stream, exclusive, exclusive != nullptr, graph_steps, graph,
+                              [&]() { return sxmc_multigroup_step_async(mg.get(), stream, args.data()); }, &why);
         if (rc) return rc;
-        for (unsigned k = 0; k < graph_steps && rc == SXMC_OK; k++) rc = sxmc_multigroup_step_async(mg, stream, args.data());
-        const std::string err = rc ? sxmc_last_error() : "";
-        int rc2 = sxmc_graph_end_capture(stream, &graph);
-        if (rc) {
-          if (graph) sxmc_graph_destroy(graph);
-          graph = nullptr;
-          (void)err;
-          return rc;
-        }
-        if (rc2) return rc2;
         recorded = graph_steps;
       }
-      int rc = sxmc_graph_launch(graph, stream, (int)(nsteps / graph_steps));
+      int rc = sxmc_graph_launch(graph.get(), stream, (int)run.replays);
       if (rc) return rc;
-      nsteps %= graph_steps;
+      nsteps = run.remainder;
     }
     for (unsigned k = 0; k < nsteps; k++) {
       // the first step of a new set of chains builds launch plans (allocations, a device-wide synchronisation),
       // which another set's recording does not tolerate: under the process's set-up mutex, like the recording
       std::unique_lock<SetupLock> excl;
       if (!stepped && exclusive) excl = std::unique_lock<SetupLock>(*exclusive);
-      int rc = sxmc_multigroup_step_async(mg, stream, args.data());
+      int rc = sxmc_multigroup_step_async(mg.get(), stream, args.data());
       if (rc) return rc;
       stepped = true;   // (the launch plans are in place once a step has been launched: recording may follow)
     }
@@ -224,8 +291,8 @@ class LockstepSet {
   SetupLock* exclusive;
   std::vector<sxmc_group_t> groups;
   std::vector<sxmc_step_args> args;
-  sxmc_multigroup_t mg = nullptr;
-  sxmc_graph_t graph = nullptr;
+  OwnedMultigroup mg;   // (declared before the graph recorded over it: destroyed after it)
+  OwnedGraph graph;
   unsigned recorded = 0;
   size_t arrived = 0;
   unsigned long long generation = 0;
@@ -375,437 +442,18 @@ class MCMC {
     return w;
   }
 
-  /** MCMC::operator() (mcmc.cpp:143-387).  data: rows of nobservables+1 floats (last = dataset id). */
+  /** MCMC::operator() (mcmc.cpp:143-387).  data: rows of nobservables+1 floats (last = dataset id).
+   *  Set up, choose the form of the steps, walk run by run, tear down: the parts are the members of Walk below. */
   Chain operator()(std::vector<float>& data, unsigned nsteps, float burnin_fraction,
                    const bool debug_mode = false, unsigned sync_interval = 10000) {
     const std::chrono::steady_clock::time_point walk_t0 = std::chrono::steady_clock::now();
-    std::unique_lock<SetupLock> excl;  // (first local: released last, after the arrays below are freed)
-    if (exclusive) excl = std::unique_lock<SetupLock>(*exclusive);
-    // array transfers of this walk are ordered on the chain's stream (a blocking copy through the legacy
-    // default stream would neither wait for a non-blocking stream nor leave other chains alone)
-    struct TransferGuard {
-      sxmc_stream_t prev;
-      explicit TransferGuard(sxmc_stream_t s) : prev(transfer_stream()) {
-        if (s) transfer_stream() = s;
-      }
-      ~TransferGuard() { transfer_stream() = prev; }
-    } transfer_guard(stream);
-    const unsigned burnin_steps = nsteps * burnin_fraction;
-    Chain chain;
-    chain.names = parameter_names;
-    const size_t ncol = nparameters + 1;
-
-    pdfz::Array<double> current_vector(nparameters, true), proposed_vector(nparameters, true);
-    for (size_t i = 0; i < nparameters; i++)
-      current_vector.writeOnlyHostPtr()[i] = parameter_means->readOnlyHostPtr()[i];
-    proposed_vector.writeOnlyHostPtr();
-    pdfz::Array<unsigned> normalizations(nsignals, true);
-    normalizations.writeOnlyHostPtr();
-    pdfz::Array<double> event_partial_sums(std::max<size_t>(nnllthreads, 1024), true);
-    event_partial_sums.writeOnlyHostPtr();
-    pdfz::Array<double> event_total_sum(1, true);
-    event_total_sum.writeOnlyHostPtr();
-    pdfz::Array<int> jump_counter(1, true), accept_counter(1, true);
-    jump_counter.writeOnlyHostPtr()[0] = 0;
-    accept_counter.writeOnlyHostPtr()[0] = 0;
-    pdfz::Array<float> jump_buffer((size_t)sync_interval * ncol, true);
-    pdfz::Array<double> current_nll(1, true), proposed_nll(1, true);
-    current_nll.writeOnlyHostPtr();
-    proposed_nll.writeOnlyHostPtr();
-
-    pdfz::Array<float> jump_width(nparameters, true);
-    {
-      const std::vector<float> w = initial_jump_widths();
-      for (size_t i = 0; i < nparameters; i++) jump_width.writeOnlyHostPtr()[i] = w[i];
-    }
-    const float scale_factor = 2.4 * 2.4 / nfloat;
-
-    // mcmc.cpp:230-242: bind, first evaluation at the current vector, then re-point at the proposal
-    const size_t nevents = data.size() / (nobservables + 1);
-    pdfz::Array<float> lut(nevents * nsignals, true);
-    for (size_t i = 0; i < pdfs.size(); i++) {
-      pdfz::Eval* p = pdfs[i];
-      p->SetEvalPoints(data);
-      p->SetPDFValueBuffer(&lut, (int)(i * nevents), 1);
-      p->SetNormalizationBuffer(&normalizations, (int)i);
-      p->SetParameterBuffer(&current_vector, (int)nsources);
-      p->EvalAsync();
-      p->EvalFinished();
-      p->SetParameterBuffer(&proposed_vector, (int)nsources);
-    }
-
-    nll(lut.readOnlyPtr(), nevents, current_vector.readOnlyPtr(), current_nll.writeOnlyPtr(),
-        normalizations.readOnlyPtr(), event_partial_sums.ptr(), event_total_sum.ptr());
-    SXMC_KERNEL_LAUNCH(pick_new_vector, 1, 64, 0, stream, (int)nparameters, rngs->ptr(), jump_width.readOnlyPtr(),
-                       current_vector.readOnlyPtr(), proposed_vector.writeOnlyPtr());
-
-    const bool batched = group != nullptr && !reference_form;
-    if (batched) {
-      // bindings must be current before the group reads them (proposal vector as parameter buffer)
-      for (pdfz::Eval* p : pdfs) dynamic_cast<pdfz::EvalHist*>(p)->Bind();
-      check(sxmc_group_set_lut_output(group, lut_output ? 1 : 0));
-      if (optimize && !optimized) {
-        check(sxmc_group_optimize(group, stream, nullptr));
-        optimized = true;
-      }
-    }
-    const bool reevaluate = nsystematics > 0 && !systematics_fixed;
-
-    // Recorded steps need a created stream (blocking: it still orders with the copies of the array
-    // accessors, which go through the legacy default stream) and the batched form.
-    const bool in_lockstep = lockstep && batched && reevaluate && consume;
-    const unsigned gsteps = (batched && reevaluate && !in_lockstep) ? graph_steps : 0;
-
-    // ---- look-ahead walk: a shadow set of evaluators over the same tables, bound to the look-ahead vector
-    bool ahead = (lookahead || lookahead_auto) && batched && reevaluate && consume && !in_lockstep && !lut_output &&
-                 nparameters <= 256;
-    if (ahead && lookahead_auto && !lookahead) {
-      int members = 0;
-      unsigned long long rows = 0, exact_rows = 0, never_rows = 0;
-      check(sxmc_group_codes_info(group, &members, &rows, &exact_rows, &never_rows));
-      ahead = members == 0;     // (a plan over codes walks sequentially)
-    }
-    if (ahead) {
-      // not every shape is offered the look-ahead pass (histograms beyond LDS; problems so small that the sequential
-      // step ends in the one-workgroup form, whose event sum is partitioned differently): those walk sequentially
-      int ok = 0;
-      check(sxmc_group_lookahead_supported(group, &ok));
-      ahead = ok != 0;
-    }
-    std::vector<std::unique_ptr<pdfz::EvalHist>> shadow;
-    sxmc_group_t shadow_group = nullptr;
-    sxmc_multigroup_t pair = nullptr;
-    pdfz::Array<double> ahead_vector(nparameters, true);
-    pdfz::Array<unsigned> ahead_norms(nsignals, true);
-    pdfz::Array<float> ahead_lut(ahead ? nevents * nsignals : 1, true);
-    pdfz::Array<int> ahead_stop(1, true);
-    struct AheadGuard {   // (the multigroup goes before its groups, the group before its evaluators)
-      sxmc_multigroup_t* pair;
-      sxmc_group_t* group;
-      ~AheadGuard() {
-        if (*pair) sxmc_multigroup_destroy(*pair);
-        if (*group) sxmc_group_destroy(*group);
-      }
-    } ahead_guard{&pair, &shadow_group};
-    if (ahead) {
-      ahead_vector.writeOnlyHostPtr();
-      ahead_norms.writeOnlyHostPtr();
-      ahead_lut.writeOnlyHostPtr();
-      std::vector<sxmc_hist_t> handles;
-      for (size_t i = 0; i < pdfs.size(); i++) {
-        pdfz::EvalHist* base = dynamic_cast<pdfz::EvalHist*>(pdfs[i]);
-        shadow.emplace_back(new pdfz::EvalHist(*base, pdfz::EvalHist::SharedSamples{}));
-        pdfz::EvalHist* p = shadow.back().get();
-        p->SetEvalPoints(data);
-        p->SetPDFValueBuffer(&ahead_lut, (int)(i * nevents), 1);
-        p->SetNormalizationBuffer(&ahead_norms, (int)i);
-        p->SetParameterBuffer(&ahead_vector, (int)nsources);
-        p->Bind();
-        handles.push_back(p->Handle());
-      }
-      check(sxmc_group_create(handles.data(), (int)handles.size(), &shadow_group));
-      check(sxmc_group_set_lut_output(shadow_group, 0));
-      // a pass of two evaluations is bound by vector issue and needs more registers than 1024 lanes leave each
-      // (spills inside the stream loop drain the loads in flight): 768 lanes, the kernel compiled for that bound
-      check(sxmc_group_set_launch_config(group, 768, 1));
-      check(sxmc_group_set_launch_config(shadow_group, 768, 1));
-      sxmc_group_t both[2] = {group, shadow_group};
-      check(sxmc_multigroup_create(both, 2, &pair));
-    }
-    bool ahead_planned = false;   // the look-ahead pair has launched once: its plans exist
-    bool setup_announced = false; // on_setup_done has been called
-    sxmc_stream_t strm = stream;
-    sxmc_graph_t graph = nullptr;
-    const bool own_stream = gsteps > 0 && !strm;
-    if (own_stream) check(sxmc_stream_create(&strm));
-
-    // Device pointers of one run of steps, resolved once per run: the accessors may copy (after the
-    // host wrote a counter or the widths), which must not happen while a graph is being recorded.
-    struct {
-      const float* lut;
-      const double *means, *sigmas, *nexpected;
-      const unsigned* n_mc;
-      const short* source_id;
-      const float* jump_width;
-      double *proposed, *current, *sums, *nll_current, *nll_proposed;
-      unsigned* norms;
-      int *accepted, *counter;
-      float* jump_buffer;
-      RNGState* rng;
-    } d;
-    auto resolve = [&]() {
-      d.lut = lut.readOnlyPtr();
-      d.means = parameter_means->readOnlyPtr();
-      d.sigmas = parameter_sigma->readOnlyPtr();
-      d.nexpected = nexpected->readOnlyPtr();
-      d.n_mc = n_mc->readOnlyPtr();
-      d.source_id = source_id->readOnlyPtr();
-      d.jump_width = jump_width.readOnlyPtr();
-      d.proposed = proposed_vector.ptr();
-      d.current = current_vector.ptr();
-      d.sums = event_partial_sums.ptr();
-      d.nll_current = current_nll.ptr();
-      d.nll_proposed = proposed_nll.ptr();
-      d.norms = normalizations.ptr();
-      d.accepted = accept_counter.ptr();
-      d.counter = jump_counter.ptr();
-      d.jump_buffer = jump_buffer.writeOnlyPtr();
-      d.rng = rngs->ptr();
-    };
-    auto one_step = [&]() {
-      int npartial = (int)nnllthreads;
-      if (batched && reevaluate && consume) {
-        // two launches: fill of all signals; lookup + event sum + step end + clearing for the next step
-        check(sxmc_group_step_async(group, strm, d.means, d.sigmas, d.rng, d.nll_current, d.nll_proposed, d.current,
-                                    d.proposed, d.accepted, d.counter, d.jump_buffer, (int)nparameters, nsources,
-                                    d.jump_width, d.nexpected, d.n_mc, d.source_id, d.norms, debug_mode ? 1 : 0));
-        return;
-      }
-      if (batched && reevaluate) {
-        // zero, fill of all signals in one kernel, lookup fused with the event partial sums
-        check(sxmc_group_eval_nll_async(group, strm, d.proposed, d.nexpected, d.n_mc, d.source_id, d.norms, d.sums,
-                                        &npartial));
-      } else {
-        if (reevaluate) {
-          // mcmc.cpp:264-271 as written.  (The evaluators launch on their own streams, which order with the legacy
-          // default stream -- where the reference launches its NLL kernels -- and with nothing else: a walk that was
-          // given its own stream waits for its step end before the evaluators read the new proposal.)
-          if (strm) check(sxmc_stream_synchronize(strm));
-          for (pdfz::Eval* p : pdfs) p->EvalAsync();
-          for (pdfz::Eval* p : pdfs) p->EvalFinished();
-        }
-        SXMC_KERNEL_LAUNCH(nll_event_chunks, nnllblocks, nllblocksize, 0, strm, d.lut, d.proposed, nevents, nsignals,
-                           d.nexpected, d.n_mc, d.source_id, d.norms, d.sums);
-      }
-      SXMC_KERNEL_LAUNCH(finish_nll_jump_pick_combo, 1, nreducethreads, nreducethreads * sizeof(double), strm,
-                         (size_t)npartial, d.sums, nsignals, nsources, d.means, d.sigmas, d.rng, d.nll_current,
-                         d.nll_proposed, d.current, d.proposed, d.accepted, d.counter, d.jump_buffer,
-                         (int)nparameters, d.jump_width, d.nexpected, d.n_mc, d.source_id, d.norms, debug_mode);
-    };
-    // Steps after which the jump buffer is read back (mcmc.cpp:351-377)
-    // (a plan with a boxed and an ordered form of the fill is asked for its form at every flush, from the parameters at
-    // that moment, and a chain moves -- config 3's resolution parameter by ~0.05 in 5 000 steps: flushes every
-    // adapt_interval steps bound how stale the choice gets; the chain does not depend on where the flushes fall)
-    bool two_forms = false;
-    auto flush_due = [&](unsigned i) {
-      return i % sync_interval == 0 || i == nsteps - 1 || i == burnin_steps - 1 || i == 2 * burnin_steps - 1 ||
-             (two_forms && adapt_interval > 0 && i % adapt_interval == adapt_interval - 1);
-    };
-
-    unsigned i = 0;
+    Walk w(*this, data, nsteps, burnin_fraction, debug_mode, sync_interval);
+    w.set_up();
+    w.choose_form();
     const std::chrono::steady_clock::time_point steps_t0 = std::chrono::steady_clock::now();
-    chain.setup_seconds = std::chrono::duration<double>(steps_t0 - walk_t0).count();
-    while (i < nsteps) {
-      // Re-tune the proposal from the burn-in samples (mcmc.cpp:274-311); the width becomes
-      // scale_factor x the standard deviation of the parameter over the steps kept so far
-      if (i == burnin_steps || i == 2 * burnin_steps) {
-        for (size_t j = 0; j < nparameters; j++) {
-          if (parameter_fixed[j]) continue;
-          const double sd = column_stddev(chain, j);
-          const double fit_width = sd > 0 ? sd : jump_width.readOnlyHostPtr()[j];
-          jump_width.hostPtr()[j] = scale_factor * fit_width;
-        }
-        if (!debug_mode) chain.rows.clear();
-      }
-
-      // steps i..f need the host only before the first and after the last
-      unsigned f = i;
-      while (!flush_due(f)) f++;
-      unsigned n = f - i + 1;
-      resolve();
-      // a plan with a boxed and an ordered form of the fill: the form of the steps up to the next flush, from the
-      // parameters the device holds now (sxmc_group_adapt_fill_form); recorded steps replay the old form, so they are
-      // recorded again further down
-      if (batched && reevaluate && !in_lockstep && !ahead) {
-        int form = 0, changed = 0;
-        check(sxmc_group_adapt_fill_form(group, &form, &changed));
-        two_forms = form != 0 && adapt_interval < sync_interval;
-        if (changed && graph) {
-          check(sxmc_graph_destroy(graph));
-          graph = nullptr;
-        }
-      }
-      const bool replay = !ahead && gsteps > 0 && i > 0 && n >= gsteps;
-      if (replay && !graph) {  // record gsteps steps once; the launch plan is current after the eager step 0
-        RecordingScope recording(exclusive, excl.owns_lock());
-        check(sxmc_graph_begin_capture(strm));
-        try {
-          for (unsigned k = 0; k < gsteps; k++) one_step();
-        } catch (...) {
-          sxmc_graph_end_capture(strm, &graph);
-          throw;
-        }
-        check(sxmc_graph_end_capture(strm, &graph));
-      }
-      // set-up is over once the first run of steps after step 0 has its graph (or needs none); a lockstep chain
-      // must not hold the lock while it waits for its partners, who need it for their own set-up.  The look-ahead
-      // walk builds its plans in its first pass and records its graph further down: it keeps the lock until then.
-      // The lock goes BEFORE the run is queued: a run is up to sync_interval steps -- a second of device work at
-      // config 3 -- and whoever holds the lock while that is queued keeps every other chain's set-up waiting.
-      if ((i > 0 || in_lockstep) && !ahead && excl.owns_lock()) excl.unlock();
-      if (i > 0 && !ahead && !setup_announced) {
-        setup_announced = true;
-        if (on_setup_done) on_setup_done();     // (an ensemble's lanes meet here: see MCMC::on_setup_done)
-      }
-      if (replay) {
-        check(sxmc_graph_launch(graph, strm, (int)(n / gsteps)));
-        n %= gsteps;
-      }
-      if (in_lockstep) {
-        // this run of steps together with the other chains of the set (recorded and replayed there)
-        sxmc_step_args a;
-        std::memset(&a, 0, sizeof a);   // (padding too: the set compares argument blocks bytewise)
-        a.d_means = d.means;
-        a.d_sigmas = d.sigmas;
-        a.d_rng = reinterpret_cast<sxmc_rng_state*>(d.rng);
-        a.d_nll_current = d.nll_current;
-        a.d_nll_proposed = d.nll_proposed;
-        a.d_v_current = d.current;
-        a.d_v_proposed = d.proposed;
-        a.d_accepted = d.accepted;
-        a.d_counter = d.counter;
-        a.d_jump_buffer = d.jump_buffer;
-        a.nparameters = (int)nparameters;
-        a.nsources = nsources;
-        a.d_jump_width = d.jump_width;
-        a.d_nexpected = d.nexpected;
-        a.d_n_mc = d.n_mc;
-        a.d_source_id = d.source_id;
-        a.d_norms = d.norms;
-        a.debug_mode = debug_mode ? 1 : 0;
-        lockstep->advance(lockstep_index, group, a, n, graph_steps);
-        n = 0;
-      }
-      if (ahead && n > 0) {
-        // exactly n more steps, taken one or two per pass: passes in rounds of about what is still needed, the step
-        // counter read back after each round; a pass beyond the stop does nothing (the counter was 0 at the flush)
-        sxmc_step_args a;
-        std::memset(&a, 0, sizeof a);
-        a.d_means = d.means;
-        a.d_sigmas = d.sigmas;
-        a.d_rng = reinterpret_cast<sxmc_rng_state*>(d.rng);
-        a.d_nll_current = d.nll_current;
-        a.d_nll_proposed = d.nll_proposed;
-        a.d_v_current = d.current;
-        a.d_v_proposed = d.proposed;
-        a.d_accepted = d.accepted;
-        a.d_counter = d.counter;
-        a.d_jump_buffer = d.jump_buffer;
-        a.nparameters = (int)nparameters;
-        a.nsources = nsources;
-        a.d_jump_width = d.jump_width;
-        a.d_nexpected = d.nexpected;
-        a.d_n_mc = d.n_mc;
-        a.d_source_id = d.source_id;
-        a.d_norms = d.norms;
-        a.debug_mode = debug_mode ? 1 : 0;
-        ahead_stop.writeOnlyHostPtr()[0] = (int)n;
-        const int* d_stop = ahead_stop.readOnlyPtr();
-        double* d_ahead = ahead_vector.ptr();
-        const unsigned* d_anorms = ahead_norms.ptr();
-        // the look-ahead vector for the chain as it stands (new widths after a re-tuning included)
-        check(sxmc_lookahead_begin(strm, (int)nparameters, reinterpret_cast<const sxmc_rng_state*>(d.rng), d.jump_width,
-                                   d.current, d_ahead));
-        auto one_pass = [&]() {
-          check(sxmc_multigroup_lookahead_step_async(pair, strm, &a, d_ahead, d_anorms, d_stop));
-          ahead_passes++;
-        };
-        unsigned done = 0;
-        while (done < n) {
-          const unsigned need = n - done;
-          const double rate = ahead_passes_seen >= 16 ? std::min(2.0, 1.03 * ahead_steps_seen / ahead_passes_seen) : 1.75;
-          unsigned k = std::max(1u, (unsigned)(need / rate));
-          const size_t p0 = ahead_passes;
-          // The pair's first pass builds its launch plans (allocations, a module load, a device-wide synchronisation)
-          // and the recording must not meet another thread's allocation: both under the set-up lock, like the
-          // sequential walk's recording.  Every other round only launches and waits on this chain's stream.
-          const bool records = gsteps > 0 && k > gsteps && !graph;
-          if (exclusive) {
-            if (!ahead_planned || records) {
-              if (!excl.owns_lock()) excl.lock();
-            } else if (i > 0 && excl.owns_lock()) {
-              excl.unlock();
-            }
-          }
-          if (gsteps > 0 && k > gsteps) {
-            if (!graph) {
-              one_pass();   // (plans in place before recording)
-              ahead_planned = true;
-              k--;
-              RecordingScope recording(exclusive, excl.owns_lock());
-              check(sxmc_graph_begin_capture(strm));
-              try {
-                for (unsigned q = 0; q < gsteps; q++) one_pass();
-              } catch (...) {
-                sxmc_graph_end_capture(strm, &graph);
-                throw;
-              }
-              check(sxmc_graph_end_capture(strm, &graph));
-              ahead_passes -= gsteps;
-              if (i > 0 && excl.owns_lock()) excl.unlock();
-            }
-            check(sxmc_graph_launch(graph, strm, (int)(k / gsteps)));
-            ahead_passes += (size_t)(k / gsteps) * gsteps;
-            k %= gsteps;
-          }
-          for (unsigned q = 0; q < k; q++) {
-            one_pass();
-            if (!ahead_planned) {
-              ahead_planned = true;
-              if (i > 0 && excl.owns_lock()) excl.unlock();
-            }
-          }
-          (void)jump_counter.ptr();   // (the device side changed behind the mirror's back: the host copy is stale)
-          const unsigned now = (unsigned)jump_counter.readOnlyHostPtr()[0];   // (a blocking copy on the chain's stream)
-          if (now <= done && now < n) throw pdfz::Error("look-ahead walk: the chain did not advance");
-          ahead_steps_seen += now - done;
-          ahead_passes_seen += ahead_passes - p0;
-          done = now;
-        }
-        n = 0;
-      }
-      for (unsigned k = 0; k < n; k++) one_step();
-
-      // Flush the jump buffer (mcmc.cpp:351-377); the host reads go through blocking copies
-      const int njumps = jump_counter.readOnlyHostPtr()[0];
-      const int naccepted = accept_counter.readOnlyHostPtr()[0];
-      if (verbose) {
-        std::printf("MCMC: Step %u/%u (%d in buffer, %d accepted)\n", f + 1, nsteps, njumps, naccepted);
-      }
-      const float* jb = jump_buffer.readOnlyHostPtr();
-      chain.rows.insert(chain.rows.end(), jb, jb + (size_t)njumps * ncol);
-      chain.accepted += (size_t)naccepted;
-      jump_counter.writeOnlyHostPtr()[0] = 0;
-      accept_counter.writeOnlyHostPtr()[0] = 0;
-      if (batched) {
-        // the cooperative step end waits inside its kernel, with a bound: a wait that ran into it left the steps of
-        // this run invalid -- never seen on a healthy device, and not to be passed on silently if it ever happens
-        unsigned timeouts = 0;
-        check(sxmc_group_step_end_timeouts(group, strm, &timeouts));
-        if (timeouts) {
-          throw pdfz::Error("MCMC: " + std::to_string(timeouts) + " workgroup(s) of the cooperative step end gave up "
-                            "waiting (sxmc_group_step_end_timeouts): the chain is not valid");
-        }
-      }
-      i = f + 1;
-    }
-    if (strm) check(sxmc_stream_synchronize(strm));
-    chain.steps_seconds = std::chrono::duration<double>(std::chrono::steady_clock::now() - steps_t0).count();
-    if (on_steps_done) on_steps_done();
-    if (lockstep) lockstep->leave(lockstep_index);
-    // the evaluators borrowed this walk's arrays (lookup table, normalisations, parameter vectors): un-bind them
-    // before they die, or the next evaluation of an evaluator would touch destroyed arrays
-    for (pdfz::Eval* p : pdfs) p->ForgetBuffers();
-    for (auto& p : shadow) p->ForgetBuffers();
-    if (exclusive && !excl.owns_lock()) excl.lock();  // tear-down frees device memory
-    if (graph) check(sxmc_graph_destroy(graph));
-    if (own_stream) check(sxmc_stream_destroy(strm));
-    if (stream) {
-      check(sxmc_stream_synchronize(stream));  // this chain only: others may be running beside it
-    } else {
-      check(sxmc_device_synchronize());
-    }
-    return chain;
+    w.chain.setup_seconds = std::chrono::duration<double>(steps_t0 - walk_t0).count();
+    for (unsigned i = 0; i < nsteps;) i = w.run(i);
+    return w.finish(steps_t0);
   }
 
   size_t NumParameters() const { return nparameters; }
@@ -850,6 +498,473 @@ class MCMC {
   }
 
  private:
+  /** The arguments of a step: the library's block plus the two pointers it lacks.  Zeroed once, padding included (a
+   *  LockstepSet compares blocks bytewise), and filled once per run (Walk::resolve). */
+  struct StepArgs {
+    sxmc_step_args a;
+    const float* lut;
+    double* sums;
+  };
+
+  /** The look-ahead walk's second set of evaluators over the same tables, bound to the look-ahead vector, and the pair
+   *  it forms with the chain's own group.  Members die in reverse order: the pair before its groups, the group before
+   *  its evaluators, the evaluators before the arrays they borrowed. */
+  struct Shadow {
+    Shadow(size_t nparameters, size_t nsignals, size_t nevents)
+        : vector(nparameters, true), norms(nsignals, true), lut(nevents * nsignals, true), stop(1, true) {}
+    pdfz::Array<double> vector;
+    pdfz::Array<unsigned> norms;
+    pdfz::Array<float> lut;
+    pdfz::Array<int> stop;
+    std::vector<std::unique_ptr<pdfz::EvalHist>> evaluators;
+    OwnedGroup group;
+    OwnedMultigroup pair;
+    bool planned = false;   //!< the pair has launched once: its launch plans exist
+  };
+
+  /** array transfers of a walk are ordered on the chain's stream (a blocking copy through the legacy default stream
+   *  would neither wait for a non-blocking stream nor leave other chains alone) */
+  struct TransferGuard {
+    sxmc_stream_t prev;
+    explicit TransferGuard(sxmc_stream_t s) : prev(transfer_stream()) {
+      if (s) transfer_stream() = s;
+    }
+    ~TransferGuard() { transfer_stream() = prev; }
+  };
+
+  /** One walk of the chain: its arrays, its graph, its stream, and the set-up lock it holds or has dropped.  THE LOCK IS
+   *  THE FIRST MEMBER: it is released last, after every array below is freed.  ~Walk is the walk's scope guard: its body
+   *  runs before any member dies, on the normal path (finish() has torn down then) and when a check() or a hook of the
+   *  caller's threw -- then it tears down with errors swallowed, and the exception travels on. */
+  struct Walk {
+    MCMC& m;
+    std::unique_lock<SetupLock> excl;
+    TransferGuard transfer_guard;
+    std::vector<float>& data;
+    const bool debug_mode;
+    const WalkSchedule plan;   // which steps end a run and where the widths are re-tuned: walk_plan.h
+    const size_t ncol, nevents;
+    const float scale_factor;
+    Chain chain;
+    pdfz::Array<double> current_vector, proposed_vector;
+    pdfz::Array<unsigned> normalizations;
+    pdfz::Array<double> event_partial_sums, event_total_sum;
+    pdfz::Array<int> jump_counter, accept_counter;
+    pdfz::Array<float> jump_buffer;
+    pdfz::Array<double> current_nll, proposed_nll;
+    pdfz::Array<float> jump_width, lut;
+    std::unique_ptr<Shadow> shadow;   // look-ahead walk only
+    OwnedGraph graph;
+    OwnedStream own_stream;           // recorded steps need a created stream: the walk's own when it was given none
+    sxmc_stream_t strm;
+    WalkForm form{};
+    StepArgs d;
+    bool two_forms = false;           // the plan holds a boxed and an ordered form of the fill (asked at every run)
+    bool setup_announced = false;     // on_setup_done has been called
+    bool torn_down = false;
+
+    Walk(MCMC& m_, std::vector<float>& data_, unsigned nsteps, float burnin_fraction, bool debug_mode_,
+         unsigned sync_interval)
+        : m(m_),
+          excl(m_.exclusive ? std::unique_lock<SetupLock>(*m_.exclusive) : std::unique_lock<SetupLock>()),
+          transfer_guard(m_.stream),
+          data(data_),
+          debug_mode(debug_mode_),
+          plan{nsteps, (unsigned)(nsteps * burnin_fraction), sync_interval, m_.adapt_interval},
+          ncol(m_.nparameters + 1),
+          nevents(data_.size() / (m_.nobservables + 1)),
+          scale_factor(2.4 * 2.4 / m_.nfloat),
+          current_vector(m_.nparameters, true),
+          proposed_vector(m_.nparameters, true),
+          normalizations(m_.nsignals, true),
+          event_partial_sums(std::max<size_t>(m_.nnllthreads, 1024), true),
+          event_total_sum(1, true),
+          jump_counter(1, true),
+          accept_counter(1, true),
+          jump_buffer((size_t)sync_interval * ncol, true),
+          current_nll(1, true),
+          proposed_nll(1, true),
+          jump_width(m_.nparameters, true),
+          lut(nevents * m_.nsignals, true),
+          strm(m_.stream) {
+      std::memset(&d, 0, sizeof d);
+      chain.names = m.parameter_names;
+    }
+    ~Walk() {
+      if (torn_down) return;
+      try {
+        tear_down(true);
+      } catch (...) {   // (the walk has failed already: its own exception is the one to report)
+      }
+    }
+    Walk(const Walk&) = delete;
+    Walk& operator=(const Walk&) = delete;
+
+    /** Buffers, bindings and the first evaluation (mcmc.cpp:198-242).  Set-up lock: held throughout. */
+    void set_up() {
+      for (size_t i = 0; i < m.nparameters; i++)
+        current_vector.writeOnlyHostPtr()[i] = m.parameter_means->readOnlyHostPtr()[i];
+      proposed_vector.writeOnlyHostPtr();
+      normalizations.writeOnlyHostPtr();
+      event_partial_sums.writeOnlyHostPtr();
+      event_total_sum.writeOnlyHostPtr();
+      jump_counter.writeOnlyHostPtr()[0] = 0;
+      accept_counter.writeOnlyHostPtr()[0] = 0;
+      current_nll.writeOnlyHostPtr();
+      proposed_nll.writeOnlyHostPtr();
+      const std::vector<float> w = m.initial_jump_widths();
+      for (size_t i = 0; i < m.nparameters; i++) jump_width.writeOnlyHostPtr()[i] = w[i];
+
+      // mcmc.cpp:230-242: bind, first evaluation at the current vector, then re-point at the proposal
+      for (size_t i = 0; i < m.pdfs.size(); i++) {
+        pdfz::Eval* p = m.pdfs[i];
+        p->SetEvalPoints(data);
+        p->SetPDFValueBuffer(&lut, (int)(i * nevents), 1);
+        p->SetNormalizationBuffer(&normalizations, (int)i);
+        p->SetParameterBuffer(&current_vector, (int)m.nsources);
+        p->EvalAsync();
+        p->EvalFinished();
+        p->SetParameterBuffer(&proposed_vector, (int)m.nsources);
+      }
+      m.nll(lut.readOnlyPtr(), nevents, current_vector.readOnlyPtr(), current_nll.writeOnlyPtr(),
+            normalizations.readOnlyPtr(), event_partial_sums.ptr(), event_total_sum.ptr());
+      SXMC_KERNEL_LAUNCH(pick_new_vector, 1, 64, 0, m.stream, (int)m.nparameters, m.rngs->ptr(),
+                         jump_width.readOnlyPtr(), current_vector.readOnlyPtr(), proposed_vector.writeOnlyPtr());
+    }
+
+    /** The form of the steps (walk_plan.h: choose_form), narrowed by what the device says about the look-ahead pass;
+     *  then what the form needs: the group bound and tuned, the shadow set, a stream to record on.  Lock: held. */
+    void choose_form() {
+      form = sxmc::choose_form(WalkFlags{m.group != nullptr, m.reference_form,
+                                         m.nsystematics > 0 && !m.systematics_fixed, m.consume, m.lut_output,
+                                         m.lockstep != nullptr, m.lookahead || m.lookahead_auto, m.nparameters,
+                                         m.graph_steps});
+      if (form.batched) {
+        // bindings must be current before the group reads them (proposal vector as parameter buffer)
+        for (pdfz::Eval* p : m.pdfs) dynamic_cast<pdfz::EvalHist*>(p)->Bind();
+        check(sxmc_group_set_lut_output(m.group, m.lut_output ? 1 : 0));
+        if (m.optimize && !m.optimized) {
+          check(sxmc_group_optimize(m.group, m.stream, nullptr));
+          m.optimized = true;
+        }
+      }
+      if (form.step == WalkForm::LOOKAHEAD && m.lookahead_auto && !m.lookahead) {
+        int members = 0;
+        unsigned long long rows = 0, exact_rows = 0, never_rows = 0;
+        check(sxmc_group_codes_info(m.group, &members, &rows, &exact_rows, &never_rows));
+        if (members != 0) form = form.narrowed();     // (a plan over codes walks sequentially)
+      }
+      if (form.step == WalkForm::LOOKAHEAD) {
+        // not every shape is offered the look-ahead pass (histograms beyond LDS; problems so small that the sequential
+        // step ends in the one-workgroup form, whose event sum is partitioned differently): those walk sequentially
+        int ok = 0;
+        check(sxmc_group_lookahead_supported(m.group, &ok));
+        if (!ok) form = form.narrowed();
+      }
+      if (form.step == WalkForm::LOOKAHEAD) set_up_shadow();
+      // Recorded steps need a created stream (blocking: it still orders with the copies of the array accessors, which
+      // go through the legacy default stream)
+      if (form.gsteps > 0 && !strm) {
+        check(sxmc_stream_create(own_stream.put()));
+        strm = own_stream.get();
+      }
+    }
+
+    /** Look-ahead walk: a shadow set of evaluators over the same tables, bound to the look-ahead vector.  Lock: held. */
+    void set_up_shadow() {
+      shadow.reset(new Shadow(m.nparameters, m.nsignals, nevents));
+      shadow->vector.writeOnlyHostPtr();
+      shadow->norms.writeOnlyHostPtr();
+      shadow->lut.writeOnlyHostPtr();
+      std::vector<sxmc_hist_t> handles;
+      for (size_t i = 0; i < m.pdfs.size(); i++) {
+        pdfz::EvalHist* base = dynamic_cast<pdfz::EvalHist*>(m.pdfs[i]);
+        shadow->evaluators.emplace_back(new pdfz::EvalHist(*base, pdfz::EvalHist::SharedSamples{}));
+        pdfz::EvalHist* p = shadow->evaluators.back().get();
+        p->SetEvalPoints(data);
+        p->SetPDFValueBuffer(&shadow->lut, (int)(i * nevents), 1);
+        p->SetNormalizationBuffer(&shadow->norms, (int)i);
+        p->SetParameterBuffer(&shadow->vector, (int)m.nsources);
+        p->Bind();
+        handles.push_back(p->Handle());
+      }
+      check(sxmc_group_create(handles.data(), (int)handles.size(), shadow->group.put()));
+      check(sxmc_group_set_lut_output(shadow->group.get(), 0));
+      // a pass of two evaluations is bound by vector issue and needs more registers than 1024 lanes leave each
+      // (spills inside the stream loop drain the loads in flight): 768 lanes, the kernel compiled for that bound
+      check(sxmc_group_set_launch_config(m.group, 768, 1));
+      check(sxmc_group_set_launch_config(shadow->group.get(), 768, 1));
+      sxmc_group_t both[2] = {m.group, shadow->group.get()};
+      check(sxmc_multigroup_create(both, 2, shadow->pair.put()));
+    }
+
+    /** Device pointers of one run of steps, resolved once per run: the accessors may copy (after the host wrote a
+     *  counter or the widths), which must not happen while a graph is being recorded. */
+    void resolve() {
+      d.lut = lut.readOnlyPtr();
+      d.sums = event_partial_sums.ptr();
+      d.a.d_means = m.parameter_means->readOnlyPtr();
+      d.a.d_sigmas = m.parameter_sigma->readOnlyPtr();
+      d.a.d_rng = m.rngs->ptr();
+      d.a.d_nll_current = current_nll.ptr();
+      d.a.d_nll_proposed = proposed_nll.ptr();
+      d.a.d_v_current = current_vector.ptr();
+      d.a.d_v_proposed = proposed_vector.ptr();
+      d.a.d_accepted = accept_counter.ptr();
+      d.a.d_counter = jump_counter.ptr();
+      d.a.d_jump_buffer = jump_buffer.writeOnlyPtr();
+      d.a.nparameters = (int)m.nparameters;
+      d.a.nsources = m.nsources;
+      d.a.d_jump_width = jump_width.readOnlyPtr();
+      d.a.d_nexpected = m.nexpected->readOnlyPtr();
+      d.a.d_n_mc = m.n_mc->readOnlyPtr();
+      d.a.d_source_id = m.source_id->readOnlyPtr();
+      d.a.d_norms = normalizations.ptr();
+      d.a.debug_mode = debug_mode ? 1 : 0;
+    }
+
+    /** One step of the sequential walk, in the form's launches. */
+    void one_step() {
+      const sxmc_step_args& a = d.a;
+      int npartial = (int)m.nnllthreads;
+      if (form.step == WalkForm::CONSUMING) {
+        // two launches: fill of all signals; lookup + event sum + step end + clearing for the next step
+        check(sxmc_group_step_async(m.group, strm, a.d_means, a.d_sigmas, a.d_rng, a.d_nll_current, a.d_nll_proposed,
+                                    a.d_v_current, a.d_v_proposed, a.d_accepted, a.d_counter, a.d_jump_buffer,
+                                    a.nparameters, a.nsources, a.d_jump_width, a.d_nexpected, a.d_n_mc, a.d_source_id,
+                                    a.d_norms, a.debug_mode));
+        return;
+      }
+      if (form.step == WalkForm::BATCHED) {
+        // zero, fill of all signals in one kernel, lookup fused with the event partial sums
+        check(sxmc_group_eval_nll_async(m.group, strm, a.d_v_proposed, a.d_nexpected, a.d_n_mc, a.d_source_id,
+                                        a.d_norms, d.sums, &npartial));
+      } else {
+        if (form.reevaluate) {
+          // mcmc.cpp:264-271 as written.  (The evaluators launch on their own streams, which order with the legacy
+          // default stream -- where the reference launches its NLL kernels -- and with nothing else: a walk that was
+          // given its own stream waits for its step end before the evaluators read the new proposal.)
+          if (strm) check(sxmc_stream_synchronize(strm));
+          for (pdfz::Eval* p : m.pdfs) p->EvalAsync();
+          for (pdfz::Eval* p : m.pdfs) p->EvalFinished();
+        }
+        SXMC_KERNEL_LAUNCH(nll_event_chunks, m.nnllblocks, m.nllblocksize, 0, strm, d.lut, a.d_v_proposed, nevents,
+                           m.nsignals, a.d_nexpected, a.d_n_mc, a.d_source_id, a.d_norms, d.sums);
+      }
+      SXMC_KERNEL_LAUNCH(finish_nll_jump_pick_combo, 1, m.nreducethreads, m.nreducethreads * sizeof(double), strm,
+                         (size_t)npartial, d.sums, m.nsignals, m.nsources, a.d_means, a.d_sigmas, a.d_rng,
+                         a.d_nll_current, a.d_nll_proposed, a.d_v_current, a.d_v_proposed, a.d_accepted, a.d_counter,
+                         a.d_jump_buffer, a.nparameters, a.d_jump_width, a.d_nexpected, a.d_n_mc, a.d_source_id,
+                         a.d_norms, debug_mode);
+    }
+
+    /** The run of steps that starts at step i: what the host does before it (re-tuning, the form of the fill), the
+     *  steps in the walk's form, the flush after them.  Returns the first step of the next run. */
+    unsigned run(unsigned i) {
+      if (plan.retune_due(i)) retune();
+      // steps i..f need the host only before the first and after the last
+      const unsigned f = plan.run_end(i, two_forms);
+      resolve();
+      // a plan with a boxed and an ordered form of the fill: the form of the steps up to the next flush, from the
+      // parameters the device holds now (sxmc_group_adapt_fill_form); recorded steps replay the old form, so they are
+      // recorded again by the run
+      if (form.adapts_fill_form()) {
+        int fill_form = 0, changed = 0;
+        check(sxmc_group_adapt_fill_form(m.group, &fill_form, &changed));
+        two_forms = fill_form != 0 && plan.adapt_interval < plan.sync_interval;
+        if (changed) check(graph.reset());
+      }
+      const unsigned n = f - i + 1;
+      switch (form.step) {
+        case WalkForm::LOCKSTEP: lockstep_run(i, n); break;
+        case WalkForm::LOOKAHEAD: lookahead_run(i, n); break;
+        default: sequential_run(i, n);
+      }
+      flush(f);
+      return f + 1;
+    }
+
+    /** Re-tune the proposal from the burn-in samples (mcmc.cpp:274-311); the width becomes scale_factor x the standard
+     *  deviation of the parameter over the steps kept so far */
+    void retune() {
+      for (size_t j = 0; j < m.nparameters; j++) {
+        if (m.parameter_fixed[j]) continue;
+        const double sd = column_stddev(chain, j);
+        const double fit_width = sd > 0 ? sd : jump_width.readOnlyHostPtr()[j];
+        jump_width.hostPtr()[j] = scale_factor * fit_width;
+      }
+      if (!debug_mode) chain.rows.clear();
+    }
+
+    /** Set-up is over: the lock goes BEFORE a run is queued -- a run is up to sync_interval steps, a second of device
+     *  work at config 3, and whoever holds the lock while that is queued keeps every other chain's set-up waiting.
+     *  announce: tell the caller, once (an ensemble's lanes meet there: see MCMC::on_setup_done). */
+    void release_before_queueing(bool announce) {
+      if (excl.owns_lock()) excl.unlock();
+      if (announce && !setup_announced) {
+        setup_announced = true;
+        if (m.on_setup_done) m.on_setup_done();
+      }
+    }
+
+    /** n steps launched by this chain: graph replays (split_run) and the remainder one by one.  Lock: the first run
+     *  (step 0, eager: it builds the launch plans) keeps it; the first run after it records its graph under the lock,
+     *  as it was taken at set-up, and releases it before anything is queued; later runs hold no lock, and re-record
+     *  (a changed fill form) without it. */
+    void sequential_run(unsigned i, unsigned n) {
+      const RunSplit split = split_run(n, form.gsteps, i == 0);
+      if (split.replays > 0 && !graph) {
+        check(record_graph(strm, m.exclusive, excl.owns_lock(), form.gsteps, graph, [&]() {
+          one_step();
+          return SXMC_OK;
+        }));
+      }
+      if (i > 0) release_before_queueing(true);
+      if (split.replays > 0) check(sxmc_graph_launch(graph.get(), strm, (int)split.replays));
+      for (unsigned k = 0; k < split.remainder; k++) one_step();
+    }
+
+    /** n steps together with the other chains of the set (recorded and replayed there).  Lock: released before the
+     *  chain waits for its partners, who need it for their own set-up; the set takes it itself where it must. */
+    void lockstep_run(unsigned i, unsigned n) {
+      release_before_queueing(i > 0);
+      m.lockstep->advance(m.lockstep_index, m.group, d.a, n, m.graph_steps);
+    }
+
+    /** Exactly n steps, taken one or two per pass: passes in rounds of about what is still needed (lookahead_round),
+     *  the step counter read back after each round; a pass beyond the stop does nothing (the counter was 0 at the
+     *  flush).  Never calls on_setup_done.  Lock: see lookahead_lock. */
+    void lookahead_run(unsigned i, unsigned n) {
+      Shadow& s = *shadow;
+      s.stop.writeOnlyHostPtr()[0] = (int)n;
+      const int* d_stop = s.stop.readOnlyPtr();
+      double* d_ahead = s.vector.ptr();
+      const unsigned* d_anorms = s.norms.ptr();
+      // the look-ahead vector for the chain as it stands (new widths after a re-tuning included)
+      check(sxmc_lookahead_begin(strm, d.a.nparameters, d.a.d_rng, d.a.d_jump_width, d.a.d_v_current, d_ahead));
+      auto one_pass = [&]() {
+        check(sxmc_multigroup_lookahead_step_async(s.pair.get(), strm, &d.a, d_ahead, d_anorms, d_stop));
+        m.ahead_passes++;
+      };
+      unsigned done = 0;
+      while (done < n) {
+        const LookaheadRound round =
+            lookahead_round(n - done, m.ahead_steps_seen, m.ahead_passes_seen, form.gsteps, (bool)graph);
+        const size_t p0 = m.ahead_passes;
+        lookahead_lock(i, round.records);
+        if (round.records) {
+          one_pass();   // (plans in place before recording)
+          s.planned = true;
+          check(record_graph(strm, m.exclusive, excl.owns_lock(), form.gsteps, graph, [&]() {
+            one_pass();
+            return SXMC_OK;
+          }));
+          m.ahead_passes -= form.gsteps;   // (recorded, not launched)
+          if (i > 0 && excl.owns_lock()) excl.unlock();   // released after the recording
+        }
+        if (round.replays > 0) {
+          check(sxmc_graph_launch(graph.get(), strm, (int)round.replays));
+          m.ahead_passes += (size_t)round.replays * form.gsteps;
+        }
+        for (unsigned q = 0; q < round.single_passes; q++) {
+          one_pass();
+          if (!s.planned) {
+            s.planned = true;
+            if (i > 0 && excl.owns_lock()) excl.unlock();   // released after the pair's first pass
+          }
+        }
+        (void)jump_counter.ptr();   // (the device side changed behind the mirror's back: the host copy is stale)
+        const unsigned now = (unsigned)jump_counter.readOnlyHostPtr()[0];   // (a blocking copy on the chain's stream)
+        if (now <= done && now < n) throw pdfz::Error("look-ahead walk: the chain did not advance");
+        m.ahead_steps_seen += now - done;
+        m.ahead_passes_seen += m.ahead_passes - p0;
+        done = now;
+      }
+    }
+
+    /** The pair's first pass builds its launch plans (allocations, a module load, a device-wide synchronisation) and a
+     *  recording must not meet another thread's allocation: a round that does either takes the set-up lock, like the
+     *  sequential walk's recording.  Every other round only launches and waits on this chain's stream: after the first
+     *  run it holds no lock.  (The first run keeps the lock, as the sequential walk's does.) */
+    void lookahead_lock(unsigned i, bool records) {
+      if (!m.exclusive) return;
+      if (!shadow->planned || records) {
+        if (!excl.owns_lock()) excl.lock();
+      } else if (i > 0 && excl.owns_lock()) {
+        excl.unlock();
+      }
+    }
+
+    /** Flush the jump buffer after step f (mcmc.cpp:351-377); the host reads go through blocking copies.  Lock: as the
+     *  run left it. */
+    void flush(unsigned f) {
+      const int njumps = jump_counter.readOnlyHostPtr()[0];
+      const int naccepted = accept_counter.readOnlyHostPtr()[0];
+      if (m.verbose) {
+        std::printf("MCMC: Step %u/%u (%d in buffer, %d accepted)\n", f + 1, plan.nsteps, njumps, naccepted);
+      }
+      const float* jb = jump_buffer.readOnlyHostPtr();
+      chain.rows.insert(chain.rows.end(), jb, jb + (size_t)njumps * ncol);
+      chain.accepted += (size_t)naccepted;
+      jump_counter.writeOnlyHostPtr()[0] = 0;
+      accept_counter.writeOnlyHostPtr()[0] = 0;
+      if (form.batched) {
+        // the cooperative step end waits inside its kernel, with a bound: a wait that ran into it left the steps of
+        // this run invalid -- never seen on a healthy device, and not to be passed on silently if it ever happens
+        unsigned timeouts = 0;
+        check(sxmc_group_step_end_timeouts(m.group, strm, &timeouts));
+        if (timeouts) {
+          throw pdfz::Error("MCMC: " + std::to_string(timeouts) + " workgroup(s) of the cooperative step end gave up "
+                            "waiting (sxmc_group_step_end_timeouts): the chain is not valid");
+        }
+      }
+    }
+
+    /** The end of a walk that went well: the caller's hook once the last step has finished, the tear-down with its
+     *  errors thrown, the final wait. */
+    Chain finish(std::chrono::steady_clock::time_point steps_t0) {
+      if (strm) check(sxmc_stream_synchronize(strm));
+      chain.steps_seconds = std::chrono::duration<double>(std::chrono::steady_clock::now() - steps_t0).count();
+      if (m.on_steps_done) m.on_steps_done();
+      tear_down(false);
+      if (m.stream) {
+        check(sxmc_stream_synchronize(m.stream));  // this chain only: others may be running beside it
+      } else {
+        check(sxmc_device_synchronize());
+      }
+      return std::move(chain);
+    }
+
+    /** What every walk leaves behind, however it ended.  unwinding: the walk failed -- wait for what it queued first
+     *  (finish() has waited already), and report nothing: the walk's own exception is the one that travels on. */
+    void tear_down(bool unwinding) {
+      torn_down = true;
+      if (unwinding) (void)(strm ? sxmc_stream_synchronize(strm) : sxmc_device_synchronize());
+      int rc_graph = SXMC_OK, rc_stream = SXMC_OK;
+      auto release = [&]() {   // tear-down frees device memory: under the lock, and the arrays die under it too
+        if (m.exclusive && !excl.owns_lock()) excl.lock();
+        rc_graph = graph.reset();
+        rc_stream = own_stream.reset();
+      };
+      try {
+        // the evaluators borrowed this walk's arrays (lookup table, normalisations, parameter vectors): un-bind them
+        // before the arrays die, or the next evaluation of an evaluator would touch destroyed arrays
+        for (pdfz::Eval* p : m.pdfs) p->ForgetBuffers();
+        if (shadow)
+          for (auto& p : shadow->evaluators) p->ForgetBuffers();
+        // (before the lock is re-taken: the set's launcher takes the two in the other order)
+        if (m.lockstep) m.lockstep->leave(m.lockstep_index);
+      } catch (...) {
+        release();   // whatever those threw, nothing is freed outside the lock
+        throw;
+      }
+      release();
+      if (!unwinding) {
+        check(rc_graph);
+        check(rc_stream);
+      }
+    }
+  };
   sxmc_stream_t stream;  //!< every launch of this chain goes here (null: the legacy default stream, as the
                          //!< reference; one non-blocking stream per chain when several run on one GPU)
   size_t nsources, nsignals, nsystematics, nobservables;

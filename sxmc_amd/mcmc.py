@@ -42,6 +42,15 @@ def make_systematic(desc):
 ADAPT_INTERVAL = 1000
 
 
+def flush_due(i, nsteps, burnin, sync_interval, adapt_interval, two_forms):
+    """Is the jump buffer read back after step i (mcmc.cpp:351-377)?  The reference's flushes -- every sync_interval
+    steps, the last step, the step before each re-tuning -- and, for a plan with two forms of the fill (two_forms),
+    every adapt_interval steps (0: never).  The rule of sxmc::WalkSchedule::flush_due (walk_plan.h), whose unsigned
+    terms burnin - 1 and 2 * burnin - 1 match no step when burnin is 0, as -1 does here."""
+    return (i % sync_interval == 0 or i == nsteps - 1 or i == burnin - 1 or i == 2 * burnin - 1 or
+            bool(two_forms and adapt_interval > 0 and i % adapt_interval == adapt_interval - 1))
+
+
 class MCMC:
     def __init__(self, workload, seed=1234, stream=None, fused=True, samples_on_device=None, share_with=None,
                  lut_output=True, consume=False):
@@ -288,13 +297,13 @@ class MCMC:
     def flush_schedule(self):
         """Indices of the steps after which the jump buffer is read back (mcmc.cpp:351-377), ascending.  The
         re-tuning points (burnin_steps, 2 * burnin_steps) each directly follow one of them."""
-        n, b = self._nsteps, self._burnin
-        due = {k for k in range(0, n, self.sync_interval)} | {k for k in (n - 1, b - 1, 2 * b - 1) if 0 <= k < n}
-        # a plan with two forms of the fill (sxmc_group_adapt_fill_form is asked at every flush): the choice is made from
-        # the parameters at the flush, and a chain moves -- flushes every ADAPT_INTERVAL steps bound how stale it gets
-        if self._two_forms():
-            due |= {k for k in range(ADAPT_INTERVAL - 1, n, ADAPT_INTERVAL)}
-        return sorted(due)
+        n, b, two_forms = self._nsteps, self._burnin, self._two_forms()
+        # flush_due decides; it is asked only at the steps where one of its terms can hold, not at every step of the walk
+        ask = set(range(0, n, self.sync_interval)) | {n - 1, b - 1, 2 * b - 1}
+        if two_forms and ADAPT_INTERVAL > 0:
+            ask |= set(range(ADAPT_INTERVAL - 1, n, ADAPT_INTERVAL))
+        return sorted(i for i in ask
+                      if 0 <= i < n and flush_due(i, n, b, self.sync_interval, ADAPT_INTERVAL, two_forms))
 
     def capture_steps(self, k, debug_mode=False):
         """Records k steps on this chain's stream as one HIP graph.  One step must have
@@ -365,9 +374,9 @@ class MCMC:
                 self._rows = [np.zeros((0, self.nparameters + 1), np.float32)]
 
     def _flush_if_due(self, i):
-        b = self._burnin
-        if i % self.sync_interval == 0 or i == self._nsteps - 1 or i == b - 1 or i == 2 * b - 1 or \
-                (i % ADAPT_INTERVAL == ADAPT_INTERVAL - 1 and self._two_forms()):
+        def due(two_forms):
+            return flush_due(i, self._nsteps, self._burnin, self.sync_interval, ADAPT_INTERVAL, two_forms)
+        if due(False) or (due(True) and self._two_forms()):     # (the plan is asked only where its answer matters)
             r, nacc = self.flush(device_wide=False)                # mcmc.cpp:351-377
             self._rows.append(r)
             self._accepted += nacc

@@ -16,6 +16,7 @@
     failed++;                                                                              \
     std::printf("[ FAIL ] %s\n    pdfz::Error: %s\n", full.c_str(), e.msg.c_str());
 #include "mini_test.h"
+#include "small_fit.h"
 
 using std::isnan;
 
@@ -366,63 +367,7 @@ TEST(DeviceArray, BlockPoolRecyclesBlocksInsideAScope) {
   EXPECT_EQ(9, d.hostPtr()[3]);
 }
 
-// ------------------------------------------------------------------ NLL launch points + MCMC driver
-static unsigned lcg(unsigned& s) {
-  s = s * 1664525u + 1013904223u;
-  return s;
-}
-static float uni(unsigned& s) { return (lcg(s) >> 8) * (1.0f / 16777216.0f); }
-
-struct SmallFit {
-  // 3 signals, 2 observables + truth + dataset, shift + resolution systematics
-  void SetUp() {
-    unsigned s = 12345;
-    observables.resize(2);
-    observables[0].field_index = 0; observables[0].bins = 12; observables[0].lower = 0; observables[0].upper = 1;
-    observables[1].field_index = 1; observables[1].bins = 9; observables[1].lower = 0; observables[1].upper = 2;
-    systematics.resize(2);
-    systematics[0].name = "shift"; systematics[0].type = pdfz::Systematic::SHIFT;
-    systematics[0].observable_field_index = 1; systematics[0].means = {0.0}; systematics[0].sigmas = {0.05};
-    systematics[0].pidx = {0};
-    systematics[1].name = "res"; systematics[1].type = pdfz::Systematic::RESOLUTION_SCALE;
-    systematics[1].observable_field_index = 0; systematics[1].truth_field_index = 2;
-    systematics[1].means = {0.0}; systematics[1].sigmas = {0.1}; systematics[1].pidx = {1};
-    for (int j = 0; j < 3; j++) {
-      const size_t n = 20000 + 777 * j;
-      std::vector<float> tab(n * 4);
-      for (size_t i = 0; i < n; i++) {
-        const float t = 0.2f + 0.25f * j + 0.3f * uni(s);
-        tab[i * 4 + 0] = t + 0.2f * (uni(s) - 0.5f);
-        tab[i * 4 + 1] = 2.2f * uni(s) - 0.1f;
-        tab[i * 4 + 2] = t;
-        tab[i * 4 + 3] = 0;
-      }
-      sxmc::Signal sig;
-      sig.name = "sig" + std::to_string(j);
-      sig.source = sxmc::Source("src" + std::to_string(j), j, 1.0f, 0.0f, false);
-      sig.nexpected = 100 + 50 * j;
-      sxmc::build_pdfz(sig, tab, 4, observables, systematics);
-      signals.push_back(sig);
-      tables.push_back(tab);
-      sources.push_back(sig.source);
-      for (int e = 0; e < 150; e++) {
-        const size_t i = lcg(s) % n;
-        data.push_back(tab[i * 4 + 0]);
-        data.push_back(tab[i * 4 + 1]);
-        data.push_back(0);
-      }
-    }
-  }
-  void TearDown() {
-    for (sxmc::Signal& s : signals) delete s.histogram;
-  }
-  std::vector<sxmc::Source> sources;
-  std::vector<sxmc::Signal> signals;
-  std::vector<sxmc::Systematic> systematics;
-  std::vector<sxmc::Observable> observables;
-  std::vector<float> data;
-  std::vector<std::vector<float>> tables;   // host copies of the sample tables (replicas on other GPUs)
-};
+// ------------------------------------------------------------------ NLL launch points + MCMC driver (small_fit.h)
 
 TEST_F(SmallFit, EfficiencyIsInDomainFraction) {
   const double eff = sxmc::get_efficiency(signals[0], systematics);
@@ -612,6 +557,108 @@ TEST_F(SmallFit, AutoWalkTakesTheLookaheadPassOnlyWhereThePlanStreamsFloatColumn
   sxmc::check(sxmc_group_lookahead_supported(g, &supported));
   sxmc::check(sxmc_group_destroy(g));
   EXPECT_EQ(b.LookaheadPasses() > 0, members == 0 && supported != 0);
+}
+
+static bool same_chain(const sxmc::Chain& a, const sxmc::Chain& b) {
+  return a.accepted == b.accepted && a.rows.size() == b.rows.size() &&
+         std::memcmp(a.rows.data(), b.rows.data(), a.rows.size() * sizeof(float)) == 0;
+}
+
+TEST_F(SmallFit, AWalkThatFailsLeavesTheNextOneUntouched) {
+  // a hook of the caller's throws once the last step has finished (nothing is in flight, nothing faults): the walk
+  // un-binds the evaluators from its arrays and releases its graph, its stream and -- the look-ahead form -- its shadow
+  // set on the way out, so the next walk over the same evaluators is the control walk bit for bit
+  auto settings = [](sxmc::MCMC& m, bool lookahead) {
+    m.graph_steps = 8;
+    m.lookahead = lookahead;
+  };
+  sxmc::MCMC control(sources, signals, systematics, observables, 7);
+  settings(control, false);
+  const sxmc::Chain c = control(data, 120, 0.2f, false, 50);
+  EXPECT_TRUE(c.accepted > 3 && c.nrows() > 0);
+  for (bool lookahead : {false, true}) {
+    sxmc::MCMC failing(sources, signals, systematics, observables, 7);
+    settings(failing, lookahead);
+    failing.on_steps_done = []() { throw std::runtime_error("the caller's hook failed"); };
+    ASSERT_THROW(failing(data, 120, 0.2f, false, 50), std::runtime_error);
+    if (lookahead) EXPECT_TRUE(failing.LookaheadPasses() > 0);
+    sxmc::MCMC again(sources, signals, systematics, observables, 7);
+    settings(again, false);
+    EXPECT_TRUE(same_chain(c, again(data, 120, 0.2f, false, 50)));
+  }
+}
+
+TEST_F(SmallFit, ALockstepChainThatFailsLeavesItsSet) {
+  // two chains of one set on two host threads; one's hook throws after its last step: it leaves the set on the way
+  // out, and its partner completes its walk.  A watchdog breaks the set if the threads have not finished in time, so
+  // that a chain left waiting fails this test instead of hanging it.
+  sxmc_stream_t strm = nullptr;
+  sxmc::check(sxmc_stream_create_nonblocking(&strm));
+  sxmc::SetupLock exclusive;
+  std::mutex mu;
+  std::condition_variable finished_cv;
+  int finished = 0;
+  bool threw[2] = {false, false}, watchdog_fired = false;
+  size_t nrows[2] = {0, 0};
+  std::string other[2];
+  {
+    sxmc::LockstepSet set(2, strm, &exclusive);
+    std::vector<std::thread> threads;
+    for (size_t t = 0; t < 2; t++) {
+      threads.emplace_back([&, t]() {
+        std::vector<sxmc::Signal> mine;
+        try {
+          {
+            std::lock_guard<sxmc::SetupLock> lock(exclusive);
+            sxmc::transfer_stream() = strm;
+            for (const sxmc::Signal& s : signals) mine.push_back(sxmc::share_pdfz(s));
+          }
+          std::unique_lock<sxmc::SetupLock> lock(exclusive);
+          std::unique_ptr<sxmc::MCMC> m(new sxmc::MCMC(sources, mine, systematics, observables, 7 + t, strm));
+          m->graph_steps = 8;
+          m->optimize = false;
+          m->exclusive = &exclusive;
+          m->lockstep = &set;
+          m->lockstep_index = t;
+          if (t == 1) m->on_steps_done = []() { throw std::runtime_error("the caller's hook failed"); };
+          lock.unlock();
+          try {
+            nrows[t] = (*m)(data, 120, 0.2f, false, 50).nrows();
+          } catch (const std::runtime_error&) {
+            threw[t] = true;
+          }
+          lock.lock();
+          m.reset();
+        } catch (const pdfz::Error& e) {
+          other[t] = e.msg;
+          set.abandon(e.msg);
+        } catch (const std::exception& e) {
+          other[t] = e.what();
+          set.abandon(e.what());
+        }
+        {
+          std::lock_guard<sxmc::SetupLock> lock(exclusive);
+          for (sxmc::Signal& s : mine) delete s.histogram;
+          sxmc::transfer_stream() = nullptr;
+        }
+        std::lock_guard<std::mutex> g(mu);
+        finished++;
+        finished_cv.notify_all();
+      });
+    }
+    {
+      std::unique_lock<std::mutex> g(mu);
+      watchdog_fired = !finished_cv.wait_for(g, std::chrono::seconds(60), [&] { return finished == 2; });
+    }
+    if (watchdog_fired) set.abandon("watchdog: a chain of the set was left waiting");
+    for (std::thread& th : threads) th.join();
+  }
+  sxmc::check(sxmc_stream_destroy(strm));
+  EXPECT_TRUE(!watchdog_fired);
+  EXPECT_EQ(other[0], std::string());
+  EXPECT_EQ(other[1], std::string());
+  EXPECT_TRUE(!threw[0] && threw[1]);
+  EXPECT_EQ((size_t)(120 - 48), nrows[0]);
 }
 
 TEST(LaneBarrier, RoundsOfUnequalSizeAndABrokenBarrier) {
