@@ -37,23 +37,12 @@
 #include <string>
 #include <vector>
 
+#include "chain.h"
 #include "fit_types.h"
 #include "nll_kernels.h"
 #include "walk_plan.h"
 
 namespace sxmc {
-
-/** The sampled likelihood space: one row per kept step = parameters..., likelihood (mcmc.cpp:100-114). */
-struct Chain {
-  std::vector<std::string> names;  //!< parameter names, then "likelihood"
-  std::vector<float> rows;         //!< row-major [nrows][names.size()]
-  size_t accepted = 0;             //!< accepted proposals over the whole walk
-  double setup_seconds = 0;        //!< of the walk that made it: entry to the first step (buffers, SetEvalPoints, first
-                                   //!< evaluation, launch-shape trials), host clock
-  double steps_seconds = 0;        //!< ... and the steps themselves, re-tunings, flushes and graph recording included
-  size_t nrows() const { return names.empty() ? 0 : rows.size() / names.size(); }
-  float at(size_t row, size_t col) const { return rows[row * names.size() + col]; }
-};
 
 /** The lock that serialises set-up, graph recording and tear-down of the chains that share a DEVICE (allocation,
  *  uploads through the legacy stream, launch-plan rebuilds and device-wide synchronisation are calls the runtime

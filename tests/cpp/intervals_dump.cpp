@@ -1,7 +1,7 @@
-// intervals_dump.cpp -- sxmc::contour_intervals / sxmc::projection_intervals (sxmc_amd/include/sxmc/ensemble.h: the
+// intervals_dump.cpp -- sxmc::contour_intervals / sxmc::projection_intervals (sxmc_amd/include/sxmc/intervals.h: the
 // C++ forms of Contour::get_interval, contour.cpp:30-69, and Projection::get_interval, projection.cpp:14-77) on a
 // chain read from a file, printed as JSON: tests/test_intervals.py compares them with the Python forms and with the
-// brute-force restatement in oracle/intervals.py on the same chain.  No device call.
+// brute-force restatement in oracle/intervals.py on the same chain.  No device call, no library: intervals.h alone.
 // Usage: intervals_dump <chain.f32> <ncolumns> <cl>      (row-major float32, last column = likelihood)
 //        intervals_dump <chain.f32> <ncolumns> <cl> --report name0,name1,...   the text of
 //            LikelihoodSpace::print_best_fit + print_correlations (likelihood.cpp:34-72) for that chain with those
@@ -9,8 +9,9 @@
 #include <cstdio>
 #include <fstream>
 #include <iostream>
+#include <stdexcept>
 
-#include "../../sxmc_amd/include/sxmc/ensemble.h"
+#include "../../sxmc_amd/include/sxmc/intervals.h"
 
 int main(int argc, char** argv) {
   if (argc != 4 && !(argc == 6 && std::string(argv[4]) == "--report")) {
@@ -63,8 +64,6 @@ int main(int argc, char** argv) {
     dump("projection", p);
     std::printf("}\n");
     return 0;
-  } catch (const pdfz::Error& e) {
-    std::fprintf(stderr, "intervals_dump: %s\n", e.msg.c_str());
   } catch (const std::exception& e) {
     std::fprintf(stderr, "intervals_dump: %s\n", e.what());
   }

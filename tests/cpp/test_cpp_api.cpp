@@ -661,44 +661,6 @@ TEST_F(SmallFit, ALockstepChainThatFailsLeavesItsSet) {
   EXPECT_EQ((size_t)(120 - 48), nrows[0]);
 }
 
-TEST(LaneBarrier, RoundsOfUnequalSizeAndABrokenBarrier) {
-  // the meeting point of ensemble_concurrent's lanes: every round's participants leave together, a last round with
-  // fewer lanes works, and a lane that fails releases everybody for good
-  sxmc::LaneBarrier meet;
-  const size_t lanes = 4, experiments = 10;     // rounds of 4, 4 and 2
-  std::atomic<int> inside{0}, worst{0};
-  std::vector<std::thread> threads;
-  for (size_t t = 0; t < lanes; t++) {
-    threads.emplace_back([&, t]() {
-      for (size_t i = t; i < experiments; i += lanes) {
-        const size_t round_lanes = std::min(lanes, experiments - (i - t));
-        meet.arrive_and_wait(round_lanes);      // "all set up"
-        const int now = ++inside;
-        int seen = worst.load();
-        while (now > seen && !worst.compare_exchange_weak(seen, now)) {
-        }
-        std::this_thread::sleep_for(std::chrono::milliseconds(2 + (int)t));
-        --inside;
-        meet.arrive_and_wait(round_lanes);      // "all stepped"
-      }
-    });
-  }
-  for (std::thread& th : threads) th.join();
-  EXPECT_TRUE(worst.load() >= 2 && worst.load() <= 4);
-  // a waiter is released by break_all, and nobody waits afterwards
-  std::atomic<bool> released{false};
-  std::thread waiter([&]() {
-    meet.arrive_and_wait(2);
-    released = true;
-  });
-  std::this_thread::sleep_for(std::chrono::milliseconds(20));
-  EXPECT_TRUE(!released.load());
-  meet.break_all();
-  waiter.join();
-  EXPECT_TRUE(released.load());
-  meet.arrive_and_wait(5);                       // returns at once
-}
-
 TEST(NllLaunch, ReferenceSpelling) {
   // the launch macro with the reference's argument order (mcmc.cpp:396-414)
   const size_t ne = 5, ns = 2, np = 2;
@@ -874,6 +836,35 @@ TEST_F(SmallFit, ConcurrentExperimentsMatchSequential) {
     EXPECT_TRUE(par[i].phases.walk_teardown >= 0 && par[i].phases.intervals >= 0);
   }
   EXPECT_TRUE(!sxmc::BlockPool::instance().active());
+}
+
+TEST_F(SmallFit, ConcurrentExperimentsWithoutLaunchTrialsMatchSequential) {
+  // ExperimentOptions::optimize = false reaches every chain a runner builds: no trial launches, and still the accepted
+  // counts and the interval bits of the one-at-a-time loop (which keeps its default, optimize = true)
+  const std::vector<unsigned> ks = {0u, 3u, 5u};
+  sxmc::ExperimentOptions opt;
+  opt.sync_interval = 100;
+  std::vector<sxmc::ExperimentResult> seq = sxmc::ensemble(ks, 11, sources, signals, systematics, observables, 200, 0.2f, opt);
+  opt.optimize = false;
+  std::vector<sxmc::ExperimentResult> par =
+      sxmc::ensemble_concurrent(ks, 11, sources, signals, systematics, observables, 200, 0.2f, 2, opt);
+  EXPECT_EQ(seq.size(), par.size());
+  auto bits = [](float v) {
+    uint32_t u;
+    std::memcpy(&u, &v, 4);
+    return u;
+  };
+  for (size_t i = 0; i < seq.size(); i++) {
+    EXPECT_EQ(seq[i].index, par[i].index);
+    EXPECT_EQ(seq[i].accepted, par[i].accepted);
+    EXPECT_EQ(seq[i].intervals.size(), par[i].intervals.size());
+    for (size_t p = 0; p < seq[i].intervals.size(); p++) {
+      EXPECT_EQ(bits(seq[i].intervals[p].lower), bits(par[i].intervals[p].lower));
+      EXPECT_EQ(bits(seq[i].intervals[p].upper), bits(par[i].intervals[p].upper));
+      EXPECT_EQ(bits(seq[i].intervals[p].point_estimate), bits(par[i].intervals[p].point_estimate));
+      EXPECT_EQ(bits(seq[i].intervals[p].coverage), bits(par[i].intervals[p].coverage));
+    }
+  }
 }
 
 TEST_F(SmallFit, LockstepExperimentsMatchSequential) {

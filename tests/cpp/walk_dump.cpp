@@ -1,6 +1,7 @@
 // walk_dump.cpp -- whole walks of sxmc::MCMC over the small fit (small_fit.h), pinned: one line per case with the
 // case's name, the chain's rows and accepted steps, a 64-bit FNV-1a hash of the bytes of Chain::rows and the first and
-// last row as float bits; for the ensemble cases, per experiment the accepted steps and every interval as float bits.
+// last row as float bits; for the ensemble cases, per experiment the accepted steps and every interval as float bits; for
+// the multi-GPU cases also a hash of the gathered block, the medians as float bits and how the devices ran.
 // Every chain walks with optimize = false where the walk is built here: the trial launches time the device, and a pinned
 // chain must not depend on timing.  Built by tests/cpp/Makefile, run by tests/test_gpu_walk_golden.py, which compares
 // the lines with tests/golden/walk_chains.json.  Without a GPU it says so and exits 0.
@@ -51,6 +52,17 @@ std::string describe(const std::vector<sxmc::ExperimentResult>& res) {
     }
   }
   return out;
+}
+
+std::string describe(const sxmc::MultiGpuEnsemble& mg) {
+  uint64_t h = 1469598103934665603ull;   // FNV-1a, 64 bit
+  const unsigned char* p = reinterpret_cast<const unsigned char*>(mg.gathered.data());
+  for (size_t i = 0; i < mg.gathered.size() * sizeof(float); i++) h = (h ^ p[i]) * 1099511628211ull;
+  char buf[48];
+  std::snprintf(buf, sizeof buf, " gathered fnv1a %016llx", (unsigned long long)h);
+  std::string out = describe(mg.results) + buf + " median_upper";
+  for (float m : mg.median_upper) out += " " + bits(m);
+  return out + " mode " + mg.device_mode;
 }
 
 void line(const std::string& name, const std::string& text) { std::printf("%s\t%s\n", name.c_str(), text.c_str()); }
@@ -111,6 +123,35 @@ int main() {
                                                                   fit.observables, 120, 0.2f, 2, 0.9f, 100, 8));
       line("ensemble_lockstep, 2 chains in 1 set, graph_steps 8", lock + (lock == seq ? " =ensemble 1" : " =ensemble 0"));
       line("ensemble_concurrent, 2 lanes, graph_steps 8", conc + (conc == seq ? " =ensemble 1" : " =ensemble 0"));
+      const std::string pseq = describe(sxmc::ensemble(ks, 31, fit.sources, fit.signals, fit.systematics, fit.observables,
+                                                       120, 0.2f, 0.9f, 100, 0, sxmc::ERROR_PROJECTION));
+      const std::string pconc = describe(sxmc::ensemble_concurrent(ks, 31, fit.sources, fit.signals, fit.systematics,
+                                                                   fit.observables, 120, 0.2f, 2, 0.9f, 100, 8, -1, nullptr,
+                                                                   sxmc::ERROR_PROJECTION));
+      line("ensemble_concurrent, projection intervals, 2 lanes, graph_steps 8",
+           pconc + (pconc == pseq ? " =ensemble 1" : " =ensemble 0"));
+    }
+    {
+      // two logical ranks on card 0, the host standing in for the all-gather: rank 0 runs experiments 0, 2, 4 and rank 1
+      // runs 1, 3
+      const std::string seq = describe(sxmc::ensemble({0u, 1u, 2u, 3u, 4u}, 31, fit.sources, fit.signals, fit.systematics,
+                                                      fit.observables, 120, 0.2f, 0.9f, 100));
+      std::vector<const std::vector<float>*> tabs;
+      for (const std::vector<float>& t : fit.tables) tabs.push_back(&t);
+      auto multi = [&](const std::string& name, unsigned lockstep_chains) {
+        sxmc::MultiGpuOptions opt;
+        opt.sync_interval = 100;
+        opt.graph_steps = 8;
+        opt.lockstep_chains = lockstep_chains;
+        opt.lockstep_sets = 1;
+        opt.nconcurrent = 2;
+        opt.exchange = sxmc::MultiGpuOptions::HOST_STAGING;
+        const sxmc::MultiGpuEnsemble mg = sxmc::ensemble_multi_gpu({0, 0}, 5, 31, fit.sources, fit.signals, tabs, 4,
+                                                                   fit.systematics, fit.observables, 120, 0.2f, opt);
+        line(name, describe(mg) + (describe(mg.results) == seq ? " =ensemble 1" : " =ensemble 0"));
+      };
+      multi("ensemble_multi_gpu, host staging, 2 ranks on device 0, lockstep 2x1", 2);
+      multi("ensemble_multi_gpu, host staging, 2 ranks on device 0, concurrent 2", 0);
     }
   } catch (const pdfz::Error& e) {
     std::fprintf(stderr, "walk_dump: %s\n", e.msg.c_str());

@@ -1,7 +1,7 @@
 """Whole walks of the C++ driver (sxmc::MCMC, sxmc_amd/include/sxmc/mcmc.h), pinned: tests/cpp/walk_dump.cpp walks the
 small fit of the C++ tests in every form -- sequential, graph-replayed, look-ahead, not consuming, the reference's
-launches, with the lookup table, debug mode from an empty chain, on a caller's stream, in lockstep sets and in
-concurrent lanes -- and each case's line (rows, accepted steps, a hash of the rows, first and last row as float bits;
+launches, with the lookup table, debug mode from an empty chain, on a caller's stream, in lockstep sets, in
+concurrent lanes and over two logical ranks of the multi-GPU runner -- and each case's line (rows, accepted steps, a hash of the rows, first and last row as float bits;
 intervals per experiment) equals tests/golden/walk_chains.json.
 
 The other walk tests compare the forms with each other, so a change that moved all of them together would pass them;
@@ -35,6 +35,9 @@ CASES = [
     "caller's non-blocking stream, graph_steps 8",
     "ensemble_lockstep, 2 chains in 1 set, graph_steps 8",
     "ensemble_concurrent, 2 lanes, graph_steps 8",
+    "ensemble_concurrent, projection intervals, 2 lanes, graph_steps 8",
+    "ensemble_multi_gpu, host staging, 2 ranks on device 0, lockstep 2x1",
+    "ensemble_multi_gpu, host staging, 2 ranks on device 0, concurrent 2",
 ]
 
 

@@ -1,9 +1,11 @@
 """Interval extraction three ways on the SAME chain: the Python form (sxmc_amd/ensemble.py),
-the C++ form (sxmc_amd/include/sxmc/ensemble.h through tests/cpp/intervals_dump) and the brute-force restatement of
+the C++ form (sxmc_amd/include/sxmc/intervals.h through tests/cpp/intervals_dump) and the brute-force restatement of
 contour.cpp:30-69 / likelihood.cpp:90-102 / projection.cpp:14-77 in oracle/intervals.py -- on synthetic chains here
 (CPU) and on a chain walked on the GPU (-m gpu), the printed-offset regime |lmin| ~ 3e5 of BASELINE config 3 included.
 Contour intervals must agree bit for bit (they are minima and maxima of chain values once the same rows are
 selected); projection limits and coverages exactly, the fitted mean to 1e-6 (three different minimisers of one chi2).
+intervals.h needs no device and no library, so the CPU cases run a second time through intervals_dump_asan, the same
+program under AddressSanitizer + UndefinedBehaviorSanitizer.
 """
 import json
 import os
@@ -16,26 +18,35 @@ from oracle import intervals as ref
 from sxmc_amd import ensemble
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-DUMP = os.path.join(ROOT, "tests", "cpp", "intervals_dump")
+SANITIZED = dict(os.environ, ASAN_OPTIONS="detect_leaks=1:abort_on_error=0",
+                 UBSAN_OPTIONS="halt_on_error=1:print_stacktrace=1")
 
 
-def cpp_intervals(chain, cl, tmp_path):
-    subprocess.check_call(["make", "-s", "-C", os.path.join(ROOT, "tests", "cpp"), "intervals_dump"])
+def run_dump(exe, args):
+    """tests/cpp/<exe> (intervals_dump or intervals_dump_asan), built if need be: its standard output."""
+    subprocess.check_call(["make", "-s", "-C", os.path.join(ROOT, "tests", "cpp"), exe])
+    r = subprocess.run([os.path.join(ROOT, "tests", "cpp", exe)] + args, capture_output=True, text=True, timeout=120,
+                       env=SANITIZED)
+    assert r.returncode == 0, r.stderr
+    assert "runtime error" not in r.stderr and "AddressSanitizer" not in r.stderr, r.stderr[-3000:]
+    return r.stdout
+
+
+def cpp_intervals(chain, cl, tmp_path, exe="intervals_dump"):
     path = os.path.join(str(tmp_path), "chain.f32")
     np.ascontiguousarray(chain, np.float32).tofile(path)
-    r = subprocess.run([DUMP, path, str(chain.shape[1]), repr(float(cl))], capture_output=True, text=True, timeout=120)
-    assert r.returncode == 0, r.stderr
+    out = run_dump(exe, [path, str(chain.shape[1]), repr(float(cl))])
     try:
-        return json.loads(r.stdout)
+        return json.loads(out)
     except ValueError:
-        raise AssertionError("intervals_dump printed something that is not JSON: " + r.stdout[:3000])
+        raise AssertionError("intervals_dump printed something that is not JSON: " + out[:3000])
 
 
-def compare_three_ways(chain, cl, tmp_path):
+def compare_three_ways(chain, cl, tmp_path, exe="intervals_dump"):
     chain = np.ascontiguousarray(chain, np.float32)
     P = chain.shape[1] - 1
     cl32 = float(np.float32(cl))                         # `float cl` in the reference (error_estimator.h)
-    cpp = cpp_intervals(chain, cl32, tmp_path)
+    cpp = cpp_intervals(chain, cl32, tmp_path, exe)
     py = ensemble.contour_intervals(chain, cl32)
     try:
         want = ref.contour_intervals(chain, cl32)
@@ -84,11 +95,18 @@ def test_python_cpp_and_restatement_agree_on_synthetic_chains(tmp_path, offset, 
     compare_three_ways(chain, cl, tmp_path)
 
 
-def test_printed_offset_changes_the_contour_at_config3_magnitudes(tmp_path):
+@pytest.mark.parametrize("offset", [12.5, -348086.3, 3.2e5, -7.123456e6])
+@pytest.mark.parametrize("cl", [0.9, 0.683])
+def test_synthetic_chains_through_the_sanitizer_build(tmp_path, offset, cl):
+    chain = synthetic_chain(int(abs(offset)) % 1000 + int(cl * 100), 4000, offset)
+    compare_three_ways(chain, cl, tmp_path, "intervals_dump_asan")
+
+
+def test_printed_offset_changes_the_contour_at_config3_magnitudes(tmp_path, exe="intervals_dump"):
     """With |lmin| = 348 086.3 the text "likelihood+348086<1.35277" applies an offset that is off by 0.3: the contour
     the reference selects is NOT the exact Delta-NLL contour, and all three implementations follow the reference."""
     chain = synthetic_chain(7, 4000, -348086.3)
-    got = compare_three_ways(chain, 0.9, tmp_path)
+    got = compare_three_ways(chain, 0.9, tmp_path, exe)
     like = chain[:, -1].astype(np.float64)
     delta = 0.5 * ref.chisquare_quantile_1dof(np.float32(0.9))
     exact = chain[like - like.min() < delta]
@@ -99,6 +117,10 @@ def test_printed_offset_changes_the_contour_at_config3_magnitudes(tmp_path):
     w = ref.projection_interval(col, float(np.float32(0.9)))
     a = ensemble.projection_interval(col, float(np.float32(0.9)))
     assert w[4] is True and a[4] is True and a[1:4] == w[1:4]
+
+
+def test_printed_offset_through_the_sanitizer_build(tmp_path):
+    test_printed_offset_changes_the_contour_at_config3_magnitudes(tmp_path, "intervals_dump_asan")
 
 
 @pytest.mark.gpu
@@ -124,7 +146,7 @@ def test_intervals_of_a_gpu_chain_three_ways(tmp_path):
     m.group.close()
 
 
-def test_best_fit_and_correlation_report(tmp_path):
+def test_best_fit_and_correlation_report(tmp_path, exe="intervals_dump"):
     """LikelihoodSpace::print_best_fit / print_correlations (likelihood.cpp:34-72, what sxmc.cpp:100-101 prints per
     experiment): the C++ text equals the Python text character for character -- parameters of the best fit in NAME
     order, the matrix' lower triangle zero as the reference leaves it, and the second best-fit block's NLL at the
@@ -135,18 +157,15 @@ def test_best_fit_and_correlation_report(tmp_path):
     chain[:, 1] += np.float32(0.7) * chain[:, 0]
     chain[:, 2] = np.float32(3.0) + np.float32(0.01) * chain[:, 2] - np.float32(0.005) * chain[:, 0]
     chain[:, -1] = np.float32(-2.5e5) + np.float32(0.5) * (chain[:, :-1] ** 2).sum(axis=1)
-    subprocess.check_call(["make", "-s", "-C", os.path.join(ROOT, "tests", "cpp"), "intervals_dump"])
     path = os.path.join(str(tmp_path), "chain.f32")
     chain.tofile(path)
     cl = float(np.float32(0.9))
-    r = subprocess.run([DUMP, path, str(chain.shape[1]), repr(cl), "--report", ",".join(names)], capture_output=True,
-                       text=True, timeout=120)
-    assert r.returncode == 0, r.stderr
+    out = run_dump(exe, [path, str(chain.shape[1]), repr(cl), "--report", ",".join(names)])
     iv = ensemble.contour_intervals(chain, cl)
     m = ensemble.correlation_matrix(chain)
     want = ensemble.format_best_fit(names, iv, chain[:, -1].min(), cl) + ensemble.format_correlations(names, m) + \
         ensemble.format_best_fit(names, iv, chain[:, -1].min(), cl, precision=3)
-    assert r.stdout == want, "\n" + r.stdout + "\n---\n" + want
+    assert out == want, "\n" + out + "\n---\n" + want
     lines = want.splitlines()
     assert [l.split(":")[0].strip() for l in lines[1:5]] == sorted(names)          # std::map order
     assert lines[5].startswith(" NLL: -2499") and lines[-1] == " NLL: -2.5e+05"
@@ -156,3 +175,7 @@ def test_best_fit_and_correlation_report(tmp_path):
     assert abs(m[0, 1] - np.corrcoef(chain[:, 0], chain[:, 1])[0, 1]) < 1e-4
     k = names.index("alpha")
     assert lines[1] == " alpha: " + ref.interval_text(iv[k, 0], iv[k, 1], iv[k, 2])
+
+
+def test_best_fit_and_correlation_report_through_the_sanitizer_build(tmp_path):
+    test_best_fit_and_correlation_report(tmp_path, "intervals_dump_asan")
