@@ -655,7 +655,8 @@ int sxmc_group_step_end_timeouts(sxmc_group_t g, sxmc_stream_t s, unsigned* time
 /* Compiles (does not load or run) the fill kernel the library would specialise at run time for a program of
  * systematics -- see sxmc_group_set_runtime_kernels.  Needs no GPU: a build check, and the test hook of the
  * run-time compilation.  ops[i] = type | obs_slot << 4 | extra_slot << 8 | npars << 12 (npars 0 = one coefficient);
- * pre_width 0 or 3 (bucketed table); sparse_runs != 0: the kernel for histograms beyond LDS over a bucketed
+ * pre_width: the table's form -- 0 rows, 1 / 2 a pre-binned column of that many bytes per sample, 3 bucketed, 5 bucketed
+ * with an ordered observable, 6 with a boxed one; sparse_runs != 0: the kernel for histograms beyond LDS over a bucketed
  * table walked in runs.  *code_bytes (optional): size of the gfx950 code object. */
 int sxmc_rtc_compile_check(int nobs, int nslot, int lds_hist, int pre_width, int sparse_runs, const unsigned* ops,
                            int nops, size_t* code_bytes);

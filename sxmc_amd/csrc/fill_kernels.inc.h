@@ -327,7 +327,7 @@ __device__ __forceinline__ void sparse_count(const SxSignalDesc& d, gptr<unsigne
 // sees a lower-dimensional problem -- every observable it is given is binned here -- plus ONE word per
 // 256-sample granule: the granule's constant contribution to the flat bin index.  A wave reads exactly one
 // granule per step (units are 4 samples, a wave covers 64 consecutive units), so that word is wave-uniform.
-constexpr int kPreGranule = 3;
+constexpr int kPreGranule = kFormBucketed;   // (the names of sxmc_device_types.h, as the kernels spell them)
 template <int PREW> struct PreVec { typedef unsigned type; };
 template <> struct PreVec<2> { typedef unsigned type __attribute__((ext_vector_type(2))); };
 template <> struct PreVec<4> { typedef unsigned type __attribute__((ext_vector_type(4))); };
@@ -671,8 +671,8 @@ __device__ __forceinline__ void fill_body(const SxSignalDesc* __restrict__ descs
 // the wave's next 64 granules in one go (one 8-byte read per granule), each step then takes its own with
 // v_readlane: scalar from there on.  NCHAIN > 1: lockstep chains (see fill_multi_body), each with its own codes.
 // The kernel itself (fill_ordered_body) follows fill_multi_body below; fill_sparse_body has an ORDERED variant.
-constexpr int kPreOrdered = 5;
-constexpr int kPreBoxed = 6;     // bucketed table with a boxed observable (fill_boxed_body, further down)
+constexpr int kPreOrdered = kFormOrdered;
+constexpr int kPreBoxed = kFormBoxed;   // bucketed table with a boxed observable (fill_boxed_body, further down)
 constexpr unsigned kOrdMixed = 0xFFFFFFFEu, kOrdSkip = 0xFFFFFFFFu;
 typedef float vfloat2 __attribute__((ext_vector_type(2)));
 

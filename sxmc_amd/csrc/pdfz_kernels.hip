@@ -19,6 +19,7 @@
 #include <hip/hip_runtime.h>
 #include <hip/hip_ext.h>
 
+#include <algorithm>
 #include <cstring>
 #include <vector>
 
@@ -977,213 +978,153 @@ __global__ __launch_bounds__(256) void untranspose_obs_kernel(const float* __res
   }
 }
 
-// A fill launch; with the launch shape's two profiling events set, through hipExtLaunchKernelGGL, which stamps them
-// with the dispatch's own begin and end (what rocprofv3 --kernel-trace reports as the kernel's duration).
+// A fill launch.  Raises the kernel's dynamic-LDS limit where the launch needs more than the default 48 KiB (on every
+// such launch: the attribute is per device).  `fused`: the whole step in this launch -- the step end's workgroups
+// (finisher + workers) are appended to the grid.  Otherwise, with the launch shape's two profiling events set, through
+// hipExtLaunchKernelGGL, which stamps them with the dispatch's own begin and end (rocprofv3 --kernel-trace's duration).
 template <typename K, typename... A>
-void launch_fill(const SxLaunchShape& sh, K k, dim3 grid, dim3 block, size_t lds, hipStream_t s, A... args) {
-  if (sh.ev_start && sh.ev_stop) {
+hipError_t launch_fill(const SxLaunchShape& sh, K k, size_t lds, bool fused, hipStream_t s, A... args) {
+  if (lds > 48 * 1024) {
+    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(k), hipFuncAttributeMaxDynamicSharedMemorySize,
+                                       (int)lds);
+    if (e != hipSuccess) return e;
+  }
+  const dim3 grid(fused ? sh.grid + sh.tail_blocks : sh.grid), block(sh.threads);
+  if (!fused && sh.ev_start && sh.ev_stop) {
     hipExtLaunchKernelGGL(k, grid, block, (std::uint32_t)lds, s, (hipEvent_t)sh.ev_start, (hipEvent_t)sh.ev_stop, 0u,
                           args...);
   } else {
     hipLaunchKernelGGL(k, grid, block, lds, s, args...);
   }
+  return hipGetLastError();
 }
 
-// Which built-in fills also exist fused with the step end (fill_step_kernel / fill_ordered_step_kernel): the ordered
-// programs, and the LDS-histogram kernels of the EMPTY program over a pre-binned column (BASELINE config 2).
-template <bool LDS_HIST, typename PROG, int PREW>
-constexpr bool has_step_form() {
-  return LDS_HIST && PROG::n == 0 && (PREW == 1 || PREW == 2);
-}
+using FillLauncher = hipError_t (*)(const SxLaunchShape&, const SxSignalDesc*, const SxSegment*, const unsigned*, hipStream_t);
 
-template <int NOBS, int NSLOT, bool LDS_HIST, typename PROG, int PREW = 0>
+// Rows, a pre-binned column or a bucketed table: fill_kernel.  Fused with the step end there are the ordered programs
+// (below) and, here, the LDS-histogram kernels of the EMPTY program over a pre-binned column (BASELINE config 2).
+template <int NOBS, int NSLOT, bool LDS_HIST, typename PROG, int FORM = kFormRows>
 hipError_t launch_fill_k(const SxLaunchShape& sh, const SxSignalDesc* descs, const SxSegment* segs,
                          const unsigned* blk_off, hipStream_t s) {
-  // LDS: 4 header words + hist_words + 64 trash words
-  // LDS-histogram launches: hist_words bins + 64 trash words; others: room for the sparse coarse filter
-  const unsigned hist_words = (unsigned)(sh.lds_bytes / 4 - 4 - (LDS_HIST ? 64 : 0));
-  if constexpr (has_step_form<LDS_HIST, PROG, PREW>()) {
-    if (sh.tail) {   // the whole step in this launch: the fill's workgroups + finisher + workers
-      auto ks = fill_step_kernel<NOBS, NSLOT, PROG, PREW>;
-      if (sh.lds_bytes > 48 * 1024) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(ks),
-                                           hipFuncAttributeMaxDynamicSharedMemorySize, (int)sh.lds_bytes);
-        if (e != hipSuccess) return e;
-      }
-      hipLaunchKernelGGL(ks, dim3(sh.grid + sh.tail_blocks), dim3(sh.threads), sh.lds_bytes, s, descs, segs, blk_off,
-                         hist_words, (unsigned)sh.debug_mode, (unsigned)sh.grid, *static_cast<const SxTailArgs*>(sh.tail));
-      return hipGetLastError();
+  const unsigned w = sx_fill_w(sh), dbg = (unsigned)sh.debug_mode;
+  if constexpr (LDS_HIST && PROG::n == 0 && sx_form_prebinned(FORM)) {
+    if (sh.tail) {
+      return launch_fill(sh, fill_step_kernel<NOBS, NSLOT, PROG, FORM>, sh.lds_bytes, true, s, descs, segs, blk_off, w,
+                         dbg, (unsigned)sh.grid, *static_cast<const SxTailArgs*>(sh.tail));
     }
   }
   if (sh.tail) return hipErrorInvalidValue;   // (the host asks sx_fill_has_step_form first)
-  auto k = fill_kernel<NOBS, NSLOT, LDS_HIST, PROG, PREW>;
-  if (sh.lds_bytes > 48 * 1024) {
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(k),
-                                       hipFuncAttributeMaxDynamicSharedMemorySize, (int)sh.lds_bytes);
-    if (e != hipSuccess) return e;
-  }
-  launch_fill(sh, k, dim3(sh.grid), dim3(sh.threads), sh.lds_bytes, s, descs, segs, blk_off, hist_words,
-              (unsigned)sh.debug_mode);
-  return hipGetLastError();
+  return launch_fill(sh, fill_kernel<NOBS, NSLOT, LDS_HIST, PROG, FORM>, sh.lds_bytes, false, s, descs, segs, blk_off, w,
+                     dbg);
 }
 
-typedef hipError_t (*FillLauncher)(const SxLaunchShape&, const SxSignalDesc*, const SxSegment*, const unsigned*,
-                                   hipStream_t);
-
+// entries per wave (keys + counts) of the per-wave LDS tables of the sparse counting over runs
+unsigned sparse_smax(const SxLaunchShape& sh) { return (unsigned)(sh.sparse_lds_bytes / 4 / (sh.threads / 64u) / 2); }
 template <int NOBS, int NSLOT, typename PROG>
 hipError_t launch_fill_sparse_k(const SxLaunchShape& sh, const SxSignalDesc* descs, const SxSegment* segs,
                                 const unsigned* blk_off, hipStream_t s) {
-  auto k = fill_sparse_kernel<NOBS, NSLOT, PROG>;
-  if (sh.sparse_lds_bytes > 48 * 1024) {
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(k), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                       (int)sh.sparse_lds_bytes);
-    if (e != hipSuccess) return e;
-  }
-  const unsigned nwaves = (unsigned)sh.threads / 64u;
-  const unsigned smax = (unsigned)(sh.sparse_lds_bytes / 4 / nwaves / 2);   // entries per wave (keys + counts)
-  launch_fill(sh, k, dim3(sh.grid), dim3(sh.threads), sh.sparse_lds_bytes, s, descs, segs, blk_off, smax,
-              (unsigned)sh.debug_mode);
-  return hipGetLastError();
+  return launch_fill(sh, fill_sparse_kernel<NOBS, NSLOT, PROG>, sh.sparse_lds_bytes, false, s, descs, segs, blk_off,
+                     sparse_smax(sh), (unsigned)sh.debug_mode);
 }
 
-// Static programs (LDS-histogram launches only).  Slots: observables 0..nobs-1, then the
-// referenced extra fields in ascending order.
-struct StaticEntry {
+// a bucketed table with an ordered observable (fill_ordered_kernel, also fused with the step end) or a boxed one
+template <int NOBS, int NSLOT, typename PROG, int FORM>
+hipError_t launch_fill_ordered_k(const SxLaunchShape& sh, const SxSignalDesc* descs, const SxSegment* segs,
+                                 const unsigned* blk_off, hipStream_t s) {
+  const unsigned w = sx_fill_w(sh), dbg = (unsigned)sh.debug_mode;
+  if constexpr (FORM == kFormBoxed) {
+    return launch_fill(sh, fill_boxed_kernel<NOBS, NSLOT, PROG>, sh.lds_bytes, false, s, descs, segs, blk_off, w, dbg);
+  } else if (sh.tail) {
+    return launch_fill(sh, fill_ordered_step_kernel<NOBS, NSLOT, PROG>, sh.lds_bytes, true, s, descs, segs, blk_off, w, dbg,
+                       (unsigned)sh.grid, *static_cast<const SxTailArgs*>(sh.tail));
+  } else {
+    return launch_fill(sh, fill_ordered_kernel<NOBS, NSLOT, PROG>, sh.lds_bytes, false, s, descs, segs, blk_off, w, dbg);
+  }
+}
+
+// The programs built in.  A program is its words, one per systematic, over SLOTS: observables 0 .. nobs - 1 binned per
+// sample, then the fields only read (ascending), then -- ordered and boxed entries -- that observable.  Anything else:
+// hiprtc.  An entry of form kFormRows serves the table as it is, with a pre-binned column and bucketed, as far as it has
+// the kernels (`HAS`); an ordered or boxed entry has the one kernel, histogram in LDS.
+struct FillEntry {
+  int form;                 // kFormRows, kFormOrdered or kFormBoxed
   int nobs, nslot, nops;
   unsigned ops[4];
-  FillLauncher fn;           // LDS histogram, all observables binned in the kernel
-  FillLauncher fn_pre[2];    // LDS histogram, observables no systematic writes pre-binned, 1 / 2 bytes per sample
-                             // (with an LDS-sized histogram the partial index of the table's programs is < 65535)
-  FillLauncher fn_g;         // histogram beyond LDS capacity (dense global atomics or sparse event-bin counters)
-  FillLauncher fn_g_pre[2];
-  FillLauncher fn_gran[2];   // bucketed table (every observable given is binned, + one offset per granule): LDS / beyond LDS
-  FillLauncher fn_sruns;     // bucketed table walked in runs, event bins counted in per-wave LDS tables
+  // [histogram in LDS / beyond it (dense global atomics or sparse event-bin counters) / bucketed table walked in runs, event
+  // bins counted in per-wave LDS tables][form: rows, pre-binned 1 / 2 bytes per sample, bucketed]; ordered and boxed: [0][0]
+  FillLauncher fn[3][4];
 };
+static_assert(kFormRows == 0 && kFormPre1 == 1 && kFormPre2 == 2 && kFormBucketed == 3, "fn is indexed by these forms");
+// kPre: LDS histogram, observables no systematic writes pre-binned; kBeyond: histogram beyond LDS, rows and pre-binned;
+// kGran: bucketed table (every observable given is binned, + one offset per granule), histogram in LDS, beyond LDS, runs
+enum : unsigned { kPre = 1, kBeyond = 2, kGran = 4 };
+template <int FORM, unsigned HAS, int NO, int NS, unsigned... OPS>
+constexpr FillEntry fill_entry() {
+  using P = StaticProg<OPS...>;
+  FillEntry e = {FORM, NO, NS, (int)sizeof...(OPS), {OPS...}, {}};
+  if constexpr (FORM != kFormRows) {
+    e.fn[0][0] = launch_fill_ordered_k<NO, NS, P, FORM>;
+  } else {
+    e.fn[0][kFormRows] = launch_fill_k<NO, NS, true, P>;
+    if constexpr (HAS & kPre) {
+      e.fn[0][kFormPre1] = launch_fill_k<NO, NS, true, P, kFormPre1>;
+      e.fn[0][kFormPre2] = launch_fill_k<NO, NS, true, P, kFormPre2>;
+    }
+    if constexpr (HAS & kBeyond) {
+      e.fn[1][kFormRows] = launch_fill_k<NO, NS, false, P, kFormRows>;
+      e.fn[1][kFormPre1] = launch_fill_k<NO, NS, false, P, kFormPre1>;
+      e.fn[1][kFormPre2] = launch_fill_k<NO, NS, false, P, kFormPre2>;
+    }
+    if constexpr (HAS & kGran) {
+      e.fn[0][kFormBucketed] = launch_fill_k<NO, NS, true, P, kFormBucketed>;
+      e.fn[1][kFormBucketed] = launch_fill_k<NO, NS, false, P, kFormBucketed>;
+      e.fn[2][kFormBucketed] = launch_fill_sparse_k<NO, NS, P>;
+    }
+  }
+  return e;
+}
 #define SX_SHIFT(o) sx_op(SXMC_SYST_SHIFT, o)
 #define SX_SCALE(o) sx_op(SXMC_SYST_SCALE, o)
 #define SX_CTSC(o) sx_op(SXMC_SYST_CTSCALE, o)
 #define SX_RES(o, e) sx_op(SXMC_SYST_RESOLUTION_SCALE, o, e)
-#define SX_NOPRE {nullptr, nullptr}
-#define SX_NOG nullptr, {nullptr, nullptr}
-#define SX_PRE(NO, NS, ...) \
-  {launch_fill_k<NO, NS, true, StaticProg<__VA_ARGS__>, 1>, launch_fill_k<NO, NS, true, StaticProg<__VA_ARGS__>, 2>}
-#define SX_G(NO, NS, ...) \
-  launch_fill_k<NO, NS, false, StaticProg<__VA_ARGS__>, 0>, \
-  {launch_fill_k<NO, NS, false, StaticProg<__VA_ARGS__>, 1>, launch_fill_k<NO, NS, false, StaticProg<__VA_ARGS__>, 2>}
-#define SX_NOGRAN {nullptr, nullptr}, nullptr
-#define SX_GRAN(NO, NS, ...) \
-  {launch_fill_k<NO, NS, true, StaticProg<__VA_ARGS__>, kPreGranule>, launch_fill_k<NO, NS, false, StaticProg<__VA_ARGS__>, kPreGranule>}, \
-  launch_fill_sparse_k<NO, NS, StaticProg<__VA_ARGS__>>
-#define SX_P1(NO, NS, PRE, G, GR, A) {NO, NS, 1, {A, 0, 0, 0}, launch_fill_k<NO, NS, true, StaticProg<A>>, PRE, G, GR}
-#define SX_P2(NO, NS, PRE, G, GR, A, B) {NO, NS, 2, {A, B, 0, 0}, launch_fill_k<NO, NS, true, StaticProg<A, B>>, PRE, G, GR}
-#define SX_P3(NO, NS, PRE, G, GR, A, B, C) {NO, NS, 3, {A, B, C, 0}, launch_fill_k<NO, NS, true, StaticProg<A, B, C>>, PRE, G, GR}
-// (no systematics: EVERY observable is untouched, so the pre-binned column carries the whole flat index and no float
-// column is streamed at all -- 1 or 2 bytes per sample instead of 4 per observable)
-#define SX_P0(NO) \
-  {NO, NO, 0, {0, 0, 0, 0}, launch_fill_k<NO, NO, true, StaticProg<>>, \
-   {launch_fill_k<NO, NO, true, StaticProg<>, 1>, launch_fill_k<NO, NO, true, StaticProg<>, 2>}, SX_NOG, SX_NOGRAN}
-const StaticEntry kStaticPrograms[] = {
-    // no systematics at all (BASELINE config 2)
-    SX_P0(1), SX_P0(2), SX_P0(3),
+#define SX_PROG(FORM, HAS, NO, NS, ...) fill_entry<FORM, HAS, NO, NS, ##__VA_ARGS__>()
+const FillEntry kPrograms[] = {
+    // no systematics at all (BASELINE config 2): EVERY observable is untouched, so the pre-binned column carries the
+    // whole flat index and no float column is streamed at all -- 1 or 2 bytes per sample instead of 4 per observable
+    SX_PROG(kFormRows, kPre, 1, 1), SX_PROG(kFormRows, kPre, 2, 2), SX_PROG(kFormRows, kPre, 3, 3),
     // 1-D (bench_sxmc pdfz: one shift; config/example.json: scale + resolution_scale).  These are also what a
     // bucketed higher-dimensional table with ONE observable written by systematics reduces to.
-    SX_P1(1, 1, SX_NOPRE, SX_NOG, SX_GRAN(1, 1, SX_SHIFT(0)), SX_SHIFT(0)),
-    SX_P1(1, 1, SX_NOPRE, SX_NOG, SX_GRAN(1, 1, SX_SCALE(0)), SX_SCALE(0)),
-    SX_P1(1, 1, SX_NOPRE, SX_NOG, SX_GRAN(1, 1, SX_CTSC(0)), SX_CTSC(0)),
-    SX_P2(1, 1, SX_NOPRE, SX_NOG, SX_GRAN(1, 1, SX_SHIFT(0), SX_SCALE(0)), SX_SHIFT(0), SX_SCALE(0)),
-    SX_P1(1, 2, SX_NOPRE, SX_NOG, SX_GRAN(1, 2, SX_RES(0, 1)), SX_RES(0, 1)),
-    SX_P2(1, 2, SX_NOPRE, SX_NOG, SX_GRAN(1, 2, SX_SCALE(0), SX_RES(0, 1)), SX_SCALE(0), SX_RES(0, 1)),
-    SX_P3(1, 2, SX_NOPRE, SX_NOG, SX_GRAN(1, 2, SX_SHIFT(0), SX_SCALE(0), SX_RES(0, 1)), SX_SHIFT(0), SX_SCALE(0),
-          SX_RES(0, 1)),
+    SX_PROG(kFormRows, kGran, 1, 1, SX_SHIFT(0)), SX_PROG(kFormRows, kGran, 1, 1, SX_SCALE(0)),
+    SX_PROG(kFormRows, kGran, 1, 1, SX_CTSC(0)), SX_PROG(kFormRows, kGran, 1, 1, SX_SHIFT(0), SX_SCALE(0)),
+    SX_PROG(kFormRows, kGran, 1, 2, SX_RES(0, 1)), SX_PROG(kFormRows, kGran, 1, 2, SX_SCALE(0), SX_RES(0, 1)),
+    SX_PROG(kFormRows, kGran, 1, 2, SX_SHIFT(0), SX_SCALE(0), SX_RES(0, 1)),
     // 2-D
-    SX_P1(2, 2, SX_PRE(2, 2, SX_SHIFT(0)), SX_NOG, SX_NOGRAN, SX_SHIFT(0)),
-    SX_P1(2, 2, SX_PRE(2, 2, SX_SCALE(0)), SX_NOG, SX_NOGRAN, SX_SCALE(0)),
-    SX_P1(2, 2, SX_PRE(2, 2, SX_SHIFT(1)), SX_NOG, SX_NOGRAN, SX_SHIFT(1)),
-    SX_P2(2, 3, SX_PRE(2, 3, SX_SCALE(0), SX_RES(0, 2)), SX_NOG, SX_NOGRAN, SX_SCALE(0), SX_RES(0, 2)),
+    SX_PROG(kFormRows, kPre, 2, 2, SX_SHIFT(0)), SX_PROG(kFormRows, kPre, 2, 2, SX_SCALE(0)),
+    SX_PROG(kFormRows, kPre, 2, 2, SX_SHIFT(1)), SX_PROG(kFormRows, kPre, 2, 3, SX_SCALE(0), SX_RES(0, 2)),
     // (also what BASELINE configs 3 and 5 reduce to once bucketed: e and r are written, the rest is not)
-    SX_P3(2, 3, SX_NOPRE, SX_NOG, SX_GRAN(2, 3, SX_SHIFT(1), SX_SCALE(0), SX_RES(0, 2)), SX_SHIFT(1), SX_SCALE(0),
-          SX_RES(0, 2)),
+    SX_PROG(kFormRows, kGran, 2, 3, SX_SHIFT(1), SX_SCALE(0), SX_RES(0, 2)),
     // 3-D (BASELINE config 3: shift(r) + scale(e) + resolution_scale(e | e_true))
-    SX_P1(3, 3, SX_PRE(3, 3, SX_SHIFT(0)), SX_NOG, SX_NOGRAN, SX_SHIFT(0)),
-    SX_P1(3, 3, SX_PRE(3, 3, SX_SCALE(0)), SX_NOG, SX_NOGRAN, SX_SCALE(0)),
-    SX_P1(3, 4, SX_PRE(3, 4, SX_RES(0, 3)), SX_NOG, SX_NOGRAN, SX_RES(0, 3)),
-    SX_P2(3, 4, SX_PRE(3, 4, SX_SCALE(0), SX_RES(0, 3)), SX_NOG, SX_NOGRAN, SX_SCALE(0), SX_RES(0, 3)),
-    SX_P3(3, 4, SX_PRE(3, 4, SX_SHIFT(1), SX_SCALE(0), SX_RES(0, 3)),
-          SX_G(3, 4, SX_SHIFT(1), SX_SCALE(0), SX_RES(0, 3)), SX_NOGRAN, SX_SHIFT(1), SX_SCALE(0), SX_RES(0, 3)),
+    SX_PROG(kFormRows, kPre, 3, 3, SX_SHIFT(0)), SX_PROG(kFormRows, kPre, 3, 3, SX_SCALE(0)),
+    SX_PROG(kFormRows, kPre, 3, 4, SX_RES(0, 3)), SX_PROG(kFormRows, kPre, 3, 4, SX_SCALE(0), SX_RES(0, 3)),
+    SX_PROG(kFormRows, kPre | kBeyond, 3, 4, SX_SHIFT(1), SX_SCALE(0), SX_RES(0, 3)),
     // 5-D (BASELINE config 5: the same three systematics, histograms beyond LDS capacity)
-    SX_P3(5, 6, SX_PRE(5, 6, SX_SHIFT(1), SX_SCALE(0), SX_RES(0, 5)),
-          SX_G(5, 6, SX_SHIFT(1), SX_SCALE(0), SX_RES(0, 5)), SX_NOGRAN, SX_SHIFT(1), SX_SCALE(0), SX_RES(0, 5)),
-};
-constexpr int kNumStatic = (int)(sizeof(kStaticPrograms) / sizeof(kStaticPrograms[0]));
-
-// Ordered programs built in (bucketed table with an ordered observable, fill_ordered_kernel): slots are the
-// observables binned per sample, the fields only read, then the ordered observable.  Anything else: hiprtc.
-template <int NOBS, int NSLOT, typename PROG>
-hipError_t launch_fill_ordered_k(const SxLaunchShape& sh, const SxSignalDesc* descs, const SxSegment* segs,
-                                 const unsigned* blk_off, hipStream_t s) {
-  if (sh.tail) {   // the whole step in this launch: the fill's workgroups + finisher + workers
-    auto ks = fill_ordered_step_kernel<NOBS, NSLOT, PROG>;
-    if (sh.lds_bytes > 48 * 1024) {
-      hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(ks),
-                                         hipFuncAttributeMaxDynamicSharedMemorySize, (int)sh.lds_bytes);
-      if (e != hipSuccess) return e;
-    }
-    hipLaunchKernelGGL(ks, dim3(sh.grid + sh.tail_blocks), dim3(sh.threads), sh.lds_bytes, s, descs, segs, blk_off,
-                       sh.lds_layout, (unsigned)sh.debug_mode, (unsigned)sh.grid, *static_cast<const SxTailArgs*>(sh.tail));
-    return hipGetLastError();
-  }
-  auto k = fill_ordered_kernel<NOBS, NSLOT, PROG>;
-  if (sh.lds_bytes > 48 * 1024) {
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(k),
-                                       hipFuncAttributeMaxDynamicSharedMemorySize, (int)sh.lds_bytes);
-    if (e != hipSuccess) return e;
-  }
-  launch_fill(sh, k, dim3(sh.grid), dim3(sh.threads), sh.lds_bytes, s, descs, segs, blk_off, sh.lds_layout,
-              (unsigned)sh.debug_mode);
-  return hipGetLastError();
-}
-struct OrderedEntry {
-  int nobs, nslot, nops;
-  unsigned ops[4];
-  FillLauncher fn;
-};
-#define SX_O1(NO, NS, A) {NO, NS, 1, {A, 0, 0, 0}, launch_fill_ordered_k<NO, NS, StaticProg<A>>}
-#define SX_O3(NO, NS, A, B, C) {NO, NS, 3, {A, B, C, 0}, launch_fill_ordered_k<NO, NS, StaticProg<A, B, C>>}
-const OrderedEntry kOrderedPrograms[] = {
-    // one observable, one shift / scale (bench_sxmc pdfz): nothing is streamed but the granule words
-    SX_O1(0, 1, SX_SHIFT(0)),
-    SX_O1(0, 1, SX_SCALE(0)),
+    SX_PROG(kFormRows, kPre | kBeyond, 5, 6, SX_SHIFT(1), SX_SCALE(0), SX_RES(0, 5)),
+    // ordered: one observable, one shift / scale (bench_sxmc pdfz): nothing is streamed but the granule words
+    SX_PROG(kFormOrdered, 0, 0, 1, SX_SHIFT(0)), SX_PROG(kFormOrdered, 0, 0, 1, SX_SCALE(0)),
     // BASELINE configs 3 and 5 bucketed: e (scale + resolution_scale against e_true) binned per sample, r (shift) ordered
-    SX_O3(1, 3, SX_SHIFT(2), SX_SCALE(0), SX_RES(0, 1)),
+    SX_PROG(kFormOrdered, 0, 1, 3, SX_SHIFT(2), SX_SCALE(0), SX_RES(0, 1)),
+    // boxed, BASELINE config 3 bucketed: r (shift) binned per sample, e (scale + resolution_scale against e_true) boxed
+    SX_PROG(kFormBoxed, 0, 1, 3, SX_SHIFT(0), SX_SCALE(2), SX_RES(2, 1)),
 };
-constexpr int kNumOrdered = (int)(sizeof(kOrderedPrograms) / sizeof(kOrderedPrograms[0]));
+constexpr int kNumPrograms = (int)(sizeof(kPrograms) / sizeof(kPrograms[0]));
 
-// Boxed programs built in (bucketed table with a boxed observable, fill_boxed_kernel): slot 0 the observable binned per
-// sample, slot 1 the truth field, slot 2 the boxed observable.  Anything else: hiprtc.
-template <int NOBS, int NSLOT, typename PROG>
-hipError_t launch_fill_boxed_k(const SxLaunchShape& sh, const SxSignalDesc* descs, const SxSegment* segs,
-                               const unsigned* blk_off, hipStream_t s) {
-  auto k = fill_boxed_kernel<NOBS, NSLOT, PROG>;
-  if (sh.lds_bytes > 48 * 1024) {
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(k),
-                                       hipFuncAttributeMaxDynamicSharedMemorySize, (int)sh.lds_bytes);
-    if (e != hipSuccess) return e;
-  }
-  launch_fill(sh, k, dim3(sh.grid), dim3(sh.threads), sh.lds_bytes, s, descs, segs, blk_off, sh.lds_layout,
-              (unsigned)sh.debug_mode);
-  return hipGetLastError();
-}
-#define SX_B3(NO, NS, A, B, C) {NO, NS, 3, {A, B, C, 0}, launch_fill_boxed_k<NO, NS, StaticProg<A, B, C>>}
-const OrderedEntry kBoxedPrograms[] = {
-    // BASELINE config 3 bucketed: r (shift) binned per sample, e (scale + resolution_scale against e_true) boxed
-    SX_B3(1, 3, SX_SHIFT(0), SX_SCALE(2), SX_RES(2, 1)),
-};
-constexpr int kNumBoxed = (int)(sizeof(kBoxedPrograms) / sizeof(kBoxedPrograms[0]));
-template <int NOBS, int NSLOT>
-hipError_t launch_fill_dyn(const SxLaunchShape& sh, const SxSignalDesc* descs, const SxSegment* segs,
-                           const unsigned* blk_off, hipStream_t s) {
-  return sh.lds_hist ? launch_fill_k<NOBS, NSLOT, true, DynamicProg>(sh, descs, segs, blk_off, s)
-                     : launch_fill_k<NOBS, NSLOT, false, DynamicProg>(sh, descs, segs, blk_off, s);
+// The launcher of built-in program `prog` for this form of table and histogram mode, or null.
+FillLauncher program_launcher(int prog, int form, int lds_hist, int sparse_runs) {
+  if (prog < 0 || prog >= kNumPrograms) return nullptr;
+  const FillEntry& e = kPrograms[prog];
+  const bool own = sx_form_ordered(form);   // (an entry of that form, its one kernel in [0][0])
+  if (e.form != (own ? form : kFormRows) || form < kFormRows || (!own && form > kFormBucketed)) return nullptr;
+  return e.fn[sparse_runs ? 2 : lds_hist ? 0 : 1][own ? 0 : form];
 }
 
 }  // namespace
@@ -1192,25 +1133,24 @@ bool sx_fill_has_specialization(int nobs, int nslot) {
   return nobs >= 1 && nobs <= 5 && nslot >= nobs && nslot <= nobs + 2;
 }
 
-// does static program `prog` have a kernel for this histogram mode, without / with a pre-binned column
-// (prebin = 1) / for a bucketed table (prebin = 3)?
-bool sx_fill_static_supports(int prog, int lds_hist, int prebin) {
-  if (prog < 0 || prog >= kNumStatic) return false;
-  const StaticEntry& e = kStaticPrograms[prog];
-  if (prebin == kPreGranule) return e.fn_gran[lds_hist ? 0 : 1] != nullptr;
-  if (prebin) return (lds_hist ? e.fn_pre[0] : e.fn_g_pre[0]) != nullptr;
-  return (lds_hist ? e.fn : e.fn_g) != nullptr;
+int sx_fill_find_program(int form, int nobs, int nslot, int nops, const unsigned* ops) {
+  const int entry_form = sx_form_ordered(form) ? form : kFormRows;
+  for (int i = 0; i < kNumPrograms; i++) {
+    const FillEntry& e = kPrograms[i];
+    const bool shape = e.form == entry_form && e.nobs == nobs && e.nslot == nslot && e.nops == nops;
+    if (shape && std::equal(ops, ops + nops, e.ops)) return i;
+  }
+  return -1;
+}
+
+bool sx_fill_supports(int prog, int form, int lds_hist, int sparse_runs) {
+  return program_launcher(prog, form, lds_hist, sparse_runs) != nullptr;
 }
 
 // Does the launch described by `sh` also exist fused with the step end (see fill_step_kernel)?
 bool sx_fill_has_step_form(const SxLaunchShape& sh) {
-  if (sh.rtc_fill || !sh.lds_hist || sh.grid <= 0) return false;
-  if (sh.pre_width == kPreOrdered) return sh.static_prog >= 0 && sh.static_prog < kNumOrdered;
-  if (sh.pre_width == 1 || sh.pre_width == 2) {
-    return sh.static_prog >= 0 && sh.static_prog < kNumStatic && kStaticPrograms[sh.static_prog].nops == 0 &&
-           kStaticPrograms[sh.static_prog].fn_pre[sh.pre_width - 1] != nullptr;
-  }
-  return false;
+  if (sh.rtc_fill || !sh.lds_hist || sh.grid <= 0 || !program_launcher(sh.static_prog, sh.form, 1, 0)) return false;
+  return sh.form == kFormOrdered || (sx_form_prebinned(sh.form) && kPrograms[sh.static_prog].nops == 0);
 }
 size_t sx_tail_args_bytes() { return sizeof(SxTailArgs); }
 // Fills the host image of a group's SxTailArgs (the device struct is private to this file).
@@ -1236,20 +1176,15 @@ void sx_tail_args_fill(void* image, const SxSignalDesc* lookup_descs, const SxSi
   std::memcpy(image, &t, sizeof t);
 }
 
-bool sx_fill_static_supports_sparse_runs(int prog) {
-  return prog >= 0 && prog < kNumStatic && kStaticPrograms[prog].fn_sruns != nullptr;
-}
-
 hipError_t sx_launch_fill_sparse_runs(const SxLaunchShape& sh, const SxSignalDesc* descs, const SxSegment* segs,
                                       const unsigned* blk_off, hipStream_t s) {
   if (sh.grid <= 0) return hipSuccess;
   if (sh.rtc_sparse) {
-    const unsigned smax = (unsigned)(sh.sparse_lds_bytes / 4 / ((unsigned)sh.threads / 64u) / 2);
-    return sx_rtc_launch(sh.rtc_sparse, sh.grid, sh.threads, sh.sparse_lds_bytes, descs, segs, blk_off, smax,
+    return sx_rtc_launch(sh.rtc_sparse, sh.grid, sh.threads, sh.sparse_lds_bytes, descs, segs, blk_off, sparse_smax(sh),
                          (unsigned)sh.debug_mode, s, sh.ev_start, sh.ev_stop);
   }
-  if (!sx_fill_static_supports_sparse_runs(sh.static_prog)) return hipErrorInvalidValue;
-  return kStaticPrograms[sh.static_prog].fn_sruns(sh, descs, segs, blk_off, s);
+  const FillLauncher fn = program_launcher(sh.static_prog, sh.form, sh.lds_hist, 1);
+  return fn ? fn(sh, descs, segs, blk_off, s) : hipErrorInvalidValue;
 }
 
 hipError_t sx_launch_prebin(const SxSignalDesc* d_desc, unsigned long long npad, unsigned mask, int width, void* out,
@@ -1261,90 +1196,31 @@ hipError_t sx_launch_prebin(const SxSignalDesc* d_desc, unsigned long long npad,
   return hipGetLastError();
 }
 
-int sx_fill_find_static_program(int nobs, int nslot, int nops, const unsigned* ops) {
-  for (int i = 0; i < kNumStatic; i++) {
-    const StaticEntry& e = kStaticPrograms[i];
-    if (e.nobs != nobs || e.nslot != nslot || e.nops != nops) continue;
-    bool same = true;
-    for (int k = 0; k < nops; k++) same = same && e.ops[k] == ops[k];
-    if (same) return i;
-  }
-  return -1;
-}
-
-int sx_fill_find_ordered_program(int nobs, int nslot, int nops, const unsigned* ops) {
-  for (int i = 0; i < kNumOrdered; i++) {
-    const OrderedEntry& e = kOrderedPrograms[i];
-    if (e.nobs != nobs || e.nslot != nslot || e.nops != nops) continue;
-    bool same = true;
-    for (int k = 0; k < nops; k++) same = same && e.ops[k] == ops[k];
-    if (same) return i;
-  }
-  return -1;
-}
-
-int sx_fill_find_boxed_program(int nobs, int nslot, int nops, const unsigned* ops) {
-  for (int i = 0; i < kNumBoxed; i++) {
-    const OrderedEntry& e = kBoxedPrograms[i];
-    if (e.nobs != nobs || e.nslot != nslot || e.nops != nops) continue;
-    bool same = true;
-    for (int k = 0; k < nops; k++) same = same && e.ops[k] == ops[k];
-    if (same) return i;
-  }
-  return -1;
-}
-
+// The fill of one launch class: the kernel specialised at run time, else the built-in program's for the table's form,
+// else the kernel that decodes the program for this (nobs, nslot), else the generic one.
 hipError_t sx_launch_fill(const SxLaunchShape& sh, const SxSignalDesc* descs, const SxSegment* segs,
                           const unsigned* blk_off, hipStream_t s) {
   if (sh.grid <= 0) return hipSuccess;
-  if (sh.pre_width == kPreBoxed && !sh.rtc_fill) {
-    if (sh.static_prog < 0 || sh.static_prog >= kNumBoxed) return hipErrorInvalidValue;
-    return kBoxedPrograms[sh.static_prog].fn(sh, descs, segs, blk_off, s);
-  }
-  if (sh.pre_width == kPreOrdered && !sh.rtc_fill) {
-    if (sh.static_prog < 0 || sh.static_prog >= kNumOrdered) return hipErrorInvalidValue;
-    return kOrderedPrograms[sh.static_prog].fn(sh, descs, segs, blk_off, s);
-  }
   if (sh.rtc_fill) {
-    const unsigned hist_words = (sh.pre_width == kPreOrdered || sh.pre_width == kPreBoxed) ? sh.lds_layout
-                                                            : (unsigned)(sh.lds_bytes / 4 - 4 - (sh.lds_hist ? 64 : 0));
-    return sx_rtc_launch(sh.rtc_fill, sh.grid, sh.threads, sh.lds_bytes, descs, segs, blk_off, hist_words,
+    return sx_rtc_launch(sh.rtc_fill, sh.grid, sh.threads, sh.lds_bytes, descs, segs, blk_off, sx_fill_w(sh),
                          (unsigned)sh.debug_mode, s, sh.ev_start, sh.ev_stop);
   }
-  if (sh.static_prog >= 0 && sh.static_prog < kNumStatic) {
-    const StaticEntry& e = kStaticPrograms[sh.static_prog];
-    FillLauncher fn = nullptr;
-    if (sh.pre_width == 0) {
-      fn = sh.lds_hist ? e.fn : e.fn_g;
-    } else if (sh.pre_width == kPreGranule) {
-      fn = e.fn_gran[sh.lds_hist ? 0 : 1];
-    } else if (sh.pre_width == 1 || sh.pre_width == 2) {
-      fn = sh.lds_hist ? e.fn_pre[sh.pre_width - 1] : e.fn_g_pre[sh.pre_width - 1];
-    }
-    if (!fn) return hipErrorInvalidValue;
-    return fn(sh, descs, segs, blk_off, s);
+  if (sx_form_ordered(sh.form) || (sh.static_prog >= 0 && sh.static_prog < kNumPrograms)) {
+    const FillLauncher fn = program_launcher(sh.static_prog, sh.form, sh.lds_hist, 0);
+    return fn ? fn(sh, descs, segs, blk_off, s) : hipErrorInvalidValue;
   }
-#define SX_CASE(NO, NS) \
-  if (sh.nobs == NO && sh.nslot == NS) return launch_fill_dyn<NO, NS>(sh, descs, segs, blk_off, s);
+#define SX_CASE(NO, NS)                                                                                  \
+  if (sh.nobs == NO && sh.nslot == NS)                                                                   \
+    return (sh.lds_hist ? launch_fill_k<NO, NS, true, DynamicProg> : launch_fill_k<NO, NS, false, DynamicProg>)( \
+        sh, descs, segs, blk_off, s);
   SX_CASE(1, 1) SX_CASE(1, 2) SX_CASE(1, 3)
   SX_CASE(2, 2) SX_CASE(2, 3) SX_CASE(2, 4)
   SX_CASE(3, 3) SX_CASE(3, 4) SX_CASE(3, 5)
   SX_CASE(4, 4) SX_CASE(4, 5) SX_CASE(4, 6)
   SX_CASE(5, 5) SX_CASE(5, 6) SX_CASE(5, 7)
 #undef SX_CASE
-  if (sh.lds_hist) {
-    auto k = fill_kernel_generic<true>;
-    if (sh.lds_bytes > 48 * 1024) {
-      hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(k),
-                                         hipFuncAttributeMaxDynamicSharedMemorySize, (int)sh.lds_bytes);
-      if (e != hipSuccess) return e;
-    }
-    launch_fill(sh, k, dim3(sh.grid), dim3(sh.threads), sh.lds_bytes, s, descs, segs, blk_off,
-                (unsigned)(sh.lds_bytes / 4 - 4 - 64));
-  } else {
-    launch_fill(sh, fill_kernel_generic<false>, dim3(sh.grid), dim3(sh.threads), (size_t)64, s, descs, segs, blk_off, 0u);
-  }
-  return hipGetLastError();
+  return sh.lds_hist ? launch_fill(sh, fill_kernel_generic<true>, sh.lds_bytes, false, s, descs, segs, blk_off, sx_fill_w(sh))
+                     : launch_fill(sh, fill_kernel_generic<false>, (size_t)64, false, s, descs, segs, blk_off, 0u);
 }
 
 hipError_t sx_launch_zero(const SxSignalDesc* d_descs, int nsig, int max_bins, unsigned* ticket, hipStream_t s) {

@@ -67,12 +67,9 @@ struct SxLaunchShape {
   void* rtc_sparse; // ... and for its sparse flavour over runs
   int sparse_runs;  // 1: the sparse flavour of this launch runs fill_sparse_kernel (bucketed table laid out in runs)
   size_t sparse_lds_bytes;
-  unsigned lds_layout;  // pre_width 5: words between the LDS histogram's replicas | log2(replicas) << 24
-  int pre_width;    // bytes per sample of the pre-binned column (1, 2, 4), 0 = none, 3 = bucketed table (one
-                    // bin offset per 256-sample granule), 5 = bucketed table with an ordered observable
-                    // (fill_ordered_kernel; static_prog then indexes the ordered programs built in)
-                    // 6 = bucketed table with a BOXED observable (fill_boxed_kernel; static_prog indexes the boxed
-                    // programs built in; lds_layout as for 5, always the padded form with queues)
+  unsigned lds_layout;  // ordered / boxed forms: words between the LDS histogram's replicas | log2(replicas) << 24
+                        // (boxed: always the padded form with queues)
+  int form;         // the table's form (kForm*, sxmc_device_types.h); static_prog indexes the programs built in for it
   // profiling (sxmc_group_profile): when set, the fill is launched through hipExtLaunchKernelGGL /
   // hipExtModuleLaunchKernel with these two HIP events, which then carry the DISPATCH's own begin and end timestamps
   // -- the kernel's duration as rocprofv3 --kernel-trace reports it.  (Two hipEventRecord calls around the launch
@@ -85,6 +82,11 @@ struct SxLaunchShape {
   int tail_blocks = 0;
 };
 bool sx_fill_has_step_form(const SxLaunchShape& sh);
+// The fill kernels' `w` argument: the replica layout (ordered / boxed forms), else the histogram words the launch's LDS
+// holds beside its 4 header words and, with the histogram in LDS, 64 trash words.
+inline unsigned sx_fill_w(const SxLaunchShape& sh) {
+  return sx_form_ordered(sh.form) ? sh.lds_layout : (unsigned)(sh.lds_bytes / 4 - 4 - (sh.lds_hist ? 64 : 0));
+}
 size_t sx_tail_args_bytes();
 void sx_tail_args_fill(void* image, const SxSignalDesc* lookup_descs, const SxSignalDesc* hist_descs, int nsig,
                        int max_bins, unsigned long long npoints, const unsigned* weight, unsigned long long* slots,
@@ -92,7 +94,7 @@ void sx_tail_args_fill(void* image, const SxSignalDesc* lookup_descs, const SxSi
 
 // A fill kernel specialised at run time (sxmc_rtc.cpp): the template arguments of fill_body / fill_sparse_body.
 struct SxRtcSpec {
-  int nobs, nslot, lds_hist, pre_width, sparse_runs;
+  int nobs, nslot, lds_hist, form, sparse_runs;
   int nchain;                    // > 1: the lockstep-chains kernel (fill_multi_body), histograms in LDS
   int max_threads;               // launch bound of the kernel (0 = 1024): several chains over an ordered table need more
                                  // registers than 1024 lanes leave (spills inside the stream loop: every reload drains
@@ -146,13 +148,11 @@ hipError_t sx_launch_fill(const SxLaunchShape& shape, const SxSignalDesc* d_desc
                           const unsigned* d_blk_off, hipStream_t s);
 hipError_t sx_launch_fill_sparse_runs(const SxLaunchShape& shape, const SxSignalDesc* d_descs, const SxSegment* d_segs,
                                       const unsigned* d_blk_off, hipStream_t s);
-bool sx_fill_static_supports_sparse_runs(int prog);
-
 bool sx_fill_has_specialization(int nobs, int nslot);
-int sx_fill_find_static_program(int nobs, int nslot, int nops, const unsigned* ops);
-int sx_fill_find_ordered_program(int nobs, int nslot, int nops, const unsigned* ops);
-int sx_fill_find_boxed_program(int nobs, int nslot, int nops, const unsigned* ops);
-bool sx_fill_static_supports(int prog, int lds_hist, int prebin);
+// The programs built in: the index of the one for this form of table and compacted problem, or -1; and whether program
+// `prog` has a kernel for this form and histogram mode (sparse_runs: the event-bin counters over a bucketed table's runs).
+int sx_fill_find_program(int form, int nobs, int nslot, int nops, const unsigned* ops);
+bool sx_fill_supports(int prog, int form, int lds_hist, int sparse_runs);
 hipError_t sx_launch_prebin(const SxSignalDesc* d_desc, unsigned long long npad, unsigned mask, int width, void* out,
                             hipStream_t s);
 // bucketed copy of a sample table (layout_kernels.hip)

@@ -24,6 +24,21 @@
 #define SXMC_QCODE_EXACT 0xFFFEu /* "outside the window: ask the exact columns" */
 #define SXMC_QCODE_NEVER 0xFFFFu /* "not finite: never counted" */
 
+// The FORM of the table a fill launch streams.  Plain ints: they are template arguments of the kernels (PREW), text in
+// the kernels generated at run time and arguments of sxmc_rtc_compile_check*.  1 and 2 are also what they count: the
+// bytes per sample of the pre-binned column.
+constexpr int kFormRows = 0;       // the table as it is; every observable is read and binned by the fill
+constexpr int kFormPre1 = 1;       // + the observables no systematic writes as ONE pre-binned column, 1 byte per sample
+constexpr int kFormPre2 = 2;       // ... 2 bytes per sample
+constexpr int kFormBucketed = 3;   // bucketed copy: one bin offset per 256-sample granule
+constexpr int kFormOrdered = 5;    // bucketed, with an ORDERED observable (fill_ordered_kernel)
+constexpr int kFormBoxed = 6;      // bucketed, with a BOXED observable (fill_boxed_kernel); LDS laid out as for ordered
+constexpr bool sx_form_boxed(int form) { return form == kFormBoxed; }
+constexpr bool sx_form_ordered(int form) { return form == kFormOrdered || sx_form_boxed(form); }     // (boxed included)
+constexpr bool sx_form_bucketed(int form) { return form == kFormBucketed || sx_form_ordered(form); } // (ordered included)
+constexpr bool sx_form_prebinned(int form) { return form == kFormPre1 || form == kFormPre2; }
+constexpr int sx_form_pre_bytes(int form) { return sx_form_prebinned(form) ? form : 0; }   // per sample of the column
+
 // One systematic, addressed by SLOT (position among the columns a launch loads), not by field.
 // Restates SystematicDescriptor (pdfz.cpp:48-54) with the parameter indices inlined.
 struct SxSystOp {

@@ -139,7 +139,7 @@ int sxmc_group_optimize(sxmc_group_t g, sxmc_stream_t s, int* chosen_threads) {
   // second choice, for bucketed tables: one team of workgroups per member or three (see class_partition: which is
   // faster differs from box to box by ~3 % either way); three must win by 1.5 % to be taken
   bool has_bucketed = false;
-  for (const LaunchClass& c : g->classes) has_bucketed = has_bucketed || ((c.shape.pre_width == 3 || c.shape.pre_width == 5 || c.shape.pre_width == 6) && c.shape.lds_hist);
+  for (const LaunchClass& c : g->classes) has_bucketed = has_bucketed || (sx_form_bucketed(c.shape.form) && c.shape.lds_hist);
   if (failure == SXMC_OK && has_bucketed && g->plan_cfg.teams == 0) {
     float ms_of[2] = {best_ms, 1e30f};
     for (int pass = 0; pass < 2 && failure == SXMC_OK; pass++) {
@@ -375,6 +375,16 @@ int sxmc_group_set_runtime_kernels(sxmc_group_t g, int enable) {
   return SXMC_OK;
 }
 
+// The table of a launch as sxmc_group_launch_info names it.  twin: the launch belongs to the ordered twin of a boxed plan
+// and is the form that runs now.
+static const char* table_name(const LaunchClass& c, bool twin) {
+  const int form = c.shape.form;
+  if (sx_form_boxed(form)) return c.dual ? "boxed+codes(now)|ordered+codes" : "boxed+codes";
+  if (sx_form_ordered(form) && twin) return c.codes ? "boxed+codes|ordered+codes(now)" : "boxed+codes|ordered(now)";
+  if (sx_form_ordered(form)) return c.codes ? "ordered+codes" : "ordered";
+  return sx_form_bucketed(form) ? "bucketed" : form != kFormRows ? "prebinned" : "rows";
+}
+
 int sxmc_group_launch_info(sxmc_group_t g, char* out, size_t n) {
   SX_REQUIRE(g && out && n > 0, "null argument");
   int rc = group_refresh(g);
@@ -390,9 +400,7 @@ int sxmc_group_launch_info(sxmc_group_t g, char* out, size_t n) {
     std::snprintf(line, sizeof line,
                   "launch %zu: members=%zu nobs=%d nslot=%d hist=%s program=%s table=%s%s threads=%d grid=%d partition=%d teams=%d lds=%zu layout=0x%08X\n",
                   i, c.member_idx.size(), c.shape.nobs, c.shape.nslot, c.shape.lds_hist ? "lds" : "global", kind,
-                  c.shape.pre_width == 6 ? (c.dual ? "boxed+codes(now)|ordered+codes" : "boxed+codes")
-                  : (two && plan == g->twin && c.shape.pre_width == 5) ? (c.codes ? "boxed+codes|ordered+codes(now)" : "boxed+codes|ordered(now)")
-                  : c.shape.pre_width == 5 ? (c.codes ? "ordered+codes" : "ordered") : c.shape.pre_width == 3 ? "bucketed" : c.shape.pre_width ? "prebinned" : "rows",
+                  table_name(c, two && plan == g->twin),
                   c.runs_mode ? (c.shape.rtc_sparse ? "+runs(runtime)" : "+runs(builtin)") : "", c.shape.threads,
                   c.shape.grid, c.partition, c.teams, (size_t)c.shape.lds_bytes, c.shape.lds_layout);
     text += line;
@@ -896,7 +904,7 @@ int sxmc_rtc_compile_check(int nobs, int nslot, int lds_hist, int pre_width, int
   k.nobs = nobs;
   k.nslot = nslot;
   k.lds_hist = lds_hist;
-  k.pre_width = pre_width;
+  k.form = pre_width;
   k.sparse_runs = sparse_runs;
   k.nops = nops;
   for (int i = 0; i < nops; i++) k.ops[i] = ops[i];
@@ -912,7 +920,7 @@ int sxmc_rtc_compile_check_lockstep(int nobs, int nslot, int pre_width, int ncha
   k.nobs = nobs;
   k.nslot = nslot;
   k.lds_hist = 1;
-  k.pre_width = pre_width;
+  k.form = pre_width;
   k.nchain = nchains;
   k.nops = nops;
   for (int i = 0; i < nops; i++) k.ops[i] = ops[i];
@@ -984,8 +992,8 @@ int sxmc_group_algorithmic_bytes(sxmc_group_t g, double* fill_read, double* hist
     bool codes = false;
     for (const LaunchClass& c : g->classes) {
       for (int idx : c.member_idx) {
-        if (idx == (int)i && c.shape.pre_width) {
-          pre_w = c.shape.pre_width;
+        if (idx == (int)i && c.shape.form != kFormRows) {
+          pre_w = sx_form_pre_bytes(c.shape.form);   // (a bucketed member is counted from its copy, below)
           for (int k = 0; k < d.nobs; k++) pre_dims += (c.pre_mask >> k) & 1u;
         }
         if (idx == (int)i) codes = c.codes;

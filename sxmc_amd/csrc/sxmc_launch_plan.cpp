@@ -468,13 +468,13 @@ int group_rebuild(sxmc_group* g);
 // What a step of the plan found it cannot lay out: group_rebuild runs the pass again without that form.
 enum class Blocked { none, order, box };
 
-inline bool is_boxed(const LaunchClass& c) { return c.shape.pre_width == 6; }
-inline bool is_ordered(const LaunchClass& c) { return c.shape.pre_width == 5 || is_boxed(c); }   // (the LDS layout, shapes and partition of the ordered form)
-inline bool is_bucketed(const LaunchClass& c) { return c.shape.pre_width == 3 || is_ordered(c); }
+inline bool is_boxed(const LaunchClass& c) { return sx_form_boxed(c.shape.form); }
+inline bool is_ordered(const LaunchClass& c) { return sx_form_ordered(c.shape.form); }   // (the LDS layout, shapes and partition of the ordered form)
+inline bool is_bucketed(const LaunchClass& c) { return sx_form_bucketed(c.shape.form); }
 
 // One member's part of the plan: the form its table takes and the kernel that runs it.
 struct MemberPlan {
-  // the key of its launch class (find_class): shape.nobs / nslot / lds_hist / pre_width / rtc_fill / rtc_sparse, prog,
+  // the key of its launch class (find_class): shape.nobs / nslot / lds_hist / form / rtc_fill / rtc_sparse, prog,
   // prog_simple, pre_mask, runs_mode; with it shape.static_prog and the boxed form's slots.  find_class copies it as
   // the new class: set nothing else on it.
   LaunchClass cls;
@@ -484,21 +484,17 @@ struct MemberPlan {
   SxSignalDesc desc;                  // the member as its fill launch sees it
 };
 
-// is there a kernel for this specialisation?  *fn: the run-time one, or null for a built-in one
-bool have_kernel(sxmc_group* g, int lds_hist, int nobs, int nslot, int prew, int runs, const std::vector<unsigned>& words,
+// is there a kernel for this specialisation?  *fn: the run-time one, or null for a built-in one (sp: its index)
+bool have_kernel(sxmc_group* g, int lds_hist, int nobs, int nslot, int form, int runs, const std::vector<unsigned>& words,
                  int sp, void** fn) {
   *fn = nullptr;
-  if (prew == 5 || prew == 6) {   // (sp: index into the ordered / boxed programs built in: histograms in LDS, no runs)
-    if (sp >= 0 && lds_hist && !runs) return true;
-  } else if (runs ? sx_fill_static_supports_sparse_runs(sp) : sx_fill_static_supports(sp, lds_hist, prew)) {
-    return true;
-  }
+  if (sx_fill_supports(sp, form, lds_hist, runs)) return true;
   if (!g->plan_cfg.rtc) return false;
   SxRtcSpec k{};
   k.nobs = nobs;
   k.nslot = nslot;
   k.lds_hist = lds_hist;
-  k.pre_width = prew;
+  k.form = form;
   k.sparse_runs = runs;
   k.nops = (int)words.size();
   for (size_t q = 0; q < words.size(); q++) k.ops[q] = words[q];
@@ -525,11 +521,9 @@ int plan_bucketed(sxmc_group* g, int i, const sxplan::SystUse& use, int ordered,
   SxSignalDesc cd;
   sxplan::compact_desc(d, cs.keep, cs.nobs2, cd, ordered);
   const std::vector<unsigned> prog2 = sxplan::prog_words(cd);
-  const int prew = box_truth >= 0 ? 6 : ordered >= 0 ? 5 : 3;
-  const int sp = box_truth >= 0 ? sx_fill_find_boxed_program(cd.nobs, cd.nslot, (int)prog2.size(), prog2.data())
-                 : ordered >= 0 ? sx_fill_find_ordered_program(cd.nobs, cd.nslot, (int)prog2.size(), prog2.data())
-                                : sx_fill_find_static_program(cd.nobs, cd.nslot, (int)prog2.size(), prog2.data());
-  if (!have_kernel(g, lds_hist, cd.nobs, cd.nslot, prew, 0, prog2, sp, &k.shape.rtc_fill)) return SXMC_OK;
+  const int form = box_truth >= 0 ? kFormBoxed : ordered >= 0 ? kFormOrdered : kFormBucketed;
+  const int sp = sx_fill_find_program(form, cd.nobs, cd.nslot, (int)prog2.size(), prog2.data());
+  if (!have_kernel(g, lds_hist, cd.nobs, cd.nslot, form, 0, prog2, sp, &k.shape.rtc_fill)) return SXMC_OK;
   const SampleStore::BucketSort* bs = nullptr;
   int rc = get_bucket_sort(h, g->d_descs + i, cs.mask, ordered, &bs, box_truth >= 0 ? d.slot_col[box_truth] : -1);
   if (rc) return rc;
@@ -543,7 +537,7 @@ int plan_bucketed(sxmc_group* g, int i, const sxplan::SystUse& use, int ordered,
   // histograms beyond LDS, evaluated at data events: per-wave runs + event bins grouped by bucket
   const bool narrow = sxplan::narrow_for_runs(d);
   k.runs_mode = !lds_hist && narrow && h->has_points && h->d_table && box_truth < 0 &&
-                have_kernel(g, lds_hist, cd.nobs, cd.nslot, prew, 1, prog2, sp, &k.shape.rtc_sparse);
+                have_kernel(g, lds_hist, cd.nobs, cd.nslot, form, 1, prog2, sp, &k.shape.rtc_sparse);
   if (!lds_hist && !narrow && h->has_points && h->d_table) {
     // (a regression on very large histograms must be visible: sxmc_group_launch_info prints this)
     g->plan_note = "histogram with a bin count or stride of 2^23 or more: the sparse counting over runs (one signed "
@@ -559,7 +553,7 @@ int plan_bucketed(sxmc_group* g, int i, const sxplan::SystUse& use, int ordered,
   k.prog_simple = true;
   k.shape.static_prog = k.shape.rtc_fill ? -1 : sp;
   k.pre_mask = cs.pre_mask;
-  k.shape.pre_width = prew;
+  k.shape.form = form;
   k.box_obs = box_truth >= 0 ? ordered : -1;
   k.box_truth = box_truth;
   return SXMC_OK;
@@ -576,16 +570,16 @@ MemberPlan plan_rows(sxmc_group* g, const SxSignalDesc& d, const sxplan::SystUse
   k.shape.nslot = spec ? d.nslot : 0;
   k.prog = sxplan::prog_words(d);
   const int sp = (spec && use.specialisable)
-                     ? sx_fill_find_static_program(k.shape.nobs, k.shape.nslot, (int)k.prog.size(), k.prog.data())
+                     ? sx_fill_find_program(kFormRows, k.shape.nobs, k.shape.nslot, (int)k.prog.size(), k.prog.data())
                      : -1;
   k.prog_simple = spec && use.specialisable &&
-                  have_kernel(g, lds_hist, k.shape.nobs, k.shape.nslot, 0, 0, k.prog, sp, &k.shape.rtc_fill);
+                  have_kernel(g, lds_hist, k.shape.nobs, k.shape.nslot, kFormRows, 0, k.prog, sp, &k.shape.rtc_fill);
   k.shape.static_prog = (k.prog_simple && !k.shape.rtc_fill) ? sp : -1;
   // pre-binning: observables that no systematic writes (built-in programs only; bucketing covers the rest)
-  if (g->plan_cfg.prebin && sx_fill_static_supports(k.shape.static_prog, lds_hist, 1)) {
+  if (g->plan_cfg.prebin && sx_fill_supports(k.shape.static_prog, kFormPre1, lds_hist, 0)) {   // (1 byte: so 2 bytes)
     const sxplan::PrebinColumns pre = sxplan::prebin_columns(d, use);
     k.pre_mask = pre.mask;
-    k.shape.pre_width = pre.width;
+    k.shape.form = pre.width;   // (kFormPre1 / kFormPre2 ARE the column's bytes per sample; 0: nothing to pre-bin)
   }
   return mp;
 }
@@ -624,7 +618,7 @@ LaunchClass& find_class(sxmc_group* g, const MemberPlan& mp, int threads) {
   for (LaunchClass& c : g->classes) {
     if (c.shape.nobs == k.shape.nobs && c.shape.nslot == k.shape.nslot && c.shape.lds_hist == k.shape.lds_hist &&
         c.prog_simple == k.prog_simple && (!k.prog_simple || c.prog == k.prog) && c.pre_mask == k.pre_mask &&
-        c.shape.pre_width == k.shape.pre_width && c.runs_mode == k.runs_mode && c.shape.rtc_fill == k.shape.rtc_fill &&
+        c.shape.form == k.shape.form && c.runs_mode == k.runs_mode && c.shape.rtc_fill == k.shape.rtc_fill &&
         c.shape.rtc_sparse == k.shape.rtc_sparse) {
       return c;
     }
@@ -739,15 +733,15 @@ int class_tables(sxmc_group* g, const std::vector<MemberPlan>& plans, const std:
     const int idx = c.member_idx[q];
     SxSignalDesc d = plans[(size_t)idx].desc;
     sxmc_hist* h = g->members[idx];
-    if (c.shape.pre_width == 1 || c.shape.pre_width == 2) {
+    if (const int width = sx_form_pre_bytes(c.shape.form)) {
       SampleStore& st = *h->store;
       std::lock_guard<std::mutex> lock(st.pre_mutex);
-      void* pre = st.find_pre(c.pre_mask, c.shape.pre_width);
+      void* pre = st.find_pre(c.pre_mask, width);
       if (!pre) {
         const size_t npad = h->nvec * SXMC_VEC;
-        SX_HIP(hipMalloc(&pre, std::max<size_t>(npad * (size_t)c.shape.pre_width, 16)));
-        st.pre.push_back({c.pre_mask, c.shape.pre_width, pre});
-        SX_HIP(sx_launch_prebin(g->d_descs + idx, npad, c.pre_mask, c.shape.pre_width, pre, nullptr));
+        SX_HIP(hipMalloc(&pre, std::max<size_t>(npad * (size_t)width, 16)));
+        st.pre.push_back({c.pre_mask, width, pre});
+        SX_HIP(sx_launch_prebin(g->d_descs + idx, npad, c.pre_mask, width, pre, nullptr));
         SX_HIP(hipDeviceSynchronize());
       }
       d.pre = pre;

@@ -4,6 +4,14 @@
 using namespace sxhost;
 
 namespace sxhost {
+// Can this launch keep several histograms per member in LDS (the chains of a lockstep set, the look-ahead pass)?  With
+// the histogram in LDS, a program that runs as straight-line code, and rows, a bucketed or an ordered table.
+static bool lockstep_class_ok(const LaunchClass& c) {
+  const int form = c.shape.form;
+  return c.shape.lds_hist && c.prog_simple && (form == kFormRows || form == kFormBucketed || form == kFormOrdered) &&
+         (c.shape.nobs != 0 || form == kFormOrdered);
+}
+
 // Chains can share a fill pass when their launch plans are the same plan over the same tables.
 bool multigroup_prepare(sxmc_multigroup* mg) {
   const size_t C = mg->groups.size();
@@ -30,25 +38,26 @@ bool multigroup_prepare(sxmc_multigroup* mg) {
   mg->fill_w.assign(g0->classes.size(), 0u);
   for (size_t i = 0; i < g0->classes.size(); i++) {
     const LaunchClass& c0 = g0->classes[i];
-    if (!c0.shape.lds_hist || !c0.prog_simple ||
-        !(c0.shape.pre_width == 0 || c0.shape.pre_width == 3 || c0.shape.pre_width == 5) ||
-        (c0.shape.nobs == 0 && c0.shape.pre_width != 5)) {
+    if (!lockstep_class_ok(c0)) {
       mg->why_not = "a launch of the plan has its histogram beyond LDS, a run-time decoded program or a pre-binned column";
       return false;
     }
     for (size_t c = 1; c < C; c++) {
       const LaunchClass& cc = mg->groups[c]->classes[i];
       if (cc.shape.nobs != c0.shape.nobs || cc.shape.nslot != c0.shape.nslot || cc.shape.lds_hist != c0.shape.lds_hist ||
-          cc.shape.pre_width != c0.shape.pre_width || cc.prog != c0.prog || cc.prog_simple != c0.prog_simple ||
+          cc.shape.form != c0.shape.form || cc.prog != c0.prog || cc.prog_simple != c0.prog_simple ||
           cc.shape.grid != c0.shape.grid || cc.shape.threads != c0.shape.threads || cc.member_idx != c0.member_idx ||
           cc.partition != c0.partition) {
         mg->why_not = "the chains' launch plans differ (systematics, launch configuration)";
         return false;
       }
     }
-    size_t hist_words = c0.shape.lds_bytes / 4 - 4 - 64;
-    size_t lds = (4 + C * hist_words + 64) * 4;
-    if (c0.shape.pre_width == 5) {
+    const bool ordered = c0.shape.form == kFormOrdered;
+    size_t hist_words = 0, lds = 0;   // the kernel's `w` argument and its LDS, for C chains
+    if (!ordered) {
+      hist_words = sx_fill_w(c0.shape);   // (one chain's histogram words: C of them between header and trash words)
+      lds = (4 + C * hist_words + 64) * 4;
+    } else {
       // ordered fill: the kernel argument is the replica layout; as many replicas as fit beside the other chains'
       // (codes: the padded form of the histograms if the chains' histograms fit that way with the smallest queues; a plan
       // with two workgroups per CU leaves each of them half the CU's LDS)
@@ -72,10 +81,10 @@ bool multigroup_prepare(sxmc_multigroup* mg) {
     k.nobs = c0.shape.nobs;
     k.nslot = c0.shape.nslot;
     k.lds_hist = 1;
-    k.pre_width = c0.shape.pre_width;
+    k.form = c0.shape.form;
     k.nchain = (int)C;
     // (ordered tables: the kernel is compiled for the workgroup size of the plan -- 512, 768 or 1024 lanes)
-    k.max_threads = c0.shape.pre_width == 5 ? (c0.shape.threads <= 512 ? 512 : c0.shape.threads <= 768 ? 768 : 1024) : 0;
+    k.max_threads = ordered ? (c0.shape.threads <= 512 ? 512 : c0.shape.threads <= 768 ? 768 : 1024) : 0;
     k.nops = (int)c0.prog.size();
     for (size_t q = 0; q < c0.prog.size(); q++) k.ops[q] = c0.prog[q];
     std::string err;
@@ -378,12 +387,10 @@ int sxmc_group_lookahead_supported(sxmc_group_t g, int* ok) {
   DeviceProps props;
   if (get_props(props)) return SXMC_OK;
   for (const LaunchClass& c : g->classes) {
-    if (!c.shape.lds_hist || !c.prog_simple ||
-        !(c.shape.pre_width == 0 || c.shape.pre_width == 3 || c.shape.pre_width == 5) ||
-        (c.shape.nobs == 0 && c.shape.pre_width != 5)) {
-      return SXMC_OK;
-    }
-    const size_t words = c.shape.pre_width == 5 ? (size_t)(c.shape.lds_layout & 0xFFFFFFu) : c.shape.lds_bytes / 4 - 4 - 64;
+    if (!lockstep_class_ok(c)) return SXMC_OK;
+    // one histogram's words: an ordered table's `w` is the layout word, whose low 24 bits are the words between replicas
+    const unsigned w = sx_fill_w(c.shape);
+    const size_t words = c.shape.form == kFormOrdered ? (w & 0xFFFFFFu) : w;
     if ((4 + 2 * words + 64) * 4 > (size_t)props.lds_per_cu) return SXMC_OK;
   }
   *ok = 1;

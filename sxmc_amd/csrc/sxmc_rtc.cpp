@@ -2,7 +2,7 @@
 //
 // The fill runs fastest as straight-line code with the program (which systematic writes which column, in which
 // order: apply_systematic, /root/reference/src/pdfz.cpp:306-331) fixed at compile time.  The library carries such
-// kernels for a handful of common programs (pdfz_kernels.hip: kStaticPrograms); for any other program it compiles
+// kernels for a handful of common programs (pdfz_kernels.hip: kPrograms); for any other program it compiles
 // the SAME kernel template (fill_kernels.inc.h, embedded as text) with hiprtc, once per program and process, and
 // launches it through the module API.  A program that cannot be compiled (no hiprtc, a compilation error) falls
 // back to the kernel that decodes the program at run time: same results, slower.
@@ -30,73 +30,54 @@ std::string join(const char* const* pieces) {
   return s;
 }
 
+// The opening of the generated kernel, up to its body: over one chain's descriptors (`descs`), or over those of the
+// chains of a lockstep set by value (`chains`); `bound`: the launch bound; dbg: whether the last argument is named.
+std::string signature(bool chains, int bound, bool dbg = true) {
+  return "extern \"C\" __global__ __launch_bounds__(" + std::to_string(bound) + ") void sx_rtc_fill(" +
+         (chains ? "SxChainDescs chains, " : "const SxSignalDesc* __restrict__ descs, ") +
+         "const SxSegment* __restrict__ segs, const unsigned* __restrict__ blk_off, unsigned w, unsigned" +
+         (dbg ? " dbg" : "") + ") {\n";
+}
+
 std::string kernel_source(const SxRtcSpec& k) {
   std::string prog = "StaticProg<";
   for (int i = 0; i < k.nops; i++) prog += (i ? ", " : "") + std::to_string(k.ops[i]) + "u";
   prog += ">";
+  const std::string shape = std::to_string(k.nobs) + ", " + std::to_string(k.nslot) + ", ";
+  const std::string one_chain = "  SxChainDescs one;\n  one.d[0] = one.d[1] = one.d[2] = one.d[3] = descs;\n";
   std::string s = "#include \"fill_kernels.inc.h\"\nusing namespace sxfill;\n";
-  if (k.pre_width == 6) {   // bucketed table with a boxed observable (fill_boxed_body)
-    s += "extern \"C\" __global__ __launch_bounds__(1024) void sx_rtc_fill(const SxSignalDesc* __restrict__ descs, "
-         "const SxSegment* __restrict__ segs, const unsigned* __restrict__ blk_off, unsigned w, unsigned dbg) {\n";
-    s += "  fill_boxed_body<" + std::to_string(k.nobs) + ", " + std::to_string(k.nslot) + ", " + prog +
-         ">(descs, segs, blk_off, w, dbg);\n}\n";
-    return s;
+  if (sx_form_boxed(k.form)) {   // bucketed table with a boxed observable (fill_boxed_body)
+    return s + signature(false, 1024) + "  fill_boxed_body<" + shape + prog + ">(descs, segs, blk_off, w, dbg);\n}\n";
   }
-  if (k.pre_width == 5 && k.sparse_runs) {   // ... its sparse counting over runs
-    s += "extern \"C\" __global__ __launch_bounds__(1024) void sx_rtc_fill(const SxSignalDesc* __restrict__ descs, "
-         "const SxSegment* __restrict__ segs, const unsigned* __restrict__ blk_off, unsigned w, unsigned dbg) {\n";
-    s += "  fill_sparse_body<" + std::to_string(k.nobs) + ", " + std::to_string(k.nslot) + ", " + prog +
-         ", true>(descs, segs, blk_off, w, dbg);\n}\n";
-    return s;
+  if (k.form == kFormOrdered && k.sparse_runs) {   // an ordered observable: its sparse counting over runs
+    return s + signature(false, 1024) + "  fill_sparse_body<" + shape + prog + ", true>(descs, segs, blk_off, w, dbg);\n}\n";
   }
-  if (k.pre_width == 5 && !k.lds_hist) {     // ... its dense evaluation with a histogram beyond LDS
-    s += "extern \"C\" __global__ __launch_bounds__(1024) void sx_rtc_fill(const SxSignalDesc* __restrict__ descs, "
-         "const SxSegment* __restrict__ segs, const unsigned* __restrict__ blk_off, unsigned w, unsigned dbg) {\n";
-    s += "  SxChainDescs one;\n  one.d[0] = one.d[1] = one.d[2] = one.d[3] = descs;\n";
-    s += "  fill_ordered_body<" + std::to_string(k.nobs) + ", " + std::to_string(k.nslot) + ", " + prog +
-         ", 1, false>(one, segs, blk_off, w, dbg);\n}\n";
-    return s;
+  if (k.form == kFormOrdered && !k.lds_hist) {     // ... its dense evaluation with a histogram beyond LDS
+    return s + signature(false, 1024) + one_chain + "  fill_ordered_body<" + shape + prog +
+           ", 1, false>(one, segs, blk_off, w, dbg);\n}\n";
   }
-  if (k.pre_width == 5) {   // bucketed table with an ordered observable (fill_ordered_body), 1 to 4 chains
-    const std::string targs = std::to_string(k.nobs) + ", " + std::to_string(k.nslot) + ", " + prog + ", " +
-                              std::to_string(k.nchain > 1 ? k.nchain : 1);
-    if (k.nchain > 1) {
-      const int bound = k.max_threads > 0 ? k.max_threads : 1024;
-      s += "extern \"C\" __global__ __launch_bounds__(" + std::to_string(bound) + ") void sx_rtc_fill(SxChainDescs chains, "
-           "const SxSegment* __restrict__ segs, const unsigned* __restrict__ blk_off, unsigned w, unsigned dbg) {\n";
-      s += "  fill_ordered_body<" + targs + ">(chains, segs, blk_off, w, dbg);\n}\n";
-    } else {
-      s += "extern \"C\" __global__ __launch_bounds__(1024) void sx_rtc_fill(const SxSignalDesc* __restrict__ descs, "
-           "const SxSegment* __restrict__ segs, const unsigned* __restrict__ blk_off, unsigned w, unsigned dbg) {\n";
-      s += "  SxChainDescs one;\n  one.d[0] = one.d[1] = one.d[2] = one.d[3] = descs;\n";
-      s += "  fill_ordered_body<" + targs + ">(one, segs, blk_off, w, dbg);\n}\n";
-    }
-    return s;
+  if (k.form == kFormOrdered && k.nchain > 1) {    // ... (fill_ordered_body) for 2 to 4 chains
+    return s + signature(true, k.max_threads > 0 ? k.max_threads : 1024) + "  fill_ordered_body<" + shape + prog + ", " +
+           std::to_string(k.nchain) + ">(chains, segs, blk_off, w, dbg);\n}\n";
+  }
+  if (k.form == kFormOrdered) {                    // ... for one chain
+    return s + signature(false, 1024) + one_chain + "  fill_ordered_body<" + shape + prog +
+           ", 1>(one, segs, blk_off, w, dbg);\n}\n";
   }
   if (k.nchain > 1) {
-    s += "extern \"C\" __global__ __launch_bounds__(1024) void sx_rtc_fill(SxChainDescs chains, "
-         "const SxSegment* __restrict__ segs, const unsigned* __restrict__ blk_off, unsigned w, unsigned) {\n";
-    s += "  fill_multi_body<" + std::to_string(k.nobs) + ", " + std::to_string(k.nslot) + ", " + prog + ", " +
-         std::to_string(k.pre_width) + ", " + std::to_string(k.nchain) + ">(chains, segs, blk_off, w);\n}\n";
-    return s;
+    return s + signature(true, 1024, false) + "  fill_multi_body<" + shape + prog + ", " + std::to_string(k.form) + ", " +
+           std::to_string(k.nchain) + ">(chains, segs, blk_off, w);\n}\n";
   }
-  s += "extern \"C\" __global__ __launch_bounds__(1024) void sx_rtc_fill(const SxSignalDesc* __restrict__ descs, "
-       "const SxSegment* __restrict__ segs, const unsigned* __restrict__ blk_off, unsigned w, unsigned dbg) {\n";
   if (k.sparse_runs) {
-    s += "  fill_sparse_body<" + std::to_string(k.nobs) + ", " + std::to_string(k.nslot) + ", " + prog +
-         ">(descs, segs, blk_off, w, dbg);\n";
-  } else {
-    s += "  fill_body<" + std::to_string(k.nobs) + ", " + std::to_string(k.nslot) + ", " +
-         (k.lds_hist ? "true" : "false") + ", " + prog + ", " + std::to_string(k.pre_width) +
-         ">(descs, segs, blk_off, w, dbg);\n";
+    return s + signature(false, 1024) + "  fill_sparse_body<" + shape + prog + ">(descs, segs, blk_off, w, dbg);\n}\n";
   }
-  s += "}\n";
-  return s;
+  return s + signature(false, 1024) + "  fill_body<" + shape + (k.lds_hist ? "true" : "false") + ", " + prog + ", " +
+         std::to_string(k.form) + ">(descs, segs, blk_off, w, dbg);\n}\n";
 }
 
 std::string spec_key(const SxRtcSpec& k) {
   std::string s = std::to_string(k.nobs) + "/" + std::to_string(k.nslot) + "/" + std::to_string(k.lds_hist) + "/" +
-                  std::to_string(k.pre_width) + "/" + std::to_string(k.sparse_runs) + "/" + std::to_string(k.nchain) + "/" +
+                  std::to_string(k.form) + "/" + std::to_string(k.sparse_runs) + "/" + std::to_string(k.nchain) + "/" +
                   std::to_string(k.max_threads) + ":";
   for (int i = 0; i < k.nops; i++) s += std::to_string(k.ops[i]) + ",";
   return s;
