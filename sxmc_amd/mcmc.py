@@ -367,8 +367,10 @@ class MCMC:
             for j in range(self.nparameters):
                 if jw[j] <= 0:
                     continue
-                sd = float(sofar[:, j].std()) if sofar.shape[0] > 1 else 0.0
-                jw[j] = self._scale_factor * (sd if sd > 0 else jw[j])
+                # the spread in double (TH1::GetRMS sums doubles), and `scale_factor * fit_width` as the double product the
+                # reference rounds to float once (mcmc.cpp:292-298): a float32 spread gave widths an ulp or two off
+                sd = float(sofar[:, j].astype(np.float64).std()) if sofar.shape[0] > 1 else 0.0
+                jw[j] = np.float32(float(self._scale_factor) * (sd if sd > 0 else float(jw[j])))
             self.jump_width.set(jw)
             if not self._debug:
                 self._rows = [np.zeros((0, self.nparameters + 1), np.float32)]

@@ -48,7 +48,12 @@ def gpu_nll(x, ne, ns, nsources, grid=64, block=256, reduce_threads=128):
     return out.get()[0], total.get()[0], sums.get()
 
 
-@pytest.mark.parametrize("ne,ns,nsources", [(1, 1, 1), (7, 2, 2), (1000, 12, 12), (100000, 12, 5), (4097, 29, 29)])
+@pytest.mark.parametrize("ne,ns,nsources", [(1, 1, 1), (7, 2, 2), (1000, 12, 12), (100000, 12, 5), (4097, 29, 29),
+                                            # the sixteen-signal request groups of nll_event_chunks_kernel: one short of
+                                            # a group, one, one over, two, two and one -- and fewer events than the
+                                            # 16 384 lanes launched (lanes with none, lanes whose look-ahead is clamped)
+                                            (300, 15, 6), (20000, 16, 16), (5000, 17, 5), (40000, 32, 9), (63, 33, 33),
+                                            (16385, 33, 7), (2, 17, 17)])
 def test_nll_chain_matches_oracle(ne, ns, nsources):
     rng = np.random.default_rng(ne + ns)
     x = random_nll_inputs(rng, ne, ns, nsources)
@@ -61,7 +66,13 @@ def test_nll_chain_matches_oracle(ne, ns, nsources):
 
 
 @pytest.mark.parametrize("grid,block,red", [(1, 64, 64), (3, 192, 256), (64, 256, 128), (16, 1024, 1024),
-                                            (5, 96, 96), (2, 33, 1)])   # partly filled waves in the reduction
+                                            (5, 96, 96), (2, 33, 1),    # partly filled waves in the reduction
+                                            # grid x block partial sums on each side of block_sum's 16-way unroll, for
+                                            # bd = 128 lanes: 1, bd - 1, 16 bd - 1, 16 bd, 16 bd + 1, 17 bd + 5 ...
+                                            (1, 1, 128), (1, 127, 128), (23, 89, 128), (16, 128, 128), (3, 683, 128),
+                                            (3, 727, 128),
+                                            # ... and for bd = 96 (a last wave half empty): 16 bd - 1, 16 bd + 1
+                                            (5, 307, 96), (29, 53, 96)])
 def test_nll_launch_shapes(grid, block, red):
     rng = np.random.default_rng(3)
     x = random_nll_inputs(rng, 5003, 6, 6)
