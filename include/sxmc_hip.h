@@ -286,9 +286,48 @@ int sxmc_kde_create(const float* samples, size_t nsamples_floats, int samples_on
                     const double* upper, size_t n_upper,
                     const double* bandwidth_scale, size_t n_bandwidth_scale,
                     unsigned dataset, sxmc_kde_t* out);
+/* Adaptive (sample-point) bandwidths, Abramson's estimator (Silverman 5.3): sxmc_kde_create with one more number, the
+ * bandwidth sensitivity alpha in [0, 1] (SXMC_ERR_INVALID otherwise, or when not finite).  alpha == 0 IS
+ * sxmc_kde_create: the same kernels, the same row layout, the same bits.  For alpha > 0 every table row i gets a
+ * factor lambda_i on all its bandwidths, fixed at creation on the UNTRANSFORMED table, after the Scott bandwidths h_d:
+ *   pilot   S0 = the n untransformed samples inside the domain.  For every table row i (inside the domain or not), in
+ *           f64 on the device:  f_i = (1/n) sum_{j in S0} w_j prod_d phi((x_id - x_jd)/h_d)/h_d,
+ *           w_j = 1 / prod_d [Phi((upper_d - x_jd)/h_d) - Phi((lower_d - x_jd)/h_d)] -- the evaluator's own
+ *           fixed-bandwidth PDF at zero systematics, continued by the same formula outside the domain.  The difference
+ *           x_id - x_jd is taken first, on the f64 values of the floats, then divided by h_d; Phi through erfc.
+ *   scale   g = exp((1/n) sum_{i in S0} ln f_i), on the host in f64, in table order (f_i > 0 on S0: a row's own term).
+ *   factors lambda_i = min(10, max(0.1, (f_i / g)^(-alpha))); a row whose f_i is not finite and positive takes 10.  The
+ *           clips bound how far the f32 coordinates of the pair sum are stretched.
+ * The factors belong to table rows: a sample keeps its lambda_i wherever the systematics move it, rows that start
+ * outside the domain and move in included.  Per evaluation, with s_i the moved samples and norm the in-domain count
+ * (unchanged: EvalHist's, bit for bit):
+ *   pdf(x) = (1/norm) sum_{i in domain} w_i prod_d phi((x_d - s_id)/(h_d lambda_i))/(h_d lambda_i),
+ *   w_i the truncation weight at bandwidth h_d lambda_i, so the integral over the domain is still exactly 1; point
+ *   codes, the NaN / 0 rules and norm == 0 as for sxmc_kde_create.
+ * sxmc_kde_random_sample draws coordinate d of an event that picked row i from N(s_id, (h_d lambda_i)^2) truncated to
+ * the domain (the same Philox words, counters, rounding and clamps); sxmc_kde_project uses, per sample and bin,
+ *   [Phi((t_j+1 - u_i)/lambda_i) - Phi((t_j - u_i)/lambda_i)] / [Phi((T - u_i)/lambda_i) - Phi(-u_i/lambda_i)].
+ * Deterministic: no floating-point atomics; the pilot's split over workgroups depends on n alone and the splits are
+ * added in order, so two creations, on any device, give the same lambda bits.
+ * Accuracy of a value: the bound of tests/kde_adaptive_reference.py; relative to the fixed-bandwidth bound the
+ * coordinate term grows by at most the largest 1/lambda_i^2 in reach of the point (<= 100 by the clips).
+ * Cost: one more multiply per pair than the fixed-bandwidth sum, rows of nobservables + 2 floats; the pilot is
+ * O(samples^2) in f64, once per creation. */
+int sxmc_kde_create_adaptive(const float* samples, size_t nsamples_floats, int samples_on_device,
+                             int nfields, int nobservables,
+                             const double* lower, size_t n_lower,
+                             const double* upper, size_t n_upper,
+                             const double* bandwidth_scale, size_t n_bandwidth_scale,
+                             unsigned dataset, double sensitivity, sxmc_kde_t* out);
+/* The sensitivity the evaluator was created with (0 for sxmc_kde_create). */
+int sxmc_kde_sensitivity(sxmc_kde_t k, double* sensitivity);
+/* lambda[0 .. nsamples): the factors fixed at creation, in table order; all 1.0 for a fixed-bandwidth evaluator.
+ * n must be nsamples. */
+int sxmc_kde_local_factors(sxmc_kde_t k, double* lambda, size_t n);
 /* A second evaluator over the SAME sample table as `base` (as sxmc_hist_create_shared: the table is shared and reference
- * counted, nothing is copied): systematics, bandwidths and prefactor copied from `base`; own rows, evaluation points,
- * bindings, partial sums and stream.  For concurrent experiments on one GPU.  May outlive `base`. */
+ * counted, nothing is copied): systematics, bandwidths, prefactor and (adaptive) the sensitivity and the factors copied
+ * from `base`, never recomputed; own rows, evaluation points, bindings, partial sums and stream.  For concurrent
+ * experiments on one GPU.  May outlive `base`. */
 int sxmc_kde_create_shared(sxmc_kde_t base, sxmc_kde_t* out);
 int sxmc_kde_destroy(sxmc_kde_t k);
 /* As sxmc_hist_add_systematic.  SXMC_ERR_INVALID beyond 7 columns (observables + fields systematics read) or 64

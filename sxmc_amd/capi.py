@@ -107,6 +107,9 @@ SIGNATURES = {
     "sxmc_hist_optimize": [_vp],
     "sxmc_hist_launch_info": [_vp, C.c_char_p, _sz],
     "sxmc_kde_create": [_vp, _sz, _i, _i, _i, _vp, _sz, _vp, _sz, _vp, _sz, _u, _pvp],
+    "sxmc_kde_create_adaptive": [_vp, _sz, _i, _i, _i, _vp, _sz, _vp, _sz, _vp, _sz, _u, _d, _pvp],
+    "sxmc_kde_sensitivity": [_vp, _pd],
+    "sxmc_kde_local_factors": [_vp, _vp, _sz],
     "sxmc_kde_destroy": [_vp],
     "sxmc_kde_add_systematic": [_vp, _i, _i, _i, _i, _vp],
     "sxmc_kde_set_eval_points": [_vp, _vp, _sz],

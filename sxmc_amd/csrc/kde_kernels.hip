@@ -14,6 +14,12 @@
 //                 codes of EvalHist::SetEvalPoints (-1 NaN, -2 zero); norm == 0 gives NaN.
 // No floating-point atomics and no order that depends on timing: two evaluations give the same bits.
 // Sampling (sxmc_kde_random_sample) and the projection onto one observable (sxmc_kde_project) follow the evaluation.
+//
+// Adaptive evaluators (bandwidth sensitivity > 0, sxmc_kde_create_adaptive) give every table row i a factor lambda_i on
+// the bandwidths, fixed at construction by kde_pilot (at the end of this file) and kept in d_lambda.  Their prepass
+// (ADAPT = true) writes rows of D + 2 floats -- the same c_d in units of the global h_d, g_i = 1 / lambda_i^2 and
+// W_i = w_i / lambda_i^D with the mass taken at h_d lambda_i -- and kde_pairs_adaptive sums W_i exp2(-g_i q); the
+// sampler and the projection read lambda in f64.  A fixed-bandwidth evaluator never runs an ADAPT instantiation.
 #include <hip/hip_runtime.h>
 
 #include "nll_device.h"
@@ -29,7 +35,7 @@ using namespace sxfill;
 constexpr int kKdeTile = SXMC_KDE_TILE;   // samples per f32 partial sum (the sample rows are padded to a multiple)
 constexpr int kKdeBlock = 256;
 
-template <int NSLOT>
+template <int NSLOT, bool ADAPT>
 __global__ __launch_bounds__(kKdeBlock) void kde_prepass_kernel(const SxSignalDesc d, const SxKdeArgs a) {
   const unsigned tid = threadIdx.x;
   const unsigned lane = tid & (kWave - 1);
@@ -61,16 +67,29 @@ __global__ __launch_bounds__(kKdeBlock) void kde_prepass_kernel(const SxSignalDe
     cnt += in ? 1u : 0u;
     if (i < a.npad) {
       double mass = 1.0;
-      float* row = a.rows + i * (unsigned long long)(d.nobs + 1);
+      float* row = a.rows + i * (unsigned long long)(d.nobs + (ADAPT ? 2 : 1));
+      double lam = 1.0, lam_pow = 1.0;   // (ADAPT) the row's factor and lambda^D
+      if constexpr (ADAPT) lam = a.lambda[i];
 #pragma unroll
       for (int k = 0; k < D; k++) {
         if (k >= d.nobs) continue;
         const double x = in ? f[k][q] : a.lower[k];
         // Phi(z) = erfc(-z / sqrt 2) / 2 with z = (edge - x) / h
-        mass = mass * (0.5 * (erfc((x - a.upper[k]) * a.inv_h_sqrt2[k]) - erfc((x - a.lower[k]) * a.inv_h_sqrt2[k])));
+        if constexpr (ADAPT) {
+          const double r = a.inv_h_sqrt2[k] / lam;   // 1 / (h lambda sqrt 2)
+          mass = mass * (0.5 * (erfc((x - a.upper[k]) * r) - erfc((x - a.lower[k]) * r)));
+          lam_pow = lam_pow * lam;
+        } else {
+          mass = mass * (0.5 * (erfc((x - a.upper[k]) * a.inv_h_sqrt2[k]) - erfc((x - a.lower[k]) * a.inv_h_sqrt2[k])));
+        }
         row[k] = in ? (float)((x - a.lower[k]) * a.cscale[k]) : 0.0f;
       }
-      row[d.nobs] = in ? (float)(1.0 / mass) : 0.0f;
+      if constexpr (ADAPT) {
+        row[d.nobs] = (float)(1.0 / (lam * lam));
+        row[d.nobs + 1] = in ? (float)(1.0 / (mass * lam_pow)) : 0.0f;
+      } else {
+        row[d.nobs] = in ? (float)(1.0 / mass) : 0.0f;
+      }
     }
   }
 #pragma unroll
@@ -111,6 +130,41 @@ __global__ __launch_bounds__(kKdeBlock) void kde_pairs_kernel(const float* __res
   part[(unsigned long long)blockIdx.y * pitch + i] = sum;
 }
 
+// The adaptive pair sum: rows of D + 2 floats (c_d, g = 1 / lambda^2, W = w / lambda^D) and the term W exp2(-g q) -- one
+// multiply more per pair than kde_pairs_kernel; everything else as there.
+template <int D>
+__global__ __launch_bounds__(kKdeBlock) void kde_pairs_adaptive_kernel(const float* __restrict__ pts,
+                                                                       unsigned long long pitch,
+                                                                       const float* __restrict__ rows,
+                                                                       unsigned tiles_per_split, unsigned ntiles,
+                                                                       double* __restrict__ part) {
+  const unsigned long long i = (unsigned long long)blockIdx.x * kKdeBlock + threadIdx.x;
+  float p[D];
+#pragma unroll
+  for (int k = 0; k < D; k++) p[k] = pts[(unsigned long long)k * pitch + i];
+  const unsigned t0 = blockIdx.y * tiles_per_split;
+  const unsigned t1 = t0 + tiles_per_split < ntiles ? t0 + tiles_per_split : ntiles;
+  double sum = 0.0;
+  for (unsigned t = t0; t < t1; t++) {
+    const float* s = rows + (unsigned long long)t * kKdeTile * (D + 2);
+    float acc = 0.0f;
+#pragma unroll 16
+    for (int j = 0; j < kKdeTile; j++) {
+      const float* r = s + j * (D + 2);
+      const float a0 = p[0] - r[0];
+      float q = a0 * a0;
+#pragma unroll
+      for (int k = 1; k < D; k++) {
+        const float ak = p[k] - r[k];
+        q = __builtin_fmaf(ak, ak, q);
+      }
+      acc = __builtin_fmaf(r[D + 1], __builtin_amdgcn_exp2f(-(r[D] * q)), acc);
+    }
+    sum += (double)acc;
+  }
+  part[(unsigned long long)blockIdx.y * pitch + i] = sum;
+}
+
 __global__ __launch_bounds__(kKdeBlock) void kde_combine_kernel(const double* __restrict__ part, unsigned long long pitch,
                                                                 int nsplit, unsigned long long npoints,
                                                                 const int* __restrict__ codes,
@@ -139,14 +193,17 @@ hipError_t sx_kde_prepass(const SxSignalDesc& d, const SxKdeArgs& a, hipStream_t
   const unsigned long long nvec = a.npad / SXMC_VEC;
   const unsigned grid = (unsigned)((nvec + kKdeBlock - 1) / kKdeBlock);
   if (grid == 0) return hipSuccess;
+#define SX_KDE_CASE(N)                                                                                       \
+  case N:                                                                                                    \
+    if (a.lambda) hipLaunchKernelGGL((kde_prepass_kernel<N, true>), dim3(grid), dim3(kKdeBlock), 0, s, d, a); \
+    else hipLaunchKernelGGL((kde_prepass_kernel<N, false>), dim3(grid), dim3(kKdeBlock), 0, s, d, a);         \
+    break;
   switch (d.nslot) {
-#define SX_KDE_CASE(N) \
-  case N: hipLaunchKernelGGL(kde_prepass_kernel<N>, dim3(grid), dim3(kKdeBlock), 0, s, d, a); break;
     SX_KDE_CASE(1) SX_KDE_CASE(2) SX_KDE_CASE(3) SX_KDE_CASE(4) SX_KDE_CASE(5) SX_KDE_CASE(6) SX_KDE_CASE(7)
-#undef SX_KDE_CASE
     default:
       return hipErrorInvalidValue;
   }
+#undef SX_KDE_CASE
   return hipGetLastError();
 }
 
@@ -158,6 +215,19 @@ hipError_t sx_kde_pairs(int D, const float* pts, unsigned long long pitch, const
     case 2: hipLaunchKernelGGL(kde_pairs_kernel<2>, grid, dim3(kKdeBlock), 0, s, pts, pitch, rows, tiles_per_split, ntiles, part); break;
     case 3: hipLaunchKernelGGL(kde_pairs_kernel<3>, grid, dim3(kKdeBlock), 0, s, pts, pitch, rows, tiles_per_split, ntiles, part); break;
     case 4: hipLaunchKernelGGL(kde_pairs_kernel<4>, grid, dim3(kKdeBlock), 0, s, pts, pitch, rows, tiles_per_split, ntiles, part); break;
+    default: return hipErrorInvalidValue;
+  }
+  return hipGetLastError();
+}
+
+hipError_t sx_kde_pairs_adaptive(int D, const float* pts, unsigned long long pitch, const float* rows,
+                                 unsigned tiles_per_split, unsigned ntiles, int nsplit, double* part, hipStream_t s) {
+  const dim3 grid((unsigned)(pitch / kKdeBlock), (unsigned)nsplit);
+  switch (D) {
+    case 1: hipLaunchKernelGGL(kde_pairs_adaptive_kernel<1>, grid, dim3(kKdeBlock), 0, s, pts, pitch, rows, tiles_per_split, ntiles, part); break;
+    case 2: hipLaunchKernelGGL(kde_pairs_adaptive_kernel<2>, grid, dim3(kKdeBlock), 0, s, pts, pitch, rows, tiles_per_split, ntiles, part); break;
+    case 3: hipLaunchKernelGGL(kde_pairs_adaptive_kernel<3>, grid, dim3(kKdeBlock), 0, s, pts, pitch, rows, tiles_per_split, ntiles, part); break;
+    case 4: hipLaunchKernelGGL(kde_pairs_adaptive_kernel<4>, grid, dim3(kKdeBlock), 0, s, pts, pitch, rows, tiles_per_split, ntiles, part); break;
     default: return hipErrorInvalidValue;
   }
   return hipGetLastError();
@@ -180,11 +250,12 @@ hipError_t sx_kde_combine(const double* part, unsigned long long pitch, int nspl
 // around its centre truncated to [lower, upper), drawn by the inverse CDF in f64.
 namespace {
 
-__global__ __launch_bounds__(kKdeBlock) void kde_flag_kernel(const float* __restrict__ rows, int D,
+// rowlen floats to a row, the weight last (D + 1, or D + 2 for an adaptive evaluator)
+__global__ __launch_bounds__(kKdeBlock) void kde_flag_kernel(const float* __restrict__ rows, int rowlen,
                                                              unsigned long long npad, unsigned* __restrict__ flag) {
   const unsigned long long i = (unsigned long long)blockIdx.x * kKdeBlock + threadIdx.x;
   if (i >= npad) return;
-  flag[i] = rows[i * (unsigned long long)(D + 1) + (unsigned long long)D] > 0.0f ? 1u : 0u;
+  flag[i] = rows[i * (unsigned long long)rowlen + (unsigned long long)(rowlen - 1)] > 0.0f ? 1u : 0u;
 }
 
 __global__ __launch_bounds__(kKdeBlock) void kde_scatter_kernel(const unsigned* __restrict__ flag,
@@ -199,8 +270,9 @@ __global__ __launch_bounds__(kKdeBlock) void kde_scatter_kernel(const unsigned* 
 __device__ __forceinline__ double kde_phi(double z) { return 0.5 * erfc(-z * 0.70710678118654752); }
 __device__ __forceinline__ double kde_phi_inv(double p) { return -1.4142135623730950 * erfcinv(2.0 * p); }
 
-template <int D>
+template <int D, bool ADAPT>
 __global__ __launch_bounds__(kKdeBlock) void kde_sample_kernel(const float* __restrict__ rows,
+                                                               const double* __restrict__ lambda,
                                                                const unsigned* __restrict__ idx, unsigned n,
                                                                const SxKdeSampleArgs g, unsigned long long seed,
                                                                unsigned long long nevents, float* __restrict__ out,
@@ -214,12 +286,15 @@ __global__ __launch_bounds__(kKdeBlock) void kde_sample_kernel(const float* __re
       const sxdev::Philox4 r1 = sxdev::philox4x32_10(e, 2ull * attempt + 1ull, seed);
       const unsigned u[4] = {r0.y, r0.z, r0.w, r1.x};
       const unsigned i = idx[(unsigned)(((unsigned long long)r0.x * n) >> 32)];   // uniform over the n rows
-      const float* row = rows + (unsigned long long)i * (D + 1);
+      const float* row = rows + (unsigned long long)i * (D + (ADAPT ? 2 : 1));
+      double lam = 1.0;   // (ADAPT) the picked row's factor on every bandwidth
+      if constexpr (ADAPT) lam = lambda[i];
       bool ok = true;
 #pragma unroll
       for (int k = 0; k < D; k++) {
         const double s = g.lower[k] + (double)row[k] * g.inv_cscale[k];   // the moved sample, from its scaled row
-        const double h = g.h[k];
+        double h = g.h[k];
+        if constexpr (ADAPT) h = h * lam;
         // truncated to [lower, upper): alpha = (lower - s) / h <= 0 < beta = (upper - s) / h.  The lower tail mass
         // pa = Phi(alpha), the upper tail mass qb = Phi(-beta), both accurate; a draw left of the median inverts
         // p = pa + u m, one right of it q = qb + (1 - u) m, so that neither tail is taken as 1 - (a number near 1)
@@ -257,11 +332,11 @@ __global__ __launch_bounds__(kKdeBlock) void kde_sample_kernel(const float* __re
 }  // namespace
 
 // the in-domain rows of the last evaluation, in table order: idx[0 .. pos[npad - 1])
-hipError_t sx_kde_compact(const float* rows, int D, unsigned long long npad, unsigned* flag, unsigned* pos,
+hipError_t sx_kde_compact(const float* rows, int rowlen, unsigned long long npad, unsigned* flag, unsigned* pos,
                           unsigned* idx, void* temp, size_t temp_bytes, hipStream_t s) {
   if (npad == 0) return hipSuccess;
   const unsigned grid = (unsigned)((npad + kKdeBlock - 1) / kKdeBlock);
-  hipLaunchKernelGGL(kde_flag_kernel, dim3(grid), dim3(kKdeBlock), 0, s, rows, D, npad, flag);
+  hipLaunchKernelGGL(kde_flag_kernel, dim3(grid), dim3(kKdeBlock), 0, s, rows, rowlen, npad, flag);
   hipError_t e = hipGetLastError();
   if (e != hipSuccess) return e;
   e = sx_inclusive_sum_u32(flag, pos, (int)npad, temp, temp_bytes, s);
@@ -270,19 +345,24 @@ hipError_t sx_kde_compact(const float* rows, int D, unsigned long long npad, uns
   return hipGetLastError();
 }
 
-hipError_t sx_kde_sample(int D, const float* rows, const unsigned* idx, unsigned n, const SxKdeSampleArgs& g,
-                         unsigned long long seed, unsigned long long nevents, float* out, unsigned* exhausted,
-                         hipStream_t s) {
+hipError_t sx_kde_sample(int D, const float* rows, const double* lambda, const unsigned* idx, unsigned n,
+                         const SxKdeSampleArgs& g, unsigned long long seed, unsigned long long nevents, float* out,
+                         unsigned* exhausted, hipStream_t s) {
   if (nevents == 0) return hipSuccess;
   const unsigned long long b = (nevents + kKdeBlock - 1) / kKdeBlock;
   const dim3 grid((unsigned)(b < 4096 ? b : 4096));
+#define SX_KDE_CASE(N)                                                                                              \
+  case N:                                                                                                           \
+    if (lambda) hipLaunchKernelGGL((kde_sample_kernel<N, true>), grid, dim3(kKdeBlock), 0, s, rows, lambda, idx, n, g, \
+                                   seed, nevents, out, exhausted);                                                  \
+    else hipLaunchKernelGGL((kde_sample_kernel<N, false>), grid, dim3(kKdeBlock), 0, s, rows, lambda, idx, n, g, seed, \
+                            nevents, out, exhausted);                                                               \
+    break;
   switch (D) {
-    case 1: hipLaunchKernelGGL(kde_sample_kernel<1>, grid, dim3(kKdeBlock), 0, s, rows, idx, n, g, seed, nevents, out, exhausted); break;
-    case 2: hipLaunchKernelGGL(kde_sample_kernel<2>, grid, dim3(kKdeBlock), 0, s, rows, idx, n, g, seed, nevents, out, exhausted); break;
-    case 3: hipLaunchKernelGGL(kde_sample_kernel<3>, grid, dim3(kKdeBlock), 0, s, rows, idx, n, g, seed, nevents, out, exhausted); break;
-    case 4: hipLaunchKernelGGL(kde_sample_kernel<4>, grid, dim3(kKdeBlock), 0, s, rows, idx, n, g, seed, nevents, out, exhausted); break;
+    SX_KDE_CASE(1) SX_KDE_CASE(2) SX_KDE_CASE(3) SX_KDE_CASE(4)
     default: return hipErrorInvalidValue;
   }
+#undef SX_KDE_CASE
   return hipGetLastError();
 }
 
@@ -298,6 +378,9 @@ hipError_t sx_kde_sample(int D, const float* rows, const unsigned* idx, unsigned
 // f64 throughout, Phi through erfc as kde_prepass and kde_sample write it; no floating-point atomics.
 namespace {
 
+// ADAPT (an adaptive evaluator): rows of D + 2 floats, and per sample three scratch doubles -- u, the reciprocal mass
+// taken at the sample's own bandwidth h lambda, and 1 / lambda, which scales every distance of the kernel below.
+template <bool ADAPT>
 __global__ __launch_bounds__(kKdeBlock) void kde_project_prep_kernel(const float* __restrict__ rows,
                                                                      const SxKdeProjectArgs a,
                                                                      double* __restrict__ scratch,
@@ -305,16 +388,25 @@ __global__ __launch_bounds__(kKdeBlock) void kde_project_prep_kernel(const float
   const unsigned long long i = (unsigned long long)blockIdx.x * kKdeBlock + threadIdx.x;
   unsigned in = 0u;
   if (i < a.npad) {
-    const float* row = rows + i * (unsigned long long)(a.D + 1);
-    double u = 0.0, inv = 0.0;
-    if (row[a.D] > 0.0f) {
+    constexpr int kExtra = ADAPT ? 2 : 1;
+    const float* row = rows + i * (unsigned long long)(a.D + kExtra);
+    double u = 0.0, inv = 0.0, il = 1.0;
+    if constexpr (ADAPT) il = 1.0 / a.lambda[i];
+    if (row[a.D + kExtra - 1] > 0.0f) {
       in = 1u;
       u = (double)row[a.obs] / a.cunit;
       const double T = (a.upper - a.lower) / a.h;
-      inv = 1.0 / (kde_phi(T - u) - kde_phi(-u));
+      if constexpr (ADAPT) inv = 1.0 / (kde_phi((T - u) * il) - kde_phi(-u * il));
+      else inv = 1.0 / (kde_phi(T - u) - kde_phi(-u));
     }
-    scratch[2ull * i] = u;
-    scratch[2ull * i + 1ull] = inv;
+    if constexpr (ADAPT) {
+      scratch[3ull * i] = u;
+      scratch[3ull * i + 1ull] = inv;
+      scratch[3ull * i + 2ull] = il;
+    } else {
+      scratch[2ull * i] = u;
+      scratch[2ull * i + 1ull] = inv;
+    }
   }
   // (every lane of the wave gets here)
 #pragma unroll
@@ -332,6 +424,7 @@ __device__ __forceinline__ double kde_project_edge(const SxKdeProjectArgs& a, un
   return (e - a.lower) / a.h;
 }
 
+template <bool ADAPT>
 __global__ __launch_bounds__(SXMC_KDE_PROJ_LANES) void kde_project_kernel(const SxKdeProjectArgs a,
                                                                           const double* __restrict__ scratch,
                                                                           double* __restrict__ part) {
@@ -343,10 +436,16 @@ __global__ __launch_bounds__(SXMC_KDE_PROJ_LANES) void kde_project_kernel(const 
   const unsigned long long r1 = r0 + a.rows_per_split < a.npad ? r0 + a.rows_per_split : a.npad;
   double sum = 0.0;
   for (unsigned long long i = r0; i < r1; i++) {
-    const double u = scratch[2ull * i];
-    const double inv = scratch[2ull * i + 1ull];
+    constexpr unsigned long long kPer = ADAPT ? 3ull : 2ull;
+    const double u = scratch[kPer * i];
+    const double inv = scratch[kPer * i + 1ull];
     if (inv == 0.0) continue;   // (wave-uniform: a row outside the domain)
-    sum += (kde_phi(t1 - u) - kde_phi(t0 - u)) * inv;
+    if constexpr (ADAPT) {
+      const double il = scratch[kPer * i + 2ull];
+      sum += (kde_phi((t1 - u) * il) - kde_phi((t0 - u) * il)) * inv;
+    } else {
+      sum += (kde_phi(t1 - u) - kde_phi(t0 - u)) * inv;
+    }
   }
   part[(unsigned long long)blockIdx.y * a.pitch + lane] = sum;
 }
@@ -372,16 +471,82 @@ hipError_t sx_kde_project(const float* rows, const SxKdeProjectArgs& a, double* 
       a.pitch < (unsigned long long)a.nbins) {
     return hipErrorInvalidValue;
   }
-  double* part = scratch + 2ull * a.npad;
-  hipLaunchKernelGGL(kde_project_prep_kernel, dim3((unsigned)((a.npad + kKdeBlock - 1) / kKdeBlock)), dim3(kKdeBlock), 0,
-                     s, rows, a, scratch, count);
+  double* part = scratch + (a.lambda ? 3ull : 2ull) * a.npad;
+  const dim3 prep((unsigned)((a.npad + kKdeBlock - 1) / kKdeBlock));
+  if (a.lambda) hipLaunchKernelGGL(kde_project_prep_kernel<true>, prep, dim3(kKdeBlock), 0, s, rows, a, scratch, count);
+  else hipLaunchKernelGGL(kde_project_prep_kernel<false>, prep, dim3(kKdeBlock), 0, s, rows, a, scratch, count);
   hipError_t e = hipGetLastError();
   if (e != hipSuccess) return e;
-  hipLaunchKernelGGL(kde_project_kernel, dim3((unsigned)(a.pitch / SXMC_KDE_PROJ_LANES), a.nsplit),
-                     dim3(SXMC_KDE_PROJ_LANES), 0, s, a, scratch, part);
+  const dim3 grid((unsigned)(a.pitch / SXMC_KDE_PROJ_LANES), a.nsplit);
+  if (a.lambda) hipLaunchKernelGGL(kde_project_kernel<true>, grid, dim3(SXMC_KDE_PROJ_LANES), 0, s, a, scratch, part);
+  else hipLaunchKernelGGL(kde_project_kernel<false>, grid, dim3(SXMC_KDE_PROJ_LANES), 0, s, a, scratch, part);
   e = hipGetLastError();
   if (e != hipSuccess) return e;
   hipLaunchKernelGGL(kde_project_combine_kernel, dim3((unsigned)(((unsigned long long)a.nbins + kKdeBlock - 1) / kKdeBlock)),
                      dim3(kKdeBlock), 0, s, a, part, count, d_prob);
+  return hipGetLastError();
+}
+
+// ------------------------------------------------------------------------------------ pilot (sxmc_kde_create_adaptive)
+// The fixed-bandwidth PDF at zero systematics taken at every table row, in f64, once per construction:
+//   f_i = (1/n) sum_{j in S0} w_j prod_d phi((x_id - x_jd) / h_d) / h_d
+// kde_project_kernel's shape: one lane per table row, the n in-domain samples wave-uniform (scalar loads of D
+// coordinates and the weight), split across workgroups (blockIdx.y) by a rule that reads the sample count alone;
+// kde_pilot_combine adds the splits in their order.  No floating-point atomics: the same bits on every device.
+namespace {
+
+template <int D>
+__global__ __launch_bounds__(kKdeBlock) void kde_pilot_kernel(const SxKdePilotArgs a, const double* __restrict__ x,
+                                                              const double* __restrict__ s0,
+                                                              double* __restrict__ part) {
+  const unsigned long long i = (unsigned long long)blockIdx.x * kKdeBlock + threadIdx.x;   // < pitch (whole blocks)
+  double p[D];
+#pragma unroll
+  for (int k = 0; k < D; k++) p[k] = x[(unsigned long long)k * a.pitch + i];
+  const unsigned long long j0 = (unsigned long long)blockIdx.y * a.per_split;
+  const unsigned long long j1 = j0 + a.per_split < a.n ? j0 + a.per_split : a.n;
+  double sum = 0.0;
+  for (unsigned long long j = j0; j < j1; j++) {
+    const double* r = s0 + j * (unsigned long long)(D + 1);
+    double q = 0.0;
+#pragma unroll
+    for (int k = 0; k < D; k++) {
+      const double z = (p[k] - r[k]) / a.h[k];   // the difference first, then the bandwidth
+      q = q + z * z;
+    }
+    sum += r[D] * exp(-0.5 * q);
+  }
+  part[(unsigned long long)blockIdx.y * a.pitch + i] = sum;
+}
+
+__global__ __launch_bounds__(kKdeBlock) void kde_pilot_combine_kernel(const SxKdePilotArgs a,
+                                                                      const double* __restrict__ part,
+                                                                      double* __restrict__ f) {
+  const unsigned long long i = (unsigned long long)blockIdx.x * kKdeBlock + threadIdx.x;
+  if (i >= a.pitch) return;
+  double s = 0.0;
+  for (unsigned k = 0; k < a.nsplit; k++) s += part[(unsigned long long)k * a.pitch + i];
+  f[i] = s * a.prefactor / (double)a.n;
+}
+
+}  // namespace
+
+hipError_t sx_kde_pilot(const SxKdePilotArgs& a, const double* x, const double* s0, double* part, double* f,
+                        hipStream_t s) {
+  if (a.pitch == 0 || a.pitch % kKdeBlock != 0 || a.n == 0 || a.per_split == 0 ||
+      (unsigned long long)a.nsplit * a.per_split < a.n) {
+    return hipErrorInvalidValue;
+  }
+  const dim3 grid((unsigned)(a.pitch / kKdeBlock), a.nsplit);
+  switch (a.D) {
+    case 1: hipLaunchKernelGGL(kde_pilot_kernel<1>, grid, dim3(kKdeBlock), 0, s, a, x, s0, part); break;
+    case 2: hipLaunchKernelGGL(kde_pilot_kernel<2>, grid, dim3(kKdeBlock), 0, s, a, x, s0, part); break;
+    case 3: hipLaunchKernelGGL(kde_pilot_kernel<3>, grid, dim3(kKdeBlock), 0, s, a, x, s0, part); break;
+    case 4: hipLaunchKernelGGL(kde_pilot_kernel<4>, grid, dim3(kKdeBlock), 0, s, a, x, s0, part); break;
+    default: return hipErrorInvalidValue;
+  }
+  hipError_t e = hipGetLastError();
+  if (e != hipSuccess) return e;
+  hipLaunchKernelGGL(kde_pilot_combine_kernel, dim3((unsigned)(a.pitch / kKdeBlock)), dim3(kKdeBlock), 0, s, a, part, f);
   return hipGetLastError();
 }

@@ -214,11 +214,17 @@ struct SxKdeArgs {
   double upper[SXMC_KDE_MAX_DIM];
   double cscale[SXMC_KDE_MAX_DIM];       // sqrt(log2(e) / 2) / h
   double inv_h_sqrt2[SXMC_KDE_MAX_DIM];  // 1 / (h sqrt 2)
+  // an adaptive evaluator's factors, [npad] (1.0 in the padding), or null.  With them the rows are D + 2 floats: the
+  // same coordinates, 1 / lambda^2 and weight / lambda^D, the mass taken at h lambda.
+  const double* lambda;
 };
 hipError_t sx_kde_prepass(const SxSignalDesc& d, const SxKdeArgs& a, hipStream_t s);
 // pts: [D][pitch] scaled point coordinates, pitch a multiple of 256; part: [nsplit][pitch]
 hipError_t sx_kde_pairs(int D, const float* pts, unsigned long long pitch, const float* rows, unsigned tiles_per_split,
                         unsigned ntiles, int nsplit, double* part, hipStream_t s);
+// rows of D + 2 floats (an adaptive evaluator's prepass); the rest as sx_kde_pairs
+hipError_t sx_kde_pairs_adaptive(int D, const float* pts, unsigned long long pitch, const float* rows,
+                                 unsigned tiles_per_split, unsigned ntiles, int nsplit, double* part, hipStream_t s);
 hipError_t sx_kde_combine(const double* part, unsigned long long pitch, int nsplit, unsigned long long npoints,
                           const int* codes, const unsigned* norm, double prefactor, float* out, long stride,
                           hipStream_t s);
@@ -236,14 +242,16 @@ struct SxKdeSampleArgs {
   int has_cuts;
   float dataset;
 };
-hipError_t sx_kde_compact(const float* rows, int D, unsigned long long npad, unsigned* flag, unsigned* pos,
+// rowlen: floats to a sample row, the weight last.
+hipError_t sx_kde_compact(const float* rows, int rowlen, unsigned long long npad, unsigned* flag, unsigned* pos,
                           unsigned* idx, void* temp, size_t temp_bytes, hipStream_t s);
 // inclusive prefix sum of n unsigned (layout_kernels.hip); temp == nullptr: temp_bytes receives the scratch it needs
 hipError_t sx_inclusive_sum_u32(const unsigned* d_in, unsigned* d_out, int n, void* temp, size_t& temp_bytes,
                                 hipStream_t s);
-hipError_t sx_kde_sample(int D, const float* rows, const unsigned* idx, unsigned n, const SxKdeSampleArgs& g,
-                         unsigned long long seed, unsigned long long nevents, float* out, unsigned* exhausted,
-                         hipStream_t s);
+// lambda: an adaptive evaluator's factors per table row (rows of D + 2 floats then), or null (rows of D + 1).
+hipError_t sx_kde_sample(int D, const float* rows, const double* lambda, const unsigned* idx, unsigned n,
+                         const SxKdeSampleArgs& g, unsigned long long seed, unsigned long long nevents, float* out,
+                         unsigned* exhausted, hipStream_t s);
 // Projection onto one observable (sxmc_kde_project; the arithmetic is written out in include/sxmc_hip.h).  scratch:
 // [2 npad] doubles (u and the reciprocal mass of every sample row), then [nsplit][pitch] partial sums, pitch = the bins
 // rounded up to SXMC_KDE_PROJ_LANES; count: the in-domain rows, zero on entry.  rows_per_split sample rows to a
@@ -257,6 +265,22 @@ struct SxKdeProjectArgs {
   double lower, upper;      // of the observable
   double h;                 // its bandwidth
   double cunit;             // sqrt(log2(e) / 2): a row's coordinate is (s - lower) / h times this
+  const double* lambda;     // an adaptive evaluator's factors, [npad], or null.  With them rows are D + 2 floats and
+                            // the per-row scratch is [3 npad]: u, the reciprocal mass at h lambda, 1 / lambda
 };
 hipError_t sx_kde_project(const float* rows, const SxKdeProjectArgs& a, double* scratch, unsigned* count, double* d_prob,
                           hipStream_t s);
+// The pilot of an adaptive evaluator (sxmc_kde_create_adaptive): the fixed-bandwidth PDF at zero systematics at every
+// table row, in f64.  x: [D][pitch] the rows' observables (pitch a multiple of 256, padded with anything finite);
+// s0: [n][D + 1] the in-domain samples and their truncation weights, in table order; part: [nsplit][pitch];
+// f: [pitch] the result.  per_split samples to a workgroup, set from n alone; the splits are added in their order.
+struct SxKdePilotArgs {
+  int D;
+  unsigned long long pitch;
+  unsigned long long n;
+  unsigned per_split, nsplit;
+  double h[SXMC_KDE_MAX_DIM];
+  double prefactor;         // 1 / ((2 pi)^(D/2) prod h)
+};
+hipError_t sx_kde_pilot(const SxKdePilotArgs& a, const double* x, const double* s0, double* part, double* f,
+                        hipStream_t s);

@@ -5,7 +5,14 @@
 // internal histogram evaluator with one bin per observable that is never evaluated itself -- it uploads the table
 // column-major, checks and packs the systematics, and gives the fill's descriptor (fill_desc), which the prepass reads
 // with the fill's own arithmetic.  So the norm is the histogram's, bit for bit.
+//
+// Adaptive bandwidths (sxmc_kde_create_adaptive, sensitivity > 0): the factors lambda of the table rows are fixed at
+// creation -- the pilot on the device, g and lambda on the host (kde_adaptive.h) -- and kept in d_lambda; with them the
+// rows are D + 2 floats and every launch takes its adaptive form.  At sensitivity 0 d_lambda is null and every launch
+// is the fixed-bandwidth one.
 #include "sxmc_host.h"
+
+#include "kde_adaptive.h"
 
 #include <limits>
 
@@ -18,7 +25,12 @@ struct sxmc_kde {
   size_t npad = 0;                 // sample rows, a multiple of SXMC_KDE_TILE
   double bw[SXMC_KDE_MAX_DIM] = {0};
   double prefactor = 0;            // 1 / ((2 pi)^(D/2) prod h)
-  float* d_rows = nullptr;         // [npad][D + 1]: scaled coordinates, weight
+  float* d_rows = nullptr;         // [npad][D + 1]: scaled coordinates, weight; adaptive: [npad][D + 2] (rowlen())
+  // adaptive bandwidths (sxmc_kde_create_adaptive): nothing of it is set or read at sensitivity 0
+  double sensitivity = 0;
+  double* d_lambda = nullptr;      // [npad] the factors of the table rows, 1.0 in the padding; null when fixed
+  std::vector<double> lambda;      // [nsamples] the same on the host
+  int rowlen() const { return D + (d_lambda ? 2 : 1); }
   // evaluation points
   bool has_points = false;
   size_t npoints = 0, pitch = 0, cap_pitch = 0;
@@ -75,24 +87,81 @@ void choose_split(size_t pitch, size_t ntiles, int cus, int& nsplit, unsigned& t
 // The cleared sample rows of a new evaluator that has its table (k->h) and npad.  On failure the table goes too: the
 // caller only drops k.
 int alloc_rows(sxmc_kde* k, const char* what) {
-  const size_t bytes = sizeof(float) * k->npad * (size_t)(k->D + 1);
+  const size_t bytes = sizeof(float) * k->npad * (size_t)k->rowlen();
   hipError_t e = hipMalloc((void**)&k->d_rows, bytes);
   if (e == hipSuccess) e = hipMemset(k->d_rows, 0, bytes);
   if (e == hipSuccess) return SXMC_OK;
   if (k->d_rows) (void)hipFree(k->d_rows);
+  if (k->d_lambda) (void)hipFree(k->d_lambda);
   sxmc_hist_destroy(k->h);
   return fail(SXMC_ERR_HIP, std::string(what) + hipGetErrorString(e));
 }
 
-}  // namespace
+// Device memory of one call, freed when it returns.
+struct Scratch {
+  void* p = nullptr;
+  ~Scratch() {
+    if (p) (void)hipFree(p);
+  }
+  hipError_t alloc(size_t bytes) { return hipMalloc(&p, bytes); }
+  double* f64() const { return static_cast<double*>(p); }
+};
 
-extern "C" {
+// The factors of an adaptive evaluator that has its table, bandwidths and npad: the pilot on the device (kde_pilot),
+// then g and lambda on the host in f64 (kde_adaptive.h) and the upload of d_lambda.  rows: the untransformed table on
+// the host; inside: its in-domain rows in table order.
+int set_local_factors(sxmc_kde* k, const float* rows, int nfields, const std::vector<size_t>& inside) {
+  const int D = k->D;
+  const size_t n = inside.size(), pitch = k->npad;
+  SxKdePilotArgs a;
+  std::memset(&a, 0, sizeof a);
+  a.D = D;
+  a.pitch = pitch;
+  a.n = n;
+  sxkde::pilot_split(n, a.per_split, a.nsplit);
+  for (int d = 0; d < D; d++) a.h[d] = k->bw[d];
+  a.prefactor = k->prefactor;
+  std::vector<double> x((size_t)D * pitch, 0.0), s0(n * (size_t)(D + 1));
+  for (size_t i = 0; i < k->nsamples; i++) {
+    for (int d = 0; d < D; d++) x[(size_t)d * pitch + i] = (double)rows[i * (size_t)nfields + (size_t)d];
+  }
+  for (size_t j = 0; j < n; j++) {
+    double mass = 1.0;
+    for (int d = 0; d < D; d++) {
+      const double v = (double)rows[inside[j] * (size_t)nfields + (size_t)d];
+      const double r = 1.0 / (k->bw[d] * M_SQRT2);
+      // (as the prepass writes it)
+      mass = mass * (0.5 * (std::erfc((v - k->h->upper[(size_t)d]) * r) - std::erfc((v - k->h->lower[(size_t)d]) * r)));
+      s0[j * (size_t)(D + 1) + (size_t)d] = v;
+    }
+    s0[j * (size_t)(D + 1) + (size_t)D] = 1.0 / mass;
+  }
+  Scratch dx, ds, dpart, df;
+  SX_HIP(dx.alloc(sizeof(double) * x.size()));
+  SX_HIP(ds.alloc(sizeof(double) * s0.size()));
+  SX_HIP(dpart.alloc(sizeof(double) * (size_t)a.nsplit * pitch));
+  SX_HIP(df.alloc(sizeof(double) * pitch));
+  const hipStream_t s = k->h->stream;
+  SX_HIP(hipMemcpyAsync(dx.p, x.data(), sizeof(double) * x.size(), hipMemcpyHostToDevice, s));
+  SX_HIP(hipMemcpyAsync(ds.p, s0.data(), sizeof(double) * s0.size(), hipMemcpyHostToDevice, s));
+  SX_HIP(sx_kde_pilot(a, dx.f64(), ds.f64(), dpart.f64(), df.f64(), s));
+  std::vector<double> f(pitch);
+  SX_HIP(hipMemcpyAsync(f.data(), df.p, sizeof(double) * pitch, hipMemcpyDeviceToHost, s));
+  SX_HIP(hipStreamSynchronize(s));
+  const double g = sxkde::pilot_scale(f.data(), inside);
+  std::vector<double> lam(pitch, 1.0);
+  for (size_t i = 0; i < k->nsamples; i++) lam[i] = sxkde::local_factor(f[i], g, k->sensitivity);
+  SX_HIP(hipMalloc((void**)&k->d_lambda, sizeof(double) * pitch));
+  SX_HIP(hipMemcpy(k->d_lambda, lam.data(), sizeof(double) * pitch, hipMemcpyHostToDevice));
+  lam.resize(k->nsamples);
+  k->lambda.swap(lam);
+  return SXMC_OK;
+}
 
-int sxmc_kde_create(const float* samples, size_t nsamples_floats, int samples_on_device, int nfields, int nobservables,
-                    const double* lower, size_t n_lower, const double* upper, size_t n_upper,
-                    const double* bandwidth_scale, size_t n_bandwidth_scale, unsigned dataset, sxmc_kde_t* out) {
-  SX_REQUIRE(out, "null argument");
-  *out = nullptr;
+// sxmc_kde_create (sensitivity 0: nothing adaptive is allocated or run) and sxmc_kde_create_adaptive
+int kde_create(const float* samples, size_t nsamples_floats, int samples_on_device, int nfields, int nobservables,
+               const double* lower, size_t n_lower, const double* upper, size_t n_upper, const double* bandwidth_scale,
+               size_t n_bandwidth_scale, unsigned dataset, double sensitivity, sxmc_kde_t* out) {
   // Eval::Eval validation, pdfz.cpp:64-82 (same order, same messages, as sxmc_hist_create)
   SX_REQUIRE(nfields > 0 && nsamples_floats % (size_t)nfields == 0,
              "Length of samples array is not divisible by number of fields.");
@@ -165,12 +234,45 @@ int sxmc_kde_create(const float* samples, size_t nsamples_floats, int samples_on
   for (int d = 0; d < D; d++) k->bw[d] = bw[d];
   k->prefactor = 1.0 / (std::pow(2.0 * M_PI, 0.5 * D) * prod_h);
   k->npad = std::max<size_t>(SXMC_KDE_TILE, (k->nsamples + SXMC_KDE_TILE - 1) / SXMC_KDE_TILE * SXMC_KDE_TILE);
+  if (sensitivity > 0) {
+    k->sensitivity = sensitivity;
+    rc = set_local_factors(k.get(), rows, nfields, inside);
+    if (rc) {
+      if (k->d_lambda) (void)hipFree(k->d_lambda);
+      sxmc_hist_destroy(k->h);
+      return rc;
+    }
+  }
   rc = alloc_rows(k.get(), "hipMalloc sample rows: ");
   if (rc) return rc;
   DeviceProps props;
   if (get_props(props) == SXMC_OK && props.cus > 0) k->cus = props.cus;
   *out = k.release();
   return SXMC_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int sxmc_kde_create(const float* samples, size_t nsamples_floats, int samples_on_device, int nfields, int nobservables,
+                    const double* lower, size_t n_lower, const double* upper, size_t n_upper,
+                    const double* bandwidth_scale, size_t n_bandwidth_scale, unsigned dataset, sxmc_kde_t* out) {
+  SX_REQUIRE(out, "null argument");
+  *out = nullptr;
+  return kde_create(samples, nsamples_floats, samples_on_device, nfields, nobservables, lower, n_lower, upper, n_upper,
+                    bandwidth_scale, n_bandwidth_scale, dataset, 0.0, out);
+}
+
+int sxmc_kde_create_adaptive(const float* samples, size_t nsamples_floats, int samples_on_device, int nfields,
+                             int nobservables, const double* lower, size_t n_lower, const double* upper,
+                             size_t n_upper, const double* bandwidth_scale, size_t n_bandwidth_scale, unsigned dataset,
+                             double sensitivity, sxmc_kde_t* out) {
+  SX_REQUIRE(out, "null argument");
+  *out = nullptr;
+  SX_REQUIRE(sxkde::valid_sensitivity(sensitivity), "Bandwidth sensitivity must be a number in [0, 1].");
+  return kde_create(samples, nsamples_floats, samples_on_device, nfields, nobservables, lower, n_lower, upper, n_upper,
+                    bandwidth_scale, n_bandwidth_scale, dataset, sensitivity, out);
 }
 
 int sxmc_kde_create_shared(sxmc_kde_t base, sxmc_kde_t* out) {
@@ -187,6 +289,17 @@ int sxmc_kde_create_shared(sxmc_kde_t base, sxmc_kde_t* out) {
   for (int d = 0; d < SXMC_KDE_MAX_DIM; d++) k->bw[d] = base->bw[d];
   k->prefactor = base->prefactor;
   k->cus = base->cus;
+  if (base->d_lambda) {   // the factors are copied, never recomputed
+    k->sensitivity = base->sensitivity;
+    k->lambda = base->lambda;
+    hipError_t e = hipMalloc((void**)&k->d_lambda, sizeof(double) * k->npad);
+    if (e == hipSuccess) e = hipMemcpy(k->d_lambda, base->d_lambda, sizeof(double) * k->npad, hipMemcpyDeviceToDevice);
+    if (e != hipSuccess) {
+      if (k->d_lambda) (void)hipFree(k->d_lambda);
+      sxmc_hist_destroy(k->h);
+      return fail(SXMC_ERR_HIP, std::string("create_shared: ") + hipGetErrorString(e));
+    }
+  }
   rc = alloc_rows(k.get(), "create_shared: ");
   if (rc) return rc;
   *out = k.release();
@@ -200,6 +313,7 @@ int sxmc_kde_destroy(sxmc_kde_t k) {
   if (k->d_scan_temp) (void)hipFree(k->d_scan_temp);
   if (k->d_proj) (void)hipFree(k->d_proj);
   if (k->d_rows) (void)hipFree(k->d_rows);
+  if (k->d_lambda) (void)hipFree(k->d_lambda);
   if (k->d_pts) (void)hipFree(k->d_pts);
   if (k->d_codes) (void)hipFree(k->d_codes);
   if (k->d_part) (void)hipFree(k->d_part);
@@ -326,11 +440,17 @@ int sxmc_kde_eval_async(sxmc_kde_t k, int do_eval_pdf) {
     a.cscale[i] = kLog2eHalfSqrt / k->bw[i];
     a.inv_h_sqrt2[i] = 1.0 / (k->bw[i] * M_SQRT2);
   }
+  a.lambda = k->d_lambda;
   SX_HIP(hipMemsetAsync(a.norm, 0, sizeof(unsigned), s));
   SX_HIP(sx_kde_prepass(d, a, s));
   if (lookup) {
-    SX_HIP(sx_kde_pairs(k->D, k->d_pts, k->pitch, k->d_rows, k->tiles_per_split,
-                        (unsigned)(k->npad / SXMC_KDE_TILE), k->nsplit, k->d_part, s));
+    const unsigned ntiles = (unsigned)(k->npad / SXMC_KDE_TILE);
+    if (k->d_lambda) {
+      SX_HIP(sx_kde_pairs_adaptive(k->D, k->d_pts, k->pitch, k->d_rows, k->tiles_per_split, ntiles, k->nsplit,
+                                   k->d_part, s));
+    } else {
+      SX_HIP(sx_kde_pairs(k->D, k->d_pts, k->pitch, k->d_rows, k->tiles_per_split, ntiles, k->nsplit, k->d_part, s));
+    }
     SX_HIP(sx_kde_combine(k->d_part, k->pitch, k->nsplit, k->npoints, k->d_codes, a.norm, k->prefactor,
                           k->pdf + k->pdf_off, (long)k->pdf_stride, s));
   }
@@ -353,6 +473,17 @@ int sxmc_kde_bandwidths(sxmc_kde_t k, double* h, size_t n) {
   SX_REQUIRE(k && h, "null argument");
   SX_REQUIRE(n == (size_t)k->D, "bandwidth buffer size mismatch");
   for (int d = 0; d < k->D; d++) h[d] = k->bw[d];
+  return SXMC_OK;
+}
+int sxmc_kde_sensitivity(sxmc_kde_t k, double* v) {
+  SX_REQUIRE(k && v, "null argument");
+  *v = k->sensitivity;
+  return SXMC_OK;
+}
+int sxmc_kde_local_factors(sxmc_kde_t k, double* lambda, size_t n) {
+  SX_REQUIRE(k && (lambda || n == 0), "null argument");
+  SX_REQUIRE(n == k->nsamples, "local factor buffer size mismatch");
+  for (size_t i = 0; i < n; i++) lambda[i] = k->d_lambda ? k->lambda[i] : 1.0;
   return SXMC_OK;
 }
 int sxmc_kde_nsamples(sxmc_kde_t k, size_t* v) {
@@ -391,7 +522,7 @@ int kde_compact(sxmc_kde_t k, unsigned& n) {
   unsigned* flag = k->d_flag;
   unsigned* pos = flag + k->npad;
   unsigned* idx = pos + k->npad;
-  SX_HIP(sx_kde_compact(k->d_rows, k->D, k->npad, flag, pos, idx, k->d_scan_temp, k->scan_temp_bytes, s));
+  SX_HIP(sx_kde_compact(k->d_rows, k->rowlen(), k->npad, flag, pos, idx, k->d_scan_temp, k->scan_temp_bytes, s));
   SX_HIP(hipMemcpyAsync(&n, pos + (k->npad - 1), sizeof(unsigned), hipMemcpyDeviceToHost, s));
   SX_HIP(hipStreamSynchronize(s));
   return SXMC_OK;
@@ -449,7 +580,7 @@ int sxmc_kde_random_sample(sxmc_kde_t k, size_t nobserved, unsigned long long se
   rc = sample_buffer(k->h, nobserved, row, d_out, d_exhausted);   // (the histogram evaluator's, on the same stream)
   if (rc) return rc;
   const unsigned* idx = k->d_flag + 2 * k->npad;
-  SX_HIP(sx_kde_sample(D, k->d_rows, idx, n, g, seed, nobserved, d_out, d_exhausted, k->h->stream));
+  SX_HIP(sx_kde_sample(D, k->d_rows, k->d_lambda, idx, n, g, seed, nobserved, d_out, d_exhausted, k->h->stream));
   return sample_read_back(k->h, nobserved, row, ": the cuts leave (almost) none of the kernel-density PDF's mass",
                           h_events);
 }
@@ -476,9 +607,10 @@ int sxmc_kde_project(sxmc_kde_t k, int obs, int nbins, double* h_prob) {
   a.upper = k->h->upper[(size_t)obs];
   a.h = k->bw[obs];
   a.cunit = kLog2eHalfSqrt;
+  a.lambda = k->d_lambda;
   const hipStream_t s = k->h->stream;
-  // [2 npad] per-row scratch, [nsplit][pitch] partials, [nbins] result, the count
-  const size_t off_prob = 2 * k->npad + (size_t)a.nsplit * a.pitch;
+  // [2 npad] per-row scratch ([3 npad] when adaptive), [nsplit][pitch] partials, [nbins] result, the count
+  const size_t off_prob = (k->d_lambda ? 3 : 2) * k->npad + (size_t)a.nsplit * a.pitch;
   const size_t need = off_prob + (size_t)nbins + 1;
   if (need > k->cap_proj) {
     SX_HIP(hipStreamSynchronize(s));   // (allocation next to queued work: settle it first)

@@ -103,7 +103,8 @@ def make_evaluators(workload):
     for s in w.signals:
         if getattr(s, "pdf", "hist") == "kernel":
             scale = s.bandwidth_scale if s.bandwidth_scale is not None else [1.0] * w.nobs
-            ev = pdfz.EvalKernel(s.samples, s.nfields, w.nobs, w.lower, w.upper, scale, dataset=s.dataset)
+            ev = pdfz.EvalKernel(s.samples, s.nfields, w.nobs, w.lower, w.upper, scale, dataset=s.dataset,
+                                 bandwidth_sensitivity=getattr(s, "bandwidth_sensitivity", 0.0))
         else:
             ev = pdfz.EvalHist(s.samples, s.nfields, w.nobs, w.lower, w.upper, w.nbins, dataset=s.dataset)
         for d in w.systematics:

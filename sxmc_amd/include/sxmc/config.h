@@ -769,6 +769,19 @@ inline void signal_pdf_from_json(Signal& s, const json::Value& c, size_t nobserv
     s.bandwidth_scale.assign(nobservables, 1.0);
   }
 }
+/** A kernel signal's "bandwidth_sensitivity": the alpha of pdfz::EvalKernel's adaptive bandwidths, a number in [0, 1];
+ *  absent: 0, the fixed bandwidths.  Refused on a histogram signal.  After signal_pdf_from_json (it reads s.pdf). */
+inline void signal_sensitivity_from_json(Signal& s, const json::Value& c) {
+  const std::string who = "signal '" + s.name + "': ";
+  s.bandwidth_sensitivity = 0.0;
+  if (!c.isMember("bandwidth_sensitivity")) return;
+  if (s.pdf != "kernel") throw ConfigError(who + "\"bandwidth_sensitivity\" is only for \"pdf\": \"kernel\"");
+  const double v = c["bandwidth_sensitivity"].asDouble("bandwidth_sensitivity");
+  if (!(std::isfinite(v) && v >= 0 && v <= 1)) {
+    throw ConfigError(who + "\"bandwidth_sensitivity\" must be a number in [0, 1]");
+  }
+  s.bandwidth_sensitivity = v;
+}
 template <typename T>
 size_t index_with_append(std::vector<T>& v, const T& x) {   // utils.h get_index_with_append
   const size_t i = std::find(v.begin(), v.end(), x) - v.begin();
@@ -890,6 +903,7 @@ inline FitConfig parse_config(const std::string& text, const std::string& base_d
     double nexpected = c.isMember("rate") ? (double)c["rate"].asFloat("rate") : (double)(-1.0f / c["scale"].asFloat("scale"));
     for (const json::Value& sv : c["systematics"].items) s.systematic_names.push_back(sv.asString("systematics[]"));
     detail::signal_pdf_from_json(s, c, fc.observables.size());
+    detail::signal_sensitivity_from_json(s, c);
     const std::string source_name = c.get("source", name.c_str());
     for (const Source& src : fc.sources)
       if (src.name == source_name) {

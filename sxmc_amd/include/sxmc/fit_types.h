@@ -62,13 +62,15 @@ struct Signal {
   size_t n_mc = 0;  //!< number of MC samples BEFORE cuts (signal.cpp:28); build_pdfz fills it in when it is 0
   std::string pdf = "hist";                   //!< "hist": pdfz::EvalHist; "kernel": pdfz::EvalKernel (kernel density)
   std::vector<double> bandwidth_scale;        //!< "kernel": one per fit observable, in fit-observable order (empty: 1.0)
+  double bandwidth_sensitivity = 0.0;         //!< "kernel": alpha of the adaptive bandwidths in [0, 1]; 0: fixed
   pdfz::Eval* histogram = nullptr;  //!< borrowed by the driver, as in the reference
   // keeps the parameter-index arrays alive (the reference leaks them, signal.cpp:139)
   std::vector<std::shared_ptr<pdfz::Array<short>>> par_arrays;
 };
 
 /** Signal::build_pdfz (signal.cpp:112-170): the evaluator of one signal with every systematic attached -- a
- *  pdfz::EvalHist, or a pdfz::EvalKernel when sig.pdf is "kernel" (bandwidth scales from sig.bandwidth_scale).
+ *  pdfz::EvalHist, or a pdfz::EvalKernel when sig.pdf is "kernel" (bandwidth scales from sig.bandwidth_scale, the
+ *  sensitivity of its adaptive bandwidths from sig.bandwidth_sensitivity).
  *  `samples` is the row-major [n][nfields] table, observables first. */
 inline void build_pdfz(Signal& sig, const std::vector<float>& samples, int nfields,
                        const std::vector<Observable>& observables, std::vector<Systematic>& systematics) {
@@ -88,7 +90,7 @@ inline void build_pdfz(Signal& sig, const std::vector<float>& samples, int nfiel
     }
     std::vector<double> scale(D, 1.0);
     for (size_t i = 0; i < D && !sig.bandwidth_scale.empty(); i++) scale.at(observables[i].field_index) = sig.bandwidth_scale[i];
-    h = new pdfz::EvalKernel(samples, nfields, (int)D, lower, upper, scale, sig.dataset);
+    h = new pdfz::EvalKernel(samples, nfields, (int)D, lower, upper, scale, sig.dataset, sig.bandwidth_sensitivity);
   } else if (sig.pdf == "hist") {
     h = new pdfz::EvalHist(samples, nfields, (int)observables.size(), lower, upper, nbins, sig.dataset);
   } else {

@@ -393,18 +393,66 @@ class EvalHist : public detail::EvalOver<detail::HistApi> {
  *  in-domain sample chosen uniformly, then per observable its Gaussian truncated to [lower, upper); every event passes
  *  the domain test above.  Counter-based (Philox4x32-10 keyed by the seed): the same seed gives the same events.
  *  Concurrent experiments: EvalKernel(base, SharedSamples{}) shares base's sample table (systematics, bandwidths
- *  copied; own rows, points, bindings and stream) and may outlive it. */
+ *  copied; own rows, points, bindings and stream) and may outlive it.
+ *
+ *  Adaptive (sample-point) bandwidths, Abramson's estimator (Silverman 5.3): the last constructor argument, the
+ *  bandwidth sensitivity alpha in [0, 1] (anything else, or not finite, throws).  alpha = 0, the default, is everything
+ *  above: the same kernels, the same row layout, the same bits.  For alpha > 0 every table row i gets a factor lambda_i
+ *  on all its bandwidths, fixed at construction on the UNTRANSFORMED table, after the Scott bandwidths h_d:
+ *    pilot    S0 = the n untransformed samples inside the domain.  For every table row i (inside or not), in f64:
+ *               f_i = (1/n) sum_{j in S0} w_j prod_d phi((x_id - x_jd)/h_d)/h_d,
+ *               w_j = 1 / prod_d [Phi((upper_d - x_jd)/h_d) - Phi((lower_d - x_jd)/h_d)],
+ *             this evaluator's own fixed-bandwidth PDF at zero systematics, taken at the sample; the same formula
+ *             continues outside the domain.  The difference x_id - x_jd is taken first, on the f64 values of the
+ *             floats, then divided by h_d; Phi through erfc, as the prepass writes it.
+ *    scale    g = exp((1/n) sum_{i in S0} ln f_i), on the host in f64, in table order; f_i > 0 on S0 because a row's
+ *             own term is positive.
+ *    factors  lambda_i = min(10, max(0.1, (f_i/g)^(-alpha))); a row whose f_i is not finite and positive takes 10.  The
+ *             clips bound how far the f32 coordinates of the pair sum are stretched.
+ *  The factors belong to table rows: a sample keeps its lambda_i wherever the systematics move it, rows that start
+ *  outside the domain and move in included.  Per evaluation, s_i the moved samples, norm the in-domain count (unchanged):
+ *    pdf(x) = (1/norm) sum_{i in domain} w_i prod_d phi((x_d - s_id)/(h_d lambda_i))/(h_d lambda_i),
+ *    w_i the truncation weight at bandwidth h_d lambda_i: the integral over the domain is still exactly 1.  Point
+ *    codes, the NaN / 0 rules and norm = 0 stay as above.
+ *  SampleEvents draws coordinate d of an event that picked row i from N(s_id, (h_d lambda_i)^2) truncated to the domain;
+ *  the Philox words, counters, rounding and clamp rules are unchanged.  Project is, per sample and bin,
+ *    [Phi((t_j+1 - u_i)/lambda_i) - Phi((t_j - u_i)/lambda_i)] / [Phi((T - u_i)/lambda_i) - Phi(-u_i/lambda_i)].
+ *  Deterministic: no floating-point atomics; the pilot's split over workgroups depends on the sample count alone and
+ *  the splits are added in order, so two constructions, on any device, give the same lambda bits (per-device
+ *  evaluators of a multi-GPU ensemble agree).  Share() and the SharedSamples constructor carry the sensitivity and the
+ *  factors over; they are not recomputed.
+ *  Accuracy: tests/kde_adaptive_reference.py has the bound; against the fixed-bandwidth bound the coordinate term
+ *  grows with the 1/lambda_i^2 of the samples in reach of the point, at most 100 by the clips.
+ *  Cost: one more multiply per pair and rows of D + 2 floats; the pilot is O(samples^2) in f64, once. */
 class EvalKernel : public detail::EvalOver<detail::KernelApi> {
  public:
   EvalKernel(const std::vector<float>& samples, int nfields, int nobservables, const std::vector<double>& lower,
-             const std::vector<double>& upper, const std::vector<double>& bandwidth_scale, unsigned dataset = 0)
+             const std::vector<double>& upper, const std::vector<double>& bandwidth_scale, unsigned dataset = 0,
+             double bandwidth_sensitivity = 0.0)
       : EvalOver(nfields, nobservables, dataset) {
-    throw_on(sxmc_kde_create(samples.data(), samples.size(), 0, nfields, nobservables, lower.data(), lower.size(),
-                             upper.data(), upper.size(), bandwidth_scale.data(), bandwidth_scale.size(), dataset,
-                             &handle));
+    throw_on(sxmc_kde_create_adaptive(samples.data(), samples.size(), 0, nfields, nobservables, lower.data(),
+                                      lower.size(), upper.data(), upper.size(), bandwidth_scale.data(),
+                                      bandwidth_scale.size(), dataset, bandwidth_sensitivity, &handle));
   }
   EvalKernel(const EvalKernel& base, SharedSamples s) : EvalOver(base, s) {}
   Eval* Share() const override { return new EvalKernel(*this, SharedSamples{}); }
+
+  /** The alpha this evaluator was constructed with (a shared evaluator: its base's). */
+  double BandwidthSensitivity() const {
+    double a = 0.0;
+    throw_on(sxmc_kde_sensitivity(handle, &a));
+    return a;
+  }
+
+  /** lambda_i of every table row, fixed at construction; all 1.0 at sensitivity 0. */
+  std::vector<double> LocalFactors() const {
+    size_t n = 0;
+    throw_on(sxmc_kde_nsamples(handle, &n));
+    std::vector<double> lambda(n);
+    double none = 0.0;
+    throw_on(sxmc_kde_local_factors(handle, n ? lambda.data() : &none, n));
+    return lambda;
+  }
 
   /** The bandwidths h_d fixed at construction (Scott's rule). */
   std::vector<double> Bandwidths() const {

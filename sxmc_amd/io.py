@@ -144,6 +144,21 @@ def signal_pdf(name, c, nobservables):
     return pdf, scale
 
 
+def signal_sensitivity(name, c, pdf):
+    """A kernel signal's "bandwidth_sensitivity": the alpha of pdfz.EvalKernel's adaptive bandwidths, a number in
+    [0, 1]; absent: 0.0, the fixed bandwidths.  Refused on a histogram signal.  Same rules and messages as
+    sxmc::detail::signal_sensitivity_from_json (config.h)."""
+    who = "signal '%s': " % name
+    if "bandwidth_sensitivity" not in c:
+        return 0.0
+    if pdf != "kernel":
+        raise ValueError(who + '"bandwidth_sensitivity" is only for "pdf": "kernel"')
+    v = _number(c["bandwidth_sensitivity"], "bandwidth_sensitivity")
+    if not (math.isfinite(v) and 0 <= v <= 1):
+        raise ValueError(who + '"bandwidth_sensitivity" must be a number in [0, 1]')
+    return v
+
+
 def load_config(path_or_text, base_dir=None):
     if os.path.exists(path_or_text):
         base_dir = base_dir or os.path.dirname(os.path.abspath(path_or_text))
@@ -241,7 +256,8 @@ def load_config(path_or_text, base_dir=None):
             scale=float(np.float32(c["scale"])) if "scale" in c else None,
             systematics=[s for s in c.get("systematics", [])],
             source=next(s for s in fc.sources if s["name"] == src_name),
-            pdf=pdf, bandwidth_scale=bandwidth_scale))
+            pdf=pdf, bandwidth_scale=bandwidth_scale,
+            bandwidth_sensitivity=signal_sensitivity(name, c, pdf)))
     fc.data = {int(k): [dict(filename=row["filename"], title=row.get("title", "")) for row in rows]
                for k, rows in root.get("data", {}).items()}
     fc.base_dir = base_dir or "."
@@ -266,7 +282,8 @@ def build_workload(fc):
         # (bandwidth scales in the workload's observable order, that of lower / upper)
         scale = [s["bandwidth_scale"][i] for i in order] if s.get("bandwidth_scale") else None
         sig = workloads.Signal(samples, nfields, nexpected, s["source"]["index"], dataset=s["dataset"],
-                               pdf=s.get("pdf", "hist"), bandwidth_scale=scale)
+                               pdf=s.get("pdf", "hist"), bandwidth_scale=scale,
+                               bandwidth_sensitivity=s.get("bandwidth_sensitivity", 0.0))
         sig.n_mc_total = n_mc
         sig.name = s["name"]
         signals.append(sig)

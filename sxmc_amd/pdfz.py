@@ -261,13 +261,33 @@ class EvalHist(_Eval):
 class EvalKernel(_Eval):
     """pdfz::EvalKernel (pdfz.h:578-625): the kernel-density PDF, contract in sxmc_amd/include/sxmc/pdfz.h.
     Same method names as EvalHist (RandomSample and Shared included), plus Bandwidths(); at most 4 observables;
-    O(points x samples) per evaluation."""
+    O(points x samples) per evaluation.  bandwidth_sensitivity in [0, 1] (alpha) turns on Abramson's adaptive
+    bandwidths h_d * lambda_i, lambda_i fixed per table row at construction (LocalFactors()); 0.0, the default, is the
+    fixed-bandwidth evaluator, the same kernels and bits as before the keyword existed."""
 
     _prefix = "sxmc_kde_"
 
-    def __init__(self, samples, nfields, nobservables, lower, upper, bandwidth_scale, dataset=0):
+    def __init__(self, samples, nfields, nobservables, lower, upper, bandwidth_scale, dataset=0,
+                 bandwidth_sensitivity=0.0):
         scale = np.ascontiguousarray(bandwidth_scale, dtype=np.float64).reshape(-1)
-        self._create(capi.load().sxmc_kde_create, samples, nfields, nobservables, lower, upper, scale, dataset)
+        alpha = float(bandwidth_sensitivity)
+        lib = capi.load()
+        if alpha == 0.0:
+            create = lib.sxmc_kde_create
+        else:
+            def create(*a):
+                return lib.sxmc_kde_create_adaptive(*a[:-1], alpha, a[-1])
+        self._create(create, samples, nfields, nobservables, lower, upper, scale, dataset)
+
+    def BandwidthSensitivity(self):
+        """The alpha the evaluator was constructed with (a shared evaluator: its base's)."""
+        return self._get("sensitivity", C.c_double)
+
+    def LocalFactors(self):
+        """lambda_i of every table row, fixed at construction (float64 [nsamples]); all 1.0 at sensitivity 0."""
+        out = np.empty(self.nsamples, dtype=np.float64)
+        self._call("local_factors", capi.ptr(out), out.size)
+        return out
 
     def Bandwidths(self):
         """h_d = bandwidth_scale_d * sigma_d * n^(-1/(D+4)) (Scott's rule), fixed at construction."""

@@ -10,7 +10,8 @@ import numpy as np
 class Signal:
     """One signal's MC sample table + how it enters the fit."""
 
-    def __init__(self, samples, nfields, nexpected, source_id, dataset=0, pdf="hist", bandwidth_scale=None):
+    def __init__(self, samples, nfields, nexpected, source_id, dataset=0, pdf="hist", bandwidth_scale=None,
+                 bandwidth_sensitivity=0.0):
         self.samples = samples              # float32 [n, nfields] row-major
         self.nfields = nfields
         self.nexpected = float(nexpected)
@@ -20,6 +21,8 @@ class Signal:
         self.pdf = pdf                      # "hist" (pdfz.EvalHist) or "kernel" (pdfz.EvalKernel)
         # "kernel": one scale per observable in the workload's observable order (None: 1.0 each)
         self.bandwidth_scale = None if bandwidth_scale is None else [float(v) for v in bandwidth_scale]
+        # "kernel": alpha of pdfz.EvalKernel's adaptive bandwidths in [0, 1]; 0: the fixed bandwidths
+        self.bandwidth_sensitivity = float(bandwidth_sensitivity)
 
     @property
     def n_mc(self):

@@ -14,8 +14,13 @@ in-domain rows, the draw, the copy of the events to the host), median of 5 calls
 ms_per_projection: host clock around one Project(obs, --project-bins) of the last evaluation (the per-row scratch, the
 sum over samples x bins, the combine, the copy of the shares to the host), both observables in turn, mean per call over
 a window of at least half of --seconds after one warm-up each.
+--adaptive: besides, in the same run, an evaluator with adaptive bandwidths (--sensitivity, default 0.5) on the same
+table, systematics and points: ms_per_eval_adaptive measured the same way right after the fixed-bandwidth window,
+adaptive_over_fixed their ratio (expected from the instruction count alone: one more v_mul_f32, 32 cycles per 64 pairs
+against 28, 1.14), and ms_pilot, the host clock around the adaptive construction minus that around a fixed-bandwidth
+construction of the same table made just before (both in the line): what the pilot, the factors and their upload add.
 Usage: python tools/kde_bench.py [--samples N] [--points E] [--seconds S] [--cpu-points K] [--sample-events M]
-                                 [--project-bins B]"""
+                                 [--project-bins B] [--adaptive] [--sensitivity A]"""
 import argparse
 import json
 import math
@@ -31,6 +36,52 @@ from sxmc_amd import capi, pdfz  # noqa: E402
 from sxmc_amd.capi import DeviceArray  # noqa: E402
 
 
+def eval_window(ev, seconds):
+    """(ms per EvalAsync + EvalFinished, calls): three warm-up evaluations, then a window of at least `seconds`."""
+    for _ in range(3):
+        ev.EvalAsync()
+        ev.EvalFinished()
+    calls, t0 = 0, time.perf_counter()
+    while True:
+        ev.EvalAsync()
+        ev.EvalFinished()
+        calls += 1
+        el = time.perf_counter() - t0
+        if el >= seconds and calls >= 3:
+            return 1e3 * el / calls, calls
+
+
+def measure_adaptive(a, samples, F, D, lower, upper, pts, par, fixed_ms):
+    """The --adaptive keys of the result line."""
+    e = pts.shape[0]
+    c0 = time.perf_counter()
+    plain = pdfz.EvalKernel(samples.ravel(), F, D, lower, upper, [1.0, 1.0])
+    capi.load().sxmc_device_synchronize()
+    c1 = time.perf_counter()
+    ev = pdfz.EvalKernel(samples.ravel(), F, D, lower, upper, [1.0, 1.0], bandwidth_sensitivity=a.sensitivity)
+    capi.load().sxmc_device_synchronize()
+    c2 = time.perf_counter()
+    plain.close()
+    ev.AddSystematic(pdfz.ShiftSystematic(1, [0]))
+    ev.AddSystematic(pdfz.ScaleSystematic(0, [1]))
+    ev.AddSystematic(pdfz.ResolutionScaleSystematic(0, 2, [2]))
+    ev.SetEvalPoints(pts.ravel())
+    pdf, norm = DeviceArray.zeros(e, np.float32), DeviceArray.zeros(1, np.uint32)
+    ev.SetPDFValueBuffer(pdf)
+    ev.SetNormalizationBuffer(norm)
+    ev.SetParameterBuffer(par)
+    ms, calls = eval_window(ev, a.seconds)
+    lam = ev.LocalFactors()
+    out = dict(sensitivity=a.sensitivity, ms_per_eval_adaptive=round(ms, 4), evaluations_adaptive=calls,
+               adaptive_over_fixed=round(ms / fixed_ms, 4), expected_adaptive_over_fixed=round(32 / 28, 4),
+               ms_construct_fixed=round(1e3 * (c1 - c0), 3), ms_construct_adaptive=round(1e3 * (c2 - c1), 3),
+               ms_pilot=round(1e3 * ((c2 - c1) - (c1 - c0)), 3), factor_min=float(lam.min()),
+               factor_max=float(lam.max()), factors_clipped=int(np.sum((lam == 0.1) | (lam == 10.0))),
+               norm_adaptive=int(norm.get()[0]), finite_values_adaptive=int(np.isfinite(pdf.get()).sum()))
+    ev.close()
+    return out
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--samples", type=int, default=1 << 17)
@@ -39,6 +90,8 @@ def main():
     ap.add_argument("--cpu-points", type=int, default=200)
     ap.add_argument("--sample-events", type=int, default=1000000)
     ap.add_argument("--project-bins", type=int, default=100)
+    ap.add_argument("--adaptive", action="store_true")
+    ap.add_argument("--sensitivity", type=float, default=0.5)
     a = ap.parse_args()
     if capi.device_count() < 1:
         raise SystemExit("kde_bench.py needs a GPU")
@@ -59,18 +112,8 @@ def main():
     ev.SetPDFValueBuffer(pdf)
     ev.SetNormalizationBuffer(norm)
     ev.SetParameterBuffer(par)
-    for _ in range(3):
-        ev.EvalAsync()
-        ev.EvalFinished()
-    calls, t0 = 0, time.perf_counter()
-    while True:
-        ev.EvalAsync()
-        ev.EvalFinished()
-        calls += 1
-        el = time.perf_counter() - t0
-        if el >= a.seconds and calls >= 3:
-            break
-    ms = 1e3 * el / calls
+    ms, calls = eval_window(ev, a.seconds)
+    adaptive = measure_adaptive(a, samples, F, D, lower, upper, pts, par, ms) if a.adaptive else {}
     pairs = float(e) * n
     rate = pairs / (ms * 1e-3)
     info = capi.device_info(0)
@@ -127,7 +170,7 @@ def main():
                           ms_per_sample_call=round(sample_ms, 4), sampled_in_domain=drawn_in_domain,
                           project_bins=a.project_bins, ms_per_projection=round(projection_ms, 4),
                           projection_sums=projection_sums,
-                          device=info["name"])))
+                          device=info["name"], **adaptive)))
 
 
 if __name__ == "__main__":
