@@ -124,14 +124,16 @@ def eval_pdf(read_bins, bins, norm, bin_volume, out=None, offset=0, stride=1):
     return out
 
 
-def nll_event_chunks(lut, pars, ne, ns, nexpected, n_mc, source_id, norms):
+def nll_event_chunks(lut, pars, ne, ns, nexpected, n_mc, source_id, norms, out=None):
+    """out: a float64 destination of one entry, written in place (a sum that is NaN is NOT written); default zeros."""
     lut = np.ascontiguousarray(lut, dtype=np.float32)
     pars = np.ascontiguousarray(pars, dtype=np.float64)
     nexpected = np.ascontiguousarray(nexpected, dtype=np.float64)
     n_mc = np.ascontiguousarray(n_mc, dtype=np.uint32)
     source_id = np.ascontiguousarray(source_id, dtype=np.int16)
     norms = np.ascontiguousarray(norms, dtype=np.uint32)
-    sums = np.zeros(1, dtype=np.float64)
+    sums = np.zeros(1, dtype=np.float64) if out is None else out
+    assert sums.dtype == np.float64 and sums.size >= 1 and sums.flags.c_contiguous
     lib().oracle_nll_event_chunks(_p(lut, C.c_float), _p(pars, C.c_double), C.c_size_t(ne),
                                   C.c_size_t(ns), _p(nexpected, C.c_double), _p(n_mc, C.c_uint),
                                   _p(source_id, C.c_short), _p(norms, C.c_uint),

@@ -7,16 +7,31 @@
  * Only tests/, __graft_entry__.smoke() and bench.py's cpu_baseline leg may load it; the
  * product (sxmc_amd/, include/) never links, imports or calls anything in oracle/.
  *
- * Pinning status:
- *   - pdfz part (SetEvalPoints, bin_samples+apply_systematic, eval_pdf): PINNED by the
- *     reference's own gtest known answers (test/test_pdfz.cpp, test_pdfz_2d.cpp,
- *     test_pdfz_syst.cpp), transcribed as data into tests/golden/pdfz_known_answers.json.
- *   - nll part (nll_event_chunks, nll_event_reduce, nll_total, jump_decider,
- *     pick_new_vector): PARITY UNPINNED.  The reference has no test, fixture or golden
- *     vector for these functions, and the reference cannot be built in this image without
- *     writing stand-ins for hemi / ROOT / CUDA headers, which is not allowed.  They are
- *     restated line by line from nll_kernels.cpp:30-188 and checked only by hand-derived
- *     closed-form cases.
+ * Pinning status: every function here is held BIT FOR BIT to the reference's own compiled code.
+ *   oracle/ref/ builds src/pdfz.cpp and src/nll_kernels.cpp unmodified in their CPU mode (g++ -DHEMI_CUDA_DISABLE, the
+ *   arithmetic flags below, the same libm) against stand-in hemi / CUDA / ROOT headers written for that purpose, with a
+ *   driver of ours around them; tests/golden/reference_parity.json records what they compute on the cases of
+ *   tests/reference_cases.py, each case also run clean under ASan + UBSan (so the reference is DEFINED on it), and
+ *   tests/test_reference_parity_cpu.py compares (and re-runs the driver where it is built).
+ *   - pdfz part (SetEvalPoints, bin_samples + apply_systematic, eval_pdf through EvalHist's public interface): bins,
+ *     norm, the whole output buffer, read_bins, bin volume; 1-5 observables, up to 3 extra fields, every kind of
+ *     systematic with 1-3 coefficients and in both orders, offsets and strides of all three buffers, both data sets,
+ *     values on and beside every kind of edge, rows moved onto edges, -0.0 / denormals / infinities / 1e30, domains far
+ *     from zero, wild parameters -- and rows whose index in an inner dimension equals nbins while the flat index stays
+ *     inside the histogram (the second deviation below: the reference bins them into the neighbouring row, and so does
+ *     bin_range here).  Also by the reference's gtest known answers (tests/golden/pdfz_known_answers.json).
+ *   - nll part: nll_event_chunks (`float eff`, the `s > 0` skip, NaN look-ups as 0), nll_event_reduce, nll_total (both
+ *     1e18 returns and their order, `sigmas[i] > 0`), jump_decider (`np < nc || u <= exp(nc - np)` at, below and above
+ *     the threshold, NaN and infinite NLLs, the appended row; `debug_mode ||` by a combo step that only it accepts) and whole finish_nll_jump_pick_combo steps on carried
+ *     state, with the scripted generator's call log pinning that a step draws its uniform first and then one normal
+ *     per parameter of width > 0, in index order.
+ *   - what stays the stand-in's: pick_new_vector's CPU branch calls gRandom->Gaus(current, width); the records pin
+ *     which parameters draw, the arguments (the float width widened to double) and the copy of the others, but the
+ *     arithmetic `mean + sigma * z` is the scripted stand-in's, chosen to be the device branch's `current + width * u`
+ *     that oracle_pick_new_vector restates.  A chunk sum that is NaN (not written, nll_kernels.cpp:113) cannot occur
+ *     with one lane over all events -- a sum of logarithms of positive numbers is finite or +inf -- so no record has
+ *     it: that line stays pinned by reading only.
+ *   No difference between this file and the reference was found on any record.
  *
  * Compile with: gcc -O2 -ffp-contract=off (x86-64 SSE2 double arithmetic, no FMA
  * contraction, no fast-math), which is the arithmetic of the reference's g++ CPU build.

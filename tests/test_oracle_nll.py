@@ -1,6 +1,8 @@
-"""CPU: hand-derived checks of the oracle's NLL restatement (nll_kernels.cpp:30-188).
-The reference holds no test for these functions, so the NLL part of the oracle is
-"parity unpinned" (oracle/sxmc_oracle.h); these cases pin it to the formulas only."""
+"""CPU: hand-derived checks of the oracle's NLL restatement (nll_kernels.cpp:30-188): closed-form cases that say what
+the functions are FOR.  What pins the restatement itself is tests/test_reference_parity_cpu.py: there every one of
+these functions is held bit for bit to records of the fitted code's own compiled CPU-mode translation unit
+(tests/golden/reference_parity.json, oracle/ref/), on inputs chosen for the edges; the fitted code holds no test of
+its own for them."""
 import math
 
 import numpy as np
