@@ -13,6 +13,7 @@
 // Steps (host side: sxmc_launch_plan.cpp, get_bucket_sort / get_bucketed): key per sample -> stable radix sort of (key, row) ->
 // first row of every key -> host lays the granules out -> gather of the streamed columns.
 #include "nll_device.h"
+#include "sxmc_host.h"   // (DeviceBuffer: the host helpers' temporaries)
 
 #include <hipcub/hipcub.hpp>
 
@@ -431,12 +432,11 @@ hipError_t sx_bucket_sort(const unsigned* keys_in, unsigned* keys_out, const uns
   hipError_t e = hipcub::DeviceRadixSort::SortPairs(nullptr, temp_bytes, keys_in, keys_out, rows_in, rows_out, (int)n, 0,
                                                     bits, s);
   if (e != hipSuccess) return e;
-  void* temp = nullptr;
-  e = hipMalloc(&temp, temp_bytes ? temp_bytes : 16);
+  sxhost::DeviceBuffer<void> temp;
+  e = (hipError_t)temp.alloc(temp_bytes ? temp_bytes : 16);
   if (e != hipSuccess) return e;
-  e = hipcub::DeviceRadixSort::SortPairs(temp, temp_bytes, keys_in, keys_out, rows_in, rows_out, (int)n, 0, bits, s);
+  e = hipcub::DeviceRadixSort::SortPairs(temp.get(), temp_bytes, keys_in, keys_out, rows_in, rows_out, (int)n, 0, bits, s);
   hipError_t e2 = hipStreamSynchronize(s);
-  (void)hipFree(temp);
   return e != hipSuccess ? e : e2;
 }
 
@@ -468,9 +468,10 @@ hipError_t sx_column_minmax(const float* cols, unsigned long long pitch, int nco
     h[2 * c] = 0xFFFFFFFFu;
     h[2 * c + 1] = 0u;
   }
-  unsigned* d = nullptr;
-  hipError_t e = hipMalloc((void**)&d, sizeof(unsigned) * 2 * ncols);
+  sxhost::DeviceBuffer<unsigned> tmp;
+  hipError_t e = (hipError_t)tmp.alloc((size_t)(2 * ncols));
   if (e != hipSuccess) return e;
+  unsigned* const d = tmp.get();
   e = hipMemcpyAsync(d, h, sizeof(unsigned) * 2 * ncols, hipMemcpyHostToDevice, s);
   if (e == hipSuccess && n) {
     hipLaunchKernelGGL(column_minmax_kernel, dim3(grid_for(n, 2048)), dim3(256), 0, s, cols, pitch, ncols, n, d);
@@ -478,7 +479,6 @@ hipError_t sx_column_minmax(const float* cols, unsigned long long pitch, int nco
   }
   if (e == hipSuccess) e = hipMemcpyAsync(h, d, sizeof(unsigned) * 2 * ncols, hipMemcpyDeviceToHost, s);
   hipError_t e2 = hipStreamSynchronize(s);
-  (void)hipFree(d);
   if (e != hipSuccess) return e;
   if (e2 != hipSuccess) return e2;
   for (int c = 0; c < 2 * ncols; c++) {
@@ -502,9 +502,10 @@ hipError_t sx_column_codes(const float* cols, unsigned long long pitch, int nslo
     plan.base[m] = base[m];
     plan.step[m] = step[m];
   }
-  unsigned* d = nullptr;
-  hipError_t e = hipMalloc((void**)&d, sizeof(unsigned) * 2);
+  sxhost::DeviceBuffer<unsigned> tmp;
+  hipError_t e = (hipError_t)tmp.alloc(2);
   if (e != hipSuccess) return e;
+  unsigned* const d = tmp.get();
   e = hipMemsetAsync(d, 0, sizeof(unsigned) * 2, s);
   if (e == hipSuccess && n) {
     hipLaunchKernelGGL(column_codes_kernel, dim3(grid_for(n, 16384)), dim3(256), 0, s, cols, pitch, plan, n, qcol, d);
@@ -513,7 +514,6 @@ hipError_t sx_column_codes(const float* cols, unsigned long long pitch, int nslo
   unsigned h[2] = {0u, 0u};
   if (e == hipSuccess) e = hipMemcpyAsync(h, d, sizeof h, hipMemcpyDeviceToHost, s);
   hipError_t e2 = hipStreamSynchronize(s);
-  (void)hipFree(d);
   if (tally) {
     tally[0] = h[0];
     tally[1] = h[1];
@@ -524,9 +524,10 @@ hipError_t sx_column_codes(const float* cols, unsigned long long pitch, int nslo
 // one column as 16-bit codes, one per row (column_codes16_kernel); tally as above
 hipError_t sx_column_codes16(const float* col, double base, double step, unsigned long long n, unsigned short* qcol,
                              unsigned long long* tally, hipStream_t s) {
-  unsigned* d = nullptr;
-  hipError_t e = hipMalloc((void**)&d, sizeof(unsigned) * 2);
+  sxhost::DeviceBuffer<unsigned> tmp;
+  hipError_t e = (hipError_t)tmp.alloc(2);
   if (e != hipSuccess) return e;
+  unsigned* const d = tmp.get();
   e = hipMemsetAsync(d, 0, sizeof(unsigned) * 2, s);
   if (e == hipSuccess && n) {
     hipLaunchKernelGGL(column_codes16_kernel, dim3(grid_for(n, 16384)), dim3(256), 0, s, col, base, step, n, qcol, d);
@@ -535,7 +536,6 @@ hipError_t sx_column_codes16(const float* col, double base, double step, unsigne
   unsigned h[2] = {0u, 0u};
   if (e == hipSuccess) e = hipMemcpyAsync(h, d, sizeof h, hipMemcpyDeviceToHost, s);
   hipError_t e2 = hipStreamSynchronize(s);
-  (void)hipFree(d);
   if (tally) {
     tally[0] = h[0];
     tally[1] = h[1];
@@ -548,12 +548,11 @@ hipError_t sx_hist_cdf(const unsigned* d_bins, unsigned* d_cdf, int nbins_total,
   size_t temp_bytes = 0;
   hipError_t e = hipcub::DeviceScan::InclusiveSum(nullptr, temp_bytes, d_bins, d_cdf, nbins_total, s);
   if (e != hipSuccess) return e;
-  void* temp = nullptr;
-  e = hipMalloc(&temp, temp_bytes ? temp_bytes : 16);
+  sxhost::DeviceBuffer<void> temp;
+  e = (hipError_t)temp.alloc(temp_bytes ? temp_bytes : 16);
   if (e != hipSuccess) return e;
-  e = hipcub::DeviceScan::InclusiveSum(temp, temp_bytes, d_bins, d_cdf, nbins_total, s);
+  e = hipcub::DeviceScan::InclusiveSum(temp.get(), temp_bytes, d_bins, d_cdf, nbins_total, s);
   hipError_t e2 = hipStreamSynchronize(s);
-  (void)hipFree(temp);
   return e != hipSuccess ? e : e2;
 }
 

@@ -151,7 +151,7 @@ int flush_deferred() {
     // trial fills (or a fill whose lookup then failed) have counted into the members' histograms and normalisations:
     // a failed evaluation leaves them zeroed, not half-counted (the error code is what the caller gets)
     const std::string why = g_last_error;
-    (void)sx_launch_zero(g->d_descs, (int)g->members.size(), g->max_bins, g->d_ticket, fl->stream);
+    (void)sx_launch_zero(g->d_descs.get(), (int)g->members.size(), g->max_bins, g->d_ticket.get(), fl->stream);
     (void)hipGetLastError();
     g_last_error = why;
   }
@@ -201,21 +201,15 @@ void forget_evaluator(sxmc_hist* h) {
 // device to drain, i.e. for whatever other chains have queued.
 int sample_buffer(sxmc_hist* h, size_t nobserved, size_t row, float*& d_events, unsigned*& d_exhausted) {
   const size_t need = sizeof(float) * nobserved * row + sizeof(unsigned);   // + the count of events never accepted
-  if (need > h->cap_sample) {
-    if (h->d_sample) SX_HIP(hipFree(h->d_sample));
-    h->d_sample = nullptr;
-    h->cap_sample = 0;
-    SX_HIP(hipMalloc((void**)&h->d_sample, need + need / 4));
-    h->cap_sample = need + need / 4;
-  }
-  d_events = h->d_sample;
+  if (need > h->d_sample.capacity()) SX_BUF(h->d_sample.grow(need + need / 4));
+  d_events = static_cast<float*>(h->d_sample.get());
   d_exhausted = reinterpret_cast<unsigned*>(d_events + nobserved * row);
   SX_HIP(hipMemsetAsync(d_exhausted, 0, sizeof(unsigned), h->stream));
   return SXMC_OK;
 }
 
 int sample_read_back(sxmc_hist* h, size_t nobserved, size_t row, const char* why, float* h_events) {
-  const unsigned* d_exhausted = reinterpret_cast<const unsigned*>(h->d_sample + nobserved * row);
+  const unsigned* d_exhausted = reinterpret_cast<const unsigned*>(static_cast<const float*>(h->d_sample.get()) + nobserved * row);
   SX_HIP(hipStreamSynchronize(h->stream));
   unsigned exhausted = 0;
   SX_HIP(hipMemcpy(&exhausted, d_exhausted, sizeof(unsigned), hipMemcpyDeviceToHost));
@@ -223,7 +217,7 @@ int sample_read_back(sxmc_hist* h, size_t nobserved, size_t row, const char* why
     return fail(SXMC_ERR_STATE, std::to_string(exhausted) + " of " + std::to_string(nobserved) +
                                     " events could not be drawn inside the cuts in 1024 attempts each" + why);
   }
-  SX_HIP(hipMemcpy(h_events, h->d_sample, sizeof(float) * nobserved * row, hipMemcpyDeviceToHost));
+  SX_HIP(hipMemcpy(h_events, h->d_sample.get(), sizeof(float) * nobserved * row, hipMemcpyDeviceToHost));
   return SXMC_OK;
 }
 
@@ -252,7 +246,7 @@ int sxmc_hist_create(const float* samples, size_t nsamples_floats, int samples_o
   SX_REQUIRE(nsamples_floats == 0 || samples, "null samples");
   SX_REQUIRE(lower && upper && nbins, "null argument");
 
-  sxmc_hist* h = new sxmc_hist;
+  auto h = std::make_unique<sxmc_hist>();   // (a failure below leaves nothing allocated)
   h->nfields = nfields;
   h->nobs = nobservables;
   h->dataset = dataset;
@@ -278,19 +272,10 @@ int sxmc_hist_create(const float* samples, size_t nsamples_floats, int samples_o
     h->stride[(size_t)i] = (int)std::min<long long>(st, INT_MAX);
   }
   total = (long long)h->stride[0] * nbins[0];
-  if (bad || total > INT_MAX) {
-    delete h;
-    return fail(SXMC_ERR_INVALID, "Histogram too large or negative bin count (total bins must fit in int).");
-  }
-  if (total == 0) {
-    delete h;
-    return fail(SXMC_ERR_INVALID, "Cannot make histogram with zero bins.");
-  }
+  SX_REQUIRE(!bad && total <= INT_MAX, "Histogram too large or negative bin count (total bins must fit in int).");
+  SX_REQUIRE(total != 0, "Cannot make histogram with zero bins.");
   for (int i = 0; i < nobservables; i++) {
-    if (!(upper[i] > lower[i])) {
-      delete h;
-      return fail(SXMC_ERR_INVALID, "Upper bound must be greater than lower bound.");
-    }
+    SX_REQUIRE(upper[i] > lower[i], "Upper bound must be greater than lower bound.");
     h->scale[(size_t)i] = nbins[i] / (upper[i] - lower[i]);  // pdfz.cpp:366-368, in host double
   }
   h->total_nbins = (int)total;
@@ -299,50 +284,30 @@ int sxmc_hist_create(const float* samples, size_t nsamples_floats, int samples_o
   h->nvec = (h->nsamples + SXMC_VEC - 1) / SXMC_VEC;
   h->pitch = std::max<size_t>(64, (h->nvec * SXMC_VEC + 63) / 64 * 64);
 
-  auto cleanup = [&](int code) {
-    if (h->d_bins) (void)hipFree(h->d_bins);
-    if (h->stream) (void)hipStreamDestroy(h->stream);
-    delete h;
-    return code;
-  };
-#define SX_HIP_H(expr)                                                                              \
-  do {                                                                                              \
-    hipError_t _e = (expr);                                                                         \
-    if (_e != hipSuccess)                                                                           \
-      return cleanup(fail(SXMC_ERR_HIP, std::string(#expr) + ": " + hipGetErrorString(_e)));        \
-  } while (0)
-
-  SX_HIP_H(hipStreamCreate(&h->stream));
+  SX_HIP(hipStreamCreate(&h->stream));
   h->store = std::make_shared<SampleStore>();
-  SX_HIP_H(hipMalloc((void**)&h->store->d_cols, sizeof(float) * h->pitch * (size_t)nfields));
-  SX_HIP_H(hipMalloc((void**)&h->d_bins, sizeof(unsigned) * (size_t)h->total_nbins));
-  SX_HIP_H(hipMemset(h->d_bins, 0, sizeof(unsigned) * (size_t)h->total_nbins));
+  SX_BUF(h->store->d_cols.alloc(h->pitch * (size_t)nfields));
+  SX_BUF(h->d_bins.alloc((size_t)h->total_nbins));
+  SX_HIP(hipMemset(h->d_bins.get(), 0, sizeof(unsigned) * (size_t)h->total_nbins));
   if (h->nsamples) {
     const float* d_aos = samples;
-    float* staging = nullptr;
+    DeviceBuffer<float> staging;
     if (!samples_on_device) {
-      SX_HIP_H(hipMalloc((void**)&staging, sizeof(float) * nsamples_floats));
-      hipError_t e = hipMemcpy(staging, samples, sizeof(float) * nsamples_floats, hipMemcpyHostToDevice);
-      if (e != hipSuccess) {
-        (void)hipFree(staging);
-        return cleanup(fail(SXMC_ERR_HIP, std::string("hipMemcpy samples: ") + hipGetErrorString(e)));
-      }
-      d_aos = staging;
+      SX_BUF(staging.alloc(nsamples_floats));
+      SX_HIP(hipMemcpy(staging.get(), samples, sizeof(float) * nsamples_floats, hipMemcpyHostToDevice));
+      d_aos = staging.get();
     }
-    hipError_t e = sx_launch_transpose(d_aos, h->store->d_cols, h->nsamples, nfields, h->pitch, h->stream);
-    if (e == hipSuccess) e = hipStreamSynchronize(h->stream);
-    if (staging) (void)hipFree(staging);
-    if (e != hipSuccess) return cleanup(fail(SXMC_ERR_HIP, std::string("transpose: ") + hipGetErrorString(e)));
+    SX_HIP(sx_launch_transpose(d_aos, h->store->d_cols.get(), h->nsamples, nfields, h->pitch, h->stream));
+    SX_HIP(hipStreamSynchronize(h->stream));
   }
-#undef SX_HIP_H
-  *out = h;
+  *out = h.release();
   return SXMC_OK;
 }
 
 int sxmc_hist_create_shared(sxmc_hist_t base, sxmc_hist_t* out) {
   SX_REQUIRE(base && out, "null argument");
   *out = nullptr;
-  sxmc_hist* h = new sxmc_hist;
+  auto h = std::make_unique<sxmc_hist>();
   h->store = base->store;  // one copy of the MC table for every evaluator that shares it
   h->nfields = base->nfields;
   h->nobs = base->nobs;
@@ -361,16 +326,10 @@ int sxmc_hist_create_shared(sxmc_hist_t base, sxmc_hist_t* out) {
   h->cfg_threads = base->cfg_threads;
   h->cfg_bpc = base->cfg_bpc;
   h->want_optimize = base->want_optimize;
-  hipError_t e = hipStreamCreate(&h->stream);
-  if (e == hipSuccess) e = hipMalloc((void**)&h->d_bins, sizeof(unsigned) * (size_t)h->total_nbins);
-  if (e == hipSuccess) e = hipMemset(h->d_bins, 0, sizeof(unsigned) * (size_t)h->total_nbins);
-  if (e != hipSuccess) {
-    if (h->d_bins) (void)hipFree(h->d_bins);
-    if (h->stream) (void)hipStreamDestroy(h->stream);
-    delete h;
-    return fail(SXMC_ERR_HIP, std::string("create_shared: ") + hipGetErrorString(e));
-  }
-  *out = h;
+  SX_HIP(hipStreamCreate(&h->stream));
+  SX_BUF(h->d_bins.alloc((size_t)h->total_nbins));
+  SX_HIP(hipMemset(h->d_bins.get(), 0, sizeof(unsigned) * (size_t)h->total_nbins));
+  *out = h.release();
   return SXMC_OK;
 }
 
@@ -388,15 +347,7 @@ int sxmc_hist_destroy(sxmc_hist_t h) {
   (void)hipStreamSynchronize(h->stream);
   forget_evaluator(h);
   if (h->self) sxmc_group_destroy(h->self);
-  if (h->d_bins) (void)hipFree(h->d_bins);
-  if (h->d_read_bins) (void)hipFree(h->d_read_bins);
-  for (void* p : h->retired) (void)hipFree(p);
-  if (h->d_cdf) (void)hipFree(h->d_cdf);
-  if (h->d_sample) (void)hipFree(h->d_sample);
-  if (h->d_marginal) (void)hipFree(h->d_marginal);
-  free_sparse(h);
-  if (h->stream) (void)hipStreamDestroy(h->stream);
-  delete h;
+  delete h;   // (its buffers, the retired ones and its stream with it)
   return SXMC_OK;
 }
 
@@ -449,15 +400,14 @@ int sxmc_hist_set_eval_points(sxmc_hist_t h, const float* points, size_t npoints
   // replaced in place: no device-wide synchronisation, and no hipFree / hipMalloc (both stall every stream of
   // the device) unless the new data set outgrows the buffer -- other chains on the GPU keep running.
   bool moved = !h->has_points;
-  if (n > h->read_bins_cap) {
-    if (h->d_read_bins) h->retired.push_back(h->d_read_bins);
-    h->d_read_bins = nullptr;
-    const size_t cap = std::max<size_t>(n + n / 4, 1024);
-    SX_HIP(hipMalloc((void**)&h->d_read_bins, sizeof(int) * cap));
-    h->read_bins_cap = cap;
+  if (n > h->d_read_bins.capacity()) {
+    // (not freed yet: the descriptors of other groups may still point at it)
+    if (h->d_read_bins) h->retired.push_back(std::move(h->d_read_bins));
+    h->has_points = false;   // (until the new table is filled: a failure below leaves an evaluator without points)
+    SX_BUF(h->d_read_bins.alloc(std::max<size_t>(n + n / 4, 1024)));
     moved = true;
   }
-  if (n) SX_HIP(hipMemcpy(h->d_read_bins, rb.data(), sizeof(int) * n, hipMemcpyHostToDevice));
+  if (n) SX_HIP(hipMemcpy(h->d_read_bins.get(), rb.data(), sizeof(int) * n, hipMemcpyHostToDevice));
   h->npoints = n;
   h->has_points = true;
   h->points_version++;
@@ -620,7 +570,7 @@ int sxmc_hist_get_bins(sxmc_hist_t h, unsigned* out, size_t n) {
                 "the histogram is not filled (the last evaluation counted only the event bins, or "
                 "sxmc_group_finish_step_async cleared it): evaluate with do_eval_pdf = 0");
   }
-  SX_HIP(hipMemcpy(out, h->d_bins, sizeof(unsigned) * n, hipMemcpyDeviceToHost));
+  SX_HIP(hipMemcpy(out, h->d_bins.get(), sizeof(unsigned) * n, hipMemcpyDeviceToHost));
   return SXMC_OK;
 }
 int sxmc_hist_project(sxmc_hist_t h, int obs, unsigned long long* h_counts, size_t n) {
@@ -634,27 +584,23 @@ int sxmc_hist_project(sxmc_hist_t h, int obs, unsigned long long* h_counts, size
                 "sxmc_group_finish_step_async cleared it): evaluate with do_eval_pdf = 0");
   }
   if (n == 0) return SXMC_OK;
-  if (n > h->cap_marginal) {
+  if (n > h->d_marginal.capacity()) {
     SX_HIP(hipStreamSynchronize(h->stream));   // (allocation next to queued work: settle it first)
-    if (h->d_marginal) SX_HIP(hipFree(h->d_marginal));
-    h->d_marginal = nullptr;
-    h->cap_marginal = 0;
-    SX_HIP(hipMalloc((void**)&h->d_marginal, sizeof(unsigned long long) * n));
-    h->cap_marginal = n;
+    SX_BUF(h->d_marginal.grow(n));
   }
   DeviceProps props;
   const unsigned cus = get_props(props) == SXMC_OK && props.cus > 0 ? (unsigned)props.cus : 256u;
-  SX_HIP(hipMemsetAsync(h->d_marginal, 0, sizeof(unsigned long long) * n, h->stream));
-  SX_HIP(sx_hist_project(h->d_bins, (unsigned long long)h->total_nbins, (unsigned)h->stride[(size_t)obs], (unsigned)n,
-                         h->d_marginal, cus * 8u, h->stream));
-  SX_HIP(hipMemcpyAsync(h_counts, h->d_marginal, sizeof(unsigned long long) * n, hipMemcpyDeviceToHost, h->stream));
+  SX_HIP(hipMemsetAsync(h->d_marginal.get(), 0, sizeof(unsigned long long) * n, h->stream));
+  SX_HIP(sx_hist_project(h->d_bins.get(), (unsigned long long)h->total_nbins, (unsigned)h->stride[(size_t)obs], (unsigned)n,
+                         h->d_marginal.get(), cus * 8u, h->stream));
+  SX_HIP(hipMemcpyAsync(h_counts, h->d_marginal.get(), sizeof(unsigned long long) * n, hipMemcpyDeviceToHost, h->stream));
   SX_HIP(hipStreamSynchronize(h->stream));
   return SXMC_OK;
 }
 int sxmc_hist_get_read_bins(sxmc_hist_t h, int* out, size_t n) {
   SX_REQUIRE(h && (out || n == 0), "null argument");
   SX_REQUIRE(h->has_points && n == h->npoints, "read_bins buffer size mismatch");
-  if (n) SX_HIP(hipMemcpy(out, h->d_read_bins, sizeof(int) * n, hipMemcpyDeviceToHost));
+  if (n) SX_HIP(hipMemcpy(out, h->d_read_bins.get(), sizeof(int) * n, hipMemcpyDeviceToHost));
   return SXMC_OK;
 }
 int sxmc_hist_get_samples(sxmc_hist_t h, float* out, size_t n) {
@@ -662,14 +608,12 @@ int sxmc_hist_get_samples(sxmc_hist_t h, float* out, size_t n) {
   SX_REQUIRE(h && (out || n == 0), "null argument");
   SX_REQUIRE(n == h->nsamples * ((size_t)h->nobs + 1), "samples buffer size mismatch");
   if (!n) return SXMC_OK;
-  float* tmp = nullptr;
-  SX_HIP(hipMalloc((void**)&tmp, sizeof(float) * n));
-  hipError_t e = sx_launch_untranspose_obs(h->store->d_cols, tmp, h->nsamples, h->nobs, h->pitch, (float)h->dataset,
-                                           h->stream);
-  if (e == hipSuccess) e = hipStreamSynchronize(h->stream);
-  if (e == hipSuccess) e = hipMemcpy(out, tmp, sizeof(float) * n, hipMemcpyDeviceToHost);
-  (void)hipFree(tmp);
-  if (e != hipSuccess) return fail(SXMC_ERR_HIP, std::string("get_samples: ") + hipGetErrorString(e));
+  DeviceBuffer<float> tmp;
+  SX_BUF(tmp.alloc(n));
+  SX_HIP(sx_launch_untranspose_obs(h->store->d_cols.get(), tmp.get(), h->nsamples, h->nobs, h->pitch, (float)h->dataset,
+                                   h->stream));
+  SX_HIP(hipStreamSynchronize(h->stream));
+  SX_HIP(hipMemcpy(out, tmp.get(), sizeof(float) * n, hipMemcpyDeviceToHost));
   return SXMC_OK;
 }
 int sxmc_hist_random_sample(sxmc_hist_t h, size_t nobserved, unsigned long long seed, const float* lowers,
@@ -682,17 +626,17 @@ int sxmc_hist_random_sample(sxmc_hist_t h, size_t nobserved, unsigned long long 
     return fail(SXMC_ERR_STATE, "the histogram is not filled: evaluate with do_eval_pdf = 0 first (CreateHistogram)");
   }
   if (nobserved == 0) return SXMC_OK;
-  if (!h->d_cdf) SX_HIP(hipMalloc((void**)&h->d_cdf, sizeof(unsigned) * (size_t)h->total_nbins));
-  SX_HIP(sx_hist_cdf(h->d_bins, h->d_cdf, h->total_nbins, h->stream));
+  if (!h->d_cdf.get()) SX_BUF(h->d_cdf.alloc((size_t)h->total_nbins));
+  SX_HIP(sx_hist_cdf(h->d_bins.get(), h->d_cdf.get(), h->total_nbins, h->stream));
   unsigned total = 0;
-  SX_HIP(hipMemcpy(&total, h->d_cdf + (h->total_nbins - 1), sizeof(unsigned), hipMemcpyDeviceToHost));
+  SX_HIP(hipMemcpy(&total, h->d_cdf.get() + (h->total_nbins - 1), sizeof(unsigned), hipMemcpyDeviceToHost));
   SX_REQUIRE(total > 0, "cannot sample an empty histogram");
   const size_t row = (size_t)h->nobs + 1;
   float* d_rows = nullptr;
   unsigned* d_exhausted = nullptr;
   int rc = sample_buffer(h, nobserved, row, d_rows, d_exhausted);
   if (rc) return rc;
-  SX_HIP(sx_random_sample(h->d_cdf, h->total_nbins, h->nobs, h->nbins.data(), h->lower.data(), h->upper.data(),
+  SX_HIP(sx_random_sample(h->d_cdf.get(), h->total_nbins, h->nobs, h->nbins.data(), h->lower.data(), h->upper.data(),
                           h->scale.data(), lowers, uppers, seed, nobserved, (float)h->dataset, d_rows, d_exhausted,
                           h->stream));
   return sample_read_back(h, nobserved, row, " (the reference would redraw for ever, pdfz.cpp:838-905): the cuts leave "

@@ -14,24 +14,17 @@ extern "C" {
 int sxmc_group_create(const sxmc_hist_t* members, int nmembers, sxmc_group_t* out) {
   SX_REQUIRE(out && nmembers >= 0 && (members || nmembers == 0), "bad arguments");
   for (int i = 0; i < nmembers; i++) SX_REQUIRE(members[i], "null member");
-  sxmc_group* g = new sxmc_group;
+  *out = nullptr;
+  auto g = std::make_unique<sxmc_group>();
   g->members.assign(members, members + nmembers);
-  hipError_t e = hipMalloc((void**)&g->d_ticket, 256);
-  if (e == hipSuccess) e = hipMemset(g->d_ticket, 0, 256);
-  if (e == hipSuccess) e = hipMalloc((void**)&g->d_step_sums, 1024 * sizeof(double));
+  SX_BUF(g->d_ticket.alloc(64));
+  SX_HIP(hipMemset(g->d_ticket.get(), 0, 256));
+  SX_BUF(g->d_step_sums.alloc(1024));
   // (the cooperative step end's hand-over slots, 128 workers at most: see step_end_is_cooperative)
-  if (e == hipSuccess) e = hipMalloc((void**)&g->d_coop_slots, sizeof(unsigned long long) * 128);
-  if (e == hipSuccess) e = hipMalloc((void**)&g->d_coop_last, sizeof(double) * 128);
-  if (e == hipSuccess) e = sx_step_end_slots_init(g->d_coop_slots, g->d_coop_last, 128);
-  if (e != hipSuccess) {
-    if (g->d_ticket) (void)hipFree(g->d_ticket);
-    if (g->d_step_sums) (void)hipFree(g->d_step_sums);
-    if (g->d_coop_slots) (void)hipFree(g->d_coop_slots);
-    if (g->d_coop_last) (void)hipFree(g->d_coop_last);
-    delete g;
-    return fail(SXMC_ERR_HIP, std::string("group allocation: ") + hipGetErrorString(e));
-  }
-  *out = g;
+  SX_BUF(g->d_coop_slots.alloc(128));
+  SX_BUF(g->d_coop_last.alloc(128));
+  SX_HIP(sx_step_end_slots_init(g->d_coop_slots.get(), g->d_coop_last.get(), 128));
+  *out = g.release();
   return SXMC_OK;
 }
 
@@ -40,26 +33,7 @@ int sxmc_group_destroy(sxmc_group_t g) {
   if (!g) return SXMC_OK;
   (void)hipDeviceSynchronize();
   if (g->coop_fits >= 0) g_stepping_groups.fetch_sub(1, std::memory_order_acq_rel);
-  for (LaunchClass& c : g->classes) free_class(c);
-  if (g->h_pin) (void)hipHostFree(g->h_pin);
-  if (g->twin) {   // (the ordered twin of a boxed plan: planned, never launched by itself)
-    for (LaunchClass& c : g->twin->classes) free_class(c);
-    if (g->twin->d_descs) (void)hipFree(g->twin->d_descs);
-    if (g->twin->d_descs_sparse) (void)hipFree(g->twin->d_descs_sparse);
-    delete g->twin;
-    g->twin = nullptr;
-  }
-  if (g->d_descs) (void)hipFree(g->d_descs);
-  if (g->d_descs_sparse) (void)hipFree(g->d_descs_sparse);
-  if (g->d_ticket) (void)hipFree(g->d_ticket);
-  if (g->d_step_sums) (void)hipFree(g->d_step_sums);
-  if (g->d_coop_slots) (void)hipFree(g->d_coop_slots);
-  if (g->d_coop_last) (void)hipFree(g->d_coop_last);
-  free_event_classes(g->ec[0]);
-  free_event_classes(g->ec[1]);
-  for (hipEvent_t e : g->ev0) (void)hipEventDestroy(e);
-  for (hipEvent_t e : g->ev1) (void)hipEventDestroy(e);
-  delete g;
+  delete g;   // (its buffers, its events and the ordered twin of a boxed plan with it)
   return SXMC_OK;
 }
 
@@ -250,9 +224,9 @@ static int box_image_width(sxmc_group* g, double* width) {
     hi_idx = std::max(hi_idx, (int)d.syst[q].pars[0]);
   }
   if (hi_idx < 0 || d.param_stride < 1 || (long)(hi_idx - lo_idx) * d.param_stride >= 256) return SXMC_OK;
-  if (!g->h_pin) SX_HIP(hipHostMalloc((void**)&g->h_pin, 256 * sizeof(double)));
+  if (!g->h_pin) SX_BUF(g->h_pin.alloc(256));
   const size_t span = (size_t)(hi_idx - lo_idx) * (size_t)d.param_stride + 1;
-  SX_HIP(hipMemcpyAsync(g->h_pin, d.params + (long)lo_idx * d.param_stride, span * sizeof(double), hipMemcpyDeviceToHost,
+  SX_HIP(hipMemcpyAsync(g->h_pin.get(), d.params + (long)lo_idx * d.param_stride, span * sizeof(double), hipMemcpyDeviceToHost,
                         g->last_stream));
   SX_HIP(hipStreamSynchronize(g->last_stream));
   double xl = 0.5 * (d.lower[cls->box_obs] + d.upper[cls->box_obs]), xh = xl + (double)cls->box_dx;
@@ -261,7 +235,7 @@ static int box_image_width(sxmc_group* g, double* width) {
   for (int q = 0; q < d.nsyst && fin; q++) {
     const SxSystOp& op = d.syst[q];
     if (op.obs_slot != cls->box_obs) continue;
-    const double c0 = g->h_pin[(size_t)((int)op.pars[0] - lo_idx) * (size_t)d.param_stride];
+    const double c0 = g->h_pin.get()[(size_t)((int)op.pars[0] - lo_idx) * (size_t)d.param_stride];
     const double pc = 0.0 + c0 * 1.0;
     if (op.type == SXMC_SYST_SHIFT) {
       xl = xl + pc;
@@ -392,7 +366,7 @@ int sxmc_group_launch_info(sxmc_group_t g, char* out, size_t n) {
   std::string text;
   // (a plan with two forms: the launches of the form that runs now, its table named with the other form beside it)
   const bool two = g->twin && !g->twin->classes.empty() && g->plan_cfg.box < 0;
-  const sxmc_group* plan = (two && g->fill_form == 2) ? g->twin : g;
+  const sxmc_group* plan = (two && g->fill_form == 2) ? g->twin.get() : g;
   for (size_t i = 0; i < plan->classes.size(); i++) {
     const LaunchClass& c = plan->classes[i];
     char line[512];
@@ -400,7 +374,7 @@ int sxmc_group_launch_info(sxmc_group_t g, char* out, size_t n) {
     std::snprintf(line, sizeof line,
                   "launch %zu: members=%zu nobs=%d nslot=%d hist=%s program=%s table=%s%s threads=%d grid=%d partition=%d teams=%d lds=%zu layout=0x%08X\n",
                   i, c.member_idx.size(), c.shape.nobs, c.shape.nslot, c.shape.lds_hist ? "lds" : "global", kind,
-                  table_name(c, two && plan == g->twin),
+                  table_name(c, two && plan == g->twin.get()),
                   c.runs_mode ? (c.shape.rtc_sparse ? "+runs(runtime)" : "+runs(builtin)") : "", c.shape.threads,
                   c.shape.grid, c.partition, c.teams, (size_t)c.shape.lds_bytes, c.shape.lds_layout);
     text += line;
@@ -460,7 +434,7 @@ int sxmc_group_eval_async(sxmc_group_t g, int do_eval_pdf, sxmc_stream_t s) {
   if (rc) return rc;
   // pdfz.cpp:474-476: no lookup without evaluation points or when do_eval_pdf is false
   if (do_eval_pdf && g->max_points > 0) {
-    SX_HIP(sx_launch_eval_pdf(sparse ? g->d_descs_sparse : g->d_descs, (int)g->members.size(), g->max_points, st));
+    SX_HIP(sx_launch_eval_pdf(sparse ? g->d_descs_sparse.get() : g->d_descs.get(), (int)g->members.size(), g->max_points, st));
   }
   return SXMC_OK;
 }
@@ -489,15 +463,15 @@ int sxmc_group_eval_nll_async(sxmc_group_t g, sxmc_stream_t s, const double* d_p
   SX_REQUIRE(g->members.size() <= 1024, "too many members for the fused evaluation");
   // lookup table wanted: one pass over the events in order; otherwise over the distinct bin tuples
   unsigned long long ne = g->members[0]->npoints;
-  const SxSignalDesc* descs = sparse ? g->d_descs_sparse : g->d_descs;
+  const SxSignalDesc* descs = sparse ? g->d_descs_sparse.get() : g->d_descs.get();
   const unsigned* weight = nullptr;
   if (!g->cfg_lut) {
     rc = ensure_event_classes(g, sparse);
     if (rc) return rc;
     const sxmc_group::EventClasses& ec = g->ec[sparse ? 1 : 0];
     ne = ec.K;
-    descs = ec.d_descs;
-    weight = ec.d_weight;
+    descs = ec.d_descs.get();
+    weight = ec.d_weight.get();
   }
   const int block = 128;
   const int grid = (int)std::min<unsigned long long>(1024, std::max<unsigned long long>(1, (ne + block - 1) / block));
@@ -530,15 +504,15 @@ int sxmc_group_mcmc_step_async(sxmc_group_t g, sxmc_stream_t s, const double* d_
   g->last_stream = st;
   const bool sparse = g->sparse_ready && g->cfg_sparse;
   unsigned long long ne = g->members[0]->npoints;
-  const SxSignalDesc* descs = sparse ? g->d_descs_sparse : g->d_descs;
+  const SxSignalDesc* descs = sparse ? g->d_descs_sparse.get() : g->d_descs.get();
   const unsigned* weight = nullptr;
   if (!g->cfg_lut) {
     rc = ensure_event_classes(g, sparse);
     if (rc) return rc;
     const sxmc_group::EventClasses& ec = g->ec[sparse ? 1 : 0];
     ne = ec.K;
-    descs = ec.d_descs;
-    weight = ec.d_weight;
+    descs = ec.d_descs.get();
+    weight = ec.d_weight.get();
   }
   rc = group_fill(g, st, sparse);  // zero (also clears the ticket) + fill
   if (rc) return rc;
@@ -564,7 +538,7 @@ int sxmc_group_mcmc_step_async(sxmc_group_t g, sxmc_stream_t s, const double* d_
   a.n_mc = d_n_mc;
   a.source_id = d_source_id;
   a.norms = d_norms;
-  SX_HIP(sx_launch_eval_nll_finish(descs, (int)g->members.size(), ne, weight, g->d_step_sums, g->d_ticket, a, grid,
+  SX_HIP(sx_launch_eval_nll_finish(descs, (int)g->members.size(), ne, weight, g->d_step_sums.get(), g->d_ticket.get(), a, grid,
                                    block, st));
   return SXMC_OK;
 }
@@ -605,8 +579,8 @@ int sxmc_group_finish_step_async(sxmc_group_t g, sxmc_stream_t s, size_t npartia
   a.source_id = d_source_id;
   a.norms = d_norms;
   const bool sparse = g->last_sparse;
-  SX_HIP(sx_launch_finish_zero(sparse ? g->d_descs_sparse : g->d_descs, (int)g->members.size(),
-                               sparse ? g->max_bins_sparse : g->max_bins, npartial_sums, d_sums, g->d_ticket, a, 128,
+  SX_HIP(sx_launch_finish_zero(sparse ? g->d_descs_sparse.get() : g->d_descs.get(), (int)g->members.size(),
+                               sparse ? g->max_bins_sparse : g->max_bins, npartial_sums, d_sums, g->d_ticket.get(), a, 128,
                                (hipStream_t)s));
   g->prezeroed = sparse ? 2 : 1;
   for (sxmc_hist* h : g->members) {
@@ -705,18 +679,18 @@ int group_step_tail(sxmc_group* g, hipStream_t st, bool sparse, const SxSignalDe
   } else if (step_end_is_cooperative(g, ne)) {
     // ONE launch: the event sum's workgroups + a finisher that waits for them inside the kernel (step_end_kernel)
     const int nvb = step_sum_blocks(ne);
-    SX_HIP(sx_launch_step_end(descs, sparse ? g->d_descs_sparse : g->d_descs, (int)g->members.size(),
-                              sparse ? g->max_bins_sparse : g->max_bins, ne, weight, g->d_coop_slots, g->d_coop_last,
-                              g->d_ticket, nvb, a, st));
+    SX_HIP(sx_launch_step_end(descs, sparse ? g->d_descs_sparse.get() : g->d_descs.get(), (int)g->members.size(),
+                              sparse ? g->max_bins_sparse : g->max_bins, ne, weight, g->d_coop_slots.get(), g->d_coop_last.get(),
+                              g->d_ticket.get(), nvb, a, st));
     g->last_step_launches += 1;
   } else {
     g->last_step_launches += 2;
     const int block = 128;
     const int grid = step_sum_blocks(ne);
     SX_HIP(sx_launch_eval_nll(descs, (int)g->members.size(), ne, weight, a.v_proposed, a.nexpected, a.n_mc, a.source_id,
-                              a.norms, g->d_step_sums, grid, block, st));
-    SX_HIP(sx_launch_finish_zero(sparse ? g->d_descs_sparse : g->d_descs, (int)g->members.size(),
-                                 sparse ? g->max_bins_sparse : g->max_bins, (size_t)grid, g->d_step_sums, g->d_ticket, a,
+                              a.norms, g->d_step_sums.get(), grid, block, st));
+    SX_HIP(sx_launch_finish_zero(sparse ? g->d_descs_sparse.get() : g->d_descs.get(), (int)g->members.size(),
+                                 sparse ? g->max_bins_sparse : g->max_bins, (size_t)grid, g->d_step_sums.get(), g->d_ticket.get(), a,
                                  128, st));
   }
   g->prezeroed = sparse ? 2 : 1;
@@ -753,15 +727,15 @@ int sxmc_group_step_async(sxmc_group_t g, sxmc_stream_t s, const double* d_means
   g->last_stream = st;
   const bool sparse = g->sparse_ready && g->cfg_sparse;
   unsigned long long ne = g->members[0]->npoints;
-  const SxSignalDesc* descs = sparse ? g->d_descs_sparse : g->d_descs;
+  const SxSignalDesc* descs = sparse ? g->d_descs_sparse.get() : g->d_descs.get();
   const unsigned* weight = nullptr;
   if (!g->cfg_lut) {
     rc = ensure_event_classes(g, sparse);  // (may upload tables: before anything is launched)
     if (rc) return rc;
     const sxmc_group::EventClasses& ec = g->ec[sparse ? 1 : 0];
     ne = ec.K;
-    descs = ec.d_descs;
-    weight = ec.d_weight;
+    descs = ec.d_descs.get();
+    weight = ec.d_weight.get();
   }
   const bool zero_launched = g->prezeroed != (sparse ? 2 : 1);   // (group_fill decides the same way, plus bookkeeping)
   SxStepArgs a;
@@ -793,8 +767,8 @@ int sxmc_group_step_async(sxmc_group_t g, sxmc_stream_t s, const double* d_means
     LaunchClass& c = g->classes[0];
     const int nvb = step_sum_blocks(ne);
     g->h_tail.resize(sx_tail_args_bytes());   // (passed to the kernel by value: frozen at capture like every argument)
-    sx_tail_args_fill(g->h_tail.data(), descs, g->d_descs, (int)g->members.size(), g->max_bins, ne, weight,
-                      g->d_coop_slots, g->d_coop_last, g->d_ticket, nvb, a);
+    sx_tail_args_fill(g->h_tail.data(), descs, g->d_descs.get(), (int)g->members.size(), g->max_bins, ne, weight,
+                      g->d_coop_slots.get(), g->d_coop_last.get(), g->d_ticket.get(), nvb, a);
     c.shape.tail = g->h_tail.data();
     c.shape.tail_blocks = nvb + 1;
   }
@@ -815,7 +789,7 @@ int sxmc_group_step_async(sxmc_group_t g, sxmc_stream_t s, const double* d_means
     g->split_events.push_back(ev);
     SX_HIP(hipEventRecord(ev, g->split_fill_stream));
     SX_HIP(hipStreamWaitEvent(st, ev, 0));
-    a.gate = g->d_ticket + 8;
+    a.gate = g->d_ticket.get() + 8;
     a.gate_value = (unsigned)node + 1u;
     g->last_step_launches = (int)g->classes.size() + (zero_launched ? 1 : 0);
     return group_step_tail(g, st, sparse, descs, ne, weight, a);
@@ -874,10 +848,10 @@ int sxmc_group_step_end_timeouts(sxmc_group_t g, sxmc_stream_t s, unsigned* time
   if (s) {
     // on the chain's own stream: a copy through the legacy stream is what the runtime refuses while ANOTHER host
     // thread records a graph on a blocking stream (see sxmc_graph_begin_capture)
-    SX_HIP(hipMemcpyAsync(timeouts, g->d_ticket + 6, sizeof(unsigned), hipMemcpyDeviceToHost, (hipStream_t)s));
+    SX_HIP(hipMemcpyAsync(timeouts, g->d_ticket.get() + 6, sizeof(unsigned), hipMemcpyDeviceToHost, (hipStream_t)s));
     SX_HIP(hipStreamSynchronize((hipStream_t)s));
   } else {
-    SX_HIP(hipMemcpy(timeouts, g->d_ticket + 6, sizeof(unsigned), hipMemcpyDeviceToHost));
+    SX_HIP(hipMemcpy(timeouts, g->d_ticket.get() + 6, sizeof(unsigned), hipMemcpyDeviceToHost));
   }
   if (*timeouts != 0u) {
     // A wait inside a cooperative step end gave up: the steps since the last check are not valid (a finisher that gave
@@ -887,8 +861,8 @@ int sxmc_group_step_end_timeouts(sxmc_group_t g, sxmc_stream_t s, unsigned* time
     // pre-zeroed, and the two-launch step end from now on.
     hipStream_t st = (hipStream_t)s;
     SX_HIP(hipStreamSynchronize(g->last_stream));
-    SX_HIP(sx_step_end_slots_init(g->d_coop_slots, g->d_coop_last, 128));
-    SX_HIP(hipMemsetAsync(g->d_ticket, 0, 256, st));
+    SX_HIP(sx_step_end_slots_init(g->d_coop_slots.get(), g->d_coop_last.get(), 128));
+    SX_HIP(hipMemsetAsync(g->d_ticket.get(), 0, 256, st));
     SX_HIP(hipStreamSynchronize(st));
     g->prezeroed = 0;
     for (sxmc_hist* h : g->members) h->cleared_by = nullptr;
@@ -975,7 +949,7 @@ int sxmc_group_algorithmic_bytes(sxmc_group_t g, double* fill_read, double* hist
   if (g->twin && !g->twin->classes.empty() && g->plan_cfg.box < 0 && g->fill_form == 2) {
     // (the ordered twin's tables are what the fill streams now; histogram and event bytes do not depend on the form)
     double fr2 = 0, hb2 = 0, ev2 = 0, fr1 = 0;
-    rc = sxmc_group_algorithmic_bytes(g->twin, &fr2, &hb2, &ev2);
+    rc = sxmc_group_algorithmic_bytes(g->twin.get(), &fr2, &hb2, &ev2);
     if (rc) return rc;
     g->fill_form = 1;
     rc = sxmc_group_algorithmic_bytes(g, &fr1, hist, event);

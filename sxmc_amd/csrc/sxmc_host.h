@@ -10,6 +10,8 @@
 //   sxmc_multigroup.cpp   lockstep chains and the look-ahead pass
 //   sxmc_nll_api.cpp      the NLL launch points with the reference's argument lists; the measurement build's test hooks
 //   sxmc_kde.cpp          the kernel-density evaluator (sxmc_kde_*) behind pdfz::EvalKernel
+// Every allocation these hold is owned by a buffer (device_buffer.h over the policies below); layout_kernels.hip's host
+// helpers take their temporaries from the same type.
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -31,6 +33,7 @@
 
 #include <rocprofiler-sdk-roctx/roctx.h>
 
+#include "device_buffer.h"
 #include "sxmc_device.h"
 #include "sxmc_plan.h"
 
@@ -96,14 +99,18 @@ struct TraceRange {
 
 }  // namespace sxhost
 
-#define SX_HIP(expr)                                                                                                \
+#define SX_HIP_STATUS_(e, text)                                                                                     \
   do {                                                                                                              \
-    hipError_t _e = (expr);                                                                                         \
+    hipError_t _e = (e);                                                                                            \
     if (_e != hipSuccess) {                                                                                         \
-      return ::sxhost::fail(SXMC_ERR_HIP, std::string(#expr) + ": " + hipGetErrorString(_e) + " (" __FILE__ ":" +    \
+      return ::sxhost::fail(SXMC_ERR_HIP, std::string(text) + ": " + hipGetErrorString(_e) + " (" __FILE__ ":" +     \
                                               std::to_string(__LINE__) + ")");                                       \
     }                                                                                                               \
   } while (0)
+// a call of the runtime: anything but a hipError_t does not compile
+#define SX_HIP(expr) SX_HIP_STATUS_(expr, #expr)
+// a buffer's alloc / grow / reset, which hands the runtime's status on as the int of device_buffer.h's policies
+#define SX_BUF(expr) SX_HIP_STATUS_(::sxhost::buffer_status(expr), #expr)
 
 #define SX_REQUIRE(cond, msg)                                  \
   do {                                                         \
@@ -111,6 +118,22 @@ struct TraceRange {
   } while (0)
 
 namespace sxhost {
+// Who owns device memory: a buffer as a member of the handle that uses it, or as a local for a temporary.  Freed when
+// the owner dies; a hipFree stalls every stream of the device, so the grow-only members are never shrunk.
+struct DeviceMem {
+  static int allocate(void** p, size_t bytes) { return (int)hipMalloc(p, bytes); }
+  static int free(void* p) { return (int)hipFree(p); }
+};
+struct PinnedMem {
+  static int allocate(void** p, size_t bytes) { return (int)hipHostMalloc(p, bytes, hipHostMallocDefault); }
+  static int free(void* p) { return (int)hipHostFree(p); }
+};
+template <typename T>
+using DeviceBuffer = sxbuf::Buffer<T, DeviceMem>;
+template <typename T>
+using PinnedBuffer = sxbuf::Buffer<T, PinnedMem>;
+inline hipError_t buffer_status(int status) { return static_cast<hipError_t>(status); }   // (SX_BUF)
+
 constexpr int kLdsMaxBins = 40960 - 128;  // 160 KiB of LDS per workgroup minus header and trash words
 
 struct HostSyst {
@@ -131,19 +154,19 @@ int get_props(DeviceProps& p);
 // pre-binned column.  Shared by evaluators created with sxmc_hist_create_shared, so that several
 // chains / experiments on one GPU read ONE copy of the MC tables.
 struct SampleStore {
-  float* d_cols = nullptr;
+  sxhost::DeviceBuffer<float> d_cols;
   // pre-binned columns built so far, one per (observable mask, width); kept until the table dies because
   // descriptors of other groups may point at them
   struct PreColumn {
     unsigned mask;
     int width;
-    void* ptr;
+    sxhost::DeviceBuffer<void> ptr;
   };
   std::vector<PreColumn> pre;
   std::mutex pre_mutex;  // evaluators sharing the table may be set up from different host threads
   void* find_pre(unsigned mask, int width) const {
     for (const PreColumn& p : pre)
-      if (p.mask == mask && p.width == width) return p.ptr;
+      if (p.mask == mask && p.width == width) return p.ptr.get();
     return nullptr;
   }
   // Bucketing (layout_kernels.hip).  The SORT of the rows by the untouched observables' bin indices is done once
@@ -155,7 +178,7 @@ struct SampleStore {
     int box_truth = -1;             // >= 0: `ordered` is a BOXED observable (fill_boxed_kernel) and this the truth field
                                     // its resolution scale reads: rows of a bucket go by (stratum of x - t, x)
     bool rejected = true;
-    unsigned* d_rows = nullptr;     // [nsamples] row numbers in sorted order (rows outside the domain last)
+    sxhost::DeviceBuffer<unsigned> d_rows;   // [nsamples] row numbers in sorted order (rows outside the domain last)
     size_t nkept = 0;               // rows inside the domain of every untouched observable
     unsigned nkeys_total = 0;       // size of the key space (= the key of "outside")
     unsigned radix[SXMC_MAX_NFIELDS] = {0};
@@ -171,18 +194,18 @@ struct SampleStore {
     int runs = 1;                   // granule order transposed for this many runs (1 = sorted order)
     bool complete = false;
     const BucketSort* sort = nullptr;
-    float* d_cols = nullptr;        // [fields.size()][pitch]
+    sxhost::DeviceBuffer<float> d_cols;     // [fields.size()][pitch]
     size_t pitch = 0;
-    unsigned* d_gpre = nullptr;     // [ngranules] bin offset of the granule
-    unsigned* d_gkp = nullptr;      // [ngranules] pairs {bucket key, bin offset}
-    float* d_gedge = nullptr;       // [ngranules] pairs {first, last} value of the sort's ordered observable
-    float* d_gbox = nullptr;        // [ngranules] {xmin, xmax, tmin, tmax} of the sort's boxed observable and its truth field
+    sxhost::DeviceBuffer<unsigned> d_gpre;  // [ngranules] bin offset of the granule
+    sxhost::DeviceBuffer<unsigned> d_gkp;   // [ngranules] pairs {bucket key, bin offset}
+    sxhost::DeviceBuffer<float> d_gedge;    // [ngranules] pairs {first, last} value of the sort's ordered observable
+    sxhost::DeviceBuffer<float> d_gbox;     // [ngranules] {xmin, xmax, tmin, tmax} of the sort's boxed observable and its truth field
     double box_dx = 0, box_dt = 0;  // ... their mean extents over the granules with finite boxes
     bool q16 = false;               // d_qcol holds ONE 16-bit code per row of field 0 (boxed tables)
     size_t ngranules = 0;           // physical granules (with the runs' padding)
     size_t nkept = 0;               // samples in the copy
     // CODES (fill_ordered_body): the streamed fields once more as 16-bit codes, two per word; built on demand
-    unsigned* d_qcol = nullptr;     // [(nq + 1) / 2][pitch]
+    sxhost::DeviceBuffer<unsigned> d_qcol;  // [(nq + 1) / 2][pitch]
     int nq = 0;                     // fields coded (the streamed ones: all but the ordered observable's)
     bool codes_tried = false;
     double qbase[SXMC_MAX_QSLOTS] = {0}, qstep[SXMC_MAX_QSLOTS] = {0};
@@ -200,20 +223,6 @@ struct SampleStore {
       if (b->sort == sort && b->fields == fields && b->runs == runs) return b.get();
     return nullptr;
   }
-  ~SampleStore() {
-    if (d_cols) (void)hipFree(d_cols);
-    for (PreColumn& p : pre) (void)hipFree(p.ptr);
-    for (auto& b : bucketed) {
-      if (b->d_cols) (void)hipFree(b->d_cols);
-      if (b->d_gpre) (void)hipFree(b->d_gpre);
-      if (b->d_gkp) (void)hipFree(b->d_gkp);
-      if (b->d_gedge) (void)hipFree(b->d_gedge);
-      if (b->d_gbox) (void)hipFree(b->d_gbox);
-      if (b->d_qcol) (void)hipFree(b->d_qcol);
-    }
-    for (auto& b : sorts)
-      if (b->d_rows) (void)hipFree(b->d_rows);
-  }
 };
 
 struct sxmc_hist {
@@ -225,15 +234,14 @@ struct sxmc_hist {
   std::vector<int> nbins, stride;
   int total_nbins = 0;
   double bin_volume = 0;
-  unsigned* d_bins = nullptr;
-  int* d_read_bins = nullptr;
-  size_t read_bins_cap = 0;        // (grow-only: a new data set of about the same size re-uses the buffer)
-  std::vector<void*> retired;      // outgrown device buffers, freed with the evaluator
-  unsigned* d_cdf = nullptr;       // prefix sums of the histogram, for sxmc_hist_random_sample
-  float* d_sample = nullptr;       // ... and the events drawn, a kernel-density evaluator's too (sxhost::sample_buffer;
-  size_t cap_sample = 0;           // grow-only: a fake experiment per walk draws about as many), bytes
-  unsigned long long* d_marginal = nullptr;   // sxmc_hist_project's totals along one observable (grow-only)
-  size_t cap_marginal = 0;
+  sxhost::DeviceBuffer<unsigned> d_bins;
+  sxhost::DeviceBuffer<int> d_read_bins;   // (grow-only: a new data set of about the same size re-uses the buffer)
+  std::vector<sxhost::DeviceBuffer<int>> retired;   // outgrown d_read_bins: other groups' descriptors may still point at
+                                                    // them, so they are freed with the evaluator
+  sxhost::DeviceBuffer<unsigned> d_cdf;    // prefix sums of the histogram, for sxmc_hist_random_sample
+  sxhost::DeviceBuffer<void> d_sample;     // ... and the events drawn, a kernel-density evaluator's too (sxhost::sample_buffer;
+                                           // grow-only: a fake experiment per walk draws about as many), bytes
+  sxhost::DeviceBuffer<unsigned long long> d_marginal;   // sxmc_hist_project's totals along one observable (grow-only)
   bool has_points = false;
   size_t npoints = 0;
   float* pdf = nullptr;
@@ -250,16 +258,16 @@ struct sxmc_hist {
   bool outputs_host_visible = false;   // a bound output (norm, pdf values) lies in memory the host reads directly
   bool want_optimize = true;       // EvalHist's `optimize` (pdfz.cpp:188, 441-448): trial launches at the first evaluation
   // sparse counting (histogram too large for LDS): one counter per distinct event bin
-  unsigned* d_cnt = nullptr;       // [ntargets]
-  int* d_read_slot = nullptr;      // [npoints]: counter slot of each event, or -1 / -2
-  unsigned* d_filter = nullptr;
-  unsigned* d_table = nullptr;
-  unsigned* d_coarse = nullptr;    // coarse filter staged in LDS by the fill kernel
+  sxhost::DeviceBuffer<unsigned> d_cnt;    // [ntargets]
+  sxhost::DeviceBuffer<int> d_read_slot;   // [npoints]: counter slot of each event, or -1 / -2
+  sxhost::DeviceBuffer<unsigned> d_filter;
+  sxhost::DeviceBuffer<unsigned> d_table;
+  sxhost::DeviceBuffer<unsigned> d_coarse; // coarse filter staged in LDS by the fill kernel
   int ntargets = 0, filter_shift = 0, table_shift = 0, coarse_shift = 0;
   // the event bins grouped by bucket, for sparse counting over a bucketed table walked in runs (fill_sparse_kernel)
-  unsigned* d_bdir = nullptr;      // [nkeys + 1] pairs {first table entry, log2 size | flag}
-  unsigned* d_btkeys = nullptr;
-  unsigned* d_btslot = nullptr;
+  sxhost::DeviceBuffer<unsigned> d_bdir;   // [nkeys + 1] pairs {first table entry, log2 size | flag}
+  sxhost::DeviceBuffer<unsigned> d_btkeys;
+  sxhost::DeviceBuffer<unsigned> d_btslot;
   unsigned btab_mask = 0;
   unsigned long long btab_points_version = 0;
   bool btab_valid = false;
@@ -273,6 +281,9 @@ struct sxmc_hist {
   // sxmc_hist_eval_async defers (see "deferred evaluations" below)
   std::shared_ptr<struct DeferredBatch> deferred;  // the host thread's batch of evaluations not launched yet it sits in
   std::shared_ptr<struct BatchInFlight> inflight;  // the batched launch the last sxmc_hist_eval_async went into
+  ~sxmc_hist() {   // (releases only: what must happen before them is sxmc_hist_destroy's)
+    if (stream) (void)hipStreamDestroy(stream);
+  }
 };
 
 // A host thread's evaluations asked for and not launched yet (sxmc_hist_eval_async).  Filled and launched by its
@@ -301,10 +312,10 @@ struct LaunchClass {
   bool prog_simple = false;
   unsigned pre_mask = 0;       // observables no systematic writes, streamed as one pre-binned column
   std::vector<int> member_idx;
-  SxSignalDesc* d_descs = nullptr;
-  SxSignalDesc* d_descs_sparse = nullptr;  // same members, sparse flavour (global-histogram classes)
-  SxSegment* d_segs = nullptr;
-  unsigned* d_blk_off = nullptr;
+  DeviceBuffer<SxSignalDesc> d_descs;
+  DeviceBuffer<SxSignalDesc> d_descs_sparse;  // same members, sparse flavour (global-histogram classes)
+  DeviceBuffer<SxSegment> d_segs;
+  DeviceBuffer<unsigned> d_blk_off;
   unsigned long long total_vec = 0;
   int partition = 0;  // 1 sliced, 2 interleaved (what build_partition chose)
   bool light = false; // a pure stream: runs best with few waves per CU (see class_waves_per_cu)
@@ -317,8 +328,6 @@ struct LaunchClass {
   unsigned padded_rstride = 0;  // ... with the LDS histogram in the padded form: words between its replicas (0: not)
   int max_bins = 0;             // the largest histogram of the members
 };
-
-void free_class(LaunchClass& c);
 
 // The settings a group's launch plan depends on: a plan built with other values than these is out of date (group_refresh).
 struct PlanConfig {
@@ -346,8 +355,8 @@ struct sxmc_group {
   std::vector<unsigned long long> seen;
   std::vector<unsigned long long> seen_points;   // members' points_version at the last (re)plan
   std::vector<SxSignalDesc> h_descs;
-  SxSignalDesc* d_descs = nullptr;  // member order: zero / eval kernels
-  SxSignalDesc* d_descs_sparse = nullptr;  // member order, sparse flavour where a member supports it
+  sxhost::DeviceBuffer<SxSignalDesc> d_descs;  // member order: zero / eval kernels
+  sxhost::DeviceBuffer<SxSignalDesc> d_descs_sparse;  // member order, sparse flavour where a member supports it
   bool sparse_ready = false;        // some member has sparse structures and all of those have points
   int max_bins_sparse = 0;
   int cfg_sparse = 1;               // count only the event bins when evaluating for lookup
@@ -355,11 +364,11 @@ struct sxmc_group {
   sxhost::PlanConfig plan_cfg, plan_cfg_seen;      // the settings the plan depends on, and those the current plan was built with
   bool order_blocked = false;                      // a plan with ordered tables beyond LDS could not be laid out in runs
   bool box_blocked = false;                        // a plan with boxed tables found no room for its codes / LDS form: planned again without
-  sxmc_group* twin = nullptr;                      // boxed plan, plan_cfg.box < 0: the same members planned in the ORDERED form (owned);
+  std::unique_ptr<sxmc_group> twin;                // boxed plan, plan_cfg.box < 0: the same members planned in the ORDERED form (owned);
                                                    // group_fill launches the one or the other (fill_form)
   bool is_twin = false;
   int fill_form = 2;                               // 1: the boxed plan's launches, 2: the twin's (where there is a twin)
-  double* h_pin = nullptr;                         // pinned host words sxmc_group_adapt_fill_form reads the parameters into
+  sxhost::PinnedBuffer<double> h_pin;              // pinned host words sxmc_group_adapt_fill_form reads the parameters into
   unsigned adapt_tick = 0;                         // deferred batches launched for this group (every 256th asks for the form)
   float box_limit = 0.12f;                         // sxmc_group_adapt_fill_form: boxed while the image of a mean box is narrower (bins)
   std::string rtc_note;                            // why a run-time specialisation could not be had (last failure)
@@ -388,10 +397,10 @@ struct sxmc_group {
   // cfg_lut == 0): one row per distinct tuple, weighted by how many events share it.  One set per descriptor
   // flavour (dense bins / sparse counter slots).
   struct EventClasses {
-    int* d_rb = nullptr;             // [nmembers][K]
-    unsigned* d_weight = nullptr;    // [K]
-    SxSignalDesc* d_descs = nullptr; // member descriptors reading the class tables, no lookup-table output
-    size_t K = 0, cap_rb = 0, cap_weight = 0;
+    sxhost::DeviceBuffer<int> d_rb;             // [nmembers][K] (grow-only, like d_weight)
+    sxhost::DeviceBuffer<unsigned> d_weight;    // [K]
+    sxhost::DeviceBuffer<SxSignalDesc> d_descs; // member descriptors reading the class tables, no lookup-table output
+    size_t K = 0;
     bool tables_valid = false, descs_valid = false;
     std::vector<unsigned long long> seen_points;
   };
@@ -403,15 +412,20 @@ struct sxmc_group {
   int prezeroed = 0;
   bool last_sparse = false;
   unsigned long long capture_epoch = 0;  // last recording this group launched in
-  unsigned* d_ticket = nullptr;  // arrival counter of the fused step end, zeroed by the zero kernel
-  double* d_step_sums = nullptr; // 1024 partial sums of the fused step
+  sxhost::DeviceBuffer<unsigned> d_ticket;  // arrival counter of the fused step end, zeroed by the zero kernel
+  sxhost::DeviceBuffer<double> d_step_sums; // 1024 partial sums of the fused step
   std::vector<char> h_tail;          // fused step (fill_step_kernel): the step end's arguments, passed to the kernel by value
-  unsigned long long* d_coop_slots = nullptr;  // cooperative step end: one hand-over slot per worker (step_end_kernel)
-  double* d_coop_last = nullptr;               // ... and the last partial of each that was not NaN
+  sxhost::DeviceBuffer<unsigned long long> d_coop_slots;  // cooperative step end: one hand-over slot per worker (step_end_kernel)
+  sxhost::DeviceBuffer<double> d_coop_last;               // ... and the last partial of each that was not NaN
   // profiling of the fill kernel
   bool prof = false;
   std::vector<hipEvent_t> ev0, ev1;
   int prof_n = 0;
+  ~sxmc_group() {   // (releases only: what must happen before them is sxmc_group_destroy's)
+    for (hipEvent_t e : ev0) (void)hipEventDestroy(e);
+    for (hipEvent_t e : ev1) (void)hipEventDestroy(e);
+    for (hipEvent_t e : split_events) (void)hipEventDestroy(e);
+  }
 };
 
 
@@ -438,7 +452,6 @@ int build_sparse(sxmc_hist* h, const std::vector<int>& rb);
 bool fused_step_requested(const sxmc_group* g);
 int group_refresh(sxmc_group* g);
 int group_check_bound(sxmc_group* g, bool need_pdf);
-void free_event_classes(sxmc_group::EventClasses& ec);
 int ensure_event_classes(sxmc_group* g, bool sparse);
 int group_prepare_fill(sxmc_group* g, hipStream_t s, bool sparse);
 int group_fill(sxmc_group* g, hipStream_t s, bool sparse = false);

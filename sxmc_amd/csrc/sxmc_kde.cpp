@@ -25,21 +25,20 @@ struct sxmc_kde {
   size_t npad = 0;                 // sample rows, a multiple of SXMC_KDE_TILE
   double bw[SXMC_KDE_MAX_DIM] = {0};
   double prefactor = 0;            // 1 / ((2 pi)^(D/2) prod h)
-  float* d_rows = nullptr;         // [npad][D + 1]: scaled coordinates, weight; adaptive: [npad][D + 2] (rowlen())
+  DeviceBuffer<float> d_rows;      // [npad][D + 1]: scaled coordinates, weight; adaptive: [npad][D + 2] (rowlen())
   // adaptive bandwidths (sxmc_kde_create_adaptive): nothing of it is set or read at sensitivity 0
   double sensitivity = 0;
-  double* d_lambda = nullptr;      // [npad] the factors of the table rows, 1.0 in the padding; null when fixed
+  DeviceBuffer<double> d_lambda;   // [npad] the factors of the table rows, 1.0 in the padding; null when fixed
   std::vector<double> lambda;      // [nsamples] the same on the host
   int rowlen() const { return D + (d_lambda ? 2 : 1); }
   // evaluation points
   bool has_points = false;
-  size_t npoints = 0, pitch = 0, cap_pitch = 0;
-  float* d_pts = nullptr;          // [D][pitch] scaled coordinates (0 where the point's code is not 0)
-  int* d_codes = nullptr;          // [pitch] EvalHist's point codes: 0 in domain, -1 outside, -2 another data set
+  size_t npoints = 0, pitch = 0;
+  DeviceBuffer<float> d_pts;       // [D][pitch] scaled coordinates (0 where the point's code is not 0); grows with d_codes
+  DeviceBuffer<int> d_codes;       // [pitch] EvalHist's point codes: 0 in domain, -1 outside, -2 another data set
   int nsplit = 1;
   unsigned tiles_per_split = 1;
-  double* d_part = nullptr;        // [nsplit][pitch] partial sums
-  size_t cap_part = 0;
+  DeviceBuffer<double> d_part;     // [nsplit][pitch] partial sums (grow-only)
   // bindings
   float* pdf = nullptr;
   int pdf_off = 0, pdf_stride = 1;
@@ -50,13 +49,13 @@ struct sxmc_kde {
   int cus = 256;
   // sampling (sxmc_kde_random_sample): the rows hold an evaluation once one has been launched
   bool evaluated = false;
-  unsigned* d_flag = nullptr;      // [npad] in-domain flags, then [npad] their inclusive prefix sum, then [npad] the
+  DeviceBuffer<unsigned> d_flag;   // [npad] in-domain flags, then [npad] their inclusive prefix sum, then [npad] the
                                    // in-domain row numbers (one allocation, made at the first draw)
-  void* d_scan_temp = nullptr;
+  DeviceBuffer<void> d_scan_temp;
   size_t scan_temp_bytes = 0;
   // projection (sxmc_kde_project): per-row scratch, partial sums, the result and the in-domain count (grow-only)
-  double* d_proj = nullptr;
-  size_t cap_proj = 0;             // doubles
+  DeviceBuffer<double> d_proj;
+  ~sxmc_kde() { sxmc_hist_destroy(h); }   // (releases only: its buffers go by themselves, the table with its evaluator)
 };
 
 namespace {
@@ -84,28 +83,13 @@ void choose_split(size_t pitch, size_t ntiles, int cus, int& nsplit, unsigned& t
   }
 }
 
-// The cleared sample rows of a new evaluator that has its table (k->h) and npad.  On failure the table goes too: the
-// caller only drops k.
-int alloc_rows(sxmc_kde* k, const char* what) {
-  const size_t bytes = sizeof(float) * k->npad * (size_t)k->rowlen();
-  hipError_t e = hipMalloc((void**)&k->d_rows, bytes);
-  if (e == hipSuccess) e = hipMemset(k->d_rows, 0, bytes);
-  if (e == hipSuccess) return SXMC_OK;
-  if (k->d_rows) (void)hipFree(k->d_rows);
-  if (k->d_lambda) (void)hipFree(k->d_lambda);
-  sxmc_hist_destroy(k->h);
-  return fail(SXMC_ERR_HIP, std::string(what) + hipGetErrorString(e));
+// The cleared sample rows of a new evaluator that has its table (k->h) and npad.
+int cleared_rows(sxmc_kde* k) {
+  const size_t n = k->npad * (size_t)k->rowlen();
+  SX_BUF(k->d_rows.alloc(n));
+  SX_HIP(hipMemset(k->d_rows.get(), 0, sizeof(float) * n));
+  return SXMC_OK;
 }
-
-// Device memory of one call, freed when it returns.
-struct Scratch {
-  void* p = nullptr;
-  ~Scratch() {
-    if (p) (void)hipFree(p);
-  }
-  hipError_t alloc(size_t bytes) { return hipMalloc(&p, bytes); }
-  double* f64() const { return static_cast<double*>(p); }
-};
 
 // The factors of an adaptive evaluator that has its table, bandwidths and npad: the pilot on the device (kde_pilot),
 // then g and lambda on the host in f64 (kde_adaptive.h) and the upload of d_lambda.  rows: the untransformed table on
@@ -136,23 +120,23 @@ int set_local_factors(sxmc_kde* k, const float* rows, int nfields, const std::ve
     }
     s0[j * (size_t)(D + 1) + (size_t)D] = 1.0 / mass;
   }
-  Scratch dx, ds, dpart, df;
-  SX_HIP(dx.alloc(sizeof(double) * x.size()));
-  SX_HIP(ds.alloc(sizeof(double) * s0.size()));
-  SX_HIP(dpart.alloc(sizeof(double) * (size_t)a.nsplit * pitch));
-  SX_HIP(df.alloc(sizeof(double) * pitch));
+  DeviceBuffer<double> dx, ds, dpart, df;   // (device memory of this call, freed when it returns)
+  SX_BUF(dx.alloc(x.size()));
+  SX_BUF(ds.alloc(s0.size()));
+  SX_BUF(dpart.alloc((size_t)a.nsplit * pitch));
+  SX_BUF(df.alloc(pitch));
   const hipStream_t s = k->h->stream;
-  SX_HIP(hipMemcpyAsync(dx.p, x.data(), sizeof(double) * x.size(), hipMemcpyHostToDevice, s));
-  SX_HIP(hipMemcpyAsync(ds.p, s0.data(), sizeof(double) * s0.size(), hipMemcpyHostToDevice, s));
-  SX_HIP(sx_kde_pilot(a, dx.f64(), ds.f64(), dpart.f64(), df.f64(), s));
+  SX_HIP(hipMemcpyAsync(dx.get(), x.data(), sizeof(double) * x.size(), hipMemcpyHostToDevice, s));
+  SX_HIP(hipMemcpyAsync(ds.get(), s0.data(), sizeof(double) * s0.size(), hipMemcpyHostToDevice, s));
+  SX_HIP(sx_kde_pilot(a, dx.get(), ds.get(), dpart.get(), df.get(), s));
   std::vector<double> f(pitch);
-  SX_HIP(hipMemcpyAsync(f.data(), df.p, sizeof(double) * pitch, hipMemcpyDeviceToHost, s));
+  SX_HIP(hipMemcpyAsync(f.data(), df.get(), sizeof(double) * pitch, hipMemcpyDeviceToHost, s));
   SX_HIP(hipStreamSynchronize(s));
   const double g = sxkde::pilot_scale(f.data(), inside);
   std::vector<double> lam(pitch, 1.0);
   for (size_t i = 0; i < k->nsamples; i++) lam[i] = sxkde::local_factor(f[i], g, k->sensitivity);
-  SX_HIP(hipMalloc((void**)&k->d_lambda, sizeof(double) * pitch));
-  SX_HIP(hipMemcpy(k->d_lambda, lam.data(), sizeof(double) * pitch, hipMemcpyHostToDevice));
+  SX_BUF(k->d_lambda.alloc(pitch));
+  SX_HIP(hipMemcpy(k->d_lambda.get(), lam.data(), sizeof(double) * pitch, hipMemcpyHostToDevice));
   lam.resize(k->nsamples);
   k->lambda.swap(lam);
   return SXMC_OK;
@@ -237,13 +221,9 @@ int kde_create(const float* samples, size_t nsamples_floats, int samples_on_devi
   if (sensitivity > 0) {
     k->sensitivity = sensitivity;
     rc = set_local_factors(k.get(), rows, nfields, inside);
-    if (rc) {
-      if (k->d_lambda) (void)hipFree(k->d_lambda);
-      sxmc_hist_destroy(k->h);
-      return rc;
-    }
+    if (rc) return rc;
   }
-  rc = alloc_rows(k.get(), "hipMalloc sample rows: ");
+  rc = cleared_rows(k.get());
   if (rc) return rc;
   DeviceProps props;
   if (get_props(props) == SXMC_OK && props.cus > 0) k->cus = props.cus;
@@ -292,15 +272,10 @@ int sxmc_kde_create_shared(sxmc_kde_t base, sxmc_kde_t* out) {
   if (base->d_lambda) {   // the factors are copied, never recomputed
     k->sensitivity = base->sensitivity;
     k->lambda = base->lambda;
-    hipError_t e = hipMalloc((void**)&k->d_lambda, sizeof(double) * k->npad);
-    if (e == hipSuccess) e = hipMemcpy(k->d_lambda, base->d_lambda, sizeof(double) * k->npad, hipMemcpyDeviceToDevice);
-    if (e != hipSuccess) {
-      if (k->d_lambda) (void)hipFree(k->d_lambda);
-      sxmc_hist_destroy(k->h);
-      return fail(SXMC_ERR_HIP, std::string("create_shared: ") + hipGetErrorString(e));
-    }
+    SX_BUF(k->d_lambda.alloc(k->npad));
+    SX_HIP(hipMemcpy(k->d_lambda.get(), base->d_lambda.get(), sizeof(double) * k->npad, hipMemcpyDeviceToDevice));
   }
-  rc = alloc_rows(k.get(), "create_shared: ");
+  rc = cleared_rows(k.get());
   if (rc) return rc;
   *out = k.release();
   return SXMC_OK;
@@ -309,16 +284,7 @@ int sxmc_kde_create_shared(sxmc_kde_t base, sxmc_kde_t* out) {
 int sxmc_kde_destroy(sxmc_kde_t k) {
   if (!k) return SXMC_OK;
   if (k->h && k->h->stream) (void)hipStreamSynchronize(k->h->stream);
-  if (k->d_flag) (void)hipFree(k->d_flag);
-  if (k->d_scan_temp) (void)hipFree(k->d_scan_temp);
-  if (k->d_proj) (void)hipFree(k->d_proj);
-  if (k->d_rows) (void)hipFree(k->d_rows);
-  if (k->d_lambda) (void)hipFree(k->d_lambda);
-  if (k->d_pts) (void)hipFree(k->d_pts);
-  if (k->d_codes) (void)hipFree(k->d_codes);
-  if (k->d_part) (void)hipFree(k->d_part);
-  sxmc_hist_destroy(k->h);
-  delete k;
+  delete k;   // (the table's evaluator, then the buffers)
   return SXMC_OK;
 }
 
@@ -369,26 +335,16 @@ int sxmc_kde_set_eval_points(sxmc_kde_t k, const float* points, size_t npoints_f
   unsigned tps = 1;
   choose_split(pitch, k->npad / SXMC_KDE_TILE, k->cus, nsplit, tps);
   SX_HIP(hipStreamSynchronize(k->h->stream));   // (an evaluation in flight reads the arrays replaced here)
-  if (pitch > k->cap_pitch) {
-    if (k->d_pts) SX_HIP(hipFree(k->d_pts));
-    if (k->d_codes) SX_HIP(hipFree(k->d_codes));
-    k->d_pts = nullptr;
-    k->d_codes = nullptr;
-    k->cap_pitch = 0;
-    SX_HIP(hipMalloc((void**)&k->d_pts, sizeof(float) * pitch * (size_t)D));
-    SX_HIP(hipMalloc((void**)&k->d_codes, sizeof(int) * pitch));
-    k->cap_pitch = pitch;
+  k->has_points = false;   // (until the new ones are in place: a failure below leaves an evaluator without points)
+  if (pitch > k->d_codes.capacity()) {   // (the two grow together, both freed first; d_codes, allocated last, says whether both are there)
+    SX_BUF(k->d_pts.reset());
+    SX_BUF(k->d_codes.reset());
+    SX_BUF(k->d_pts.alloc(pitch * (size_t)D));
+    SX_BUF(k->d_codes.alloc(pitch));
   }
-  const size_t part = (size_t)nsplit * pitch;
-  if (part > k->cap_part) {
-    if (k->d_part) SX_HIP(hipFree(k->d_part));
-    k->d_part = nullptr;
-    k->cap_part = 0;
-    SX_HIP(hipMalloc((void**)&k->d_part, sizeof(double) * part));
-    k->cap_part = part;
-  }
-  SX_HIP(hipMemcpy(k->d_pts, pts.data(), sizeof(float) * pts.size(), hipMemcpyHostToDevice));
-  SX_HIP(hipMemcpy(k->d_codes, codes.data(), sizeof(int) * pitch, hipMemcpyHostToDevice));
+  SX_BUF(k->d_part.grow((size_t)nsplit * pitch));
+  SX_HIP(hipMemcpy(k->d_pts.get(), pts.data(), sizeof(float) * pts.size(), hipMemcpyHostToDevice));
+  SX_HIP(hipMemcpy(k->d_codes.get(), codes.data(), sizeof(int) * pitch, hipMemcpyHostToDevice));
   k->npoints = n;
   k->pitch = pitch;
   k->nsplit = nsplit;
@@ -431,7 +387,7 @@ int sxmc_kde_eval_async(sxmc_kde_t k, int do_eval_pdf) {
   d.param_stride = k->par_stride;
   SxKdeArgs a;
   std::memset(&a, 0, sizeof a);
-  a.rows = k->d_rows;
+  a.rows = k->d_rows.get();
   a.npad = k->npad;
   a.norm = k->norm + k->norm_off;
   for (int i = 0; i < k->D; i++) {
@@ -440,18 +396,18 @@ int sxmc_kde_eval_async(sxmc_kde_t k, int do_eval_pdf) {
     a.cscale[i] = kLog2eHalfSqrt / k->bw[i];
     a.inv_h_sqrt2[i] = 1.0 / (k->bw[i] * M_SQRT2);
   }
-  a.lambda = k->d_lambda;
+  a.lambda = k->d_lambda.get();
   SX_HIP(hipMemsetAsync(a.norm, 0, sizeof(unsigned), s));
   SX_HIP(sx_kde_prepass(d, a, s));
   if (lookup) {
     const unsigned ntiles = (unsigned)(k->npad / SXMC_KDE_TILE);
-    if (k->d_lambda) {
-      SX_HIP(sx_kde_pairs_adaptive(k->D, k->d_pts, k->pitch, k->d_rows, k->tiles_per_split, ntiles, k->nsplit,
-                                   k->d_part, s));
+    if (k->d_lambda.get()) {
+      SX_HIP(sx_kde_pairs_adaptive(k->D, k->d_pts.get(), k->pitch, k->d_rows.get(), k->tiles_per_split, ntiles, k->nsplit,
+                                   k->d_part.get(), s));
     } else {
-      SX_HIP(sx_kde_pairs(k->D, k->d_pts, k->pitch, k->d_rows, k->tiles_per_split, ntiles, k->nsplit, k->d_part, s));
+      SX_HIP(sx_kde_pairs(k->D, k->d_pts.get(), k->pitch, k->d_rows.get(), k->tiles_per_split, ntiles, k->nsplit, k->d_part.get(), s));
     }
-    SX_HIP(sx_kde_combine(k->d_part, k->pitch, k->nsplit, k->npoints, k->d_codes, a.norm, k->prefactor,
+    SX_HIP(sx_kde_combine(k->d_part.get(), k->pitch, k->nsplit, k->npoints, k->d_codes.get(), a.norm, k->prefactor,
                           k->pdf + k->pdf_off, (long)k->pdf_stride, s));
   }
   k->evaluated = true;
@@ -509,20 +465,20 @@ int kde_compact(sxmc_kde_t k, unsigned& n) {
   }
   SX_REQUIRE(k->npad <= 0x7FFFFFFFull, "EvalKernel: too many samples to draw from");
   const hipStream_t s = k->h->stream;
-  if (!k->d_flag) {
+  if (!k->d_flag.get()) {
     SX_HIP(hipStreamSynchronize(s));   // (allocation next to queued work: settle it first)
-    if (!k->d_scan_temp) {
+    if (!k->d_scan_temp.get()) {
       size_t temp = 0;
       SX_HIP(sx_inclusive_sum_u32(nullptr, nullptr, (int)k->npad, nullptr, temp, s));
-      SX_HIP(hipMalloc((void**)&k->d_scan_temp, std::max<size_t>(temp, 16)));
+      SX_BUF(k->d_scan_temp.alloc(std::max<size_t>(temp, 16)));
       k->scan_temp_bytes = temp;
     }
-    SX_HIP(hipMalloc((void**)&k->d_flag, sizeof(unsigned) * 3 * k->npad));
+    SX_BUF(k->d_flag.alloc(3 * k->npad));
   }
-  unsigned* flag = k->d_flag;
+  unsigned* flag = k->d_flag.get();
   unsigned* pos = flag + k->npad;
   unsigned* idx = pos + k->npad;
-  SX_HIP(sx_kde_compact(k->d_rows, k->rowlen(), k->npad, flag, pos, idx, k->d_scan_temp, k->scan_temp_bytes, s));
+  SX_HIP(sx_kde_compact(k->d_rows.get(), k->rowlen(), k->npad, flag, pos, idx, k->d_scan_temp.get(), k->scan_temp_bytes, s));
   SX_HIP(hipMemcpyAsync(&n, pos + (k->npad - 1), sizeof(unsigned), hipMemcpyDeviceToHost, s));
   SX_HIP(hipStreamSynchronize(s));
   return SXMC_OK;
@@ -579,8 +535,8 @@ int sxmc_kde_random_sample(sxmc_kde_t k, size_t nobserved, unsigned long long se
   unsigned* d_exhausted = nullptr;
   rc = sample_buffer(k->h, nobserved, row, d_out, d_exhausted);   // (the histogram evaluator's, on the same stream)
   if (rc) return rc;
-  const unsigned* idx = k->d_flag + 2 * k->npad;
-  SX_HIP(sx_kde_sample(D, k->d_rows, k->d_lambda, idx, n, g, seed, nobserved, d_out, d_exhausted, k->h->stream));
+  const unsigned* idx = k->d_flag.get() + 2 * k->npad;
+  SX_HIP(sx_kde_sample(D, k->d_rows.get(), k->d_lambda.get(), idx, n, g, seed, nobserved, d_out, d_exhausted, k->h->stream));
   return sample_read_back(k->h, nobserved, row, ": the cuts leave (almost) none of the kernel-density PDF's mass",
                           h_events);
 }
@@ -607,23 +563,19 @@ int sxmc_kde_project(sxmc_kde_t k, int obs, int nbins, double* h_prob) {
   a.upper = k->h->upper[(size_t)obs];
   a.h = k->bw[obs];
   a.cunit = kLog2eHalfSqrt;
-  a.lambda = k->d_lambda;
+  a.lambda = k->d_lambda.get();
   const hipStream_t s = k->h->stream;
   // [2 npad] per-row scratch ([3 npad] when adaptive), [nsplit][pitch] partials, [nbins] result, the count
   const size_t off_prob = (k->d_lambda ? 3 : 2) * k->npad + (size_t)a.nsplit * a.pitch;
   const size_t need = off_prob + (size_t)nbins + 1;
-  if (need > k->cap_proj) {
+  if (need > k->d_proj.capacity()) {
     SX_HIP(hipStreamSynchronize(s));   // (allocation next to queued work: settle it first)
-    if (k->d_proj) SX_HIP(hipFree(k->d_proj));
-    k->d_proj = nullptr;
-    k->cap_proj = 0;
-    SX_HIP(hipMalloc((void**)&k->d_proj, sizeof(double) * need));
-    k->cap_proj = need;
+    SX_BUF(k->d_proj.grow(need));
   }
-  double* d_prob = k->d_proj + off_prob;
+  double* d_prob = k->d_proj.get() + off_prob;
   unsigned* d_count = reinterpret_cast<unsigned*>(d_prob + nbins);
   SX_HIP(hipMemsetAsync(d_count, 0, sizeof(unsigned), s));
-  SX_HIP(sx_kde_project(k->d_rows, a, k->d_proj, d_count, d_prob, s));
+  SX_HIP(sx_kde_project(k->d_rows.get(), a, k->d_proj.get(), d_count, d_prob, s));
   SX_HIP(hipMemcpyAsync(h_prob, d_prob, sizeof(double) * (size_t)nbins, hipMemcpyDeviceToHost, s));
   SX_HIP(hipStreamSynchronize(s));
   return SXMC_OK;

@@ -8,11 +8,11 @@ namespace sxhost {
 
 using sxplan::apportion_workgroups;
 
-// a host vector's copy on the device, allocated for at least `room` elements
+// a host vector's copy on the device, in an empty buffer allocated for at least `room` elements
 template <typename T>
-hipError_t upload(const std::vector<T>& v, T** d, size_t room = 0) {
-  const hipError_t e = hipMalloc((void**)d, sizeof(T) * std::max(v.size(), room));
-  return (e != hipSuccess || v.empty()) ? e : hipMemcpy(*d, v.data(), sizeof(T) * v.size(), hipMemcpyHostToDevice);
+hipError_t upload(const std::vector<T>& v, DeviceBuffer<T>& d, size_t room = 0) {
+  const hipError_t e = (hipError_t)d.alloc(std::max(v.size(), room));
+  return (e != hipSuccess || v.empty()) ? e : hipMemcpy(d.get(), v.data(), sizeof(T) * v.size(), hipMemcpyHostToDevice);
 }
 
 // Slot assignment: observables first (slot k = field k), then every other field a systematic
@@ -36,26 +36,20 @@ int slot_of(const std::vector<int>& slot_col, int field) {
   return 0;
 }
 
-void free_bucket_tables(sxmc_hist* h) {
-  if (h->d_bdir) (void)hipFree(h->d_bdir);
-  if (h->d_btkeys) (void)hipFree(h->d_btkeys);
-  if (h->d_btslot) (void)hipFree(h->d_btslot);
-  h->d_bdir = h->d_btkeys = h->d_btslot = nullptr;
+void reset_bucket_tables(sxmc_hist* h) {
+  h->d_bdir.reset();
+  h->d_btkeys.reset();
+  h->d_btslot.reset();
   h->btab_valid = false;
 }
 
 void free_sparse(sxmc_hist* h) {
-  free_bucket_tables(h);
-  if (h->d_cnt) (void)hipFree(h->d_cnt);
-  if (h->d_read_slot) (void)hipFree(h->d_read_slot);
-  if (h->d_filter) (void)hipFree(h->d_filter);
-  if (h->d_table) (void)hipFree(h->d_table);
-  if (h->d_coarse) (void)hipFree(h->d_coarse);
-  h->d_coarse = nullptr;
-  h->d_cnt = nullptr;
-  h->d_read_slot = nullptr;
-  h->d_filter = nullptr;
-  h->d_table = nullptr;
+  reset_bucket_tables(h);
+  h->d_cnt.reset();
+  h->d_read_slot.reset();
+  h->d_filter.reset();
+  h->d_table.reset();
+  h->d_coarse.reset();
   h->ntargets = 0;
   h->targets.clear();
   h->h_read_slot.clear();
@@ -72,12 +66,12 @@ int build_sparse(sxmc_hist* h, const std::vector<int>& rb) {
   const std::vector<int>& slot = st.slot;
   const size_t T = targets.size();
   const int cbits = st.cbits, fbits = st.fbits, tbits = st.tbits;
-  SX_HIP(hipMalloc((void**)&h->d_cnt, sizeof(unsigned) * std::max<size_t>(T, 4)));
-  SX_HIP(hipMemset(h->d_cnt, 0, sizeof(unsigned) * std::max<size_t>(T, 4)));
-  SX_HIP(upload(slot, &h->d_read_slot, 1));
-  SX_HIP(upload(filter, &h->d_filter));
-  SX_HIP(upload(table, &h->d_table));
-  SX_HIP(upload(coarse, &h->d_coarse));
+  SX_BUF(h->d_cnt.alloc(std::max<size_t>(T, 4)));
+  SX_HIP(hipMemset(h->d_cnt.get(), 0, sizeof(unsigned) * std::max<size_t>(T, 4)));
+  SX_HIP(upload(slot, h->d_read_slot, 1));
+  SX_HIP(upload(filter, h->d_filter));
+  SX_HIP(upload(table, h->d_table));
+  SX_HIP(upload(coarse, h->d_coarse));
   h->h_read_slot = slot;
   h->coarse_shift = 32 - cbits;
   h->ntargets = (int)T;
@@ -90,14 +84,14 @@ int build_sparse(sxmc_hist* h, const std::vector<int>& rb) {
 // The sparse flavour of a member's descriptor: counters instead of the histogram, slots instead of bins.
 void make_sparse_desc(const sxmc_hist* h, SxSignalDesc& d) {
   d.sparse_real_nbins = h->total_nbins;
-  d.bins = h->d_cnt;
+  d.bins = h->d_cnt.get();
   d.total_nbins = std::max(h->ntargets, 1);
-  d.read_bins = h->d_read_slot;
-  d.sparse_filter = h->d_filter;
-  d.sparse_table = h->d_table;
+  d.read_bins = h->d_read_slot.get();
+  d.sparse_filter = h->d_filter.get();
+  d.sparse_table = h->d_table.get();
   d.sparse_filter_shift = h->filter_shift;
   d.sparse_table_shift = h->table_shift;
-  d.sparse_coarse = h->d_coarse;
+  d.sparse_coarse = h->d_coarse.get();
   d.sparse_coarse_shift = h->coarse_shift;
 }
 
@@ -105,11 +99,11 @@ int fill_desc(const sxmc_hist* h, SxSignalDesc& d) {
   std::memset(&d, 0, sizeof(d));
   std::vector<int> slot_col;
   member_slots(h, slot_col);
-  d.cols = h->store->d_cols;
+  d.cols = h->store->d_cols.get();
   d.col_pitch = h->pitch;
   d.nsamples = h->nsamples;
   d.nvec = h->nvec;
-  d.bins = h->d_bins;
+  d.bins = h->d_bins.get();
   d.norm = h->norm ? h->norm + h->norm_off : nullptr;
   d.total_nbins = h->total_nbins;
   d.nobs = h->nobs;
@@ -141,25 +135,13 @@ int fill_desc(const sxmc_hist* h, SxSignalDesc& d) {
     }
   }
   d.ncoef = ncoef;
-  d.read_bins = h->has_points ? h->d_read_bins : nullptr;
+  d.read_bins = h->has_points ? h->d_read_bins.get() : nullptr;
   d.npoints = h->has_points ? h->npoints : 0;
   d.pdf_out = h->pdf ? h->pdf + h->pdf_off : nullptr;
   d.pdf_stride = h->pdf_stride;
   d.bin_volume = h->bin_volume;
   return SXMC_OK;
 }
-
-struct DevBuf {  // device temporary, freed on scope exit
-  void* p = nullptr;
-  ~DevBuf() {
-    if (p) (void)hipFree(p);
-  }
-  hipError_t alloc(size_t bytes) { return hipMalloc(&p, bytes ? bytes : 16); }
-  template <typename T>
-  T* as() const {
-    return static_cast<T*>(p);
-  }
-};
 
 // strata of x - t inside a bucket of a boxed table (SXMC_BOX_STRATA, measurement build: 1 .. 16).  More strata make the
 // boxes narrower in x - t and wider in x: at BASELINE config 3 a CPU model of the layout puts the granules whose box
@@ -207,55 +189,54 @@ int get_bucket_sort(sxmc_hist* h, const SxSignalDesc* d_full_desc, unsigned mask
   const unsigned outside = (unsigned)nkeys;
   const int bits = ceil_log2((size_t)nkeys + 1);
 
-  DevBuf keys0, keys1, rows0, dfirst;
-  SX_HIP(keys0.alloc(n * 4));
-  SX_HIP(keys1.alloc(n * 4));
-  SX_HIP(rows0.alloc(n * 4));
-  SX_HIP(hipMalloc((void**)&b->d_rows, n * 4));
-  SX_HIP(dfirst.alloc((nkeys + 1) * 4));
-  SX_HIP(hipMemset(dfirst.p, 0xFF, (nkeys + 1) * 4));
+  DeviceBuffer<unsigned> keys0, keys1, rows0, dfirst;   // (temporaries: freed on every way out)
+  SX_BUF(keys0.alloc(n));
+  SX_BUF(keys1.alloc(n));
+  SX_BUF(rows0.alloc(n));
+  SX_BUF(b->d_rows.alloc(n));
+  SX_BUF(dfirst.alloc(nkeys + 1));
+  SX_HIP(hipMemset(dfirst.get(), 0xFF, (nkeys + 1) * 4));
   const unsigned* order_rows = nullptr;
-  DevBuf rows1;
+  DeviceBuffer<unsigned> rows1;
   if (ordered >= 0) {
     // rows by the ordered observable's value first; the stable sort by bucket below keeps that order inside a bucket
-    SX_HIP(rows1.alloc(n * 4));
+    SX_BUF(rows1.alloc(n));
     if (box_truth >= 0) {
       // BOXED observable: strata of x - t (their boundaries: quantiles, read off a first sort), x ascending inside
-      const float* colx = st.d_cols + (size_t)ordered * h->pitch;
-      const float* colt = st.d_cols + (size_t)box_truth * h->pitch;
+      const float* colx = st.d_cols.get() + (size_t)ordered * h->pitch;
+      const float* colt = st.d_cols.get() + (size_t)box_truth * h->pitch;
       const int nstrata = box_strata();
       unsigned bounds[16] = {0};
       if (nstrata > 1) {
-        SX_HIP(sx_box_keys(colx, colt, n, 1, 1, nullptr, keys0.as<unsigned>(), rows0.as<unsigned>(), nullptr));
-        SX_HIP(sx_bucket_sort(keys0.as<unsigned>(), keys1.as<unsigned>(), rows0.as<unsigned>(), rows1.as<unsigned>(), n, 32,
+        SX_HIP(sx_box_keys(colx, colt, n, 1, 1, nullptr, keys0.get(), rows0.get(), nullptr));
+        SX_HIP(sx_bucket_sort(keys0.get(), keys1.get(), rows0.get(), rows1.get(), n, 32,
                               nullptr));
         for (int k = 0; k + 1 < nstrata; k++) {
-          SX_HIP(hipMemcpy(&bounds[k], keys1.as<unsigned>() + (size_t)((double)n * (k + 1) / nstrata), 4,
+          SX_HIP(hipMemcpy(&bounds[k], keys1.get() + (size_t)((double)n * (k + 1) / nstrata), 4,
                            hipMemcpyDeviceToHost));
         }
       }
-      SX_HIP(sx_box_keys(colx, colt, n, 2, nstrata, bounds, keys0.as<unsigned>(), rows0.as<unsigned>(), nullptr));
+      SX_HIP(sx_box_keys(colx, colt, n, 2, nstrata, bounds, keys0.get(), rows0.get(), nullptr));
     } else {
-      SX_HIP(sx_order_keys(st.d_cols + (size_t)ordered * h->pitch, n, keys0.as<unsigned>(),
-                           rows0.as<unsigned>(), nullptr));
+      SX_HIP(sx_order_keys(st.d_cols.get() + (size_t)ordered * h->pitch, n, keys0.get(),
+                           rows0.get(), nullptr));
     }
-    SX_HIP(sx_bucket_sort(keys0.as<unsigned>(), keys1.as<unsigned>(), rows0.as<unsigned>(), rows1.as<unsigned>(), n, 32,
+    SX_HIP(sx_bucket_sort(keys0.get(), keys1.get(), rows0.get(), rows1.get(), n, 32,
                           nullptr));
-    order_rows = rows1.as<unsigned>();
+    order_rows = rows1.get();
   }
-  SX_HIP(sx_bucket_keys(d_full_desc, n, mask, b->radix, outside, order_rows, keys0.as<unsigned>(), rows0.as<unsigned>(),
+  SX_HIP(sx_bucket_keys(d_full_desc, n, mask, b->radix, outside, order_rows, keys0.get(), rows0.get(),
                         nullptr));
-  SX_HIP(sx_bucket_sort(keys0.as<unsigned>(), keys1.as<unsigned>(), rows0.as<unsigned>(), b->d_rows, n, bits, nullptr));
-  SX_HIP(sx_bucket_first(keys1.as<unsigned>(), n, dfirst.as<unsigned>(), nullptr));
+  SX_HIP(sx_bucket_sort(keys0.get(), keys1.get(), rows0.get(), b->d_rows.get(), n, bits, nullptr));
+  SX_HIP(sx_bucket_first(keys1.get(), n, dfirst.get(), nullptr));
   std::vector<unsigned> first((size_t)nkeys + 1);
-  SX_HIP(hipMemcpy(first.data(), dfirst.p, first.size() * 4, hipMemcpyDeviceToHost));
+  SX_HIP(hipMemcpy(first.data(), dfirst.get(), first.size() * 4, hipMemcpyDeviceToHost));
 
   // logical granules: bucket by bucket, each bucket padded to whole granules (sxmc_plan.h)
   sxplan::GranulePlan gp;
   sxplan::bucket_granules(first, outside, n, gp);
   if (!gp.worth_it) {  // mostly padding: not worth it
-    (void)hipFree(b->d_rows);
-    b->d_rows = nullptr;
+    b->d_rows.reset();
     return SXMC_OK;
   }
   b->lsrc = gp.lsrc;
@@ -299,28 +280,28 @@ int get_bucketed(sxmc_hist* h, const SampleStore::BucketSort* bs, const std::vec
   b->ngranules = P;
   b->nkept = bs->nkept;
   b->pitch = std::max<size_t>(64, P * 256);
-  DevBuf dsrc, dvalid;
-  SX_HIP(hipMalloc((void**)&b->d_cols, sizeof(float) * b->pitch * fields.size()));
-  SX_HIP(hipMalloc((void**)&b->d_gpre, sizeof(unsigned) * A));
-  SX_HIP(hipMalloc((void**)&b->d_gkp, sizeof(unsigned) * 2 * A));
-  SX_HIP(hipMemcpy(b->d_gpre, ppre.data(), sizeof(unsigned) * A, hipMemcpyHostToDevice));
-  SX_HIP(hipMemcpy(b->d_gkp, pkp.data(), sizeof(unsigned) * 2 * A, hipMemcpyHostToDevice));
-  SX_HIP(dsrc.alloc(A * 4));
-  SX_HIP(dvalid.alloc(A * 4));
-  SX_HIP(hipMemcpy(dsrc.p, psrc.data(), A * 4, hipMemcpyHostToDevice));
-  SX_HIP(hipMemcpy(dvalid.p, pvalid.data(), A * 4, hipMemcpyHostToDevice));
-  SX_HIP(sx_bucket_gather(st.d_cols, h->pitch, (int)fields.size(), fields.data(), bs->d_rows, dsrc.as<unsigned>(),
-                          dvalid.as<unsigned>(), P, b->d_cols, b->pitch, nullptr));
+  DeviceBuffer<unsigned> dsrc, dvalid;   // (temporaries)
+  SX_BUF(b->d_cols.alloc(b->pitch * fields.size()));
+  SX_BUF(b->d_gpre.alloc(A));
+  SX_BUF(b->d_gkp.alloc(2 * A));
+  SX_HIP(hipMemcpy(b->d_gpre.get(), ppre.data(), sizeof(unsigned) * A, hipMemcpyHostToDevice));
+  SX_HIP(hipMemcpy(b->d_gkp.get(), pkp.data(), sizeof(unsigned) * 2 * A, hipMemcpyHostToDevice));
+  SX_BUF(dsrc.alloc(A ? A : 4));
+  SX_BUF(dvalid.alloc(A ? A : 4));
+  SX_HIP(hipMemcpy(dsrc.get(), psrc.data(), A * 4, hipMemcpyHostToDevice));
+  SX_HIP(hipMemcpy(dvalid.get(), pvalid.data(), A * 4, hipMemcpyHostToDevice));
+  SX_HIP(sx_bucket_gather(st.d_cols.get(), h->pitch, (int)fields.size(), fields.data(), bs->d_rows.get(), dsrc.get(),
+                          dvalid.get(), P, b->d_cols.get(), b->pitch, nullptr));
   if (bs->ordered >= 0 && bs->box_truth >= 0) {
     // the boxed observable's column is the last of `fields`, its truth field the one before (sxplan::compact_slots)
     SX_REQUIRE(fields.size() >= 2, "a boxed layout streams its observable and the truth field");
-    SX_HIP(hipMalloc((void**)&b->d_gbox, sizeof(float) * 4 * A));
-    SX_HIP(hipMemset(b->d_gbox, 0xFF, sizeof(float) * 4 * A));   // (NaN: a granule never written is left to the float columns)
-    SX_HIP(sx_bucket_boxes(b->d_cols + (fields.size() - 1) * b->pitch, b->d_cols + (fields.size() - 2) * b->pitch,
-                           dvalid.as<unsigned>(), P, b->d_gbox, nullptr));
+    SX_BUF(b->d_gbox.alloc(4 * A));
+    SX_HIP(hipMemset(b->d_gbox.get(), 0xFF, sizeof(float) * 4 * A));   // (NaN: a granule never written is left to the float columns)
+    SX_HIP(sx_bucket_boxes(b->d_cols.get() + (fields.size() - 1) * b->pitch, b->d_cols.get() + (fields.size() - 2) * b->pitch,
+                           dvalid.get(), P, b->d_gbox.get(), nullptr));
     {   // mean extents of the finite boxes (what a dual launch estimates the share of straddling granules from)
       std::vector<float> hb(4 * P);
-      if (P) SX_HIP(hipMemcpy(hb.data(), b->d_gbox, sizeof(float) * 4 * P, hipMemcpyDeviceToHost));
+      if (P) SX_HIP(hipMemcpy(hb.data(), b->d_gbox.get(), sizeof(float) * 4 * P, hipMemcpyDeviceToHost));
       // (the mean of the lower nine tenths: the granules of a bucket's thin tails are wide whatever the layout and are
       // few; they straddle an edge at any parameters and say nothing about the rest)
       std::vector<double> ex, et;
@@ -343,9 +324,9 @@ int get_bucketed(sxmc_hist* h, const SampleStore::BucketSort* bs, const std::vec
     }
   } else if (bs->ordered >= 0) {
     // the ordered observable's column is the last of `fields` (sxplan::compact_slots)
-    SX_HIP(hipMalloc((void**)&b->d_gedge, sizeof(float) * 2 * A));
-    SX_HIP(hipMemset(b->d_gedge, 0, sizeof(float) * 2 * A));
-    SX_HIP(sx_bucket_edges(b->d_cols + (fields.size() - 1) * b->pitch, dvalid.as<unsigned>(), P, b->d_gedge, nullptr));
+    SX_BUF(b->d_gedge.alloc(2 * A));
+    SX_HIP(hipMemset(b->d_gedge.get(), 0, sizeof(float) * 2 * A));
+    SX_HIP(sx_bucket_edges(b->d_cols.get() + (fields.size() - 1) * b->pitch, dvalid.get(), P, b->d_gedge.get(), nullptr));
   }
   SX_HIP(hipDeviceSynchronize());
   b->complete = true;
@@ -387,7 +368,7 @@ int get_bucket_codes(sxmc_hist* h, const SampleStore::Bucketed* bkc, const SxSig
   }
   const unsigned long long n = (unsigned long long)b->ngranules * 256ull;
   float mm[2 * SXMC_MAX_NFIELDS];
-  SX_HIP(sx_column_minmax(b->d_cols, b->pitch, nq, n, mm, nullptr));
+  SX_HIP(sx_column_minmax(b->d_cols.get(), b->pitch, nq, n, mm, nullptr));
   sxplan::CodeWindows cw;   // (sxmc_plan.h: pure, tested without a device)
   sxplan::code_windows(mm, nq, cd.nobs, cd.lower, cd.upper, cw);
   for (int m = 0; m < nq; m++) {
@@ -406,20 +387,18 @@ int get_bucket_codes(sxmc_hist* h, const SampleStore::Bucketed* bkc, const SxSig
   }();
   if (!(ambiguous <= 2e-3) && !gate_lifted) return SXMC_OK;
   // (the codes are an extra: a table they do not fit beside -- +4 bytes per row and pair of fields -- keeps its float stream)
-  if (hipMalloc((void**)&b->d_qcol, boxed ? sizeof(unsigned short) * b->pitch
-                                          : sizeof(unsigned) * b->pitch * (size_t)((nq + 1) / 2)) != hipSuccess) {
+  // (elements are words: a boxed table's 16-bit codes take half a word per row, and the pitch is even)
+  if (b->d_qcol.alloc(boxed ? b->pitch / 2 : b->pitch * (size_t)((nq + 1) / 2)) != 0) {
     (void)hipGetLastError();
-    b->d_qcol = nullptr;
     return SXMC_OK;
   }
   unsigned long long tally[2] = {0, 0};
   b->q16 = boxed;
-  hipError_t e = boxed ? sx_column_codes16(b->d_cols, b->qbase[0], b->qstep[0], n, reinterpret_cast<unsigned short*>(b->d_qcol),
+  hipError_t e = boxed ? sx_column_codes16(b->d_cols.get(), b->qbase[0], b->qstep[0], n, reinterpret_cast<unsigned short*>(b->d_qcol.get()),
                                            tally, nullptr)
-                       : sx_column_codes(b->d_cols, b->pitch, nq, b->qbase, b->qstep, n, b->d_qcol, tally, nullptr);
+                       : sx_column_codes(b->d_cols.get(), b->pitch, nq, b->qbase, b->qstep, n, b->d_qcol.get(), tally, nullptr);
   if (e != hipSuccess || (double)tally[0] > 0.02 * (double)std::max<size_t>(b->nkept, 1)) {
-    (void)hipFree(b->d_qcol);
-    b->d_qcol = nullptr;
+    b->d_qcol.reset();
     if (e != hipSuccess) return fail(SXMC_ERR_HIP, std::string("codes of a bucketed table: ") + hipGetErrorString(e));
     return SXMC_OK;
   }
@@ -436,13 +415,13 @@ int get_bucket_codes(sxmc_hist* h, const SampleStore::Bucketed* bkc, const SxSig
 // distinct event bins, as in build_sparse).  Rebuilt when the evaluation points or the untouched set change.
 int build_bucket_tables(sxmc_hist* h, const SampleStore::BucketSort* bs) {
   if (h->btab_valid && h->btab_mask == bs->mask && h->btab_points_version == h->points_version) return SXMC_OK;
-  free_bucket_tables(h);
+  reset_bucket_tables(h);
   sxplan::BucketTables bt;   // directory + per-bucket tables of the event bins (sxmc_plan.h)
   sxplan::bucket_tables(bs->nkeys_total, bs->mask, bs->radix, h->nbins.data(), h->stride.data(), h->nobs, h->targets, bt);
   const std::vector<unsigned>&dir = bt.dir, &tkeys = bt.tkeys, &tslot = bt.tslot;
-  SX_HIP(upload(dir, &h->d_bdir));
-  SX_HIP(upload(tkeys, &h->d_btkeys, 4));
-  SX_HIP(upload(tslot, &h->d_btslot, 4));
+  SX_HIP(upload(dir, h->d_bdir));
+  SX_HIP(upload(tkeys, h->d_btkeys, 4));
+  SX_HIP(upload(tslot, h->d_btslot, 4));
   h->btab_mask = bs->mask;
   h->btab_points_version = h->points_version;
   h->btab_valid = true;
@@ -475,7 +454,7 @@ inline bool is_bucketed(const LaunchClass& c) { return sx_form_bucketed(c.shape.
 // One member's part of the plan: the form its table takes and the kernel that runs it.
 struct MemberPlan {
   // the key of its launch class (find_class): shape.nobs / nslot / lds_hist / form / rtc_fill / rtc_sparse, prog,
-  // prog_simple, pre_mask, runs_mode; with it shape.static_prog and the boxed form's slots.  find_class copies it as
+  // prog_simple, pre_mask, runs_mode; with it shape.static_prog and the boxed form's slots.  find_class moves it in as
   // the new class: set nothing else on it.
   LaunchClass cls;
   // bucketed forms: what to lay out once the class's shape is known
@@ -525,7 +504,7 @@ int plan_bucketed(sxmc_group* g, int i, const sxplan::SystUse& use, int ordered,
   const int sp = sx_fill_find_program(form, cd.nobs, cd.nslot, (int)prog2.size(), prog2.data());
   if (!have_kernel(g, lds_hist, cd.nobs, cd.nslot, form, 0, prog2, sp, &k.shape.rtc_fill)) return SXMC_OK;
   const SampleStore::BucketSort* bs = nullptr;
-  int rc = get_bucket_sort(h, g->d_descs + i, cs.mask, ordered, &bs, box_truth >= 0 ? d.slot_col[box_truth] : -1);
+  int rc = get_bucket_sort(h, g->d_descs.get() + i, cs.mask, ordered, &bs, box_truth >= 0 ? d.slot_col[box_truth] : -1);
   if (rc) return rc;
   if (!bs) {
     k.shape.rtc_fill = nullptr;
@@ -613,7 +592,7 @@ int plan_member(sxmc_group* g, const DeviceProps& props, int i, MemberPlan& mp) 
 }
 
 // The launch class of a member's plan: members with the same kernel and table form share a launch.
-LaunchClass& find_class(sxmc_group* g, const MemberPlan& mp, int threads) {
+LaunchClass& find_class(sxmc_group* g, MemberPlan& mp, int threads) {
   const LaunchClass& k = mp.cls;
   for (LaunchClass& c : g->classes) {
     if (c.shape.nobs == k.shape.nobs && c.shape.nslot == k.shape.nslot && c.shape.lds_hist == k.shape.lds_hist &&
@@ -623,7 +602,7 @@ LaunchClass& find_class(sxmc_group* g, const MemberPlan& mp, int threads) {
       return c;
     }
   }
-  g->classes.push_back(k);
+  g->classes.push_back(std::move(mp.cls));   // (nothing reads the plan's key after this)
   g->classes.back().shape.threads = threads;
   return g->classes.back();
 }
@@ -645,9 +624,9 @@ int build_sparse_descs(sxmc_group* g) {
         for (int k = 0; k < i; k++) {
           const sxmc_hist* o = g->members[k];
           if (o->d_table && o->total_nbins == h->total_nbins && o->targets == h->targets) {
-            sparse_descs[(size_t)i].sparse_filter = o->d_filter;
-            sparse_descs[(size_t)i].sparse_table = o->d_table;
-            sparse_descs[(size_t)i].sparse_coarse = o->d_coarse;
+            sparse_descs[(size_t)i].sparse_filter = o->d_filter.get();
+            sparse_descs[(size_t)i].sparse_table = o->d_table.get();
+            sparse_descs[(size_t)i].sparse_coarse = o->d_coarse.get();
             break;
           }
         }
@@ -662,8 +641,8 @@ int build_sparse_descs(sxmc_group* g) {
   g->h_descs_sparse = sparse_descs;
   g->ec[0].descs_valid = g->ec[1].descs_valid = false;
   g->prezeroed = 0;
-  if (!g->d_descs_sparse) SX_HIP(hipMalloc((void**)&g->d_descs_sparse, sizeof(SxSignalDesc) * std::max(n, 1)));
-  if (n) SX_HIP(hipMemcpy(g->d_descs_sparse, sparse_descs.data(), sizeof(SxSignalDesc) * n, hipMemcpyHostToDevice));
+  if (!g->d_descs_sparse) SX_BUF(g->d_descs_sparse.alloc((size_t)std::max(n, 1)));
+  if (n) SX_HIP(hipMemcpy(g->d_descs_sparse.get(), sparse_descs.data(), sizeof(SxSignalDesc) * n, hipMemcpyHostToDevice));
   return SXMC_OK;
 }
 
@@ -739,9 +718,11 @@ int class_tables(sxmc_group* g, const std::vector<MemberPlan>& plans, const std:
       void* pre = st.find_pre(c.pre_mask, width);
       if (!pre) {
         const size_t npad = h->nvec * SXMC_VEC;
-        SX_HIP(hipMalloc(&pre, std::max<size_t>(npad * (size_t)width, 16)));
-        st.pre.push_back({c.pre_mask, width, pre});
-        SX_HIP(sx_launch_prebin(g->d_descs + idx, npad, c.pre_mask, width, pre, nullptr));
+        DeviceBuffer<void> column;
+        SX_BUF(column.alloc(std::max<size_t>(npad * (size_t)width, 16)));
+        pre = column.get();
+        st.pre.push_back({c.pre_mask, width, std::move(column)});
+        SX_HIP(sx_launch_prebin(g->d_descs.get() + idx, npad, c.pre_mask, width, pre, nullptr));
         SX_HIP(hipDeviceSynchronize());
       }
       d.pre = pre;
@@ -751,13 +732,13 @@ int class_tables(sxmc_group* g, const std::vector<MemberPlan>& plans, const std:
       const SampleStore::Bucketed* bk = nullptr;
       int rc = get_bucketed(h, plans[(size_t)idx].sort, plans[(size_t)idx].fields, runs, &bk);
       if (rc) return rc;
-      d.cols = bk->d_cols;
+      d.cols = bk->d_cols.get();
       d.col_pitch = bk->pitch;
       d.nsamples = bk->ngranules * 256;
       d.nvec = bk->ngranules * 64;
-      d.pre = bk->d_gpre;
-      d.edges = bk->d_gedge;
-      d.boxes = bk->d_gbox;
+      d.pre = bk->d_gpre.get();
+      d.edges = bk->d_gedge.get();
+      d.boxes = bk->d_gbox.get();
       if (boxed) {   // (launch-wide: the largest of the members' mean extents)
         c.box_dx = std::max(c.box_dx, (float)bk->box_dx);
         c.box_dt = std::max(c.box_dt, (float)bk->box_dt);
@@ -777,7 +758,7 @@ int class_tables(sxmc_group* g, const std::vector<MemberPlan>& plans, const std:
         rc = get_bucket_codes(h, bk, d);
         if (rc) return rc;
         if (bk->d_qcol) {
-          d.qcol = bk->d_qcol;
+          d.qcol = bk->d_qcol.get();
           for (int m = 0; m < bk->nq; m++) {
             d.qbase[m] = bk->qbase[m];
             d.qstep[m] = bk->qstep[m];
@@ -793,7 +774,7 @@ int class_tables(sxmc_group* g, const std::vector<MemberPlan>& plans, const std:
     }
     d.vec_start = prefix;
     prefix += d.nvec;
-    d.step_gate = g->d_ticket + 8;     // (read by the measurement build's gated fill only)
+    d.step_gate = g->d_ticket.get() + 8;     // (read by the measurement build's gated fill only)
     descs.push_back(d);
   }
   c.total_vec = prefix;
@@ -887,7 +868,7 @@ void class_lds_layout(sxmc_group* g, const DeviceProps& props, LaunchClass& c, c
 
 // The class's descriptors on the device, in both flavours.
 int class_upload_descs(sxmc_group* g, LaunchClass& c, const std::vector<SxSignalDesc>& descs) {
-  SX_HIP(upload(descs, &c.d_descs));
+  SX_HIP(upload(descs, c.d_descs));
   if (!(g->sparse_ready && !c.shape.lds_hist)) return SXMC_OK;
   std::vector<SxSignalDesc> sd = descs;
   for (size_t q = 0; q < sd.size(); q++) {
@@ -908,13 +889,13 @@ int class_upload_descs(sxmc_group* g, LaunchClass& c, const std::vector<SxSignal
           break;
         }
       }
-      sd[q].sparse_dir = owner->d_bdir;
-      sd[q].sparse_tkeys = owner->d_btkeys;
-      sd[q].sparse_tslot = owner->d_btslot;
-      sd[q].pre = g->member_bucket[(size_t)c.member_idx[q]]->d_gkp;   // {bucket key, bin offset} per granule
+      sd[q].sparse_dir = owner->d_bdir.get();
+      sd[q].sparse_tkeys = owner->d_btkeys.get();
+      sd[q].sparse_tslot = owner->d_btslot.get();
+      sd[q].pre = g->member_bucket[(size_t)c.member_idx[q]]->d_gkp.get();   // {bucket key, bin offset} per granule
     }
   }
-  SX_HIP(upload(sd, &c.d_descs_sparse));
+  SX_HIP(upload(sd, c.d_descs_sparse));
   return SXMC_OK;
 }
 
@@ -950,8 +931,8 @@ int class_partition(sxmc_group* g, LaunchClass& c, const std::vector<SxSignalDes
     sxplan::build_partition(nvec, c.shape.grid, c.shape.threads, g->plan_cfg.partition, segs, blk_off, c.partition,
                             bucketed ? 64 : 1, groups);
   }
-  SX_HIP(upload(segs, &c.d_segs, 1));
-  SX_HIP(upload(blk_off, &c.d_blk_off));
+  SX_HIP(upload(segs, c.d_segs, 1));
+  SX_HIP(upload(blk_off, c.d_blk_off));
   return SXMC_OK;
 }
 
@@ -992,10 +973,10 @@ int plan_twin(sxmc_group* g, Blocked& blocked) {
   const bool two = any_boxed && g->plan_cfg.box < 0;
   if (two) {
     if (!g->twin) {
-      g->twin = new sxmc_group;
+      g->twin = std::make_unique<sxmc_group>();
       g->twin->is_twin = true;
     }
-    sxmc_group* t = g->twin;
+    sxmc_group* t = g->twin.get();
     t->members = g->members;
     t->plan_cfg = g->plan_cfg;
     t->plan_cfg.box = 0;
@@ -1009,7 +990,6 @@ int plan_twin(sxmc_group* g, Blocked& blocked) {
     }
     for (LaunchClass& c : g->classes) c.dual = is_boxed(c);
   } else if (g->twin && !any_boxed) {
-    for (LaunchClass& c : g->twin->classes) free_class(c);
     g->twin->classes.clear();
   }
   if (!two) g->fill_form = 1;   // (no twin: the plan's own launches)
@@ -1025,7 +1005,6 @@ int plan_pass(sxmc_group* g, const DeviceProps& props, Blocked& blocked) {
   SX_HIP(hipDeviceSynchronize());
   const int n = (int)g->members.size();
   g->h_descs.assign((size_t)n, SxSignalDesc{});
-  for (LaunchClass& c : g->classes) free_class(c);
   g->classes.clear();
   g->max_bins = 0;
   g->max_points = 0;
@@ -1036,8 +1015,8 @@ int plan_pass(sxmc_group* g, const DeviceProps& props, Blocked& blocked) {
   if (threads < 64 || threads > 1024 || threads % 64) threads = 512;
 
   for (int i = 0; i < n; i++) fill_desc(g->members[i], g->h_descs[i]);
-  if (!g->d_descs) SX_HIP(hipMalloc((void**)&g->d_descs, sizeof(SxSignalDesc) * std::max(n, 1)));
-  if (n) SX_HIP(hipMemcpy(g->d_descs, g->h_descs.data(), sizeof(SxSignalDesc) * n, hipMemcpyHostToDevice));
+  if (!g->d_descs) SX_BUF(g->d_descs.alloc((size_t)std::max(n, 1)));
+  if (n) SX_HIP(hipMemcpy(g->d_descs.get(), g->h_descs.data(), sizeof(SxSignalDesc) * n, hipMemcpyHostToDevice));
 
   std::vector<MemberPlan> plans((size_t)n);
   g->member_bucket.assign((size_t)n, nullptr);
@@ -1095,7 +1074,7 @@ int group_update_points(sxmc_group* g) {
     sxmc_hist* h = g->members[i];
     const unsigned long long np = h->has_points ? h->npoints : 0;
     for (std::vector<SxSignalDesc>* set : {&g->h_descs, &g->h_descs_sparse}) {
-      (*set)[(size_t)i].read_bins = h->has_points ? h->d_read_bins : nullptr;
+      (*set)[(size_t)i].read_bins = h->has_points ? h->d_read_bins.get() : nullptr;
       (*set)[(size_t)i].npoints = np;
     }
     g->max_points = std::max(g->max_points, np);
@@ -1103,8 +1082,8 @@ int group_update_points(sxmc_group* g) {
     g->seen_points[(size_t)i] = h->points_version;
   }
   if (n) {
-    SX_HIP(hipMemcpy(g->d_descs, g->h_descs.data(), sizeof(SxSignalDesc) * n, hipMemcpyHostToDevice));
-    SX_HIP(hipMemcpy(g->d_descs_sparse, g->h_descs_sparse.data(), sizeof(SxSignalDesc) * n, hipMemcpyHostToDevice));
+    SX_HIP(hipMemcpy(g->d_descs.get(), g->h_descs.data(), sizeof(SxSignalDesc) * n, hipMemcpyHostToDevice));
+    SX_HIP(hipMemcpy(g->d_descs_sparse.get(), g->h_descs_sparse.data(), sizeof(SxSignalDesc) * n, hipMemcpyHostToDevice));
   }
   g->ec[0].descs_valid = g->ec[1].descs_valid = false;
   return SXMC_OK;
@@ -1133,13 +1112,6 @@ int group_check_bound(sxmc_group* g, bool need_pdf) {
   return SXMC_OK;
 }
 
-void free_event_classes(sxmc_group::EventClasses& ec) {
-  if (ec.d_rb) (void)hipFree(ec.d_rb);
-  if (ec.d_weight) (void)hipFree(ec.d_weight);
-  if (ec.d_descs) (void)hipFree(ec.d_descs);
-  ec = sxmc_group::EventClasses{};
-}
-
 // Event classes of one descriptor flavour, built on the host from the members' event-bin tables:
 // events with the same bin (counter slot) in every member contribute the same term to the event sum,
 // so the sum runs over the distinct tuples, each weighted by its multiplicity.  Tables are rebuilt when
@@ -1161,7 +1133,7 @@ int ensure_event_classes(sxmc_group* g, bool sparse) {
     std::vector<const std::vector<int>*> arr(S);
     for (size_t j = 0; j < S; j++) {
       const sxmc_hist* h = g->members[j];
-      const bool slots = sparse && flavour[j].read_bins == h->d_read_slot && h->d_read_slot != nullptr;
+      const bool slots = sparse && flavour[j].read_bins == h->d_read_slot.get() && h->d_read_slot;
       arr[j] = slots ? &h->h_read_slot : &h->h_read_bins;
       if (arr[j]->size() != E) return fail(SXMC_ERR_STATE, "event-bin table of a member is missing");
     }
@@ -1170,20 +1142,10 @@ int ensure_event_classes(sxmc_group* g, bool sparse) {
     const size_t K = cls.K;
     const std::vector<int>& tables = cls.tables;
     const std::vector<unsigned>& weight = cls.weight;
-    if (tables.size() > ec.cap_rb) {
-      if (ec.d_rb) SX_HIP(hipFree(ec.d_rb));
-      ec.d_rb = nullptr;
-      ec.cap_rb = tables.size() + tables.size() / 4;
-      SX_HIP(hipMalloc((void**)&ec.d_rb, sizeof(int) * ec.cap_rb));
-    }
-    if (std::max<size_t>(K, 1) > ec.cap_weight) {
-      if (ec.d_weight) SX_HIP(hipFree(ec.d_weight));
-      ec.d_weight = nullptr;
-      ec.cap_weight = K + K / 4 + 16;
-      SX_HIP(hipMalloc((void**)&ec.d_weight, sizeof(unsigned) * ec.cap_weight));
-    }
-    SX_HIP(hipMemcpy(ec.d_rb, tables.data(), sizeof(int) * tables.size(), hipMemcpyHostToDevice));
-    if (K) SX_HIP(hipMemcpy(ec.d_weight, weight.data(), sizeof(unsigned) * K, hipMemcpyHostToDevice));
+    if (tables.size() > ec.d_rb.capacity()) SX_BUF(ec.d_rb.grow(tables.size() + tables.size() / 4));
+    if (std::max<size_t>(K, 1) > ec.d_weight.capacity()) SX_BUF(ec.d_weight.grow(K + K / 4 + 16));
+    SX_HIP(hipMemcpy(ec.d_rb.get(), tables.data(), sizeof(int) * tables.size(), hipMemcpyHostToDevice));
+    if (K) SX_HIP(hipMemcpy(ec.d_weight.get(), weight.data(), sizeof(unsigned) * K, hipMemcpyHostToDevice));
     ec.K = K;
     ec.seen_points.resize(S);
     for (size_t j = 0; j < S; j++) ec.seen_points[j] = g->members[j]->points_version;
@@ -1192,12 +1154,12 @@ int ensure_event_classes(sxmc_group* g, bool sparse) {
   }
   std::vector<SxSignalDesc> descs = flavour;
   for (size_t j = 0; j < S; j++) {
-    descs[j].read_bins = ec.d_rb + j * ec.K;
+    descs[j].read_bins = ec.d_rb.get() + j * ec.K;
     descs[j].npoints = ec.K;
     descs[j].pdf_out = nullptr;
   }
-  if (!ec.d_descs) SX_HIP(hipMalloc((void**)&ec.d_descs, sizeof(SxSignalDesc) * std::max<size_t>(S, 1)));
-  SX_HIP(hipMemcpy(ec.d_descs, descs.data(), sizeof(SxSignalDesc) * S, hipMemcpyHostToDevice));
+  if (!ec.d_descs) SX_BUF(ec.d_descs.alloc(std::max<size_t>(S, 1)));
+  SX_HIP(hipMemcpy(ec.d_descs.get(), descs.data(), sizeof(SxSignalDesc) * S, hipMemcpyHostToDevice));
   ec.descs_valid = true;
   return SXMC_OK;
 }
@@ -1221,8 +1183,8 @@ int group_prepare_fill(sxmc_group* g, hipStream_t s, bool sparse) {
   g->prezeroed = 0;
   g->last_sparse = sparse;
   if (!skip_zero) {
-    SX_HIP(sx_launch_zero(sparse ? g->d_descs_sparse : g->d_descs, (int)g->members.size(),
-                          sparse ? g->max_bins_sparse : g->max_bins, g->d_ticket, s));
+    SX_HIP(sx_launch_zero(sparse ? g->d_descs_sparse.get() : g->d_descs.get(), (int)g->members.size(),
+                          sparse ? g->max_bins_sparse : g->max_bins, g->d_ticket.get(), s));
   }
   for (size_t i = 0; i < g->members.size(); i++) {
     g->members[i]->bins_valid = g->members[i]->total_nbins > kLdsMaxBins ? !sparse : true;
@@ -1236,7 +1198,7 @@ int group_fill(sxmc_group* g, hipStream_t s, bool sparse) {
   int rc = group_prepare_fill(g, s, sparse);
   if (rc) return rc;
   // (a boxed plan with an ordered twin: the launches of the plan fill_form names -- sxmc_group_adapt_fill_form)
-  sxmc_group* plan = (g->twin && !g->twin->classes.empty() && g->fill_form == 2 && g->plan_cfg.box < 0) ? g->twin : g;
+  sxmc_group* plan = (g->twin && !g->twin->classes.empty() && g->fill_form == 2 && g->plan_cfg.box < 0) ? g->twin.get() : g;
   for (LaunchClass& c : plan->classes) {
     // profiled launches (sxmc_group_profile) carry two events stamped with the dispatch's own begin and end
     const bool rec = g->prof && !t_capturing && g->prof_n < (int)g->ev0.size() && c.shape.grid > 0;
@@ -1244,10 +1206,10 @@ int group_fill(sxmc_group* g, hipStream_t s, bool sparse) {
     c.shape.ev_stop = rec ? (void*)g->ev1[g->prof_n] : nullptr;
     c.shape.debug_mode = g->debug_mode;
     if (sparse && c.d_descs_sparse && c.shape.sparse_runs) {
-      SX_HIP(sx_launch_fill_sparse_runs(c.shape, c.d_descs_sparse, c.d_segs, c.d_blk_off, s));
+      SX_HIP(sx_launch_fill_sparse_runs(c.shape, c.d_descs_sparse.get(), c.d_segs.get(), c.d_blk_off.get(), s));
     } else {
-      SX_HIP(sx_launch_fill(c.shape, (sparse && c.d_descs_sparse) ? c.d_descs_sparse : c.d_descs, c.d_segs,
-                            c.d_blk_off, s));
+      SX_HIP(sx_launch_fill(c.shape, (sparse && c.d_descs_sparse) ? c.d_descs_sparse.get() : c.d_descs.get(), c.d_segs.get(),
+                            c.d_blk_off.get(), s));
     }
     c.shape.ev_start = c.shape.ev_stop = nullptr;
     if (rec) g->prof_n++;

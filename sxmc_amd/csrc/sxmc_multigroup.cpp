@@ -169,10 +169,10 @@ int sxmc_multigroup_step_async(sxmc_multigroup_t mg, sxmc_stream_t s, const sxmc
     const LaunchClass& c0 = g0->classes[i];
     if (c0.shape.grid <= 0) continue;
     SxChainDescsHost ch{};
-    for (size_t c = 0; c < C; c++) ch.d[c] = mg->groups[c]->classes[i].d_descs;
+    for (size_t c = 0; c < C; c++) ch.d[c] = mg->groups[c]->classes[i].d_descs.get();
     const bool rec = g0->prof && !t_capturing && g0->prof_n < (int)g0->ev0.size();
-    SX_HIP(sx_rtc_launch_multi(mg->fill_fn[i], c0.shape.grid, c0.shape.threads, mg->lds_bytes[i], ch, c0.d_segs,
-                               c0.d_blk_off, mg->fill_w[i], (unsigned)mg->groups[0]->debug_mode, st,
+    SX_HIP(sx_rtc_launch_multi(mg->fill_fn[i], c0.shape.grid, c0.shape.threads, mg->lds_bytes[i], ch, c0.d_segs.get(),
+                               c0.d_blk_off.get(), mg->fill_w[i], (unsigned)mg->groups[0]->debug_mode, st,
                                rec ? (void*)g0->ev0[g0->prof_n] : nullptr, rec ? (void*)g0->ev1[g0->prof_n] : nullptr));
     if (rec) g0->prof_n++;
   }
@@ -190,13 +190,13 @@ int sxmc_multigroup_step_async(sxmc_multigroup_t mg, sxmc_stream_t s, const sxmc
     const sxmc_step_args& p = args[c];
     g->last_step_launches += (int)g0->classes.size();
     unsigned long long ne = g->members[0]->npoints;
-    const SxSignalDesc* descs = g->d_descs;
+    const SxSignalDesc* descs = g->d_descs.get();
     const unsigned* weight = nullptr;
     if (!g->cfg_lut) {
       const sxmc_group::EventClasses& ec = g->ec[0];
       ne = ec.K;
-      descs = ec.d_descs;
-      weight = ec.d_weight;
+      descs = ec.d_descs.get();
+      weight = ec.d_weight.get();
     }
     SxStepArgs a;
     a.nsignals = g->members.size();
@@ -221,11 +221,11 @@ int sxmc_multigroup_step_async(sxmc_multigroup_t mg, sxmc_stream_t s, const sxmc
     if (joint) {
       SxChainEnd& e = ends.c[c];
       e.lookup_descs = descs;
-      e.hist_descs = g->d_descs;
+      e.hist_descs = g->d_descs.get();
       e.nrows = ne;
       e.weight = weight;
-      e.sums = g->d_step_sums;
-      e.ticket = g->d_ticket;
+      e.sums = g->d_step_sums.get();
+      e.ticket = g->d_ticket.get();
       e.nblocks = (unsigned)step_sum_blocks(ne);
       e.a = a;
       g->last_step_launches += 2;
@@ -310,11 +310,11 @@ int sxmc_multigroup_lookahead_step_async(sxmc_multigroup_t mg, sxmc_stream_t s, 
     const LaunchClass& c0 = ga->classes[i];
     if (c0.shape.grid <= 0) continue;
     SxChainDescsHost ch{};
-    ch.d[0] = ga->classes[i].d_descs;
-    ch.d[1] = gb->classes[i].d_descs;
+    ch.d[0] = ga->classes[i].d_descs.get();
+    ch.d[1] = gb->classes[i].d_descs.get();
     const bool rec = ga->prof && !t_capturing && ga->prof_n < (int)ga->ev0.size();
-    SX_HIP(sx_rtc_launch_multi(mg->fill_fn[i], c0.shape.grid, c0.shape.threads, mg->lds_bytes[i], ch, c0.d_segs,
-                               c0.d_blk_off, mg->fill_w[i], (unsigned)mg->groups[0]->debug_mode, st,
+    SX_HIP(sx_rtc_launch_multi(mg->fill_fn[i], c0.shape.grid, c0.shape.threads, mg->lds_bytes[i], ch, c0.d_segs.get(),
+                               c0.d_blk_off.get(), mg->fill_w[i], (unsigned)mg->groups[0]->debug_mode, st,
                                rec ? (void*)ga->ev0[ga->prof_n] : nullptr, rec ? (void*)ga->ev1[ga->prof_n] : nullptr));
     if (rec) ga->prof_n++;
   }
@@ -348,15 +348,15 @@ int sxmc_multigroup_lookahead_step_async(sxmc_multigroup_t mg, sxmc_stream_t s, 
   // (step_end2_kernel; the same switch as the sequential step's), else lookup + event sums, then step end + clearing
   const bool coop = 2 * half <= kCoopMaxWorkers && step_end_is_cooperative(ga, ne);
   if (coop) {
-    SX_HIP(sx_launch_step_end2(ea.d_descs, eb.d_descs, ga->d_descs, gb->d_descs, (int)ga->members.size(),
-                               std::max(ga->max_bins, gb->max_bins), ne, ea.d_weight, eb.d_weight, ga->d_coop_slots,
-                               ga->d_coop_last, ga->d_ticket, half, d_norms_lookahead, d_v_lookahead, d_cap, k, st));
+    SX_HIP(sx_launch_step_end2(ea.d_descs.get(), eb.d_descs.get(), ga->d_descs.get(), gb->d_descs.get(), (int)ga->members.size(),
+                               std::max(ga->max_bins, gb->max_bins), ne, ea.d_weight.get(), eb.d_weight.get(), ga->d_coop_slots.get(),
+                               ga->d_coop_last.get(), ga->d_ticket.get(), half, d_norms_lookahead, d_v_lookahead, d_cap, k, st));
   } else {
-    SX_HIP(sx_launch_eval_nll2(ea.d_descs, eb.d_descs, (int)ga->members.size(), ne, ea.d_weight, eb.d_weight,
+    SX_HIP(sx_launch_eval_nll2(ea.d_descs.get(), eb.d_descs.get(), (int)ga->members.size(), ne, ea.d_weight.get(), eb.d_weight.get(),
                                a->d_v_proposed, d_v_lookahead, a->d_nexpected, a->d_n_mc, a->d_source_id, a->d_norms,
-                               d_norms_lookahead, ga->d_step_sums, gb->d_step_sums, half, block, st));
-    SX_HIP(sx_launch_finish2_zero(ga->d_descs, gb->d_descs, (int)ga->members.size(), std::max(ga->max_bins, gb->max_bins),
-                                  (size_t)half, ga->d_step_sums, gb->d_step_sums, d_norms_lookahead, d_v_lookahead, d_cap, k,
+                               d_norms_lookahead, ga->d_step_sums.get(), gb->d_step_sums.get(), half, block, st));
+    SX_HIP(sx_launch_finish2_zero(ga->d_descs.get(), gb->d_descs.get(), (int)ga->members.size(), std::max(ga->max_bins, gb->max_bins),
+                                  (size_t)half, ga->d_step_sums.get(), gb->d_step_sums.get(), d_norms_lookahead, d_v_lookahead, d_cap, k,
                                   128, st));
   }
   for (size_t c = 0; c < 2; c++) {

@@ -48,17 +48,6 @@ int get_props(DeviceProps& p) {
   return SXMC_OK;
 }
 
-void free_class(LaunchClass& c) {
-  if (c.d_descs) (void)hipFree(c.d_descs);
-  if (c.d_descs_sparse) (void)hipFree(c.d_descs_sparse);
-  c.d_descs_sparse = nullptr;
-  if (c.d_segs) (void)hipFree(c.d_segs);
-  if (c.d_blk_off) (void)hipFree(c.d_blk_off);
-  c.d_descs = nullptr;
-  c.d_segs = nullptr;
-  c.d_blk_off = nullptr;
-}
-
 // LAZY EvalFinished.  A batch launched on the legacy default stream is ordered, on the device, before everything the
 // caller does next through this ABI on that stream or on any blocking stream -- its NLL kernels (mcmc.cpp:314-348),
 // blocking copies to the host, the next evaluation.  So sxmc_hist_eval_finished of such a batch does not stop the host:
