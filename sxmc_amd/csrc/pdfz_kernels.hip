@@ -207,8 +207,26 @@ struct EvalMember {
 // tables, the first row's weight: set by SetEvalPoints) have been ISSUED and before anything the fill writes is read
 // (histograms, normalisations): the fused step kernel waits there for the fill's workgroups, with those loads in
 // flight under the wait.
-template <int BD = 0, typename Ready>   // (BD > 0: the workgroup's logical size, see block_sum in nll_device.h)
-__device__ __forceinline__ double eval_nll_block_part(const SxSignalDesc* __restrict__ descs, int nsig,
+//
+// WHERE THE LOOK-UP POINTERS COME FROM (`mem`).  MembersFromDescs: the descriptor array in device memory (every form but one).
+// MembersFromTable: also the by-value table of the cooperative step end (SxStepEndTable, at most 16 members, a kernel
+// argument: the pointers to the rows' bins and to the histograms sit in scalar registers from the start).  With it the
+// first row's gathers bins[rb] are issued as soon as rb is there, BEFORE the LDS staging of the members' factors and its
+// barrier, which they need nothing from: the staging's own two dependent loads (descriptor j, then its normalisation;
+// source_id, then the parameter) run beside the look-ups' two instead of between them.
+// The arithmetic is one text for both: same expressions, same order, same partial sums.
+struct MembersFromDescs {
+  static constexpr bool kTable = false;
+  const SxSignalDesc* __restrict__ descs;
+};
+struct MembersFromTable {
+  static constexpr bool kTable = true;
+  const SxSignalDesc* __restrict__ descs;
+  const SxStepEndTable& t;
+};
+
+template <int BD = 0, typename Members, typename Ready>   // (BD > 0: the workgroup's logical size, see block_sum in nll_device.h)
+__device__ __forceinline__ double eval_nll_block_part(const Members& mem, int nsig,
                                                       unsigned long long npoints, const unsigned* __restrict__ weight,
                                                       const double* __restrict__ pars,
                                                       const double* __restrict__ nexpected,
@@ -216,6 +234,7 @@ __device__ __forceinline__ double eval_nll_block_part(const SxSignalDesc* __rest
                                                       const short* __restrict__ source_id,
                                                       const unsigned* __restrict__ norms, double* sh,
                                                       unsigned block_index, unsigned nblocks, Ready&& ready) {
+  constexpr bool kTable = Members::kTable;
   double* s_wave = sh;  // [16] wave sums, then nsig EvalMember records
   EvalMember* s_mem = reinterpret_cast<EvalMember*>(sh + 16);
   const unsigned bdim = BD > 0 ? (unsigned)BD : blockDim.x;
@@ -224,6 +243,7 @@ __device__ __forceinline__ double eval_nll_block_part(const SxSignalDesc* __rest
   // need only the descriptors (uniform, scalar loads), so the loads fly while the per-member factors
   // below are fetched and staged.
   constexpr int U = 16;
+  static_assert(!kTable || U == SXMC_STEP_END_MEMBERS, "the table holds one pass of members");
   int rb[U];
   unsigned long long i = (unsigned long long)block_index * bdim + threadIdx.x;
   // (clamped indices, no branches: all U table addresses are fetched together, then all U loads issued)
@@ -231,11 +251,18 @@ __device__ __forceinline__ double eval_nll_block_part(const SxSignalDesc* __rest
     const unsigned long long evc = ev < npoints ? ev : npoints - 1;
     gptr<const int> table[U];
 #pragma unroll
-    for (int u = 0; u < U; u++) table[u] = to_global(descs[min(j0 + u, nsig - 1)].read_bins);
+    for (int u = 0; u < U; u++) {
+      if constexpr (kTable) table[u] = to_global(mem.t.read_bins[u]);   // (entries past nsig repeat the last member)
+      else table[u] = to_global(mem.descs[min(j0 + u, nsig - 1)].read_bins);
+    }
 #pragma unroll
     for (int u = 0; u < U; u++) rb[u] = table[u][evc];
 #pragma unroll
     for (int u = 0; u < U; u++) rb[u] = (j0 + u < nsig && ev < npoints) ? rb[u] : -2;
+  };
+  auto bins_of = [&](int j0, int u) {
+    if constexpr (kTable) return to_global(mem.t.bins[u]);
+    else return to_global(s_mem[j0 + u].bins);
   };
   if (npoints == 0 || nsig <= 0) {   // uniform: nothing to look up
     ready();
@@ -243,18 +270,56 @@ __device__ __forceinline__ double eval_nll_block_part(const SxSignalDesc* __rest
   }
   load_read_bins(i, 0);
   unsigned wfirst = weight ? to_global(weight)[i < npoints ? i : npoints - 1] : 1u;
-  ready();
+  unsigned count[U];   // (table form: the first row's counts are gathered before the staging barrier)
 
-  for (int j = threadIdx.x; j < nsig; j += (int)bdim) {
-    const SxSignalDesc& d = descs[j];
+  // member j's staged record from its loaded inputs (one text for both forms)
+  auto stage = [&](int j, const SxSignalDesc& d, unsigned normv, double volume, unsigned nj, unsigned nmc, double par,
+                   double nexp) {
     s_mem[j].read_bins = d.read_bins;
     s_mem[j].bins = d.bins;
     s_mem[j].out = d.pdf_out;
     s_mem[j].stride = d.pdf_stride;
-    s_mem[j].bin_norm = (double)(*to_global((const unsigned*)d.norm)) * d.bin_volume;
-    const float eff = (float)(1.0 * norms[j] / n_mc[j]);             // nll_kernels.cpp:105
-    s_mem[j].coef = pars[source_id[j]] * nexpected[j] * eff;         // left-to-right, :107
+    s_mem[j].bin_norm = (double)normv * volume;
+    const float eff = (float)(1.0 * nj / nmc);                       // nll_kernels.cpp:105
+    s_mem[j].coef = par * nexp * eff;                                // left-to-right, :107
+  };
+  if constexpr (kTable) {
+    // Lane j stages member j (at most 16: one pass).  Every lane loads, at a clamped index, so that the loads are one
+    // instruction stream in the order of what they depend on: first what needs nothing (issued right behind the rows'
+    // bins), then -- once the rows' bins are there -- the gathers, and beside them the staging's second level.
+    const int j = min((int)threadIdx.x, nsig - 1);
+    const SxSignalDesc& d = mem.descs[j];
+    const unsigned* normp = d.norm;
+    const double volume = d.bin_volume;
+    const short sid = source_id[j];
+    const unsigned nmc = n_mc[j];
+    const double nexp = nexpected[j];
+    ready();
+    const unsigned nj = norms[j];
+    const unsigned normv = *to_global(normp);
+    const double par = pars[sid];
+    // (the gathers without branches -- a row outside a member reads bin 0 and drops it: with every load issued on every
+    //  path the waits below count exactly, and none of them stands between the gathers and the staging's loads)
+#pragma unroll
+    for (int u = 0; u < U; u++) count[u] = bins_of(0, u)[rb[u] >= 0 ? rb[u] : 0];
+#pragma unroll
+    for (int u = 0; u < U; u++) count[u] = (rb[u] >= 0) ? count[u] : 0u;
+    // (no `if (threadIdx.x < nsig)`: the lanes past the last member store its record once more, the same values to the
+    //  same place -- behind a branch the compiler moves every load above into it, BEHIND the gathers and their waits)
+    stage(j, d, normv, volume, nj, nmc, par, nexp);
+  } else {
+    ready();
+    for (int j = threadIdx.x; j < nsig; j += (int)bdim) {
+      const SxSignalDesc& d = mem.descs[j];
+      stage(j, d, *to_global((const unsigned*)d.norm), d.bin_volume, norms[j], n_mc[j], pars[source_id[j]], nexpected[j]);
+    }
   }
+#if SXMC_WG_STAMPS
+  if (kTable && BD == 0) {
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");                 // (measurement build: the gathers have landed)
+    SX_WG_STAMP(1);
+  }
+#endif
   __syncthreads();
 
   double sum = 0.0;
@@ -266,11 +331,19 @@ __device__ __forceinline__ double eval_nll_block_part(const SxSignalDesc* __rest
     //  path that is nothing but round trips)
     const unsigned wrow = requested ? wfirst : (weight ? to_global(weight)[i] : 1u);
     for (int j0 = 0; j0 < nsig; j0 += U) {
+      const bool gathered = kTable && requested;
       if (!requested) load_read_bins(i, j0);
       requested = false;
-      unsigned count[U];
+      if (!gathered) {
 #pragma unroll
-      for (int u = 0; u < U; u++) count[u] = (rb[u] >= 0) ? to_global(s_mem[j0 + u].bins)[rb[u]] : 0u;
+        for (int u = 0; u < U; u++) count[u] = (rb[u] >= 0) ? bins_of(j0, u)[rb[u]] : 0u;
+      }
+#if SXMC_WG_STAMPS
+      if (!kTable && BD == 0 && i < bdim * nblocks) {
+        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");               // (measurement build: the gathers have landed)
+        SX_WG_STAMP(1);
+      }
+#endif
 #pragma unroll
       for (int u = 0; u < U; u++) {
         if (j0 + u < nsig) {
@@ -297,6 +370,19 @@ __device__ __forceinline__ double eval_nll_block_part(const SxSignalDesc* __rest
     for (int w = 0; w < (int)(bdim / kWave); w++) t += s_wave[w];
   }
   return t;
+}
+
+template <int BD = 0, typename Ready>
+__device__ __forceinline__ double eval_nll_block_part(const SxSignalDesc* __restrict__ descs, int nsig,
+                                                      unsigned long long npoints, const unsigned* __restrict__ weight,
+                                                      const double* __restrict__ pars,
+                                                      const double* __restrict__ nexpected,
+                                                      const unsigned* __restrict__ n_mc,
+                                                      const short* __restrict__ source_id,
+                                                      const unsigned* __restrict__ norms, double* sh,
+                                                      unsigned block_index, unsigned nblocks, Ready&& ready) {
+  return eval_nll_block_part<BD>(MembersFromDescs{descs}, nsig, npoints, weight, pars, nexpected, n_mc, source_id, norms,
+                                 sh, block_index, nblocks, ready);
 }
 
 template <int BD = 0>
@@ -557,8 +643,9 @@ constexpr unsigned long long kSlotEmpty = 0x7FF8DEADBEEF0001ull, kSlotNaN = 0x7F
 // `ready`: called by every thread of the workgroup, once, before anything the fill writes is read (see
 // eval_nll_block_part): nothing for step_end_kernel, whose launch follows the fill's; the wait for the fill's workgroups
 // in fill_step_kernel.
-template <int BD, typename Ready>
-__device__ __forceinline__ void step_end_role(unsigned role, unsigned W, const SxSignalDesc* __restrict__ lookup_descs,
+// `lookup`: where the workers' members come from (MembersFromDescs / MembersFromTable, see eval_nll_block_part).
+template <int BD, typename Members, typename Ready>
+__device__ __forceinline__ void step_end_role(unsigned role, unsigned W, const Members& lookup,
                                               const SxSignalDesc* __restrict__ hist_descs, int nsig,
                                               unsigned long long npoints, const unsigned* __restrict__ weight,
                                               unsigned long long* slots, double* last_good, unsigned* sync,
@@ -596,6 +683,7 @@ __device__ __forceinline__ void step_end_role(unsigned role, unsigned W, const S
                                         s_part[i] = t;
                                       }
                                       __syncthreads();
+                                      if (BD == 0) SX_WG_STAMP(1);   // (measurement build: the finisher holds all partials)
                                       // every partial is in: the look-ups are over.  Empty the slots -- for the next
                                       // launch, and as the workers' signal that the histograms may be cleared.
                                       if (i < nvb) {
@@ -613,17 +701,19 @@ __device__ __forceinline__ void step_end_role(unsigned role, unsigned W, const S
 #endif
     for (int j = threadIdx.x; j < nsig; j += (int)bdim) *hist_descs[j].norm = 0u;
     if (threadIdx.x == 0) sync[0] = 0u;   // (the ticket of the other step-end forms: as finish_zero_kernel leaves it)
+    if (BD == 0) SX_WG_STAMP(2);
     return;
   }
   // ---- a worker: its virtual block of the event sum, as eval_nll_kernel's workgroup does it
   const unsigned vb = role;
-  const double t = eval_nll_block_part<BD>(lookup_descs, nsig, npoints, weight, a.v_proposed, a.nexpected, a.n_mc,
+  const double t = eval_nll_block_part<BD>(lookup, nsig, npoints, weight, a.v_proposed, a.nexpected, a.n_mc,
                                            a.source_id, a.norms, sh, vb, nvb, ready);
   __shared__ int s_clear;
   if (threadIdx.x == 0) {
     __hip_atomic_store(slots + vb, isnan(t) ? kSlotNaN : (unsigned long long)__double_as_longlong(t), __ATOMIC_RELAXED,
                        __HIP_MEMORY_SCOPE_AGENT);
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");   // (the store has landed before this lane starts reading the slot)
+    if (BD == 0) SX_WG_STAMP(2);                       // (measurement build: the worker's slot is stored)
     // the histograms may be cleared once the finisher has every worker's partial: it then empties the slots
     unsigned it = 0;
     for (; it < kEndSpinLimit; it++) {
@@ -649,14 +739,23 @@ __device__ __forceinline__ void step_end_role(unsigned role, unsigned W, const S
   }
 }
 
+// TABLE: the workers' look-up pointers arrive by value (`table`: groups of up to 16 members -- the flagship's and config
+// 2's step end) beside `lookup_descs`; otherwise everything comes from `lookup_descs`, and `table` is not read.
+template <bool TABLE>
 __global__ __launch_bounds__(128) void step_end_kernel(const SxSignalDesc* __restrict__ lookup_descs,
                                                        const SxSignalDesc* __restrict__ hist_descs, int nsig,
                                                        unsigned long long npoints, const unsigned* __restrict__ weight,
                                                        unsigned long long* slots, double* last_good, unsigned* sync,
-                                                       unsigned nvb, unsigned zblocks, SxStepArgs a) {
+                                                       unsigned nvb, unsigned zblocks, SxStepArgs a, SxStepEndTable table) {
   extern __shared__ double sh[];
-  step_end_role<0>(blockIdx.x, gridDim.x - 1u, lookup_descs, hist_descs, nsig, npoints, weight, slots, last_good, sync,
-                   nvb, zblocks, a, sh, [] {});
+  SX_WG_STAMP(0);   // (measurement build: entry; worker: gathers landed / finisher: all partials held; slot stored / exit)
+  if constexpr (TABLE) {
+    step_end_role<0>(blockIdx.x, gridDim.x - 1u, MembersFromTable{lookup_descs, table}, hist_descs, nsig, npoints, weight, slots,
+                     last_good, sync, nvb, zblocks, a, sh, [] {});
+  } else {
+    step_end_role<0>(blockIdx.x, gridDim.x - 1u, MembersFromDescs{lookup_descs}, hist_descs, nsig, npoints, weight, slots,
+                     last_good, sync, nvb, zblocks, a, sh, [] {});
+  }
 }
 
 // THE WHOLE STEP IN ONE LAUNCH: fill_step_kernel = a fill kernel + the roles above as extra workgroups of the SAME launch.
@@ -724,7 +823,7 @@ __device__ __forceinline__ void fill_step_body(unsigned nfill, const SxTailArgs&
     SX_WG_STAMP(1);
     __syncthreads();
   };
-  step_end_role<128>(role, W, t.lookup_descs, t.hist_descs, t.nsig, t.npoints, t.weight, t.slots, t.last_good, t.sync,
+  step_end_role<128>(role, W, MembersFromDescs{t.lookup_descs}, t.hist_descs, t.nsig, t.npoints, t.weight, t.slots, t.last_good, t.sync,
                      t.nvb, t.zblocks, t.a, sh_tail, fill_done);
   // the finisher is the last to need the count of this launch: it zeroes it for the next one
   if (role == W && threadIdx.x == 0) {
@@ -1309,14 +1408,20 @@ hipError_t sx_launch_finish_zero(const SxSignalDesc* d_descs, int nsig, int max_
 
 hipError_t sx_launch_step_end(const SxSignalDesc* lookup_descs, const SxSignalDesc* hist_descs, int nsig, int max_bins,
                               unsigned long long npoints, const unsigned* weight, unsigned long long* slots,
-                              double* last_good, unsigned* sync, int nvb, const SxStepArgs& a, hipStream_t s) {
+                              double* last_good, unsigned* sync, int nvb, const SxStepArgs& a, hipStream_t s,
+                              const SxStepEndTable* table) {
   const int block = 128;   // (the rows of a virtual block of the event sum: eval_nll_kernel's workgroup)
   const size_t shmem = 16 * sizeof(double) + (size_t)((nsig + 15) / 16 * 16) * sizeof(EvalMember);  // whole chunks
   int zb = (max_bins / 4 + block - 1) / block;
   if (zb < 1) zb = 1;
   if (zb > 1024) zb = 1024;
-  hipLaunchKernelGGL(step_end_kernel, dim3((unsigned)nvb + 1u), dim3(block), shmem, s, lookup_descs, hist_descs, nsig,
-                     npoints, weight, slots, last_good, sync, (unsigned)nvb, (unsigned)zb, a);
+  if (table && nsig <= SXMC_STEP_END_MEMBERS) {
+    hipLaunchKernelGGL(step_end_kernel<true>, dim3((unsigned)nvb + 1u), dim3(block), shmem, s, lookup_descs, hist_descs,
+                       nsig, npoints, weight, slots, last_good, sync, (unsigned)nvb, (unsigned)zb, a, *table);
+  } else {
+    hipLaunchKernelGGL(step_end_kernel<false>, dim3((unsigned)nvb + 1u), dim3(block), shmem, s, lookup_descs, hist_descs,
+                       nsig, npoints, weight, slots, last_good, sync, (unsigned)nvb, (unsigned)zb, a, SxStepEndTable{});
+  }
   return hipGetLastError();
 }
 
@@ -1341,7 +1446,10 @@ hipError_t sx_launch_step_end2(const SxSignalDesc* lookup_a, const SxSignalDesc*
 int sx_step_end_resident_capacity(int nsig, int cus) {
   const size_t shmem = 16 * sizeof(double) + (size_t)((nsig + 15) / 16 * 16) * sizeof(EvalMember);
   int per_cu = 0;
-  if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, step_end_kernel, 128, shmem) != hipSuccess) {
+  const hipError_t e = nsig <= SXMC_STEP_END_MEMBERS
+                           ? hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, step_end_kernel<true>, 128, shmem)
+                           : hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, step_end_kernel<false>, 128, shmem);
+  if (e != hipSuccess) {
     (void)hipGetLastError();
     return 0;
   }

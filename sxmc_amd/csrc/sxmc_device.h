@@ -36,6 +36,30 @@ struct SxStepArgs {
   unsigned gate_value = 0;
 };
 
+// The cooperative step end's look-up pointers BY VALUE (step_end_kernel<true>): per member the two tables a worker's
+// dependent loads go through -- the rows' bins, then the histogram at those bins -- as a kernel argument, so that they
+// arrive in scalar registers with the launch instead of behind two more loads (the descriptor array's address, then
+// fields of descriptors that span several cache lines each).  Built by the host from the same descriptors it uploads
+// (sx_step_end_table_fill), wherever it uploads them; groups of more than SXMC_STEP_END_MEMBERS members keep the
+// descriptor form.  Only what sits on that chain is here: 16 members x 4 scalar registers is what a wave can hold
+// without spilling (a member's other fields -- normalisation, bin volume, lookup-table output -- feed the LDS staging,
+// which lane j reads from descriptor j in parallel with the look-ups and needs no sooner than they land; the
+// per-signal rates nexpected / n_mc / source_id are the caller's device arrays, which the library cannot see change).
+#define SXMC_STEP_END_MEMBERS 16
+struct SxStepEndTable {   // (entries past the last member repeat it: every entry can be addressed)
+  const int* read_bins[SXMC_STEP_END_MEMBERS];    // the rows' bins (event classes, or the events themselves)
+  const unsigned* bins[SXMC_STEP_END_MEMBERS];
+};
+inline bool sx_step_end_table_fill(SxStepEndTable& t, const SxSignalDesc* descs, size_t nsig) {
+  if (nsig == 0 || nsig > SXMC_STEP_END_MEMBERS) return false;
+  for (size_t u = 0; u < SXMC_STEP_END_MEMBERS; u++) {
+    const SxSignalDesc& d = descs[u < nsig ? u : nsig - 1];
+    t.read_bins[u] = d.read_bins;
+    t.bins[u] = d.bins;
+  }
+  return true;
+}
+
 // The step ends of the chains of a lockstep set, launched together (sxmc_multigroup_step_async): per chain what
 // eval_nll_kernel and finish_zero_kernel take.  Passed by value (kernel argument); the chain is blockIdx.y.
 #define SXMC_MAX_LOCKSTEP 4
@@ -117,7 +141,8 @@ hipError_t sx_rtc_launch(void* fn, int grid, int threads, size_t lds_bytes, cons
 hipError_t sx_launch_zero(const SxSignalDesc* d_descs, int nsig, int max_bins, unsigned* ticket, hipStream_t s);
 hipError_t sx_launch_step_end(const SxSignalDesc* lookup_descs, const SxSignalDesc* hist_descs, int nsig, int max_bins,
                               unsigned long long npoints, const unsigned* weight, unsigned long long* slots,
-                              double* last_good, unsigned* sync, int nvb, const SxStepArgs& a, hipStream_t s);
+                              double* last_good, unsigned* sync, int nvb, const SxStepArgs& a, hipStream_t s,
+                              const SxStepEndTable* table = nullptr);   // (the lookup members by value, or null)
 hipError_t sx_launch_step_end2(const SxSignalDesc* lookup_a, const SxSignalDesc* lookup_b, const SxSignalDesc* hist_a,
                                const SxSignalDesc* hist_b, int nsig, int max_bins, unsigned long long npoints,
                                const unsigned* weight_a, const unsigned* weight_b, unsigned long long* slots,

@@ -679,9 +679,21 @@ int group_step_tail(sxmc_group* g, hipStream_t st, bool sparse, const SxSignalDe
   } else if (step_end_is_cooperative(g, ne)) {
     // ONE launch: the event sum's workgroups + a finisher that waits for them inside the kernel (step_end_kernel)
     const int nvb = step_sum_blocks(ne);
+    // up to 16 members: the workers take the lookup descriptors by value (SxStepEndTable) -- the event classes' copy, made
+    // where their descriptors are uploaded, or for rows that are the events themselves the members' own descriptors as
+    // the host holds them (h_descs: uploaded whenever they change)
+    const sxmc_group::EventClasses& ec = g->ec[sparse ? 1 : 0];
+    SxStepEndTable own;
+    const SxStepEndTable* table = nullptr;
+    if (descs == ec.d_descs.get() && ec.d_descs) {
+      table = ec.has_table ? &ec.table : nullptr;
+    } else {
+      const std::vector<SxSignalDesc>& flavour = sparse ? g->h_descs_sparse : g->h_descs;
+      if (sx_step_end_table_fill(own, flavour.data(), flavour.size())) table = &own;
+    }
     SX_HIP(sx_launch_step_end(descs, sparse ? g->d_descs_sparse.get() : g->d_descs.get(), (int)g->members.size(),
                               sparse ? g->max_bins_sparse : g->max_bins, ne, weight, g->d_coop_slots.get(), g->d_coop_last.get(),
-                              g->d_ticket.get(), nvb, a, st));
+                              g->d_ticket.get(), nvb, a, st, table));
     g->last_step_launches += 1;
   } else {
     g->last_step_launches += 2;

@@ -400,6 +400,8 @@ struct sxmc_group {
     sxhost::DeviceBuffer<int> d_rb;             // [nmembers][K] (grow-only, like d_weight)
     sxhost::DeviceBuffer<unsigned> d_weight;    // [K]
     sxhost::DeviceBuffer<SxSignalDesc> d_descs; // member descriptors reading the class tables, no lookup-table output
+    SxStepEndTable table;                       // the same descriptors as the cooperative step end takes them by value,
+    bool has_table = false;                     // ... built with every upload of d_descs (up to 16 members)
     size_t K = 0;
     bool tables_valid = false, descs_valid = false;
     std::vector<unsigned long long> seen_points;

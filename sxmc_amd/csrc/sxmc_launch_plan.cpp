@@ -1160,6 +1160,9 @@ int ensure_event_classes(sxmc_group* g, bool sparse) {
   }
   if (!ec.d_descs) SX_BUF(ec.d_descs.alloc(std::max<size_t>(S, 1)));
   SX_HIP(hipMemcpy(ec.d_descs.get(), descs.data(), sizeof(SxSignalDesc) * S, hipMemcpyHostToDevice));
+  // (the by-value form of the same descriptors: a kernel argument, so a recorded step end holds the copy it was recorded
+  // with -- like the row count and the weights beside it; this function refuses to rebuild any of them under a recording)
+  ec.has_table = sx_step_end_table_fill(ec.table, descs.data(), S);
   ec.descs_valid = true;
   return SXMC_OK;
 }
