@@ -169,8 +169,8 @@ __device__ __forceinline__ double block_sum(size_t n, const double* sums, double
 //     loaded once, lane j forms signal j's expected-rate term and lane i parameter i's constraint term
 //     (the divisions), lane i draws its proposal deviate (lane 0 its uniform first: same consumption
 //     order of generator 0 as jump_decider followed by pick_new_vector), the partial sums are reduced;
-//   phase B (lane 0): the terms are added in the reference's order (so the value is the sequential
-//     loop's, bit for bit), accept or reject;
+//   phase B (every lane the same, from registers filled before the sums are waited for): the terms are added in
+//     the reference's order (so the value is the sequential loop's, bit for bit), accept or reject; lane 0 stores;
 //   phase C (all lanes): vector copy, jump-buffer append and next proposal, one parameter per lane.
 // Vectors longer than kStage fall back to the plain sequential form.
 constexpr int kStage = 256;
@@ -179,7 +179,11 @@ constexpr int kStage = 256;
 // `wait`: called by every thread of the workgroup, once, after everything that does not need the partial sums has
 // been loaded and computed (phase A) and before the sums are read -- the cooperative step end (step_end_kernel) waits
 // there for the workgroups that are still summing, so that phase A runs under their look-ups.
-template <int BD = 0, typename Wait>
+// R: how many of phase B's addends every lane holds in registers across the wait and the reduction (the rest is read from
+// LDS behind them): 32 -- 64 VGPRs -- in the kernels bounded at 128 lanes (the cooperative step ends) and at 256 (the
+// two-launch step ends: finish_zero_kernel, finish2_zero_kernel, finish_zero_chains_kernel, eval_nll_finish_kernel, 113-115
+// VGPRs in all), 8 in kernels bounded at 1024 lanes, which have 128 registers (BD > 0: the fused step; tail_step_kernel).
+template <int BD = 0, int R = (BD > 0 ? 8 : 32), typename Wait>
 __device__ __forceinline__ bool finish_step_device_w(size_t npartial_sums, const double* sums, size_t nsignals,
                                                      size_t nsources, const double* means, const double* sigmas,
                                                      sxmc_rng_state* rng, double* nll_current,
@@ -190,11 +194,12 @@ __device__ __forceinline__ bool finish_step_device_w(size_t npartial_sums, const
                                                      const short* source_id, const unsigned* norms,
                                                      bool debug_mode, Wait&& wait) {
   __shared__ double s_wave[17];
-  __shared__ double s_vprop[kStage], s_vcur[kStage], s_pen[kStage], s_z[kStage], s_term[kStage];
+  __shared__ double s_vprop[kStage], s_vcur[kStage], s_z[kStage];
+  __shared__ double s_add[2 * kStage];      // phase B's addends in its order: the signals' terms, then the constraints'
   __shared__ float s_jw[kStage];
-  __shared__ unsigned char s_flag[kStage];  // bit 0: constraint term present, bit 1: negative source rate
-  __shared__ int s_accept, s_count;
-  __shared__ double s_nllcur, s_u;
+  __shared__ unsigned s_badw[16];           // per wave: one of its parameters is a negative source rate
+  __shared__ int s_count, s_nacc;
+  __shared__ double s_nc, s_u;
 
   const unsigned bdim = BD > 0 ? (unsigned)BD : blockDim.x;
   const bool staged = nparameters <= kStage && nsignals <= (size_t)kStage;
@@ -209,34 +214,44 @@ __device__ __forceinline__ bool finish_step_device_w(size_t npartial_sums, const
     }
     __threadfence_block();
     __syncthreads();
-    pick_new_vector_device(nparameters, rng, jump_width, v_current, v_proposed);
+    // pick_new_vector over THIS workgroup's lanes (pick_new_vector_device strides over the grid: inside a launch of several
+    // workgroups -- every step end of a group -- the finisher's lanes are not the grid's first, and parameters were left
+    // without a proposal)
+    for (int i = threadIdx.x; i < nparameters; i += (int)bdim) {
+      if (jump_width[i] > 0) {  // fixed parameters carry width -1 (mcmc.cpp:204-207)
+        const double u = rng_normal(&rng[i]);
+        v_proposed[i] = v_current[i] + jump_width[i] * u;
+      } else {
+        v_proposed[i] = v_current[i];
+      }
+    }
     __syncthreads();
     return nll_current[0] == nll_proposed[0];   // (long vectors: accepted, or a tie, which changes nothing)
   }
 
   // ---- phase A
-  double nc = 0.0;
-  int count = 0;
   if (threadIdx.x == 0) {
-    nc = nll_current[0];
-    count = counter[0];
+    s_nc = nll_current[0];
+    s_count = counter[0];
+    s_nacc = accepted[0];   // (read here, so that the accept path only stores)
   }
+  double* const s_pen = s_add + nsignals;
+  bool negative_rate = false;
   for (int i = threadIdx.x; i < nparameters; i += (int)bdim) {
     const double p = v_proposed[i], mean = means[i], sigma = sigmas[i];
     const float jw = jump_width[i];
     s_vprop[i] = p;
     s_vcur[i] = v_current[i];
     s_jw[i] = jw;
-    unsigned char flag = 0;
-    double pen = 0.0;
+    // (a parameter without a constraint adds -0.0, which leaves every sum as it is, bit for bit: x + -0.0 == x for
+    //  every x, both zeros and NaN included)
+    double pen = -0.0;
     if (sigma > 0) {  // nll_kernels.cpp:181-184
       const double x = (p - mean) / sigma;
       pen = 0.5 * x * x;
-      flag |= 1;
     }
-    if ((size_t)i < nsources && p < 0) flag |= 2;  // :176-179
+    if ((size_t)i < nsources && p < 0) negative_rate = true;  // :176-179
     s_pen[i] = pen;
-    s_flag[i] = flag;
     if (i == 0 || jw > 0) {
       sxmc_rng_state st = rng[i];
       if (i == 0) s_u = rng_uniform(&st);            // jump_decider's draw (nll_kernels.cpp:63)
@@ -245,52 +260,69 @@ __device__ __forceinline__ bool finish_step_device_w(size_t npartial_sums, const
     }
   }
   for (int j = threadIdx.x; j < (int)nsignals; j += (int)bdim) {
-    s_term[j] = v_proposed[source_id[j]] * nexpected[j] * norms[j] / n_mc[j];  // :169-172
+    s_add[j] = v_proposed[source_id[j]] * nexpected[j] * norms[j] / n_mc[j];  // :169-172
   }
-  wait();
-  const double total_sum = block_sum<BD>(npartial_sums, sums, s_wave);  // barriers inside: LDS is visible after
-
-  // ---- phase B
-  if (threadIdx.x == 0) {
-    double sum = -total_sum;
-    bool bad = isnan(sum);
-    if (!bad) {
-      for (unsigned j = 0; j < nsignals; j++) sum += s_term[j];
-      for (int i = 0; i < nparameters; i++) {
-        if (s_flag[i] & 2) {
-          bad = true;
-          break;
-        }
-        if (s_flag[i] & 1) sum += s_pen[i];
-      }
-    }
-    const double np = bad ? 1e18 : sum;
-    nll_proposed[0] = np;
-    const bool accept = debug_mode || (np < nc || s_u <= exp(nc - np));  // Metropolis, :69-77
-    if (accept) {
-      nll_current[0] = np;
-      accepted[0] += 1;
-    }
-    counter[0] = count + 1;
-    s_accept = accept ? 1 : 0;
-    s_count = count;
-    s_nllcur = accept ? np : nc;
+  const int nwaves = ((int)bdim + kWave - 1) / kWave;
+  {
+    const unsigned long long any_negative = __ballot(negative_rate);
+    if ((threadIdx.x & (kWave - 1)) == 0) s_badw[threadIdx.x / kWave] = any_negative != 0ull ? 1u : 0u;
   }
   __syncthreads();
+  // Everything phase B adds is known now.  EVERY lane takes it into registers before the wait (the first kRegAdd addends,
+  // fetched together; all lanes read the same words), so that what follows the partial sums' reduction is a chain of
+  // additions, the exp and the stores: no LDS round trip per addend, and no broadcast of the decision with its barrier --
+  // each lane decides for itself, from the same values by the same operations, and lane 0 stores.
+  constexpr int kRegAdd = R;
+  static_assert(R > 0 && R % 8 == 0, "whole blocks of eight additions");
+  const int nadd = (int)nsignals + nparameters;
+  double add[kRegAdd];
+#pragma unroll
+  for (int k = 0; k < kRegAdd; k++) add[k] = s_add[min(k, max(nadd - 1, 0))];
+#pragma unroll
+  for (int k = 0; k < kRegAdd; k++) add[k] = k < nadd ? add[k] : -0.0;
+  bool bad = false;
+  for (int w = 0; w < nwaves; w++) bad = bad || s_badw[w] != 0u;
+  const double nc = s_nc, u = s_u;
+  const int count = s_count, nacc = s_nacc;
+  wait();
+  const double total_sum = block_sum<BD>(npartial_sums, sums, s_wave);  // barriers inside
+
+  // ---- phase B: the reference's sum, term by term in its order; 1e18 on a NaN event sum or a negative source rate
+  double sum = -total_sum;
+  bad = bad || isnan(sum);
+#pragma unroll
+  for (int k0 = 0; k0 < kRegAdd; k0 += 8) {
+    if (k0 < nadd) {
+#pragma unroll
+      for (int k = 0; k < 8; k++) sum += add[k0 + k];
+    }
+  }
+  for (int k = kRegAdd; k < nadd; k++) sum += s_add[k];
+  const double np = bad ? 1e18 : sum;
+  const bool accept = debug_mode || (np < nc || u <= exp(nc - np));  // Metropolis, :69-77
+  if (threadIdx.x == 0) {
+    nll_proposed[0] = np;
+    if (accept) {
+      nll_current[0] = np;
+      accepted[0] = nacc + 1;
+    }
+    counter[0] = count + 1;
+  }
 
   // ---- phase C
-  const bool accept = s_accept != 0;
-  const size_t row = (size_t)s_count * (size_t)(nparameters + 1);
+  const double nllcur = accept ? np : nc;
+  const size_t row = (size_t)count * (size_t)(nparameters + 1);
   for (int i = threadIdx.x; i < nparameters; i += (int)bdim) {
     const double cur = accept ? s_vprop[i] : s_vcur[i];
     if (accept) v_current[i] = cur;
     jump_buffer[row + i] = (float)cur;
     v_proposed[i] = (s_jw[i] > 0) ? cur + s_jw[i] * s_z[i] : cur;  // :40-47
   }
-  if (threadIdx.x == 0) jump_buffer[row + nparameters] = (float)s_nllcur;
+  if (threadIdx.x == 0) jump_buffer[row + nparameters] = (float)nllcur;
   return accept;
 }
 
+template <int R = 32>
 __device__ __forceinline__ bool finish_step_device(size_t npartial_sums, const double* sums, size_t nsignals,
                                                    size_t nsources, const double* means, const double* sigmas,
                                                    sxmc_rng_state* rng, double* nll_current,
@@ -300,7 +332,7 @@ __device__ __forceinline__ bool finish_step_device(size_t npartial_sums, const d
                                                    const double* nexpected, const unsigned* n_mc,
                                                    const short* source_id, const unsigned* norms,
                                                    bool debug_mode) {
-  return finish_step_device_w<0>(npartial_sums, sums, nsignals, nsources, means, sigmas, rng, nll_current, nll_proposed,
+  return finish_step_device_w<0, R>(npartial_sums, sums, nsignals, nsources, means, sigmas, rng, nll_current, nll_proposed,
                               v_current, v_proposed, accepted, counter, jump_buffer, nparameters, jump_width, nexpected,
                               n_mc, source_id, norms, debug_mode, [] {});
 }

@@ -562,7 +562,8 @@ __global__ __launch_bounds__(1024) void tail_step_kernel(const SxSignalDesc* __r
       eval_nll_block(descs, nsig, npoints, weight, a.v_proposed, a.nexpected, a.n_mc, a.source_id, a.norms, sh);
   if (threadIdx.x == 0) s_total = isnan(t) ? 0.0 : t;   // (nll_kernels.cpp:113-115: a NaN partial is not stored)
   __syncthreads();
-  sxdev::finish_step_device(1, &s_total, a.nsignals, a.nsources, a.means, a.sigmas, a.rng, a.nll_current,
+  // (a launch bound of 1024 lanes, 128 registers: few of phase B's addends in registers)
+  sxdev::finish_step_device<8>(1, &s_total, a.nsignals, a.nsources, a.means, a.sigmas, a.rng, a.nll_current,
                             a.nll_proposed, a.v_current, a.v_proposed, a.accepted, a.counter, a.jump_buffer,
                             a.nparameters, a.jump_width, a.nexpected, a.n_mc, a.source_id, a.norms,
                             a.debug_mode != 0);
@@ -657,6 +658,12 @@ __device__ __forceinline__ void step_end_role(unsigned role, unsigned W, const M
     // ---- the finisher (its phase A reads the normalisations: after the fill)
     ready();
     __shared__ double s_part[128];
+    // (the normalisations' addresses are fetched now, beside phase A's loads: the clearing stores below then wait for
+    //  nothing -- lane j's member j; a group of more members than lanes goes round again after the step)
+    unsigned* const my_norm = nsig > 0 ? hist_descs[min((int)threadIdx.x, nsig - 1)].norm : nullptr;
+    // (only the staged form has read the normalisations by the time it waits: vectors longer than kStage total the NLL
+    //  from them BEHIND the wait, nll_total_device, and are cleared behind the step as before)
+    const bool clear_in_wait = a.nparameters <= sxdev::kStage && a.nsignals <= (size_t)sxdev::kStage;
     sxdev::finish_step_device_w<BD>(nvb, s_part, a.nsignals, a.nsources, a.means, a.sigmas, a.rng, a.nll_current,
                                     a.nll_proposed, a.v_current, a.v_proposed, a.accepted, a.counter, a.jump_buffer,
                                     a.nparameters, a.jump_width, a.nexpected, a.n_mc, a.source_id, a.norms,
@@ -689,6 +696,10 @@ __device__ __forceinline__ void step_end_role(unsigned role, unsigned W, const M
                                       if (i < nvb) {
                                         __hip_atomic_store(slots + i, kSlotEmpty, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
                                       }
+                                      // ... and nothing reads the normalisations any more either (the workers did while
+                                      // staging, this workgroup in phase A, before the barrier above): cleared here, out
+                                      // of the way of phases B and C, not behind them
+                                      if (clear_in_wait && (int)i < nsig) *my_norm = 0u;
                                     });
     __syncthreads();
 #if SXMC_MEASURE
@@ -699,7 +710,8 @@ __device__ __forceinline__ void step_end_role(unsigned role, unsigned W, const M
       __hip_atomic_store(a.gate, a.gate_value, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     }
 #endif
-    for (int j = threadIdx.x; j < nsig; j += (int)bdim) *hist_descs[j].norm = 0u;
+    if (!clear_in_wait && (int)threadIdx.x < nsig) *my_norm = 0u;
+    for (int j = (int)(threadIdx.x + bdim); j < nsig; j += (int)bdim) *hist_descs[j].norm = 0u;
     if (threadIdx.x == 0) sync[0] = 0u;   // (the ticket of the other step-end forms: as finish_zero_kernel leaves it)
     if (BD == 0) SX_WG_STAMP(2);
     return;
@@ -712,6 +724,22 @@ __device__ __forceinline__ void step_end_role(unsigned role, unsigned W, const M
   if (threadIdx.x == 0) {
     __hip_atomic_store(slots + vb, isnan(t) ? kSlotNaN : (unsigned long long)__double_as_longlong(t), __ATOMIC_RELAXED,
                        __HIP_MEMORY_SCOPE_AGENT);
+  }
+  // What the clearing needs of the histograms' descriptors -- address and bin count per member -- is fetched BEFORE the
+  // wait for the finisher's signal (behind the slot's store, which is on its way) and parked in LDS (over the staged member
+  // records, which nothing reads any more: every lane is past the event sum's last barrier), so that the clearing stores
+  // issue the moment the slot reads empty, not two scalar loads and a wait per piece later.
+  struct HistRange {
+    unsigned* bins;
+    unsigned n, pad;
+  };
+  static_assert(sizeof(HistRange) <= sizeof(EvalMember), "parked over the member records");
+  HistRange* const s_hist = reinterpret_cast<HistRange*>(sh + 16);
+  for (int j = threadIdx.x; j < nsig; j += (int)bdim) {
+    s_hist[j].bins = hist_descs[j].bins;
+    s_hist[j].n = (unsigned)hist_descs[j].total_nbins;
+  }
+  if (threadIdx.x == 0) {
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");   // (the store has landed before this lane starts reading the slot)
     if (BD == 0) SX_WG_STAMP(2);                       // (measurement build: the worker's slot is stored)
     // the histograms may be cleared once the finisher has every worker's partial: it then empties the slots
@@ -727,10 +755,10 @@ __device__ __forceinline__ void step_end_role(unsigned role, unsigned W, const M
   if (!s_clear) return;
   const unsigned npieces = zblocks * (unsigned)nsig;
   for (unsigned p = role; p < npieces; p += W) {
-    const SxSignalDesc& d = hist_descs[p / zblocks];
+    const HistRange d = s_hist[p / zblocks];
     const unsigned chunk = p % zblocks;
     unsigned* bins = d.bins;
-    const unsigned n = (unsigned)d.total_nbins;
+    const unsigned n = d.n;
     const unsigned n4 = n >> 2;
     uint4* b4 = reinterpret_cast<uint4*>(bins);
     const unsigned stride = zblocks * bdim;
