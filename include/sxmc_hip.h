@@ -343,6 +343,22 @@ int sxmc_kde_set_parameter_buffer(sxmc_kde_t k, const double* d_params, int offs
 int sxmc_kde_eval_async(sxmc_kde_t k, int do_eval_pdf);
 int sxmc_kde_eval_finished(sxmc_kde_t k);
 int sxmc_kde_get_stream(sxmc_kde_t k, sxmc_stream_t* s);
+/* What sxmc_kde_eval_async launches -- norm clear, prepass, pair sum, combine: the same kernels, the same split over
+ * workgroups, the same bits -- on the CALLER's stream `s`, for a walk that keeps its whole step on one stream (a mixed
+ * fit: sxmc_group_eval_columns_nll_async).  Capture-safe: no allocation, no blocking copy, no wait, so it may be recorded
+ * into a graph (sxmc_graph_begin_capture on `s`).  The evaluator remembers `s`: set_eval_points, random_sample,
+ * sample_pool, project, eval_async, eval_finished and destroy wait for the last work given to it before they touch the
+ * evaluator's own stream (a host wait, once; SXMC_ERR_STATE while a graph is being recorded), and this entry waits for
+ * work on the evaluator's own stream that no eval_finished has waited for (outside a recording; inside one that is
+ * SXMC_ERR_STATE: call eval_finished first). */
+int sxmc_kde_eval_on_stream_async(sxmc_kde_t k, int do_eval_pdf, sxmc_stream_t s);
+/* The parameter indices the attached systematics read, in the order attached: the `pars` of add_systematic, before the
+ * parameter buffer's offset and stride.  *n: how many there are; pars[0 .. min(cap, *n)) is written.  A walk re-evaluates
+ * a kernel-density signal only when one of them floats. */
+int sxmc_kde_parameters_read(sxmc_kde_t k, short* pars, size_t cap, size_t* n);
+/* Evaluations launched so far, by eval_async or eval_on_stream_async (launches recorded into a graph count when they are
+ * recorded, not when the graph is replayed).  For tests and reports, like sxmc_deferred_eval_stats. */
+int sxmc_kde_evaluation_count(sxmc_kde_t k, unsigned long long* n);
 /* h[0 .. nobservables): the bandwidths fixed at creation. */
 int sxmc_kde_bandwidths(sxmc_kde_t k, double* h, size_t n);
 int sxmc_kde_nsamples(sxmc_kde_t k, size_t* nsamples);
@@ -571,6 +587,49 @@ int sxmc_group_finish_step_async(sxmc_group_t g, sxmc_stream_t s, size_t npartia
                                  int nparameters, size_t nsources, const float* d_jump_width,
                                  const double* d_nexpected, const unsigned* d_n_mc, const short* d_source_id,
                                  const unsigned* d_norms, int debug_mode);
+/* MIXED FITS: a walk whose lookup table has columns the group does not write -- kernel-density signals
+ * (sxmc_kde_eval_on_stream_async) beside the histogram members.  sxmc_group_set_columns describes the walk's `nsignals`
+ * columns in signal order, a host array: member_of_signal[j] >= 0 is that member of `g`, looked up from its histogram;
+ * -1 is a dense column somebody else writes.  Every member must appear exactly once; anything else (a null argument,
+ * nsignals < 1, an index below -1 or beyond the members, a member twice or not at all) is SXMC_ERR_INVALID.  The table
+ * is uploaded here, once (waits for the group's last stream; not while a graph is recorded): the two step entries below
+ * neither copy nor allocate. */
+int sxmc_group_set_columns(sxmc_group_t g, int nsignals, const int* member_of_signal);
+/* The group's zero and fill exactly as sxmc_group_eval_async(g, 1, s) does them (boxed, ordered, codes, the event-bin
+ * counters of histograms beyond LDS, the zero launch skipped after a clearing step end), then nll_event_chunks
+ * (nll_kernels.cpp:89-116) over the mixed table with the histogram columns looked up IN PLACE (columns_kernels.hip):
+ * d_sums[0 .. grid * block) receives, bit for bit, what sxmc_launch_nll_event_chunks(grid, block, ...) gives over the
+ * fully materialised table -- lane t sums events t, t + grid * block, ... in index order, the terms of an event in
+ * signal order, a histogram column's value being eval_pdf's (pdfz.cpp:423-434) from the descriptors
+ * sxmc_group_eval_async's lookup would be given, so sparse plans look up what they count.  Dense column j is
+ * d_lut[j * nevents + i], valid on `s` when the kernel runs; the histogram members' columns of d_lut are NOT written
+ * (d_lut may be null when there is no dense column).  d_norms: the walk's normalisation array in signal order (a
+ * member's own slot is read for its bin norm).  Requires sxmc_group_set_columns, members that share one set of points
+ * of `nevents` rows, 1 <= block <= 256, at most 1024 columns.  Capture-safe once the group has evaluated.
+ * MEASURED SLOWER than materialising (sxmc_group_eval_async(g, 1, s) + sxmc_launch_nll_event_chunks) where the event
+ * sum is large: the look-ups, a double division each, sit on the event sum's `grid` workgroups -- 64 in a walk --
+ * instead of the whole device.  tests/cpp/mixed_walk --bench, 20 000 steps, twice, on two cards: 8 histogram signals of
+ * 4e6 samples + 2 kernel-density signals, 4.75e4 events, graph replays of 100 steps: 6 240 / 6 237 steps/s in place
+ * against 6 312 / 6 259 materialised (-0.8 %), and 6 387 / 6 390 against 6 477 / 6 482 (-1.4 %, the repeats agreeing
+ * to 0.1 %); 1 histogram + 2 kernel-density signals, 874 events (one event to a lane, one launch less): 25 580 / 25 720
+ * against 24 620 / 24 620, and 25 210 / 25 060 against 24 190 / 24 150 (+4 %).  So sxmc::MCMC materialises by default
+ * and takes this entry on request (MCMC::columns_in_place). */
+int sxmc_group_eval_columns_nll_async(sxmc_group_t g, sxmc_stream_t s, const float* d_lut, size_t nevents,
+                                      const double* d_pars, const double* d_nexpected, const unsigned* d_n_mc,
+                                      const short* d_source_id, const unsigned* d_norms, double* d_sums, int grid,
+                                      int block);
+/* sxmc_group_finish_step_async for a mixed fit (same arguments): the step end -- finish_nll_jump_pick_combo, nll_total
+ * over all signals -- runs over the `nsignals` columns of sxmc_group_set_columns, not over the members; the clearing
+ * covers the group's histograms and its MEMBERS' normalisation slots only: the slots of dense columns are left as they
+ * are (a kernel-density signal no floating parameter touches keeps the norm of its last evaluation).  Follows
+ * sxmc_group_eval_columns_nll_async, or sxmc_group_eval_async + sxmc_launch_nll_event_chunks, on the same stream. */
+int sxmc_group_finish_columns_step_async(sxmc_group_t g, sxmc_stream_t s, size_t npartial_sums, const double* d_sums,
+                                         const double* d_means, const double* d_sigmas, sxmc_rng_state* d_rng,
+                                         double* d_nll_current, double* d_nll_proposed, double* d_v_current,
+                                         double* d_v_proposed, int* d_accepted, int* d_counter, float* d_jump_buffer,
+                                         int nparameters, size_t nsources, const float* d_jump_width,
+                                         const double* d_nexpected, const unsigned* d_n_mc, const short* d_source_id,
+                                         const unsigned* d_norms, int debug_mode);
 /* One whole MCMC step (mcmc.cpp:264-271 + 314-348) for a walk that reads neither histograms, normalisations nor
  * the lookup table between steps: the fill of all members, then lookup + nll_event_chunks (nll_kernels.cpp:89-116)
  * + nll_event_reduce + nll_total + finish_nll_jump_pick_combo (:230-271) + the clearing the next evaluation

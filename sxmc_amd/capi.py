@@ -118,6 +118,9 @@ SIGNATURES = {
     "sxmc_kde_set_parameter_buffer": [_vp, _vp, _i, _i],
     "sxmc_kde_eval_async": [_vp, _i],
     "sxmc_kde_eval_finished": [_vp],
+    "sxmc_kde_eval_on_stream_async": [_vp, _i, _vp],
+    "sxmc_kde_parameters_read": [_vp, _vp, _sz, _psz],
+    "sxmc_kde_evaluation_count": [_vp, C.POINTER(C.c_ulonglong)],
     "sxmc_kde_get_stream": [_vp, _pvp],
     "sxmc_kde_bandwidths": [_vp, _vp, _sz],
     "sxmc_kde_nsamples": [_vp, _psz],
@@ -170,6 +173,10 @@ SIGNATURES = {
     "sxmc_group_lookahead_supported": [_vp, _pi],
     "sxmc_group_finish_step_async": [_vp, _vp, _sz, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _sz,
                                      _vp, _vp, _vp, _vp, _vp, _i],
+    "sxmc_group_set_columns": [_vp, _i, _vp],
+    "sxmc_group_eval_columns_nll_async": [_vp, _vp, _vp, _sz, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i],
+    "sxmc_group_finish_columns_step_async": [_vp, _vp, _sz, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i,
+                                             _sz, _vp, _vp, _vp, _vp, _vp, _i],
     "sxmc_group_synchronize": [_vp],
     "sxmc_group_profile": [_vp, _i, _i],
     "sxmc_group_profile_read": [_vp, _pd, _pi],

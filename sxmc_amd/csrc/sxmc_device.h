@@ -220,6 +220,12 @@ hipError_t sx_launch_eval_nll(const SxSignalDesc* d_descs, int nsig, unsigned lo
                               const unsigned* weight, const double* pars, const double* nexpected, const unsigned* n_mc,
                               const short* source_id, const unsigned* norms, double* sums,
                               int grid, int block, hipStream_t s);
+// The event sum over a mixed table (columns_kernels.hip): d_member_of[j] >= 0: column j is looked up from that member of
+// d_descs; -1: column j of lut (ne floats at lut + j * ne).  block <= 256.  Writes sums[0 .. grid * block).
+hipError_t sx_launch_nll_columns(const SxSignalDesc* d_descs, const int* d_member_of, int nsignals, const float* lut,
+                                 unsigned long long ne, const double* pars, const double* nexpected,
+                                 const unsigned* n_mc, const short* source_id, const unsigned* norms, double* sums,
+                                 int grid, int block, hipStream_t s);
 hipError_t sx_launch_pow_int(const double* x, int n, int i, double* out, hipStream_t s);
 hipError_t sx_launch_transpose(const float* aos, float* cols, unsigned long long nsamples,
                                int nfields, unsigned long long col_pitch, hipStream_t s);

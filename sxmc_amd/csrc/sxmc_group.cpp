@@ -590,6 +590,104 @@ int sxmc_group_finish_step_async(sxmc_group_t g, sxmc_stream_t s, size_t npartia
   return SXMC_OK;
 }
 
+// ------------------------------------------------------------------------------ mixed fits
+int sxmc_group_set_columns(sxmc_group_t g, int nsignals, const int* member_of_signal) {
+  SX_REQUIRE(g, "null group");
+  if (const char* why = sxplan::columns_error((int)g->members.size(), nsignals, member_of_signal)) {
+    return fail(SXMC_ERR_INVALID, why);
+  }
+  SX_REQUIRE(!t_capturing, "not while recording a graph");
+  SX_FLUSH();
+  if (g->built) SX_HIP(hipStreamSynchronize(g->last_stream));   // (a step in flight reads the table replaced here)
+  if ((size_t)nsignals > g->d_col_member.capacity()) SX_BUF(g->d_col_member.grow((size_t)nsignals));
+  SX_HIP(hipMemcpy(g->d_col_member.get(), member_of_signal, sizeof(int) * (size_t)nsignals, hipMemcpyHostToDevice));
+  g->col_member.assign(member_of_signal, member_of_signal + nsignals);
+  return SXMC_OK;
+}
+
+int sxmc_group_eval_columns_nll_async(sxmc_group_t g, sxmc_stream_t s, const float* d_lut, size_t nevents,
+                                      const double* d_pars, const double* d_nexpected, const unsigned* d_n_mc,
+                                      const short* d_source_id, const unsigned* d_norms, double* d_sums, int grid,
+                                      int block) {
+  SX_REQUIRE(g, "null group");
+  SX_FLUSH();
+  SX_ORDER(s);
+  SX_REQUIRE(d_pars && d_nexpected && d_n_mc && d_source_id && d_norms && d_sums, "null argument");
+  SX_REQUIRE(grid >= 1 && grid <= 65535 && block >= 1 && block <= 256, "grid must be 1 .. 65535, block 1 .. 256");
+  if (g->col_member.empty()) return fail(SXMC_ERR_STATE, "eval_columns_nll before sxmc_group_set_columns");
+  SX_REQUIRE(d_lut || g->col_member.size() == g->members.size(), "null lookup table with dense columns");
+  SX_REQUIRE(g->col_member.size() <= 1024, "too many columns for the mixed event sum");
+  int rc = group_refresh(g);
+  if (rc) return rc;
+  rc = group_check_bound(g, false);
+  if (rc) return rc;
+  if (!g->members.empty()) {
+    if (!g->same_points) return fail(SXMC_ERR_STATE, "members do not share one set of evaluation points");
+    SX_REQUIRE(g->members[0]->npoints == nevents, "nevents is not the members' number of evaluation points");
+  }
+  hipStream_t st = (hipStream_t)s;
+  g->last_stream = st;
+  // (as sxmc_group_eval_async(g, 1, s): histograms beyond LDS capacity count just the event bins, and the look-ups
+  // below go through the descriptors that evaluation's sx_launch_eval_pdf would be given)
+  const bool sparse = g->sparse_ready && g->cfg_sparse;
+  rc = group_fill(g, st, sparse);
+  if (rc) return rc;
+  SX_HIP(sx_launch_nll_columns(sparse ? g->d_descs_sparse.get() : g->d_descs.get(), g->d_col_member.get(),
+                               (int)g->col_member.size(), d_lut, nevents, d_pars, d_nexpected, d_n_mc, d_source_id,
+                               d_norms, d_sums, grid, block, st));
+  return SXMC_OK;
+}
+
+int sxmc_group_finish_columns_step_async(sxmc_group_t g, sxmc_stream_t s, size_t npartial_sums, const double* d_sums,
+                                         const double* d_means, const double* d_sigmas, sxmc_rng_state* d_rng,
+                                         double* d_nll_current, double* d_nll_proposed, double* d_v_current,
+                                         double* d_v_proposed, int* d_accepted, int* d_counter, float* d_jump_buffer,
+                                         int nparameters, size_t nsources, const float* d_jump_width,
+                                         const double* d_nexpected, const unsigned* d_n_mc, const short* d_source_id,
+                                         const unsigned* d_norms, int debug_mode) {
+  SX_REQUIRE(g, "null group");
+  SX_FLUSH();
+  SX_ORDER(s);
+  SX_REQUIRE(d_sums && d_means && d_sigmas && d_rng && d_nll_current && d_nll_proposed && d_v_current &&
+                 d_v_proposed && d_accepted && d_counter && d_jump_buffer && d_jump_width && d_nexpected &&
+                 d_n_mc && d_source_id && d_norms,
+             "null argument");
+  SX_REQUIRE(nparameters > 0, "nparameters must be positive");
+  if (g->col_member.empty()) return fail(SXMC_ERR_STATE, "finish_columns_step before sxmc_group_set_columns");
+  if (!g->built) return fail(SXMC_ERR_STATE, "finish_columns_step before any evaluation of the group");
+  SxStepArgs a;
+  a.nsignals = g->col_member.size();   // (the step end runs over every column; the clearing below over the members)
+  a.nsources = nsources;
+  a.means = d_means;
+  a.sigmas = d_sigmas;
+  a.rng = d_rng;
+  a.nll_current = d_nll_current;
+  a.nll_proposed = d_nll_proposed;
+  a.v_current = d_v_current;
+  a.v_proposed = d_v_proposed;
+  a.accepted = d_accepted;
+  a.counter = d_counter;
+  a.jump_buffer = d_jump_buffer;
+  a.nparameters = nparameters;
+  a.debug_mode = debug_mode;
+  a.jump_width = d_jump_width;
+  a.nexpected = d_nexpected;
+  a.n_mc = d_n_mc;
+  a.source_id = d_source_id;
+  a.norms = d_norms;
+  const bool sparse = g->last_sparse;
+  SX_HIP(sx_launch_finish_zero(sparse ? g->d_descs_sparse.get() : g->d_descs.get(), (int)g->members.size(),
+                               sparse ? g->max_bins_sparse : g->max_bins, npartial_sums, d_sums, g->d_ticket.get(), a, 128,
+                               (hipStream_t)s));
+  g->last_stream = (hipStream_t)s;
+  g->prezeroed = sparse ? 2 : 1;
+  for (sxmc_hist* h : g->members) {
+    h->bins_valid = false;
+    h->cleared_by = g;
+  }
+  return SXMC_OK;
+}
+
 }  // extern "C" (helpers below are internal)
 
 namespace sxhost {

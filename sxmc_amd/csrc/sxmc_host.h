@@ -10,6 +10,7 @@
 //   sxmc_multigroup.cpp   lockstep chains and the look-ahead pass
 //   sxmc_nll_api.cpp      the NLL launch points with the reference's argument lists; the measurement build's test hooks
 //   sxmc_kde.cpp          the kernel-density evaluator (sxmc_kde_*) behind pdfz::EvalKernel
+// (the kernels: pdfz_kernels.hip, nll_kernels.hip, kde_kernels.hip, columns_kernels.hip, layout_kernels.hip, project_kernels.hip)
 // Every allocation these hold is owned by a buffer (device_buffer.h over the policies below); layout_kernels.hip's host
 // helpers take their temporaries from the same type.
 #pragma once
@@ -409,6 +410,10 @@ struct sxmc_group {
   EventClasses ec[2];               // [0] dense, [1] sparse flavour
   std::vector<SxSignalDesc> h_descs_sparse;
   int cfg_lut = 1;
+  // sxmc_group_set_columns: the lookup table of a mixed fit in signal order, per column the member looked up in place or
+  // -1 for a dense column somebody else writes; uploaded there, once (the step entries neither copy nor allocate)
+  std::vector<int> col_member;
+  sxhost::DeviceBuffer<int> d_col_member;
   // sxmc_group_finish_step_async zeroes histograms and normalisations for the next evaluation: that
   // evaluation then skips its zero kernel.  0 = nothing pre-zeroed, 1 = dense flavour, 2 = sparse flavour.
   int prezeroed = 0;

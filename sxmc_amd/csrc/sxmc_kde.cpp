@@ -47,6 +47,14 @@ struct sxmc_kde {
   const double* params = nullptr;
   int par_off = 0, par_stride = 1;
   int cus = 256;
+  // streams: the evaluator's own (h->stream) carries everything but sxmc_kde_eval_on_stream_async, which launches on the
+  // caller's.  ext_stream: the caller's stream of the last such launch while nothing has waited for it; own_pending:
+  // work has gone to the own stream since it was last waited for.  Whoever takes the other stream next waits first
+  // (order_after_caller / sxmc_kde_eval_on_stream_async).
+  hipStream_t ext_stream = nullptr;
+  bool ext_pending = false;
+  bool own_pending = false;
+  unsigned long long evaluations = 0;   // launched so far, by either entry (sxmc_kde_evaluation_count)
   // sampling (sxmc_kde_random_sample): the rows hold an evaluation once one has been launched
   bool evaluated = false;
   DeviceBuffer<unsigned> d_flag;   // [npad] in-domain flags, then [npad] their inclusive prefix sum, then [npad] the
@@ -81,6 +89,21 @@ void choose_split(size_t pitch, size_t ntiles, int cus, int& nsplit, unsigned& t
       tiles_per_split = (unsigned)tps;
     }
   }
+}
+
+// Everything but sxmc_kde_eval_on_stream_async works on the evaluator's own stream: after the last work that entry gave
+// to its caller's stream.  (A host wait: these are set-up and read-out calls; not while a graph is recorded.)
+int order_after_caller(sxmc_kde* k) {
+  if (!k->ext_pending) return SXMC_OK;
+  if (t_capturing) return fail(SXMC_ERR_STATE, "EvalKernel: not while recording a graph");
+  // (a caller that destroyed its stream without an eval_finished in between: the runtime refuses the handle, and the
+  // device-wide wait covers whatever that stream still carried)
+  if (hipStreamSynchronize(k->ext_stream) != hipSuccess) {
+    (void)hipGetLastError();
+    SX_HIP(hipDeviceSynchronize());
+  }
+  k->ext_pending = false;
+  return SXMC_OK;
 }
 
 // The cleared sample rows of a new evaluator that has its table (k->h) and npad.
@@ -283,6 +306,7 @@ int sxmc_kde_create_shared(sxmc_kde_t base, sxmc_kde_t* out) {
 
 int sxmc_kde_destroy(sxmc_kde_t k) {
   if (!k) return SXMC_OK;
+  (void)order_after_caller(k);
   if (k->h && k->h->stream) (void)hipStreamSynchronize(k->h->stream);
   delete k;   // (the table's evaluator, then the buffers)
   return SXMC_OK;
@@ -334,6 +358,7 @@ int sxmc_kde_set_eval_points(sxmc_kde_t k, const float* points, size_t npoints_f
   int nsplit = 1;
   unsigned tps = 1;
   choose_split(pitch, k->npad / SXMC_KDE_TILE, k->cus, nsplit, tps);
+  if (int rc_ = order_after_caller(k)) return rc_;
   SX_HIP(hipStreamSynchronize(k->h->stream));   // (an evaluation in flight reads the arrays replaced here)
   k->has_points = false;   // (until the new ones are in place: a failure below leaves an evaluator without points)
   if (pitch > k->d_codes.capacity()) {   // (the two grow together, both freed first; d_codes, allocated last, says whether both are there)
@@ -374,13 +399,17 @@ int sxmc_kde_set_parameter_buffer(sxmc_kde_t k, const double* d_params, int offs
   return SXMC_OK;
 }
 
-int sxmc_kde_eval_async(sxmc_kde_t k, int do_eval_pdf) {
-  SX_REQUIRE(k, "null evaluator");
+}  // extern "C"
+
+namespace {
+
+// An evaluation's launches on stream s: norm clear, prepass, and for a lookup the pair sum and the combine.  No
+// allocation, no blocking copy, no wait: what a recording tolerates.
+int kde_launch(sxmc_kde* k, int do_eval_pdf, hipStream_t s) {
   if (!k->norm) return fail(SXMC_ERR_STATE, "evaluation before SetNormalizationBuffer");
   if (!k->h->systs.empty() && !k->params) return fail(SXMC_ERR_STATE, "evaluation before SetParameterBuffer");
   const bool lookup = do_eval_pdf && k->has_points && k->npoints > 0;
   if (lookup && !k->pdf) return fail(SXMC_ERR_STATE, "evaluation before SetPDFValueBuffer");
-  const hipStream_t s = k->h->stream;
   SxSignalDesc d;
   fill_desc(k->h, d);
   d.params = k->params ? k->params + k->par_off : nullptr;
@@ -411,12 +440,71 @@ int sxmc_kde_eval_async(sxmc_kde_t k, int do_eval_pdf) {
                           k->pdf + k->pdf_off, (long)k->pdf_stride, s));
   }
   k->evaluated = true;
+  k->evaluations++;
+  return SXMC_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int sxmc_kde_eval_async(sxmc_kde_t k, int do_eval_pdf) {
+  SX_REQUIRE(k, "null evaluator");
+  int rc = order_after_caller(k);
+  if (rc) return rc;
+  k->own_pending = true;
+  return kde_launch(k, do_eval_pdf, k->h->stream);
+}
+
+int sxmc_kde_eval_on_stream_async(sxmc_kde_t k, int do_eval_pdf, sxmc_stream_t s) {
+  SX_REQUIRE(k, "null evaluator");
+  const hipStream_t st = (hipStream_t)s;
+  if (k->own_pending && st != k->h->stream) {
+    // (work on the evaluator's own stream that nothing has waited for: it reads and writes what this launch does)
+    if (t_capturing) return fail(SXMC_ERR_STATE, "EvalKernel: EvalFinished before recording evaluations on another stream");
+    SX_HIP(hipStreamSynchronize(k->h->stream));
+    k->own_pending = false;
+  }
+  if (k->ext_pending && k->ext_stream != st) {
+    int rc = order_after_caller(k);
+    if (rc) return rc;
+  }
+  int rc = kde_launch(k, do_eval_pdf, st);
+  if (rc) return rc;
+  if (st != k->h->stream) {
+    k->ext_stream = st;
+    k->ext_pending = true;
+  } else {
+    k->own_pending = true;
+  }
   return SXMC_OK;
 }
 
 int sxmc_kde_eval_finished(sxmc_kde_t k) {
   SX_REQUIRE(k, "null evaluator");
+  int rc = order_after_caller(k);
+  if (rc) return rc;
   SX_HIP(hipStreamSynchronize(k->h->stream));
+  k->own_pending = false;
+  return SXMC_OK;
+}
+
+int sxmc_kde_parameters_read(sxmc_kde_t k, short* pars, size_t cap, size_t* n) {
+  SX_REQUIRE(k && n && (pars || cap == 0), "null argument");
+  size_t count = 0;
+  for (const HostSyst& s : k->h->systs) {
+    for (short p : s.pars) {
+      if (count < cap) pars[count] = p;
+      count++;
+    }
+  }
+  *n = count;
+  return SXMC_OK;
+}
+
+int sxmc_kde_evaluation_count(sxmc_kde_t k, unsigned long long* n) {
+  SX_REQUIRE(k && n, "null argument");
+  *n = k->evaluations;
   return SXMC_OK;
 }
 
@@ -464,6 +552,7 @@ int kde_compact(sxmc_kde_t k, unsigned& n) {
     return fail(SXMC_ERR_STATE, "EvalKernel: nothing to draw from before an evaluation (EvalAsync first)");
   }
   SX_REQUIRE(k->npad <= 0x7FFFFFFFull, "EvalKernel: too many samples to draw from");
+  if (int rc_ = order_after_caller(k)) return rc_;
   const hipStream_t s = k->h->stream;
   if (!k->d_flag.get()) {
     SX_HIP(hipStreamSynchronize(s));   // (allocation next to queued work: settle it first)
@@ -564,6 +653,7 @@ int sxmc_kde_project(sxmc_kde_t k, int obs, int nbins, double* h_prob) {
   a.h = k->bw[obs];
   a.cunit = kLog2eHalfSqrt;
   a.lambda = k->d_lambda.get();
+  if (int rc_ = order_after_caller(k)) return rc_;
   const hipStream_t s = k->h->stream;
   // [2 npad] per-row scratch ([3 npad] when adaptive), [nsplit][pitch] partials, [nbins] result, the count
   const size_t off_prob = (k->d_lambda ? 3 : 2) * k->npad + (size_t)a.nsplit * a.pitch;

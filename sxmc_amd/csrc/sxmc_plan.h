@@ -10,6 +10,7 @@
 //   bucket_granules / bucket_key_offsets / bucketed_layout   bucketed copies of a sample table (layout_kernels.hip)
 //   bucket_tables          per-bucket event-bin tables of fill_sparse_kernel
 //   event_classes          distinct tuples of event bins, weighted by multiplicity (eval_nll_kernel)
+//   columns_error          the column table of a mixed fit (sxmc_group_set_columns)
 //   code_windows / ordered_lds_layout / padded_rstride_of   codes and LDS of the ordered and boxed fills
 //   syst_use / choose_ordered / choose_boxed / compact_slots / prebin_columns   the form a member's table takes
 #pragma once
@@ -440,6 +441,23 @@ inline void event_classes(const std::vector<const std::vector<int>*>& arr, size_
   o.tables.assign(std::max<size_t>(S * o.K, 1), 0);
   for (size_t j = 0; j < S; j++)
     for (size_t k = 0; k < o.K; k++) o.tables[j * o.K + k] = (*arr[j])[o.first[k]];
+}
+
+// ---------------------------------------------------------------------------------------------- mixed columns
+// sxmc_group_set_columns: the walk's columns in signal order, member_of_signal[j] >= 0 a member of the group, -1 a dense
+// column somebody else writes.  Valid: nothing below -1 or beyond the last member, every member exactly once.  Returns
+// null, or what is wrong.
+inline const char* columns_error(int nmembers, int nsignals, const int* member_of_signal) {
+  if (nmembers < 0 || nsignals < 1 || !member_of_signal) return "set_columns: no columns";
+  std::vector<int> seen((size_t)nmembers, 0);
+  for (int j = 0; j < nsignals; j++) {
+    const int m = member_of_signal[j];
+    if (m < -1 || m >= nmembers) return "set_columns: a column names no member of the group";
+    if (m >= 0 && seen[(size_t)m]++) return "set_columns: a member appears in two columns";
+  }
+  for (int m = 0; m < nmembers; m++)
+    if (!seen[(size_t)m]) return "set_columns: a member appears in no column";
+  return nullptr;
 }
 
 // CODES (fill_ordered_body): the window [base, base + 65532 step] of every streamed field of an ordered table, from the

@@ -11,6 +11,11 @@
 // nll_event_chunks, finish_nll_jump_pick_combo); both forms give the same numbers up to the
 // summation order of the event partial sums.
 //
+// A fit with kernel-density signals (pdfz::EvalKernel) among its histograms walks the MIXED form: the kernel members
+// that read a floating parameter are evaluated on the walk's own stream, the histogram members form the group, the event
+// sum runs over both kinds of column, and the step end clears the group only (Walk::mixed_step) -- no host wait between
+// steps, recordable, and the per-evaluator chain bit for bit.
+//
 // The walk's SCHEDULE -- which steps end a run of steps, where the widths are re-tuned, how a run splits into graph
 // replays and a remainder, how many passes a round of the look-ahead walk launches,
 // which form the steps take (choose_form) -- is walk_plan.h: pure functions, tested without a device.  The walk and
@@ -326,6 +331,13 @@ class MCMC {
   std::function<void()> on_setup_done, on_steps_done;
   bool lut_output = false;      //!< materialise the lookup table in the batched step (nothing reads it; when
                                 //!< false the event sum runs over distinct event-bin tuples, see sxmc_hip.h)
+  bool columns_in_place = false;  //!< MIXED form: sum the events with the histogram columns looked up in place
+                                  //!< (sxmc_group_eval_columns_nll_async: one launch less, the members' columns of the
+                                  //!< table not written) instead of materialising them.  Same chain bit for bit.  Off
+                                  //!< by default: measured 0.8-1.4 % SLOWER per step at 8 histogram signals x
+                                  //!< 4.75e4 events (its look-ups and divisions sit on the event sum's 64
+                                  //!< workgroups), 4 % faster at 1 x 874 (README, "Mixed walks"); ignored with
+                                  //!< lut_output
   unsigned long long seed = 0;  //!< gRandom->GetSeed() in the reference (mcmc.cpp:125)
 
   MCMC(const std::vector<Source>& sources, const std::vector<Signal>& signals,
@@ -387,17 +399,32 @@ class MCMC {
     const int nb = (int)(nparameters / bs + 1);
     SXMC_KERNEL_LAUNCH(init_device_rngs, nb, bs, 0, stream, (int)nparameters, seed, rngs->writeOnlyPtr());
 
-    // the batched form needs every evaluator to be a histogram evaluator of this library
+    // the batched forms need every evaluator to be a histogram evaluator of this library; with kernel-density
+    // evaluators of this library among them the walk is MIXED: the histogram members form the group (none: no group),
+    // which is told where its members' columns sit among the signals'
     std::vector<sxmc_hist_t> handles;
+    std::vector<int> member_of_signal;
     for (pdfz::Eval* p : pdfs) {
       pdfz::EvalHist* h = dynamic_cast<pdfz::EvalHist*>(p);
-      if (!h) {
+      pdfz::EvalKernel* k = dynamic_cast<pdfz::EvalKernel*>(p);
+      if (!h && !k) {
         handles.clear();
+        kernels.clear();
         break;
       }
-      handles.push_back(h->Handle());
+      member_of_signal.push_back(h ? (int)handles.size() : -1);
+      if (h) handles.push_back(h->Handle());
+      if (k) kernels.push_back(KernelMember{k, false});
     }
     if (!handles.empty()) check(sxmc_group_create(handles.data(), (int)handles.size(), &group));
+    if (group && !kernels.empty()) {
+      const int rc = sxmc_group_set_columns(group, (int)member_of_signal.size(), member_of_signal.data());
+      if (rc) {
+        sxmc_group_destroy(group);   // (the destructor does not run for an object whose constructor threw)
+        group = nullptr;
+        check(rc);
+      }
+    }
   }
 
   ~MCMC() {
@@ -446,6 +473,9 @@ class MCMC {
   }
 
   size_t NumParameters() const { return nparameters; }
+  /** The form the steps of the last walk took (walk_plan.h: WalkForm::Step), valid after a walk: "reference", "batched",
+   *  "consuming", "lockstep", "lookahead" or "mixed". */
+  const char* WalkFormName() const { return form_name; }
   /** Look-ahead walk: passes over the tables launched so far (each evaluates twice and takes one or two steps). */
   size_t LookaheadPasses() const { return ahead_passes; }
 
@@ -627,10 +657,26 @@ class MCMC {
       form = sxmc::choose_form(WalkFlags{m.group != nullptr, m.reference_form,
                                          m.nsystematics > 0 && !m.systematics_fixed, m.consume, m.lut_output,
                                          m.lockstep != nullptr, m.lookahead || m.lookahead_auto, m.nparameters,
-                                         m.graph_steps});
+                                         m.graph_steps, !m.kernels.empty()});
+      if (form.step == WalkForm::MIXED) {
+        // the kernel members are launched through their handles: bindings current, and which of them a step re-evaluates
+        for (KernelMember& k : m.kernels) {
+          k.eval->Bind();
+          short pars[SXMC_MAX_SYST * SXMC_MAX_SYST_PARS];
+          size_t n = 0;
+          check(sxmc_kde_parameters_read(k.eval->Handle(), pars, sizeof pars / sizeof pars[0], &n));
+          if (n > sizeof pars / sizeof pars[0]) throw pdfz::Error("MCMC: a kernel-density signal reads too many parameters");
+          k.floats = false;
+          for (size_t q = 0; q < n; q++) {
+            const size_t index = m.nsources + (size_t)pars[q];
+            k.floats = k.floats || index >= m.nparameters || !m.parameter_fixed[index];
+          }
+        }
+      }
       if (form.batched) {
         // bindings must be current before the group reads them (proposal vector as parameter buffer)
-        for (pdfz::Eval* p : m.pdfs) dynamic_cast<pdfz::EvalHist*>(p)->Bind();
+        for (pdfz::Eval* p : m.pdfs)
+          if (pdfz::EvalHist* h = dynamic_cast<pdfz::EvalHist*>(p)) h->Bind();
         check(sxmc_group_set_lut_output(m.group, m.lut_output ? 1 : 0));
         if (m.optimize && !m.optimized) {
           check(sxmc_group_optimize(m.group, m.stream, nullptr));
@@ -657,6 +703,8 @@ class MCMC {
         check(sxmc_stream_create(own_stream.put()));
         strm = own_stream.get();
       }
+      static const char* const names[] = {"reference", "batched", "consuming", "lockstep", "lookahead", "mixed"};
+      m.form_name = names[form.step];
     }
 
     /** Look-ahead walk: a shadow set of evaluators over the same tables, bound to the look-ahead vector.  Lock: held. */
@@ -716,6 +764,10 @@ class MCMC {
     void one_step() {
       const sxmc_step_args& a = d.a;
       int npartial = (int)m.nnllthreads;
+      if (form.step == WalkForm::MIXED) {
+        mixed_step();
+        return;
+      }
       if (form.step == WalkForm::CONSUMING) {
         // two launches: fill of all signals; lookup + event sum + step end + clearing for the next step
         check(sxmc_group_step_async(m.group, strm, a.d_means, a.d_sigmas, a.d_rng, a.d_nll_current, a.d_nll_proposed,
@@ -742,6 +794,49 @@ class MCMC {
       }
       SXMC_KERNEL_LAUNCH(finish_nll_jump_pick_combo, 1, m.nreducethreads, m.nreducethreads * sizeof(double), strm,
                          (size_t)npartial, d.sums, m.nsignals, m.nsources, a.d_means, a.d_sigmas, a.d_rng,
+                         a.d_nll_current, a.d_nll_proposed, a.d_v_current, a.d_v_proposed, a.d_accepted, a.d_counter,
+                         a.d_jump_buffer, a.nparameters, a.d_jump_width, a.d_nexpected, a.d_n_mc, a.d_source_id,
+                         a.d_norms, debug_mode);
+    }
+
+    /** One step of a MIXED walk, every launch on the walk's stream and none of them a wait, a copy or an allocation (so
+     *  the step can be recorded): the kernel members that read a floating parameter (sxmc_kde_eval_on_stream_async), the
+     *  group's evaluation into its columns of the table (sxmc_group_eval_async), nll_event_chunks over the whole table
+     *  (the reference's 64 x 256 lanes), and the step end over all signals, which clears the group's histograms and
+     *  its members' normalisations only: the table is whole after every step, with or without lut_output.
+     *  columns_in_place: fill and event sum in one entry instead, the histogram columns looked up in place
+     *  (sxmc_group_eval_columns_nll_async; see the flag for what was measured).  consume = false: the plain
+     *  step end, the group zeroes itself.  No group: kernel evaluations, nll_event_chunks, step end.  Where nothing is
+     *  re-evaluated (no floating systematic) the table of the set-up is summed.  The chain is REFERENCE's bit for bit. */
+    void mixed_step() {
+      const sxmc_step_args& a = d.a;
+      bool summed = false;
+      if (form.reevaluate) {
+        for (const KernelMember& k : m.kernels)
+          if (k.floats) check(sxmc_kde_eval_on_stream_async(k.eval->Handle(), 1, strm));
+        if (m.group && m.columns_in_place && !m.lut_output) {
+          check(sxmc_group_eval_columns_nll_async(m.group, strm, d.lut, nevents, a.d_v_proposed, a.d_nexpected, a.d_n_mc,
+                                                  a.d_source_id, a.d_norms, d.sums, (int)m.nnllblocks,
+                                                  (int)m.nllblocksize));
+          summed = true;
+        } else if (m.group) {
+          check(sxmc_group_eval_async(m.group, 1, strm));
+        }
+      }
+      if (!summed) {
+        SXMC_KERNEL_LAUNCH(nll_event_chunks, m.nnllblocks, m.nllblocksize, 0, strm, d.lut, a.d_v_proposed, nevents,
+                           m.nsignals, a.d_nexpected, a.d_n_mc, a.d_source_id, a.d_norms, d.sums);
+      }
+      if (m.group && form.reevaluate && m.consume) {
+        check(sxmc_group_finish_columns_step_async(m.group, strm, (size_t)m.nnllthreads, d.sums, a.d_means, a.d_sigmas,
+                                                   a.d_rng, a.d_nll_current, a.d_nll_proposed, a.d_v_current,
+                                                   a.d_v_proposed, a.d_accepted, a.d_counter, a.d_jump_buffer,
+                                                   a.nparameters, a.nsources, a.d_jump_width, a.d_nexpected, a.d_n_mc,
+                                                   a.d_source_id, a.d_norms, a.debug_mode));
+        return;
+      }
+      SXMC_KERNEL_LAUNCH(finish_nll_jump_pick_combo, 1, m.nreducethreads, m.nreducethreads * sizeof(double), strm,
+                         (size_t)m.nnllthreads, d.sums, m.nsignals, m.nsources, a.d_means, a.d_sigmas, a.d_rng,
                          a.d_nll_current, a.d_nll_proposed, a.d_v_current, a.d_v_proposed, a.d_accepted, a.d_counter,
                          a.d_jump_buffer, a.nparameters, a.d_jump_width, a.d_nexpected, a.d_n_mc, a.d_source_id,
                          a.d_norms, debug_mode);
@@ -938,6 +1033,10 @@ class MCMC {
       try {
         // the evaluators borrowed this walk's arrays (lookup table, normalisations, parameter vectors): un-bind them
         // before the arrays die, or the next evaluation of an evaluator would touch destroyed arrays
+        // (a mixed walk launched its kernel members on this walk's stream, which they remember: they let go of it
+        //  here, while it exists -- everything on it has been waited for)
+        if (form.step == WalkForm::MIXED)
+          for (const KernelMember& k : m.kernels) k.eval->EvalFinished();
         for (pdfz::Eval* p : m.pdfs) p->ForgetBuffers();
         if (shadow)
           for (auto& p : shadow->evaluators) p->ForgetBuffers();
@@ -968,6 +1067,15 @@ class MCMC {
   std::vector<bool> parameter_fixed;
   std::vector<pdfz::Eval*> pdfs;
   sxmc_group_t group = nullptr;
+  /** A kernel-density member of a mixed fit.  floats: one of the parameters its systematics read is not fixed (asked of
+   *  the evaluator at every walk); the others keep the column and the norm of the set-up evaluation -- the evaluation is
+   *  deterministic, so skipping it leaves the chain unchanged. */
+  struct KernelMember {
+    pdfz::EvalKernel* eval;
+    bool floats;
+  };
+  std::vector<KernelMember> kernels;   //!< non-empty: every evaluator is an EvalHist or an EvalKernel (the walk is MIXED)
+  const char* form_name = "reference";
   bool optimized = false;
   size_t ahead_passes = 0, ahead_passes_seen = 0;   //!< look-ahead walk: passes launched / counted in the rate below
   double ahead_steps_seen = 0;

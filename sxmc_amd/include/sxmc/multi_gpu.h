@@ -71,7 +71,8 @@ struct MultiGpuEnsemble {
   };
   std::vector<LockUse> setup_locks;
   /** how each device ran its experiments: "lockstep" (ensemble_lockstep) or "concurrent" (ensemble_concurrent) --
-   *  also when lockstep was asked for and a kernel-density signal ruled it out (lockstep batches histogram fills) */
+   *  also when lockstep was asked for and a kernel-density signal ruled it out (lockstep batches histogram fills; the
+   *  lanes then walk the MIXED form, batched and recordable like a histogram fit's) */
   std::string device_mode;
 };
 
@@ -327,7 +328,8 @@ inline MultiGpuEnsemble ensemble_multi_gpu(const std::vector<int>& devices, unsi
   out.rank_seconds.assign(G, 0.0);
   out.rank_setup_seconds.assign(G, 0.0);
   // lockstep sets batch the chains' histogram fills: a kernel-density signal runs its device's experiments as
-  // ensemble_concurrent lanes instead
+  // ensemble_concurrent lanes instead.  Every such lane walks the MIXED form (mcmc.h): its histogram signals in their
+  // group, its kernel-density signals on the lane's stream, no host wait between steps, recorded when graph_steps asks
   bool any_kernel = false;
   for (const Signal& s : signals) any_kernel = any_kernel || s.pdf == "kernel";
   run.lockstep = opt.lockstep_chains >= 2 && !any_kernel;

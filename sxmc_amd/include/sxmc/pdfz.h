@@ -454,6 +454,31 @@ class EvalKernel : public detail::EvalOver<detail::KernelApi> {
     return lambda;
   }
 
+  /** sxmc_kde_eval_on_stream_async: the launches of EvalAsync on the caller's stream (bindings made current first, as
+   *  EvalAsync does), capture-safe; the evaluator orders its other calls after it.  For a walk that keeps its whole
+   *  step on one stream. */
+  void EvalOnStream(sxmc_stream_t stream, bool do_eval_pdf = true) {
+    Bind();
+    throw_on(sxmc_kde_eval_on_stream_async(handle, do_eval_pdf ? 1 : 0, stream));
+  }
+
+  /** The parameter indices the attached systematics read, before the parameter buffer's offset. */
+  std::vector<short> ParametersRead() const {
+    size_t n = 0;
+    short none = 0;
+    throw_on(sxmc_kde_parameters_read(handle, &none, 0, &n));
+    std::vector<short> pars(n);
+    if (n) throw_on(sxmc_kde_parameters_read(handle, pars.data(), n, &n));
+    return pars;
+  }
+
+  /** Evaluations launched so far, by EvalAsync or EvalOnStream (a recorded launch counts once, when recorded). */
+  unsigned long long EvaluationCount() const {
+    unsigned long long n = 0;
+    throw_on(sxmc_kde_evaluation_count(handle, &n));
+    return n;
+  }
+
   /** The bandwidths h_d fixed at construction (Scott's rule). */
   std::vector<double> Bandwidths() const {
     std::vector<double> h((size_t)nobservables);

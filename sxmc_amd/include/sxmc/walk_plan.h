@@ -81,6 +81,8 @@ struct WalkFlags {
   bool lookahead_asked;    //!< lookahead or lookahead_auto
   size_t nparameters;
   unsigned graph_steps;
+  bool mixed = false;      //!< there are kernel-density members, and every evaluator is a histogram or kernel-density
+                           //!< evaluator of this library; has_group then says whether there are histogram members
 };
 /** The form of the walk's steps, from the flags alone.  LOOKAHEAD is a candidate: two questions to the device (does the
  *  plan stream codes, is the pass offered for this shape) may still narrow it to CONSUMING, see narrowed(). */
@@ -90,15 +92,21 @@ struct WalkForm {
     BATCHED,     //!< one group evaluation fused with the event sum, then the step end
     CONSUMING,   //!< the group's fused step, which also clears histograms and normalisations for the next one
     LOCKSTEP,    //!< the consuming step, launched by the chain's lockstep set for all its chains
-    LOOKAHEAD    //!< the consuming step over a pair of evaluator sets: one or two steps per pass
+    LOOKAHEAD,   //!< the consuming step over a pair of evaluator sets: one or two steps per pass
+    MIXED        //!< kernel-density members evaluated on the walk's stream, the histogram members in their group, the
+                 //!< event sum over both kinds of column: the per-evaluator chain bit for bit, no host wait between steps
   } step;
   bool batched;      //!< the group is bound, tuned and asked for step-end time-outs (also where nothing is re-evaluated)
   bool reevaluate;
   unsigned gsteps;   //!< steps (LOOKAHEAD: passes) per recorded graph; 0: nothing is recorded
-  bool adapts_fill_form() const { return step == BATCHED || step == CONSUMING; }
+  bool adapts_fill_form() const { return step == BATCHED || step == CONSUMING || (step == MIXED && batched); }
   WalkForm narrowed() const { return WalkForm{CONSUMING, batched, reevaluate, gsteps}; }
 };
 inline WalkForm choose_form(const WalkFlags& f) {
+  // a fit with kernel-density members: one form whether or not systematics float (lockstep sets and the look-ahead pass
+  // are not offered with such members); its steps are recorded like the batched forms'
+  if (f.mixed && !f.reference_form) return WalkForm{WalkForm::MIXED, f.has_group, f.systematics_float, f.graph_steps};
+  if (f.mixed) return WalkForm{WalkForm::REFERENCE, false, f.systematics_float, 0};
   const bool batched = f.has_group && !f.reference_form;
   const bool fused = batched && f.systematics_float;
   WalkForm::Step step = WalkForm::REFERENCE;

@@ -249,6 +249,31 @@ class EvalGroup:
                   ptr(accepted), ptr(counter), ptr(jump_buffer), int(nparameters), int(nsources), ptr(jump_width),
                   ptr(nexpected), ptr(n_mc), ptr(source_id), ptr(norms), int(bool(debug_mode)))
 
+    def SetColumns(self, member_of_signal):
+        """MIXED FITS: the walk's columns in signal order -- >= 0: that member of the group, looked up from its
+        histogram; -1: a dense column somebody else writes (a kernel-density evaluator).  Every member exactly once
+        (sxmc_group_set_columns; uploaded here, once)."""
+        cols = np.ascontiguousarray(member_of_signal, dtype=np.int32).reshape(-1)
+        capi.call("sxmc_group_set_columns", self._g, cols.size, ptr(cols))
+
+    def EvalColumnsNllAsync(self, stream, lut, nevents, pars, nexpected, n_mc, source_id, norms, sums, grid=64,
+                            block=256):
+        """The group's zero and fill as EvalAsync(True) does them, then nll_event_chunks(grid, block) over the mixed
+        table with the histogram columns looked up in place: sums[0 .. grid * block) bit for bit what the materialised
+        table gives; the members' columns of `lut` are not written (sxmc_group_eval_columns_nll_async)."""
+        capi.call("sxmc_group_eval_columns_nll_async", self._g, ptr(stream), ptr(lut), int(nevents), ptr(pars),
+                  ptr(nexpected), ptr(n_mc), ptr(source_id), ptr(norms), ptr(sums), int(grid), int(block))
+
+    def FinishColumnsStepAsync(self, stream, npartial_sums, sums, means, sigmas, rng, nll_current, nll_proposed,
+                               v_current, v_proposed, accepted, counter, jump_buffer, nparameters, nsources,
+                               jump_width, nexpected, n_mc, source_id, norms, debug_mode=False):
+        """FinishStepAsync for a mixed fit: the step end over all the columns of SetColumns, the clearing over the
+        group's histograms and its members' normalisation slots only (sxmc_group_finish_columns_step_async)."""
+        capi.call("sxmc_group_finish_columns_step_async", self._g, ptr(stream), int(npartial_sums), ptr(sums),
+                  ptr(means), ptr(sigmas), ptr(rng), ptr(nll_current), ptr(nll_proposed), ptr(v_current),
+                  ptr(v_proposed), ptr(accepted), ptr(counter), ptr(jump_buffer), int(nparameters), int(nsources),
+                  ptr(jump_width), ptr(nexpected), ptr(n_mc), ptr(source_id), ptr(norms), int(bool(debug_mode)))
+
     def EvalFinished(self):
         capi.call("sxmc_group_synchronize", self._g)
 

@@ -295,6 +295,23 @@ class EvalKernel(_Eval):
         self._call("bandwidths", capi.ptr(out), out.size)
         return out
 
+    def EvalOnStream(self, stream, do_eval_pdf=True):
+        """EvalAsync's launches on the caller's stream (sxmc_kde_eval_on_stream_async): same kernels, same bits,
+        capture-safe; the evaluator orders its other calls after the last work given to that stream."""
+        self._call("eval_on_stream_async", int(bool(do_eval_pdf)), capi.ptr(stream))
+
+    def ParametersRead(self):
+        """The parameter indices the attached systematics read (int16), before the parameter buffer's offset."""
+        n = C.c_size_t(0)
+        self._call("parameters_read", None, 0, C.byref(n))
+        out = np.zeros(n.value, dtype=np.int16)
+        self._call("parameters_read", capi.ptr(out), out.size, C.byref(n))
+        return out
+
+    def EvaluationCount(self):
+        """Evaluations launched so far, by EvalAsync or EvalOnStream (for tests and reports)."""
+        return self._get("evaluation_count", C.c_ulonglong)
+
     def SamplePool(self):
         """How many samples the last evaluation left inside the domain, as the sampler counts them (= the norm)."""
         return self._get("sample_pool", C.c_size_t)
