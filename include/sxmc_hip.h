@@ -643,7 +643,8 @@ int sxmc_group_finish_columns_step_async(sxmc_group_t g, sxmc_stream_t s, size_t
  * The NLL is evaluated at d_v_proposed, which is also the members' parameter buffer in a walk (mcmc.cpp:241).
  * Histograms and normalisations are CLEARED when this returns, as after sxmc_group_finish_step_async; the
  * lookup table is written only when sxmc_group_set_lut_output is on.  The one-workgroup form adds the log terms
- * in another order than the many-workgroup form (NLL equal to ~1e-15 relative). */
+ * in the many-workgroup form's order -- its waves' sums block of 128 rows by block -- so the NLL, and with it the chain,
+ * is the same bit for bit whichever form ends the step (tests/test_gpu_step_end_forms.py). */
 int sxmc_group_step_async(sxmc_group_t g, sxmc_stream_t s, const double* d_means, const double* d_sigmas,
                           sxmc_rng_state* d_rng, double* d_nll_current, double* d_nll_proposed,
                           double* d_v_current, double* d_v_proposed, int* d_accepted, int* d_counter,
@@ -712,7 +713,7 @@ int sxmc_multigroup_lookahead_step_async(sxmc_multigroup_t mg, sxmc_stream_t s, 
 /* *ok = 1 when a walk over this group (evaluation points set, buffers bound) can be taken by the look-ahead pass and
  * stay the sequential chain bit for bit.  0: histograms beyond LDS, a materialised lookup table, members with
  * different points -- or a problem so small (at most 256 look-ups per step) that the sequential step ends in the
- * one-workgroup form, whose event sum is partitioned differently: walk sequentially then. */
+ * one-workgroup form, which the pass has no counterpart of: walk sequentially then. */
 int sxmc_group_lookahead_supported(sxmc_group_t g, int* ok);
 int sxmc_lookahead_begin(sxmc_stream_t s, int nparameters, const sxmc_rng_state* d_rng, const float* d_jump_width,
                          const double* d_v_current, double* d_v_lookahead);

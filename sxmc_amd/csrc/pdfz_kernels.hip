@@ -560,7 +560,17 @@ __global__ __launch_bounds__(1024) void tail_step_kernel(const SxSignalDesc* __r
   __shared__ double s_total;
   const double t =
       eval_nll_block(descs, nsig, npoints, weight, a.v_proposed, a.nexpected, a.n_mc, a.source_id, a.norms, sh);
-  if (threadIdx.x == 0) s_total = isnan(t) ? 0.0 : t;   // (nll_kernels.cpp:113-115: a NaN partial is not stored)
+  if (threadIdx.x == 0) {
+    // The sequential step sums the rows in blocks of 128 (eval_nll_kernel: two waves each) and its finisher adds the
+    // blocks' partial sums (block_sum).  This form is taken for at most 256 rows -- waves 0 .. 3 here, two such blocks
+    // --, and (w0 + w1) + (w2 + w3) is not ((w0 + w1) + w2) + w3 to the last bit: beyond one block the waves' sums (still
+    // in sh[0 .. 3]) are added block by block, so that the NLL is the sequential step's whatever form ends the step.
+    // (the host's rule, step_end_takes_tail: at most kTailMaxLookups rows, two blocks of kStepSumRows rows = two waves each)
+    static_assert(kStepSumRows == 2 * kWave && kTailMaxLookups <= 2 * kStepSumRows, "waves 0 .. 3: two blocks of two waves");
+    double total = t;
+    if (npoints > kStepSumRows && nsig > 0) total = ((0.0 + sh[0]) + sh[1]) + ((0.0 + sh[2]) + sh[3]);
+    s_total = isnan(total) ? 0.0 : total;   // (nll_kernels.cpp:113-115: a NaN partial is not stored)
+  }
   __syncthreads();
   // (a launch bound of 1024 lanes, 128 registers: few of phase B's addends in registers)
   sxdev::finish_step_device<8>(1, &s_total, a.nsignals, a.nsources, a.means, a.sigmas, a.rng, a.nll_current,

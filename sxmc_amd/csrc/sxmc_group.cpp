@@ -694,18 +694,20 @@ namespace sxhost {
 // The end of a step after the fill: lookup + event sum + finish_nll_jump_pick_combo + the clearing for the next
 // evaluation -- one workgroup in one launch where that is small, two launches otherwise (see sxmc_group_step_async).
 // Does the end of a step over `ne` rows take the one-workgroup form (tail_step_kernel)?  One rule, asked by the
-// sequential step and by the look-ahead walk (which must partition its event sum exactly like the sequential step,
-// or the two could round the NLL differently and part ways at an accept boundary).
+// sequential step and by the look-ahead walk.  That form adds its waves' sums in the blocks of the many-workgroup forms,
+// so the NLL is the same bit for bit whichever ends the step; the look-ahead pass is still not offered for such a shape:
+// it has no one-workgroup end of its own, and a step this small is launch latency, which a second evaluation per pass
+// does not shorten.
 bool step_end_takes_tail(const sxmc_group* g, bool sparse, unsigned long long ne) {
   unsigned long long words = 0;
   const std::vector<SxSignalDesc>& flavour = sparse ? g->h_descs_sparse : g->h_descs;
   for (const SxSignalDesc& d : flavour) words += (unsigned long long)d.total_nbins;
   const unsigned long long gathers = ne * g->members.size();
-  return gathers <= 256ull && words <= (1ull << 16) && g->cfg_tail != 0;
+  return gathers <= kTailMaxLookups && words <= (1ull << 16) && g->cfg_tail != 0;
 }
 // workgroups of 128 rows the event sum of a step is cut into (eval_nll_kernel; eval_nll2_kernel per candidate)
 int step_sum_blocks(unsigned long long ne) {
-  return (int)std::min<unsigned long long>(1024, std::max<unsigned long long>(1, (ne + 127) / 128));
+  return (int)std::min<unsigned long long>(1024, std::max<unsigned long long>(1, (ne + kStepSumRows - 1) / kStepSumRows));
 }
 // Does the step end run as ONE cooperative launch (step_end_kernel: workgroups that wait for each other inside the
 // kernel)?  By default (sxmc_group_set_cooperative_step_end / SXMC_COOP_STEP_END=0 switch it off), where the whole grid

@@ -287,7 +287,7 @@ int sxmc_multigroup_lookahead_step_async(sxmc_multigroup_t mg, sxmc_stream_t s, 
   if (step_end_takes_tail(ga, false, ga->ec[0].K)) {
     return fail(SXMC_ERR_STATE,
                 "the look-ahead walk is not offered for this shape: the sequential step ends in the one-workgroup form "
-                "(at most 256 look-ups), whose event sum is partitioned differently -- walk sequentially "
+                "(at most 256 look-ups), which the pass has no counterpart of -- walk sequentially "
                 "(sxmc_group_lookahead_supported says so beforehand)");
   }
   if (replan) {

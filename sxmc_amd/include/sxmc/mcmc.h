@@ -691,7 +691,7 @@ class MCMC {
       }
       if (form.step == WalkForm::LOOKAHEAD) {
         // not every shape is offered the look-ahead pass (histograms beyond LDS; problems so small that the sequential
-        // step ends in the one-workgroup form, whose event sum is partitioned differently): those walk sequentially
+        // step ends in the one-workgroup form, which the pass has no counterpart of): those walk sequentially
         int ok = 0;
         check(sxmc_group_lookahead_supported(m.group, &ok));
         if (!ok) form = form.narrowed();

@@ -1,6 +1,10 @@
 """GPU parity tests of the NLL half of the path (nll_kernels) and of the whole MCMC step,
 against the CPU oracle.  Tolerance: 1e-6 relative on the summed NLL is what BASELINE.json's
-north_star asks; the kernels are held to 1e-12 here (only the summation order differs)."""
+north_star asks; the kernels are held to 1e-12 here (only the summation order differs).
+
+The look-ahead walk and the lockstep sets are walked here over config 3 scaled down (12 members, one class count per
+test); their edges -- 16 / 17 members, a block of 128 rows more or less, the worker and parameter limits, chains of very
+different sizes -- and those of the one-workgroup and fused step ends are in tests/test_gpu_step_end_forms.py."""
 import math
 
 import numpy as np

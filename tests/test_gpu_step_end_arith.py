@@ -10,7 +10,13 @@ except where the replay's own numbers come from another implementation of the sa
 deviate, the oracle's NLL): there the project's bounds for those apply (tests/test_gpu_step_replay.py).
 
 Small tables throughout (about 3 000 samples per signal, 1 500 events): the step end does not see the table size.
+
+This file pins the SEQUENTIAL step end.  The other forms that call the same device functions -- the look-ahead pass, the
+lockstep sets' joint ends, the one-workgroup end, the fused step -- are walked at the same edges, and at their own limits,
+in tests/test_gpu_step_end_forms.py (cases: tests/step_end_form_cases.py).
 """
+import copy
+
 import numpy as np
 import pytest
 
@@ -167,6 +173,88 @@ NSTEPS, FLUSH = 80, 20
 _followed = {}
 
 
+class Replay:
+    """One chain beside the host replay of its steps (tests/step_reference.py), one decided step at a time: the device's
+    proposal within the project's bound on a device normal (tests/test_gpu_step_replay.py, follow()), its NLL against the
+    oracle's within NLL_RTOL, and from those the replay's decision, counters, jump-buffer rows, current values and
+    generator offsets, bit for bit.  Shared by followed() below and tests/test_gpu_step_end_forms.py.
+    m: a chain after setup(), `rows` its jump buffer's rows; events: the chain's own, where they are not w's."""
+
+    def __init__(self, m, w, seed, rows, events=None):
+        capi.synchronize()                                      # (the set-up's first proposal is drawn on the chain's stream)
+        self.m, self.rows = m, rows
+        self.w = w
+        if events is not None:
+            self.w = copy.copy(w)
+            self.w.events = events
+        jw = m.jump_width.get()
+        self.ref = StepReference(seed, jw, m.current_vector.get(), m.current_nll.get()[0], rows)
+        self.ref.first_proposal()
+        self.free = jw > 0
+        self.width = np.clip(jw.astype(np.float64), 0.0, None)
+        self.v_cur, self.nll_cur = m.current_vector.get(), m.current_nll.get()[0]
+        self.k = self.accepted = self.negative = 0
+
+    def proposal(self, vp):
+        """vp is what the replay proposes now: the project's bound on a device normal."""
+        ref = self.ref
+        tol = 8e-12 * self.width + 2.0 ** -52 * np.abs(ref.v_proposed)
+        assert np.all(np.abs(vp - ref.v_proposed) <= tol), (self.k, vp, ref.v_proposed)
+        assert np.array_equal(bits(vp[~self.free]), bits(self.v_cur[~self.free]))
+
+    def before(self):
+        """Ahead of a step's launch: the pending proposal and the counters."""
+        m = self.m
+        self.vp = m.proposed_vector.get()
+        self.proposal(self.vp)
+        self.acc_before, self.count = int(m.accept_counter.get()[0]), int(m.jump_counter.get()[0])
+        assert (self.acc_before, self.count) == (self.ref.accepted, self.ref.count)
+
+    def oracle(self, v):
+        return oracle_nll_of_workload(self.w, v)[0]
+
+    def refused_unseen(self):
+        """A step the device decided and then overwrote the NLL of (the look-ahead pass's A-step after a rejection): the
+        replay decides it from the oracle's NLL, and it must be a rejection too."""
+        rec = self.ref.step(self.oracle(self.vp), v_proposed=self.vp)
+        assert not rec["accept"], (self.k, rec)
+        self.k += 1
+        self.count += 1
+
+    def after(self, vp, check_nll):
+        """The step over proposal vp has run: its NLL, the decision and everything the decision implies."""
+        m, ref, k = self.m, self.ref, self.k
+        P = vp.size
+        got = m.proposed_nll.get()[0]
+        if np.any(vp[:self.w.nsources] < 0):                    # nll_kernels.cpp:176-179: 1e18, and a finite chain says no
+            self.negative += 1
+            assert got == 1e18, (k, got)
+        elif check_nll:
+            want = self.oracle(vp)
+            assert got == want or abs(got - want) <= NLL_RTOL * abs(want), (k, got, want)
+        rec = ref.step(got, v_proposed=vp)
+        accepted = int(m.accept_counter.get()[0]) - self.acc_before
+        assert accepted == int(rec["accept"]), (k, rec)
+        assert not (got == 1e18 and accepted), k
+        self.v_cur = vp if accepted else self.v_cur
+        self.nll_cur = got if accepted else self.nll_cur
+        assert np.array_equal(bits(m.current_vector.get()), bits(self.v_cur)), k
+        assert bits(m.current_nll.get())[0] == bits(np.array([self.nll_cur]))[0], k
+        assert int(m.jump_counter.get()[0]) == ref.count == self.count + 1
+        jb = m.jump_buffer.get().reshape(self.rows, P + 1)
+        assert np.array_equal(bits(jb[:ref.count]), bits(ref.jump_buffer[:ref.count])), (k, self.count)
+        assert np.array_equal(bits(jb[self.count, :P]), bits(self.v_cur.astype(np.float32)))
+        assert bits(jb[self.count, P:])[0] == bits(np.array([self.nll_cur], np.float64).astype(np.float32))[0]
+        st = m.rngs.get().reshape(P, 4)
+        assert [int(o) for o in st[:, 2]] == ref.offsets, k
+        self.k += 1
+        self.accepted += accepted
+
+    def flushed(self):
+        """The chain's flush() has reset its counters."""
+        self.ref.accepted = self.ref.count = 0
+
+
 def followed(nsig):
     """The cooperative step end launched one by one, every step followed by the host replay.  Returns the flushes'
     records (computed once, shared, never modified)."""
@@ -177,57 +265,24 @@ def followed(nsig):
     sigmas = w.parameter_sigmas()
     assert np.count_nonzero(sigmas == 0) == w.nsources and np.count_nonzero(sigmas > 0) >= 1
     m = new_chain(w, True, False, FLUSH, jw)
-    P, S = w.nparameters, w.nsources
-    capi.synchronize()
-    ref = StepReference(SEED, jw, m.current_vector.get(), m.current_nll.get()[0], FLUSH)
-    ref.first_proposal()
-    free = jw > 0
-    width = np.clip(jw.astype(np.float64), 0.0, None)
-    out, negative, accepted_total = [], 0, 0
-    v_cur, nll_cur = m.current_vector.get(), m.current_nll.get()[0]
+    r = Replay(m, w, SEED, FLUSH)
+    out, accepted_total = [], 0
     for k in range(NSTEPS):
-        vp = m.proposed_vector.get()
-        # the proposal: the project's bound on a device normal (tests/test_gpu_step_replay.py, follow())
-        tol = 8e-12 * width + 2.0 ** -52 * np.abs(ref.v_proposed)
-        assert np.all(np.abs(vp - ref.v_proposed) <= tol), (k, vp, ref.v_proposed)
-        assert np.array_equal(bits(vp[~free]), bits(v_cur[~free]))
-        acc_before, count = int(m.accept_counter.get()[0]), int(m.jump_counter.get()[0])
-        assert (acc_before, count) == (ref.accepted, ref.count)
+        r.before()
         m.step()
         capi.synchronize()
         # (the fill + ONE step-end launch; a chain's first step zeroes the histograms in a launch of its own before them)
         assert m.group.LastStepLaunches() == (3 if k == 0 else 2), (k, m.group.LastStepLaunches())
         assert m.group.StepEndTimeouts() == 0
-        got = m.proposed_nll.get()[0]
-        if np.any(vp[:S] < 0):                                  # nll_kernels.cpp:176-179: 1e18, and a finite chain says no
-            negative += 1
-            assert got == 1e18, (k, got)
-        elif k % 8 == 0:
-            want = oracle_nll_of_workload(w, vp)[0]
-            assert got == want or abs(got - want) <= NLL_RTOL * abs(want), (k, got, want)
-        rec = ref.step(got, v_proposed=vp)
-        accepted = int(m.accept_counter.get()[0]) - acc_before
-        assert accepted == int(rec["accept"]), (k, rec)
-        assert not (got == 1e18 and accepted), k
-        v_cur = vp if accepted else v_cur
-        nll_cur = got if accepted else nll_cur
-        assert np.array_equal(bits(m.current_vector.get()), bits(v_cur)), k
-        assert bits(m.current_nll.get())[0] == bits(np.array([nll_cur]))[0], k
-        assert int(m.jump_counter.get()[0]) == ref.count == count + 1
-        jb = m.jump_buffer.get().reshape(FLUSH, P + 1)
-        assert np.array_equal(bits(jb[:ref.count]), bits(ref.jump_buffer[:ref.count])), (k, count)
-        assert np.array_equal(bits(jb[count, :P]), bits(v_cur.astype(np.float32)))
-        assert bits(jb[count, P:])[0] == bits(np.array([nll_cur], np.float64).astype(np.float32))[0]
-        st = m.rngs.get().reshape(P, 4)
-        assert [int(o) for o in st[:, 2]] == ref.offsets, k
+        r.after(r.vp, k % 8 == 0)
         if (k + 1) % FLUSH == 0:
-            r = record(m)
-            assert (r["nacc"], r["count"]) == (ref.accepted, ref.count)
-            accepted_total += r["nacc"]
-            out.append(r)
-            ref.accepted = ref.count = 0
+            rec = record(m)
+            assert (rec["nacc"], rec["count"]) == (r.ref.accepted, r.ref.count)
+            accepted_total += rec["nacc"]
+            out.append(rec)
+            r.flushed()
     close(m)
-    assert negative >= 1, negative
+    assert r.negative >= 1, r.negative
     assert 0 < accepted_total < NSTEPS, accepted_total
     _followed[nsig] = out
     return out
