@@ -391,6 +391,60 @@ int sxmc_kde_sample_pool(sxmc_kde_t k, size_t* n);
  * returns when h_prob is filled; the rows are left untouched.  SXMC_ERR_INVALID: a null argument, obs outside
  * [0, nobservables), nbins < 1.  SXMC_ERR_STATE before any evaluation. */
 int sxmc_kde_project(sxmc_kde_t k, int obs, int nbins, double* h_prob);
+/* scale[0 .. nobservables): the bandwidth scales the evaluator was created with (a shared evaluator: its base's). */
+int sxmc_kde_bandwidth_scale(sxmc_kde_t k, double* scale, size_t n);
+/* Bandwidths by leave-one-out likelihood cross-validation (Silverman 3.4.4): the bandwidths that maximise the
+ * log-likelihood of the sample under its own estimate with each row left out of its own sum.  Contract, all in f64 on
+ * the f64 values of the float table at zero systematics:
+ *   rows     the n untransformed rows inside the domain, in table order; with max_rows > 0 and n > max_rows every
+ *            ceil(n / max_rows)-th of them from the first (max_rows == 0: all).  m of them are scored; m < 2 is
+ *            SXMC_ERR_INVALID.
+ *   score    for a candidate bandwidth vector h, [L_d, U_d) the domain, Phi through erfc as the prepass and the pilot
+ *            write it:
+ *              M_jd(h)  = Phi((U_d - x_jd)/h_d) - Phi((L_d - x_jd)/h_d)
+ *              f_-i(h)  = 1/(m-1) sum_{j != i} prod_d phi((x_id - x_jd)/h_d) / (h_d M_jd(h))
+ *              score(h) = (1/m) sum_i ln f_-i(h)
+ *            The pair j == i is left out of the sum, never subtracted afterwards (for an isolated row subtraction would
+ *            cancel what the score is about); rows with equal coordinates are different rows.  A row with f_-i = 0
+ *            (no neighbour within exp's range) contributes -inf: the candidate scores -inf and is never chosen.
+ *   device   one lane per scored row, the m sample rows wave-uniform; per pair the D squared differences e_d once, per
+ *            candidate q = sum_d e_d / (2 h_d^2) with the reciprocal taken once per scan, one exp and one multiply-add
+ *            by the weight 1 / prod_d (h_d M_jd) into the candidate's own accumulator: K <= 32 candidates share the
+ *            loads and the differences of one pass over the m^2 pairs.
+ *   order    no floating-point atomics.  The sample rows are cut over workgroups by a rule that reads m and K alone
+ *            (sxmc_amd/csrc/kde_cv.h, cv_split, beside the pilot's), the partial sums are added in split order, then
+ *            the logarithm is taken; the m logarithms of a candidate are added on the host in table order.  Two calls
+ *            give the same score bits, on any device, and so does a shared evaluator.
+ *   subsets  the candidates of a search are scaled to the rows scored: h_cd = s_c sigma_d m^(-1/(D+4)), sigma_d the
+ *            evaluator's own standard deviation over all n in-domain rows.  n^(-1/(D+4)) is the exponent Scott's rule
+ *            and the AMISE optimum share, so a multiplier found on m rows carries over to n.
+ *   grid     multipliers s_k = lo (hi/lo)^(k/(steps-1)), k = 0 .. steps - 1 (taken through log2 / exp2, so that powers of two are
+ *            met exactly); 1 <= steps <= 32, 0 < lo <= hi, both finite.  The default lo = 1/8, hi = 4, steps = 21 has
+ *            ratio 2^(1/4) and 1 on the grid.
+ *   choice   the largest finite score; a tie goes to the multiplier with the smaller |ln s|, then to the smaller s; no
+ *            finite score at all is SXMC_ERR_INVALID with a message.
+ *   search   (a) one scan of a common multiplier on all observables; (b) with per_observable one round of coordinate
+ *            scans in observable order over the same grid, the other observables held at the values chosen so far.
+ *            The value held is on the grid, so the chosen score never decreases from one scan to the next.
+ * Cross-validation chooses the GLOBAL scales, the Scott stage: an adaptive evaluator created with the chosen scales
+ * runs its pilot and takes its factors lambda_i at the chosen bandwidths, as if the scales had been typed in.  The
+ * evaluator these are called on keeps its own bandwidths, fixed at creation, and neither call touches its rows or
+ * its last evaluation.  Accuracy of a score: the bound of tests/kde_cv_reference.py.  Cost O(m^2 K) per scan.
+ *
+ * sxmc_kde_cv_scores: the primitive, no search.  bandwidths[c * nobservables + d]: ncandidates (1 .. 32) absolute
+ * candidate vectors, positive and finite; scores[c] their scores; *rows_used (may be null) = m.
+ * sxmc_kde_cv_select: the search on the evaluator's table.  scale_out[0 .. nobservables): the chosen multipliers of
+ * Scott's rule, a bandwidth_scale for sxmc_kde_create.  The report, every pointer of which may be null: *score the
+ * score of the choice; *score_at_one the common scan's score at s = 1 (NaN when 1 is not on the grid);
+ * at_edge[d] = 1 when the choice of observable d sits on the first or last grid value (widen the grid); *rows_used = m;
+ * *nscans = 1 or 1 + nobservables; scan_grid and scan_scores [nscans][steps] every scan's multipliers and scores, the
+ * common scan first; scan_chosen[nscans] the index each scan chose.
+ * Argument validation (null arguments, the candidate count and values, the grid, m < 2) needs no GPU. */
+int sxmc_kde_cv_scores(sxmc_kde_t k, const double* bandwidths, int ncandidates, size_t max_rows, double* scores,
+                       size_t* rows_used);
+int sxmc_kde_cv_select(sxmc_kde_t k, double lo, double hi, int steps, int per_observable, size_t max_rows,
+                       double* scale_out, size_t n_scale, double* score, double* score_at_one, int* at_edge,
+                       size_t* rows_used, int* nscans, double* scan_grid, double* scan_scores, int* scan_chosen);
 
 /* ---------------------------------------------------------------- evaluator group ----------- */
 /* The "EvalAsync on all signals, then EvalFinished on all" of mcmc.cpp:264-271 and

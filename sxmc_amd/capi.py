@@ -129,6 +129,9 @@ SIGNATURES = {
     "sxmc_kde_random_sample": [_vp, _sz, _ull, _vp, _vp, _vp],
     "sxmc_kde_sample_pool": [_vp, _psz],
     "sxmc_kde_project": [_vp, _i, _i, _vp],
+    "sxmc_kde_bandwidth_scale": [_vp, _vp, _sz],
+    "sxmc_kde_cv_scores": [_vp, _vp, _i, _sz, _vp, _psz],
+    "sxmc_kde_cv_select": [_vp, _d, _d, _i, _i, _sz, _vp, _sz, _pd, _pd, _vp, _psz, _pi, _vp, _vp, _vp],
     "sxmc_group_create": [_vp, _i, _pvp],
     "sxmc_group_destroy": [_vp],
     "sxmc_group_set_launch_config": [_vp, _i, _i],

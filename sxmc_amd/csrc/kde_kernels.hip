@@ -20,6 +20,10 @@
 // (ADAPT = true) writes rows of D + 2 floats -- the same c_d in units of the global h_d, g_i = 1 / lambda_i^2 and
 // W_i = w_i / lambda_i^D with the mass taken at h_d lambda_i -- and kde_pairs_adaptive sums W_i exp2(-g_i q); the
 // sampler and the projection read lambda in f64.  A fixed-bandwidth evaluator never runs an ADAPT instantiation.
+//
+// Bandwidth cross-validation (sxmc_kde_cv_scores / sxmc_kde_cv_select) scores K candidate bandwidth vectors in one f64
+// pass over the pairs of the untransformed in-domain rows: kde_cv_weights, kde_cv_pairs and kde_cv_combine, last in
+// this file.  It reads the table only and leaves the rows of the last evaluation alone.
 #include <hip/hip_runtime.h>
 
 #include "nll_device.h"
@@ -548,5 +552,131 @@ hipError_t sx_kde_pilot(const SxKdePilotArgs& a, const double* x, const double* 
   hipError_t e = hipGetLastError();
   if (e != hipSuccess) return e;
   hipLaunchKernelGGL(kde_pilot_combine_kernel, dim3((unsigned)(a.pitch / kKdeBlock)), dim3(kKdeBlock), 0, s, a, part, f);
+  return hipGetLastError();
+}
+
+// ------------------------------------------------------------------------------------ cross-validation (sxmc_kde_cv_scores)
+// The leave-one-out log-likelihood of K candidate bandwidth vectors on m rows, one pass over the m^2 pairs in f64:
+//   ln f_-i(h_c) = ln[ 1/(m-1) sum_{j != i} prod_d phi((x_id - x_jd) / h_cd) / (h_cd M_jd(h_c)) ]
+//   kde_cv_weights  one lane per sample j: its K weights 1 / prod_d (h_cd M_jd), M through erfc as the prepass and the
+//                   pilot write it, once per scan (0 for the padding candidates)
+//   kde_cv_pairs    the pilot's shape: one lane per scored row i, the samples wave-uniform (scalar loads of the D
+//                   coordinates and the KP weights), split across workgroups (blockIdx.y).  Per pair the D squared
+//                   differences once; per candidate q = sum_d e_d g_cd with g = 1 / (2 h^2) (no division), one exp, one
+//                   multiply-add into the candidate's own accumulator.  The pair j == i is left out by a select on the
+//                   row index, never subtracted.
+//   kde_cv_combine  per row and candidate the splits added in their order, times 1 / ((2 pi)^(D/2) (m - 1)), and the
+//                   logarithm (-inf for a row without a neighbour in exp's range)
+// The m logarithms of a candidate are added on the host in table order.  No floating-point atomics.
+namespace {
+
+__global__ __launch_bounds__(kKdeBlock) void kde_cv_weights_kernel(const SxKdeCvArgs a, double* __restrict__ s0,
+                                                                   const double* __restrict__ cand) {
+  const unsigned long long j = (unsigned long long)blockIdx.x * kKdeBlock + threadIdx.x;
+  if (j >= a.m) return;
+  double* row = s0 + j * (unsigned long long)(a.D + a.KP);
+  const double* inv_h_sqrt2 = cand + (unsigned long long)a.KP * a.D;
+  const double* prod_h = cand + 2ull * a.KP * a.D;
+  for (int c = 0; c < a.KP; c++) {
+    double w = 0.0;
+    if (c < a.K) {
+      double mass = 1.0;
+      for (int d = 0; d < a.D; d++) {
+        const double x = row[d], r = inv_h_sqrt2[c * a.D + d];
+        mass = mass * (0.5 * (erfc((x - a.upper[d]) * r) - erfc((x - a.lower[d]) * r)));
+      }
+      w = 1.0 / (prod_h[c] * mass);
+    }
+    row[a.D + c] = w;
+  }
+}
+
+template <int D, int KP>
+__global__ __launch_bounds__(kKdeBlock) void kde_cv_pairs_kernel(const SxKdeCvArgs a, const double* __restrict__ x,
+                                                                 const double* __restrict__ s0,
+                                                                 const double* __restrict__ g,
+                                                                 double* __restrict__ part) {
+  const unsigned i = blockIdx.x * kKdeBlock + threadIdx.x;   // < pitch (whole blocks)
+  double p[D];
+#pragma unroll
+  for (int k = 0; k < D; k++) p[k] = x[(unsigned long long)k * a.pitch + i];
+  const unsigned j0 = blockIdx.y * a.per_split;
+  const unsigned j1 = a.m - j0 > a.per_split ? j0 + a.per_split : a.m;   // (j0 < m: nsplit * per_split covers m tightly)
+  double acc[KP];
+#pragma unroll
+  for (int c = 0; c < KP; c++) acc[c] = 0.0;
+  for (unsigned j = j0; j < j1; j++) {
+    const double* r = s0 + (unsigned long long)j * (D + KP);
+    double e[D];
+#pragma unroll
+    for (int k = 0; k < D; k++) {
+      const double z = p[k] - r[k];
+      e[k] = z * z;
+    }
+    const bool other = j != i;
+#pragma unroll
+    for (int c = 0; c < KP; c++) {
+      double q = e[0] * g[c * D];
+#pragma unroll
+      for (int k = 1; k < D; k++) q = __builtin_fma(e[k], g[c * D + k], q);
+      const double t = r[D + c] * exp(-q);
+      acc[c] += other ? t : 0.0;
+    }
+  }
+#pragma unroll
+  for (int c = 0; c < KP; c++) part[((unsigned long long)blockIdx.y * KP + c) * a.pitch + i] = acc[c];
+}
+
+__global__ __launch_bounds__(kKdeBlock) void kde_cv_combine_kernel(const SxKdeCvArgs a, const double* __restrict__ part,
+                                                                   double* __restrict__ lnf) {
+  const unsigned long long i = (unsigned long long)blockIdx.x * kKdeBlock + threadIdx.x;
+  const unsigned c = blockIdx.y;   // < K
+  if (i >= a.pitch) return;
+  double s = 0.0;
+  for (unsigned k = 0; k < a.nsplit; k++) s += part[((unsigned long long)k * a.KP + c) * a.pitch + i];
+  lnf[(unsigned long long)c * a.pitch + i] = log(s * a.prefactor);
+}
+
+template <int D>
+hipError_t kde_cv_launch_pairs(const SxKdeCvArgs& a, const double* x, const double* s0, const double* cand, double* part,
+                               hipStream_t s) {
+  const dim3 grid((unsigned)(a.pitch / kKdeBlock), a.nsplit);
+#define SX_KDE_CASE(N)                                                                                           \
+  case N:                                                                                                        \
+    hipLaunchKernelGGL((kde_cv_pairs_kernel<D, N>), grid, dim3(kKdeBlock), 0, s, a, x, s0, cand, part);          \
+    break;
+  switch (a.KP) {
+    SX_KDE_CASE(1) SX_KDE_CASE(8) SX_KDE_CASE(16) SX_KDE_CASE(24) SX_KDE_CASE(32)
+    default: return hipErrorInvalidValue;
+  }
+#undef SX_KDE_CASE
+  return hipGetLastError();
+}
+
+}  // namespace
+
+// the candidate counts the pair kernel is built for
+int sx_kde_cv_padded(int K) { return K <= 1 ? 1 : (K + 7) / 8 * 8; }
+
+hipError_t sx_kde_cv_scan(const SxKdeCvArgs& a, const double* x, double* s0, const double* cand, double* part,
+                          double* lnf, hipStream_t s) {
+  if (a.pitch == 0 || a.pitch % kKdeBlock != 0 || a.m < 2 || a.m > a.pitch || a.pitch > 0x7FFFFF00ull || a.K < 1 ||
+      a.K > SXMC_KDE_CV_MAX || a.KP != sx_kde_cv_padded(a.K) || a.per_split == 0 || a.nsplit == 0 ||
+      (unsigned long long)a.nsplit * a.per_split < a.m || (unsigned long long)(a.nsplit - 1) * a.per_split >= a.m) {
+    return hipErrorInvalidValue;
+  }
+  hipLaunchKernelGGL(kde_cv_weights_kernel, dim3((a.m + kKdeBlock - 1) / kKdeBlock), dim3(kKdeBlock), 0, s, a, s0, cand);
+  hipError_t e = hipGetLastError();
+  if (e != hipSuccess) return e;
+  switch (a.D) {
+    case 1: e = kde_cv_launch_pairs<1>(a, x, s0, cand, part, s); break;
+    case 2: e = kde_cv_launch_pairs<2>(a, x, s0, cand, part, s); break;
+    case 3: e = kde_cv_launch_pairs<3>(a, x, s0, cand, part, s); break;
+    case 4: e = kde_cv_launch_pairs<4>(a, x, s0, cand, part, s); break;
+    default: return hipErrorInvalidValue;
+  }
+  if (e != hipSuccess) return e;
+  hipLaunchKernelGGL(kde_cv_combine_kernel, dim3((unsigned)(a.pitch / kKdeBlock), (unsigned)a.K), dim3(kKdeBlock), 0, s, a,
+                     part, lnf);
   return hipGetLastError();
 }

@@ -323,3 +323,22 @@ struct SxKdePilotArgs {
 };
 hipError_t sx_kde_pilot(const SxKdePilotArgs& a, const double* x, const double* s0, double* part, double* f,
                         hipStream_t s);
+// One scan of likelihood cross-validation (sxmc_kde_cv_scores): K candidate bandwidth vectors scored on m rows in one
+// pass over the pairs.  KP: K rounded up to a count the pair kernel is built for (sx_kde_cv_padded; the padding weighs
+// 0).  x: [D][pitch] the m rows' observables (pitch a multiple of 256, zeros beyond m); s0: [m][D + KP] per sample its
+// D observables, then (written by the scan itself) its KP weights 1 / prod_d (h_cd M_jd); cand: [KP][D] g_cd =
+// 1 / (2 h_cd^2), then [KP][D] 1 / (h_cd sqrt 2), then [KP] prod_d h_cd; part: [nsplit][KP][pitch];
+// lnf: [K][pitch] the result, ln f_-i per candidate and row.  per_split rows to a workgroup, set from m and K alone.
+#define SXMC_KDE_CV_MAX 32
+struct SxKdeCvArgs {
+  int D, K, KP;
+  unsigned m;
+  unsigned long long pitch;
+  unsigned per_split, nsplit;
+  double lower[SXMC_KDE_MAX_DIM];
+  double upper[SXMC_KDE_MAX_DIM];
+  double prefactor;         // 1 / ((2 pi)^(D/2) (m - 1))
+};
+int sx_kde_cv_padded(int K);
+hipError_t sx_kde_cv_scan(const SxKdeCvArgs& a, const double* x, double* s0, const double* cand, double* part,
+                          double* lnf, hipStream_t s);

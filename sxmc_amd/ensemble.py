@@ -102,9 +102,20 @@ def make_evaluators(workload):
     out = []
     for s in w.signals:
         if getattr(s, "pdf", "hist") == "kernel":
-            scale = s.bandwidth_scale if s.bandwidth_scale is not None else [1.0] * w.nobs
-            ev = pdfz.EvalKernel(s.samples, s.nfields, w.nobs, w.lower, w.upper, scale, dataset=s.dataset,
-                                 bandwidth_sensitivity=getattr(s, "bandwidth_sensitivity", 0.0))
+            alpha = getattr(s, "bandwidth_sensitivity", 0.0)
+            if getattr(s, "bandwidth_cv", None) is not None:
+                # "bandwidth_scale": "cv": chosen once, here; from now on the signal carries the numbers, so that
+                # every later evaluator of it is built with them typed in and nothing is searched again
+                ev = pdfz.EvalKernel.CrossValidated(s.samples, s.nfields, w.nobs, w.lower, w.upper,
+                                                    pdfz.CvOptions(**s.bandwidth_cv), dataset=s.dataset,
+                                                    bandwidth_sensitivity=alpha)
+                s.bandwidth_scale = [float(v) for v in ev.BandwidthScale()]
+                s.bandwidth_cv = None
+                s.cv_report = ev.CvReport()
+            else:
+                scale = s.bandwidth_scale if s.bandwidth_scale is not None else [1.0] * w.nobs
+                ev = pdfz.EvalKernel(s.samples, s.nfields, w.nobs, w.lower, w.upper, scale, dataset=s.dataset,
+                                     bandwidth_sensitivity=alpha)
         else:
             ev = pdfz.EvalHist(s.samples, s.nfields, w.nobs, w.lower, w.upper, w.nbins, dataset=s.dataset)
         for d in w.systematics:

@@ -750,10 +750,14 @@ inline void signal_pdf_from_json(Signal& s, const json::Value& c, size_t nobserv
     throw ConfigError(who + "unknown \"pdf\" \"" + s.pdf + "\" (\"hist\" or \"kernel\")");
   }
   s.bandwidth_scale.clear();
+  s.bandwidth_cv = false;
   if (c.isMember("bandwidth_scale")) {
     if (s.pdf != "kernel") throw ConfigError(who + "\"bandwidth_scale\" is only for \"pdf\": \"kernel\"");
     const json::Value& b = c["bandwidth_scale"];
-    if (b.kind == json::Value::Array) {
+    if (b.kind == json::Value::String && b.str == "cv") {   // chosen by cross-validation when the evaluator is built
+      s.bandwidth_cv = true;
+      s.bandwidth_scale.assign(nobservables, 1.0);
+    } else if (b.kind == json::Value::Array) {
       if (b.size() != nobservables) {
         throw ConfigError(who + "\"bandwidth_scale\" has " + std::to_string(b.size()) + " values for " +
                           std::to_string(nobservables) + " fit observables");
@@ -781,6 +785,36 @@ inline void signal_sensitivity_from_json(Signal& s, const json::Value& c) {
     throw ConfigError(who + "\"bandwidth_sensitivity\" must be a number in [0, 1]");
   }
   s.bandwidth_sensitivity = v;
+}
+/** A kernel signal's "bandwidth_cv", the grid and the search behind "bandwidth_scale": "cv" -- an object with any of
+ *  "lo", "hi", "steps", "per_observable" (default true) and "max_rows" (default 65536; 0: all rows).  Refused on a
+ *  histogram signal, without "bandwidth_scale": "cv", with another key or with a bad grid.  After signal_pdf_from_json. */
+inline void signal_cv_from_json(Signal& s, const json::Value& c) {
+  const std::string who = "signal '" + s.name + "': ";
+  s.cv = pdfz::EvalKernel::CvOptions();
+  if (!c.isMember("bandwidth_cv")) return;
+  if (s.pdf != "kernel") throw ConfigError(who + "\"bandwidth_cv\" is only for \"pdf\": \"kernel\"");
+  if (!s.bandwidth_cv) throw ConfigError(who + "\"bandwidth_cv\" needs \"bandwidth_scale\": \"cv\"");
+  const json::Value& o = c["bandwidth_cv"];
+  if (o.kind != json::Value::Object) throw ConfigError(who + "\"bandwidth_cv\" must be an object");
+  for (const auto& kv : o.members) {
+    const std::string& k = kv.first;
+    if (k != "lo" && k != "hi" && k != "steps" && k != "per_observable" && k != "max_rows") {
+      throw ConfigError(who + "\"bandwidth_cv\" has no key \"" + k + "\"");
+    }
+  }
+  s.cv.lo = o.get("lo", s.cv.lo);
+  s.cv.hi = o.get("hi", s.cv.hi);
+  const long long steps = o.isMember("steps") ? o["steps"].asInt("steps") : (long long)s.cv.steps;
+  s.cv.per_observable = o.get("per_observable", true);
+  const long long max_rows = o.isMember("max_rows") ? o["max_rows"].asInt("max_rows") : (long long)s.cv.max_rows;
+  if (!(steps >= 1 && steps <= 32)) throw ConfigError(who + "Cross-validation steps must be between 1 and 32.");
+  if (!(std::isfinite(s.cv.lo) && std::isfinite(s.cv.hi) && s.cv.lo > 0 && s.cv.lo <= s.cv.hi)) {
+    throw ConfigError(who + "Cross-validation grid needs 0 < lo <= hi, both finite.");
+  }
+  if (max_rows < 0) throw ConfigError(who + "\"bandwidth_cv\": \"max_rows\" must not be negative");
+  s.cv.steps = (int)steps;
+  s.cv.max_rows = (size_t)max_rows;
 }
 template <typename T>
 size_t index_with_append(std::vector<T>& v, const T& x) {   // utils.h get_index_with_append
@@ -904,6 +938,7 @@ inline FitConfig parse_config(const std::string& text, const std::string& base_d
     for (const json::Value& sv : c["systematics"].items) s.systematic_names.push_back(sv.asString("systematics[]"));
     detail::signal_pdf_from_json(s, c, fc.observables.size());
     detail::signal_sensitivity_from_json(s, c);
+    detail::signal_cv_from_json(s, c);
     const std::string source_name = c.get("source", name.c_str());
     for (const Source& src : fc.sources)
       if (src.name == source_name) {

@@ -63,14 +63,18 @@ struct Signal {
   std::string pdf = "hist";                   //!< "hist": pdfz::EvalHist; "kernel": pdfz::EvalKernel (kernel density)
   std::vector<double> bandwidth_scale;        //!< "kernel": one per fit observable, in fit-observable order (empty: 1.0)
   double bandwidth_sensitivity = 0.0;         //!< "kernel": alpha of the adaptive bandwidths in [0, 1]; 0: fixed
+  bool bandwidth_cv = false;                  //!< "kernel": bandwidth_scale is still to be chosen by cross-validation
+                                              //!< (build_pdfz chooses, writes bandwidth_scale and clears the flag)
+  pdfz::EvalKernel::CvOptions cv;             //!< ... on this grid, with this search
   pdfz::Eval* histogram = nullptr;  //!< borrowed by the driver, as in the reference
   // keeps the parameter-index arrays alive (the reference leaks them, signal.cpp:139)
   std::vector<std::shared_ptr<pdfz::Array<short>>> par_arrays;
 };
 
 /** Signal::build_pdfz (signal.cpp:112-170): the evaluator of one signal with every systematic attached -- a
- *  pdfz::EvalHist, or a pdfz::EvalKernel when sig.pdf is "kernel" (bandwidth scales from sig.bandwidth_scale, the
- *  sensitivity of its adaptive bandwidths from sig.bandwidth_sensitivity).
+ *  pdfz::EvalHist, or a pdfz::EvalKernel when sig.pdf is "kernel" (bandwidth scales from sig.bandwidth_scale, or chosen by
+ *  cross-validation when sig.bandwidth_cv is set; the sensitivity of its adaptive bandwidths from
+ *  sig.bandwidth_sensitivity).
  *  `samples` is the row-major [n][nfields] table, observables first. */
 inline void build_pdfz(Signal& sig, const std::vector<float>& samples, int nfields,
                        const std::vector<Observable>& observables, std::vector<Systematic>& systematics) {
@@ -90,7 +94,19 @@ inline void build_pdfz(Signal& sig, const std::vector<float>& samples, int nfiel
     }
     std::vector<double> scale(D, 1.0);
     for (size_t i = 0; i < D && !sig.bandwidth_scale.empty(); i++) scale.at(observables[i].field_index) = sig.bandwidth_scale[i];
-    h = new pdfz::EvalKernel(samples, nfields, (int)D, lower, upper, scale, sig.dataset, sig.bandwidth_sensitivity);
+    if (sig.bandwidth_cv) {
+      // "bandwidth_scale": "cv": chosen once, here; from now on the signal carries the numbers, so that every later
+      // evaluator of it (another device's, a shared one) is built with them typed in and nothing is searched again
+      pdfz::EvalKernel* k = pdfz::EvalKernel::CrossValidated(samples, nfields, (int)D, lower, upper, sig.cv, sig.dataset,
+                                                             sig.bandwidth_sensitivity);
+      const std::vector<double> chosen = k->BandwidthScale();
+      sig.bandwidth_scale.assign(D, 1.0);
+      for (size_t i = 0; i < D; i++) sig.bandwidth_scale[i] = chosen.at(observables[i].field_index);
+      sig.bandwidth_cv = false;
+      h = k;
+    } else {
+      h = new pdfz::EvalKernel(samples, nfields, (int)D, lower, upper, scale, sig.dataset, sig.bandwidth_sensitivity);
+    }
   } else if (sig.pdf == "hist") {
     h = new pdfz::EvalHist(samples, nfields, (int)observables.size(), lower, upper, nbins, sig.dataset);
   } else {

@@ -365,6 +365,30 @@ class EvalHist : public detail::EvalOver<detail::HistApi> {
   std::vector<int> axis_nbins;   //!< bins per observable, as constructed
 };
 
+/** pdfz::EvalKernel::CvOptions, the grid and the search of its cross-validation: multipliers lo (hi/lo)^(k/(steps-1)) of Scott's rule, a common scan
+ *  and (per_observable) one coordinate scan per observable, on at most max_rows rows (0: all). */
+struct KernelCvOptions {
+  double lo = 0.125, hi = 4.0;
+  int steps = 21;
+  bool per_observable = true;
+  size_t max_rows = 65536;
+};
+/** pdfz::EvalKernel::CvScan, one scan of a search; observable -1 is the common multiplier on all observables. */
+struct KernelCvScan {
+  int observable = -1;
+  std::vector<double> grid, scores;
+  int chosen = -1;
+};
+/** pdfz::EvalKernel::CvResult, what a search chose. */
+struct KernelCvResult {
+  std::vector<double> scale;   //!< the chosen multipliers of Scott's rule: a bandwidth_scale
+  double score = 0.0;          //!< the score of the choice
+  double score_at_one = 0.0;   //!< the common scan's score at s = 1; NaN when 1 is not on the grid
+  std::vector<KernelCvScan> scans;   //!< the common scan, then one per observable
+  std::vector<int> at_edge;    //!< per observable: the choice sits on the first or last grid value
+  size_t rows_used = 0;        //!< m
+};
+
 /** pdfz::EvalKernel (pdfz.h:578-625; declared by the reference, implemented here): the kernel-density PDF, the unbinned
  *  alternative to EvalHist for signals whose Monte Carlo sample is too small to fill a fine histogram.
  *
@@ -423,9 +447,111 @@ class EvalHist : public detail::EvalOver<detail::HistApi> {
  *  factors over; they are not recomputed.
  *  Accuracy: tests/kde_adaptive_reference.py has the bound; against the fixed-bandwidth bound the coordinate term
  *  grows with the 1/lambda_i^2 of the samples in reach of the point, at most 100 by the clips.
- *  Cost: one more multiply per pair and rows of D + 2 floats; the pilot is O(samples^2) in f64, once. */
+ *  Cost: one more multiply per pair and rows of D + 2 floats; the pilot is O(samples^2) in f64, once.
+ *
+ *  Cross-validated bandwidth scales (Silverman 3.4.4): CrossValidated(...) instead of the constructor, or
+ *  SelectBandwidthScale / CvScores on an evaluator.  All in f64 on the f64 values of the float table at zero
+ *  systematics, over the m untransformed rows inside the domain (with max_rows > 0 and n > max_rows every
+ *  ceil(n / max_rows)-th of them in table order; m < 2 throws):
+ *    M_jd(h)  = Phi((U_d - x_jd)/h_d) - Phi((L_d - x_jd)/h_d)            (Phi through erfc, as the prepass and the pilot)
+ *    f_-i(h)  = 1/(m-1) sum_{j != i} prod_d phi((x_id - x_jd)/h_d) / (h_d M_jd(h))
+ *    score(h) = (1/m) sum_i ln f_-i(h)
+ *  The pair j == i is left out of the sum, never subtracted afterwards; a row with f_-i = 0 contributes -inf, the
+ *  candidate then scores -inf and is never chosen.  Candidates of a search are h_cd = s_c sigma_d m^(-1/(D+4)), sigma_d
+ *  this evaluator's own standard deviation over all n in-domain rows: n^(-1/(D+4)) is the exponent Scott's rule and the
+ *  AMISE optimum share, so a multiplier found on m rows carries over to n.  Multipliers s_k = lo (hi/lo)^(k/(steps-1))
+ *  (default 1/8 .. 4 in 21 steps: ratio 2^(1/4), 1 on the grid; at most 32 steps).  The largest finite score wins; a
+ *  tie goes to the smaller |ln s|, then the smaller s; no finite score throws.  The search is one scan of a common
+ *  multiplier on all observables, then (per_observable) one coordinate scan per observable in order with the others
+ *  held at the values chosen so far, so the chosen score never decreases.  It chooses the GLOBAL scales, the Scott
+ *  stage: with a sensitivity > 0 the pilot and the factors are then taken at the chosen bandwidths, exactly as if the
+ *  scales had been typed in.  Deterministic: no floating-point atomics, the split over workgroups depends on m and the
+ *  candidate count alone, partial sums are added in split order and the m logarithms on the host in table order -- two
+ *  calls, a Share()d evaluator and any device give the same score bits.  An evaluator's own bandwidths never change.
+ *  Accuracy: the bound of tests/kde_cv_reference.py.  Cost O(m^2 K) per scan of K candidates. */
 class EvalKernel : public detail::EvalOver<detail::KernelApi> {
  public:
+  typedef KernelCvOptions CvOptions;
+  typedef KernelCvScan CvScan;
+  typedef KernelCvResult CvResult;
+
+  /** Bandwidth scales by leave-one-out likelihood cross-validation (Silverman 3.4.4; the contract is written out at
+   *  sxmc_kde_cv_scores in include/sxmc_hip.h): over the m untransformed in-domain rows (every ceil(n / max_rows)-th
+   *  when n > max_rows), in f64,
+   *      M_jd(h) = Phi((U_d - x_jd)/h_d) - Phi((L_d - x_jd)/h_d),
+   *      f_-i(h) = 1/(m-1) sum_{j != i} prod_d phi((x_id - x_jd)/h_d) / (h_d M_jd(h)),   score(h) = (1/m) sum_i ln f_-i(h),
+   *  the pair j == i left out of the sum (never subtracted), a row with f_-i = 0 making the score -inf, m < 2 an
+   *  error; candidates h_cd = s_c sigma_d m^(-1/(D+4)) with sigma_d over all n rows, so that a multiplier found on m
+   *  rows carries over to n; the largest finite score wins, a tie going to the smaller |ln s|, then the smaller s.
+   *  A provisional fixed-bandwidth evaluator at scale 1 runs the search; the evaluator returned is constructed with
+   *  the chosen scales and the asked sensitivity, exactly as if the scales had been typed in (an adaptive evaluator's
+   *  pilot and factors are taken at the chosen bandwidths).  No floating-point atomics; the same bits on any device.
+   *  The caller deletes the evaluator. */
+  static EvalKernel* CrossValidated(const std::vector<float>& samples, int nfields, int nobservables,
+                                    const std::vector<double>& lower, const std::vector<double>& upper,
+                                    const CvOptions& options = CvOptions(), unsigned dataset = 0,
+                                    double bandwidth_sensitivity = 0.0) {
+    CvResult report;
+    {
+      const EvalKernel pilot(samples, nfields, nobservables, lower, upper,
+                             std::vector<double>((size_t)(nobservables > 0 ? nobservables : 0), 1.0), dataset);
+      report = pilot.SelectBandwidthScale(options);
+    }
+    EvalKernel* k = new EvalKernel(samples, nfields, nobservables, lower, upper, report.scale, dataset,
+                                   bandwidth_sensitivity);
+    k->cv_report = report;
+    k->cross_validated = true;
+    return k;
+  }
+
+  /** score(h) of each absolute candidate bandwidth vector (candidates[c * nobservables + d], at most 32 of them) on
+   *  this evaluator's table; no search.  rows_used: m. */
+  std::vector<double> CvScores(const std::vector<double>& candidates, size_t max_rows = 0,
+                               size_t* rows_used = nullptr) const {
+    if (nobservables <= 0 || candidates.size() % (size_t)nobservables != 0) {
+      throw Error("Number of candidate bandwidths not divisible by number of observables.");
+    }
+    std::vector<double> scores(candidates.size() / (size_t)nobservables);
+    double none = 0.0;
+    throw_on(sxmc_kde_cv_scores(handle, candidates.data(), (int)scores.size(), max_rows,
+                                scores.empty() ? &none : scores.data(), rows_used));
+    return scores;
+  }
+
+  /** The search on this evaluator's table; its own bandwidths do not change. */
+  CvResult SelectBandwidthScale(const CvOptions& o = CvOptions()) const {
+    const size_t D = (size_t)nobservables, steps = (size_t)(o.steps > 0 ? o.steps : 1);
+    CvResult r;
+    r.scale.assign(D, 0.0);
+    r.at_edge.assign(D, 0);
+    std::vector<double> grid((1 + D) * steps, 0.0), scores((1 + D) * steps, 0.0);
+    std::vector<int> chosen(1 + D, -1);
+    int nscans = 0;
+    throw_on(sxmc_kde_cv_select(handle, o.lo, o.hi, o.steps, o.per_observable ? 1 : 0, o.max_rows, r.scale.data(), D,
+                                &r.score, &r.score_at_one, r.at_edge.data(), &r.rows_used, &nscans, grid.data(),
+                                scores.data(), chosen.data()));
+    for (size_t s = 0; s < (size_t)nscans; s++) {
+      CvScan scan;
+      scan.observable = (int)s - 1;
+      scan.grid.assign(grid.begin() + (long)(s * steps), grid.begin() + (long)((s + 1) * steps));
+      scan.scores.assign(scores.begin() + (long)(s * steps), scores.begin() + (long)((s + 1) * steps));
+      scan.chosen = chosen[s];
+      r.scans.push_back(scan);
+    }
+    return r;
+  }
+
+  /** The bandwidth scales this evaluator was constructed with: typed in, or chosen by CrossValidated. */
+  std::vector<double> BandwidthScale() const {
+    std::vector<double> s((size_t)nobservables);
+    throw_on(sxmc_kde_bandwidth_scale(handle, s.data(), s.size()));
+    return s;
+  }
+
+  /** Whether CrossValidated made this evaluator (or the one it shares its table with), and that search's report. */
+  bool CrossValidatedScales() const { return cross_validated; }
+  const CvResult& CvReport() const { return cv_report; }
+
   EvalKernel(const std::vector<float>& samples, int nfields, int nobservables, const std::vector<double>& lower,
              const std::vector<double>& upper, const std::vector<double>& bandwidth_scale, unsigned dataset = 0,
              double bandwidth_sensitivity = 0.0)
@@ -434,7 +560,8 @@ class EvalKernel : public detail::EvalOver<detail::KernelApi> {
                                       lower.size(), upper.data(), upper.size(), bandwidth_scale.data(),
                                       bandwidth_scale.size(), dataset, bandwidth_sensitivity, &handle));
   }
-  EvalKernel(const EvalKernel& base, SharedSamples s) : EvalOver(base, s) {}
+  EvalKernel(const EvalKernel& base, SharedSamples s)
+      : EvalOver(base, s), cv_report(base.cv_report), cross_validated(base.cross_validated) {}
   Eval* Share() const override { return new EvalKernel(*this, SharedSamples{}); }
 
   /** The alpha this evaluator was constructed with (a shared evaluator: its base's). */
@@ -494,6 +621,10 @@ class EvalKernel : public detail::EvalOver<detail::KernelApi> {
     throw_on(sxmc_kde_project(handle, obs, nbins, out.empty() ? &none : out.data()));
     return out;
   }
+
+ private:
+  CvResult cv_report;
+  bool cross_validated = false;
 };
 
 }  // namespace pdfz

@@ -133,6 +133,8 @@ def signal_pdf(name, c, nobservables):
     if pdf != "kernel":
         raise ValueError(who + '"bandwidth_scale" is only for "pdf": "kernel"')
     b = c["bandwidth_scale"]
+    if isinstance(b, str) and b == "cv":       # chosen by cross-validation when the evaluator is built (signal_cv)
+        return pdf, [1.0] * nobservables
     if isinstance(b, list):
         if len(b) != nobservables:
             raise ValueError(who + '"bandwidth_scale" has %d values for %d fit observables' % (len(b), nobservables))
@@ -157,6 +159,58 @@ def signal_sensitivity(name, c, pdf):
     if not (math.isfinite(v) and 0 <= v <= 1):
         raise ValueError(who + '"bandwidth_sensitivity" must be a number in [0, 1]')
     return v
+
+
+def _integer(v, what):
+    """json::Value::asInt of config.h."""
+    d = _number(v, what)
+    if not (math.isfinite(d) and d == math.floor(d) and abs(d) < 9.0e18):
+        raise ValueError("%s: not an integer" % what)
+    return int(d)
+
+
+CV_KEYS = ("lo", "hi", "steps", "per_observable", "max_rows")
+
+
+def signal_cv(name, c, pdf):
+    """A kernel signal's cross-validated bandwidth scales: None unless "bandwidth_scale" is "cv", else the grid and
+    the search as a dict(lo, hi, steps, per_observable, max_rows) -- the defaults of pdfz.CvOptions overridden by the
+    optional object "bandwidth_cv".  "bandwidth_cv" is refused on a histogram signal, without "bandwidth_scale": "cv",
+    with another key or with a bad grid.  Same rules and messages as sxmc::detail::signal_cv_from_json (config.h)."""
+    who = "signal '%s': " % name
+    is_cv = pdf == "kernel" and isinstance(c.get("bandwidth_scale"), str) and c["bandwidth_scale"] == "cv"
+    cv = dict(lo=0.125, hi=4.0, steps=21, per_observable=True, max_rows=65536)
+    if "bandwidth_cv" not in c:
+        return cv if is_cv else None
+    if pdf != "kernel":
+        raise ValueError(who + '"bandwidth_cv" is only for "pdf": "kernel"')
+    if not is_cv:
+        raise ValueError(who + '"bandwidth_cv" needs "bandwidth_scale": "cv"')
+    o = c["bandwidth_cv"]
+    if not isinstance(o, dict):
+        raise ValueError(who + '"bandwidth_cv" must be an object')
+    for k in sorted(o, key=lambda k: k.encode()):
+        if k not in CV_KEYS:
+            raise ValueError(who + '"bandwidth_cv" has no key "%s"' % k)
+    if "lo" in o:
+        cv["lo"] = _number(o["lo"], "lo")
+    if "hi" in o:
+        cv["hi"] = _number(o["hi"], "hi")
+    if "steps" in o:
+        cv["steps"] = _integer(o["steps"], "steps")
+    if "per_observable" in o:
+        if not isinstance(o["per_observable"], (bool, int, float)):
+            raise ValueError("per_observable: not a boolean")
+        cv["per_observable"] = bool(o["per_observable"])
+    if "max_rows" in o:
+        cv["max_rows"] = _integer(o["max_rows"], "max_rows")
+    if not 1 <= cv["steps"] <= 32:
+        raise ValueError(who + "Cross-validation steps must be between 1 and 32.")
+    if not (math.isfinite(cv["lo"]) and math.isfinite(cv["hi"]) and 0 < cv["lo"] <= cv["hi"]):
+        raise ValueError(who + "Cross-validation grid needs 0 < lo <= hi, both finite.")
+    if cv["max_rows"] < 0:
+        raise ValueError(who + '"bandwidth_cv": "max_rows" must not be negative')
+    return cv
 
 
 def load_config(path_or_text, base_dir=None):
@@ -257,7 +311,8 @@ def load_config(path_or_text, base_dir=None):
             systematics=[s for s in c.get("systematics", [])],
             source=next(s for s in fc.sources if s["name"] == src_name),
             pdf=pdf, bandwidth_scale=bandwidth_scale,
-            bandwidth_sensitivity=signal_sensitivity(name, c, pdf)))
+            bandwidth_sensitivity=signal_sensitivity(name, c, pdf),
+            bandwidth_cv=signal_cv(name, c, pdf)))
     fc.data = {int(k): [dict(filename=row["filename"], title=row.get("title", "")) for row in rows]
                for k, rows in root.get("data", {}).items()}
     fc.base_dir = base_dir or "."
@@ -283,7 +338,8 @@ def build_workload(fc):
         scale = [s["bandwidth_scale"][i] for i in order] if s.get("bandwidth_scale") else None
         sig = workloads.Signal(samples, nfields, nexpected, s["source"]["index"], dataset=s["dataset"],
                                pdf=s.get("pdf", "hist"), bandwidth_scale=scale,
-                               bandwidth_sensitivity=s.get("bandwidth_sensitivity", 0.0))
+                               bandwidth_sensitivity=s.get("bandwidth_sensitivity", 0.0),
+                               bandwidth_cv=s.get("bandwidth_cv"))
         sig.n_mc_total = n_mc
         sig.name = s["name"]
         signals.append(sig)

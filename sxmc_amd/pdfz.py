@@ -258,6 +258,40 @@ class EvalHist(_Eval):
         return out
 
 
+class CvOptions:
+    """The grid and the search of EvalKernel's cross-validation (sxmc_amd/csrc/kde_cv.h): multipliers
+    lo (hi/lo)^(k/(steps-1)) of Scott's rule, a common scan and (per_observable) one coordinate scan per observable,
+    on at most max_rows rows (0: all)."""
+
+    def __init__(self, lo=0.125, hi=4.0, steps=21, per_observable=True, max_rows=65536):
+        self.lo, self.hi, self.steps = float(lo), float(hi), int(steps)
+        self.per_observable, self.max_rows = bool(per_observable), int(max_rows)
+
+    def __eq__(self, other):
+        return isinstance(other, CvOptions) and vars(self) == vars(other)
+
+    def __repr__(self):
+        return "CvOptions(lo=%r, hi=%r, steps=%d, per_observable=%r, max_rows=%d)" % (
+            self.lo, self.hi, self.steps, self.per_observable, self.max_rows)
+
+
+class CvScan:
+    """One scan of a search: observable -1 is the common multiplier on all observables."""
+
+    def __init__(self, observable, grid, scores, chosen):
+        self.observable, self.grid, self.scores, self.chosen = int(observable), grid, scores, int(chosen)
+
+
+class CvReport:
+    """What a search chose: `scale` (a bandwidth_scale), its `score`, `score_at_one` (NaN when 1 is not on the
+    grid), every scan, `at_edge[d]` when observable d's choice sits on the first or last grid value, `rows_used`."""
+
+    def __init__(self, scale, score, score_at_one, scans, at_edge, rows_used):
+        self.scale = np.asarray(scale, dtype=np.float64)
+        self.score, self.score_at_one = float(score), float(score_at_one)
+        self.scans, self.at_edge, self.rows_used = list(scans), list(at_edge), int(rows_used)
+
+
 class EvalKernel(_Eval):
     """pdfz::EvalKernel (pdfz.h:578-625): the kernel-density PDF, contract in sxmc_amd/include/sxmc/pdfz.h.
     Same method names as EvalHist (RandomSample and Shared included), plus Bandwidths(); at most 4 observables;
@@ -278,6 +312,66 @@ class EvalKernel(_Eval):
             def create(*a):
                 return lib.sxmc_kde_create_adaptive(*a[:-1], alpha, a[-1])
         self._create(create, samples, nfields, nobservables, lower, upper, scale, dataset)
+
+    @classmethod
+    def CrossValidated(cls, samples, nfields, nobservables, lower, upper, options=None, dataset=0,
+                       bandwidth_sensitivity=0.0):
+        """An evaluator whose bandwidth scales are chosen by leave-one-out likelihood cross-validation
+        (sxmc_kde_cv_select, contract in include/sxmc_hip.h): a provisional fixed-bandwidth evaluator at scale 1 runs
+        the search, then the evaluator is built with the chosen scales and the asked sensitivity, exactly as if the
+        scales had been typed in.  CvReport() is the search's report."""
+        pilot = cls(samples, nfields, nobservables, lower, upper, np.ones(int(nobservables)), dataset)
+        try:
+            report = pilot.SelectBandwidthScale(options)
+        finally:
+            pilot.close()
+        self = cls(samples, nfields, nobservables, lower, upper, report.scale, dataset, bandwidth_sensitivity)
+        self._cv_report = report
+        return self
+
+    @classmethod
+    def Shared(cls, base):
+        self = super().Shared(base)
+        self._cv_report = getattr(base, "_cv_report", None)
+        return self
+
+    def CvScores(self, candidates, max_rows=0):
+        """score(h) of each absolute candidate bandwidth vector (rows of `candidates`, at most 32) on this evaluator's
+        table, and the rows scored: (float64 [K], m).  No search (sxmc_kde_cv_scores)."""
+        cand = np.ascontiguousarray(candidates, dtype=np.float64).reshape(-1, self.nobservables)
+        scores = np.empty(cand.shape[0], dtype=np.float64)
+        m = C.c_size_t(0)
+        self._call("cv_scores", capi.ptr(cand), cand.shape[0], int(max_rows), capi.ptr(scores), C.byref(m))
+        return scores, m.value
+
+    def SelectBandwidthScale(self, options=None):
+        """The search of sxmc_kde_cv_select on this evaluator's table: a CvReport whose `scale` is a bandwidth_scale.
+        The evaluator's own bandwidths do not change."""
+        o = options if options is not None else CvOptions()
+        D, steps = self.nobservables, int(o.steps)
+        room = (1 + D) * max(steps, 1)
+        scale = np.zeros(D)
+        score, at_one = C.c_double(0), C.c_double(0)
+        at_edge = np.zeros(D, dtype=np.int32)
+        rows, nscans = C.c_size_t(0), C.c_int(0)
+        grid, scores = np.zeros(room), np.zeros(room)
+        chosen = np.zeros(1 + D, dtype=np.int32)
+        self._call("cv_select", float(o.lo), float(o.hi), steps, int(bool(o.per_observable)), int(o.max_rows),
+                   capi.ptr(scale), D, C.byref(score), C.byref(at_one), capi.ptr(at_edge), C.byref(rows),
+                   C.byref(nscans), capi.ptr(grid), capi.ptr(scores), capi.ptr(chosen))
+        scans = [CvScan(s - 1, grid[s * steps:(s + 1) * steps].copy(), scores[s * steps:(s + 1) * steps].copy(),
+                        int(chosen[s])) for s in range(nscans.value)]
+        return CvReport(scale, score.value, at_one.value, scans, [bool(e) for e in at_edge], rows.value)
+
+    def BandwidthScale(self):
+        """The bandwidth scales the evaluator was constructed with: typed in, or chosen by CrossValidated."""
+        out = np.empty(self.nobservables, dtype=np.float64)
+        self._call("bandwidth_scale", capi.ptr(out), out.size)
+        return out
+
+    def CvReport(self):
+        """The report of the search behind CrossValidated (a shared evaluator: its base's); None otherwise."""
+        return getattr(self, "_cv_report", None)
 
     def BandwidthSensitivity(self):
         """The alpha the evaluator was constructed with (a shared evaluator: its base's)."""

@@ -11,7 +11,7 @@ class Signal:
     """One signal's MC sample table + how it enters the fit."""
 
     def __init__(self, samples, nfields, nexpected, source_id, dataset=0, pdf="hist", bandwidth_scale=None,
-                 bandwidth_sensitivity=0.0):
+                 bandwidth_sensitivity=0.0, bandwidth_cv=None):
         self.samples = samples              # float32 [n, nfields] row-major
         self.nfields = nfields
         self.nexpected = float(nexpected)
@@ -23,6 +23,11 @@ class Signal:
         self.bandwidth_scale = None if bandwidth_scale is None else [float(v) for v in bandwidth_scale]
         # "kernel": alpha of pdfz.EvalKernel's adaptive bandwidths in [0, 1]; 0: the fixed bandwidths
         self.bandwidth_sensitivity = float(bandwidth_sensitivity)
+        # "kernel": the keywords of pdfz.CvOptions while bandwidth_scale is still to be chosen by cross-validation
+        # ("bandwidth_scale": "cv"); whoever builds the signal's first evaluator chooses, stores the numbers in
+        # bandwidth_scale and the report in cv_report, and sets this back to None
+        self.bandwidth_cv = None if bandwidth_cv is None else dict(bandwidth_cv)
+        self.cv_report = None
 
     @property
     def n_mc(self):

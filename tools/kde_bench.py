@@ -19,8 +19,15 @@ table, systematics and points: ms_per_eval_adaptive measured the same way right 
 adaptive_over_fixed their ratio (expected from the instruction count alone: one more v_mul_f32, 32 cycles per 64 pairs
 against 28, 1.14), and ms_pilot, the host clock around the adaptive construction minus that around a fixed-bandwidth
 construction of the same table made just before (both in the line): what the pilot, the factors and their upload add.
+--cv: instead of all the above, bandwidth cross-validation on the same table (one JSON line, tool "kde_bench_cv"):
+ms_pilot as above (the yardstick, in the same run); ms_scan, the host clock around one CvScores call of the default
+grid's K = 21 candidates on every in-domain row (rows read back, constants and weights, the fused pair kernel, the
+logarithms back and added); scan_over_k_pilots = ms_scan / (21 ms_pilot), and the same per pair (the pilot takes every
+table row against the in-domain rows, a scan the in-domain rows against themselves); ms_search_all_rows and
+ms_search_default, the host clock around SelectBandwidthScale with max_rows = 0 and with the default max_rows, and what
+they chose.
 Usage: python tools/kde_bench.py [--samples N] [--points E] [--seconds S] [--cpu-points K] [--sample-events M]
-                                 [--project-bins B] [--adaptive] [--sensitivity A]"""
+                                 [--project-bins B] [--adaptive] [--sensitivity A] [--cv]"""
 import argparse
 import json
 import math
@@ -82,6 +89,48 @@ def measure_adaptive(a, samples, F, D, lower, upper, pts, par, fixed_ms):
     return out
 
 
+def measure_cv(a, samples, F, D, lower, upper):
+    """The result line of --cv."""
+    sync = capi.load().sxmc_device_synchronize
+    pdfz.EvalKernel(samples.ravel(), F, D, lower, upper, [1.0] * D, bandwidth_sensitivity=a.sensitivity).close()   # warm
+    c0 = time.perf_counter()
+    ev = pdfz.EvalKernel(samples.ravel(), F, D, lower, upper, [1.0] * D)
+    sync()
+    c1 = time.perf_counter()
+    ad = pdfz.EvalKernel(samples.ravel(), F, D, lower, upper, [1.0] * D, bandwidth_sensitivity=a.sensitivity)
+    sync()
+    c2 = time.perf_counter()
+    ad.close()
+    ms_pilot = 1e3 * ((c2 - c1) - (c1 - c0))
+    o = pdfz.CvOptions()
+    grid = o.lo * (o.hi / o.lo) ** (np.arange(o.steps) / (o.steps - 1))
+    cand = grid[:, None] * ev.Bandwidths()[None, :]           # (the multipliers on the evaluator's own Scott bandwidths)
+    ev.CvScores(cand, 4096)                                   # warm: the kernels' code, the allocator
+    t0 = time.perf_counter()
+    scores, m = ev.CvScores(cand, 0)
+    ms_scan = 1e3 * (time.perf_counter() - t0)
+    t0 = time.perf_counter()
+    full = ev.SelectBandwidthScale(pdfz.CvOptions(max_rows=0))
+    ms_full = 1e3 * (time.perf_counter() - t0)
+    t0 = time.perf_counter()
+    dflt = ev.SelectBandwidthScale(o)
+    ms_default = 1e3 * (time.perf_counter() - t0)
+    n = samples.shape[0]
+    pilot_pairs, scan_pairs = float(n) * m, float(m) * m
+    ev.close()
+    return dict(tool="kde_bench_cv", samples=n, observables=D, rows_scored=int(m), candidates=int(o.steps),
+                ms_construct_fixed=round(1e3 * (c1 - c0), 3), ms_construct_adaptive=round(1e3 * (c2 - c1), 3),
+                ms_pilot=round(ms_pilot, 3), ms_scan=round(ms_scan, 3),
+                scan_over_k_pilots=round(ms_scan / (o.steps * ms_pilot), 4),
+                scan_over_k_pilots_per_pair=round((ms_scan / scan_pairs) / (o.steps * ms_pilot / pilot_pairs), 4),
+                finite_scores=int(np.isfinite(scores).sum()), best_multiplier_of_scan=float(grid[int(np.nanargmax(scores))]),
+                ms_search_all_rows=round(ms_full, 3), chosen_all_rows=[float(v) for v in full.scale],
+                score_all_rows=full.score, score_at_one_all_rows=full.score_at_one,
+                ms_search_default=round(ms_default, 3), rows_default=dflt.rows_used,
+                chosen_default=[float(v) for v in dflt.scale], at_edge_default=dflt.at_edge,
+                device=capi.device_info(0)["name"])
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--samples", type=int, default=1 << 17)
@@ -92,6 +141,7 @@ def main():
     ap.add_argument("--project-bins", type=int, default=100)
     ap.add_argument("--adaptive", action="store_true")
     ap.add_argument("--sensitivity", type=float, default=0.5)
+    ap.add_argument("--cv", action="store_true")
     a = ap.parse_args()
     if capi.device_count() < 1:
         raise SystemExit("kde_bench.py needs a GPU")
@@ -101,6 +151,9 @@ def main():
     t = rng.normal(5.0, 1.5, n)
     samples = np.stack([t + rng.normal(0, 0.4, n), rng.uniform(-1, 1, n), t], axis=1).astype(np.float32)
     lower, upper = [0.0, -1.0], [10.0, 1.0]
+    if a.cv:
+        print(json.dumps(measure_cv(a, samples, F, D, lower, upper)))
+        return
     ev = pdfz.EvalKernel(samples.ravel(), F, D, lower, upper, [1.0, 1.0])
     ev.AddSystematic(pdfz.ShiftSystematic(1, [0]))
     ev.AddSystematic(pdfz.ScaleSystematic(0, [1]))
