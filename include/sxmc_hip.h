@@ -391,6 +391,58 @@ int sxmc_kde_sample_pool(sxmc_kde_t k, size_t* n);
  * returns when h_prob is filled; the rows are left untouched.  SXMC_ERR_INVALID: a null argument, obs outside
  * [0, nobservables), nbins < 1.  SXMC_ERR_STATE before any evaluation. */
 int sxmc_kde_project(sxmc_kde_t k, int obs, int nbins, double* h_prob);
+/* A cutoff radius R on the pair sum, in units of each sample's own bandwidth (h_d, or h_d lambda_i when adaptive):
+ * opt-in, and an approximation whose error is the bound stated here.  R = 0, the default, is everything above: the same
+ * kernels, the same row layout, the same bits.  Accepted: 0, or 1 <= R <= +infinity; anything else, NaN included, is
+ * SXMC_ERR_INVALID (checked first, without a device).
+ *   qcut   = R^2 log2(e) / 2, as an f32 rounded up.
+ *   q'     of a pair = g_i sum_d (c_pd - c_id)^2 exactly as the pair kernels compute it in f32 (the square of the first
+ *            difference, a fused multiply-add per further observable, then times g_i; g_i = 1 for fixed bandwidths).
+ *   A pair is dropped only if the kernel's own f32 q' for it would have been >= qcut; pairs below qcut are always
+ *   summed.  A value therefore lies between the full sum and the sum over the pairs with q' < qcut (before the common
+ *   rounding bound of tests/kde_cutoff_reference.py); each dropped term is at most W_i 2^-qcut.  So the PDF no longer
+ *   integrates to exactly 1: it falls short by at most the dropped mass, at most 2^-qcut (2 pi)^(-D/2) / prod h times
+ *   the mean weight per point.  From qcut > 149 (R >= 15) every dropped exp2 is exactly 0 in f32 and the values are
+ *   those of R = +infinity bit for bit.  R = +infinity drops nothing but sums in the sorted order below.
+ * Pairs are dropped a 256-sample tile at a time against a wave of 64 points at a time:
+ *   order    when a cutoff is first set the host orders the table rows by their UNTRANSFORMED coordinates clamped to the
+ *            domain: a plain sort for one observable, else the Morton order of a fixed grid of 2^(32 / D) cells per
+ *            observable over [lower, upper); stable, ties by table index.  Built once per table and kept on the device;
+ *            evaluators made by sxmc_kde_create_shared use it and copy R from their base.
+ *   gather   per evaluation, after the unchanged prepass (which keeps writing its rows in table order; random_sample,
+ *            sample_pool and project keep reading them and return the bytes of the same evaluator at R = 0), one more
+ *            launch copies the rows into that order and writes each tile's box: min and max of c_d over its rows with
+ *            weight > 0, and their smallest g when adaptive.  The boxes are of the MOVED samples of this evaluation, so
+ *            the culling is exact under any systematic; the order only keeps tiles compact.  A tile without such a row
+ *            has an empty box and is never visited.
+ *   points   set_eval_points sorts the live points (code 0) by the same key, the others last, and keeps the
+ *            permutation for the combine, which still writes pdf_out[offset + stride * i] for the caller's i; one box per
+ *            wave of 64 sorted points, over live points only; a wave without live points visits nothing.
+ *   visit    per wave and tile gap_d = max(0, tile_lo_d - wave_hi_d, wave_lo_d - tile_hi_d) and q_lb from the gaps by
+ *            the pair's own operation sequence, times the tile's smallest g.  Rounding is monotone, so every pair of that
+ *            wave and tile has q' >= q_lb: no margin.  A tile is visited iff q_lb < qcut
+ *            (sxmc_amd/csrc/kde_cutoff.h, cutoff_visit: one function for the device and for a host replay).
+ *   sums     f32 within a visited tile, f64 across the visited tiles in tile order, the sample split over workgroups
+ *            and the combine in split order as without a cutoff; the split itself is the plain one's with the tiles of
+ *            a workgroup doubled up to 16 while four workgroups remain to every resident one (kde_cutoff.h,
+ *            cutoff_split), so that a wave's tile tests and its count are paid once per 16 tiles.
+ * What does not change: the norm, the point codes, the NaN and 0 rules, norm == 0; bandwidths, local factors,
+ * cross-validation and the pilot.  What does: a point's value depends on which other points share its wave (the decision
+ * is per wave), always inside the envelope above.  Two evaluations, a shared evaluator and any device still give the
+ * same bits: no floating-point atomics, and the tiles a wave visits depend on the data alone.
+ * sxmc_kde_set_cutoff: the evaluator must be idle (it waits for its streams); SXMC_ERR_STATE while a graph is being
+ * recorded.  Plans the points again if they are already set.  Every buffer an evaluation needs is allocated here or in
+ * set_eval_points, so sxmc_kde_eval_on_stream_async stays capture-safe.
+ * sxmc_kde_cutoff_stats: of the LAST evaluation, the tiles its waves visited (each wave and sample split adds its own with
+ * one integer atomic, into one of 64 counters that are added on the host) and tiles_possible = live point-waves x tiles; both 0 when that evaluation had no cutoff or no
+ * lookup.  Waits for the evaluator.
+ * sxmc_kde_cutoff_boxes (for tests: a host replay of the visit test): the tile boxes the last evaluation wrote,
+ * [tiles][9] floats lo[4], hi[4], smallest g, and the wave boxes of the point plan, [pitch / 64][8] floats lo[4], hi[4],
+ * pitch the points rounded up to 256.  SXMC_ERR_STATE without a cutoff or points. */
+int sxmc_kde_set_cutoff(sxmc_kde_t k, double R);
+int sxmc_kde_cutoff(sxmc_kde_t k, double* R);
+int sxmc_kde_cutoff_stats(sxmc_kde_t k, unsigned long long* tiles_visited, unsigned long long* tiles_possible);
+int sxmc_kde_cutoff_boxes(sxmc_kde_t k, float* tile_boxes, size_t ntile_floats, float* wave_boxes, size_t nwave_floats);
 /* scale[0 .. nobservables): the bandwidth scales the evaluator was created with (a shared evaluator: its base's). */
 int sxmc_kde_bandwidth_scale(sxmc_kde_t k, double* scale, size_t n);
 /* Bandwidths by leave-one-out likelihood cross-validation (Silverman 3.4.4): the bandwidths that maximise the

@@ -24,11 +24,16 @@
 // Bandwidth cross-validation (sxmc_kde_cv_scores / sxmc_kde_cv_select) scores K candidate bandwidth vectors in one f64
 // pass over the pairs of the untransformed in-domain rows: kde_cv_weights, kde_cv_pairs and kde_cv_combine, last in
 // this file.  It reads the table only and leaves the rows of the last evaluation alone.
+//
+// A cutoff radius (sxmc_kde_set_cutoff, R > 0) puts kde_cutoff_gather between the prepass and the pair sum and replaces
+// the latter two launches by kde_pairs_cutoff and kde_combine_sorted (after kde_combine below; the pure parts in
+// kde_cutoff.h).  At R = 0 none of them runs.
 #include <hip/hip_runtime.h>
 
 #include "nll_device.h"
 
 #include "fill_kernels.inc.h"
+#include "kde_cutoff.h"
 
 #pragma clang fp contract(off)
 
@@ -191,7 +196,236 @@ __global__ __launch_bounds__(kKdeBlock) void kde_combine_kernel(const double* __
   out[stride * (long)i] = v;
 }
 
+// ------------------------------------------------------------------------------------ cutoff radius (sxmc_kde_set_cutoff)
+// With a cutoff the pair sum runs on a second copy of the prepass's rows in the spatial order of kde_cutoff.h, and on
+// points sorted by the same key: kde_cutoff_gather, kde_pairs_cutoff and kde_combine_sorted below.  The prepass, the
+// sampler and the projection are untouched and keep the rows in table order.
+
+// One workgroup per tile: row perm[k] of the prepass's rows goes to place k of the sorted rows, and the tile's box --
+// min and max of c_d over its rows with weight > 0, and the smallest g when adaptive -- to box[tile] (kCutBox floats;
+// empty: lo = +inf, hi = -inf, g = 1).  perm is a permutation of [0, npad), the grid npad / 256 workgroups.
+template <int D, bool ADAPT>
+__global__ __launch_bounds__(kKdeBlock) void kde_cutoff_gather_kernel(const float* __restrict__ rows,
+                                                                      const unsigned* __restrict__ perm,
+                                                                      float* __restrict__ sorted,
+                                                                      float* __restrict__ box) {
+  constexpr int kRow = D + (ADAPT ? 2 : 1);
+  constexpr float kInf = __builtin_huge_valf();
+  __shared__ float red[kKdeBlock / kWave][2 * D + 1];
+  const unsigned tid = threadIdx.x, lane = tid & (kWave - 1), wv = tid / kWave;
+  const unsigned long long k = (unsigned long long)blockIdx.x * kKdeBlock + tid;
+  const float* src = rows + (unsigned long long)perm[k] * kRow;
+  float* dst = sorted + k * kRow;
+  float r[kRow];
+#pragma unroll
+  for (int j = 0; j < kRow; j++) {
+    r[j] = src[j];
+    dst[j] = r[j];
+  }
+  const bool live = r[kRow - 1] > 0.0f;
+  float lo[D], hi[D], g = kInf;
+#pragma unroll
+  for (int d = 0; d < D; d++) {
+    lo[d] = live ? r[d] : kInf;
+    hi[d] = live ? r[d] : -kInf;
+  }
+  if constexpr (ADAPT) g = live ? r[D] : kInf;
+#pragma unroll
+  for (int off = kWave / 2; off > 0; off >>= 1) {
+#pragma unroll
+    for (int d = 0; d < D; d++) {
+      lo[d] = fminf(lo[d], __shfl_down(lo[d], off, kWave));
+      hi[d] = fmaxf(hi[d], __shfl_down(hi[d], off, kWave));
+    }
+    if constexpr (ADAPT) g = fminf(g, __shfl_down(g, off, kWave));
+  }
+  if (lane == 0) {
+#pragma unroll
+    for (int d = 0; d < D; d++) {
+      red[wv][d] = lo[d];
+      red[wv][D + d] = hi[d];
+    }
+    red[wv][2 * D] = g;
+  }
+  __syncthreads();
+  if (tid == 0) {
+    float* b = box + (unsigned long long)blockIdx.x * sxkde::kCutBox;
+#pragma unroll
+    for (int d = 0; d < sxkde::kCutMaxDim; d++) {
+      float l = kInf, h = -kInf;   // (the observables the evaluator does not have keep an empty range)
+      for (int w = 0; w < kKdeBlock / kWave && d < D; w++) {
+        l = fminf(l, red[w][d % D]);
+        h = fmaxf(h, red[w][D + d % D]);
+      }
+      b[d] = l;
+      b[sxkde::kCutMaxDim + d] = h;
+    }
+    float gm = kInf;
+    for (int w = 0; w < kKdeBlock / kWave; w++) gm = fminf(gm, red[w][2 * D]);
+    b[2 * sxkde::kCutMaxDim] = (ADAPT && gm < kInf) ? gm : 1.0f;
+  }
+}
+
+// The f32 sum of one tile's terms at one point: the inner loop of kde_pairs_kernel / kde_pairs_adaptive_kernel.
+template <int D, bool ADAPT>
+__device__ __forceinline__ float kde_tile_sum(const float (&p)[D], const float* __restrict__ s) {
+  constexpr int kRow = D + (ADAPT ? 2 : 1);
+  float acc = 0.0f;
+#pragma unroll 16
+  for (int j = 0; j < kKdeTile; j++) {
+    const float* r = s + j * kRow;
+    const float a0 = p[0] - r[0];
+    float q = a0 * a0;
+#pragma unroll
+    for (int k = 1; k < D; k++) {
+      const float ak = p[k] - r[k];
+      q = __builtin_fmaf(ak, ak, q);
+    }
+    if constexpr (ADAPT) acc = __builtin_fmaf(r[D + 1], __builtin_amdgcn_exp2f(-(r[D] * q)), acc);
+    else acc = __builtin_fmaf(r[D], __builtin_amdgcn_exp2f(-q), acc);
+  }
+  return acc;
+}
+
+// The culled pair sum: kde_pairs_kernel's shape on the sorted points and rows, but each wave visits, of its split's
+// tiles, only those whose box lies within the cutoff of the wave's own box (sxkde::cutoff_visit, one lane per tile, 64
+// tiles at a time; the set bits of the ballot walked in tile order with the tile number made provably uniform, so that
+// the rows still come through scalar loads).  f32 within a tile, f64 across the visited tiles in tile order.  No
+// barrier: the waves of a workgroup take different tile lists.  Each wave adds the tiles it visited to one of
+// sxkde::kCutCounters counters (one integer atomic; one address would serialise every wave of the grid).
+template <int D, bool ADAPT>
+__global__ __launch_bounds__(kKdeBlock) void kde_pairs_cutoff_kernel(const float* __restrict__ pts,
+                                                                     unsigned long long pitch,
+                                                                     const float* __restrict__ rows,
+                                                                     const float* __restrict__ tile_box,
+                                                                     const float* __restrict__ wave_box,
+                                                                     unsigned tiles_per_split, unsigned ntiles,
+                                                                     float qcut, double* __restrict__ part,
+                                                                     unsigned long long* __restrict__ visited) {
+  constexpr int kRow = D + (ADAPT ? 2 : 1);
+  const unsigned long long i = (unsigned long long)blockIdx.x * kKdeBlock + threadIdx.x;
+  const unsigned lane = threadIdx.x & (kWave - 1);
+  float p[D];
+#pragma unroll
+  for (int k = 0; k < D; k++) p[k] = pts[(unsigned long long)k * pitch + i];
+  // the wave's own box (the wave number is the same in every lane: made so for the compiler too)
+  const unsigned wave = __builtin_amdgcn_readfirstlane(blockIdx.x * (kKdeBlock / kWave) + threadIdx.x / kWave);
+  const float* wb = wave_box + (unsigned long long)wave * sxkde::kCutWaveBox;
+  float wlo[D], whi[D];
+#pragma unroll
+  for (int k = 0; k < D; k++) {
+    wlo[k] = wb[k];
+    whi[k] = wb[sxkde::kCutMaxDim + k];
+  }
+  const unsigned t0 = blockIdx.y * tiles_per_split;
+  const unsigned t1 = t0 + tiles_per_split < ntiles ? t0 + tiles_per_split : ntiles;
+  double sum = 0.0;
+  unsigned nvisited = 0;
+  for (unsigned base = t0; base < t1; base += kWave) {
+    const unsigned t = base + lane;
+    bool visit = false;
+    if (t < t1) {
+      const float* b = tile_box + (unsigned long long)t * sxkde::kCutBox;
+      float tlo[D], thi[D];
+#pragma unroll
+      for (int k = 0; k < D; k++) {
+        tlo[k] = b[k];
+        thi[k] = b[sxkde::kCutMaxDim + k];
+      }
+      visit = sxkde::cutoff_visit<D>(tlo, thi, b[2 * sxkde::kCutMaxDim], wlo, whi, qcut);
+    }
+    unsigned long long mask = __builtin_amdgcn_ballot_w64(visit);
+    nvisited += (unsigned)__builtin_popcountll(mask);
+    while (mask != 0ull) {
+      const unsigned tt = __builtin_amdgcn_readfirstlane(base + (unsigned)__builtin_ctzll(mask));
+      mask &= mask - 1ull;
+      sum += (double)kde_tile_sum<D, ADAPT>(p, rows + (unsigned long long)tt * kKdeTile * kRow);
+    }
+  }
+  part[(unsigned long long)blockIdx.y * pitch + i] = sum;
+  if (lane == 0 && nvisited != 0u) {
+    unsigned long long* counter =
+        visited + ((blockIdx.x + blockIdx.y) % sxkde::kCutCounters) * (unsigned)sxkde::kCutCounterStride;
+    __hip_atomic_fetch_add(counter, (unsigned long long)nvisited, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+  }
+}
+
+// kde_combine_kernel for sorted points, one lane per sorted place j: the partial sums are read in that order and the
+// value goes to the caller's point order[j] (codes in the caller's order).
+__global__ __launch_bounds__(kKdeBlock) void kde_combine_sorted_kernel(const double* __restrict__ part,
+                                                                       unsigned long long pitch, int nsplit,
+                                                                       unsigned long long npoints,
+                                                                       const int* __restrict__ codes,
+                                                                       const unsigned* __restrict__ order,
+                                                                       const unsigned* __restrict__ norm,
+                                                                       double prefactor, float* __restrict__ out,
+                                                                       long stride) {
+  const unsigned long long j = (unsigned long long)blockIdx.x * kKdeBlock + threadIdx.x;
+  if (j >= npoints) return;
+  const unsigned long long i = order[j];
+  const int code = codes[i];
+  float v;
+  if (code == -2) {
+    v = 0.0f;
+  } else if (code < 0) {
+    v = __int_as_float(0x7fc00000);
+  } else {
+    double s = 0.0;
+    for (int k = 0; k < nsplit; k++) s += part[(unsigned long long)k * pitch + j];
+    const unsigned n = *norm;
+    v = n == 0u ? __int_as_float(0x7fc00000) : (float)(s * prefactor / (double)n);
+  }
+  out[stride * (long)i] = v;
+}
+
 }  // namespace
+
+hipError_t sx_kde_cutoff_gather(int D, bool adaptive, const float* rows, const unsigned* perm, unsigned ntiles,
+                                float* sorted, float* box, hipStream_t s) {
+  if (ntiles == 0) return hipSuccess;
+#define SX_KDE_CASE(N)                                                                                                  \
+  case N:                                                                                                               \
+    if (adaptive) hipLaunchKernelGGL((kde_cutoff_gather_kernel<N, true>), dim3(ntiles), dim3(kKdeBlock), 0, s, rows, perm, \
+                                     sorted, box);                                                                      \
+    else hipLaunchKernelGGL((kde_cutoff_gather_kernel<N, false>), dim3(ntiles), dim3(kKdeBlock), 0, s, rows, perm, sorted, \
+                            box);                                                                                       \
+    break;
+  switch (D) {
+    SX_KDE_CASE(1) SX_KDE_CASE(2) SX_KDE_CASE(3) SX_KDE_CASE(4)
+    default: return hipErrorInvalidValue;
+  }
+#undef SX_KDE_CASE
+  return hipGetLastError();
+}
+
+hipError_t sx_kde_pairs_cutoff(int D, bool adaptive, const float* pts, unsigned long long pitch, const float* rows,
+                               const float* tile_box, const float* wave_box, unsigned tiles_per_split, unsigned ntiles,
+                               int nsplit, float qcut, double* part, unsigned long long* visited, hipStream_t s) {
+  const dim3 grid((unsigned)(pitch / kKdeBlock), (unsigned)nsplit);
+#define SX_KDE_CASE(N)                                                                                                 \
+  case N:                                                                                                              \
+    if (adaptive) hipLaunchKernelGGL((kde_pairs_cutoff_kernel<N, true>), grid, dim3(kKdeBlock), 0, s, pts, pitch, rows,  \
+                                     tile_box, wave_box, tiles_per_split, ntiles, qcut, part, visited);                \
+    else hipLaunchKernelGGL((kde_pairs_cutoff_kernel<N, false>), grid, dim3(kKdeBlock), 0, s, pts, pitch, rows, tile_box, \
+                            wave_box, tiles_per_split, ntiles, qcut, part, visited);                                   \
+    break;
+  switch (D) {
+    SX_KDE_CASE(1) SX_KDE_CASE(2) SX_KDE_CASE(3) SX_KDE_CASE(4)
+    default: return hipErrorInvalidValue;
+  }
+#undef SX_KDE_CASE
+  return hipGetLastError();
+}
+
+hipError_t sx_kde_combine_sorted(const double* part, unsigned long long pitch, int nsplit, unsigned long long npoints,
+                                 const int* codes, const unsigned* order, const unsigned* norm, double prefactor,
+                                 float* out, long stride, hipStream_t s) {
+  if (npoints == 0) return hipSuccess;
+  const unsigned grid = (unsigned)((npoints + kKdeBlock - 1) / kKdeBlock);
+  hipLaunchKernelGGL(kde_combine_sorted_kernel, dim3(grid), dim3(kKdeBlock), 0, s, part, pitch, nsplit, npoints, codes,
+                     order, norm, prefactor, out, stride);
+  return hipGetLastError();
+}
 
 hipError_t sx_kde_prepass(const SxSignalDesc& d, const SxKdeArgs& a, hipStream_t s) {
   const unsigned long long nvec = a.npad / SXMC_VEC;

@@ -267,6 +267,19 @@ hipError_t sx_kde_pairs_adaptive(int D, const float* pts, unsigned long long pit
 hipError_t sx_kde_combine(const double* part, unsigned long long pitch, int nsplit, unsigned long long npoints,
                           const int* codes, const unsigned* norm, double prefactor, float* out, long stride,
                           hipStream_t s);
+// The cutoff radius (sxmc_kde_set_cutoff; kde_cutoff.h has the pure parts).  perm: [ntiles * 256] a permutation of the
+// sample rows; sorted: the rows in that order; box: [ntiles][sxkde::kCutBox] the tiles' boxes, written by the gather.
+hipError_t sx_kde_cutoff_gather(int D, bool adaptive, const float* rows, const unsigned* perm, unsigned ntiles,
+                                float* sorted, float* box, hipStream_t s);
+// pts: the sorted points; wave_box: [pitch / 64][sxkde::kCutWaveBox]; visited: the tiles visited, added to --
+// sxkde::kCutCounters counters, sxkde::kCutCounterStride 64-bit words apart.
+hipError_t sx_kde_pairs_cutoff(int D, bool adaptive, const float* pts, unsigned long long pitch, const float* rows,
+                               const float* tile_box, const float* wave_box, unsigned tiles_per_split, unsigned ntiles,
+                               int nsplit, float qcut, double* part, unsigned long long* visited, hipStream_t s);
+// order: [npoints] the caller's point that stands at each sorted place
+hipError_t sx_kde_combine_sorted(const double* part, unsigned long long pitch, int nsplit, unsigned long long npoints,
+                                 const int* codes, const unsigned* order, const unsigned* norm, double prefactor,
+                                 float* out, long stride, hipStream_t s);
 // Sampling from the last evaluation (sxmc_kde_random_sample): the in-domain rows listed by a flag, an inclusive scan
 // (temp: the scan's scratch, temp_bytes of it) and a scatter into idx; then one lane per event.
 struct SxKdeSampleArgs {

@@ -15,12 +15,20 @@
 // rows are read back from the table, the candidates' constants made on the host, the weights, the pair sums and the
 // logarithms on the device (kde_cv_* of kde_kernels.hip), the m logarithms of a candidate added here in table order.
 // The evaluator keeps sigma, its scales and the in-domain count from creation for it; its bandwidths never change.
+//
+// A cutoff radius (sxmc_kde_set_cutoff; the pure parts in kde_cutoff.h): the spatial order of the table rows is made on
+// the host when a cutoff is first set and kept on the device (shared evaluators hold the same buffer); the points are
+// planned in the same order by set_eval_points, which keeps the caller's points so that a change of R can plan them
+// again.  Everything an evaluation needs is allocated there: kde_launch allocates nothing.  At R = 0 the launches are
+// the ones above and the points stay in the caller's order.
 #include "sxmc_host.h"
 
 #include "kde_adaptive.h"
+#include "kde_cutoff.h"
 #include "kde_cv.h"
 
 #include <limits>
+#include <memory>
 
 using namespace sxhost;
 
@@ -71,6 +79,21 @@ struct sxmc_kde {
                                    // in-domain row numbers (one allocation, made at the first draw)
   DeviceBuffer<void> d_scan_temp;
   size_t scan_temp_bytes = 0;
+  // cutoff radius (sxmc_kde_set_cutoff): nothing of it is read at R = 0
+  double cutoff = 0;               // R
+  float qcut = 0;                  // sxkde::cutoff_qcut(R)
+  std::shared_ptr<DeviceBuffer<unsigned>> d_perm;   // [npad] the table rows in spatial order; one per table, shared
+  DeviceBuffer<float> d_sorted;    // [npad][rowlen()] the prepass's rows in that order (kde_cutoff_gather)
+  DeviceBuffer<float> d_tile_box;  // [npad / tile][kCutBox] the tiles' boxes of the last evaluation
+  DeviceBuffer<unsigned long long> d_visited;   // the tiles the last evaluation's waves visited: kCutCounters
+                                                // counters kCutCounterStride words apart, added on the host
+  std::vector<float> host_points;  // the caller's points as last set (a change of R plans them again)
+  bool points_sorted = false;      // the point plan in place is the sorted one
+  DeviceBuffer<unsigned> d_inv;    // [pitch] the caller's point that stands at each sorted place
+  DeviceBuffer<float> d_wave_box;  // [pitch / 64][kCutWaveBox] the boxes of the waves of sorted points
+  size_t live_waves = 0;           // waves with a live point
+  unsigned long long last_possible = 0;   // live_waves * tiles of the last evaluation (0 without a lookup or a cutoff)
+  bool last_cut = false;           // the last evaluation ran a lookup with a cutoff
   // projection (sxmc_kde_project): per-row scratch, partial sums, the result and the in-domain count (grow-only)
   DeviceBuffer<double> d_proj;
   ~sxmc_kde() { sxmc_hist_destroy(h); }   // (releases only: its buffers go by themselves, the table with its evaluator)
@@ -121,6 +144,121 @@ int cleared_rows(sxmc_kde* k) {
   const size_t n = k->npad * (size_t)k->rowlen();
   SX_BUF(k->d_rows.alloc(n));
   SX_HIP(hipMemset(k->d_rows.get(), 0, sizeof(float) * n));
+  return SXMC_OK;
+}
+
+constexpr size_t kVisitedWords = (size_t)sxkde::kCutCounters * sxkde::kCutCounterStride;
+
+// What an evaluation with a cutoff writes besides the rows: allocated once, cleared.
+int cutoff_buffers(sxmc_kde* k) {
+  const size_t ntiles = k->npad / SXMC_KDE_TILE;
+  if (!k->d_sorted.get()) {
+    const size_t n = k->npad * (size_t)k->rowlen();
+    SX_BUF(k->d_sorted.alloc(n));
+    SX_HIP(hipMemset(k->d_sorted.get(), 0, sizeof(float) * n));
+  }
+  if (!k->d_tile_box.get()) {
+    std::vector<float> box(ntiles * (size_t)sxkde::kCutBox, 1.0f);
+    for (size_t t = 0; t < ntiles; t++) sxkde::cutoff_empty_box(&box[t * sxkde::kCutBox], &box[t * sxkde::kCutBox + sxkde::kCutMaxDim]);
+    SX_BUF(k->d_tile_box.alloc(box.size()));
+    SX_HIP(hipMemcpy(k->d_tile_box.get(), box.data(), sizeof(float) * box.size(), hipMemcpyHostToDevice));
+  }
+  if (!k->d_visited.get()) {
+    SX_BUF(k->d_visited.alloc(kVisitedWords));
+    SX_HIP(hipMemset(k->d_visited.get(), 0, sizeof(unsigned long long) * kVisitedWords));
+  }
+  return SXMC_OK;
+}
+
+// The spatial order of the table rows (kde_cutoff.h), from the untransformed table read back, onto the device.
+int cutoff_sample_order(sxmc_kde* k) {
+  const int D = k->D;
+  const size_t n = k->nsamples;
+  SX_REQUIRE(k->npad <= 0xFFFFFFFFull, "EvalKernel: too many samples for a cutoff");
+  std::vector<float> cols((size_t)D * n), x((size_t)D * n);
+  for (int d = 0; d < D && n; d++) {   // (column d of the column-major table is observable d)
+    SX_HIP(hipMemcpy(cols.data() + (size_t)d * n, k->h->store->d_cols.get() + (size_t)d * k->h->pitch, sizeof(float) * n,
+                     hipMemcpyDeviceToHost));
+  }
+  for (size_t i = 0; i < n; i++) {
+    for (int d = 0; d < D; d++) x[i * (size_t)D + (size_t)d] = cols[(size_t)d * n + i];
+  }
+  const std::vector<uint32_t> order = sxkde::cutoff_sample_order(D, x.data(), (size_t)D, n, k->npad, k->h->lower.data(),
+                                                                 k->h->upper.data());
+  auto perm = std::make_shared<DeviceBuffer<unsigned>>();
+  SX_BUF(perm->alloc(k->npad));
+  SX_HIP(hipMemcpy(perm->get(), order.data(), sizeof(unsigned) * k->npad, hipMemcpyHostToDevice));
+  k->d_perm = perm;
+  return SXMC_OK;
+}
+
+// The points of k->host_points onto the device, in the caller's order (R = 0) or sorted with the waves' boxes and the
+// permutation (R > 0).  The evaluator is idle.
+int plan_points(sxmc_kde* k) {
+  const int D = k->D;
+  const size_t row = (size_t)D + 1;
+  const float* points = k->host_points.data();
+  const size_t n = k->host_points.size() / row;
+  // EvalHist's point codes (pdfz.cpp:264-301) with one bin of zero scale per observable: every point inside the
+  // domain of this data set lands in bin 0
+  const std::vector<double> zero((size_t)D, 0.0);
+  const std::vector<int> unit((size_t)D, 1);
+  std::vector<int> codes;
+  sxplan::eval_point_bins(points, n, D, k->h->lower.data(), k->h->upper.data(), zero.data(), unit.data(), 1,
+                          k->h->dataset, codes);
+  const size_t pitch = std::max<size_t>(256, (n + 255) / 256 * 256);
+  const bool sorted = k->cutoff > 0;
+  std::vector<uint32_t> order;   // (sorted) the point that stands at each sorted place
+  size_t nlive = 0;
+  if (sorted) order = sxkde::cutoff_point_order(D, points, n, codes.data(), k->h->lower.data(), k->h->upper.data(), &nlive);
+  std::vector<float> pts(pitch * (size_t)D, 0.0f);
+  for (size_t j = 0; j < n; j++) {
+    const size_t i = sorted ? order[j] : j;
+    if (codes[i] != 0) continue;
+    for (int d = 0; d < D; d++) {
+      const double c = ((double)points[i * row + (size_t)d] - k->h->lower[(size_t)d]) * (kLog2eHalfSqrt / k->bw[d]);
+      pts[(size_t)d * pitch + j] = (float)c;
+    }
+  }
+  codes.resize(pitch, -1);
+  int nsplit = 1;
+  unsigned tps = 1;
+  choose_split(pitch, k->npad / SXMC_KDE_TILE, k->cus, nsplit, tps);
+  if (sorted) sxkde::cutoff_split(pitch / 256, k->npad / SXMC_KDE_TILE, (unsigned long long)k->cus * 8, tps, nsplit);
+  k->has_points = false;   // (until the new ones are in place: a failure below leaves an evaluator without points)
+  if (pitch > k->d_codes.capacity()) {   // (the two grow together, both freed first; d_codes, allocated last, says whether both are there)
+    SX_BUF(k->d_pts.reset());
+    SX_BUF(k->d_codes.reset());
+    SX_BUF(k->d_pts.alloc(pitch * (size_t)D));
+    SX_BUF(k->d_codes.alloc(pitch));
+  }
+  SX_BUF(k->d_part.grow((size_t)nsplit * pitch));
+  SX_HIP(hipMemcpy(k->d_pts.get(), pts.data(), sizeof(float) * pts.size(), hipMemcpyHostToDevice));
+  SX_HIP(hipMemcpy(k->d_codes.get(), codes.data(), sizeof(int) * pitch, hipMemcpyHostToDevice));
+  k->live_waves = 0;
+  if (sorted) {
+    const size_t nwaves = pitch / sxkde::kCutWave;
+    std::vector<unsigned> place(pitch, 0u);
+    for (size_t j = 0; j < n; j++) place[j] = order[j];
+    std::vector<unsigned char> live(pitch, 0);
+    for (size_t j = 0; j < nlive; j++) live[j] = 1;   // (the live points stand first)
+    std::vector<float> box(nwaves * (size_t)sxkde::kCutWaveBox);
+    for (size_t w = 0; w < nwaves; w++) {
+      sxkde::cutoff_wave_box(D, pts.data(), pitch, w * sxkde::kCutWave, sxkde::kCutWave, live.data(),
+                             &box[w * sxkde::kCutWaveBox]);
+      if (w * sxkde::kCutWave < nlive) k->live_waves++;
+    }
+    SX_BUF(k->d_inv.grow(pitch));
+    SX_BUF(k->d_wave_box.grow(box.size()));
+    SX_HIP(hipMemcpy(k->d_inv.get(), place.data(), sizeof(unsigned) * pitch, hipMemcpyHostToDevice));
+    SX_HIP(hipMemcpy(k->d_wave_box.get(), box.data(), sizeof(float) * box.size(), hipMemcpyHostToDevice));
+  }
+  k->points_sorted = sorted;
+  k->npoints = n;
+  k->pitch = pitch;
+  k->nsplit = nsplit;
+  k->tiles_per_split = tps;
+  k->has_points = true;
   return SXMC_OK;
 }
 
@@ -321,6 +459,13 @@ int sxmc_kde_create_shared(sxmc_kde_t base, sxmc_kde_t* out) {
   }
   rc = cleared_rows(k.get());
   if (rc) return rc;
+  if (base->cutoff > 0) {   // the base's R on the base's order
+    k->d_perm = base->d_perm;
+    rc = cutoff_buffers(k.get());
+    if (rc) return rc;
+    k->cutoff = base->cutoff;
+    k->qcut = base->qcut;
+  }
   *out = k.release();
   return SXMC_OK;
 }
@@ -359,44 +504,11 @@ int sxmc_kde_set_eval_points(sxmc_kde_t k, const float* points, size_t npoints_f
   SX_REQUIRE(npoints_floats == 0 || points, "null points");
   const size_t n = npoints_floats / row;
   SX_REQUIRE(n <= (size_t)INT_MAX, "too many evaluation points");
-  // EvalHist's point codes (pdfz.cpp:264-301) with one bin of zero scale per observable: every point inside the
-  // domain of this data set lands in bin 0
-  const std::vector<double> zero((size_t)D, 0.0);
-  const std::vector<int> unit((size_t)D, 1);
-  std::vector<int> codes;
-  sxplan::eval_point_bins(points, n, D, k->h->lower.data(), k->h->upper.data(), zero.data(), unit.data(), 1,
-                          k->h->dataset, codes);
-  const size_t pitch = std::max<size_t>(256, (n + 255) / 256 * 256);
-  std::vector<float> pts(pitch * (size_t)D, 0.0f);
-  codes.resize(pitch, -1);
-  for (size_t i = 0; i < n; i++) {
-    if (codes[i] != 0) continue;
-    for (int d = 0; d < D; d++) {
-      const double c = ((double)points[i * row + (size_t)d] - k->h->lower[(size_t)d]) * (kLog2eHalfSqrt / k->bw[d]);
-      pts[(size_t)d * pitch + i] = (float)c;
-    }
-  }
-  int nsplit = 1;
-  unsigned tps = 1;
-  choose_split(pitch, k->npad / SXMC_KDE_TILE, k->cus, nsplit, tps);
   if (int rc_ = order_after_caller(k)) return rc_;
   SX_HIP(hipStreamSynchronize(k->h->stream));   // (an evaluation in flight reads the arrays replaced here)
-  k->has_points = false;   // (until the new ones are in place: a failure below leaves an evaluator without points)
-  if (pitch > k->d_codes.capacity()) {   // (the two grow together, both freed first; d_codes, allocated last, says whether both are there)
-    SX_BUF(k->d_pts.reset());
-    SX_BUF(k->d_codes.reset());
-    SX_BUF(k->d_pts.alloc(pitch * (size_t)D));
-    SX_BUF(k->d_codes.alloc(pitch));
-  }
-  SX_BUF(k->d_part.grow((size_t)nsplit * pitch));
-  SX_HIP(hipMemcpy(k->d_pts.get(), pts.data(), sizeof(float) * pts.size(), hipMemcpyHostToDevice));
-  SX_HIP(hipMemcpy(k->d_codes.get(), codes.data(), sizeof(int) * pitch, hipMemcpyHostToDevice));
-  k->npoints = n;
-  k->pitch = pitch;
-  k->nsplit = nsplit;
-  k->tiles_per_split = tps;
-  k->has_points = true;
-  return SXMC_OK;
+  k->has_points = false;
+  k->host_points.assign(points, points + npoints_floats);
+  return plan_points(k);
 }
 
 int sxmc_kde_set_pdf_value_buffer(sxmc_kde_t k, float* d_output, int offset, int stride) {
@@ -451,15 +563,30 @@ int kde_launch(sxmc_kde* k, int do_eval_pdf, hipStream_t s) {
   SX_HIP(sx_kde_prepass(d, a, s));
   if (lookup) {
     const unsigned ntiles = (unsigned)(k->npad / SXMC_KDE_TILE);
-    if (k->d_lambda.get()) {
+    if (k->cutoff > 0) {
+      if (!k->points_sorted || !k->d_perm) return fail(SXMC_ERR_STATE, "EvalKernel: the cutoff's point plan is missing");
+      const bool adaptive = k->d_lambda.get() != nullptr;
+      SX_HIP(hipMemsetAsync(k->d_visited.get(), 0, sizeof(unsigned long long) * kVisitedWords, s));
+      SX_HIP(sx_kde_cutoff_gather(k->D, adaptive, k->d_rows.get(), k->d_perm->get(), ntiles, k->d_sorted.get(),
+                                  k->d_tile_box.get(), s));
+      SX_HIP(sx_kde_pairs_cutoff(k->D, adaptive, k->d_pts.get(), k->pitch, k->d_sorted.get(), k->d_tile_box.get(),
+                                 k->d_wave_box.get(), k->tiles_per_split, ntiles, k->nsplit, k->qcut, k->d_part.get(),
+                                 k->d_visited.get(), s));
+      SX_HIP(sx_kde_combine_sorted(k->d_part.get(), k->pitch, k->nsplit, k->npoints, k->d_codes.get(), k->d_inv.get(),
+                                   a.norm, k->prefactor, k->pdf + k->pdf_off, (long)k->pdf_stride, s));
+    } else if (k->d_lambda.get()) {
       SX_HIP(sx_kde_pairs_adaptive(k->D, k->d_pts.get(), k->pitch, k->d_rows.get(), k->tiles_per_split, ntiles, k->nsplit,
                                    k->d_part.get(), s));
     } else {
       SX_HIP(sx_kde_pairs(k->D, k->d_pts.get(), k->pitch, k->d_rows.get(), k->tiles_per_split, ntiles, k->nsplit, k->d_part.get(), s));
     }
-    SX_HIP(sx_kde_combine(k->d_part.get(), k->pitch, k->nsplit, k->npoints, k->d_codes.get(), a.norm, k->prefactor,
-                          k->pdf + k->pdf_off, (long)k->pdf_stride, s));
+    if (!(k->cutoff > 0)) {
+      SX_HIP(sx_kde_combine(k->d_part.get(), k->pitch, k->nsplit, k->npoints, k->d_codes.get(), a.norm, k->prefactor,
+                            k->pdf + k->pdf_off, (long)k->pdf_stride, s));
+    }
   }
+  k->last_cut = lookup && k->cutoff > 0;
+  k->last_possible = k->last_cut ? (unsigned long long)k->live_waves * (k->npad / SXMC_KDE_TILE) : 0ull;
   k->evaluated = true;
   k->evaluations++;
   return SXMC_OK;
@@ -554,6 +681,57 @@ int sxmc_kde_local_factors(sxmc_kde_t k, double* lambda, size_t n) {
 int sxmc_kde_nsamples(sxmc_kde_t k, size_t* v) {
   SX_REQUIRE(k && v, "null argument");
   *v = k->nsamples;
+  return SXMC_OK;
+}
+int sxmc_kde_set_cutoff(sxmc_kde_t k, double R) {
+  SX_REQUIRE(sxkde::valid_cutoff(R), "Bandwidth cutoff must be 0 or a number >= 1 (infinity allowed).");
+  SX_REQUIRE(k, "null evaluator");
+  if (t_capturing) return fail(SXMC_ERR_STATE, "EvalKernel: not while recording a graph");
+  if (int rc_ = order_after_caller(k)) return rc_;
+  SX_HIP(hipStreamSynchronize(k->h->stream));
+  k->own_pending = false;
+  if (R > 0) {
+    if (!k->d_perm) {
+      if (int rc_ = cutoff_sample_order(k)) return rc_;
+    }
+    if (int rc_ = cutoff_buffers(k)) return rc_;
+  }
+  const bool replan = k->has_points && (R > 0) != k->points_sorted;
+  k->cutoff = R;
+  k->qcut = sxkde::cutoff_qcut(R);
+  if (replan) return plan_points(k);
+  return SXMC_OK;
+}
+int sxmc_kde_cutoff(sxmc_kde_t k, double* R) {
+  SX_REQUIRE(k && R, "null argument");
+  *R = k->cutoff;
+  return SXMC_OK;
+}
+int sxmc_kde_cutoff_stats(sxmc_kde_t k, unsigned long long* tiles_visited, unsigned long long* tiles_possible) {
+  SX_REQUIRE(k && tiles_visited && tiles_possible, "null argument");
+  *tiles_visited = 0;
+  *tiles_possible = 0;
+  if (!k->evaluated || !k->last_cut) return SXMC_OK;
+  if (int rc_ = order_after_caller(k)) return rc_;
+  SX_HIP(hipStreamSynchronize(k->h->stream));
+  std::vector<unsigned long long> counters(kVisitedWords);
+  SX_HIP(hipMemcpy(counters.data(), k->d_visited.get(), sizeof(unsigned long long) * kVisitedWords, hipMemcpyDeviceToHost));
+  for (int c = 0; c < sxkde::kCutCounters; c++) *tiles_visited += counters[(size_t)c * sxkde::kCutCounterStride];
+  *tiles_possible = k->last_possible;
+  return SXMC_OK;
+}
+int sxmc_kde_cutoff_boxes(sxmc_kde_t k, float* tile_boxes, size_t ntile_floats, float* wave_boxes, size_t nwave_floats) {
+  SX_REQUIRE(k && tile_boxes && wave_boxes, "null argument");
+  if (!(k->cutoff > 0) || !k->has_points || !k->points_sorted) {
+    return fail(SXMC_ERR_STATE, "EvalKernel: no boxes without a cutoff and evaluation points");
+  }
+  SX_REQUIRE(ntile_floats == k->npad / SXMC_KDE_TILE * (size_t)sxkde::kCutBox &&
+                 nwave_floats == k->pitch / sxkde::kCutWave * (size_t)sxkde::kCutWaveBox,
+             "cutoff box buffer size mismatch");
+  if (int rc_ = order_after_caller(k)) return rc_;
+  SX_HIP(hipStreamSynchronize(k->h->stream));
+  SX_HIP(hipMemcpy(tile_boxes, k->d_tile_box.get(), sizeof(float) * ntile_floats, hipMemcpyDeviceToHost));
+  SX_HIP(hipMemcpy(wave_boxes, k->d_wave_box.get(), sizeof(float) * nwave_floats, hipMemcpyDeviceToHost));
   return SXMC_OK;
 }
 int sxmc_kde_npoints(sxmc_kde_t k, size_t* v) {

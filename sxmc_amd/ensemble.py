@@ -116,6 +116,8 @@ def make_evaluators(workload):
                 scale = s.bandwidth_scale if s.bandwidth_scale is not None else [1.0] * w.nobs
                 ev = pdfz.EvalKernel(s.samples, s.nfields, w.nobs, w.lower, w.upper, scale, dataset=s.dataset,
                                      bandwidth_sensitivity=alpha)
+            if getattr(s, "bandwidth_cutoff", 0.0) != 0.0:
+                ev.SetCutoff(s.bandwidth_cutoff)
         else:
             ev = pdfz.EvalHist(s.samples, s.nfields, w.nobs, w.lower, w.upper, w.nbins, dataset=s.dataset)
         for d in w.systematics:

@@ -786,6 +786,18 @@ inline void signal_sensitivity_from_json(Signal& s, const json::Value& c) {
   }
   s.bandwidth_sensitivity = v;
 }
+/** A kernel signal's "bandwidth_cutoff": the cutoff radius R of pdfz::EvalKernel's pair sum in bandwidths
+ *  (EvalKernel::SetCutoff): 0, or a number >= 1, infinity included; absent: 0, no cutoff.  Refused on a histogram signal.
+ *  After signal_pdf_from_json (it reads s.pdf). */
+inline void signal_cutoff_from_json(Signal& s, const json::Value& c) {
+  const std::string who = "signal '" + s.name + "': ";
+  s.bandwidth_cutoff = 0.0;
+  if (!c.isMember("bandwidth_cutoff")) return;
+  if (s.pdf != "kernel") throw ConfigError(who + "\"bandwidth_cutoff\" is only for \"pdf\": \"kernel\"");
+  const double v = c["bandwidth_cutoff"].asDouble("bandwidth_cutoff");
+  if (!(v == 0.0 || v >= 1.0)) throw ConfigError(who + "\"bandwidth_cutoff\" must be 0 or a number >= 1");
+  s.bandwidth_cutoff = v;
+}
 /** A kernel signal's "bandwidth_cv", the grid and the search behind "bandwidth_scale": "cv" -- an object with any of
  *  "lo", "hi", "steps", "per_observable" (default true) and "max_rows" (default 65536; 0: all rows).  Refused on a
  *  histogram signal, without "bandwidth_scale": "cv", with another key or with a bad grid.  After signal_pdf_from_json. */
@@ -939,6 +951,7 @@ inline FitConfig parse_config(const std::string& text, const std::string& base_d
     detail::signal_pdf_from_json(s, c, fc.observables.size());
     detail::signal_sensitivity_from_json(s, c);
     detail::signal_cv_from_json(s, c);
+    detail::signal_cutoff_from_json(s, c);
     const std::string source_name = c.get("source", name.c_str());
     for (const Source& src : fc.sources)
       if (src.name == source_name) {

@@ -63,6 +63,7 @@ struct Signal {
   std::string pdf = "hist";                   //!< "hist": pdfz::EvalHist; "kernel": pdfz::EvalKernel (kernel density)
   std::vector<double> bandwidth_scale;        //!< "kernel": one per fit observable, in fit-observable order (empty: 1.0)
   double bandwidth_sensitivity = 0.0;         //!< "kernel": alpha of the adaptive bandwidths in [0, 1]; 0: fixed
+  double bandwidth_cutoff = 0.0;              //!< "kernel": cutoff radius of the pair sum in bandwidths; 0: none
   bool bandwidth_cv = false;                  //!< "kernel": bandwidth_scale is still to be chosen by cross-validation
                                               //!< (build_pdfz chooses, writes bandwidth_scale and clears the flag)
   pdfz::EvalKernel::CvOptions cv;             //!< ... on this grid, with this search
@@ -74,7 +75,7 @@ struct Signal {
 /** Signal::build_pdfz (signal.cpp:112-170): the evaluator of one signal with every systematic attached -- a
  *  pdfz::EvalHist, or a pdfz::EvalKernel when sig.pdf is "kernel" (bandwidth scales from sig.bandwidth_scale, or chosen by
  *  cross-validation when sig.bandwidth_cv is set; the sensitivity of its adaptive bandwidths from
- *  sig.bandwidth_sensitivity).
+ *  sig.bandwidth_sensitivity, the cutoff radius of its pair sum from sig.bandwidth_cutoff).
  *  `samples` is the row-major [n][nfields] table, observables first. */
 inline void build_pdfz(Signal& sig, const std::vector<float>& samples, int nfields,
                        const std::vector<Observable>& observables, std::vector<Systematic>& systematics) {
@@ -107,6 +108,7 @@ inline void build_pdfz(Signal& sig, const std::vector<float>& samples, int nfiel
     } else {
       h = new pdfz::EvalKernel(samples, nfields, (int)D, lower, upper, scale, sig.dataset, sig.bandwidth_sensitivity);
     }
+    if (sig.bandwidth_cutoff != 0.0) static_cast<pdfz::EvalKernel*>(h)->SetCutoff(sig.bandwidth_cutoff);
   } else if (sig.pdf == "hist") {
     h = new pdfz::EvalHist(samples, nfields, (int)observables.size(), lower, upper, nbins, sig.dataset);
   } else {

@@ -468,7 +468,38 @@ struct KernelCvResult {
  *  scales had been typed in.  Deterministic: no floating-point atomics, the split over workgroups depends on m and the
  *  candidate count alone, partial sums are added in split order and the m logarithms on the host in table order -- two
  *  calls, a Share()d evaluator and any device give the same score bits.  An evaluator's own bandwidths never change.
- *  Accuracy: the bound of tests/kde_cv_reference.py.  Cost O(m^2 K) per scan of K candidates. */
+ *  Accuracy: the bound of tests/kde_cv_reference.py.  Cost O(m^2 K) per scan of K candidates.
+ *
+ *  Cutoff radius: SetCutoff(R), R in units of each sample's own bandwidth (h_d, or h_d lambda_i when adaptive).  Opt-in,
+ *  and an approximation whose error is the bound stated here.  R = 0, the default, is everything above: the same
+ *  kernels, the same row layout, the same bits.  Accepted: 0, or 1 <= R <= +infinity; anything else, NaN included, throws.
+ *    qcut   = R^2 log2(e) / 2, as an f32 rounded up.
+ *    q'     of a pair = g_i sum_d (c_pd - c_id)^2 exactly as the pair kernels compute it in f32, c the coordinates
+ *             scaled by sqrt(log2(e) / 2) / h_d and g_i = 1 / lambda_i^2 (1 for fixed bandwidths).
+ *    A pair is dropped only if the kernel's own f32 q' for it would have been >= qcut; pairs below qcut are always
+ *    summed.  A value therefore lies between the full sum and the sum over the pairs with q' < qcut, and each dropped
+ *    term is at most W_i 2^-qcut.  The PDF no longer integrates to exactly 1: it falls short by at most the dropped
+ *    mass.  From R = 15 (qcut > 149) every dropped exp2 is exactly 0 in f32 and the values are those of R = +infinity
+ *    bit for bit; R = +infinity drops nothing but sums in the sorted order below.
+ *  Pairs are dropped a 256-sample tile at a time, against a wave of 64 points at a time.  When a cutoff is first set the
+ *  host orders the table rows by their untransformed coordinates clamped to the domain (a plain sort for one observable,
+ *  else the Morton order of a fixed cell grid over [lower, upper); stable, ties by table index), once per table; it is
+ *  kept on the device and Share()d evaluators use it and copy R.  Per evaluation, after the unchanged prepass, one more
+ *  launch copies the rows into that order and writes each tile's box from the MOVED samples (min and max of c_d over
+ *  the rows with weight > 0, their smallest g when adaptive), which makes the culling exact under any systematic; a tile
+ *  without such a row is never visited.  SetEvalPoints sorts the live points by the same key, the others last, with one
+ *  box per wave over live points only; values still go to pdf_out[offset + stride * i] for the caller's i.  Per wave and
+ *  tile gap_d = max(0, tile_lo_d - wave_hi_d, wave_lo_d - tile_hi_d), and q_lb from the gaps by the pair's own operation
+ *  sequence times the tile's smallest g; rounding is monotone, so every pair of that wave and tile has q' >= q_lb with
+ *  no margin, and the tile is visited iff q_lb < qcut (sxmc_amd/csrc/kde_cutoff.h).  f32 within a visited tile, f64
+ *  across the visited tiles in tile order.
+ *  What does not change: the norm, the point codes, the NaN and 0 rules, norm == 0; Bandwidths, LocalFactors,
+ *  cross-validation and the pilot; SampleEvents and Project, which keep reading the prepass's rows in table order and
+ *  return the bytes of the same evaluator at R = 0.  What does: a point's value depends on which other points share its
+ *  wave, always inside the envelope above.  Two evaluations, a shared evaluator and any device still give the same bits:
+ *  no floating-point atomics, and the tiles a wave visits depend on the data alone.  EvalOnStream stays capture-safe:
+ *  every buffer is allocated by SetCutoff or SetEvalPoints.  SetCutoff needs an idle evaluator and throws while a graph
+ *  is being recorded; it plans the points again if they are already set.  Accuracy: tests/kde_cutoff_reference.py. */
 class EvalKernel : public detail::EvalOver<detail::KernelApi> {
  public:
   typedef KernelCvOptions CvOptions;
@@ -604,6 +635,18 @@ class EvalKernel : public detail::EvalOver<detail::KernelApi> {
     unsigned long long n = 0;
     throw_on(sxmc_kde_evaluation_count(handle, &n));
     return n;
+  }
+
+  /** The cutoff radius (class comment, "Cutoff radius"; sxmc_kde_set_cutoff): 0 off, or 1 <= R <= +infinity. */
+  void SetCutoff(double R) { throw_on(sxmc_kde_set_cutoff(handle, R)); }
+  double Cutoff() const {
+    double R = 0.0;
+    throw_on(sxmc_kde_cutoff(handle, &R));
+    return R;
+  }
+  /** Of the last evaluation: the tiles its waves visited, and live point-waves x tiles; both 0 without a cutoff. */
+  void CutoffStats(unsigned long long& tiles_visited, unsigned long long& tiles_possible) const {
+    throw_on(sxmc_kde_cutoff_stats(handle, &tiles_visited, &tiles_possible));
   }
 
   /** The bandwidths h_d fixed at construction (Scott's rule). */

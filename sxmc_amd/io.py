@@ -161,6 +161,21 @@ def signal_sensitivity(name, c, pdf):
     return v
 
 
+def signal_cutoff(name, c, pdf):
+    """A kernel signal's "bandwidth_cutoff": the cutoff radius R of pdfz.EvalKernel's pair sum in bandwidths
+    (EvalKernel.SetCutoff): 0, or a number >= 1, infinity included; absent: 0.0, no cutoff.  Refused on a histogram
+    signal.  Same rules and messages as sxmc::detail::signal_cutoff_from_json (config.h)."""
+    who = "signal '%s': " % name
+    if "bandwidth_cutoff" not in c:
+        return 0.0
+    if pdf != "kernel":
+        raise ValueError(who + '"bandwidth_cutoff" is only for "pdf": "kernel"')
+    v = _number(c["bandwidth_cutoff"], "bandwidth_cutoff")
+    if not (v == 0.0 or v >= 1.0):
+        raise ValueError(who + '"bandwidth_cutoff" must be 0 or a number >= 1')
+    return v
+
+
 def _integer(v, what):
     """json::Value::asInt of config.h."""
     d = _number(v, what)
@@ -312,7 +327,8 @@ def load_config(path_or_text, base_dir=None):
             source=next(s for s in fc.sources if s["name"] == src_name),
             pdf=pdf, bandwidth_scale=bandwidth_scale,
             bandwidth_sensitivity=signal_sensitivity(name, c, pdf),
-            bandwidth_cv=signal_cv(name, c, pdf)))
+            bandwidth_cv=signal_cv(name, c, pdf),
+            bandwidth_cutoff=signal_cutoff(name, c, pdf)))
     fc.data = {int(k): [dict(filename=row["filename"], title=row.get("title", "")) for row in rows]
                for k, rows in root.get("data", {}).items()}
     fc.base_dir = base_dir or "."
@@ -339,7 +355,8 @@ def build_workload(fc):
         sig = workloads.Signal(samples, nfields, nexpected, s["source"]["index"], dataset=s["dataset"],
                                pdf=s.get("pdf", "hist"), bandwidth_scale=scale,
                                bandwidth_sensitivity=s.get("bandwidth_sensitivity", 0.0),
-                               bandwidth_cv=s.get("bandwidth_cv"))
+                               bandwidth_cv=s.get("bandwidth_cv"),
+                               bandwidth_cutoff=s.get("bandwidth_cutoff", 0.0))
         sig.n_mc_total = n_mc
         sig.name = s["name"]
         signals.append(sig)

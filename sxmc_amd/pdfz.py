@@ -383,6 +383,31 @@ class EvalKernel(_Eval):
         self._call("local_factors", capi.ptr(out), out.size)
         return out
 
+    def SetCutoff(self, R):
+        """A cutoff radius on the pair sum in units of each sample's own bandwidth (sxmc_kde_set_cutoff, contract in
+        include/sxmc_hip.h): 0 turns it off (the evaluator as it was, bit for bit), 1 <= R <= inf drops pairs at least
+        R bandwidths apart, a 256-sample tile against a wave of 64 points at a time.  The evaluator must be idle."""
+        self._call("set_cutoff", float(R))
+
+    def Cutoff(self):
+        """R (a shared evaluator: its base's when it was made)."""
+        return self._get("cutoff", C.c_double)
+
+    def CutoffStats(self):
+        """(tiles_visited, tiles_possible) of the last evaluation; (0, 0) when it ran without a cutoff or a lookup."""
+        visited, possible = C.c_ulonglong(0), C.c_ulonglong(0)
+        self._call("cutoff_stats", C.byref(visited), C.byref(possible))
+        return visited.value, possible.value
+
+    def CutoffBoxes(self):
+        """(tile boxes [tiles, 9], wave boxes [waves, 8]) as float32: lo[4], hi[4] (and a tile's smallest g) of the
+        last evaluation's sorted sample tiles and of the point plan's waves (sxmc_kde_cutoff_boxes; for tests)."""
+        ntiles = max(1, -(-self.nsamples // 256))
+        nwaves = max(256, -(-self.npoints // 256) * 256) // 64
+        tiles, waves = np.zeros((ntiles, 9), np.float32), np.zeros((nwaves, 8), np.float32)
+        self._call("cutoff_boxes", capi.ptr(tiles), tiles.size, capi.ptr(waves), waves.size)
+        return tiles, waves
+
     def Bandwidths(self):
         """h_d = bandwidth_scale_d * sigma_d * n^(-1/(D+4)) (Scott's rule), fixed at construction."""
         out = np.empty(self.nobservables, dtype=np.float64)

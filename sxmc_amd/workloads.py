@@ -11,7 +11,7 @@ class Signal:
     """One signal's MC sample table + how it enters the fit."""
 
     def __init__(self, samples, nfields, nexpected, source_id, dataset=0, pdf="hist", bandwidth_scale=None,
-                 bandwidth_sensitivity=0.0, bandwidth_cv=None):
+                 bandwidth_sensitivity=0.0, bandwidth_cv=None, bandwidth_cutoff=0.0):
         self.samples = samples              # float32 [n, nfields] row-major
         self.nfields = nfields
         self.nexpected = float(nexpected)
@@ -28,6 +28,8 @@ class Signal:
         # bandwidth_scale and the report in cv_report, and sets this back to None
         self.bandwidth_cv = None if bandwidth_cv is None else dict(bandwidth_cv)
         self.cv_report = None
+        # "kernel": the cutoff radius of the pair sum in bandwidths (pdfz.EvalKernel.SetCutoff); 0: none
+        self.bandwidth_cutoff = float(bandwidth_cutoff)
 
     @property
     def n_mc(self):

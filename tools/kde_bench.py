@@ -26,8 +26,13 @@ logarithms back and added); scan_over_k_pilots = ms_scan / (21 ms_pilot), and th
 table row against the in-domain rows, a scan the in-domain rows against themselves); ms_search_all_rows and
 ms_search_default, the host clock around SelectBandwidthScale with max_rows = 0 and with the default max_rows, and what
 they chose.
+--cutoff: instead of all the above, the cutoff radius (EvalKernel.SetCutoff) at the default shape, fixed and adaptive
+bandwidths in one process (one JSON line, tool "kde_bench_cutoff"): per R in 0, 0 again (the run-to-run spread), +inf
+(every pair, in sorted order: the price of the gather and the mask walk), 6 and 4 the ms per evaluation measured as
+above, tiles_visited / tiles_possible of the last evaluation, and the largest relative change of a value against
+R = 0; and the host clock around SetEvalPoints without and with the point-side sort.
 Usage: python tools/kde_bench.py [--samples N] [--points E] [--seconds S] [--cpu-points K] [--sample-events M]
-                                 [--project-bins B] [--adaptive] [--sensitivity A] [--cv]"""
+                                 [--project-bins B] [--adaptive] [--sensitivity A] [--cv] [--cutoff]"""
 import argparse
 import json
 import math
@@ -131,6 +136,50 @@ def measure_cv(a, samples, F, D, lower, upper):
                 device=capi.device_info(0)["name"])
 
 
+def measure_cutoff(a, samples, F, D, lower, upper, pts, params):
+    """The result line of --cutoff: fixed and adaptive, ms per evaluation at R = 0 (twice: the run-to-run spread),
+    +inf (the price of the gather and the mask walk), 6 and 4, with the visited share of the tiles and the largest
+    relative change of a value against R = 0 over the values above 1e-3 of the largest."""
+    e = pts.shape[0]
+    par = DeviceArray(params)
+    out = dict(tool="kde_bench_cutoff", samples=samples.shape[0], points=e, observables=D,
+               systematics=["shift", "scale", "resolution_scale"], device=capi.device_info(0)["name"])
+    for mode, alpha in (("fixed", 0.0), ("adaptive", a.sensitivity)):
+        ev = pdfz.EvalKernel(samples.ravel(), F, D, lower, upper, [1.0] * D, bandwidth_sensitivity=alpha)
+        ev.AddSystematic(pdfz.ShiftSystematic(1, [0]))
+        ev.AddSystematic(pdfz.ScaleSystematic(0, [1]))
+        ev.AddSystematic(pdfz.ResolutionScaleSystematic(0, 2, [2]))
+        c0 = time.perf_counter()
+        ev.SetEvalPoints(pts.ravel())
+        ms_points_plain = 1e3 * (time.perf_counter() - c0)
+        pdf, norm = DeviceArray.zeros(e, np.float32), DeviceArray.zeros(1, np.uint32)
+        ev.SetPDFValueBuffer(pdf)
+        ev.SetNormalizationBuffer(norm)
+        ev.SetParameterBuffer(par)
+        rows, base = [], None
+        for label, R in (("0", 0.0), ("0_again", 0.0), ("inf", math.inf), ("6", 6.0), ("4", 4.0)):
+            c0 = time.perf_counter()
+            ev.SetCutoff(R)
+            ms_set = 1e3 * (time.perf_counter() - c0)
+            ms, calls = eval_window(ev, a.seconds)
+            visited, possible = ev.CutoffStats()
+            v = pdf.get().astype(np.float64)
+            if base is None:
+                base = v
+            big = base >= 1e-3 * np.nanmax(base)
+            rows.append(dict(R=label, ms_per_eval=round(ms, 4), evaluations=calls, ms_set_cutoff=round(ms_set, 3),
+                             tiles_visited=visited, tiles_possible=possible,
+                             visited_fraction=round(visited / possible, 5) if possible else None,
+                             worst_relative_change=float(np.max(np.abs(v[big] - base[big]) / base[big])),
+                             norm=int(norm.get()[0])))
+        c0 = time.perf_counter()
+        ev.SetEvalPoints(pts.ravel())
+        out[mode] = dict(rows=rows, ms_set_eval_points_plain=round(ms_points_plain, 3),
+                         ms_set_eval_points_sorted=round(1e3 * (time.perf_counter() - c0), 3))
+        ev.close()
+    return out
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--samples", type=int, default=1 << 17)
@@ -142,6 +191,7 @@ def main():
     ap.add_argument("--adaptive", action="store_true")
     ap.add_argument("--sensitivity", type=float, default=0.5)
     ap.add_argument("--cv", action="store_true")
+    ap.add_argument("--cutoff", action="store_true")
     a = ap.parse_args()
     if capi.device_count() < 1:
         raise SystemExit("kde_bench.py needs a GPU")
@@ -153,6 +203,10 @@ def main():
     lower, upper = [0.0, -1.0], [10.0, 1.0]
     if a.cv:
         print(json.dumps(measure_cv(a, samples, F, D, lower, upper)))
+        return
+    if a.cutoff:
+        pts = np.stack([rng.uniform(0, 10, e), rng.uniform(-1, 1, e), np.zeros(e)], axis=1).astype(np.float32)
+        print(json.dumps(measure_cutoff(a, samples, F, D, lower, upper, pts, np.array([0.01, 0.02, 0.05]))))
         return
     ev = pdfz.EvalKernel(samples.ravel(), F, D, lower, upper, [1.0, 1.0])
     ev.AddSystematic(pdfz.ShiftSystematic(1, [0]))
