@@ -14,26 +14,32 @@
 //                 codes of EvalHist::SetEvalPoints (-1 NaN, -2 zero); norm == 0 gives NaN.
 // No floating-point atomics and no order that depends on timing: two evaluations give the same bits.
 // Sampling (sxmc_kde_random_sample) and the projection onto one observable (sxmc_kde_project) follow the evaluation.
+// A kernel templated on the observables D (and on ADAPT) is picked from the run-time values by kde_for_dim /
+// kde_for_dim_adapt below, the one place that does so.
 //
 // Adaptive evaluators (bandwidth sensitivity > 0, sxmc_kde_create_adaptive) give every table row i a factor lambda_i on
 // the bandwidths, fixed at construction by kde_pilot (at the end of this file) and kept in d_lambda.  Their prepass
 // (ADAPT = true) writes rows of D + 2 floats -- the same c_d in units of the global h_d, g_i = 1 / lambda_i^2 and
-// W_i = w_i / lambda_i^D with the mass taken at h_d lambda_i -- and kde_pairs_adaptive sums W_i exp2(-g_i q); the
+// W_i = w_i / lambda_i^D with the mass taken at h_d lambda_i -- and kde_pairs<D, true> sums W_i exp2(-g_i q); the
 // sampler and the projection read lambda in f64.  A fixed-bandwidth evaluator never runs an ADAPT instantiation.
 //
 // Bandwidth cross-validation (sxmc_kde_cv_scores / sxmc_kde_cv_select) scores K candidate bandwidth vectors in one f64
 // pass over the pairs of the untransformed in-domain rows: kde_cv_weights, kde_cv_pairs and kde_cv_combine, last in
 // this file.  It reads the table only and leaves the rows of the last evaluation alone.
 //
-// A cutoff radius (sxmc_kde_set_cutoff, R > 0) puts kde_cutoff_gather between the prepass and the pair sum and replaces
-// the latter two launches by kde_pairs_cutoff and kde_combine_sorted (after kde_combine below; the pure parts in
-// kde_cutoff.h).  At R = 0 none of them runs.
+// A cutoff radius (sxmc_kde_set_cutoff, R > 0) puts kde_cutoff_gather between the prepass and the pair sum, replaces
+// the latter by kde_pairs_cutoff (both after kde_combine below; the pure parts in kde_cutoff.h) and gives kde_combine
+// the order of the sorted points.  At R = 0 neither runs and kde_combine takes no order.
 #include <hip/hip_runtime.h>
+
+#include <type_traits>
+#include <utility>
 
 #include "nll_device.h"
 
 #include "fill_kernels.inc.h"
 #include "kde_cutoff.h"
+#include "kde_plan.h"
 
 #pragma clang fp contract(off)
 
@@ -43,6 +49,26 @@ using namespace sxfill;
 
 constexpr int kKdeTile = SXMC_KDE_TILE;   // samples per f32 partial sum (the sample rows are padded to a multiple)
 constexpr int kKdeBlock = 256;
+
+// The one run-time to compile-time dispatch of this file: f(std::integral_constant<int, N>{}) for N = D in
+// [1, SXMC_KDE_MAX_DIM] (kde_for_dim), or in [1, MAX] (kde_for_range: the prepass's slots), else hipErrorInvalidValue.
+template <int MAX, class F>
+hipError_t kde_for_range(int n, F&& f) {
+  if constexpr (MAX >= 1) {
+    if (n == MAX) return f(std::integral_constant<int, MAX>{});
+    return kde_for_range<MAX - 1>(n, std::forward<F>(f));
+  }
+  return hipErrorInvalidValue;
+}
+template <class F>
+hipError_t kde_for_dim(int D, F&& f) {
+  return kde_for_range<SXMC_KDE_MAX_DIM>(D, std::forward<F>(f));
+}
+// ... and f(dim, std::bool_constant<adaptive>{})
+template <class F>
+hipError_t kde_for_dim_adapt(int D, bool adaptive, F&& f) {
+  return kde_for_dim(D, [&](auto dim) { return adaptive ? f(dim, std::true_type{}) : f(dim, std::false_type{}); });
+}
 
 template <int NSLOT, bool ADAPT>
 __global__ __launch_bounds__(kKdeBlock) void kde_prepass_kernel(const SxSignalDesc d, const SxKdeArgs a) {
@@ -83,14 +109,12 @@ __global__ __launch_bounds__(kKdeBlock) void kde_prepass_kernel(const SxSignalDe
       for (int k = 0; k < D; k++) {
         if (k >= d.nobs) continue;
         const double x = in ? f[k][q] : a.lower[k];
-        // Phi(z) = erfc(-z / sqrt 2) / 2 with z = (edge - x) / h
+        double r = a.inv_h_sqrt2[k];
         if constexpr (ADAPT) {
-          const double r = a.inv_h_sqrt2[k] / lam;   // 1 / (h lambda sqrt 2)
-          mass = mass * (0.5 * (erfc((x - a.upper[k]) * r) - erfc((x - a.lower[k]) * r)));
+          r = r / lam;   // 1 / (h lambda sqrt 2)
           lam_pow = lam_pow * lam;
-        } else {
-          mass = mass * (0.5 * (erfc((x - a.upper[k]) * a.inv_h_sqrt2[k]) - erfc((x - a.lower[k]) * a.inv_h_sqrt2[k])));
         }
+        mass = mass * sxkde::truncation_mass(x, a.lower[k], a.upper[k], r);
         row[k] = in ? (float)((x - a.lower[k]) * a.cscale[k]) : 0.0f;
       }
       if constexpr (ADAPT) {
@@ -106,12 +130,36 @@ __global__ __launch_bounds__(kKdeBlock) void kde_prepass_kernel(const SxSignalDe
   if (lane == 0 && cnt != 0u) __hip_atomic_fetch_add(a.norm, cnt, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
 }
 
+// The pair sum's inner loop, written once: the f32 sum of one tile's terms at one point.  Rows of D + 1 floats (c_d, w)
+// and the term w exp2(-q), or (ADAPT) of D + 2 floats (c_d, g = 1 / lambda^2, W = w / lambda^D) and the term
+// W exp2(-g q): one multiply more per pair.
+template <int D, bool ADAPT>
+__device__ __forceinline__ float kde_tile_sum(const float (&p)[D], const float* __restrict__ s) {
+  constexpr int kRow = D + (ADAPT ? 2 : 1);
+  float acc = 0.0f;
+#pragma unroll 16
+  for (int j = 0; j < kKdeTile; j++) {
+    const float* r = s + j * kRow;
+    const float a0 = p[0] - r[0];
+    float q = a0 * a0;
+#pragma unroll
+    for (int k = 1; k < D; k++) {
+      const float ak = p[k] - r[k];
+      q = __builtin_fmaf(ak, ak, q);
+    }
+    if constexpr (ADAPT) acc = __builtin_fmaf(r[D + 1], __builtin_amdgcn_exp2f(-(r[D] * q)), acc);
+    else acc = __builtin_fmaf(r[D], __builtin_amdgcn_exp2f(-q), acc);
+  }
+  return acc;
+}
+
 // One lane per point; every lane of the grid runs the full trip count (points are padded with zeros), so the sample
 // rows are read at wave-uniform addresses: scalar loads, SGPR operands of the vector instructions.
-template <int D>
+template <int D, bool ADAPT>
 __global__ __launch_bounds__(kKdeBlock) void kde_pairs_kernel(const float* __restrict__ pts, unsigned long long pitch,
                                                               const float* __restrict__ rows, unsigned tiles_per_split,
                                                               unsigned ntiles, double* __restrict__ part) {
+  constexpr int kRow = D + (ADAPT ? 2 : 1);
   const unsigned long long i = (unsigned long long)blockIdx.x * kKdeBlock + threadIdx.x;
   float p[D];
 #pragma unroll
@@ -120,67 +168,23 @@ __global__ __launch_bounds__(kKdeBlock) void kde_pairs_kernel(const float* __res
   const unsigned t1 = t0 + tiles_per_split < ntiles ? t0 + tiles_per_split : ntiles;
   double sum = 0.0;
   for (unsigned t = t0; t < t1; t++) {
-    const float* s = rows + (unsigned long long)t * kKdeTile * (D + 1);
-    float acc = 0.0f;
-#pragma unroll 16
-    for (int j = 0; j < kKdeTile; j++) {
-      const float* r = s + j * (D + 1);
-      const float a0 = p[0] - r[0];
-      float q = a0 * a0;
-#pragma unroll
-      for (int k = 1; k < D; k++) {
-        const float ak = p[k] - r[k];
-        q = __builtin_fmaf(ak, ak, q);
-      }
-      acc = __builtin_fmaf(r[D], __builtin_amdgcn_exp2f(-q), acc);
-    }
-    sum += (double)acc;
+    sum += (double)kde_tile_sum<D, ADAPT>(p, rows + (unsigned long long)t * kKdeTile * kRow);
   }
   part[(unsigned long long)blockIdx.y * pitch + i] = sum;
 }
 
-// The adaptive pair sum: rows of D + 2 floats (c_d, g = 1 / lambda^2, W = w / lambda^D) and the term W exp2(-g q) -- one
-// multiply more per pair than kde_pairs_kernel; everything else as there.
-template <int D>
-__global__ __launch_bounds__(kKdeBlock) void kde_pairs_adaptive_kernel(const float* __restrict__ pts,
-                                                                       unsigned long long pitch,
-                                                                       const float* __restrict__ rows,
-                                                                       unsigned tiles_per_split, unsigned ntiles,
-                                                                       double* __restrict__ part) {
-  const unsigned long long i = (unsigned long long)blockIdx.x * kKdeBlock + threadIdx.x;
-  float p[D];
-#pragma unroll
-  for (int k = 0; k < D; k++) p[k] = pts[(unsigned long long)k * pitch + i];
-  const unsigned t0 = blockIdx.y * tiles_per_split;
-  const unsigned t1 = t0 + tiles_per_split < ntiles ? t0 + tiles_per_split : ntiles;
-  double sum = 0.0;
-  for (unsigned t = t0; t < t1; t++) {
-    const float* s = rows + (unsigned long long)t * kKdeTile * (D + 2);
-    float acc = 0.0f;
-#pragma unroll 16
-    for (int j = 0; j < kKdeTile; j++) {
-      const float* r = s + j * (D + 2);
-      const float a0 = p[0] - r[0];
-      float q = a0 * a0;
-#pragma unroll
-      for (int k = 1; k < D; k++) {
-        const float ak = p[k] - r[k];
-        q = __builtin_fmaf(ak, ak, q);
-      }
-      acc = __builtin_fmaf(r[D + 1], __builtin_amdgcn_exp2f(-(r[D] * q)), acc);
-    }
-    sum += (double)acc;
-  }
-  part[(unsigned long long)blockIdx.y * pitch + i] = sum;
-}
-
+// One lane per place j of the partial sums, which are added in split order; the value goes to point order[j] -- the
+// caller's point that stands at sorted place j (a cutoff) -- or to point j when order is null.  codes: in the caller's
+// order.
 __global__ __launch_bounds__(kKdeBlock) void kde_combine_kernel(const double* __restrict__ part, unsigned long long pitch,
                                                                 int nsplit, unsigned long long npoints,
                                                                 const int* __restrict__ codes,
+                                                                const unsigned* __restrict__ order,
                                                                 const unsigned* __restrict__ norm, double prefactor,
                                                                 float* __restrict__ out, long stride) {
-  const unsigned long long i = (unsigned long long)blockIdx.x * kKdeBlock + threadIdx.x;
-  if (i >= npoints) return;
+  const unsigned long long j = (unsigned long long)blockIdx.x * kKdeBlock + threadIdx.x;
+  if (j >= npoints) return;
+  const unsigned long long i = order ? order[j] : j;
   const int code = codes[i];
   float v;
   if (code == -2) {
@@ -189,7 +193,7 @@ __global__ __launch_bounds__(kKdeBlock) void kde_combine_kernel(const double* __
     v = __int_as_float(0x7fc00000);        // outside the domain
   } else {
     double s = 0.0;
-    for (int k = 0; k < nsplit; k++) s += part[(unsigned long long)k * pitch + i];
+    for (int k = 0; k < nsplit; k++) s += part[(unsigned long long)k * pitch + j];
     const unsigned n = *norm;
     v = n == 0u ? __int_as_float(0x7fc00000) : (float)(s * prefactor / (double)n);
   }
@@ -198,8 +202,8 @@ __global__ __launch_bounds__(kKdeBlock) void kde_combine_kernel(const double* __
 
 // ------------------------------------------------------------------------------------ cutoff radius (sxmc_kde_set_cutoff)
 // With a cutoff the pair sum runs on a second copy of the prepass's rows in the spatial order of kde_cutoff.h, and on
-// points sorted by the same key: kde_cutoff_gather, kde_pairs_cutoff and kde_combine_sorted below.  The prepass, the
-// sampler and the projection are untouched and keep the rows in table order.
+// points sorted by the same key: kde_cutoff_gather and kde_pairs_cutoff below, and kde_combine with the points' order.
+// The prepass, the sampler and the projection are untouched and keep the rows in table order.
 
 // One workgroup per tile: row perm[k] of the prepass's rows goes to place k of the sorted rows, and the tile's box --
 // min and max of c_d over its rows with weight > 0, and the smallest g when adaptive -- to box[tile] (kCutBox floats;
@@ -266,27 +270,6 @@ __global__ __launch_bounds__(kKdeBlock) void kde_cutoff_gather_kernel(const floa
   }
 }
 
-// The f32 sum of one tile's terms at one point: the inner loop of kde_pairs_kernel / kde_pairs_adaptive_kernel.
-template <int D, bool ADAPT>
-__device__ __forceinline__ float kde_tile_sum(const float (&p)[D], const float* __restrict__ s) {
-  constexpr int kRow = D + (ADAPT ? 2 : 1);
-  float acc = 0.0f;
-#pragma unroll 16
-  for (int j = 0; j < kKdeTile; j++) {
-    const float* r = s + j * kRow;
-    const float a0 = p[0] - r[0];
-    float q = a0 * a0;
-#pragma unroll
-    for (int k = 1; k < D; k++) {
-      const float ak = p[k] - r[k];
-      q = __builtin_fmaf(ak, ak, q);
-    }
-    if constexpr (ADAPT) acc = __builtin_fmaf(r[D + 1], __builtin_amdgcn_exp2f(-(r[D] * q)), acc);
-    else acc = __builtin_fmaf(r[D], __builtin_amdgcn_exp2f(-q), acc);
-  }
-  return acc;
-}
-
 // The culled pair sum: kde_pairs_kernel's shape on the sorted points and rows, but each wave visits, of its split's
 // tiles, only those whose box lies within the cutoff of the wave's own box (sxkde::cutoff_visit, one lane per tile, 64
 // tiles at a time; the set bits of the ballot walked in tile order with the tile number made provably uniform, so that
@@ -350,135 +333,59 @@ __global__ __launch_bounds__(kKdeBlock) void kde_pairs_cutoff_kernel(const float
   }
 }
 
-// kde_combine_kernel for sorted points, one lane per sorted place j: the partial sums are read in that order and the
-// value goes to the caller's point order[j] (codes in the caller's order).
-__global__ __launch_bounds__(kKdeBlock) void kde_combine_sorted_kernel(const double* __restrict__ part,
-                                                                       unsigned long long pitch, int nsplit,
-                                                                       unsigned long long npoints,
-                                                                       const int* __restrict__ codes,
-                                                                       const unsigned* __restrict__ order,
-                                                                       const unsigned* __restrict__ norm,
-                                                                       double prefactor, float* __restrict__ out,
-                                                                       long stride) {
-  const unsigned long long j = (unsigned long long)blockIdx.x * kKdeBlock + threadIdx.x;
-  if (j >= npoints) return;
-  const unsigned long long i = order[j];
-  const int code = codes[i];
-  float v;
-  if (code == -2) {
-    v = 0.0f;
-  } else if (code < 0) {
-    v = __int_as_float(0x7fc00000);
-  } else {
-    double s = 0.0;
-    for (int k = 0; k < nsplit; k++) s += part[(unsigned long long)k * pitch + j];
-    const unsigned n = *norm;
-    v = n == 0u ? __int_as_float(0x7fc00000) : (float)(s * prefactor / (double)n);
-  }
-  out[stride * (long)i] = v;
+}  // namespace
+
+hipError_t sx_kde_prepass(const SxSignalDesc& d, const SxKdeArgs& a, hipStream_t s) {
+  const unsigned long long nvec = a.npad / SXMC_VEC;
+  const unsigned grid = (unsigned)((nvec + kKdeBlock - 1) / kKdeBlock);
+  if (grid == 0) return hipSuccess;
+  return kde_for_range<7>(d.nslot, [&](auto nslot) {
+    constexpr int N = decltype(nslot)::value;
+    if (a.lambda) hipLaunchKernelGGL((kde_prepass_kernel<N, true>), dim3(grid), dim3(kKdeBlock), 0, s, d, a);
+    else hipLaunchKernelGGL((kde_prepass_kernel<N, false>), dim3(grid), dim3(kKdeBlock), 0, s, d, a);
+    return hipGetLastError();
+  });
 }
 
-}  // namespace
+hipError_t sx_kde_pairs(int D, bool adaptive, const float* pts, unsigned long long pitch, const float* rows,
+                        unsigned tiles_per_split, unsigned ntiles, int nsplit, double* part, hipStream_t s) {
+  const dim3 grid((unsigned)(pitch / kKdeBlock), (unsigned)nsplit);
+  return kde_for_dim_adapt(D, adaptive, [&](auto dim, auto adapt) {
+    hipLaunchKernelGGL((kde_pairs_kernel<decltype(dim)::value, decltype(adapt)::value>), grid, dim3(kKdeBlock), 0, s,
+                       pts, pitch, rows, tiles_per_split, ntiles, part);
+    return hipGetLastError();
+  });
+}
+
+hipError_t sx_kde_combine(const double* part, unsigned long long pitch, int nsplit, unsigned long long npoints,
+                          const int* codes, const unsigned* order, const unsigned* norm, double prefactor, float* out,
+                          long stride, hipStream_t s) {
+  if (npoints == 0) return hipSuccess;
+  const unsigned grid = (unsigned)((npoints + kKdeBlock - 1) / kKdeBlock);
+  hipLaunchKernelGGL(kde_combine_kernel, dim3(grid), dim3(kKdeBlock), 0, s, part, pitch, nsplit, npoints, codes, order,
+                     norm, prefactor, out, stride);
+  return hipGetLastError();
+}
 
 hipError_t sx_kde_cutoff_gather(int D, bool adaptive, const float* rows, const unsigned* perm, unsigned ntiles,
                                 float* sorted, float* box, hipStream_t s) {
   if (ntiles == 0) return hipSuccess;
-#define SX_KDE_CASE(N)                                                                                                  \
-  case N:                                                                                                               \
-    if (adaptive) hipLaunchKernelGGL((kde_cutoff_gather_kernel<N, true>), dim3(ntiles), dim3(kKdeBlock), 0, s, rows, perm, \
-                                     sorted, box);                                                                      \
-    else hipLaunchKernelGGL((kde_cutoff_gather_kernel<N, false>), dim3(ntiles), dim3(kKdeBlock), 0, s, rows, perm, sorted, \
-                            box);                                                                                       \
-    break;
-  switch (D) {
-    SX_KDE_CASE(1) SX_KDE_CASE(2) SX_KDE_CASE(3) SX_KDE_CASE(4)
-    default: return hipErrorInvalidValue;
-  }
-#undef SX_KDE_CASE
-  return hipGetLastError();
+  return kde_for_dim_adapt(D, adaptive, [&](auto dim, auto adapt) {
+    hipLaunchKernelGGL((kde_cutoff_gather_kernel<decltype(dim)::value, decltype(adapt)::value>), dim3(ntiles),
+                       dim3(kKdeBlock), 0, s, rows, perm, sorted, box);
+    return hipGetLastError();
+  });
 }
 
 hipError_t sx_kde_pairs_cutoff(int D, bool adaptive, const float* pts, unsigned long long pitch, const float* rows,
                                const float* tile_box, const float* wave_box, unsigned tiles_per_split, unsigned ntiles,
                                int nsplit, float qcut, double* part, unsigned long long* visited, hipStream_t s) {
   const dim3 grid((unsigned)(pitch / kKdeBlock), (unsigned)nsplit);
-#define SX_KDE_CASE(N)                                                                                                 \
-  case N:                                                                                                              \
-    if (adaptive) hipLaunchKernelGGL((kde_pairs_cutoff_kernel<N, true>), grid, dim3(kKdeBlock), 0, s, pts, pitch, rows,  \
-                                     tile_box, wave_box, tiles_per_split, ntiles, qcut, part, visited);                \
-    else hipLaunchKernelGGL((kde_pairs_cutoff_kernel<N, false>), grid, dim3(kKdeBlock), 0, s, pts, pitch, rows, tile_box, \
-                            wave_box, tiles_per_split, ntiles, qcut, part, visited);                                   \
-    break;
-  switch (D) {
-    SX_KDE_CASE(1) SX_KDE_CASE(2) SX_KDE_CASE(3) SX_KDE_CASE(4)
-    default: return hipErrorInvalidValue;
-  }
-#undef SX_KDE_CASE
-  return hipGetLastError();
-}
-
-hipError_t sx_kde_combine_sorted(const double* part, unsigned long long pitch, int nsplit, unsigned long long npoints,
-                                 const int* codes, const unsigned* order, const unsigned* norm, double prefactor,
-                                 float* out, long stride, hipStream_t s) {
-  if (npoints == 0) return hipSuccess;
-  const unsigned grid = (unsigned)((npoints + kKdeBlock - 1) / kKdeBlock);
-  hipLaunchKernelGGL(kde_combine_sorted_kernel, dim3(grid), dim3(kKdeBlock), 0, s, part, pitch, nsplit, npoints, codes,
-                     order, norm, prefactor, out, stride);
-  return hipGetLastError();
-}
-
-hipError_t sx_kde_prepass(const SxSignalDesc& d, const SxKdeArgs& a, hipStream_t s) {
-  const unsigned long long nvec = a.npad / SXMC_VEC;
-  const unsigned grid = (unsigned)((nvec + kKdeBlock - 1) / kKdeBlock);
-  if (grid == 0) return hipSuccess;
-#define SX_KDE_CASE(N)                                                                                       \
-  case N:                                                                                                    \
-    if (a.lambda) hipLaunchKernelGGL((kde_prepass_kernel<N, true>), dim3(grid), dim3(kKdeBlock), 0, s, d, a); \
-    else hipLaunchKernelGGL((kde_prepass_kernel<N, false>), dim3(grid), dim3(kKdeBlock), 0, s, d, a);         \
-    break;
-  switch (d.nslot) {
-    SX_KDE_CASE(1) SX_KDE_CASE(2) SX_KDE_CASE(3) SX_KDE_CASE(4) SX_KDE_CASE(5) SX_KDE_CASE(6) SX_KDE_CASE(7)
-    default:
-      return hipErrorInvalidValue;
-  }
-#undef SX_KDE_CASE
-  return hipGetLastError();
-}
-
-hipError_t sx_kde_pairs(int D, const float* pts, unsigned long long pitch, const float* rows, unsigned tiles_per_split,
-                        unsigned ntiles, int nsplit, double* part, hipStream_t s) {
-  const dim3 grid((unsigned)(pitch / kKdeBlock), (unsigned)nsplit);
-  switch (D) {
-    case 1: hipLaunchKernelGGL(kde_pairs_kernel<1>, grid, dim3(kKdeBlock), 0, s, pts, pitch, rows, tiles_per_split, ntiles, part); break;
-    case 2: hipLaunchKernelGGL(kde_pairs_kernel<2>, grid, dim3(kKdeBlock), 0, s, pts, pitch, rows, tiles_per_split, ntiles, part); break;
-    case 3: hipLaunchKernelGGL(kde_pairs_kernel<3>, grid, dim3(kKdeBlock), 0, s, pts, pitch, rows, tiles_per_split, ntiles, part); break;
-    case 4: hipLaunchKernelGGL(kde_pairs_kernel<4>, grid, dim3(kKdeBlock), 0, s, pts, pitch, rows, tiles_per_split, ntiles, part); break;
-    default: return hipErrorInvalidValue;
-  }
-  return hipGetLastError();
-}
-
-hipError_t sx_kde_pairs_adaptive(int D, const float* pts, unsigned long long pitch, const float* rows,
-                                 unsigned tiles_per_split, unsigned ntiles, int nsplit, double* part, hipStream_t s) {
-  const dim3 grid((unsigned)(pitch / kKdeBlock), (unsigned)nsplit);
-  switch (D) {
-    case 1: hipLaunchKernelGGL(kde_pairs_adaptive_kernel<1>, grid, dim3(kKdeBlock), 0, s, pts, pitch, rows, tiles_per_split, ntiles, part); break;
-    case 2: hipLaunchKernelGGL(kde_pairs_adaptive_kernel<2>, grid, dim3(kKdeBlock), 0, s, pts, pitch, rows, tiles_per_split, ntiles, part); break;
-    case 3: hipLaunchKernelGGL(kde_pairs_adaptive_kernel<3>, grid, dim3(kKdeBlock), 0, s, pts, pitch, rows, tiles_per_split, ntiles, part); break;
-    case 4: hipLaunchKernelGGL(kde_pairs_adaptive_kernel<4>, grid, dim3(kKdeBlock), 0, s, pts, pitch, rows, tiles_per_split, ntiles, part); break;
-    default: return hipErrorInvalidValue;
-  }
-  return hipGetLastError();
-}
-
-hipError_t sx_kde_combine(const double* part, unsigned long long pitch, int nsplit, unsigned long long npoints,
-                          const int* codes, const unsigned* norm, double prefactor, float* out, long stride,
-                          hipStream_t s) {
-  if (npoints == 0) return hipSuccess;
-  const unsigned grid = (unsigned)((npoints + kKdeBlock - 1) / kKdeBlock);
-  hipLaunchKernelGGL(kde_combine_kernel, dim3(grid), dim3(kKdeBlock), 0, s, part, pitch, nsplit, npoints, codes, norm,
-                     prefactor, out, stride);
-  return hipGetLastError();
+  return kde_for_dim_adapt(D, adaptive, [&](auto dim, auto adapt) {
+    hipLaunchKernelGGL((kde_pairs_cutoff_kernel<decltype(dim)::value, decltype(adapt)::value>), grid, dim3(kKdeBlock),
+                       0, s, pts, pitch, rows, tile_box, wave_box, tiles_per_split, ntiles, qcut, part, visited);
+    return hipGetLastError();
+  });
 }
 
 // ------------------------------------------------------------------------------------ sampling (sxmc_kde_random_sample)
@@ -589,19 +496,11 @@ hipError_t sx_kde_sample(int D, const float* rows, const double* lambda, const u
   if (nevents == 0) return hipSuccess;
   const unsigned long long b = (nevents + kKdeBlock - 1) / kKdeBlock;
   const dim3 grid((unsigned)(b < 4096 ? b : 4096));
-#define SX_KDE_CASE(N)                                                                                              \
-  case N:                                                                                                           \
-    if (lambda) hipLaunchKernelGGL((kde_sample_kernel<N, true>), grid, dim3(kKdeBlock), 0, s, rows, lambda, idx, n, g, \
-                                   seed, nevents, out, exhausted);                                                  \
-    else hipLaunchKernelGGL((kde_sample_kernel<N, false>), grid, dim3(kKdeBlock), 0, s, rows, lambda, idx, n, g, seed, \
-                            nevents, out, exhausted);                                                               \
-    break;
-  switch (D) {
-    SX_KDE_CASE(1) SX_KDE_CASE(2) SX_KDE_CASE(3) SX_KDE_CASE(4)
-    default: return hipErrorInvalidValue;
-  }
-#undef SX_KDE_CASE
-  return hipGetLastError();
+  return kde_for_dim_adapt(D, lambda != nullptr, [&](auto dim, auto adapt) {
+    hipLaunchKernelGGL((kde_sample_kernel<decltype(dim)::value, decltype(adapt)::value>), grid, dim3(kKdeBlock), 0, s,
+                       rows, lambda, idx, n, g, seed, nevents, out, exhausted);
+    return hipGetLastError();
+  });
 }
 
 // ------------------------------------------------------------------------------------ projection (sxmc_kde_project)
@@ -776,14 +675,10 @@ hipError_t sx_kde_pilot(const SxKdePilotArgs& a, const double* x, const double* 
     return hipErrorInvalidValue;
   }
   const dim3 grid((unsigned)(a.pitch / kKdeBlock), a.nsplit);
-  switch (a.D) {
-    case 1: hipLaunchKernelGGL(kde_pilot_kernel<1>, grid, dim3(kKdeBlock), 0, s, a, x, s0, part); break;
-    case 2: hipLaunchKernelGGL(kde_pilot_kernel<2>, grid, dim3(kKdeBlock), 0, s, a, x, s0, part); break;
-    case 3: hipLaunchKernelGGL(kde_pilot_kernel<3>, grid, dim3(kKdeBlock), 0, s, a, x, s0, part); break;
-    case 4: hipLaunchKernelGGL(kde_pilot_kernel<4>, grid, dim3(kKdeBlock), 0, s, a, x, s0, part); break;
-    default: return hipErrorInvalidValue;
-  }
-  hipError_t e = hipGetLastError();
+  const hipError_t e = kde_for_dim(a.D, [&](auto dim) {
+    hipLaunchKernelGGL(kde_pilot_kernel<decltype(dim)::value>, grid, dim3(kKdeBlock), 0, s, a, x, s0, part);
+    return hipGetLastError();
+  });
   if (e != hipSuccess) return e;
   hipLaunchKernelGGL(kde_pilot_combine_kernel, dim3((unsigned)(a.pitch / kKdeBlock)), dim3(kKdeBlock), 0, s, a, part, f);
   return hipGetLastError();
@@ -816,8 +711,7 @@ __global__ __launch_bounds__(kKdeBlock) void kde_cv_weights_kernel(const SxKdeCv
     if (c < a.K) {
       double mass = 1.0;
       for (int d = 0; d < a.D; d++) {
-        const double x = row[d], r = inv_h_sqrt2[c * a.D + d];
-        mass = mass * (0.5 * (erfc((x - a.upper[d]) * r) - erfc((x - a.lower[d]) * r)));
+        mass = mass * sxkde::truncation_mass(row[d], a.lower[d], a.upper[d], inv_h_sqrt2[c * a.D + d]);
       }
       w = 1.0 / (prod_h[c] * mass);
     }
@@ -871,20 +765,17 @@ __global__ __launch_bounds__(kKdeBlock) void kde_cv_combine_kernel(const SxKdeCv
   lnf[(unsigned long long)c * a.pitch + i] = log(s * a.prefactor);
 }
 
+// the pair kernel of D observables and KP candidates (sx_kde_cv_padded: 1, 8, 16, 24 or 32)
 template <int D>
 hipError_t kde_cv_launch_pairs(const SxKdeCvArgs& a, const double* x, const double* s0, const double* cand, double* part,
                                hipStream_t s) {
   const dim3 grid((unsigned)(a.pitch / kKdeBlock), a.nsplit);
-#define SX_KDE_CASE(N)                                                                                           \
-  case N:                                                                                                        \
-    hipLaunchKernelGGL((kde_cv_pairs_kernel<D, N>), grid, dim3(kKdeBlock), 0, s, a, x, s0, cand, part);          \
-    break;
-  switch (a.KP) {
-    SX_KDE_CASE(1) SX_KDE_CASE(8) SX_KDE_CASE(16) SX_KDE_CASE(24) SX_KDE_CASE(32)
-    default: return hipErrorInvalidValue;
-  }
-#undef SX_KDE_CASE
-  return hipGetLastError();
+  const int nth = a.KP == 1 ? 1 : (a.KP >= 8 && a.KP % 8 == 0) ? a.KP / 8 + 1 : 0;   // of that list, from 1
+  return kde_for_range<5>(nth, [&](auto n) {
+    constexpr int KP = decltype(n)::value == 1 ? 1 : (decltype(n)::value - 1) * 8;
+    hipLaunchKernelGGL((kde_cv_pairs_kernel<D, KP>), grid, dim3(kKdeBlock), 0, s, a, x, s0, cand, part);
+    return hipGetLastError();
+  });
 }
 
 }  // namespace
@@ -902,13 +793,7 @@ hipError_t sx_kde_cv_scan(const SxKdeCvArgs& a, const double* x, double* s0, con
   hipLaunchKernelGGL(kde_cv_weights_kernel, dim3((a.m + kKdeBlock - 1) / kKdeBlock), dim3(kKdeBlock), 0, s, a, s0, cand);
   hipError_t e = hipGetLastError();
   if (e != hipSuccess) return e;
-  switch (a.D) {
-    case 1: e = kde_cv_launch_pairs<1>(a, x, s0, cand, part, s); break;
-    case 2: e = kde_cv_launch_pairs<2>(a, x, s0, cand, part, s); break;
-    case 3: e = kde_cv_launch_pairs<3>(a, x, s0, cand, part, s); break;
-    case 4: e = kde_cv_launch_pairs<4>(a, x, s0, cand, part, s); break;
-    default: return hipErrorInvalidValue;
-  }
+  e = kde_for_dim(a.D, [&](auto dim) { return kde_cv_launch_pairs<decltype(dim)::value>(a, x, s0, cand, part, s); });
   if (e != hipSuccess) return e;
   hipLaunchKernelGGL(kde_cv_combine_kernel, dim3((unsigned)(a.pitch / kKdeBlock), (unsigned)a.K), dim3(kKdeBlock), 0, s, a,
                      part, lnf);

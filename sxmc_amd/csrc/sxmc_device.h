@@ -241,7 +241,7 @@ hipError_t sx_launch_untranspose_obs(const float* cols, float* out, unsigned lon
                                      int nobs, unsigned long long col_pitch, float dataset,
                                      hipStream_t s);
 
-// pdfz::EvalKernel (kde_kernels.hip, sxmc_kde.cpp)
+// pdfz::EvalKernel (kde_kernels.hip; sxmc_kde.cpp, sxmc_kde_cv.cpp, sxmc_kde_draw.cpp)
 #define SXMC_KDE_MAX_DIM 4   // observables of a kernel-density evaluator
 #define SXMC_KDE_TILE 256    // samples per f32 partial sum of the pair kernel; sample rows are padded to a multiple
 // The prepass's geometry: rows = [npad][nobs + 1] floats (scaled coordinates, weight), norm = the in-domain counter.
@@ -258,15 +258,15 @@ struct SxKdeArgs {
   const double* lambda;
 };
 hipError_t sx_kde_prepass(const SxSignalDesc& d, const SxKdeArgs& a, hipStream_t s);
-// pts: [D][pitch] scaled point coordinates, pitch a multiple of 256; part: [nsplit][pitch]
-hipError_t sx_kde_pairs(int D, const float* pts, unsigned long long pitch, const float* rows, unsigned tiles_per_split,
-                        unsigned ntiles, int nsplit, double* part, hipStream_t s);
-// rows of D + 2 floats (an adaptive evaluator's prepass); the rest as sx_kde_pairs
-hipError_t sx_kde_pairs_adaptive(int D, const float* pts, unsigned long long pitch, const float* rows,
-                                 unsigned tiles_per_split, unsigned ntiles, int nsplit, double* part, hipStream_t s);
+// pts: [D][pitch] scaled point coordinates, pitch a multiple of 256; part: [nsplit][pitch]; adaptive: rows of D + 2
+// floats (an adaptive evaluator's prepass)
+hipError_t sx_kde_pairs(int D, bool adaptive, const float* pts, unsigned long long pitch, const float* rows,
+                        unsigned tiles_per_split, unsigned ntiles, int nsplit, double* part, hipStream_t s);
+// order: null (the partial sums stand in the caller's point order), or [npoints] the caller's point that stands at each
+// sorted place (a cutoff); codes: in the caller's order
 hipError_t sx_kde_combine(const double* part, unsigned long long pitch, int nsplit, unsigned long long npoints,
-                          const int* codes, const unsigned* norm, double prefactor, float* out, long stride,
-                          hipStream_t s);
+                          const int* codes, const unsigned* order, const unsigned* norm, double prefactor, float* out,
+                          long stride, hipStream_t s);
 // The cutoff radius (sxmc_kde_set_cutoff; kde_cutoff.h has the pure parts).  perm: [ntiles * 256] a permutation of the
 // sample rows; sorted: the rows in that order; box: [ntiles][sxkde::kCutBox] the tiles' boxes, written by the gather.
 hipError_t sx_kde_cutoff_gather(int D, bool adaptive, const float* rows, const unsigned* perm, unsigned ntiles,
@@ -276,10 +276,6 @@ hipError_t sx_kde_cutoff_gather(int D, bool adaptive, const float* rows, const u
 hipError_t sx_kde_pairs_cutoff(int D, bool adaptive, const float* pts, unsigned long long pitch, const float* rows,
                                const float* tile_box, const float* wave_box, unsigned tiles_per_split, unsigned ntiles,
                                int nsplit, float qcut, double* part, unsigned long long* visited, hipStream_t s);
-// order: [npoints] the caller's point that stands at each sorted place
-hipError_t sx_kde_combine_sorted(const double* part, unsigned long long pitch, int nsplit, unsigned long long npoints,
-                                 const int* codes, const unsigned* order, const unsigned* norm, double prefactor,
-                                 float* out, long stride, hipStream_t s);
 // Sampling from the last evaluation (sxmc_kde_random_sample): the in-domain rows listed by a flag, an inclusive scan
 // (temp: the scan's scratch, temp_bytes of it) and a scatter into idx; then one lane per event.
 struct SxKdeSampleArgs {

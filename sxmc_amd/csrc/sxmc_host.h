@@ -9,7 +9,10 @@
 //   sxmc_group.cpp        the group entry points: configuration, autotune, evaluation, the step and its step-end forms
 //   sxmc_multigroup.cpp   lockstep chains and the look-ahead pass
 //   sxmc_nll_api.cpp      the NLL launch points with the reference's argument lists; the measurement build's test hooks
-//   sxmc_kde.cpp          the kernel-density evaluator (sxmc_kde_*) behind pdfz::EvalKernel
+//   sxmc_kde.cpp          the kernel-density evaluator (sxmc_kde_*) behind pdfz::EvalKernel: creation, points, bindings,
+//                         launch, streams, accessors (its state, shared with the next two: sxmc_kde_state.h)
+//   sxmc_kde_cv.cpp       ... its bandwidth cross-validation
+//   sxmc_kde_draw.cpp     ... what reads the last evaluation's rows: sampling and the projection
 // (the kernels: pdfz_kernels.hip, nll_kernels.hip, kde_kernels.hip, columns_kernels.hip, layout_kernels.hip, project_kernels.hip)
 // Every allocation these hold is owned by a buffer (device_buffer.h over the policies below); layout_kernels.hip's host
 // helpers take their temporaries from the same type.

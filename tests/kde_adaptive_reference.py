@@ -13,7 +13,7 @@ a_d = c_pd - c_id, q = sum_d a_d^2 -- a term is t = W exp2(-q'), q' = g q, g = 1
 prefactor 1 / ((2 pi)^(D/2) prod h) is the fixed-bandwidth one.
 
 The bound, derived as kde_reference.py derives its own (u = 2^-24, first order).  The adaptive pair kernel
-(kde_pairs_adaptive_kernel) forms q exactly as the fixed one does, so |dq| <= 4 u c_max sum_d |a_d| + (D + 3) u q;
+(kde_pairs_kernel<D, true>) forms q exactly as the fixed one does, so |dq| <= 4 u c_max sum_d |a_d| + (D + 3) u q;
 then it multiplies by g, itself rounded to f32: two more roundings, each u relative on q', so
   |dq'| <= g (4 u c_max sum_d |a_d| + (D + 3) u q) + 2 u q' = 4 u c_max g sum_d |a_d| + (D + 5) u q',
 and the term moves by ln 2 |dq'| relative.  exp2 is v_exp_f32 (2 u) and W an f32 (u): 3 u as before.  The tile sum in

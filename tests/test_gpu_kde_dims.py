@@ -22,7 +22,7 @@ CUS = 256   # MI355X: choose_split's resident workgroups are 8 per CU
 
 
 def choose_split(pitch, ntiles, cus=CUS):
-    """sxmc_kde.cpp's choose_split: (nsplit, tiles per split)."""
+    """kde_plan.h's pair_split: (nsplit, tiles per split)."""
     pblocks, slots = pitch // 256, cus * 8
     best, out = None, (1, ntiles)
     for s in range(1, min(ntiles, max(1, 64 * slots // pblocks)) + 1):
