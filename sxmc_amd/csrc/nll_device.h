@@ -1,5 +1,5 @@
 // nll_device.h -- device functions of the NLL half of the MCMC step, shared by nll_kernels.hip (the
-// reference's separate entry points) and pdfz_kernels.hip (the fused lookup + event sum + step end).
+// reference's separate entry points) and step_end_kernels.inc.h (the fused lookup + event sum + step end).
 // See nll_kernels.hip for the reference lines each one restates.
 #pragma once
 

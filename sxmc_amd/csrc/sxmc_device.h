@@ -9,6 +9,7 @@
 
 #include "../../include/sxmc_hip.h"
 
+#include "step_end_plan.h"   // (the step end's grids, LDS and ticket words: pure, shared with the host's rules)
 #include "sxmc_device_types.h"
 
 // Arguments of finish_nll_jump_pick_combo (nll_kernels.h:190-207) for the fused step end.
@@ -59,14 +60,6 @@ inline bool sx_step_end_table_fill(SxStepEndTable& t, const SxSignalDesc* descs,
   }
   return true;
 }
-
-// The event sum of a step is cut into blocks of kStepSumRows rows (eval_nll_kernel's workgroups: 128 lanes, two waves), and
-// the one-workgroup step end (tail_step_kernel) is taken for at most kTailMaxLookups look-ups, rows x members -- so for at
-// most two such blocks, whose waves' sums it adds block by block.  One pair of constants for the host's rules
-// (step_sum_blocks, step_end_takes_tail) and the kernel that depends on them.
-constexpr unsigned kStepSumRows = 128;
-constexpr unsigned long long kTailMaxLookups = 256;
-static_assert(kTailMaxLookups <= 2 * kStepSumRows, "tail_step_kernel adds the waves' sums of at most two blocks of the event sum");
 
 // The step ends of the chains of a lockstep set, launched together (sxmc_multigroup_step_async): per chain what
 // eval_nll_kernel and finish_zero_kernel take.  Passed by value (kernel argument); the chain is blockIdx.y.

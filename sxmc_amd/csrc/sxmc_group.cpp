@@ -6,6 +6,83 @@ using namespace sxhost;
 
 namespace sxhost {
 std::atomic<int> g_stepping_groups{0};
+
+SxStepArgs sx_step_args(const sxmc_step_args& p, size_t nsignals) {
+  SxStepArgs a;   // (the measurement build's gate keeps its defaults)
+  a.nsignals = nsignals;
+  a.nsources = p.nsources;
+  a.means = p.d_means;
+  a.sigmas = p.d_sigmas;
+  a.rng = p.d_rng;
+  a.nll_current = p.d_nll_current;
+  a.nll_proposed = p.d_nll_proposed;
+  a.v_current = p.d_v_current;
+  a.v_proposed = p.d_v_proposed;
+  a.accepted = p.d_accepted;
+  a.counter = p.d_counter;
+  a.jump_buffer = p.d_jump_buffer;
+  a.nparameters = p.nparameters;
+  a.debug_mode = p.debug_mode;
+  a.jump_width = p.d_jump_width;
+  a.nexpected = p.d_nexpected;
+  a.n_mc = p.d_n_mc;
+  a.source_id = p.d_source_id;
+  a.norms = p.d_norms;
+  return a;
+}
+
+// The step entry points' loose parameters (in their order) as the public pack: the one place that pairs them with its fields.
+static sxmc_step_args pack_step_args(const double* d_means, const double* d_sigmas, sxmc_rng_state* d_rng,
+                                     double* d_nll_current, double* d_nll_proposed, double* d_v_current,
+                                     double* d_v_proposed, int* d_accepted, int* d_counter, float* d_jump_buffer,
+                                     int nparameters, size_t nsources, const float* d_jump_width,
+                                     const double* d_nexpected, const unsigned* d_n_mc, const short* d_source_id,
+                                     const unsigned* d_norms, int debug_mode) {
+  sxmc_step_args p;
+  p.d_means = d_means;
+  p.d_sigmas = d_sigmas;
+  p.d_rng = d_rng;
+  p.d_nll_current = d_nll_current;
+  p.d_nll_proposed = d_nll_proposed;
+  p.d_v_current = d_v_current;
+  p.d_v_proposed = d_v_proposed;
+  p.d_accepted = d_accepted;
+  p.d_counter = d_counter;
+  p.d_jump_buffer = d_jump_buffer;
+  p.nparameters = nparameters;
+  p.nsources = nsources;
+  p.d_jump_width = d_jump_width;
+  p.d_nexpected = d_nexpected;
+  p.d_n_mc = d_n_mc;
+  p.d_source_id = d_source_id;
+  p.d_norms = d_norms;
+  p.debug_mode = debug_mode;
+  return p;
+}
+
+StepRows step_rows(const sxmc_group* g, bool sparse) {
+  if (g->cfg_lut) return {sparse ? g->d_descs_sparse.get() : g->d_descs.get(), nullptr, g->members[0]->npoints};
+  const sxmc_group::EventClasses& ec = g->ec[sparse ? 1 : 0];
+  return {ec.d_descs.get(), ec.d_weight.get(), ec.K};
+}
+
+void mark_cleared(sxmc_group* g, bool sparse) {
+  g->prezeroed = sparse ? 2 : 1;
+  for (sxmc_hist* h : g->members) {
+    h->bins_valid = false;
+    h->cleared_by = g;
+  }
+}
+
+// the second launch of the two-launch step end: finish_nll_jump_pick_combo over the partial sums beside the clearing
+static int finish_and_clear(sxmc_group* g, hipStream_t st, bool sparse, size_t npartial, const double* d_sums,
+                            const SxStepArgs& a) {
+  SX_HIP(sx_launch_finish_zero(sparse ? g->d_descs_sparse.get() : g->d_descs.get(), (int)g->members.size(),
+                               sparse ? g->max_bins_sparse : g->max_bins, npartial, d_sums,
+                               g->d_ticket.get() + sxstep::kTicket, a, 128, st));
+  mark_cleared(g, sparse);
+  return SXMC_OK;
+}
 }  // namespace sxhost
 
 extern "C" {
@@ -17,13 +94,13 @@ int sxmc_group_create(const sxmc_hist_t* members, int nmembers, sxmc_group_t* ou
   *out = nullptr;
   auto g = std::make_unique<sxmc_group>();
   g->members.assign(members, members + nmembers);
-  SX_BUF(g->d_ticket.alloc(64));
-  SX_HIP(hipMemset(g->d_ticket.get(), 0, 256));
+  SX_BUF(g->d_ticket.alloc(sxstep::kTicketWords));
+  SX_HIP(hipMemset(g->d_ticket.get(), 0, sxstep::kTicketWords * sizeof(unsigned)));
   SX_BUF(g->d_step_sums.alloc(1024));
-  // (the cooperative step end's hand-over slots, 128 workers at most: see step_end_is_cooperative)
-  SX_BUF(g->d_coop_slots.alloc(128));
-  SX_BUF(g->d_coop_last.alloc(128));
-  SX_HIP(sx_step_end_slots_init(g->d_coop_slots.get(), g->d_coop_last.get(), 128));
+  // (the cooperative step end's hand-over slots, one per worker: see step_end_is_cooperative)
+  SX_BUF(g->d_coop_slots.alloc(kCoopMaxWorkers));
+  SX_BUF(g->d_coop_last.alloc(kCoopMaxWorkers));
+  SX_HIP(sx_step_end_slots_init(g->d_coop_slots.get(), g->d_coop_last.get(), kCoopMaxWorkers));
   *out = g.release();
   return SXMC_OK;
 }
@@ -462,21 +539,14 @@ int sxmc_group_eval_nll_async(sxmc_group_t g, sxmc_stream_t s, const double* d_p
   if (rc) return rc;
   SX_REQUIRE(g->members.size() <= 1024, "too many members for the fused evaluation");
   // lookup table wanted: one pass over the events in order; otherwise over the distinct bin tuples
-  unsigned long long ne = g->members[0]->npoints;
-  const SxSignalDesc* descs = sparse ? g->d_descs_sparse.get() : g->d_descs.get();
-  const unsigned* weight = nullptr;
   if (!g->cfg_lut) {
     rc = ensure_event_classes(g, sparse);
     if (rc) return rc;
-    const sxmc_group::EventClasses& ec = g->ec[sparse ? 1 : 0];
-    ne = ec.K;
-    descs = ec.d_descs.get();
-    weight = ec.d_weight.get();
   }
-  const int block = 128;
-  const int grid = (int)std::min<unsigned long long>(1024, std::max<unsigned long long>(1, (ne + block - 1) / block));
-  SX_HIP(sx_launch_eval_nll(descs, (int)g->members.size(), ne, weight, d_pars, d_nexpected, d_n_mc, d_source_id,
-                            d_norms, d_sums, grid, block, st));
+  const StepRows rows = step_rows(g, sparse);
+  const int grid = step_sum_blocks(rows.ne);
+  SX_HIP(sx_launch_eval_nll(rows.descs, (int)g->members.size(), rows.ne, rows.weight, d_pars, d_nexpected, d_n_mc,
+                            d_source_id, d_norms, d_sums, grid, (int)sxstep::kStepSumRows, st));
   *npartial_out = grid;
   return SXMC_OK;
 }
@@ -503,43 +573,19 @@ int sxmc_group_mcmc_step_async(sxmc_group_t g, sxmc_stream_t s, const double* d_
   hipStream_t st = (hipStream_t)s;
   g->last_stream = st;
   const bool sparse = g->sparse_ready && g->cfg_sparse;
-  unsigned long long ne = g->members[0]->npoints;
-  const SxSignalDesc* descs = sparse ? g->d_descs_sparse.get() : g->d_descs.get();
-  const unsigned* weight = nullptr;
   if (!g->cfg_lut) {
     rc = ensure_event_classes(g, sparse);
     if (rc) return rc;
-    const sxmc_group::EventClasses& ec = g->ec[sparse ? 1 : 0];
-    ne = ec.K;
-    descs = ec.d_descs.get();
-    weight = ec.d_weight.get();
   }
+  const StepRows rows = step_rows(g, sparse);
   rc = group_fill(g, st, sparse);  // zero (also clears the ticket) + fill
   if (rc) return rc;
-  const int block = 128;
-  const int grid = (int)std::min<unsigned long long>(1024, std::max<unsigned long long>(1, (ne + block - 1) / block));
-  SxStepArgs a;
-  a.nsignals = g->members.size();
-  a.nsources = nsources;
-  a.means = d_means;
-  a.sigmas = d_sigmas;
-  a.rng = d_rng;
-  a.nll_current = d_nll_current;
-  a.nll_proposed = d_nll_proposed;
-  a.v_current = d_v_current;
-  a.v_proposed = d_v_proposed;
-  a.accepted = d_accepted;
-  a.counter = d_counter;
-  a.jump_buffer = d_jump_buffer;
-  a.nparameters = nparameters;
-  a.debug_mode = debug_mode;
-  a.jump_width = d_jump_width;
-  a.nexpected = d_nexpected;
-  a.n_mc = d_n_mc;
-  a.source_id = d_source_id;
-  a.norms = d_norms;
-  SX_HIP(sx_launch_eval_nll_finish(descs, (int)g->members.size(), ne, weight, g->d_step_sums.get(), g->d_ticket.get(), a, grid,
-                                   block, st));
+  const sxmc_step_args p = pack_step_args(d_means, d_sigmas, d_rng, d_nll_current, d_nll_proposed, d_v_current, d_v_proposed,
+                                          d_accepted, d_counter, d_jump_buffer, nparameters, nsources, d_jump_width,
+                                          d_nexpected, d_n_mc, d_source_id, d_norms, debug_mode);
+  SX_HIP(sx_launch_eval_nll_finish(rows.descs, (int)g->members.size(), rows.ne, rows.weight, g->d_step_sums.get(),
+                                   g->d_ticket.get() + sxstep::kTicket, sx_step_args(p, g->members.size()),
+                                   step_sum_blocks(rows.ne), (int)sxstep::kStepSumRows, st));
   return SXMC_OK;
 }
 
@@ -558,36 +604,10 @@ int sxmc_group_finish_step_async(sxmc_group_t g, sxmc_stream_t s, size_t npartia
              "null argument");
   SX_REQUIRE(nparameters > 0, "nparameters must be positive");
   if (!g->built) return fail(SXMC_ERR_STATE, "finish_step before any evaluation of the group");
-  SxStepArgs a;
-  a.nsignals = g->members.size();
-  a.nsources = nsources;
-  a.means = d_means;
-  a.sigmas = d_sigmas;
-  a.rng = d_rng;
-  a.nll_current = d_nll_current;
-  a.nll_proposed = d_nll_proposed;
-  a.v_current = d_v_current;
-  a.v_proposed = d_v_proposed;
-  a.accepted = d_accepted;
-  a.counter = d_counter;
-  a.jump_buffer = d_jump_buffer;
-  a.nparameters = nparameters;
-  a.debug_mode = debug_mode;
-  a.jump_width = d_jump_width;
-  a.nexpected = d_nexpected;
-  a.n_mc = d_n_mc;
-  a.source_id = d_source_id;
-  a.norms = d_norms;
-  const bool sparse = g->last_sparse;
-  SX_HIP(sx_launch_finish_zero(sparse ? g->d_descs_sparse.get() : g->d_descs.get(), (int)g->members.size(),
-                               sparse ? g->max_bins_sparse : g->max_bins, npartial_sums, d_sums, g->d_ticket.get(), a, 128,
-                               (hipStream_t)s));
-  g->prezeroed = sparse ? 2 : 1;
-  for (sxmc_hist* h : g->members) {
-    h->bins_valid = false;
-    h->cleared_by = g;
-  }
-  return SXMC_OK;
+  const sxmc_step_args p = pack_step_args(d_means, d_sigmas, d_rng, d_nll_current, d_nll_proposed, d_v_current, d_v_proposed,
+                                          d_accepted, d_counter, d_jump_buffer, nparameters, nsources, d_jump_width,
+                                          d_nexpected, d_n_mc, d_source_id, d_norms, debug_mode);
+  return finish_and_clear(g, (hipStream_t)s, g->last_sparse, npartial_sums, d_sums, sx_step_args(p, g->members.size()));
 }
 
 // ------------------------------------------------------------------------------ mixed fits
@@ -655,37 +675,13 @@ int sxmc_group_finish_columns_step_async(sxmc_group_t g, sxmc_stream_t s, size_t
   SX_REQUIRE(nparameters > 0, "nparameters must be positive");
   if (g->col_member.empty()) return fail(SXMC_ERR_STATE, "finish_columns_step before sxmc_group_set_columns");
   if (!g->built) return fail(SXMC_ERR_STATE, "finish_columns_step before any evaluation of the group");
-  SxStepArgs a;
-  a.nsignals = g->col_member.size();   // (the step end runs over every column; the clearing below over the members)
-  a.nsources = nsources;
-  a.means = d_means;
-  a.sigmas = d_sigmas;
-  a.rng = d_rng;
-  a.nll_current = d_nll_current;
-  a.nll_proposed = d_nll_proposed;
-  a.v_current = d_v_current;
-  a.v_proposed = d_v_proposed;
-  a.accepted = d_accepted;
-  a.counter = d_counter;
-  a.jump_buffer = d_jump_buffer;
-  a.nparameters = nparameters;
-  a.debug_mode = debug_mode;
-  a.jump_width = d_jump_width;
-  a.nexpected = d_nexpected;
-  a.n_mc = d_n_mc;
-  a.source_id = d_source_id;
-  a.norms = d_norms;
-  const bool sparse = g->last_sparse;
-  SX_HIP(sx_launch_finish_zero(sparse ? g->d_descs_sparse.get() : g->d_descs.get(), (int)g->members.size(),
-                               sparse ? g->max_bins_sparse : g->max_bins, npartial_sums, d_sums, g->d_ticket.get(), a, 128,
-                               (hipStream_t)s));
-  g->last_stream = (hipStream_t)s;
-  g->prezeroed = sparse ? 2 : 1;
-  for (sxmc_hist* h : g->members) {
-    h->bins_valid = false;
-    h->cleared_by = g;
-  }
-  return SXMC_OK;
+  const sxmc_step_args p = pack_step_args(d_means, d_sigmas, d_rng, d_nll_current, d_nll_proposed, d_v_current, d_v_proposed,
+                                          d_accepted, d_counter, d_jump_buffer, nparameters, nsources, d_jump_width,
+                                          d_nexpected, d_n_mc, d_source_id, d_norms, debug_mode);
+  // (the step end runs over every column; the clearing over the members)
+  const int rc = finish_and_clear(g, (hipStream_t)s, g->last_sparse, npartial_sums, d_sums, sx_step_args(p, g->col_member.size()));
+  if (rc == SXMC_OK) g->last_stream = (hipStream_t)s;
+  return rc;
 }
 
 }  // extern "C" (helpers below are internal)
@@ -703,11 +699,7 @@ bool step_end_takes_tail(const sxmc_group* g, bool sparse, unsigned long long ne
   const std::vector<SxSignalDesc>& flavour = sparse ? g->h_descs_sparse : g->h_descs;
   for (const SxSignalDesc& d : flavour) words += (unsigned long long)d.total_nbins;
   const unsigned long long gathers = ne * g->members.size();
-  return gathers <= kTailMaxLookups && words <= (1ull << 16) && g->cfg_tail != 0;
-}
-// workgroups of 128 rows the event sum of a step is cut into (eval_nll_kernel; eval_nll2_kernel per candidate)
-int step_sum_blocks(unsigned long long ne) {
-  return (int)std::min<unsigned long long>(1024, std::max<unsigned long long>(1, (ne + kStepSumRows - 1) / kStepSumRows));
+  return gathers <= sxstep::kTailMaxLookups && words <= (1ull << 16) && g->cfg_tail != 0;
 }
 // Does the step end run as ONE cooperative launch (step_end_kernel: workgroups that wait for each other inside the
 // kernel)?  By default (sxmc_group_set_cooperative_step_end / SXMC_COOP_STEP_END=0 switch it off), where the whole grid
@@ -761,55 +753,47 @@ bool step_is_fused(const sxmc_group* g, bool sparse, unsigned long long ne, int 
   if (!sx_fill_has_step_form(c.shape) || c.shape.threads < 128) return false;
   DeviceProps props;
   if (get_props(props)) return false;
-  const size_t staging = 16 * sizeof(double) + ((g->members.size() + 15) / 16 * 16) * 48;   // eval_nll_block_part's
+  const size_t staging = sxstep::step_end_lds_bytes(g->members.size());   // eval_nll_block_part's
   return c.shape.lds_bytes >= staging && c.shape.lds_bytes + 16 * 1024 <= (size_t)props.lds_per_cu;
 }
 
-int group_step_tail(sxmc_group* g, hipStream_t st, bool sparse, const SxSignalDesc* descs, unsigned long long ne,
-                    const unsigned* weight, const SxStepArgs& a) {
+int group_step_tail(sxmc_group* g, hipStream_t st, bool sparse, const StepRows& rows, const SxStepArgs& a) {
   TraceRange trace("sxmc: step end (lookup + event sum, finish_nll_jump_pick_combo + clearing)");
   // How much the end of the step has to touch decides its shape.  One workgroup doing all of it in one launch
   // saves a launch and a boundary, but a row costs S double divisions and a log: measured at BASELINE config 3
   // (~8000 rows x 12 members) one CU needs 59 us for what ~60 workgroups + the step-end launch do in 15.6 us, and
   // at config 2 (~2500 x 6) 16 us against 9, at the bench_pdfz shape (1000 x 1) 8 us against 7; config 1 (10 x 2)
   // gains 0.6 us of 14.7.  Only the smallest problems take it.
-  if (step_end_takes_tail(g, sparse, ne)) {
-    SX_HIP(sx_launch_tail_step(descs, (int)g->members.size(), ne, weight, a, st));
+  if (step_end_takes_tail(g, sparse, rows.ne)) {
+    SX_HIP(sx_launch_tail_step(rows.descs, (int)g->members.size(), rows.ne, rows.weight, a, st));
     g->last_step_launches += 1;
-  } else if (step_end_is_cooperative(g, ne)) {
+  } else if (step_end_is_cooperative(g, rows.ne)) {
     // ONE launch: the event sum's workgroups + a finisher that waits for them inside the kernel (step_end_kernel)
-    const int nvb = step_sum_blocks(ne);
+    const int nvb = step_sum_blocks(rows.ne);
     // up to 16 members: the workers take the lookup descriptors by value (SxStepEndTable) -- the event classes' copy, made
     // where their descriptors are uploaded, or for rows that are the events themselves the members' own descriptors as
     // the host holds them (h_descs: uploaded whenever they change)
     const sxmc_group::EventClasses& ec = g->ec[sparse ? 1 : 0];
     SxStepEndTable own;
     const SxStepEndTable* table = nullptr;
-    if (descs == ec.d_descs.get() && ec.d_descs) {
+    if (rows.descs == ec.d_descs.get() && ec.d_descs) {
       table = ec.has_table ? &ec.table : nullptr;
     } else {
       const std::vector<SxSignalDesc>& flavour = sparse ? g->h_descs_sparse : g->h_descs;
       if (sx_step_end_table_fill(own, flavour.data(), flavour.size())) table = &own;
     }
-    SX_HIP(sx_launch_step_end(descs, sparse ? g->d_descs_sparse.get() : g->d_descs.get(), (int)g->members.size(),
-                              sparse ? g->max_bins_sparse : g->max_bins, ne, weight, g->d_coop_slots.get(), g->d_coop_last.get(),
-                              g->d_ticket.get(), nvb, a, st, table));
+    SX_HIP(sx_launch_step_end(rows.descs, sparse ? g->d_descs_sparse.get() : g->d_descs.get(), (int)g->members.size(),
+                              sparse ? g->max_bins_sparse : g->max_bins, rows.ne, rows.weight, g->d_coop_slots.get(),
+                              g->d_coop_last.get(), g->d_ticket.get(), nvb, a, st, table));
     g->last_step_launches += 1;
   } else {
     g->last_step_launches += 2;
-    const int block = 128;
-    const int grid = step_sum_blocks(ne);
-    SX_HIP(sx_launch_eval_nll(descs, (int)g->members.size(), ne, weight, a.v_proposed, a.nexpected, a.n_mc, a.source_id,
-                              a.norms, g->d_step_sums.get(), grid, block, st));
-    SX_HIP(sx_launch_finish_zero(sparse ? g->d_descs_sparse.get() : g->d_descs.get(), (int)g->members.size(),
-                                 sparse ? g->max_bins_sparse : g->max_bins, (size_t)grid, g->d_step_sums.get(), g->d_ticket.get(), a,
-                                 128, st));
+    const int grid = step_sum_blocks(rows.ne);
+    SX_HIP(sx_launch_eval_nll(rows.descs, (int)g->members.size(), rows.ne, rows.weight, a.v_proposed, a.nexpected, a.n_mc,
+                              a.source_id, a.norms, g->d_step_sums.get(), grid, (int)sxstep::kStepSumRows, st));
+    return finish_and_clear(g, st, sparse, (size_t)grid, g->d_step_sums.get(), a);
   }
-  g->prezeroed = sparse ? 2 : 1;
-  for (sxmc_hist* h : g->members) {
-    h->bins_valid = false;
-    h->cleared_by = g;
-  }
+  mark_cleared(g, sparse);
   return SXMC_OK;
 }
 }  // namespace sxhost
@@ -838,38 +822,17 @@ int sxmc_group_step_async(sxmc_group_t g, sxmc_stream_t s, const double* d_means
   hipStream_t st = (hipStream_t)s;
   g->last_stream = st;
   const bool sparse = g->sparse_ready && g->cfg_sparse;
-  unsigned long long ne = g->members[0]->npoints;
-  const SxSignalDesc* descs = sparse ? g->d_descs_sparse.get() : g->d_descs.get();
-  const unsigned* weight = nullptr;
   if (!g->cfg_lut) {
     rc = ensure_event_classes(g, sparse);  // (may upload tables: before anything is launched)
     if (rc) return rc;
-    const sxmc_group::EventClasses& ec = g->ec[sparse ? 1 : 0];
-    ne = ec.K;
-    descs = ec.d_descs.get();
-    weight = ec.d_weight.get();
   }
+  const StepRows rows = step_rows(g, sparse);
+  const unsigned long long ne = rows.ne;
   const bool zero_launched = g->prezeroed != (sparse ? 2 : 1);   // (group_fill decides the same way, plus bookkeeping)
-  SxStepArgs a;
-  a.nsignals = g->members.size();
-  a.nsources = nsources;
-  a.means = d_means;
-  a.sigmas = d_sigmas;
-  a.rng = d_rng;
-  a.nll_current = d_nll_current;
-  a.nll_proposed = d_nll_proposed;
-  a.v_current = d_v_current;
-  a.v_proposed = d_v_proposed;
-  a.accepted = d_accepted;
-  a.counter = d_counter;
-  a.jump_buffer = d_jump_buffer;
-  a.nparameters = nparameters;
-  a.debug_mode = debug_mode;
-  a.jump_width = d_jump_width;
-  a.nexpected = d_nexpected;
-  a.n_mc = d_n_mc;
-  a.source_id = d_source_id;
-  a.norms = d_norms;
+  const sxmc_step_args p = pack_step_args(d_means, d_sigmas, d_rng, d_nll_current, d_nll_proposed, d_v_current, d_v_proposed,
+                                          d_accepted, d_counter, d_jump_buffer, nparameters, nsources, d_jump_width,
+                                          d_nexpected, d_n_mc, d_source_id, d_norms, debug_mode);
+  SxStepArgs a = sx_step_args(p, g->members.size());
   // THE WHOLE STEP IN ONE LAUNCH where the fill has that form (fill_step_kernel: the fill's workgroups, then a finisher
   // and the event sum's workers as later blocks of the same grid) -- not for a launch whose fill is being timed
   // (sxmc_group_profile: the fill alone is what the roofline figures are about, so profiled steps stay two launches)
@@ -879,7 +842,7 @@ int sxmc_group_step_async(sxmc_group_t g, sxmc_stream_t s, const double* d_means
     LaunchClass& c = g->classes[0];
     const int nvb = step_sum_blocks(ne);
     g->h_tail.resize(sx_tail_args_bytes());   // (passed to the kernel by value: frozen at capture like every argument)
-    sx_tail_args_fill(g->h_tail.data(), descs, g->d_descs.get(), (int)g->members.size(), g->max_bins, ne, weight,
+    sx_tail_args_fill(g->h_tail.data(), rows.descs, g->d_descs.get(), (int)g->members.size(), g->max_bins, ne, rows.weight,
                       g->d_coop_slots.get(), g->d_coop_last.get(), g->d_ticket.get(), nvb, a);
     c.shape.tail = g->h_tail.data();
     c.shape.tail_blocks = nvb + 1;
@@ -901,10 +864,10 @@ int sxmc_group_step_async(sxmc_group_t g, sxmc_stream_t s, const double* d_means
     g->split_events.push_back(ev);
     SX_HIP(hipEventRecord(ev, g->split_fill_stream));
     SX_HIP(hipStreamWaitEvent(st, ev, 0));
-    a.gate = g->d_ticket.get() + 8;
+    a.gate = g->d_ticket.get() + sxstep::kGate;
     a.gate_value = (unsigned)node + 1u;
     g->last_step_launches = (int)g->classes.size() + (zero_launched ? 1 : 0);
-    return group_step_tail(g, st, sparse, descs, ne, weight, a);
+    return group_step_tail(g, st, sparse, rows, a);
   }
 #endif
   rc = group_fill(g, st, sparse);
@@ -915,14 +878,10 @@ int sxmc_group_step_async(sxmc_group_t g, sxmc_stream_t s, const double* d_means
   if (rc) return rc;
   g->last_step_launches = (int)g->classes.size() + (zero_launched ? 1 : 0);
   if (fused) {
-    g->prezeroed = 1;
-    for (sxmc_hist* h : g->members) {
-      h->bins_valid = false;
-      h->cleared_by = g;
-    }
+    mark_cleared(g, false);   // (never sparse: step_is_fused)
     return SXMC_OK;
   }
-  return group_step_tail(g, st, sparse, descs, ne, weight, a);
+  return group_step_tail(g, st, sparse, rows, a);
 }
 
 }  // extern "C"
@@ -960,10 +919,10 @@ int sxmc_group_step_end_timeouts(sxmc_group_t g, sxmc_stream_t s, unsigned* time
   if (s) {
     // on the chain's own stream: a copy through the legacy stream is what the runtime refuses while ANOTHER host
     // thread records a graph on a blocking stream (see sxmc_graph_begin_capture)
-    SX_HIP(hipMemcpyAsync(timeouts, g->d_ticket.get() + 6, sizeof(unsigned), hipMemcpyDeviceToHost, (hipStream_t)s));
+    SX_HIP(hipMemcpyAsync(timeouts, g->d_ticket.get() + sxstep::kTimeouts, sizeof(unsigned), hipMemcpyDeviceToHost, (hipStream_t)s));
     SX_HIP(hipStreamSynchronize((hipStream_t)s));
   } else {
-    SX_HIP(hipMemcpy(timeouts, g->d_ticket.get() + 6, sizeof(unsigned), hipMemcpyDeviceToHost));
+    SX_HIP(hipMemcpy(timeouts, g->d_ticket.get() + sxstep::kTimeouts, sizeof(unsigned), hipMemcpyDeviceToHost));
   }
   if (*timeouts != 0u) {
     // A wait inside a cooperative step end gave up: the steps since the last check are not valid (a finisher that gave
@@ -973,8 +932,8 @@ int sxmc_group_step_end_timeouts(sxmc_group_t g, sxmc_stream_t s, unsigned* time
     // pre-zeroed, and the two-launch step end from now on.
     hipStream_t st = (hipStream_t)s;
     SX_HIP(hipStreamSynchronize(g->last_stream));
-    SX_HIP(sx_step_end_slots_init(g->d_coop_slots.get(), g->d_coop_last.get(), 128));
-    SX_HIP(hipMemsetAsync(g->d_ticket.get(), 0, 256, st));
+    SX_HIP(sx_step_end_slots_init(g->d_coop_slots.get(), g->d_coop_last.get(), kCoopMaxWorkers));
+    SX_HIP(hipMemsetAsync(g->d_ticket.get(), 0, sxstep::kTicketWords * sizeof(unsigned), st));
     SX_HIP(hipStreamSynchronize(st));
     g->prezeroed = 0;
     for (sxmc_hist* h : g->members) h->cleared_by = nullptr;

@@ -13,7 +13,12 @@
 //                         launch, streams, accessors (its state, shared with the next two: sxmc_kde_state.h)
 //   sxmc_kde_cv.cpp       ... its bandwidth cross-validation
 //   sxmc_kde_draw.cpp     ... what reads the last evaluation's rows: sampling and the projection
-// (the kernels: pdfz_kernels.hip, nll_kernels.hip, kde_kernels.hip, columns_kernels.hip, layout_kernels.hip, project_kernels.hip)
+// The kernels, each file with its launchers:
+//   pdfz_kernels.hip      zero, the fills (bodies: fill_kernels.inc.h) and their registry, PDF lookup, pre-binning, transposes
+//     step_end_kernels.inc.h   ... and, in the same translation unit, the end of a step in all its forms
+//                              (its grids, LDS size and ticket words: step_end_plan.h, pure)
+//   nll_kernels.hip       the reference's separate NLL entry points (device parts: nll_device.h)
+//   kde_kernels.hip, columns_kernels.hip, layout_kernels.hip, project_kernels.hip
 // Every allocation these hold is owned by a buffer (device_buffer.h over the policies below); layout_kernels.hip's host
 // helpers take their temporaries from the same type.
 #pragma once
@@ -422,7 +427,7 @@ struct sxmc_group {
   int prezeroed = 0;
   bool last_sparse = false;
   unsigned long long capture_epoch = 0;  // last recording this group launched in
-  sxhost::DeviceBuffer<unsigned> d_ticket;  // arrival counter of the fused step end, zeroed by the zero kernel
+  sxhost::DeviceBuffer<unsigned> d_ticket;  // the step ends' sxstep::kTicketWords words (the ticket, zeroed by the zero kernel; timeouts; ...)
   sxhost::DeviceBuffer<double> d_step_sums; // 1024 partial sums of the fused step
   std::vector<char> h_tail;          // fused step (fill_step_kernel): the step end's arguments, passed to the kernel by value
   sxhost::DeviceBuffer<unsigned long long> d_coop_slots;  // cooperative step end: one hand-over slot per worker (step_end_kernel)
@@ -494,13 +499,23 @@ int sample_read_back(sxmc_hist* h, size_t nobserved, size_t row, const char* why
 
 // ---- the step and its end (sxmc_group.cpp)
 extern std::atomic<int> g_stepping_groups;       // groups of this process that have stepped a chain (see note_stepping)
-constexpr int kCoopMaxWorkers = 128;
+using sxstep::kCoopMaxWorkers;
+using sxstep::step_sum_blocks;
+// the kernels' argument pack from the public one; nsignals: the columns finish_nll_jump_pick_combo runs over
+SxStepArgs sx_step_args(const sxmc_step_args& p, size_t nsignals);
+// The rows a step end walks: the event classes (their descriptors, events per class, K) or, with the lookup table
+// wanted, the events themselves.  ensure_event_classes comes first, before anything is launched: the caller's.
+struct StepRows {
+  const SxSignalDesc* descs;
+  const unsigned* weight;
+  unsigned long long ne;
+};
+StepRows step_rows(const sxmc_group* g, bool sparse);
+void mark_cleared(sxmc_group* g, bool sparse);   // a step end has cleared this flavour's histograms and normalisations
 bool step_end_takes_tail(const sxmc_group* g, bool sparse, unsigned long long ne);
-int step_sum_blocks(unsigned long long ne);
 void note_stepping(sxmc_group* g);
 bool step_end_is_cooperative(const sxmc_group* g, unsigned long long ne);
-int group_step_tail(sxmc_group* g, hipStream_t st, bool sparse, const SxSignalDesc* descs, unsigned long long ne,
-                    const unsigned* weight, const SxStepArgs& a);
+int group_step_tail(sxmc_group* g, hipStream_t st, bool sparse, const StepRows& rows, const SxStepArgs& a);
 
 }  // namespace sxhost
 

@@ -774,7 +774,7 @@ int class_tables(sxmc_group* g, const std::vector<MemberPlan>& plans, const std:
     }
     d.vec_start = prefix;
     prefix += d.nvec;
-    d.step_gate = g->d_ticket.get() + 8;     // (read by the measurement build's gated fill only)
+    d.step_gate = g->d_ticket.get() + sxstep::kGate;    // (read by the measurement build's gated fill only)
     descs.push_back(d);
   }
   c.total_vec = prefix;

@@ -182,61 +182,30 @@ int sxmc_multigroup_step_async(sxmc_multigroup_t mg, sxmc_stream_t s, const sxmc
   for (size_t c = 0; c < C && joint; c++) {
     const sxmc_group* g = mg->groups[c];
     joint = g->max_bins == g0->max_bins &&
-            !step_end_takes_tail(g, false, g->cfg_lut ? g->members[0]->npoints : g->ec[0].K);
+            !step_end_takes_tail(g, false, step_rows(g, false).ne);
   }
   SxChainEnds ends{};
   for (size_t c = 0; c < C; c++) {
     sxmc_group* g = mg->groups[c];
     const sxmc_step_args& p = args[c];
     g->last_step_launches += (int)g0->classes.size();
-    unsigned long long ne = g->members[0]->npoints;
-    const SxSignalDesc* descs = g->d_descs.get();
-    const unsigned* weight = nullptr;
-    if (!g->cfg_lut) {
-      const sxmc_group::EventClasses& ec = g->ec[0];
-      ne = ec.K;
-      descs = ec.d_descs.get();
-      weight = ec.d_weight.get();
-    }
-    SxStepArgs a;
-    a.nsignals = g->members.size();
-    a.nsources = p.nsources;
-    a.means = p.d_means;
-    a.sigmas = p.d_sigmas;
-    a.rng = p.d_rng;
-    a.nll_current = p.d_nll_current;
-    a.nll_proposed = p.d_nll_proposed;
-    a.v_current = p.d_v_current;
-    a.v_proposed = p.d_v_proposed;
-    a.accepted = p.d_accepted;
-    a.counter = p.d_counter;
-    a.jump_buffer = p.d_jump_buffer;
-    a.nparameters = p.nparameters;
-    a.debug_mode = p.debug_mode;
-    a.jump_width = p.d_jump_width;
-    a.nexpected = p.d_nexpected;
-    a.n_mc = p.d_n_mc;
-    a.source_id = p.d_source_id;
-    a.norms = p.d_norms;
+    const StepRows rows = step_rows(g, false);   // (ensure_event_classes: in the first loop, before anything was launched)
+    const SxStepArgs a = sx_step_args(p, g->members.size());
     if (joint) {
       SxChainEnd& e = ends.c[c];
-      e.lookup_descs = descs;
+      e.lookup_descs = rows.descs;
       e.hist_descs = g->d_descs.get();
-      e.nrows = ne;
-      e.weight = weight;
+      e.nrows = rows.ne;
+      e.weight = rows.weight;
       e.sums = g->d_step_sums.get();
-      e.ticket = g->d_ticket.get();
-      e.nblocks = (unsigned)step_sum_blocks(ne);
+      e.ticket = g->d_ticket.get() + sxstep::kTicket;
+      e.nblocks = (unsigned)step_sum_blocks(rows.ne);
       e.a = a;
       g->last_step_launches += 2;
-      g->prezeroed = 1;
-      for (sxmc_hist* h : g->members) {
-        h->bins_valid = false;
-        h->cleared_by = g;
-      }
+      mark_cleared(g, false);
       continue;
     }
-    int rc = group_step_tail(g, st, false, descs, ne, weight, a);
+    int rc = group_step_tail(g, st, false, rows, a);
     if (rc) return rc;
   }
   if (joint) SX_HIP(sx_launch_chain_ends(ends, (int)C, (int)g0->members.size(), g0->max_bins, 128, st));
@@ -320,30 +289,11 @@ int sxmc_multigroup_lookahead_step_async(sxmc_multigroup_t mg, sxmc_stream_t s, 
   }
   const sxmc_group::EventClasses &ea = ga->ec[0], &eb = gb->ec[0];
   const unsigned long long ne = ea.K;
-  const int block = 128;
+  const int block = (int)sxstep::kStepSumRows;
   // each candidate's event sum is cut exactly like the sequential step's (group_step_tail): the same blocks of 128
   // rows, the same cap, so the partial sums and their reduction round identically
   const int half = step_sum_blocks(ne);
-  SxStepArgs k;
-  k.nsignals = ga->members.size();
-  k.nsources = a->nsources;
-  k.means = a->d_means;
-  k.sigmas = a->d_sigmas;
-  k.rng = a->d_rng;
-  k.nll_current = a->d_nll_current;
-  k.nll_proposed = a->d_nll_proposed;
-  k.v_current = a->d_v_current;
-  k.v_proposed = a->d_v_proposed;
-  k.accepted = a->d_accepted;
-  k.counter = a->d_counter;
-  k.jump_buffer = a->d_jump_buffer;
-  k.nparameters = a->nparameters;
-  k.debug_mode = a->debug_mode;
-  k.jump_width = a->d_jump_width;
-  k.nexpected = a->d_nexpected;
-  k.n_mc = a->d_n_mc;
-  k.source_id = a->d_source_id;
-  k.norms = a->d_norms;
+  const SxStepArgs k = sx_step_args(*a, ga->members.size());
   // the pass's step end: ONE cooperative launch where both candidates' event sums fit 128 lanes of a finisher
   // (step_end2_kernel; the same switch as the sequential step's), else lookup + event sums, then step end + clearing
   const bool coop = 2 * half <= kCoopMaxWorkers && step_end_is_cooperative(ga, ne);
@@ -362,11 +312,7 @@ int sxmc_multigroup_lookahead_step_async(sxmc_multigroup_t mg, sxmc_stream_t s, 
   for (size_t c = 0; c < 2; c++) {
     sxmc_group* g = mg->groups[c];
     g->last_step_launches += (int)ga->classes.size() + (coop ? 1 : 2);
-    g->prezeroed = 1;
-    for (sxmc_hist* h : g->members) {
-      h->bins_valid = false;
-      h->cleared_by = g;
-    }
+    mark_cleared(g, false);
   }
   return SXMC_OK;
 }
