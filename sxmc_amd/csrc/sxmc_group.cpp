@@ -110,7 +110,7 @@ int sxmc_group_destroy(sxmc_group_t g) {
   if (!g) return SXMC_OK;
   (void)hipDeviceSynchronize();
   if (g->coop_fits >= 0) g_stepping_groups.fetch_sub(1, std::memory_order_acq_rel);
-  delete g;   // (its buffers, its events and the ordered twin of a boxed plan with it)
+  delete g;   // (its buffers, its events and both its launch plans with it)
   return SXMC_OK;
 }
 
@@ -136,8 +136,8 @@ int sxmc_group_optimize(sxmc_group_t g, sxmc_stream_t s, int* chosen_threads) {
   if (rc) return rc;
   // only the pure-stream launches have anything to choose: how many lanes per CU keep HBM busiest differs
   // by a few per cent from one box to the next
-  if (g->classes.empty() || g->plan_cfg.threads > 0 || g->plan_cfg.bpc > 0) return SXMC_OK;
-  for (const LaunchClass& c : g->classes)
+  if (g->plan.classes.empty() || g->plan_cfg.threads > 0 || g->plan_cfg.bpc > 0) return SXMC_OK;
+  for (const LaunchClass& c : g->plan.classes)
     if (!c.light) return SXMC_OK;
   hipStream_t st = (hipStream_t)s;
   hipEvent_t e0, e1;
@@ -145,7 +145,7 @@ int sxmc_group_optimize(sxmc_group_t g, sxmc_stream_t s, int* chosen_threads) {
   SX_HIP(hipEventCreate(&e1));
   // (over codes a lane has half the bytes per unit in flight: the larger shapes are the candidates there)
   bool has_codes = false;
-  for (const LaunchClass& c : g->classes) has_codes = has_codes || c.codes;
+  for (const LaunchClass& c : g->plan.classes) has_codes = has_codes || c.codes;
   // (threads, workgroups per CU; the first is what class_codes_shape / class_waves_per_cu take where nothing is asked for)
   typedef std::pair<int, int> Shape;
   const std::vector<Shape> candidates =
@@ -190,7 +190,7 @@ int sxmc_group_optimize(sxmc_group_t g, sxmc_stream_t s, int* chosen_threads) {
   // second choice, for bucketed tables: one team of workgroups per member or three (see class_partition: which is
   // faster differs from box to box by ~3 % either way); three must win by 1.5 % to be taken
   bool has_bucketed = false;
-  for (const LaunchClass& c : g->classes) has_bucketed = has_bucketed || (sx_form_bucketed(c.shape.form) && c.shape.lds_hist);
+  for (const LaunchClass& c : g->plan.classes) has_bucketed = has_bucketed || (sx_form_bucketed(c.shape.form) && c.shape.lds_hist);
   if (failure == SXMC_OK && has_bucketed && g->plan_cfg.teams == 0) {
     float ms_of[2] = {best_ms, 1e30f};
     for (int pass = 0; pass < 2 && failure == SXMC_OK; pass++) {
@@ -262,7 +262,7 @@ int sxmc_group_set_ordering(sxmc_group_t g, int enable) {
 int sxmc_group_set_boxes(sxmc_group_t g, int enable) {
   SX_REQUIRE(g, "null group");
   g->plan_cfg.box = enable < 0 ? -1 : enable ? 1 : 0;
-  g->box_blocked = false;
+  g->plan.box_blocked = false;
   return SXMC_OK;
 }
 
@@ -277,7 +277,7 @@ int sxmc_group_set_fill_form(sxmc_group_t g, int form) {
   SX_FLUSH();
   int rc = group_refresh(g);
   if (rc) return rc;
-  SX_REQUIRE(g->twin && !g->twin->classes.empty() && g->plan_cfg.box < 0, "the group's plan has one form only");
+  SX_REQUIRE(has_two_forms(g), "the group's plan has one form only");
   g->fill_form = form;
   return SXMC_OK;
 }
@@ -288,7 +288,7 @@ int sxmc_group_set_fill_form(sxmc_group_t g, int form) {
 static int box_image_width(sxmc_group* g, double* width) {
   *width = HUGE_VAL;
   const LaunchClass* cls = nullptr;
-  for (const LaunchClass& c : g->classes) cls = (c.dual && !cls) ? &c : cls;
+  for (const LaunchClass& c : g->plan.classes) cls = (c.dual && !cls) ? &c : cls;
   if (!cls || cls->member_idx.empty() || cls->box_obs < 0) return SXMC_OK;
   const SxSignalDesc& d = g->h_descs[(size_t)cls->member_idx[0]];
   if (!d.params) return SXMC_OK;
@@ -342,7 +342,7 @@ int sxmc_group_adapt_fill_form(sxmc_group_t g, int* form, int* changed) {
   if (t_capturing) return fail(SXMC_ERR_STATE, "the form of the fill is not chosen while a graph is being recorded");
   int rc = group_refresh(g);
   if (rc) return rc;
-  if (!(g->twin && !g->twin->classes.empty() && g->plan_cfg.box < 0)) return SXMC_OK;   // (one form only)
+  if (!has_two_forms(g)) return SXMC_OK;
   SX_HIP(hipStreamSynchronize(g->last_stream));
   double width = HUGE_VAL;
   rc = box_image_width(g, &width);
@@ -360,7 +360,7 @@ int sxmc_group_fill_form(sxmc_group_t g, int* form) {
   SX_FLUSH();
   int rc = group_refresh(g);
   if (rc) return rc;
-  *form = (g->twin && !g->twin->classes.empty() && g->plan_cfg.box < 0) ? g->fill_form : 0;
+  *form = has_two_forms(g) ? g->fill_form : 0;
   return SXMC_OK;
 }
 
@@ -385,10 +385,10 @@ int sxmc_group_codes_info(sxmc_group_t g, int* members, unsigned long long* rows
   if (rc) return rc;
   *members = 0;
   *rows = *exact_rows = *never_rows = 0;
-  for (const LaunchClass& c : g->classes) {
+  for (const LaunchClass& c : g->plan.classes) {
     if (!c.codes) continue;
     for (int idx : c.member_idx) {
-      const SampleStore::Bucketed* bk = g->member_bucket[(size_t)idx];
+      const SampleStore::Bucketed* bk = g->plan.member_bucket[(size_t)idx];
       if (!bk || !bk->d_qcol) continue;
       *members += 1;
       *rows += (unsigned long long)bk->ngranules * 256ull;
@@ -405,10 +405,10 @@ int sxmc_group_codes_windows(sxmc_group_t g, int member, int* nfields, double* b
   int rc = group_refresh(g);
   if (rc) return rc;
   *nfields = 0;
-  for (const LaunchClass& c : g->classes) {
+  for (const LaunchClass& c : g->plan.classes) {
     if (!c.codes) continue;
     for (int idx : c.member_idx) {
-      const SampleStore::Bucketed* bk = g->member_bucket[(size_t)idx];
+      const SampleStore::Bucketed* bk = g->plan.member_bucket[(size_t)idx];
       if (idx != member || !bk || !bk->d_qcol) continue;
       *nfields = bk->nq;
       for (int m = 0; m < bk->nq; m++) {
@@ -426,12 +426,12 @@ int sxmc_group_set_runtime_kernels(sxmc_group_t g, int enable) {
   return SXMC_OK;
 }
 
-// The table of a launch as sxmc_group_launch_info names it.  twin: the launch belongs to the ordered twin of a boxed plan
-// and is the form that runs now.
-static const char* table_name(const LaunchClass& c, bool twin) {
+// The table of a launch as sxmc_group_launch_info names it.  beside_boxed: the launch belongs to the ordered plan beside a
+// boxed one and is the form that runs now.
+static const char* table_name(const LaunchClass& c, bool beside_boxed) {
   const int form = c.shape.form;
   if (sx_form_boxed(form)) return c.dual ? "boxed+codes(now)|ordered+codes" : "boxed+codes";
-  if (sx_form_ordered(form) && twin) return c.codes ? "boxed+codes|ordered+codes(now)" : "boxed+codes|ordered(now)";
+  if (sx_form_ordered(form) && beside_boxed) return c.codes ? "boxed+codes|ordered+codes(now)" : "boxed+codes|ordered(now)";
   if (sx_form_ordered(form)) return c.codes ? "ordered+codes" : "ordered";
   return sx_form_bucketed(form) ? "bucketed" : form != kFormRows ? "prebinned" : "rows";
 }
@@ -442,22 +442,21 @@ int sxmc_group_launch_info(sxmc_group_t g, char* out, size_t n) {
   if (rc) return rc;
   std::string text;
   // (a plan with two forms: the launches of the form that runs now, its table named with the other form beside it)
-  const bool two = g->twin && !g->twin->classes.empty() && g->plan_cfg.box < 0;
-  const sxmc_group* plan = (two && g->fill_form == 2) ? g->twin.get() : g;
-  for (size_t i = 0; i < plan->classes.size(); i++) {
-    const LaunchClass& c = plan->classes[i];
+  const LaunchPlan& plan = active_plan(g);
+  for (size_t i = 0; i < plan.classes.size(); i++) {
+    const LaunchClass& c = plan.classes[i];
     char line[512];
     const char* kind = c.shape.rtc_fill ? "runtime" : c.shape.static_prog >= 0 ? "builtin" : c.shape.nobs ? "decoded" : "generic";
     std::snprintf(line, sizeof line,
                   "launch %zu: members=%zu nobs=%d nslot=%d hist=%s program=%s table=%s%s threads=%d grid=%d partition=%d teams=%d lds=%zu layout=0x%08X\n",
                   i, c.member_idx.size(), c.shape.nobs, c.shape.nslot, c.shape.lds_hist ? "lds" : "global", kind,
-                  table_name(c, two && plan == g->twin.get()),
+                  table_name(c, &plan == &g->ordered),
                   c.runs_mode ? (c.shape.rtc_sparse ? "+runs(runtime)" : "+runs(builtin)") : "", c.shape.threads,
                   c.shape.grid, c.partition, c.teams, (size_t)c.shape.lds_bytes, c.shape.lds_layout);
     text += line;
   }
   if (!g->rtc_note.empty()) text += "runtime specialisation failed: " + g->rtc_note.substr(0, 300) + "\n";
-  if (!g->plan_note.empty()) text += "note: " + g->plan_note + "\n";
+  if (!g->plan.note.empty()) text += "note: " + g->plan.note + "\n";
   std::snprintf(out, n, "%s", text.c_str());
   return SXMC_OK;
 }
@@ -745,11 +744,11 @@ bool step_end_is_cooperative(const sxmc_group* g, unsigned long long ne) {
 // pre-binned column: config 2), the vectors are short enough for the finisher's staged form, and the fill's LDS leaves
 // room for the roles' own.
 bool step_is_fused(const sxmc_group* g, bool sparse, unsigned long long ne, int nparameters) {
-  const int on = fused_step_requested(g) ? 1 : 0;
-  if (!on || sparse || g->classes.size() != 1 || (g->debug_mode & ~8)) return false;   // (8: the fused launch without its roles)
+  const int on = fused_step_requested(g->plan_cfg) ? 1 : 0;
+  if (!on || sparse || g->plan.classes.size() != 1 || (g->debug_mode & ~8)) return false;   // (8: the fused launch without its roles)
   if (step_end_takes_tail(g, sparse, ne) || !step_end_is_cooperative(g, ne)) return false;
   if (nparameters > 256 || g->members.size() > 256) return false;
-  const LaunchClass& c = g->classes[0];
+  const LaunchClass& c = g->plan.classes[0];
   if (!sx_fill_has_step_form(c.shape) || c.shape.threads < 128) return false;
   DeviceProps props;
   if (get_props(props)) return false;
@@ -839,7 +838,7 @@ int sxmc_group_step_async(sxmc_group_t g, sxmc_stream_t s, const double* d_means
   const bool profiled = g->prof && !t_capturing && g->prof_n < (int)g->ev0.size();
   const bool fused = !profiled && step_is_fused(g, sparse, ne, nparameters);
   if (fused) {
-    LaunchClass& c = g->classes[0];
+    LaunchClass& c = g->plan.classes[0];
     const int nvb = step_sum_blocks(ne);
     g->h_tail.resize(sx_tail_args_bytes());   // (passed to the kernel by value: frozen at capture like every argument)
     sx_tail_args_fill(g->h_tail.data(), rows.descs, g->d_descs.get(), (int)g->members.size(), g->max_bins, ne, rows.weight,
@@ -851,7 +850,7 @@ int sxmc_group_step_async(sxmc_group_t g, sxmc_stream_t s, const double* d_means
   // THE GATED STEP (measurement build only; sxmc_measure_set_gated_step): the fill goes to a stream of its own, ordered
   // after the previous FILL but not after the previous step end -- it runs its prologue beside that kernel and waits
   // for the proposal inside (fill_ordered_body, dbg bit 6); the step end follows on `s` once the fill has ended.
-  if (g->split_fill_stream && !fused && !sparse && g->classes.size() == 1 && step_end_is_cooperative(g, ne) &&
+  if (g->split_fill_stream && !fused && !sparse && g->plan.classes.size() == 1 && step_end_is_cooperative(g, ne) &&
       !step_end_takes_tail(g, sparse, ne)) {
     const int node = g->split_node & 15;
     const int saved = g->debug_mode;
@@ -866,17 +865,17 @@ int sxmc_group_step_async(sxmc_group_t g, sxmc_stream_t s, const double* d_means
     SX_HIP(hipStreamWaitEvent(st, ev, 0));
     a.gate = g->d_ticket.get() + sxstep::kGate;
     a.gate_value = (unsigned)node + 1u;
-    g->last_step_launches = (int)g->classes.size() + (zero_launched ? 1 : 0);
+    g->last_step_launches = (int)g->plan.classes.size() + (zero_launched ? 1 : 0);
     return group_step_tail(g, st, sparse, rows, a);
   }
 #endif
   rc = group_fill(g, st, sparse);
   if (fused) {
-    g->classes[0].shape.tail = nullptr;
-    g->classes[0].shape.tail_blocks = 0;
+    g->plan.classes[0].shape.tail = nullptr;
+    g->plan.classes[0].shape.tail_blocks = 0;
   }
   if (rc) return rc;
-  g->last_step_launches = (int)g->classes.size() + (zero_launched ? 1 : 0);
+  g->last_step_launches = (int)g->plan.classes.size() + (zero_launched ? 1 : 0);
   if (fused) {
     mark_cleared(g, false);   // (never sparse: step_is_fused)
     return SXMC_OK;
@@ -1013,21 +1012,8 @@ int sxmc_group_profile_read(sxmc_group_t g, double* fill_ms_total, int* nlaunche
   return SXMC_OK;
 }
 
-int sxmc_group_algorithmic_bytes(sxmc_group_t g, double* fill_read, double* hist, double* event) {
-  SX_REQUIRE(g && fill_read && hist && event, "null argument");
-  int rc = group_refresh(g);
-  if (rc) return rc;
-  if (g->twin && !g->twin->classes.empty() && g->plan_cfg.box < 0 && g->fill_form == 2) {
-    // (the ordered twin's tables are what the fill streams now; histogram and event bytes do not depend on the form)
-    double fr2 = 0, hb2 = 0, ev2 = 0, fr1 = 0;
-    rc = sxmc_group_algorithmic_bytes(g->twin.get(), &fr2, &hb2, &ev2);
-    if (rc) return rc;
-    g->fill_form = 1;
-    rc = sxmc_group_algorithmic_bytes(g, &fr1, hist, event);
-    g->fill_form = 2;
-    *fill_read = fr2;
-    return rc;
-  }
+// What an evaluation moves at the least: the tables the fills of `plan` stream; the group's histogram and event traffic.
+static void algorithmic_bytes(const sxmc_group* g, const LaunchPlan& plan, double* fill_read, double* hist, double* event) {
   double fr = 0, hb = 0, ev = 0;
   for (size_t i = 0; i < g->members.size(); i++) {
     const sxmc_hist* h = g->members[i];
@@ -1035,7 +1021,7 @@ int sxmc_group_algorithmic_bytes(sxmc_group_t g, double* fill_read, double* hist
     // columns the fill streams: float slots minus the observables covered by the pre-binned column
     int pre_w = 0, pre_dims = 0;
     bool codes = false;
-    for (const LaunchClass& c : g->classes) {
+    for (const LaunchClass& c : plan.classes) {
       for (int idx : c.member_idx) {
         if (idx == (int)i && c.shape.form != kFormRows) {
           pre_w = sx_form_pre_bytes(c.shape.form);   // (a bucketed member is counted from its copy, below)
@@ -1044,7 +1030,7 @@ int sxmc_group_algorithmic_bytes(sxmc_group_t g, double* fill_read, double* hist
         if (idx == (int)i) codes = c.codes;
       }
     }
-    if (const SampleStore::Bucketed* bk = i < g->member_bucket.size() ? g->member_bucket[i] : nullptr) {
+    if (const SampleStore::Bucketed* bk = i < plan.member_bucket.size() ? plan.member_bucket[i] : nullptr) {
       // bucketed table: the columns that change, for the samples inside the domain of the untouched observables,
       // + one word per granule
       // (ordered: that observable's column is needed only in the granules that straddle a bin edge -- which ones
@@ -1073,6 +1059,13 @@ int sxmc_group_algorithmic_bytes(sxmc_group_t g, double* fill_read, double* hist
   *fill_read = fr;
   *hist = hb;
   *event = ev;
+}
+
+int sxmc_group_algorithmic_bytes(sxmc_group_t g, double* fill_read, double* hist, double* event) {
+  SX_REQUIRE(g && fill_read && hist && event, "null argument");
+  int rc = group_refresh(g);
+  if (rc) return rc;
+  algorithmic_bytes(g, active_plan(g), fill_read, hist, event);
   return SXMC_OK;
 }
 

@@ -3,8 +3,9 @@
 // the others.  Internal.  The units, by concern:
 //   sxmc_runtime.cpp      errors, tracing, device / memory / stream / graph / event entry points, the lazy EvalFinished's
 //                         bookkeeping (settle), the capture gate
-//   sxmc_launch_plan.cpp  a group's launch plan: tables (bucketed copies, codes, sparse structures), launch classes,
-//                         partitions, refresh; event classes; the fill launches (group_fill)
+//   sxmc_launch_plan.cpp  a group's launch plans (LaunchPlan, one per form of the tables; the planner's steps take the group,
+//                         a PlanConfig and the plan they fill): tables (bucketed copies, codes, sparse structures), launch
+//                         classes, partitions, refresh; event classes; the fill launches (group_fill, over active_plan)
 //   sxmc_evaluator.cpp    the evaluator (sxmc_hist_*) and the deferred batches behind its EvalAsync / EvalFinished
 //   sxmc_group.cpp        the group entry points: configuration, autotune, evaluation, the step and its step-end forms
 //   sxmc_multigroup.cpp   lockstep chains and the look-ahead pass
@@ -331,7 +332,7 @@ struct LaunchClass {
   bool runs_mode = false;  // bucketed tables laid out in per-wave runs; the sparse flavour runs fill_sparse_kernel
   int teams = 1;           // teams of workgroups per member over a bucketed table (sxplan::interleaved_segments)
   bool codes = false;      // ordered tables: the streamed columns go as 16-bit codes (fill_ordered_body's CODES)
-  bool dual = false;       // boxed tables with an ordered twin plan beside them (sxmc_group::twin, sxmc_group_adapt_fill_form)
+  bool dual = false;       // boxed tables with the ordered plan beside them (sxmc_group::ordered, sxmc_group_adapt_fill_form)
   float box_dx = 0, box_dt = 0;   // ... mean extents of the members' granule boxes, what the choice is made from
   int box_obs = -1, box_truth = -1;   // ... the boxed observable and its truth field, as slots of the members' full descriptors
   unsigned padded_rstride = 0;  // ... with the LDS histogram in the padded form: words between its replicas (0: not)
@@ -357,6 +358,17 @@ struct PlanConfig {
            queue_log == o.queue_log && fused == o.fused;
   }
 };
+
+// What one pass of the planner produces for one form of the members' tables (sxmc_launch_plan.cpp).  What does not
+// depend on the form -- the members, their descriptors in member order -- is the group's, once.
+struct LaunchPlan {
+  std::vector<LaunchClass> classes;
+  std::vector<const SampleStore::Bucketed*> member_bucket;  // per member: the copy its fill streams, or null
+  std::string note;              // why a launch of the plan took a slower general path (for launch_info)
+  bool order_blocked = false;    // ordered tables beyond LDS could not be laid out in runs: planned without.  Never cleared.
+  bool box_blocked = false;      // boxed tables found no room for their codes / LDS form, or no ordered plan beside them: ditto.  Cleared by sxmc_group_set_boxes only.
+  void clear() { classes.clear(); member_bucket.clear(); note.clear(); }   // (the flags stay: they say what not to try again)
+};
 }  // namespace sxhost
 
 struct sxmc_group {
@@ -369,19 +381,15 @@ struct sxmc_group {
   bool sparse_ready = false;        // some member has sparse structures and all of those have points
   int max_bins_sparse = 0;
   int cfg_sparse = 1;               // count only the event bins when evaluating for lookup
-  std::vector<sxhost::LaunchClass> classes;
   sxhost::PlanConfig plan_cfg, plan_cfg_seen;      // the settings the plan depends on, and those the current plan was built with
-  bool order_blocked = false;                      // a plan with ordered tables beyond LDS could not be laid out in runs
-  bool box_blocked = false;                        // a plan with boxed tables found no room for its codes / LDS form: planned again without
-  std::unique_ptr<sxmc_group> twin;                // boxed plan, plan_cfg.box < 0: the same members planned in the ORDERED form (owned);
-                                                   // group_fill launches the one or the other (fill_form)
-  bool is_twin = false;
-  int fill_form = 2;                               // 1: the boxed plan's launches, 2: the twin's (where there is a twin)
+  sxhost::LaunchPlan plan;                         // the plan of plan_cfg
+  sxhost::LaunchPlan ordered;                      // ... and, where that one is boxed and plan_cfg.box < 0, the same members planned in
+                                                   // the ORDERED form (plan_cfg with box = 0); empty whenever the plan has one form
+  int fill_form = 2;                               // 1: the boxed plan's launches, 2: the ordered plan's (where there are two forms)
   sxhost::PinnedBuffer<double> h_pin;              // pinned host words sxmc_group_adapt_fill_form reads the parameters into
   unsigned adapt_tick = 0;                         // deferred batches launched for this group (every 256th asks for the form)
   float box_limit = 0.12f;                         // sxmc_group_adapt_fill_form: boxed while the image of a mean box is narrower (bins)
   std::string rtc_note;                            // why a run-time specialisation could not be had (last failure)
-  std::string plan_note;                           // why a launch of the plan took a slower general path (for launch_info)
   int cfg_tail = 1;                                // sxmc_group_step_async: the one-workgroup step end where it fits
   bool tuned = false;                              // a deferred batch's group: the launch-shape trials have run
   int trial_launches = 0;                          // fills sxmc_group_optimize has launched for this group (all calls)
@@ -390,7 +398,6 @@ struct sxmc_group {
                                                    //     stepping in this process fit the device many times over?
   int last_step_launches = 0;                      // kernels the last sxmc_group_step_async launched
   unsigned long long plan_generation = 0;          // counts launch plans built (a multigroup re-validates on change)
-  std::vector<const SampleStore::Bucketed*> member_bucket;  // per member: the copy its fill streams, or null
   int debug_mode = 0;
   // measurement build only (the gated step): the stream this group's NEXT step puts its fill on, beside the step end of
   // the step before (null: the step is launched on one stream, as always), and the step's index inside its recording
@@ -464,8 +471,13 @@ void member_slots(const sxmc_hist* h, std::vector<int>& slot_col);
 int fill_desc(const sxmc_hist* h, SxSignalDesc& d);   // a member's descriptor: table, slots, systematics, bindings
 void free_sparse(sxmc_hist* h);
 int build_sparse(sxmc_hist* h, const std::vector<int>& rb);
-bool fused_step_requested(const sxmc_group* g);
+bool fused_step_requested(const PlanConfig& cfg);
 int group_refresh(sxmc_group* g);
+// Has the plan two forms, and which one do the fills launch now?  Read behind a group_refresh: the ordered plan is
+// emptied by every rebuild that leaves one form, so no setting needs asking again here.
+inline bool has_two_forms(const sxmc_group* g) { return !g->ordered.classes.empty(); }
+template <class Group>   // (sxmc_group or const sxmc_group)
+auto& active_plan(Group* g) { return has_two_forms(g) && g->fill_form == 2 ? g->ordered : g->plan; }
 int group_check_bound(sxmc_group* g, bool need_pdf);
 int ensure_event_classes(sxmc_group* g, bool sparse);
 int group_prepare_fill(sxmc_group* g, hipStream_t s, bool sparse);

@@ -342,8 +342,8 @@ int get_bucketed(sxmc_hist* h, const SampleStore::BucketSort* bs, const std::vec
 // instead); the window of a field that is only read is its finite range, cut to three such widths around the
 // observables' windows when they overlap at all.  Built once per copy; left out (d_qcol stays null) when more than
 // 2 % of the rows would ask the exact columns: such a table gains nothing.
-bool codes_enabled(const sxmc_group* g) {
-  if (g->plan_cfg.codes >= 0) return g->plan_cfg.codes != 0;
+bool codes_enabled(const PlanConfig& cfg) {
+  if (cfg.codes >= 0) return cfg.codes != 0;
   static const bool on = [] {
     const char* e = std::getenv("SXMC_CODES");
     return !e || std::atoi(e) != 0;
@@ -431,20 +431,20 @@ int build_bucket_tables(sxmc_hist* h, const SampleStore::BucketSort* bs) {
 
 // The whole step in one launch (fill_step_kernel), when asked for: its role workgroups carry the fill's LDS allotment
 // and need 16 KB of their own beside it, which the plan of an ordered fill then leaves free.
-bool fused_step_requested(const sxmc_group* g) {
+bool fused_step_requested(const PlanConfig& cfg) {
   static const int env_default = [] {
     const char* e = std::getenv("SXMC_FUSED_STEP");
     return (e && e[0] == '1') ? 1 : 0;
   }();
-  return (g->plan_cfg.fused < 0 ? env_default : g->plan_cfg.fused) != 0;
+  return (cfg.fused < 0 ? env_default : cfg.fused) != 0;
 }
-
-int group_rebuild(sxmc_group* g);
 
 // ---- the launch plan, step by step.  What a step decides without the device is in sxmc_plan.h (syst_use, choose_ordered,
 // choose_boxed, compact_slots, prebin_columns, ordered_lds_layout); here: the kernel tables, the device's tables, uploads.
+// A step reads the group `g` for its members and the descriptors both forms share and `cfg` for the settings of the form it
+// plans; what it produces goes into the LaunchPlan (or the class of it) it is handed, never into the group (but rtc_note).
 
-// What a step of the plan found it cannot lay out: group_rebuild runs the pass again without that form.
+// What a step of the plan found it cannot lay out: plan_form runs the pass again without that form.
 enum class Blocked { none, order, box };
 
 inline bool is_boxed(const LaunchClass& c) { return sx_form_boxed(c.shape.form); }
@@ -464,11 +464,11 @@ struct MemberPlan {
 };
 
 // is there a kernel for this specialisation?  *fn: the run-time one, or null for a built-in one (sp: its index)
-bool have_kernel(sxmc_group* g, int lds_hist, int nobs, int nslot, int form, int runs, const std::vector<unsigned>& words,
-                 int sp, void** fn) {
+bool have_kernel(sxmc_group* g, const PlanConfig& cfg, int lds_hist, int nobs, int nslot, int form, int runs,
+                 const std::vector<unsigned>& words, int sp, void** fn) {
   *fn = nullptr;
   if (sx_fill_supports(sp, form, lds_hist, runs)) return true;
-  if (!g->plan_cfg.rtc) return false;
+  if (!cfg.rtc) return false;
   SxRtcSpec k{};
   k.nobs = nobs;
   k.nslot = nslot;
@@ -489,7 +489,8 @@ bool have_kernel(sxmc_group* g, int lds_hist, int nobs, int nslot, int form, int
 // worked out per evaluation from the granule's end values, except in the granules that straddle a bin edge.
 // box_truth >= 0: `ordered` is a BOXED observable (fill_boxed_kernel) and box_truth the slot of its truth field.
 // mp.sort stays null where the form does not apply: no such shape, no kernel, or bucketing does not pay for the table.
-int plan_bucketed(sxmc_group* g, int i, const sxplan::SystUse& use, int ordered, int box_truth, MemberPlan& mp) {
+int plan_bucketed(sxmc_group* g, const PlanConfig& cfg, LaunchPlan& plan, int i, const sxplan::SystUse& use, int ordered,
+                  int box_truth, MemberPlan& mp) {
   mp = MemberPlan{};
   LaunchClass& k = mp.cls;
   sxmc_hist* h = g->members[(size_t)i];
@@ -502,7 +503,7 @@ int plan_bucketed(sxmc_group* g, int i, const sxplan::SystUse& use, int ordered,
   const std::vector<unsigned> prog2 = sxplan::prog_words(cd);
   const int form = box_truth >= 0 ? kFormBoxed : ordered >= 0 ? kFormOrdered : kFormBucketed;
   const int sp = sx_fill_find_program(form, cd.nobs, cd.nslot, (int)prog2.size(), prog2.data());
-  if (!have_kernel(g, lds_hist, cd.nobs, cd.nslot, form, 0, prog2, sp, &k.shape.rtc_fill)) return SXMC_OK;
+  if (!have_kernel(g, cfg, lds_hist, cd.nobs, cd.nslot, form, 0, prog2, sp, &k.shape.rtc_fill)) return SXMC_OK;
   const SampleStore::BucketSort* bs = nullptr;
   int rc = get_bucket_sort(h, g->d_descs.get() + i, cs.mask, ordered, &bs, box_truth >= 0 ? d.slot_col[box_truth] : -1);
   if (rc) return rc;
@@ -516,10 +517,10 @@ int plan_bucketed(sxmc_group* g, int i, const sxplan::SystUse& use, int ordered,
   // histograms beyond LDS, evaluated at data events: per-wave runs + event bins grouped by bucket
   const bool narrow = sxplan::narrow_for_runs(d);
   k.runs_mode = !lds_hist && narrow && h->has_points && h->d_table && box_truth < 0 &&
-                have_kernel(g, lds_hist, cd.nobs, cd.nslot, form, 1, prog2, sp, &k.shape.rtc_sparse);
+                have_kernel(g, cfg, lds_hist, cd.nobs, cd.nslot, form, 1, prog2, sp, &k.shape.rtc_sparse);
   if (!lds_hist && !narrow && h->has_points && h->d_table) {
     // (a regression on very large histograms must be visible: sxmc_group_launch_info prints this)
-    g->plan_note = "histogram with a bin count or stride of 2^23 or more: the sparse counting over runs (one signed "
+    plan.note = "histogram with a bin count or stride of 2^23 or more: the sparse counting over runs (one signed "
                    "24-bit multiply-add per index) does not apply, the general sparse path runs instead";
   }
   if (k.runs_mode) {
@@ -539,7 +540,7 @@ int plan_bucketed(sxmc_group* g, int i, const sxplan::SystUse& use, int ordered,
 }
 
 // The table as it is: rows, or with the observables no systematic writes pre-binned.
-MemberPlan plan_rows(sxmc_group* g, const SxSignalDesc& d, const sxplan::SystUse& use, int lds_hist) {
+MemberPlan plan_rows(sxmc_group* g, const PlanConfig& cfg, const SxSignalDesc& d, const sxplan::SystUse& use, int lds_hist) {
   MemberPlan mp{};
   LaunchClass& k = mp.cls;
   mp.desc = d;
@@ -552,10 +553,10 @@ MemberPlan plan_rows(sxmc_group* g, const SxSignalDesc& d, const sxplan::SystUse
                      ? sx_fill_find_program(kFormRows, k.shape.nobs, k.shape.nslot, (int)k.prog.size(), k.prog.data())
                      : -1;
   k.prog_simple = spec && use.specialisable &&
-                  have_kernel(g, lds_hist, k.shape.nobs, k.shape.nslot, kFormRows, 0, k.prog, sp, &k.shape.rtc_fill);
+                  have_kernel(g, cfg, lds_hist, k.shape.nobs, k.shape.nslot, kFormRows, 0, k.prog, sp, &k.shape.rtc_fill);
   k.shape.static_prog = (k.prog_simple && !k.shape.rtc_fill) ? sp : -1;
   // pre-binning: observables that no systematic writes (built-in programs only; bucketing covers the rest)
-  if (g->plan_cfg.prebin && sx_fill_supports(k.shape.static_prog, kFormPre1, lds_hist, 0)) {   // (1 byte: so 2 bytes)
+  if (cfg.prebin && sx_fill_supports(k.shape.static_prog, kFormPre1, lds_hist, 0)) {   // (1 byte: so 2 bytes)
     const sxplan::PrebinColumns pre = sxplan::prebin_columns(d, use);
     k.pre_mask = pre.mask;
     k.shape.form = pre.width;   // (kFormPre1 / kFormPre2 ARE the column's bytes per sample; 0: nothing to pre-bin)
@@ -565,36 +566,35 @@ MemberPlan plan_rows(sxmc_group* g, const SxSignalDesc& d, const sxplan::SystUse
 
 // The form member i's table takes: boxed, ordered, bucketed, pre-binned or rows -- the first that applies, pays and
 // has a kernel.
-int plan_member(sxmc_group* g, const DeviceProps& props, int i, MemberPlan& mp) {
+int plan_member(sxmc_group* g, const PlanConfig& cfg, LaunchPlan& plan, const DeviceProps& props, int i, MemberPlan& mp) {
   sxmc_hist* h = g->members[(size_t)i];
   const SxSignalDesc& d = g->h_descs[(size_t)i];
-  const PlanConfig& cfg = g->plan_cfg;
   const int lds_hist = h->total_nbins <= kLdsMaxBins ? 1 : 0;
   const sxplan::SystUse use = sxplan::syst_use(d);
   if (cfg.bucket && d.nsyst > 0 && use.specialisable) {
-    const bool runs_possible = !g->order_blocked && h->has_points && h->d_table && (int)g->members.size() <= props.cus;
+    const bool runs_possible = !plan.order_blocked && h->has_points && h->d_table && (int)g->members.size() <= props.cus;
     const int ordered = sxplan::choose_ordered(d, use, cfg.order, lds_hist != 0, runs_possible);
     // (the boxed form: beside the ordered one, codes on)
-    const bool box_on = cfg.box != 0 && !g->box_blocked && cfg.order && lds_hist && codes_enabled(g);
+    const bool box_on = cfg.box != 0 && !plan.box_blocked && cfg.order && lds_hist && codes_enabled(cfg);
     const sxplan::BoxChoice box = sxplan::choose_boxed(d, use, box_on ? cfg.box : 0, box_strata(), lds_hist != 0);
     int rc = SXMC_OK;
     mp = MemberPlan{};
-    if (box.obs >= 0) rc = plan_bucketed(g, i, use, box.obs, box.truth, mp);
+    if (box.obs >= 0) rc = plan_bucketed(g, cfg, plan, i, use, box.obs, box.truth, mp);
     if (!rc && !mp.sort && ordered >= 0) {
-      rc = plan_bucketed(g, i, use, ordered, -1, mp);
+      rc = plan_bucketed(g, cfg, plan, i, use, ordered, -1, mp);
       if (mp.sort && !lds_hist && !mp.cls.runs_mode) mp = MemberPlan{};   // (no kernel for the runs: the unordered layout has the filter path)
     }
-    if (!rc && !mp.sort) rc = plan_bucketed(g, i, use, -1, -1, mp);
+    if (!rc && !mp.sort) rc = plan_bucketed(g, cfg, plan, i, use, -1, -1, mp);
     if (rc || mp.sort) return rc;
   }
-  mp = plan_rows(g, d, use, lds_hist);
+  mp = plan_rows(g, cfg, d, use, lds_hist);
   return SXMC_OK;
 }
 
 // The launch class of a member's plan: members with the same kernel and table form share a launch.
-LaunchClass& find_class(sxmc_group* g, MemberPlan& mp, int threads) {
+LaunchClass& find_class(LaunchPlan& plan, MemberPlan& mp, int threads) {
   const LaunchClass& k = mp.cls;
-  for (LaunchClass& c : g->classes) {
+  for (LaunchClass& c : plan.classes) {
     if (c.shape.nobs == k.shape.nobs && c.shape.nslot == k.shape.nslot && c.shape.lds_hist == k.shape.lds_hist &&
         c.prog_simple == k.prog_simple && (!k.prog_simple || c.prog == k.prog) && c.pre_mask == k.pre_mask &&
         c.shape.form == k.shape.form && c.runs_mode == k.runs_mode && c.shape.rtc_fill == k.shape.rtc_fill &&
@@ -602,9 +602,9 @@ LaunchClass& find_class(sxmc_group* g, MemberPlan& mp, int threads) {
       return c;
     }
   }
-  g->classes.push_back(std::move(mp.cls));   // (nothing reads the plan's key after this)
-  g->classes.back().shape.threads = threads;
-  return g->classes.back();
+  plan.classes.push_back(std::move(mp.cls));   // (nothing reads the plan's key after this)
+  plan.classes.back().shape.threads = threads;
+  return plan.classes.back();
 }
 
 // sparse flavour: members whose histogram exceeds LDS count into per-event-bin counters
@@ -647,9 +647,8 @@ int build_sparse_descs(sxmc_group* g) {
 }
 
 // ---- threads per workgroup and LDS of a class, before its tables are laid out.  K (runs mode): workgroups per member.
-void class_threads_and_lds(sxmc_group* g, const DeviceProps& props, const std::vector<MemberPlan>& plans, LaunchClass& c,
-                           std::vector<int>& K, Blocked& blocked) {
-  const PlanConfig& cfg = g->plan_cfg;
+void class_threads_and_lds(const sxmc_group* g, const PlanConfig& cfg, const LaunchPlan& plan, const DeviceProps& props,
+                           const std::vector<MemberPlan>& plans, LaunchClass& c, std::vector<int>& K, Blocked& blocked) {
   c.max_bins = 0;
   for (int idx : c.member_idx) c.max_bins = std::max(c.max_bins, g->h_descs[(size_t)idx].total_nbins);
   c.shape.lds_bytes = c.shape.lds_hist ? ((size_t)c.max_bins + 4 + 64) * 4 : 64;
@@ -671,7 +670,7 @@ void class_threads_and_lds(sxmc_group* g, const DeviceProps& props, const std::v
     const int rbpc = std::min(cfg.bpc > 0 ? cfg.bpc : std::max(1, 1536 / rthreads),
                               std::max(1, (int)((size_t)props.lds_per_cu / need)));
     if (need > (size_t)props.lds_per_cu || !apportion_workgroups(sizes, props.cus * rbpc, rthreads, K)) {
-      if (is_ordered(c) && !g->order_blocked) {   // the ordered layout needs the runs: plan again without it
+      if (is_ordered(c) && !plan.order_blocked) {   // the ordered layout needs the runs: plan again without it
         blocked = Blocked::order;
         return;
       }
@@ -704,8 +703,8 @@ void class_threads_and_lds(sxmc_group* g, const DeviceProps& props, const std::v
 
 // ---- the tables of a class's members, now that the shape is known (pre-binned column, bucketed copy, codes), and their
 // descriptors as the fill reads them
-int class_tables(sxmc_group* g, const std::vector<MemberPlan>& plans, const std::vector<int>& K, LaunchClass& c,
-                 std::vector<SxSignalDesc>& descs, Blocked& blocked) {
+int class_tables(const sxmc_group* g, const PlanConfig& cfg, LaunchPlan& plan, const std::vector<MemberPlan>& plans,
+                 const std::vector<int>& K, LaunchClass& c, std::vector<SxSignalDesc>& descs, Blocked& blocked) {
   const bool boxed = is_boxed(c);
   unsigned long long prefix = 0;
   for (size_t q = 0; q < c.member_idx.size(); q++) {
@@ -743,7 +742,7 @@ int class_tables(sxmc_group* g, const std::vector<MemberPlan>& plans, const std:
         c.box_dx = std::max(c.box_dx, (float)bk->box_dx);
         c.box_dt = std::max(c.box_dt, (float)bk->box_dt);
       }
-      g->member_bucket[(size_t)idx] = bk;
+      plan.member_bucket[(size_t)idx] = bk;
       // CODES: ordered table, histogram in LDS, 2 to 4 streamed fields, every systematic on them affine (one
       // coefficient) -- the conditions fill_ordered_body's kCodes states at compile time
       // (Histograms beyond LDS, counted at the event bins over run-walked tables -- BASELINE config 5 -- were given
@@ -752,7 +751,7 @@ int class_tables(sxmc_group* g, const std::vector<MemberPlan>& plans, const std:
       // units hold one; the fix-up then runs almost everywhere.  Codes pay where bins are coarse against 2^-16 of
       // the window: not offered there.)
       bool affine = is_ordered(c) && c.shape.lds_hist && c.shape.nobs >= 1 && (boxed || c.shape.nslot - 1 >= 2) &&
-                    c.shape.nslot - 1 <= SXMC_MAX_QSLOTS && !c.runs_mode && codes_enabled(g);
+                    c.shape.nslot - 1 <= SXMC_MAX_QSLOTS && !c.runs_mode && codes_enabled(cfg);
       for (unsigned w : c.prog) affine = affine && ((int)((w >> 4) & 15u) == c.shape.nslot - 1 || ((w >> 12) & 15u) == 0u);
       if (affine) {
         rc = get_bucket_codes(h, bk, d);
@@ -788,8 +787,8 @@ int class_tables(sxmc_group* g, const std::vector<MemberPlan>& plans, const std:
 // against 12 430 and 12 840 (profiles/r04b_codes_shapes_ab.log).  A histogram too large for two workgroups' LDS:
 // one of 768.  sxmc_group_optimize times these shapes on the box it runs on.
 // Sets the class's threads; returns its workgroups per CU, or 0 where the shape is not this function's to choose.
-int class_codes_shape(const sxmc_group* g, const DeviceProps& props, LaunchClass& c) {
-  if (!(c.codes && g->plan_cfg.threads <= 0 && g->plan_cfg.bpc <= 0)) return 0;
+int class_codes_shape(const PlanConfig& cfg, const DeviceProps& props, LaunchClass& c) {
+  if (!(c.codes && cfg.threads <= 0 && cfg.bpc <= 0)) return 0;
   const size_t one = std::max(c.shape.lds_bytes, sxplan::ordered_lds_bytes(sxplan::ordered_rstride_plain(c.max_bins), 1, 0)) +
                      ordered_queue_bytes(kMinQueueLog);
   bool codes_two = 2 * (one + 2048) <= (size_t)props.lds_per_cu && c.shape.nobs == 1;   // (+ the padded form's guard rows)
@@ -812,7 +811,7 @@ int class_codes_shape(const sxmc_group* g, const DeviceProps& props, LaunchClass
 // -8 % at BASELINE config 3).  Members whose per-sample arithmetic is long (a run-time decoded program
 // of two or more systematics, the shape-agnostic kernel) or that probe L2 per sample (histograms
 // beyond LDS) need the second set of waves to hide it.  codes_bpc: class_codes_shape's answer.
-int class_waves_per_cu(const sxmc_group* g, const DeviceProps& props, LaunchClass& c, int codes_bpc) {
+int class_waves_per_cu(const sxmc_group* g, const PlanConfig& cfg, const DeviceProps& props, LaunchClass& c, int codes_bpc) {
   int cls_nsyst = 0;
   for (int idx : c.member_idx) cls_nsyst = std::max(cls_nsyst, g->h_descs[(size_t)idx].nsyst);
   const bool ordered = is_ordered(c);
@@ -820,7 +819,7 @@ int class_waves_per_cu(const sxmc_group* g, const DeviceProps& props, LaunchClas
   c.light = c.shape.lds_hist && (c.shape.nobs > 0 || ordered) &&
             (c.shape.static_prog >= 0 || c.shape.rtc_fill || cls_nsyst <= 1) &&
             stream_bytes >= 2.0e8;  // (short launches are ramp-bound: they take all the waves)
-  int bpc = g->plan_cfg.bpc > 0 ? g->plan_cfg.bpc : codes_bpc ? codes_bpc : std::max(1, (c.light ? 512 : 1024) / c.shape.threads);
+  int bpc = cfg.bpc > 0 ? cfg.bpc : codes_bpc ? codes_bpc : std::max(1, (c.light ? 512 : 1024) / c.shape.threads);
   const size_t lds_need = std::max(c.shape.lds_bytes, c.shape.sparse_lds_bytes);
   const int lds_limit = std::max(1, (int)((size_t)props.lds_per_cu / std::max<size_t>(lds_need, 1)));
   return std::min(bpc, lds_limit);
@@ -828,7 +827,7 @@ int class_waves_per_cu(const sxmc_group* g, const DeviceProps& props, LaunchClas
 
 // The LDS of an ordered or boxed class with its histograms in LDS: replicas, padded or plain form, queues
 // (sxplan::ordered_lds_layout) in the workgroup's share of the CU's LDS.
-void class_lds_layout(sxmc_group* g, const DeviceProps& props, LaunchClass& c, const std::vector<SxSignalDesc>& descs,
+void class_lds_layout(const PlanConfig& cfg, const DeviceProps& props, LaunchClass& c, const std::vector<SxSignalDesc>& descs,
                       int bpc, Blocked& blocked) {
   c.shape.lds_layout = 0;
   if (!(is_ordered(c) && c.shape.lds_hist)) return;
@@ -846,9 +845,9 @@ void class_lds_layout(sxmc_group* g, const DeviceProps& props, LaunchClass& c, c
   sxplan::OrderedLdsIn in;
   in.max_bins = c.max_bins;
   in.codes = c.codes;
-  in.share = ((size_t)props.lds_per_cu - lds_reserve) / (size_t)std::max(1, bpc) - (fused_step_requested(g) ? 16 * 1024 : 0);
+  in.share = ((size_t)props.lds_per_cu - lds_reserve) / (size_t)std::max(1, bpc) - (fused_step_requested(cfg) ? 16 * 1024 : 0);
   in.rlog_max = rlog_max;
-  in.queue_cap = g->plan_cfg.queue_log;
+  in.queue_cap = cfg.queue_log;
   // the padded form of the histogram where every member qualifies (one observable binned per sample, the
   // outermost dimension) and it fits with room for the smallest queue; then the queues of ambiguous rows, in
   // what the replicas leave of the workgroup's share
@@ -867,7 +866,7 @@ void class_lds_layout(sxmc_group* g, const DeviceProps& props, LaunchClass& c, c
 }
 
 // The class's descriptors on the device, in both flavours.
-int class_upload_descs(sxmc_group* g, LaunchClass& c, const std::vector<SxSignalDesc>& descs) {
+int class_upload_descs(const sxmc_group* g, const LaunchPlan& plan, LaunchClass& c, const std::vector<SxSignalDesc>& descs) {
   SX_HIP(upload(descs, c.d_descs));
   if (!(g->sparse_ready && !c.shape.lds_hist)) return SXMC_OK;
   std::vector<SxSignalDesc> sd = descs;
@@ -892,7 +891,7 @@ int class_upload_descs(sxmc_group* g, LaunchClass& c, const std::vector<SxSignal
       sd[q].sparse_dir = owner->d_bdir.get();
       sd[q].sparse_tkeys = owner->d_btkeys.get();
       sd[q].sparse_tslot = owner->d_btslot.get();
-      sd[q].pre = g->member_bucket[(size_t)c.member_idx[q]]->d_gkp.get();   // {bucket key, bin offset} per granule
+      sd[q].pre = plan.member_bucket[(size_t)c.member_idx[q]]->d_gkp.get();   // {bucket key, bin offset} per granule
     }
   }
   SX_HIP(upload(sd, c.d_descs_sparse));
@@ -900,7 +899,7 @@ int class_upload_descs(sxmc_group* g, LaunchClass& c, const std::vector<SxSignal
 }
 
 // Who reads which units of the class's members.
-int class_partition(sxmc_group* g, LaunchClass& c, const std::vector<SxSignalDesc>& descs, const std::vector<int>& K) {
+int class_partition(const PlanConfig& cfg, LaunchClass& c, const std::vector<SxSignalDesc>& descs, const std::vector<int>& K) {
   if (c.shape.grid <= 0) return SXMC_OK;
   std::vector<SxSegment> segs;
   std::vector<unsigned> blk_off;
@@ -926,9 +925,9 @@ int class_partition(sxmc_group* g, LaunchClass& c, const std::vector<SxSignalDes
     // fill 63.4-63.5 us and step 77.9 against 65.0-65.1 and 79.9-80.0 for one team; 3-10 teams in between.)
     const bool bucketed = is_bucketed(c);
     const int groups = (bucketed && c.shape.lds_hist)
-                           ? (forced_groups > 0 ? forced_groups : g->plan_cfg.teams > 0 ? g->plan_cfg.teams : is_boxed(c) ? 20 : 1) : 1;
+                           ? (forced_groups > 0 ? forced_groups : cfg.teams > 0 ? cfg.teams : is_boxed(c) ? 20 : 1) : 1;
     c.teams = groups;
-    sxplan::build_partition(nvec, c.shape.grid, c.shape.threads, g->plan_cfg.partition, segs, blk_off, c.partition,
+    sxplan::build_partition(nvec, c.shape.grid, c.shape.threads, cfg.partition, segs, blk_off, c.partition,
                             bucketed ? 64 : 1, groups);
   }
   SX_HIP(upload(segs, c.d_segs, 1));
@@ -937,16 +936,17 @@ int class_partition(sxmc_group* g, LaunchClass& c, const std::vector<SxSignalDes
 }
 
 // One class from its members' plans to a launch: shape, tables, LDS, grid, descriptors, partition.
-int plan_class(sxmc_group* g, const DeviceProps& props, const std::vector<MemberPlan>& plans, LaunchClass& c, Blocked& blocked) {
+int plan_class(const sxmc_group* g, const PlanConfig& cfg, LaunchPlan& plan, const DeviceProps& props,
+               const std::vector<MemberPlan>& plans, LaunchClass& c, Blocked& blocked) {
   std::vector<int> K;   // runs mode: workgroups per member
-  class_threads_and_lds(g, props, plans, c, K, blocked);
+  class_threads_and_lds(g, cfg, plan, props, plans, c, K, blocked);
   if (blocked != Blocked::none) return SXMC_OK;
   std::vector<SxSignalDesc> descs;
-  int rc = class_tables(g, plans, K, c, descs, blocked);
+  int rc = class_tables(g, cfg, plan, plans, K, c, descs, blocked);
   if (rc || blocked != Blocked::none) return rc;
-  const int codes_bpc = class_codes_shape(g, props, c);   // (sets shape.threads, which the next line reads)
-  const int bpc = class_waves_per_cu(g, props, c, codes_bpc);
-  class_lds_layout(g, props, c, descs, bpc, blocked);
+  const int codes_bpc = class_codes_shape(cfg, props, c);   // (sets shape.threads, which the next line reads)
+  const int bpc = class_waves_per_cu(g, cfg, props, c, codes_bpc);
+  class_lds_layout(cfg, props, c, descs, bpc, blocked);
   if (blocked != Blocked::none) return SXMC_OK;
   const unsigned long long want = (c.total_vec + c.shape.threads - 1) / c.shape.threads;  // >= 1 unit per lane
   const unsigned long long grid = std::max<unsigned long long>(1, std::min((unsigned long long)props.cus * bpc, want));
@@ -957,99 +957,94 @@ int plan_class(sxmc_group* g, const DeviceProps& props, const std::vector<Member
     c.shape.grid = used;
     c.shape.sparse_runs = 1;
   }
-  rc = class_upload_descs(g, c, descs);
-  return rc ? rc : class_partition(g, c, descs, K);
+  rc = class_upload_descs(g, plan, c, descs);
+  return rc ? rc : class_partition(cfg, c, descs, K);
 }
 
-// BOXED plans, plan_cfg.box < 0 (the default): the boxed form is fast only while few boxes straddle an edge, which depends on
-// the parameters of the evaluation.  The same members are therefore planned a second time in the ORDERED form (a twin
-// group: its own tables, partition, launch shape), group_fill launches the plan `fill_form` names, and the host moves
-// that between flushes of a walk (sxmc_group_adapt_fill_form).  Until it is asked to, the ordered form runs: a caller
-// that never asks gets round 4's kernel.  No twin (the ordered form does not apply): the plan is built again without boxes.
-int plan_twin(sxmc_group* g, Blocked& blocked) {
-  if (g->is_twin) return SXMC_OK;
-  bool any_boxed = false;
-  for (const LaunchClass& c : g->classes) any_boxed = any_boxed || is_boxed(c);
-  const bool two = any_boxed && g->plan_cfg.box < 0;
-  if (two) {
-    if (!g->twin) {
-      g->twin = std::make_unique<sxmc_group>();
-      g->twin->is_twin = true;
-    }
-    sxmc_group* t = g->twin.get();
-    t->members = g->members;
-    t->plan_cfg = g->plan_cfg;
-    t->plan_cfg.box = 0;
-    int rc = group_rebuild(t);
-    if (rc) return rc;
-    bool ok = !t->classes.empty();
-    for (const LaunchClass& c : t->classes) ok = ok && !is_boxed(c);
-    if (!ok) {
-      blocked = Blocked::box;
-      return SXMC_OK;
-    }
-    for (LaunchClass& c : g->classes) c.dual = is_boxed(c);
-  } else if (g->twin && !any_boxed) {
-    g->twin->classes.clear();
-  }
-  if (!two) g->fill_form = 1;   // (no twin: the plan's own launches)
-  else if (g->fill_form != 1) g->fill_form = 2;
-  return SXMC_OK;
-}
-
-// One pass over the plan, from the members' descriptors to the classes' launches.  `blocked`: a step found the ordered or
-// the boxed form cannot be laid out; what the pass has allocated is freed by the next one's start.
-int plan_pass(sxmc_group* g, const DeviceProps& props, Blocked& blocked) {
+// What both forms of the plan share, once per rebuild: the members' descriptors in member order, in both flavours,
+// and what the group keeps about them.
+int plan_shared_descs(sxmc_group* g) {
   // Descriptors may still be read by kernels in flight on another stream: rebuilds are rare
   // (bindings change only during setup), so a device-wide sync is the simple safe choice.
   SX_HIP(hipDeviceSynchronize());
   const int n = (int)g->members.size();
   g->h_descs.assign((size_t)n, SxSignalDesc{});
-  g->classes.clear();
   g->max_bins = 0;
   g->max_points = 0;
   g->same_points = n > 0;
-  g->plan_note.clear();
-
-  int threads = g->plan_cfg.threads > 0 ? g->plan_cfg.threads : 512;
-  if (threads < 64 || threads > 1024 || threads % 64) threads = 512;
-
-  for (int i = 0; i < n; i++) fill_desc(g->members[i], g->h_descs[i]);
-  if (!g->d_descs) SX_BUF(g->d_descs.alloc((size_t)std::max(n, 1)));
-  if (n) SX_HIP(hipMemcpy(g->d_descs.get(), g->h_descs.data(), sizeof(SxSignalDesc) * n, hipMemcpyHostToDevice));
-
-  std::vector<MemberPlan> plans((size_t)n);
-  g->member_bucket.assign((size_t)n, nullptr);
   for (int i = 0; i < n; i++) {
     const sxmc_hist* h = g->members[i];
+    fill_desc(h, g->h_descs[i]);
     g->max_bins = std::max(g->max_bins, h->total_nbins);
     g->max_points = std::max<unsigned long long>(g->max_points, g->h_descs[i].npoints);
     if (!h->has_points || h->npoints != g->members[0]->npoints) g->same_points = false;
-    int rc = plan_member(g, props, i, plans[(size_t)i]);
-    if (rc) return rc;
-    find_class(g, plans[(size_t)i], threads).member_idx.push_back(i);
   }
-  int rc = build_sparse_descs(g);
-  if (rc) return rc;
-  for (LaunchClass& c : g->classes) {
-    rc = plan_class(g, props, plans, c, blocked);
-    if (rc || blocked != Blocked::none) return rc;
-  }
-  return plan_twin(g, blocked);
+  if (!g->d_descs) SX_BUF(g->d_descs.alloc((size_t)std::max(n, 1)));
+  if (n) SX_HIP(hipMemcpy(g->d_descs.get(), g->h_descs.data(), sizeof(SxSignalDesc) * n, hipMemcpyHostToDevice));
+  return build_sparse_descs(g);
 }
 
+// One pass over a plan, from the members' forms to the classes' launches.  `blocked`: a step found the ordered or the
+// boxed form cannot be laid out; what the pass has allocated is freed by the next one's start.
+int plan_pass(sxmc_group* g, const PlanConfig& cfg, const DeviceProps& props, LaunchPlan& plan, Blocked& blocked) {
+  plan.clear();
+  int threads = cfg.threads > 0 ? cfg.threads : 512;
+  if (threads < 64 || threads > 1024 || threads % 64) threads = 512;
+  const int n = (int)g->members.size();
+  std::vector<MemberPlan> plans((size_t)n);
+  plan.member_bucket.assign((size_t)n, nullptr);
+  for (int i = 0; i < n; i++) {
+    int rc = plan_member(g, cfg, plan, props, i, plans[(size_t)i]);
+    if (rc) return rc;
+    find_class(plan, plans[(size_t)i], threads).member_idx.push_back(i);
+  }
+  for (LaunchClass& c : plan.classes) {
+    int rc = plan_class(g, cfg, plan, props, plans, c, blocked);
+    if (rc || blocked != Blocked::none) return rc;
+  }
+  return SXMC_OK;
+}
+
+// The plan of `cfg`: passes until no step is blocked (at most three: each of the plan's two flags is set once).
+int plan_form(sxmc_group* g, const PlanConfig& cfg, const DeviceProps& props, LaunchPlan& plan) {
+  for (;;) {
+    Blocked blocked = Blocked::none;
+    int rc = plan_pass(g, cfg, props, plan, blocked);
+    if (rc || blocked == Blocked::none) return rc;
+    (blocked == Blocked::order ? plan.order_blocked : plan.box_blocked) = true;
+  }
+}
+
+inline bool any_boxed(const LaunchPlan& plan) { return std::any_of(plan.classes.begin(), plan.classes.end(), is_boxed); }
+
+// BOXED plans, plan_cfg.box < 0 (the default): the boxed form is fast only while few boxes straddle an edge, which depends on
+// the parameters of the evaluation.  The same members are therefore planned a second time in the ORDERED form (g->ordered:
+// the same passes with box = 0 over the same descriptors), group_fill launches the plan `fill_form` names, and the host
+// moves that between flushes of a walk (sxmc_group_adapt_fill_form).  Until it is asked to, the ordered form runs: a caller
+// that never asks gets round 4's kernel.  No ordered plan (the form does not apply): the plan is built again without boxes.
 int group_rebuild(sxmc_group* g) {
   TraceRange trace("sxmc: launch plan (tables, partitions, kernels)");
   DeviceProps props;
   int rc = get_props(props);
   if (rc) return rc;
-  for (;;) {   // (at most three passes: each of the two flags is set once)
-    Blocked blocked = Blocked::none;
-    rc = plan_pass(g, props, blocked);
+  rc = plan_shared_descs(g);
+  if (rc) return rc;
+  bool two = false;
+  for (;;) {
+    rc = plan_form(g, g->plan_cfg, props, g->plan);
     if (rc) return rc;
-    if (blocked == Blocked::none) break;
-    (blocked == Blocked::order ? g->order_blocked : g->box_blocked) = true;
+    two = g->plan_cfg.box < 0 && any_boxed(g->plan);
+    if (!two) break;
+    PlanConfig ordered_cfg = g->plan_cfg;
+    ordered_cfg.box = 0;
+    rc = plan_form(g, ordered_cfg, props, g->ordered);
+    if (rc) return rc;
+    if (!g->ordered.classes.empty() && !any_boxed(g->ordered)) break;
+    g->plan.box_blocked = true;
   }
+  if (!two) g->ordered.clear();   // (what has_two_forms asks)
+  for (LaunchClass& c : g->plan.classes) c.dual = two && is_boxed(c);
+  g->fill_form = two && g->fill_form != 1 ? 2 : 1;   // (one form: the plan's own launches; a form of 1 survives a replan)
   const size_t n = g->members.size();
   g->seen.resize(n);
   g->seen_points.resize(n);
@@ -1200,9 +1195,8 @@ int group_fill(sxmc_group* g, hipStream_t s, bool sparse) {
   sparse = sparse && g->sparse_ready && g->cfg_sparse;
   int rc = group_prepare_fill(g, s, sparse);
   if (rc) return rc;
-  // (a boxed plan with an ordered twin: the launches of the plan fill_form names -- sxmc_group_adapt_fill_form)
-  sxmc_group* plan = (g->twin && !g->twin->classes.empty() && g->fill_form == 2 && g->plan_cfg.box < 0) ? g->twin.get() : g;
-  for (LaunchClass& c : plan->classes) {
+  // (a plan with two forms: the launches of the one fill_form names -- sxmc_group_adapt_fill_form)
+  for (LaunchClass& c : active_plan(g).classes) {
     // profiled launches (sxmc_group_profile) carry two events stamped with the dispatch's own begin and end
     const bool rec = g->prof && !t_capturing && g->prof_n < (int)g->ev0.size() && c.shape.grid > 0;
     c.shape.ev_start = rec ? (void*)g->ev0[g->prof_n] : nullptr;

@@ -19,7 +19,7 @@ bool multigroup_prepare(sxmc_multigroup* mg) {
   mg->why_not.clear();
   for (size_t c = 1; c < C; c++) {
     sxmc_group* g = mg->groups[c];
-    if (g->members.size() != g0->members.size() || g->classes.size() != g0->classes.size()) {
+    if (g->members.size() != g0->members.size() || g->plan.classes.size() != g0->plan.classes.size()) {
       mg->why_not = "the chains' groups differ in members or launches";
       return false;
     }
@@ -33,17 +33,17 @@ bool multigroup_prepare(sxmc_multigroup* mg) {
   }
   DeviceProps props;
   if (get_props(props)) return false;
-  mg->fill_fn.assign(g0->classes.size(), nullptr);
-  mg->lds_bytes.assign(g0->classes.size(), 0);
-  mg->fill_w.assign(g0->classes.size(), 0u);
-  for (size_t i = 0; i < g0->classes.size(); i++) {
-    const LaunchClass& c0 = g0->classes[i];
+  mg->fill_fn.assign(g0->plan.classes.size(), nullptr);
+  mg->lds_bytes.assign(g0->plan.classes.size(), 0);
+  mg->fill_w.assign(g0->plan.classes.size(), 0u);
+  for (size_t i = 0; i < g0->plan.classes.size(); i++) {
+    const LaunchClass& c0 = g0->plan.classes[i];
     if (!lockstep_class_ok(c0)) {
       mg->why_not = "a launch of the plan has its histogram beyond LDS, a run-time decoded program or a pre-binned column";
       return false;
     }
     for (size_t c = 1; c < C; c++) {
-      const LaunchClass& cc = mg->groups[c]->classes[i];
+      const LaunchClass& cc = mg->groups[c]->plan.classes[i];
       if (cc.shape.nobs != c0.shape.nobs || cc.shape.nslot != c0.shape.nslot || cc.shape.lds_hist != c0.shape.lds_hist ||
           cc.shape.form != c0.shape.form || cc.prog != c0.prog || cc.prog_simple != c0.prog_simple ||
           cc.shape.grid != c0.shape.grid || cc.shape.threads != c0.shape.threads || cc.member_idx != c0.member_idx ||
@@ -165,11 +165,11 @@ int sxmc_multigroup_step_async(sxmc_multigroup_t mg, sxmc_stream_t s, const sxmc
   }
   // ONE pass over the tables for all chains
   sxmc_group* g0 = mg->groups[0];
-  for (size_t i = 0; i < g0->classes.size(); i++) {
-    const LaunchClass& c0 = g0->classes[i];
+  for (size_t i = 0; i < g0->plan.classes.size(); i++) {
+    const LaunchClass& c0 = g0->plan.classes[i];
     if (c0.shape.grid <= 0) continue;
     SxChainDescsHost ch{};
-    for (size_t c = 0; c < C; c++) ch.d[c] = mg->groups[c]->classes[i].d_descs.get();
+    for (size_t c = 0; c < C; c++) ch.d[c] = mg->groups[c]->plan.classes[i].d_descs.get();
     const bool rec = g0->prof && !t_capturing && g0->prof_n < (int)g0->ev0.size();
     SX_HIP(sx_rtc_launch_multi(mg->fill_fn[i], c0.shape.grid, c0.shape.threads, mg->lds_bytes[i], ch, c0.d_segs.get(),
                                c0.d_blk_off.get(), mg->fill_w[i], (unsigned)mg->groups[0]->debug_mode, st,
@@ -188,7 +188,7 @@ int sxmc_multigroup_step_async(sxmc_multigroup_t mg, sxmc_stream_t s, const sxmc
   for (size_t c = 0; c < C; c++) {
     sxmc_group* g = mg->groups[c];
     const sxmc_step_args& p = args[c];
-    g->last_step_launches += (int)g0->classes.size();
+    g->last_step_launches += (int)g0->plan.classes.size();
     const StepRows rows = step_rows(g, false);   // (ensure_event_classes: in the first loop, before anything was launched)
     const SxStepArgs a = sx_step_args(p, g->members.size());
     if (joint) {
@@ -275,12 +275,12 @@ int sxmc_multigroup_lookahead_step_async(sxmc_multigroup_t mg, sxmc_stream_t s, 
     if (rc) return rc;
     g->last_step_launches = zero_launched ? 1 : 0;
   }
-  for (size_t i = 0; i < ga->classes.size(); i++) {
-    const LaunchClass& c0 = ga->classes[i];
+  for (size_t i = 0; i < ga->plan.classes.size(); i++) {
+    const LaunchClass& c0 = ga->plan.classes[i];
     if (c0.shape.grid <= 0) continue;
     SxChainDescsHost ch{};
-    ch.d[0] = ga->classes[i].d_descs.get();
-    ch.d[1] = gb->classes[i].d_descs.get();
+    ch.d[0] = ga->plan.classes[i].d_descs.get();
+    ch.d[1] = gb->plan.classes[i].d_descs.get();
     const bool rec = ga->prof && !t_capturing && ga->prof_n < (int)ga->ev0.size();
     SX_HIP(sx_rtc_launch_multi(mg->fill_fn[i], c0.shape.grid, c0.shape.threads, mg->lds_bytes[i], ch, c0.d_segs.get(),
                                c0.d_blk_off.get(), mg->fill_w[i], (unsigned)mg->groups[0]->debug_mode, st,
@@ -311,7 +311,7 @@ int sxmc_multigroup_lookahead_step_async(sxmc_multigroup_t mg, sxmc_stream_t s, 
   }
   for (size_t c = 0; c < 2; c++) {
     sxmc_group* g = mg->groups[c];
-    g->last_step_launches += (int)ga->classes.size() + (coop ? 1 : 2);
+    g->last_step_launches += (int)ga->plan.classes.size() + (coop ? 1 : 2);
     mark_cleared(g, false);
   }
   return SXMC_OK;
@@ -320,7 +320,7 @@ int sxmc_multigroup_lookahead_step_async(sxmc_multigroup_t mg, sxmc_stream_t s, 
 int sxmc_group_lookahead_supported(sxmc_group_t g, int* ok) {
   SX_REQUIRE(g && ok, "null argument");
   *ok = 0;
-  g->plan_cfg.box = 0;   // (the look-ahead pass runs over the ordered form: the question is asked of that plan)
+  g->plan_cfg.box = 0;   // (the pass runs over the ordered form; the question could be asked of g->ordered and leave the setting alone)
   int rc = group_refresh(g);
   if (rc) return rc;
   if (!g->same_points || g->cfg_lut || (g->sparse_ready && g->cfg_sparse) || g->members.empty()) return SXMC_OK;
@@ -332,7 +332,7 @@ int sxmc_group_lookahead_supported(sxmc_group_t g, int* ok) {
   // will require of every launch of the plan
   DeviceProps props;
   if (get_props(props)) return SXMC_OK;
-  for (const LaunchClass& c : g->classes) {
+  for (const LaunchClass& c : g->plan.classes) {
     if (!lockstep_class_ok(c)) return SXMC_OK;
     // one histogram's words: an ordered table's `w` is the layout word, whose low 24 bits are the words between replicas
     const unsigned w = sx_fill_w(c.shape);

@@ -256,6 +256,83 @@ def test_boxed_plan_comes_with_an_ordered_twin():
     assert group.FillForm() == 0 and "table=boxed+codes " in group.LaunchInfo()
 
 
+def data_events(rng, tabs, n):
+    """n events [e, r, c, DATASET] drawn from the tables' rows, a few of them outside the domain or on its ends."""
+    rows = np.concatenate([t[rng.integers(0, t.shape[0], size=n // len(tabs) + 1), :3] for t in tabs])[:n]
+    ev = np.zeros((n, 4), np.float32)
+    ev[:, :3] = rows
+    ev[rng.choice(n, size=7, replace=False), 0] = [50.0, -1.0, 9.999999, 10.0, np.inf, 0.0, -0.0]
+    return ev
+
+
+def test_new_events_of_the_same_count_reach_both_forms_without_a_replan():
+    """Both forms of a plan read the group's ONE set of member descriptors.  New evaluation points of the same count
+    patch those descriptors in place, with no replan (group_update_points): bins, normalisations and looked-up values
+    are then the same bits in either form, and the bits of a group built on the new events with boxes off.
+
+    Tables: config 3's, at the smallest size at which a member's default plan is boxed and so has two forms -- 4
+    granules of 256 rows per edge (20 bins + 1), unwritten bucket (20) and stratum (2): 860 160 rows
+    (sxplan::choose_boxed)."""
+    rng = np.random.default_rng(68)
+    sizes = [860160, 860160 + 4099]
+    tabs = [c3_table(rng, n, j) for j, n in enumerate(sizes)]
+    S, E = len(tabs), 3001
+    params = [0.02, -0.004, 0.01]
+    old_events, new_events = data_events(rng, tabs, E), data_events(rng, tabs, E)
+    assert not np.array_equal(old_events.view(np.uint32), new_events.view(np.uint32))
+
+    def build(events):
+        group, evs, norms, pbuf = make_group(tabs, C3, params)
+        lut = DeviceArray(np.full(S * E, 777.0, np.float32))
+        for j, e in enumerate(evs):
+            e.SetEvalPoints(events)
+            e.SetPDFValueBuffer(lut, j * E, 1)
+        return group, evs, norms, lut
+
+    def both_forms(group, evs, norms, lut):
+        got = {}
+        for form in (1, 2):
+            group.SetFillForm(form)
+            assert group.FillForm() == form
+            group.EvalAsync(True)
+            group.EvalFinished()
+            got[form] = ([e.GetBins() for e in evs], norms.get(), lut.get().view(np.uint32), group.LaunchInfo(),
+                         group.AlgorithmicBytes())
+        return got
+
+    def same(a, b):
+        return all(np.array_equal(x, y) for x, y in zip(a[0], b[0])) and np.array_equal(a[1], b[1]) and np.array_equal(a[2], b[2])
+
+    group, evs, norms, lut = build(old_events)
+    assert group.FillForm() == 2 and "boxed+codes|ordered+codes(now)" in group.LaunchInfo(), group.LaunchInfo()
+    before = both_forms(group, evs, norms, lut)
+    assert same(before[1], before[2])
+    for e in evs:
+        e.SetEvalPoints(new_events)
+    after = both_forms(group, evs, norms, lut)
+    for form in (1, 2):
+        assert after[form][3] == before[form][3], (form, before[form][3], after[form][3])      # the plan, as it was
+        b, a = before[form][4], after[form][4]
+        assert a["fill_read"] == b["fill_read"] and a["hist"] == b["hist"], (form, b, a)
+        assert a["event"] == b["event"] == 16.0 * E * S, (form, b, a)
+    assert before[1][4]["fill_read"] < before[2][4]["fill_read"] and before[1][4]["hist"] == before[2][4]["hist"]
+    assert same(after[1], after[2])
+    assert not np.array_equal(after[1][2], before[1][2])                 # (the new events are looked up)
+    assert all(np.array_equal(x, y) for x, y in zip(after[1][0], before[1][0]))   # (the histograms do not depend on them)
+
+    fresh, evs2, norms2, lut2 = build(new_events)
+    fresh.SetBoxes(False)
+    assert fresh.FillForm() == 0 and "boxed" not in fresh.LaunchInfo()
+    fresh.EvalAsync(True)
+    fresh.EvalFinished()
+    want = ([e.GetBins() for e in evs2], norms2.get(), lut2.get().view(np.uint32))
+    assert same(after[1], want) and same(after[2], want)
+    for j, t in enumerate(tabs):      # ... and they are the oracle's
+        o = oracle_eval(t, 5, LO, HI, NB, C3, params, points=new_events)
+        assert np.array_equal(want[0][j], o["bins"]) and want[1][j] == o["norm"]
+        assert np.array_equal(want[2][j * E:(j + 1) * E], o["out"].view(np.uint32))
+
+
 def test_walks_are_the_same_chain_in_either_form():
     """A walk over a plan with both forms: forced boxed, forced ordered, and left to sxmc_group_adapt_fill_form (asked at
     the first step and at every flush, the recorded steps recorded again when the form changes) -- the fills are
