@@ -438,11 +438,17 @@ int sxmc_kde_project(sxmc_kde_t k, int obs, int nbins, double* h_prob);
  * lookup.  Waits for the evaluator.
  * sxmc_kde_cutoff_boxes (for tests: a host replay of the visit test): the tile boxes the last evaluation wrote,
  * [tiles][9] floats lo[4], hi[4], smallest g, and the wave boxes of the point plan, [pitch / 64][8] floats lo[4], hi[4],
- * pitch the points rounded up to 256.  SXMC_ERR_STATE without a cutoff or points. */
+ * pitch the points rounded up to 256.  SXMC_ERR_STATE without a cutoff or points.
+ * sxmc_kde_pair_split (for tests: which regime of the pair sum a shape reaches on this device): the split of the
+ * current point plan, with or without a cutoff -- the pair sum's next launch has nsplit workgroups to every 256 points,
+ * each over tiles_per_split tiles of 256 sample rows (the last split: what is left of them).  It depends on the points,
+ * the table, the device's compute units and whether a cutoff is set.  Reads the plan only: no launch, no wait.
+ * SXMC_ERR_STATE without points. */
 int sxmc_kde_set_cutoff(sxmc_kde_t k, double R);
 int sxmc_kde_cutoff(sxmc_kde_t k, double* R);
 int sxmc_kde_cutoff_stats(sxmc_kde_t k, unsigned long long* tiles_visited, unsigned long long* tiles_possible);
 int sxmc_kde_cutoff_boxes(sxmc_kde_t k, float* tile_boxes, size_t ntile_floats, float* wave_boxes, size_t nwave_floats);
+int sxmc_kde_pair_split(sxmc_kde_t k, int* nsplit, unsigned* tiles_per_split);
 /* scale[0 .. nobservables): the bandwidth scales the evaluator was created with (a shared evaluator: its base's). */
 int sxmc_kde_bandwidth_scale(sxmc_kde_t k, double* scale, size_t n);
 /* Bandwidths by leave-one-out likelihood cross-validation (Silverman 3.4.4): the bandwidths that maximise the

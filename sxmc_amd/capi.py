@@ -134,6 +134,7 @@ SIGNATURES = {
     "sxmc_kde_cutoff": [_vp, _pd],
     "sxmc_kde_cutoff_stats": [_vp, C.POINTER(C.c_ulonglong), C.POINTER(C.c_ulonglong)],
     "sxmc_kde_cutoff_boxes": [_vp, _vp, _sz, _vp, _sz],
+    "sxmc_kde_pair_split": [_vp, _pi, C.POINTER(C.c_uint)],
     "sxmc_kde_cv_scores": [_vp, _vp, _i, _sz, _vp, _psz],
     "sxmc_kde_cv_select": [_vp, _d, _d, _i, _i, _sz, _vp, _sz, _pd, _pd, _vp, _psz, _pi, _vp, _vp, _vp],
     "sxmc_group_create": [_vp, _i, _pvp],

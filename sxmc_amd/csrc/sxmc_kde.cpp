@@ -626,6 +626,13 @@ int sxmc_kde_cutoff_boxes(sxmc_kde_t k, float* tile_boxes, size_t ntile_floats, 
   SX_HIP(hipMemcpy(wave_boxes, k->cut.d_wave_box.get(), sizeof(float) * nwave_floats, hipMemcpyDeviceToHost));
   return SXMC_OK;
 }
+int sxmc_kde_pair_split(sxmc_kde_t k, int* nsplit, unsigned* tiles_per_split) {
+  SX_REQUIRE(k && nsplit && tiles_per_split, "null argument");
+  if (!k->has_points) return fail(SXMC_ERR_STATE, "EvalKernel: no pair split without evaluation points");
+  *nsplit = k->nsplit;
+  *tiles_per_split = k->tiles_per_split;
+  return SXMC_OK;
+}
 int sxmc_kde_npoints(sxmc_kde_t k, size_t* v) {
   SX_REQUIRE(k && v, "null argument");
   *v = k->has_points ? k->npoints : 0;

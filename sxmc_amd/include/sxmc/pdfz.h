@@ -648,6 +648,10 @@ class EvalKernel : public detail::EvalOver<detail::KernelApi> {
   void CutoffStats(unsigned long long& tiles_visited, unsigned long long& tiles_possible) const {
     throw_on(sxmc_kde_cutoff_stats(handle, &tiles_visited, &tiles_possible));
   }
+  /** Of the current point plan: the pair sum's workgroups to every 256 points, and the sample tiles each walks. */
+  void PairSplit(int& nsplit, unsigned& tiles_per_split) const {
+    throw_on(sxmc_kde_pair_split(handle, &nsplit, &tiles_per_split));
+  }
 
   /** The bandwidths h_d fixed at construction (Scott's rule). */
   std::vector<double> Bandwidths() const {

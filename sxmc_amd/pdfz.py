@@ -408,6 +408,13 @@ class EvalKernel(_Eval):
         self._call("cutoff_boxes", capi.ptr(tiles), tiles.size, capi.ptr(waves), waves.size)
         return tiles, waves
 
+    def PairSplit(self):
+        """(nsplit, tiles_per_split) of the current point plan: the workgroups to every 256 points of the pair sum's
+        next launch and the 256-row sample tiles each walks (sxmc_kde_pair_split; for tests).  Launches nothing."""
+        nsplit, tps = C.c_int(0), C.c_uint(0)
+        self._call("pair_split", C.byref(nsplit), C.byref(tps))
+        return nsplit.value, tps.value
+
     def Bandwidths(self):
         """h_d = bandwidth_scale_d * sigma_d * n^(-1/(D+4)) (Scott's rule), fixed at construction."""
         out = np.empty(self.nobservables, dtype=np.float64)

@@ -53,12 +53,19 @@ class CutoffRef:
     c_max: float
 
 
-def ref_cutoff(samples, nfields, nobs, lower, upper, scale, alpha, systs, params, points, R, dataset=0, also_drop=0.8):
+def ref_cutoff(samples, nfields, nobs, lower, upper, scale, alpha, systs, params, points, R, dataset=0, also_drop=0.8,
+               lam=None):
+    """lam: the local factors of every table row as an INPUT (float64 [rows]) instead of ref_local_factors, whose cost
+    grows as rows^2 -- for tables too large for it; only read when alpha > 0."""
     lower, upper = np.asarray(lower, np.float64), np.asarray(upper, np.float64)
     D = nobs
     h = ref_bandwidths(samples, nfields, D, lower, upper, scale)
     nrows = np.asarray(samples).size // nfields
-    lam = ref_local_factors(samples, nfields, D, lower, upper, scale, alpha) if alpha > 0 else np.ones(nrows)
+    if alpha > 0 and lam is not None:
+        lam = np.array(lam, np.float64)
+        assert lam.shape == (nrows,) and np.all(lam > 0)
+    else:
+        lam = ref_local_factors(samples, nfields, D, lower, upper, scale, alpha) if alpha > 0 else np.ones(nrows)
     s = ref_transform(samples, nfields, systs, params)[:, :D]
     with np.errstate(invalid="ignore"):
         inside = np.all((s >= lower) & (s < upper), axis=1)
@@ -193,6 +200,42 @@ def cutoff_points(D, E, rng, lower, upper):
         p[2, :D] = lower + 0.21 * wid
         p[2, D] = 1.0
     return p.astype(np.float32).ravel()
+
+
+# The shapes at which a workgroup of the culled pair sum walks many tiles (tests/test_gpu_kde_cutoff_splits.py):
+# (points, sample rows), the smallest at which kde_plan.h's pair_split followed by kde_cutoff.h's cutoff_split gives,
+# on 256 compute units, the split named -- which the GPU tests read back from the evaluator, not from here.
+REGIMES = {
+    "A": (16384, 24700),       # (25, 4): several bits in one ballot; the last split holds 1 tile of 4
+    "A'": (16384, 130000),     # (32, 16): 16 bits; the last split holds 12
+    "B1": (524188, 17000),     # (1, 67): two rounds of 64 tiles, the second with 3 lanes
+    "B2": (262144, 35000),     # (2, 69): two rounds in each split; the second split clipped to 68
+    "C1": (100000, 10400),     # plain (41, 1) becomes (21, 2): cutoff_split doubles; the last split holds 1
+    "C2": (100000, 131072),    # plain 2 tiles per split becomes (32, 16): the doubling taken three times
+}
+SUBSAMPLE = 1024               # at most this many of the caller's points are compared
+PAIRS_PER_CASE = 2.5e7         # ... and about this many pairs, so that a case's reference takes a few seconds
+
+
+def regime_inputs(name, D, rows=None):
+    """(samples, nfields, lower, upper, points) of a regime at D observables; rows: a smaller table from the same
+    generator (the points stay the same: they have a generator of their own)."""
+    npts, nrows = REGIMES[name]
+    seed = 8800 + 10 * sorted(REGIMES).index(name) + D
+    samples, nf, lower, upper = cutoff_table(D, nrows if rows is None else rows, np.random.default_rng(seed))
+    return samples, nf, lower, upper, cutoff_points(D, npts, np.random.default_rng(seed + 100), lower, upper)
+
+
+def strided(npts, nrows=0):
+    """The places of the caller's points that are compared: the three special points of cutoff_points, every stride-th
+    from the first, and the last -- at most SUBSAMPLE of them, fewer against a table of many rows."""
+    if npts <= SUBSAMPLE:
+        return np.arange(npts)
+    want = int(min(SUBSAMPLE, max(128, PAIRS_PER_CASE // max(nrows, 1)))) - 3
+    stride = -(-npts // want)
+    idx = np.unique(np.concatenate([[0, 1, 2, npts - 1], np.arange(0, npts, stride)]))
+    assert len(idx) <= SUBSAMPLE and idx[-1] == npts - 1
+    return idx
 
 
 def clip_table(N=1000):

@@ -14,7 +14,8 @@ from sxmc_amd import capi, pdfz
 from tests.test_abi import declared_symbols, exported
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-NEW_ENTRY_POINTS = {"sxmc_kde_set_cutoff", "sxmc_kde_cutoff", "sxmc_kde_cutoff_stats", "sxmc_kde_cutoff_boxes"}
+NEW_ENTRY_POINTS = {"sxmc_kde_set_cutoff", "sxmc_kde_cutoff", "sxmc_kde_cutoff_stats", "sxmc_kde_cutoff_boxes",
+                    "sxmc_kde_pair_split"}
 
 
 @pytest.mark.parametrize("flags", [["-O2"], ["-O1", "-g", "-fsanitize=address,undefined",
@@ -33,7 +34,7 @@ def test_new_entry_points_are_declared_exported_and_in_the_ctypes_table():
     assert NEW_ENTRY_POINTS <= set(declared_symbols())
     assert NEW_ENTRY_POINTS <= exported(capi.LIB_PATH)
     assert NEW_ENTRY_POINTS <= set(capi.SIGNATURES)
-    for name in ("SetCutoff", "Cutoff", "CutoffStats"):
+    for name in ("SetCutoff", "Cutoff", "CutoffStats", "PairSplit"):
         assert callable(getattr(pdfz.EvalKernel, name))
 
 
@@ -49,3 +50,5 @@ def test_invalid_radii_are_refused_without_a_device():
     assert lib.sxmc_kde_cutoff(None, C.byref(v)) == capi.ERR_INVALID
     a, b = C.c_ulonglong(0), C.c_ulonglong(0)
     assert lib.sxmc_kde_cutoff_stats(None, C.byref(a), C.byref(b)) == capi.ERR_INVALID
+    n, t = C.c_int(0), C.c_uint(0)
+    assert lib.sxmc_kde_pair_split(None, C.byref(n), C.byref(t)) == capi.ERR_INVALID
