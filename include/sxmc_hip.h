@@ -28,6 +28,7 @@ extern "C" {
 #define SXMC_ERR_INVALID 1 /* argument validation failed: where the reference throws pdfz::Error */
 #define SXMC_ERR_HIP 2     /* a HIP runtime call failed (reference: checkCuda) */
 #define SXMC_ERR_STATE 3   /* call sequence error, e.g. eval before the buffers are bound */
+#define SXMC_ERR_SHAPE 4   /* a shape the requested form has no kernel for (a proposal factor beyond 256 parameters) */
 
 #define SXMC_MAX_NFIELDS 10   /* pdfz.cpp:17 MAX_NFIELDS */
 #define SXMC_MAX_SYST 16      /* systematics per evaluator (reference: unbounded array, pdfz.cpp:126-132) */
@@ -661,6 +662,38 @@ int sxmc_group_launch_info(sxmc_group_t g, char* out, size_t n);
  * rounding (the terms are added in another order); the work no longer grows with the number of
  * events.  sxmc_group_eval_async always writes the table. */
 int sxmc_group_set_lut_output(sxmc_group_t g, int enable);
+/* CORRELATED PROPOSALS (opt-in; NULL, the default, is the reference's diagonal proposal, bit for bit).  With a factor
+ * set, every step end this group launches -- sxmc_group_step_async in all its forms (one-workgroup, cooperative,
+ * two-launch, fused), sxmc_group_mcmc_step_async, sxmc_group_finish_step_async, sxmc_group_finish_columns_step_async --
+ * writes the next proposal as
+ *     v_proposed[i] = v_current[i] + d_i,   d_i = sum_{j <= i} L_ij z_j   for a free parameter i (jump width > 0),
+ *     v_proposed[i] = v_current[i]                                        for a fixed one,
+ * where z is exactly the diagonal proposal's draw (same generators, order and offsets; z_j = 0 for a fixed j), d_i
+ * starts at 0 and takes its terms in ascending j, each as ONE fused multiply-add in double, and the final addition is
+ * rounded once.  The widths d_jump_width still say which parameters are free; their magnitudes are not read.
+ * LAYOUT: d_factor holds P x P doubles (P = nparameters), COLUMN-major: L_ij at d_factor[j * P + i], so that lanes
+ * i, i + 1, ... read consecutive addresses for a fixed j.  Only j <= i is read.  The pointer is BORROWED: it must stay
+ * valid while steps are in flight or recorded in a graph; its CONTENTS may change between steps (a re-tuning rewrites
+ * them in place, and recorded graphs stay valid).  The product is formed before the step end waits for the event sums.
+ * At step time SXMC_ERR_SHAPE beyond 256 parameters or 256 signals (the step end's unstaged form has no such product).
+ * The look-ahead pass and lockstep sets have no correlated form: with a factor set on a member group
+ * sxmc_multigroup_step_async and sxmc_multigroup_lookahead_step_async return SXMC_ERR_STATE, and
+ * sxmc_group_lookahead_supported answers 0. */
+int sxmc_group_set_proposal_factor(sxmc_group_t g, const double* d_factor);
+/* The re-tuning of a correlated proposal, on the host (no device call; usable without a GPU).  rows: nrows kept rows
+ * of the jump buffer, nparameters + 1 floats each (the last is the NLL, not read); new_widths: the widths AFTER the
+ * reference's re-tuning (<= 0: a fixed parameter).  With every float widened to double and every sum taken
+ * sequentially in row order:
+ *   mean_j = (sum_r x_rj) / nrows;  S_jk = sum_r (x_rj - mean_j)(x_rk - mean_k);
+ *   R_jk = S_jk / (sqrt(S_jj) sqrt(S_kk)), R_jj = 1; a column with S_jj == 0 (or no rows) is decoupled: its row and
+ *   column of R are the identity's;  R_b = (1 - b) R + b I off the diagonal, 1 on it, b = shrinkage in (0, 1];
+ *   T = the Cholesky factor of R_b row by row (Cholesky-Banachiewicz); a pivot that is not positive doubles b (capped at
+ *   1, where T = I) and the factorisation starts again;  L = diag((double)new_widths) T.
+ * Rows and columns of fixed parameters are zero.  factor: nparameters^2 doubles in sxmc_group_set_proposal_factor's
+ * layout (all of them written); shrinkage_used (optional): the b that succeeded.  nrows == 0: L = diag(new_widths).
+ * SXMC_ERR_INVALID: a null argument (rows may be null when nrows == 0), nparameters < 1, shrinkage outside (0, 1]. */
+int sxmc_proposal_factor(const float* rows, size_t nrows, int nparameters, const float* new_widths, double shrinkage,
+                         double* factor, double* shrinkage_used);
 int sxmc_group_eval_async(sxmc_group_t g, int do_eval_pdf, sxmc_stream_t s);
 /* As sxmc_group_eval_async(g, 1, s) followed by nll_event_chunks (nll_kernels.cpp:89-116) over
  * the members' lookup table, with the table lookup and the event sum fused in one kernel: the
@@ -930,6 +963,21 @@ int sxmc_launch_finish_nll_jump_pick_combo(int grid, int block, sxmc_stream_t s,
                                            const double* d_nexpected, const unsigned* d_n_mc,
                                            const short* d_source_id, const unsigned* d_norms,
                                            int debug_mode);
+/* The same with a correlated proposal's factor (sxmc_group_set_proposal_factor: law and layout), for walks that have no
+ * group to carry it.  d_factor == NULL: exactly the launch above.  SXMC_ERR_SHAPE with a factor and more than 256
+ * parameters or signals. */
+int sxmc_launch_finish_nll_jump_pick_combo_factor(int grid, int block, sxmc_stream_t s,
+                                                  size_t npartial_sums, const double* d_sums,
+                                                  size_t nsignals, size_t nsources,
+                                                  const double* d_means, const double* d_sigmas,
+                                                  sxmc_rng_state* d_rng, double* d_nll_current,
+                                                  double* d_nll_proposed, double* d_v_current,
+                                                  double* d_v_proposed, int* d_accepted,
+                                                  int* d_counter, float* d_jump_buffer,
+                                                  int nparameters, const float* d_jump_width,
+                                                  const double* d_nexpected, const unsigned* d_n_mc,
+                                                  const short* d_source_id, const unsigned* d_norms,
+                                                  int debug_mode, const double* d_factor);
 
 /* ---------------------------------------------------------------- multi-GPU exchange (RCCL) ----- */
 /* Fake experiments shard over the GPUs of a node one experiment per rank with NO data-path collective

@@ -13,7 +13,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 # SXMC_HIP_LIB selects another build of the same library (A/B experiments on kernel variants)
 LIB_PATH = os.environ.get("SXMC_HIP_LIB") or os.path.join(_HERE, "csrc", "libsxmc_hip.so")
 
-OK, ERR_INVALID, ERR_HIP, ERR_STATE = 0, 1, 2, 3
+OK, ERR_INVALID, ERR_HIP, ERR_STATE, ERR_SHAPE = 0, 1, 2, 3, 4
 MAX_NFIELDS, MAX_SYST, MAX_SYST_PARS = 10, 16, 8
 SYST_SHIFT, SYST_SCALE, SYST_RESOLUTION_SCALE, SYST_CTSCALE = 0, 1, 2, 3
 
@@ -159,6 +159,8 @@ SIGNATURES = {
     "sxmc_group_set_runtime_kernels": [_vp, _i],
     "sxmc_group_launch_info": [_vp, C.c_char_p, _sz],
     "sxmc_group_set_lut_output": [_vp, _i],
+    "sxmc_group_set_proposal_factor": [_vp, _vp],
+    "sxmc_proposal_factor": [_vp, _sz, _i, _vp, _d, _vp, _pd],
     "sxmc_group_eval_async": [_vp, _i, _vp],
     "sxmc_group_eval_nll_async": [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _pi],
     "sxmc_group_mcmc_step_async": [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _sz, _vp,
@@ -197,6 +199,8 @@ SIGNATURES = {
     "sxmc_launch_nll_total": [_i, _i, _vp, _sz, _vp, _sz, _sz, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp],
     "sxmc_launch_finish_nll_jump_pick_combo": [_i, _i, _vp, _sz, _vp, _sz, _sz, _vp, _vp, _vp, _vp, _vp,
                                                _vp, _vp, _vp, _vp, _vp, _i, _vp, _vp, _vp, _vp, _vp, _i],
+    "sxmc_launch_finish_nll_jump_pick_combo_factor": [_i, _i, _vp, _sz, _vp, _sz, _sz, _vp, _vp, _vp, _vp, _vp,
+                                                      _vp, _vp, _vp, _vp, _vp, _i, _vp, _vp, _vp, _vp, _vp, _i, _vp],
     "sxmc_comm_init_all": [_vp, _i, _pvp],
     "sxmc_comm_unique_id": [C.c_char_p, _sz],
     "sxmc_comm_init_rank": [C.c_char_p, _sz, _i, _i, _pvp],

@@ -192,9 +192,10 @@ __device__ __forceinline__ bool finish_step_device_w(size_t npartial_sums, const
                                                      int nparameters, const float* jump_width,
                                                      const double* nexpected, const unsigned* n_mc,
                                                      const short* source_id, const unsigned* norms,
-                                                     bool debug_mode, Wait&& wait) {
+                                                     const double* factor, bool debug_mode, Wait&& wait) {
   __shared__ double s_wave[17];
   __shared__ double s_vprop[kStage], s_vcur[kStage], s_z[kStage];
+  __shared__ double s_d[kStage];            // with a factor: the next proposal's displacement (L z)_i, formed in phase A
   __shared__ double s_add[2 * kStage];      // phase B's addends in its order: the signals' terms, then the constraints'
   __shared__ float s_jw[kStage];
   __shared__ unsigned s_badw[16];           // per wave: one of its parameters is a negative source rate
@@ -257,6 +258,8 @@ __device__ __forceinline__ bool finish_step_device_w(size_t npartial_sums, const
       if (i == 0) s_u = rng_uniform(&st);            // jump_decider's draw (nll_kernels.cpp:63)
       s_z[i] = (jw > 0) ? rng_normal(&st) : 0.0;     // pick_new_vector's draw (:42), free parameters only
       rng[i].offset = st.offset;
+    } else if (factor != nullptr) {
+      s_z[i] = 0.0;   // a fixed parameter draws nothing and its z is 0: the product below reads every z_j, j <= i
     }
   }
   for (int j = threadIdx.x; j < (int)nsignals; j += (int)bdim) {
@@ -284,6 +287,31 @@ __device__ __forceinline__ bool finish_step_device_w(size_t npartial_sums, const
   for (int w = 0; w < nwaves; w++) bad = bad || s_badw[w] != 0u;
   const double nc = s_nc, u = s_u;
   const int count = s_count, nacc = s_nacc;
+  // The correlated proposal (include/sxmc_hip.h, sxmc_group_set_proposal_factor): lane i's displacement d_i = sum over
+  // j <= i of L_ij z_j, ascending in j, one fma per term -- here, behind the barrier that published s_z and ahead of the
+  // wait, so that it runs under the event sums of the other workgroups; phase C adds it to whichever vector the decision
+  // leaves.  L_ij stands at factor[j * P + i]: for a fixed j a wave's lanes read consecutive doubles, and z_j is one LDS
+  // word for all of them (a broadcast).  The loads do not depend on the chain of fmas: eight are in flight at a time.
+  // s_d[i] is written and read by the same lane (the same stride in phase C): no barrier of its own.
+  if (factor != nullptr) {
+    for (int i = threadIdx.x; i < nparameters; i += (int)bdim) {
+      double d = 0.0;
+      if (s_jw[i] > 0) {
+        const double* col = factor + i;
+        const size_t P = (size_t)nparameters;
+        int j = 0;
+        for (; j + 8 <= i + 1; j += 8) {
+          double l[8];
+#pragma unroll
+          for (int k = 0; k < 8; k++) l[k] = col[(size_t)(j + k) * P];
+#pragma unroll
+          for (int k = 0; k < 8; k++) d = __fma_rn(l[k], s_z[j + k], d);
+        }
+        for (; j <= i; j++) d = __fma_rn(col[(size_t)j * P], s_z[j], d);
+      }
+      s_d[i] = d;
+    }
+  }
   wait();
   const double total_sum = block_sum<BD>(npartial_sums, sums, s_wave);  // barriers inside
 
@@ -316,7 +344,11 @@ __device__ __forceinline__ bool finish_step_device_w(size_t npartial_sums, const
     const double cur = accept ? s_vprop[i] : s_vcur[i];
     if (accept) v_current[i] = cur;
     jump_buffer[row + i] = (float)cur;
-    v_proposed[i] = (s_jw[i] > 0) ? cur + s_jw[i] * s_z[i] : cur;  // :40-47
+    if (factor != nullptr) {
+      v_proposed[i] = (s_jw[i] > 0) ? __dadd_rn(cur, s_d[i]) : cur;
+    } else {
+      v_proposed[i] = (s_jw[i] > 0) ? cur + s_jw[i] * s_z[i] : cur;  // :40-47
+    }
   }
   if (threadIdx.x == 0) jump_buffer[row + nparameters] = (float)nllcur;
   return accept;
@@ -331,10 +363,10 @@ __device__ __forceinline__ bool finish_step_device(size_t npartial_sums, const d
                                                    int nparameters, const float* jump_width,
                                                    const double* nexpected, const unsigned* n_mc,
                                                    const short* source_id, const unsigned* norms,
-                                                   bool debug_mode) {
+                                                   const double* factor, bool debug_mode) {
   return finish_step_device_w<0, R>(npartial_sums, sums, nsignals, nsources, means, sigmas, rng, nll_current, nll_proposed,
                               v_current, v_proposed, accepted, counter, jump_buffer, nparameters, jump_width, nexpected,
-                              n_mc, source_id, norms, debug_mode, [] {});
+                              n_mc, source_id, norms, factor, debug_mode, [] {});
 }
 
 // What the NEXT call of finish_step_device would propose if the step it decides were rejected -- i.e. from the

@@ -134,10 +134,10 @@ __global__ void finish_nll_jump_pick_combo_kernel(size_t npartial_sums, const do
                                                   int nparameters, const float* jump_width,
                                                   const double* nexpected, const unsigned* n_mc,
                                                   const short* source_id, const unsigned* norms,
-                                                  bool debug_mode) {
+                                                  const double* factor, bool debug_mode) {
   finish_step_device(npartial_sums, sums, nsignals, nsources, means, sigmas, rng, nll_current, nll_proposed,
                      v_current, v_proposed, accepted, counter, jump_buffer, nparameters, jump_width, nexpected,
-                     n_mc, source_id, norms, debug_mode);
+                     n_mc, source_id, norms, factor, debug_mode);
 }
 
 }  // namespace
@@ -198,10 +198,11 @@ hipError_t sx_nll_finish_combo(int block, hipStream_t s, size_t npartial, const 
                                double* nll_current, double* nll_proposed, double* v_current, double* v_proposed,
                                int* accepted, int* counter, float* jump_buffer, int nparameters,
                                const float* jump_width, const double* nexpected, const unsigned* n_mc,
-                               const short* source_id, const unsigned* norms, bool debug_mode) {
+                               const short* source_id, const unsigned* norms, const double* factor,
+                               bool debug_mode) {
   hipLaunchKernelGGL(finish_nll_jump_pick_combo_kernel, dim3(1), dim3(block), 0, s, npartial, sums, nsignals,
                      nsources, means, sigmas, rng, nll_current, nll_proposed, v_current, v_proposed, accepted,
-                     counter, jump_buffer, nparameters, jump_width, nexpected, n_mc, source_id, norms,
+                     counter, jump_buffer, nparameters, jump_width, nexpected, n_mc, source_id, norms, factor,
                      debug_mode);
   return hipGetLastError();
 }

@@ -35,6 +35,10 @@ struct SxStepArgs {
   // measurement build only (the gated step): the finisher stores gate_value to *gate once the next proposal is written
   unsigned* gate = nullptr;
   unsigned gate_value = 0;
+  // the correlated proposal's lower-triangular factor, P x P doubles with L_ij at [j * P + i], or null: the diagonal
+  // proposal (include/sxmc_hip.h, sxmc_group_set_proposal_factor).  Staged step ends only (at most 256 parameters and
+  // signals); the look-ahead pass and the lockstep sets' joint ends never get one.
+  const double* factor = nullptr;
 };
 
 // The cooperative step end's look-up pointers BY VALUE (step_end_kernel<true>): per member the two tables a worker's

@@ -7,8 +7,16 @@ using namespace sxhost;
 namespace sxhost {
 std::atomic<int> g_stepping_groups{0};
 
-SxStepArgs sx_step_args(const sxmc_step_args& p, size_t nsignals) {
+int proposal_factor_check(const double* factor, int nparameters, size_t nsignals) {
+  if (factor && (nparameters > 256 || nsignals > 256)) {
+    return fail(SXMC_ERR_SHAPE, "a proposal factor needs the staged step end: at most 256 parameters and 256 signals");
+  }
+  return SXMC_OK;
+}
+
+SxStepArgs sx_step_args(const sxmc_step_args& p, size_t nsignals, const double* factor) {
   SxStepArgs a;   // (the measurement build's gate keeps its defaults)
+  a.factor = factor;
   a.nsignals = nsignals;
   a.nsources = p.nsources;
   a.means = p.d_means;
@@ -467,6 +475,12 @@ int sxmc_group_set_lut_output(sxmc_group_t g, int enable) {
   return SXMC_OK;
 }
 
+int sxmc_group_set_proposal_factor(sxmc_group_t g, const double* d_factor) {
+  SX_REQUIRE(g, "null group");
+  g->proposal_factor = d_factor;   // (borrowed; read by sx_step_args at every step end the group launches)
+  return SXMC_OK;
+}
+
 #if SXMC_MEASURE
 // measurement build only, THE GATED STEP: the group's next sxmc_group_step_async puts its fill on `fill_stream` (null:
 // back to one stream) as step `node` (0 .. 15) of a recording; sxmc_measure_stream_fork makes `to` wait for what `from`
@@ -563,6 +577,7 @@ int sxmc_group_mcmc_step_async(sxmc_group_t g, sxmc_stream_t s, const double* d_
                  d_norms,
              "null argument");
   SX_REQUIRE(nparameters > 0, "nparameters must be positive");
+  if (int bad = proposal_factor_check(g->proposal_factor, nparameters, g->members.size())) return bad;
   int rc = group_refresh(g);
   if (rc) return rc;
   rc = group_check_bound(g, true);
@@ -583,7 +598,8 @@ int sxmc_group_mcmc_step_async(sxmc_group_t g, sxmc_stream_t s, const double* d_
                                           d_accepted, d_counter, d_jump_buffer, nparameters, nsources, d_jump_width,
                                           d_nexpected, d_n_mc, d_source_id, d_norms, debug_mode);
   SX_HIP(sx_launch_eval_nll_finish(rows.descs, (int)g->members.size(), rows.ne, rows.weight, g->d_step_sums.get(),
-                                   g->d_ticket.get() + sxstep::kTicket, sx_step_args(p, g->members.size()),
+                                   g->d_ticket.get() + sxstep::kTicket,
+                                   sx_step_args(p, g->members.size(), g->proposal_factor),
                                    step_sum_blocks(rows.ne), (int)sxstep::kStepSumRows, st));
   return SXMC_OK;
 }
@@ -606,7 +622,9 @@ int sxmc_group_finish_step_async(sxmc_group_t g, sxmc_stream_t s, size_t npartia
   const sxmc_step_args p = pack_step_args(d_means, d_sigmas, d_rng, d_nll_current, d_nll_proposed, d_v_current, d_v_proposed,
                                           d_accepted, d_counter, d_jump_buffer, nparameters, nsources, d_jump_width,
                                           d_nexpected, d_n_mc, d_source_id, d_norms, debug_mode);
-  return finish_and_clear(g, (hipStream_t)s, g->last_sparse, npartial_sums, d_sums, sx_step_args(p, g->members.size()));
+  if (int rc = proposal_factor_check(g->proposal_factor, nparameters, g->members.size())) return rc;
+  return finish_and_clear(g, (hipStream_t)s, g->last_sparse, npartial_sums, d_sums,
+                          sx_step_args(p, g->members.size(), g->proposal_factor));
 }
 
 // ------------------------------------------------------------------------------ mixed fits
@@ -678,7 +696,9 @@ int sxmc_group_finish_columns_step_async(sxmc_group_t g, sxmc_stream_t s, size_t
                                           d_accepted, d_counter, d_jump_buffer, nparameters, nsources, d_jump_width,
                                           d_nexpected, d_n_mc, d_source_id, d_norms, debug_mode);
   // (the step end runs over every column; the clearing over the members)
-  const int rc = finish_and_clear(g, (hipStream_t)s, g->last_sparse, npartial_sums, d_sums, sx_step_args(p, g->col_member.size()));
+  if (int rc = proposal_factor_check(g->proposal_factor, nparameters, g->col_member.size())) return rc;
+  const int rc = finish_and_clear(g, (hipStream_t)s, g->last_sparse, npartial_sums, d_sums,
+                                  sx_step_args(p, g->col_member.size(), g->proposal_factor));
   if (rc == SXMC_OK) g->last_stream = (hipStream_t)s;
   return rc;
 }
@@ -811,6 +831,7 @@ int sxmc_group_step_async(sxmc_group_t g, sxmc_stream_t s, const double* d_means
                  d_norms,
              "null argument");
   SX_REQUIRE(nparameters > 0, "nparameters must be positive");
+  if (int bad = proposal_factor_check(g->proposal_factor, nparameters, g->members.size())) return bad;
   int rc = group_refresh(g);
   if (rc) return rc;
   rc = group_check_bound(g, true);
@@ -831,7 +852,7 @@ int sxmc_group_step_async(sxmc_group_t g, sxmc_stream_t s, const double* d_means
   const sxmc_step_args p = pack_step_args(d_means, d_sigmas, d_rng, d_nll_current, d_nll_proposed, d_v_current, d_v_proposed,
                                           d_accepted, d_counter, d_jump_buffer, nparameters, nsources, d_jump_width,
                                           d_nexpected, d_n_mc, d_source_id, d_norms, debug_mode);
-  SxStepArgs a = sx_step_args(p, g->members.size());
+  SxStepArgs a = sx_step_args(p, g->members.size(), g->proposal_factor);
   // THE WHOLE STEP IN ONE LAUNCH where the fill has that form (fill_step_kernel: the fill's workgroups, then a finisher
   // and the event sum's workers as later blocks of the same grid) -- not for a launch whose fill is being timed
   // (sxmc_group_profile: the fill alone is what the roofline figures are about, so profiled steps stay two launches)

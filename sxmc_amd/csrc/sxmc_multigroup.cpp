@@ -124,6 +124,12 @@ int sxmc_multigroup_step_async(sxmc_multigroup_t mg, sxmc_stream_t s, const sxmc
   SX_REQUIRE(mg && args, "null argument");
   hipStream_t st = (hipStream_t)s;
   const size_t C = mg->groups.size();
+  for (const sxmc_group* g : mg->groups) {
+    if (g->proposal_factor) {
+      return fail(SXMC_ERR_STATE, "a member group has a proposal factor set: lockstep sets have no correlated step end "
+                                  "-- step the chains one by one (sxmc_group_step_async)");
+    }
+  }
   // every chain's own plan first (may upload: before anything is launched)
   bool replan = mg->seen.size() != C;
   for (size_t c = 0; c < C; c++) {
@@ -232,6 +238,12 @@ int sxmc_multigroup_lookahead_step_async(sxmc_multigroup_t mg, sxmc_stream_t s, 
                  a->d_nexpected && a->d_n_mc && a->d_source_id && a->d_norms && a->nparameters > 0,
              "null argument");
   SX_REQUIRE(a->nparameters <= 256, "the look-ahead walk stages its vectors in LDS: at most 256 parameters");
+  for (const sxmc_group* g : mg->groups) {
+    if (g->proposal_factor) {
+      return fail(SXMC_ERR_STATE, "a member group has a proposal factor set: the look-ahead pass has no correlated form "
+                                  "-- walk sequentially (sxmc_group_lookahead_supported says so beforehand)");
+    }
+  }
   hipStream_t st = (hipStream_t)s;
   bool replan = mg->seen.size() != 2;
   for (size_t c = 0; c < 2; c++) {
@@ -320,6 +332,7 @@ int sxmc_multigroup_lookahead_step_async(sxmc_multigroup_t mg, sxmc_stream_t s, 
 int sxmc_group_lookahead_supported(sxmc_group_t g, int* ok) {
   SX_REQUIRE(g && ok, "null argument");
   *ok = 0;
+  if (g->proposal_factor) return SXMC_OK;   // (no correlated look-ahead pass; asked before the group is touched)
   g->plan_cfg.box = 0;   // (the pass runs over the ordered form; the question could be asked of g->ordered and leave the setting alone)
   int rc = group_refresh(g);
   if (rc) return rc;

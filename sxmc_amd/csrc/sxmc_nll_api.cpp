@@ -2,6 +2,8 @@
 // the test hooks.
 #include "sxmc_host.h"
 
+#include "proposal_factor.h"
+
 using namespace sxhost;
 
 extern "C" {
@@ -93,7 +95,38 @@ int sxmc_launch_finish_nll_jump_pick_combo(int grid, int block, sxmc_stream_t s,
   SX_HIP(sx_nll_finish_combo(block, (hipStream_t)s, npartial_sums, d_sums, nsignals, nsources, d_means, d_sigmas,
                              d_rng, d_nll_current, d_nll_proposed, d_v_current, d_v_proposed, d_accepted,
                              d_counter, d_jump_buffer, nparameters, d_jump_width, d_nexpected, d_n_mc, d_source_id,
-                             d_norms, debug_mode != 0));
+                             d_norms, nullptr, debug_mode != 0));
+  return SXMC_OK;
+}
+
+int sxmc_launch_finish_nll_jump_pick_combo_factor(int grid, int block, sxmc_stream_t s, size_t npartial_sums,
+                                                  const double* d_sums, size_t nsignals, size_t nsources,
+                                                  const double* d_means, const double* d_sigmas, sxmc_rng_state* d_rng,
+                                                  double* d_nll_current, double* d_nll_proposed, double* d_v_current,
+                                                  double* d_v_proposed, int* d_accepted, int* d_counter,
+                                                  float* d_jump_buffer, int nparameters, const float* d_jump_width,
+                                                  const double* d_nexpected, const unsigned* d_n_mc,
+                                                  const short* d_source_id, const unsigned* d_norms, int debug_mode,
+                                                  const double* d_factor) {
+  SX_FLUSH();
+  SX_ORDER(s);
+  if (int rc = check_launch(grid, block)) return rc;
+  SX_REQUIRE(grid == 1, "finish_nll_jump_pick_combo runs in one workgroup");
+  if (int rc = proposal_factor_check(d_factor, nparameters, nsignals)) return rc;
+  SX_HIP(sx_nll_finish_combo(block, (hipStream_t)s, npartial_sums, d_sums, nsignals, nsources, d_means, d_sigmas,
+                             d_rng, d_nll_current, d_nll_proposed, d_v_current, d_v_proposed, d_accepted,
+                             d_counter, d_jump_buffer, nparameters, d_jump_width, d_nexpected, d_n_mc, d_source_id,
+                             d_norms, d_factor, debug_mode != 0));
+  return SXMC_OK;
+}
+
+// The re-tuning of a correlated proposal: host arithmetic only (proposal_factor.h), nothing of the device is touched.
+int sxmc_proposal_factor(const float* rows, size_t nrows, int nparameters, const float* new_widths, double shrinkage,
+                         double* factor, double* shrinkage_used) {
+  SX_REQUIRE(nparameters >= 1 && new_widths && factor && (rows || nrows == 0), "bad arguments");
+  SX_REQUIRE(shrinkage > 0.0 && shrinkage <= 1.0, "the proposal shrinkage must lie in (0, 1]");
+  const double used = sxproposal::proposal_factor(rows, nrows, (size_t)nparameters, new_widths, shrinkage, factor);
+  if (shrinkage_used) *shrinkage_used = used;
   return SXMC_OK;
 }
 

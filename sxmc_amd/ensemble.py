@@ -354,11 +354,12 @@ def projection_interval(values, cl=0.9, nbins=100):
 
 # ------------------------------------------------------------------------------------ the ensemble
 def run_experiment(workload, seed, nsteps, burnin_fraction=0.1, cl=0.9, sync_interval=10000, mcmc=None,
-                   form="fused", graph_steps=0, lookahead=False):
+                   form="fused", graph_steps=0, lookahead=False, proposal="diagonal", proposal_shrinkage=0.05):
     """One iteration of the loop in sxmc.cpp:59-145: fake data -> MCMC -> intervals.
     Reuses `mcmc` (evaluators with the MC tables resident in HBM) across experiments when given.
     lookahead: walk with two evaluations per pass over the tables (MCMC.walk(lookahead=True): the same chain, about a
     quarter more steps per second when one experiment has the GPU to itself; `mcmc` then needs a created stream).
+    proposal, proposal_shrinkage: MCMC.walk's ("covariance": the correlated proposal; it walks sequentially).
     Returns (intervals float32 [P, 4], chain, accepted)."""
     rng = np.random.default_rng(seed)
     if mcmc is None:
@@ -368,12 +369,13 @@ def run_experiment(workload, seed, nsteps, burnin_fraction=0.1, cl=0.9, sync_int
         mcmc.reseed(seed & 0xFFFFFFFF)
     data, _ = make_fake_dataset(rng, workload, mcmc.pdfs, poisson=True)
     chain, accepted = mcmc.walk(data, nsteps, burnin_fraction, sync_interval=sync_interval, graph_steps=graph_steps,
-                                lookahead=lookahead and mcmc.stream is not None and mcmc.consume)
+                                lookahead=lookahead and mcmc.stream is not None and mcmc.consume, proposal=proposal,
+                                proposal_shrinkage=proposal_shrinkage)
     return contour_intervals(chain, cl), chain, accepted
 
 
 def run_experiments_in_lockstep(workload, seeds, nsteps, sets, burnin_fraction=0.1, cl=0.9, sync_interval=10000,
-                                graph_steps=0, timing=None):
+                                graph_steps=0, timing=None, proposal="diagonal"):
     """len(seeds) fake experiments at once on one GPU, the chains grouped into lockstep sets (mcmc.LockstepChains:
     the chains of a set share a stream and ONE fill pass per step; different sets run on different streams, so one
     set's step ends overlap another's fill).  Same schedule of re-tunings and flushes as a single walk; every
@@ -382,6 +384,9 @@ def run_experiments_in_lockstep(workload, seeds, nsteps, sets, burnin_fraction=0
     chain's set-up (fake data, evaluation points, first evaluation) to the last flush, re-tunings and flushes
     included -- which is what an experiment of BASELINE's 1e5 steps consists of."""
     import time
+    if proposal != "diagonal":
+        raise ValueError("lockstep sets have no correlated step end: proposal %r walks one experiment per chain "
+                         "(run_experiment, run_experiments_concurrently)" % (proposal,))
     chains = [m for st in sets for m in st.chains]
     assert len(seeds) == len(chains)
     for st in sets:
@@ -418,7 +423,7 @@ def run_experiments_in_lockstep(workload, seeds, nsteps, sets, burnin_fraction=0
 
 
 def run_experiments_concurrently(workload, seeds, nsteps, chains, burnin_fraction=0.1, cl=0.9, sync_interval=10000,
-                                 graph_steps=0):
+                                 graph_steps=0, proposal="diagonal", proposal_shrinkage=0.05):
     """len(chains) fake experiments at once on one GPU (BASELINE config 4: one experiment per stream):
     the chains share one resident copy of the MC tables (MCMC(..., share_with=...), own non-blocking
     streams) and are advanced in turn, so one experiment's small kernels overlap another's fill.
@@ -429,7 +434,8 @@ def run_experiments_concurrently(workload, seeds, nsteps, chains, burnin_fractio
         rng = np.random.default_rng(seed)
         m.reseed(seed & 0xFFFFFFFF)
         data, _ = make_fake_dataset(rng, workload, m.pdfs, poisson=True)
-        m.walk_begin(data, nsteps, burnin_fraction, sync_interval=sync_interval)
+        m.walk_begin(data, nsteps, burnin_fraction, sync_interval=sync_interval, proposal=proposal,
+                     proposal_shrinkage=proposal_shrinkage)
     if graph_steps <= 0:
         for i in range(nsteps):
             for m in chains:

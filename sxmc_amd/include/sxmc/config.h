@@ -680,6 +680,8 @@ struct FitConfig {
   float confidence = 0.683f;
   std::string signal_name;
   std::string samples;   //!< fit.samples: a saved chain to take the intervals from INSTEAD of walking (sxmc.cpp:84-94)
+  std::string proposal = "diagonal";   //!< fit.proposal: "diagonal" (the reference's) or "covariance" (mcmc.h: Proposal)
+  double proposal_shrinkage = 0.05;    //!< fit.proposal_shrinkage in (0, 1]: only with "covariance"
   std::vector<Observable> observables, cuts;
   std::vector<Systematic> systematics;            //!< union over the signals, parameters numbered in that order
   std::vector<Source> sources;
@@ -842,6 +844,26 @@ inline std::string join_path(const std::string& dir, const std::string& f) {
 
 /** Parse a configuration text (the reference's schema).  load_tables: also read every signal's and data set's
  *  table relative to base_dir. */
+namespace detail {
+/** The fit's "proposal" ("diagonal", the default, or "covariance": the correlated proposal of sxmc::MCMC) and, for
+ *  "covariance" only, "proposal_shrinkage": a number in (0, 1]; absent: 0.05.  A configuration without the keys loads as
+ *  before.  Same rules and messages as sxmc_amd.io.fit_proposal. */
+inline void fit_proposal_from_json(FitConfig& fc, const json::Value& fit) {
+  fc.proposal = fit.isMember("proposal") ? fit["proposal"].asString("proposal") : std::string("diagonal");
+  if (fc.proposal != "diagonal" && fc.proposal != "covariance") {
+    throw ConfigError("fit: unknown \"proposal\" \"" + fc.proposal + "\" (\"diagonal\" or \"covariance\")");
+  }
+  fc.proposal_shrinkage = 0.05;
+  if (!fit.isMember("proposal_shrinkage")) return;
+  if (fc.proposal != "covariance") {
+    throw ConfigError("fit: \"proposal_shrinkage\" is only for \"proposal\": \"covariance\"");
+  }
+  const double v = fit["proposal_shrinkage"].asDouble("proposal_shrinkage");
+  if (!(v > 0 && v <= 1)) throw ConfigError("fit: \"proposal_shrinkage\" must be a number in (0, 1]");
+  fc.proposal_shrinkage = v;
+}
+}  // namespace detail
+
 inline FitConfig parse_config(const std::string& text, const std::string& base_dir, bool load_tables = true) {
   const json::Value root = json::parse(text);
   const json::Value& fit = root["fit"];
@@ -870,6 +892,7 @@ inline FitConfig parse_config(const std::string& text, const std::string& base_d
   fc.confidence = (float)fit.get("confidence", 0.683);
   fc.signal_name = fit.get("signal_name", "");
   fc.samples = fit.get("samples", "");   // config.cpp:51
+  detail::fit_proposal_from_json(fc, fit);
 
   // observables and cuts (config.cpp:77-95)
   for (const json::Value& v : fit["observables"].items) {

@@ -96,6 +96,8 @@ struct ExperimentOptions {
   /** set-up, graph recording and tear-down of the lanes take this lock instead of one of the call's own
    *  (ensemble_multi_gpu passes the device's, so that lanes of one card started from different calls still take turns) */
   SetupLock* device_exclusive = nullptr;
+  Proposal proposal = Proposal::DIAGONAL;   //!< MCMC::proposal of every chain the runner builds (fit.proposal);
+  double proposal_shrinkage = 0.05;         //!< ensemble_lockstep refuses COVARIANCE: its sets have no such step end
 };
 
 /** Where an experiment runs when it is one of several in flight: all "none" for the one-at-a-time loop. */
@@ -163,6 +165,8 @@ inline std::unique_ptr<MCMC> experiment_chain(std::vector<Source>& sources, std:
                                               const LaneContext& lane) {
   std::unique_ptr<MCMC> mcmc(new MCMC(sources, signals, systematics, observables, seed, lane.stream));
   mcmc->graph_steps = opt.graph_steps;
+  mcmc->proposal = opt.proposal;
+  mcmc->proposal_shrinkage = opt.proposal_shrinkage;
   mcmc->exclusive = lane.exclusive;
   mcmc->lockstep = lane.lockstep;
   mcmc->lockstep_index = lane.lockstep_index;
@@ -388,6 +392,10 @@ inline std::vector<ExperimentResult> ensemble_lockstep(const std::vector<unsigne
                                                        std::vector<Observable>& observables, unsigned nsteps,
                                                        float burnin_fraction, unsigned chains_per_set, unsigned nsets,
                                                        const ExperimentOptions& opt) {
+  if (opt.proposal == Proposal::COVARIANCE) {
+    throw pdfz::Error("ensemble_lockstep: a lockstep set has no correlated step end: run a COVARIANCE ensemble one "
+                      "experiment per chain (ensemble, ensemble_concurrent)");
+  }
   PoolScope pool;   // the experiments' arrays recycle their blocks instead of allocating and freeing (device_array.h)
   const size_t L = std::max(2u, std::min(4u, chains_per_set)), S = std::max(1u, nsets), lanes = L * S;
   const size_t usable = experiments.size() / lanes * lanes;

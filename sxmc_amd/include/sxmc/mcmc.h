@@ -294,8 +294,18 @@ class LockstepSet {
   std::string why;
 };
 
+/** The proposal of a walk: the reference's independent Gaussians, or v_current + L z with L rebuilt at the two
+ *  re-tunings from the chain's own correlations (README, "Correlated proposals"). */
+enum class Proposal { DIAGONAL, COVARIANCE };
+
 class MCMC {
  public:
+  Proposal proposal = Proposal::DIAGONAL;   //!< COVARIANCE: the next proposal is v_current + L z, L the lower-triangular
+                                            //!< factor sxmc_proposal_factor builds at each re-tuning (diag(w) before the
+                                            //!< first); every marginal width stays the reference's.  Every sequential
+                                            //!< form takes it; asked with lookahead the walk goes sequentially; a chain
+                                            //!< of a lockstep set refuses it
+  double proposal_shrinkage = 0.05;         //!< in (0, 1]: the correlations are shrunk towards the identity by this much
   LockstepSet* lockstep = nullptr;  //!< set: this chain steps together with the other chains of the set (same
   size_t lockstep_index = 0;        //!< sample tables, same systematics, the set's stream); every run of steps is
                                     //!< launched (graph replays of graph_steps steps) by the chain that arrives last
@@ -473,6 +483,12 @@ class MCMC {
   }
 
   size_t NumParameters() const { return nparameters; }
+  /** The factor the last walk ended with, P x P doubles with L_ij at [j * P + i] (empty after a DIAGONAL walk), and
+   *  the shrinkage it was built with (doubled where a pivot failed: sxmc_proposal_factor). */
+  const std::vector<double>& ProposalFactor(double* shrinkage_used = nullptr) const {
+    if (shrinkage_used) *shrinkage_used = last_shrinkage;
+    return last_factor;
+  }
   /** The form the steps of the last walk took (walk_plan.h: WalkForm::Step), valid after a walk: "reference", "batched",
    *  "consuming", "lockstep", "lookahead" or "mixed". */
   const char* WalkFormName() const { return form_name; }
@@ -572,12 +588,15 @@ class MCMC {
     pdfz::Array<float> jump_buffer;
     pdfz::Array<double> current_nll, proposed_nll;
     pdfz::Array<float> jump_width, lut;
+    const bool covariance;            // the walk's proposal is the correlated one
+    std::unique_ptr<pdfz::Array<double>> factor;   // its factor, P x P: one device array for the walk's lifetime (none otherwise)
     std::unique_ptr<Shadow> shadow;   // look-ahead walk only
     OwnedGraph graph;
     OwnedStream own_stream;           // recorded steps need a created stream: the walk's own when it was given none
     sxmc_stream_t strm;
     WalkForm form{};
     StepArgs d;
+    const double* d_factor = nullptr; // the factor on the device, or null: resolved with d
     bool two_forms = false;           // the plan holds a boxed and an ordered form of the fill (asked at every run)
     bool setup_announced = false;     // on_setup_done has been called
     bool torn_down = false;
@@ -605,6 +624,8 @@ class MCMC {
           proposed_nll(1, true),
           jump_width(m_.nparameters, true),
           lut(nevents * m_.nsignals, true),
+          covariance(m_.proposal == Proposal::COVARIANCE),
+          factor(covariance ? new pdfz::Array<double>(m_.nparameters * m_.nparameters, true) : nullptr),
           strm(m_.stream) {
       std::memset(&d, 0, sizeof d);
       chain.names = m.parameter_names;
@@ -633,6 +654,11 @@ class MCMC {
       proposed_nll.writeOnlyHostPtr();
       const std::vector<float> w = m.initial_jump_widths();
       for (size_t i = 0; i < m.nparameters; i++) jump_width.writeOnlyHostPtr()[i] = w[i];
+      m.last_factor.clear();
+      if (covariance) {
+        if (m.lockstep) throw pdfz::Error("MCMC: a lockstep set has no correlated step end: walk a COVARIANCE chain alone");
+        rebuild_factor(nullptr, 0);   // (L = diag(w), through the re-tuning's own code)
+      }
 
       // mcmc.cpp:230-242: bind, first evaluation at the current vector, then re-point at the proposal
       for (size_t i = 0; i < m.pdfs.size(); i++) {
@@ -654,7 +680,7 @@ class MCMC {
     /** The form of the steps (walk_plan.h: choose_form), narrowed by what the device says about the look-ahead pass;
      *  then what the form needs: the group bound and tuned, the shadow set, a stream to record on.  Lock: held. */
     void choose_form() {
-      form = sxmc::choose_form(WalkFlags{m.group != nullptr, m.reference_form,
+      form = sxmc::choose_form(covariance, WalkFlags{m.group != nullptr, m.reference_form,
                                          m.nsystematics > 0 && !m.systematics_fixed, m.consume, m.lut_output,
                                          m.lockstep != nullptr, m.lookahead || m.lookahead_auto, m.nparameters,
                                          m.graph_steps, !m.kernels.empty()});
@@ -758,6 +784,10 @@ class MCMC {
       d.a.d_source_id = m.source_id->readOnlyPtr();
       d.a.d_norms = normalizations.ptr();
       d.a.debug_mode = debug_mode ? 1 : 0;
+      // the factor like the widths: uploaded here, after a re-tuning wrote it, never under a recording; the address is
+      // the same for the whole walk, so recorded steps survive a re-tuning
+      d_factor = covariance ? factor->readOnlyPtr() : nullptr;
+      if (m.group) check(sxmc_group_set_proposal_factor(m.group, d_factor));
     }
 
     /** One step of the sequential walk, in the form's launches. */
@@ -796,7 +826,7 @@ class MCMC {
                          (size_t)npartial, d.sums, m.nsignals, m.nsources, a.d_means, a.d_sigmas, a.d_rng,
                          a.d_nll_current, a.d_nll_proposed, a.d_v_current, a.d_v_proposed, a.d_accepted, a.d_counter,
                          a.d_jump_buffer, a.nparameters, a.d_jump_width, a.d_nexpected, a.d_n_mc, a.d_source_id,
-                         a.d_norms, debug_mode);
+                         a.d_norms, debug_mode, d_factor);
     }
 
     /** One step of a MIXED walk, every launch on the walk's stream and none of them a wait, a copy or an allocation (so
@@ -839,7 +869,7 @@ class MCMC {
                          (size_t)m.nnllthreads, d.sums, m.nsignals, m.nsources, a.d_means, a.d_sigmas, a.d_rng,
                          a.d_nll_current, a.d_nll_proposed, a.d_v_current, a.d_v_proposed, a.d_accepted, a.d_counter,
                          a.d_jump_buffer, a.nparameters, a.d_jump_width, a.d_nexpected, a.d_n_mc, a.d_source_id,
-                         a.d_norms, debug_mode);
+                         a.d_norms, debug_mode, d_factor);
     }
 
     /** The run of steps that starts at step i: what the host does before it (re-tuning, the form of the fill), the
@@ -877,7 +907,16 @@ class MCMC {
         const double fit_width = sd > 0 ? sd : jump_width.readOnlyHostPtr()[j];
         jump_width.hostPtr()[j] = scale_factor * fit_width;
       }
+      if (covariance) rebuild_factor(chain.rows.data(), chain.nrows());
       if (!debug_mode) chain.rows.clear();
+    }
+
+    /** The factor of the correlated proposal from the rows kept so far and the widths as they now stand: the library's
+     *  one implementation (sxmc_proposal_factor), into the walk's one array. */
+    void rebuild_factor(const float* rows, size_t nrows) {
+      check(sxmc_proposal_factor(rows, nrows, (int)m.nparameters, jump_width.readOnlyHostPtr(), m.proposal_shrinkage,
+                                 factor->hostPtr(), &m.last_shrinkage));
+      m.last_factor.assign(factor->readOnlyHostPtr(), factor->readOnlyHostPtr() + m.nparameters * m.nparameters);
     }
 
     /** Set-up is over: the lock goes BEFORE a run is queued -- a run is up to sync_interval steps, a second of device
@@ -1038,6 +1077,7 @@ class MCMC {
         if (form.step == WalkForm::MIXED)
           for (const KernelMember& k : m.kernels) k.eval->EvalFinished();
         for (pdfz::Eval* p : m.pdfs) p->ForgetBuffers();
+        if (m.group) (void)sxmc_group_set_proposal_factor(m.group, nullptr);   // (it borrowed this walk's factor)
         if (shadow)
           for (auto& p : shadow->evaluators) p->ForgetBuffers();
         // (before the lock is re-taken: the set's launcher takes the two in the other order)
@@ -1076,6 +1116,8 @@ class MCMC {
   };
   std::vector<KernelMember> kernels;   //!< non-empty: every evaluator is an EvalHist or an EvalKernel (the walk is MIXED)
   const char* form_name = "reference";
+  std::vector<double> last_factor;     //!< ProposalFactor(): the last COVARIANCE walk's factor, as the device read it
+  double last_shrinkage = 0;
   bool optimized = false;
   size_t ahead_passes = 0, ahead_passes_seen = 0;   //!< look-ahead walk: passes launched / counted in the rate below
   double ahead_steps_seen = 0;

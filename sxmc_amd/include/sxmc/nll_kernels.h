@@ -79,6 +79,23 @@ inline void finish_nll_jump_pick_combo(int grid, int block, size_t, sxmc_stream_
                                                debug_mode ? 1 : 0));
 }
 
+/** The same with a correlated proposal's factor behind debug_mode (include/sxmc_hip.h, sxmc_group_set_proposal_factor:
+ *  the law and the layout; null: the launch above): for walks that have no group to carry it. */
+inline void finish_nll_jump_pick_combo(int grid, int block, size_t, sxmc_stream_t stream,
+                                       const size_t npartial_sums, const double* sums, const size_t nsignals,
+                                       const size_t nsources, const double* means, const double* sigmas,
+                                       RNGState* rng, double* nll_current, double* nll_proposed,
+                                       double* v_current, double* v_proposed, int* accepted, int* counter,
+                                       float* jump_buffer, int nparameters, const float* jump_width,
+                                       const double* nexpected, const unsigned* n_mc, const short* source_id,
+                                       const unsigned* norms, const bool debug_mode, const double* factor) {
+  check(sxmc_launch_finish_nll_jump_pick_combo_factor(grid, block, stream, npartial_sums, sums, nsignals, nsources,
+                                                      means, sigmas, rng, nll_current, nll_proposed, v_current,
+                                                      v_proposed, accepted, counter, jump_buffer, nparameters,
+                                                      jump_width, nexpected, n_mc, source_id, norms,
+                                                      debug_mode ? 1 : 0, factor));
+}
+
 }  // namespace launch
 }  // namespace sxmc
 

@@ -83,6 +83,8 @@ struct WalkFlags {
   unsigned graph_steps;
   bool mixed = false;      //!< there are kernel-density members, and every evaluator is a histogram or kernel-density
                            //!< evaluator of this library; has_group then says whether there are histogram members
+  bool covariance_proposal = false;   //!< the proposal is the correlated one: every sequential form takes it, the
+                                     //!< look-ahead pass and lockstep sets have no such step end
 };
 /** The form of the walk's steps, from the flags alone.  LOOKAHEAD is a candidate: two questions to the device (does the
  *  plan stream codes, is the pass offered for this shape) may still narrow it to CONSUMING, see narrowed(). */
@@ -112,12 +114,21 @@ inline WalkForm choose_form(const WalkFlags& f) {
   WalkForm::Step step = WalkForm::REFERENCE;
   if (fused && !f.consume) step = WalkForm::BATCHED;
   if (fused && f.consume) {
-    step = f.in_lockstep_set ? WalkForm::LOCKSTEP
+    // (a correlated proposal: asked with lookahead, or given a lockstep set, the walk goes sequentially)
+    step = f.covariance_proposal ? WalkForm::CONSUMING
+           : f.in_lockstep_set   ? WalkForm::LOCKSTEP
            : (f.lookahead_asked && !f.lut_output && f.nparameters <= 256) ? WalkForm::LOOKAHEAD
                                                                            : WalkForm::CONSUMING;
   }
   // recorded steps need the batched form; a lockstep chain's steps are recorded by its set
   return WalkForm{step, batched, f.systematics_float, (fused && step != WalkForm::LOCKSTEP) ? f.graph_steps : 0};
+}
+
+/** The same for a walk whose proposal is named apart from its other facts (mcmc.h: the proposal is the walk's, the rest
+ *  are the chain's). */
+inline WalkForm choose_form(bool covariance_proposal, WalkFlags f) {
+  f.covariance_proposal = covariance_proposal;
+  return choose_form(f);
 }
 
 }  // namespace sxmc

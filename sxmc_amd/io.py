@@ -228,6 +228,26 @@ def signal_cv(name, c, pdf):
     return cv
 
 
+def fit_proposal(fit):
+    """The fit's "proposal" ("diagonal", the default, or "covariance": the correlated proposal of the walkers) and, for
+    "covariance" only, "proposal_shrinkage": a number in (0, 1]; absent: 0.05.  -> (proposal, shrinkage).  A
+    configuration without the keys loads as before.  Same rules and messages as sxmc::detail::fit_proposal_from_json
+    (config.h)."""
+    proposal = fit.get("proposal", "diagonal")
+    if not isinstance(proposal, str):
+        raise ValueError("proposal: not a string")
+    if proposal not in ("diagonal", "covariance"):
+        raise ValueError('fit: unknown "proposal" "%s" ("diagonal" or "covariance")' % proposal)
+    if "proposal_shrinkage" not in fit:
+        return proposal, 0.05
+    if proposal != "covariance":
+        raise ValueError('fit: "proposal_shrinkage" is only for "proposal": "covariance"')
+    v = _number(fit["proposal_shrinkage"], "proposal_shrinkage")
+    if not 0 < v <= 1:
+        raise ValueError('fit: "proposal_shrinkage" must be a number in (0, 1]')
+    return proposal, v
+
+
 def load_config(path_or_text, base_dir=None):
     if os.path.exists(path_or_text):
         base_dir = base_dir or os.path.dirname(os.path.abspath(path_or_text))
@@ -252,6 +272,7 @@ def load_config(path_or_text, base_dir=None):
     fc.confidence = float(np.float32(fit.get("confidence", 0.683)))
     fc.signal_name = fit.get("signal_name", "")
     fc.samples = fit.get("samples", "")      # config.cpp:51: a saved chain to use INSTEAD of walking (sxmc.cpp:84-94)
+    fc.proposal, fc.proposal_shrinkage = fit_proposal(fit)
 
     def observable(name):
         c = obs_params[name]
@@ -476,7 +497,8 @@ def run_config(path, out_dir=None, nexperiments=None, nsteps=None, report=None, 
         if events is None:
             events, _ = ensemble.make_fake_dataset(rng, w, m.pdfs, poisson=True)
         m.reseed(((fc.seed << 20) + i) & 0xFFFFFFFF)
-        chain, _ = m.walk(events, nsteps, fc.burnin_fraction, debug_mode=fc.debug_mode)
+        chain, _ = m.walk(events, nsteps, fc.burnin_fraction, debug_mode=fc.debug_mode, proposal=fc.proposal,
+                          proposal_shrinkage=fc.proposal_shrinkage)
         if fc.error_type == "projection":                       # likelihood.cpp:104-137: the chosen estimator
             cols = [ensemble.projection_interval(chain[:, p], fc.confidence) for p in range(chain.shape[1] - 1)]
             iv = np.array([c[:4] for c in cols], np.float32)

@@ -119,6 +119,11 @@ class MCMC:
         self.lut = None
         self.nevents = 0
         self._graph, self._graph_steps = None, 0
+        # the correlated proposal (walk(proposal="covariance")): one P x P device array for the chain's lifetime, so that
+        # its address outlives re-tunings and recorded graphs; None while the proposal is the diagonal one
+        self.proposal_factor = None
+        self._factor_buffer = None
+        self.proposal_shrinkage_used = None
 
     # mcmc.cpp:198-228 (keeps the reference's `i < nsignals` test at :217)
     def initial_jump_widths(self, fixed=None):
@@ -238,7 +243,7 @@ class MCMC:
                                        self.current_vector, self.proposed_vector, self.accept_counter,
                                        self.jump_counter, self.jump_buffer, self.nparameters, self.jump_width,
                                        self.nexpected, self.n_mc, self.source_id, self.normalizations,
-                                       debug_mode)
+                                       debug_mode, factor=self.proposal_factor)
 
     def _launching(self, n):
         """Every step appends a row to the jump buffer (sync_interval rows, jump_decider nll_kernels.cpp:78-84, which
@@ -256,13 +261,17 @@ class MCMC:
         self.rngs = nll.make_rngs(self.nparameters, seed, self.stream)
 
     def walk(self, data, nsteps, burnin_fraction, debug_mode=False, sync_interval=10000, graph_steps=0,
-             lookahead=False):
+             lookahead=False, proposal="diagonal", proposal_shrinkage=0.05):
         """MCMC::operator() (mcmc.cpp:143-387): start at the means, walk nsteps, re-tune the proposal
         widths from the chain's spread at burnin_steps and 2 * burnin_steps (dropping the steps so far
         unless debug_mode).  Returns (chain [nkept, P + 1] float32, accepted).
         graph_steps = K > 0 replays a HIP graph of K recorded steps wherever K steps fit between two
-        points that need the host (re-tuning, jump-buffer flush); the chain is the same."""
-        self.walk_begin(data, nsteps, burnin_fraction, debug_mode, sync_interval)
+        points that need the host (re-tuning, jump-buffer flush); the chain is the same.
+        proposal="covariance": v_proposed = v_current + L z with L a lower-triangular factor rebuilt at the two
+        re-tunings from the kept rows' correlations, shrunk towards the identity by proposal_shrinkage (README,
+        "Correlated proposals"; include/sxmc_hip.h, sxmc_proposal_factor); every parameter's marginal width stays the
+        reference's.  Such a walk is always sequential: asked with lookahead it walks step by step."""
+        self.walk_begin(data, nsteps, burnin_fraction, debug_mode, sync_interval, proposal, proposal_shrinkage)
         self.lookahead_passes = 0
         # (a shape the look-ahead pass is not offered for -- see Group.LookaheadSupported -- walks sequentially)
         if lookahead and self.group.LookaheadSupported():
@@ -346,8 +355,14 @@ class MCMC:
 
     # The same walk cut into per-step pieces, so that several chains can be advanced in turn and have
     # their kernels in flight together (one stream per chain).
-    def walk_begin(self, data, nsteps, burnin_fraction, debug_mode=False, sync_interval=10000):
+    def walk_begin(self, data, nsteps, burnin_fraction, debug_mode=False, sync_interval=10000, proposal="diagonal",
+                   proposal_shrinkage=0.05):
         w = self.w
+        if proposal not in ("diagonal", "covariance"):
+            raise ValueError('proposal must be "diagonal" or "covariance", not %r' % (proposal,))
+        if not 0.0 < float(proposal_shrinkage) <= 1.0:
+            raise ValueError("proposal_shrinkage must lie in (0, 1], not %r" % (proposal_shrinkage,))
+        self._shrinkage = float(proposal_shrinkage)
         self._nsteps, self._debug = nsteps, debug_mode
         self._burnin = int(nsteps * burnin_fraction)
         self.current_vector.set(w.parameter_means().astype(np.float64))
@@ -357,7 +372,34 @@ class MCMC:
         # mcmc.cpp:199: nfloat = the parameters that are not fixed (a fixed one carries jump width <= 0)
         nfloat = max(1, int(np.count_nonzero(self.jump_width.get() > 0)))
         self._scale_factor = np.float32(2.4 * 2.4 / nfloat)
+        self._set_proposal(proposal)
         self._rows, self._accepted = [np.zeros((0, self.nparameters + 1), np.float32)], 0
+
+    def _set_proposal(self, proposal):
+        """Diagonal: no factor anywhere.  Covariance: L = diag(w) through the re-tuning's own code path (no rows), in the
+        chain's one device array, handed to the group (its step ends) and to the group-less launch point (step())."""
+        if self._graph is not None and (proposal == "covariance") != (self.proposal_factor is not None):
+            graph, self._graph = self._graph, None          # (recorded steps hold the other law's arguments)
+            if hasattr(graph, "close"):
+                graph.close()
+        if proposal == "covariance":
+            P = self.nparameters
+            if self._factor_buffer is None:
+                self._factor_buffer = DeviceArray.zeros(P * P, np.float64)
+            factor, self.proposal_shrinkage_used = nll.proposal_factor(np.zeros((0, P + 1), np.float32),
+                                                                       self.jump_width.get(), self._shrinkage)
+            self._factor_buffer.set(factor)
+            self.proposal_factor = self._factor_buffer
+        else:
+            self.proposal_factor = None
+        self.group.SetProposalFactor(self.proposal_factor)
+
+    def ProposalFactor(self):
+        """The last factor as [P, P] (L[i, j]) and the shrinkage it was built with; (None, None) for a diagonal walk."""
+        if self.proposal_factor is None:
+            return None, None
+        P = self.nparameters
+        return self.proposal_factor.get().reshape(P, P).T.copy(), self.proposal_shrinkage_used
 
     def _retune_if_due(self, i):
         b = self._burnin
@@ -372,6 +414,10 @@ class MCMC:
                 sd = float(sofar[:, j].astype(np.float64).std()) if sofar.shape[0] > 1 else 0.0
                 jw[j] = np.float32(float(self._scale_factor) * (sd if sd > 0 else float(jw[j])))
             self.jump_width.set(jw)
+            if self.proposal_factor is not None:
+                # (in place: the address recorded graphs and the group hold stays; the proposal already drawn stands)
+                factor, self.proposal_shrinkage_used = nll.proposal_factor(sofar, jw, self._shrinkage)
+                self.proposal_factor.set(factor)
             if not self._debug:
                 self._rows = [np.zeros((0, self.nparameters + 1), np.float32)]
 

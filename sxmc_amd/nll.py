@@ -38,6 +38,20 @@ def nll_event_chunks(grid, block, stream, lut, pars, ne, ns, nexpected, n_mc, so
               ptr(nexpected), ptr(n_mc), ptr(source_id), ptr(norms), ptr(sums))
 
 
+def proposal_factor(rows, new_widths, shrinkage=0.05):
+    """The re-tuning of a correlated proposal (sxmc_proposal_factor, host arithmetic only): rows [nrows, P + 1] float32
+    kept rows of the chain, new_widths [P] float32 the re-tuned widths (<= 0: fixed).  Returns (factor, shrinkage used):
+    factor is [P * P] float64 in the device's layout, L_ij at [j * P + i]."""
+    w = np.ascontiguousarray(new_widths, np.float32).reshape(-1)
+    P = w.size
+    r = np.ascontiguousarray(rows, np.float32).reshape(-1, P + 1)
+    out = np.zeros(P * P, np.float64)
+    used = C.c_double(0.0)
+    capi.call("sxmc_proposal_factor", ptr(r) if r.shape[0] else None, int(r.shape[0]), int(P), ptr(w),
+              float(shrinkage), ptr(out), C.byref(used))
+    return out, used.value
+
+
 def nll_event_reduce(grid, block, stream, nthreads, sums, total_sum):
     capi.call("sxmc_launch_nll_event_reduce", grid, block, ptr(stream), int(nthreads), ptr(sums), ptr(total_sum))
 
@@ -52,7 +66,16 @@ def nll_total(grid, block, stream, nparameters, pars, nsignals, nsources, means,
 def finish_nll_jump_pick_combo(grid, block, stream, npartial_sums, sums, nsignals, nsources, means, sigmas,
                                rng, nll_current, nll_proposed, v_current, v_proposed, accepted, counter,
                                jump_buffer, nparameters, jump_width, nexpected, n_mc, source_id, norms,
-                               debug_mode=False):
+                               debug_mode=False, factor=None):
+    """factor: a correlated proposal's P x P factor on the device (sxmc_group_set_proposal_factor in include/sxmc_hip.h
+    has the law and the layout), or None: the diagonal proposal through the reference-shaped launch point."""
+    if factor is not None:
+        capi.call("sxmc_launch_finish_nll_jump_pick_combo_factor", grid, block, ptr(stream), int(npartial_sums),
+                  ptr(sums), int(nsignals), int(nsources), ptr(means), ptr(sigmas), ptr(rng), ptr(nll_current),
+                  ptr(nll_proposed), ptr(v_current), ptr(v_proposed), ptr(accepted), ptr(counter),
+                  ptr(jump_buffer), int(nparameters), ptr(jump_width), ptr(nexpected), ptr(n_mc), ptr(source_id),
+                  ptr(norms), int(bool(debug_mode)), ptr(factor))
+        return
     capi.call("sxmc_launch_finish_nll_jump_pick_combo", grid, block, ptr(stream), int(npartial_sums),
               ptr(sums), int(nsignals), int(nsources), ptr(means), ptr(sigmas), ptr(rng), ptr(nll_current),
               ptr(nll_proposed), ptr(v_current), ptr(v_proposed), ptr(accepted), ptr(counter),
@@ -160,6 +183,12 @@ class EvalGroup:
         buf = C.create_string_buffer(8192)
         capi.call("sxmc_group_launch_info", self._g, buf, len(buf))
         return buf.value.decode()
+
+    def SetProposalFactor(self, factor):
+        """A correlated proposal for every step end this group launches: factor, a DeviceArray of P x P doubles (borrowed:
+        keep it alive; its contents may be rewritten between steps), or None for the diagonal proposal
+        (sxmc_group_set_proposal_factor)."""
+        capi.call("sxmc_group_set_proposal_factor", self._g, ptr(factor))
 
     def SetLutOutput(self, enable):
         """False: EvalNllAsync / McmcStepAsync do not write the lookup table and sum over the distinct tuples
