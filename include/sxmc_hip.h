@@ -373,7 +373,26 @@ int sxmc_kde_npoints(sxmc_kde_t k, size_t* npoints);
  * neither) the event is redrawn, a new sample and new coordinates, up to 1024 attempts; then SXMC_ERR_STATE with the
  * count.  h_events: nobserved rows of nobservables + 1 floats (last = dataset id).  Counter-based: Philox4x32-10 keyed
  * by `seed`, counters (event, 2 attempt) and (event, 2 attempt + 1) -- the same seed and parameters give the same
- * bits, on a shared evaluator too.  nobserved == 0 does nothing.  1 to 4 observables. */
+ * bits, on a shared evaluator too.  nobserved == 0 does nothing.  1 to 4 observables.  Which word does what, as
+ * tests/kde_sample_reference.py restates it and the device output equals, bit for bit wherever the last bits of the
+ * device's erfc and erfcinv cannot decide a rounding:
+ *   words    event e, attempt t (from 0): block A = Philox4x32-10 with counter words (e low, e high, 2t, 0), block B
+ *            with (e low, e high, 2t + 1, 0), both with key (seed low, seed high), each giving x, y, z, w
+ *   row      the in-domain rows of the last evaluation are listed in table order (n of them); A.x picks place
+ *            (A.x * n) >> 32 of that list
+ *   point    observables 0..3 take the words A.y, A.z, A.w, B.x in this order.  With c the float the evaluation left
+ *            for the row and observable, (float)((x - lower) * (0.84932180028801907 / h)), every operation rounded
+ *            in f64: s = lower + (double)c * (h / 0.84932180028801907) and hw = h * lambda[table row] (lambda = 1 on a
+ *            fixed-bandwidth evaluator: the factor belongs to the table row, not to the place in the list);
+ *            pa = Phi((lower - s) / hw), qb = Phi((s - upper) / hw), Phi(z) = 0.5 * erfc(-z * 0.70710678118654752),
+ *            m = (0.5 - pa) + (0.5 - qb), p = pa + (word + 0.5) * 2^-32 * m
+ *   branch   p <= 0.5: z = -1.4142135623730950 * erfcinv(2 p); otherwise the complement is formed without
+ *            cancellation, q = qb + ((2^32 - 1 - word) + 0.5) * 2^-32 * m, and z = +1.4142135623730950 * erfcinv(2 q);
+ *            xd = s + hw * z
+ *   float    xf = (float)xd; then xf = bottom, the smallest float >= lower, if not (xf >= lower), then xf = top, the
+ *            largest float < upper, if not (xf < upper): both tests in f64 on the float, after the rounding
+ *   cuts     on the floats: while xf > upper cut or xf < lower cut in any observable (all are drawn first) the event
+ *            takes attempt t + 1, a new row and new words */
 int sxmc_kde_random_sample(sxmc_kde_t k, size_t nobserved, unsigned long long seed, const float* lowers,
                            const float* uppers, float* h_events);
 /* n: how many samples the last evaluation left inside the domain, counted by the sampler's own compaction (its norm;
