@@ -699,6 +699,28 @@ int sxmc_group_set_lut_output(sxmc_group_t g, int enable);
  * sxmc_multigroup_step_async and sxmc_multigroup_lookahead_step_async return SXMC_ERR_STATE, and
  * sxmc_group_lookahead_supported answers 0. */
 int sxmc_group_set_proposal_factor(sxmc_group_t g, const double* d_factor);
+/* WEIGHTED DATA EVENTS (opt-in; without weights a group runs the kernels it ran before, bit for bit).  THE LAW
+ * (restated for tests in tests/weighted_events_reference.py):
+ *   - event i has a weight w_i, a finite double >= 0; the log-likelihood's event term becomes sum_i w_i log(s_i), with
+ *     s_i exactly the unweighted s (same look-ups, same -1 / -2 / NaN rules, same s > 0 guard).  nll_total is untouched.
+ *   - rows are CLASSES (sxmc_group_set_lut_output off): the class weight is W_k = sum of w_i over the events of class k
+ *     in ASCENDING EVENT INDEX, in double, added one by one; a row's term is W_k * log(s_k), rounded once; the terms are
+ *     added in the order and partition of the unweighted kernels.
+ *   - rows are EVENTS (lut_output on, and sxmc_launch_nll_event_chunks_weighted): the term is w_i * log(s_i); the
+ *     lookup table is written as before.
+ * Two exact consequences: weights all 1.0 give every partial sum and every chain of the unweighted group as bytes; and
+ * integer weights m_i >= 1 with lut_output off give, as bytes, the unweighted walk over the data set in which event i is
+ * repeated m_i times.
+ * h_weights is a HOST array of nevents doubles and is copied; NULL, 0 switches weights off.  SXMC_ERR_INVALID: a weight
+ * that is NaN, infinite or negative (the message names the first such index).  SXMC_ERR_STATE: under a graph recording;
+ * and, at the next evaluation, a count that differs from the members' evaluation points.  Setting weights invalidates
+ * the event classes, as new points do.  The weights reach sxmc_group_eval_nll_async, sxmc_group_mcmc_step_async and
+ * sxmc_group_step_async in all its forms (one-workgroup, cooperative, two-launch, fused); sxmc_group_finish_step_async and
+ * sxmc_group_finish_columns_step_async finish whatever partial sums they are given.  There is no weighted lockstep set,
+ * look-ahead pass or in-place column sum: with weights set, sxmc_multigroup_step_async,
+ * sxmc_multigroup_lookahead_step_async and sxmc_group_eval_columns_nll_async return SXMC_ERR_STATE, and
+ * sxmc_group_lookahead_supported answers 0. */
+int sxmc_group_set_event_weights(sxmc_group_t g, const double* h_weights, size_t nevents);
 /* The re-tuning of a correlated proposal, on the host (no device call; usable without a GPU).  rows: nrows kept rows
  * of the jump buffer, nparameters + 1 floats each (the last is the NLL, not read); new_widths: the widths AFTER the
  * reference's re-tuning (<= 0: a fixed parameter).  With every float widened to double and every sum taken
@@ -959,6 +981,13 @@ int sxmc_launch_nll_event_chunks(int grid, int block, sxmc_stream_t s, const flo
                                  const double* d_nexpected, const unsigned* d_n_mc,
                                  const short* d_source_id, const unsigned* d_norms,
                                  double* d_sums);
+/* The same with one weight per event (the law: sxmc_group_set_event_weights): thread t adds d_weights[i] * log(s_i),
+ * rounded once, over its events i = t, t + grid*block, ... in index order.  d_weights: ne doubles in DEVICE memory. */
+int sxmc_launch_nll_event_chunks_weighted(int grid, int block, sxmc_stream_t s, const float* d_lut,
+                                          const double* d_pars, size_t ne, size_t ns,
+                                          const double* d_nexpected, const unsigned* d_n_mc,
+                                          const short* d_source_id, const unsigned* d_norms,
+                                          double* d_sums, const double* d_weights);
 /* nll_event_reduce (nll_kernels.cpp:209-212); grid must be 1 */
 int sxmc_launch_nll_event_reduce(int grid, int block, sxmc_stream_t s, size_t nthreads,
                                  const double* d_sums, double* d_total_sum);

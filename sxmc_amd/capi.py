@@ -160,6 +160,7 @@ SIGNATURES = {
     "sxmc_group_launch_info": [_vp, C.c_char_p, _sz],
     "sxmc_group_set_lut_output": [_vp, _i],
     "sxmc_group_set_proposal_factor": [_vp, _vp],
+    "sxmc_group_set_event_weights": [_vp, _vp, _sz],
     "sxmc_proposal_factor": [_vp, _sz, _i, _vp, _d, _vp, _pd],
     "sxmc_group_eval_async": [_vp, _i, _vp],
     "sxmc_group_eval_nll_async": [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _pi],
@@ -195,6 +196,7 @@ SIGNATURES = {
     "sxmc_launch_pick_new_vector": [_i, _i, _vp, _i, _vp, _vp, _vp, _vp],
     "sxmc_launch_jump_decider": [_i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _u, _vp, _vp, _vp],
     "sxmc_launch_nll_event_chunks": [_i, _i, _vp, _vp, _vp, _sz, _sz, _vp, _vp, _vp, _vp, _vp],
+    "sxmc_launch_nll_event_chunks_weighted": [_i, _i, _vp, _vp, _vp, _sz, _sz, _vp, _vp, _vp, _vp, _vp, _vp],
     "sxmc_launch_nll_event_reduce": [_i, _i, _vp, _sz, _vp, _vp],
     "sxmc_launch_nll_total": [_i, _i, _vp, _sz, _vp, _sz, _sz, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp],
     "sxmc_launch_finish_nll_jump_pick_combo": [_i, _i, _vp, _sz, _vp, _sz, _sz, _vp, _vp, _vp, _vp, _vp,

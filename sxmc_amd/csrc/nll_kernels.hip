@@ -59,11 +59,16 @@ __global__ void jump_decider_kernel(sxmc_rng_state* rng, double* nll_current, co
   }
 }
 
-__global__ void nll_event_chunks_kernel(const float* __restrict__ lut, const double* __restrict__ pars,
-                                        size_t ne, size_t ns, const double* __restrict__ nexpected,
-                                        const unsigned* __restrict__ n_mc,
-                                        const short* __restrict__ source_id,
-                                        const unsigned* __restrict__ norms, double* sums) {
+// The body of nll_event_chunks_kernel and of its weighted sibling: one text.  WEIGHTED: event i's term is weight[i] *
+// log(s), rounded once; lane t still sums the events t, t + grid * block, ... in index order.  The weight is asked for
+// at the top of the event's round, before the table values are consumed: it is there when the logarithm is.
+template <bool WEIGHTED>
+__device__ __forceinline__ void nll_event_chunks_body(const float* __restrict__ lut, const double* __restrict__ pars,
+                                                      size_t ne, size_t ns, const double* __restrict__ nexpected,
+                                                      const unsigned* __restrict__ n_mc,
+                                                      const short* __restrict__ source_id,
+                                                      const unsigned* __restrict__ norms, double* sums,
+                                                      const double* __restrict__ weight) {
   extern __shared__ double s_coef[];  // [ns]: pars[sid] * nexpected * eff, the event-independent factor
   for (size_t j = threadIdx.x; j < ns; j += blockDim.x) {
     const float eff = (float)(1.0 * norms[j] / n_mc[j]);
@@ -95,6 +100,8 @@ __global__ void nll_event_chunks_kernel(const float* __restrict__ lut, const dou
   for (size_t i = offset; i < ne; i += stride) {
     double s = 0;
     float v[U];
+    double w = 1.0;
+    if constexpr (WEIGHTED) w = weight[i];
 #pragma unroll
     for (int u = 0; u < U; u++) v[u] = nxt[u];
     for (size_t j0 = 0; j0 < ns; j0 += U) {
@@ -105,9 +112,31 @@ __global__ void nll_event_chunks_kernel(const float* __restrict__ lut, const dou
         if (j0 + (size_t)u < ns) s = s + s_coef[j0 + u] * (double)(!isnan(v[u]) ? v[u] : 0.0f);  // NaN: empty histogram
       }
     }
-    if (s > 0) sum += log(s);
+    if constexpr (WEIGHTED) {
+      if (s > 0) sum += w * log(s);
+    } else {
+      if (s > 0) sum += log(s);
+    }
   }
   if (!isnan(sum)) sums[offset] = sum;
+}
+
+// (the unweighted kernel keeps the argument list it had; the weighted sibling takes the weights behind it)
+__global__ void nll_event_chunks_kernel(const float* __restrict__ lut, const double* __restrict__ pars,
+                                        size_t ne, size_t ns, const double* __restrict__ nexpected,
+                                        const unsigned* __restrict__ n_mc,
+                                        const short* __restrict__ source_id,
+                                        const unsigned* __restrict__ norms, double* sums) {
+  nll_event_chunks_body<false>(lut, pars, ne, ns, nexpected, n_mc, source_id, norms, sums, nullptr);
+}
+
+__global__ void nll_event_chunks_weighted_kernel(const float* __restrict__ lut, const double* __restrict__ pars,
+                                                 size_t ne, size_t ns, const double* __restrict__ nexpected,
+                                                 const unsigned* __restrict__ n_mc,
+                                                 const short* __restrict__ source_id,
+                                                 const unsigned* __restrict__ norms, double* sums,
+                                                 const double* __restrict__ weight) {
+  nll_event_chunks_body<true>(lut, pars, ne, ns, nexpected, n_mc, source_id, norms, sums, weight);
 }
 
 __global__ void nll_event_reduce_kernel(size_t nthreads, const double* sums, double* total_sum) {
@@ -176,6 +205,15 @@ hipError_t sx_nll_event_chunks(int grid, int block, hipStream_t s, const float* 
                                const short* source_id, const unsigned* norms, double* sums) {
   hipLaunchKernelGGL(nll_event_chunks_kernel, dim3(grid), dim3(block), ns * sizeof(double), s, lut, pars, ne,
                      ns, nexpected, n_mc, source_id, norms, sums);
+  return hipGetLastError();
+}
+
+hipError_t sx_nll_event_chunks_weighted(int grid, int block, hipStream_t s, const float* lut, const double* pars,
+                                        size_t ne, size_t ns, const double* nexpected, const unsigned* n_mc,
+                                        const short* source_id, const unsigned* norms, double* sums,
+                                        const double* weight) {
+  hipLaunchKernelGGL(nll_event_chunks_weighted_kernel, dim3(grid), dim3(block), ns * sizeof(double), s, lut, pars, ne,
+                     ns, nexpected, n_mc, source_id, norms, sums, weight);
   return hipGetLastError();
 }
 

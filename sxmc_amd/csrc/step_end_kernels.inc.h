@@ -15,6 +15,7 @@
 #pragma once
 
 #include <cstring>
+#include <type_traits>
 #include <vector>
 
 #include "step_end_plan.h"
@@ -64,9 +65,14 @@ struct MembersFromTable {
   const SxStepEndTable& t;
 };
 
-template <int BD = 0, typename Members, typename Ready>   // (BD > 0: the workgroup's logical size, see block_sum in nll_device.h)
+//
+// THE ROW WEIGHT'S TYPE (`W`, taken from the pointer): unsigned -- how many events a class holds (the walks' default; null:
+// every row counts once) -- or double: real event weights (sxmc_group_set_event_weights), per class their sum W_k in
+// ascending event order, or per event when the rows are the events.  The term is (double)weight[row] * log(s), rounded
+// once, in both; the unsigned instantiations are the text they were, and 1.0 weights give their bytes.
+template <int BD = 0, typename W, typename Members, typename Ready>   // (BD > 0: the workgroup's logical size, see block_sum in nll_device.h)
 __device__ __forceinline__ double eval_nll_block_part(const Members& mem, int nsig,
-                                                      unsigned long long npoints, const unsigned* __restrict__ weight,
+                                                      unsigned long long npoints, const W* __restrict__ weight,
                                                       const double* __restrict__ pars,
                                                       const double* __restrict__ nexpected,
                                                       const unsigned* __restrict__ n_mc,
@@ -108,7 +114,8 @@ __device__ __forceinline__ double eval_nll_block_part(const Members& mem, int ns
     return 0.0;
   }
   load_read_bins(i, 0);
-  unsigned wfirst = weight ? to_global(weight)[i < npoints ? i : npoints - 1] : 1u;
+  static_assert(std::is_same<W, unsigned>::value || std::is_same<W, double>::value, "a count or a real weight");
+  W wfirst = weight ? to_global(weight)[i < npoints ? i : npoints - 1] : W(1);
   unsigned count[U];   // (table form: the first row's counts are gathered before the staging barrier)
 
   // member j's staged record from its loaded inputs (one text for both forms)
@@ -168,7 +175,7 @@ __device__ __forceinline__ double eval_nll_block_part(const Members& mem, int ns
     double s = 0.0;
     // (the row's weight is asked for before the gathers, not after the logarithm: one memory round trip less on a
     //  path that is nothing but round trips)
-    const unsigned wrow = requested ? wfirst : (weight ? to_global(weight)[i] : 1u);
+    const W wrow = requested ? wfirst : (weight ? to_global(weight)[i] : W(1));
     for (int j0 = 0; j0 < nsig; j0 += U) {
       const bool gathered = kTable && requested;
       if (!requested) load_read_bins(i, j0);
@@ -211,9 +218,9 @@ __device__ __forceinline__ double eval_nll_block_part(const Members& mem, int ns
   return t;
 }
 
-template <int BD = 0, typename Ready>
+template <int BD = 0, typename W, typename Ready>
 __device__ __forceinline__ double eval_nll_block_part(const SxSignalDesc* __restrict__ descs, int nsig,
-                                                      unsigned long long npoints, const unsigned* __restrict__ weight,
+                                                      unsigned long long npoints, const W* __restrict__ weight,
                                                       const double* __restrict__ pars,
                                                       const double* __restrict__ nexpected,
                                                       const unsigned* __restrict__ n_mc,
@@ -224,9 +231,9 @@ __device__ __forceinline__ double eval_nll_block_part(const SxSignalDesc* __rest
                                  sh, block_index, nblocks, ready);
 }
 
-template <int BD = 0>
+template <int BD = 0, typename W>
 __device__ __forceinline__ double eval_nll_block_part(const SxSignalDesc* __restrict__ descs, int nsig,
-                                                      unsigned long long npoints, const unsigned* __restrict__ weight,
+                                                      unsigned long long npoints, const W* __restrict__ weight,
                                                       const double* __restrict__ pars,
                                                       const double* __restrict__ nexpected,
                                                       const unsigned* __restrict__ n_mc,
@@ -237,8 +244,9 @@ __device__ __forceinline__ double eval_nll_block_part(const SxSignalDesc* __rest
                                  nblocks, [] {});
 }
 
+template <typename W>
 __device__ __forceinline__ double eval_nll_block(const SxSignalDesc* __restrict__ descs, int nsig,
-                                                 unsigned long long npoints, const unsigned* __restrict__ weight,
+                                                 unsigned long long npoints, const W* __restrict__ weight,
                                                  const double* __restrict__ pars,
                                                  const double* __restrict__ nexpected,
                                                  const unsigned* __restrict__ n_mc,
@@ -382,9 +390,10 @@ __device__ __forceinline__ void lookahead_decide(size_t npartial, const double* 
 }
 
 // ------------------------------------------------------------------------------------ sequential, ticket, look-ahead
+template <typename W>
 __global__ __launch_bounds__(256) void eval_nll_kernel(const SxSignalDesc* __restrict__ descs, int nsig,
                                                        unsigned long long npoints,
-                                                       const unsigned* __restrict__ weight,
+                                                       const W* __restrict__ weight,
                                                        const double* __restrict__ pars,
                                                        const double* __restrict__ nexpected,
                                                        const unsigned* __restrict__ n_mc,
@@ -401,9 +410,10 @@ __global__ __launch_bounds__(256) void eval_nll_kernel(const SxSignalDesc* __res
 // finish_nll_jump_pick_combo.  Hand-off of the partial sums follows the agent-scope release/acquire
 // recipe for gfx950: partial stored, drained and released by lane 0 before its ticket; the last arriver
 // acquires (invalidating its CU's L1) before any of its lanes read the partials.
+template <typename W>
 __global__ __launch_bounds__(256) void eval_nll_finish_kernel(const SxSignalDesc* __restrict__ descs, int nsig,
                                                               unsigned long long npoints,
-                                                              const unsigned* __restrict__ weight, double* sums,
+                                                              const W* __restrict__ weight, double* sums,
                                                               unsigned* ticket, SxStepArgs a) {
   extern __shared__ double sh[];
   const double t =
@@ -488,9 +498,22 @@ __global__ void peek_next_proposal_kernel(int nparameters, const sxmc_rng_state*
 // is a chain of memory latencies, not work: as its own kernels (lookup + event sum over ~40 workgroups, then the
 // step end beside the zeroing) it costs two launch ramps, two kernel boundaries and a round trip of the partial
 // sums through memory; here it is one ramp, and the step's other inputs are in flight under the gathers.
+// `Wait`: Nothing, or NothingWeighted, a type of the same meaning.  WHY TWO TYPES: finish_step_device_w keeps its staging
+// in static __shared__ arrays, one set per instantiation (see `Nothing`), and an instantiation used by TWO kernels has
+// its arrays laid out in the module's shared LDS block instead of the one kernel's own.  OBSERVED (hipcc of ROCm 7, -O3,
+// gfx950, `make asm`): with both weight types finishing through finish_step_w<0, 8, Nothing> the COUNTS' kernel lost 27-30
+// of its 4 648 instructions -- phase B's addends were read from LDS in another order and its loop unrolled otherwise --,
+// with a `Wait` type of its own per kernel it is the parent's code instruction for instruction, as the issue that
+// brought the weights asked (this kernel IS the step end of small fits).  WHEN IT CAN GO: once the staging is owned by
+// the calling kernel (passed in, not static), or when a diff of `make asm` shows the unsigned kernel unchanged
+// without it; nothing but speed depends on it -- the results are the same either way.
+struct NothingWeighted {
+  __device__ __forceinline__ void operator()() const {}
+};
+template <typename W, typename Wait>
 __global__ __launch_bounds__(1024) void tail_step_kernel(const SxSignalDesc* __restrict__ descs, int nsig,
                                                          unsigned long long npoints,
-                                                         const unsigned* __restrict__ weight, SxStepArgs a) {
+                                                         const W* __restrict__ weight, SxStepArgs a) {
   using sxstep::kStepSumRows;
   extern __shared__ double sh[];
   __shared__ double s_total;
@@ -509,7 +532,7 @@ __global__ __launch_bounds__(1024) void tail_step_kernel(const SxSignalDesc* __r
   }
   __syncthreads();
   // (a launch bound of 1024 lanes, 128 registers: few of phase B's addends in registers)
-  finish_step<8>(1, &s_total, a);
+  finish_step_w<0, 8>(1, &s_total, a, a.norms, Wait{});
   // (the normalisations were last read before the barriers inside finish_step_device)
   for (int j = 0; j < nsig; j++) {
     const SxSignalDesc& d = descs[j];
@@ -573,9 +596,10 @@ struct SxTailArgs {
   const SxSignalDesc* lookup_descs;
   const SxSignalDesc* hist_descs;
   int nsig;
-  unsigned nvb, zblocks, pad;
+  unsigned nvb, zblocks;
+  unsigned real_weights;        // 0: `weight` points at unsigned counts (or is null); 1: at doubles (the same 8 bytes)
   unsigned long long npoints;
-  const unsigned* weight;
+  const void* weight;
   unsigned long long* slots;
   double* last_good;
   unsigned* sync;
@@ -588,10 +612,10 @@ struct SxTailArgs {
 // eval_nll_block_part): nothing for step_end_kernel, whose launch follows the fill's; the wait for the fill's workgroups
 // in fill_step_kernel.
 // `lookup`: where the workers' members come from (MembersFromDescs / MembersFromTable, see eval_nll_block_part).
-template <int BD, typename Members, typename Ready>
+template <int BD, typename Wt, typename Members, typename Ready>
 __device__ __forceinline__ void step_end_role(unsigned role, unsigned W, const Members& lookup,
                                               const SxSignalDesc* __restrict__ hist_descs, int nsig,
-                                              unsigned long long npoints, const unsigned* __restrict__ weight,
+                                              unsigned long long npoints, const Wt* __restrict__ weight,
                                               unsigned long long* slots, double* last_good, unsigned* sync,
                                               unsigned nvb, unsigned zblocks, const SxStepArgs& a, double* sh,
                                               Ready&& ready) {
@@ -666,10 +690,10 @@ __device__ __forceinline__ void step_end_role(unsigned role, unsigned W, const M
 
 // TABLE: the workers' look-up pointers arrive by value (`table`: groups of up to 16 members -- the flagship's and config
 // 2's step end) beside `lookup_descs`; otherwise everything comes from `lookup_descs`, and `table` is not read.
-template <bool TABLE>
+template <bool TABLE, typename Wt = unsigned>
 __global__ __launch_bounds__(128) void step_end_kernel(const SxSignalDesc* __restrict__ lookup_descs,
                                                        const SxSignalDesc* __restrict__ hist_descs, int nsig,
-                                                       unsigned long long npoints, const unsigned* __restrict__ weight,
+                                                       unsigned long long npoints, const Wt* __restrict__ weight,
                                                        unsigned long long* slots, double* last_good, unsigned* sync,
                                                        unsigned nvb, unsigned zblocks, SxStepArgs a, SxStepEndTable table) {
   extern __shared__ double sh[];
@@ -737,8 +761,15 @@ __device__ __forceinline__ void fill_step_body(unsigned nfill, const SxTailArgs&
     SX_WG_STAMP(1);
     __syncthreads();
   };
-  step_end_role<128>(role, W, MembersFromDescs{t.lookup_descs}, t.hist_descs, t.nsig, t.npoints, t.weight, t.slots, t.last_good, t.sync,
-                     t.nvb, t.zblocks, t.a, sh_tail, fill_done);
+  // (uniform, a kernel argument.  Real event weights: the WORKERS take the roles' double instantiation; the finisher never
+  //  sees the weights and stays in the other, so that the kernel holds one set of the finisher's staging arrays in LDS)
+  if (t.real_weights && role != W) {
+    step_end_role<128>(role, W, MembersFromDescs{t.lookup_descs}, t.hist_descs, t.nsig, t.npoints,
+                       static_cast<const double*>(t.weight), t.slots, t.last_good, t.sync, t.nvb, t.zblocks, t.a, sh_tail, fill_done);
+  } else {
+    step_end_role<128>(role, W, MembersFromDescs{t.lookup_descs}, t.hist_descs, t.nsig, t.npoints,
+                       static_cast<const unsigned*>(t.weight), t.slots, t.last_good, t.sync, t.nvb, t.zblocks, t.a, sh_tail, fill_done);
+  }
   // the finisher is the last to need the count of this launch: it zeroes it for the next one
   if (role == W && threadIdx.x == 0) __hip_atomic_store(done, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
   SX_WG_STAMP(2);
@@ -827,8 +858,8 @@ __global__ __launch_bounds__(256) void finish_zero_chains_kernel(SxChainEnds e, 
 size_t sx_tail_args_bytes() { return sizeof(SxTailArgs); }
 // Fills the host image of a group's SxTailArgs (the device struct is private to this file).
 void sx_tail_args_fill(void* image, const SxSignalDesc* lookup_descs, const SxSignalDesc* hist_descs, int nsig,
-                       int max_bins, unsigned long long npoints, const unsigned* weight, unsigned long long* slots,
-                       double* last_good, unsigned* sync, int nvb, const SxStepArgs& a) {
+                       int max_bins, unsigned long long npoints, const unsigned* weight, const double* real_weight,
+                       unsigned long long* slots, double* last_good, unsigned* sync, int nvb, const SxStepArgs& a) {
   SxTailArgs t;
   std::memset(&t, 0, sizeof t);   // (padding too: the host compares images bytewise to see whether to upload again)
   t.lookup_descs = lookup_descs;
@@ -837,7 +868,8 @@ void sx_tail_args_fill(void* image, const SxSignalDesc* lookup_descs, const SxSi
   t.nvb = (unsigned)nvb;
   t.zblocks = (unsigned)sxstep::zero_blocks(max_bins, 128);   // (the roles are workgroups of 128)
   t.npoints = npoints;
-  t.weight = weight;
+  t.weight = real_weight ? static_cast<const void*>(real_weight) : static_cast<const void*>(weight);
+  t.real_weights = real_weight ? 1u : 0u;
   t.slots = slots;
   t.last_good = last_good;
   t.sync = sync;
@@ -845,19 +877,22 @@ void sx_tail_args_fill(void* image, const SxSignalDesc* lookup_descs, const SxSi
   std::memcpy(image, &t, sizeof t);
 }
 
+// (each launcher of a row sum twice, by the weight's type: counts or real weights -- one text)
+template <typename W>
 hipError_t sx_launch_eval_nll(const SxSignalDesc* d_descs, int nsig, unsigned long long npoints,
-                              const unsigned* weight, const double* pars, const double* nexpected, const unsigned* n_mc,
+                              const W* weight, const double* pars, const double* nexpected, const unsigned* n_mc,
                               const short* source_id, const unsigned* norms, double* sums,
                               int grid, int block, hipStream_t s) {
-  hipLaunchKernelGGL(eval_nll_kernel, dim3(grid), dim3(block), sxstep::step_end_lds_bytes(nsig), s, d_descs, nsig, npoints,
+  hipLaunchKernelGGL(eval_nll_kernel<W>, dim3(grid), dim3(block), sxstep::step_end_lds_bytes(nsig), s, d_descs, nsig, npoints,
                      weight, pars, nexpected, n_mc, source_id, norms, sums);
   return hipGetLastError();
 }
 
+template <typename W>
 hipError_t sx_launch_eval_nll_finish(const SxSignalDesc* d_descs, int nsig, unsigned long long npoints,
-                                      const unsigned* weight, double* sums, unsigned* ticket, const SxStepArgs& a,
+                                      const W* weight, double* sums, unsigned* ticket, const SxStepArgs& a,
                                       int grid, int block, hipStream_t s) {
-  hipLaunchKernelGGL(eval_nll_finish_kernel, dim3(grid), dim3(block), sxstep::step_end_lds_bytes(nsig), s, d_descs, nsig,
+  hipLaunchKernelGGL(eval_nll_finish_kernel<W>, dim3(grid), dim3(block), sxstep::step_end_lds_bytes(nsig), s, d_descs, nsig,
                      npoints, weight, sums, ticket, a);
   return hipGetLastError();
 }
@@ -889,10 +924,12 @@ hipError_t sx_launch_peek_next_proposal(int nparameters, const sxmc_rng_state* r
   return hipGetLastError();
 }
 
+template <typename W>
 hipError_t sx_launch_tail_step(const SxSignalDesc* d_descs, int nsig, unsigned long long npoints,
-                               const unsigned* weight, const SxStepArgs& a, hipStream_t s) {
-  hipLaunchKernelGGL(tail_step_kernel, dim3(1), dim3(1024), sxstep::step_end_lds_bytes(nsig), s, d_descs, nsig, npoints,
-                     weight, a);
+                               const W* weight, const SxStepArgs& a, hipStream_t s) {
+  using Wait = typename std::conditional<std::is_same<W, double>::value, NothingWeighted, Nothing>::type;
+  hipLaunchKernelGGL((tail_step_kernel<W, Wait>), dim3(1), dim3(1024), sxstep::step_end_lds_bytes(nsig), s, d_descs, nsig,
+                     npoints, weight, a);
   return hipGetLastError();
 }
 
@@ -904,18 +941,19 @@ hipError_t sx_launch_finish_zero(const SxSignalDesc* d_descs, int nsig, int max_
   return hipGetLastError();
 }
 
+template <typename W>
 hipError_t sx_launch_step_end(const SxSignalDesc* lookup_descs, const SxSignalDesc* hist_descs, int nsig, int max_bins,
-                              unsigned long long npoints, const unsigned* weight, unsigned long long* slots,
+                              unsigned long long npoints, const W* weight, unsigned long long* slots,
                               double* last_good, unsigned* sync, int nvb, const SxStepArgs& a, hipStream_t s,
                               const SxStepEndTable* table) {
   const int block = 128;   // (the rows of a virtual block of the event sum: eval_nll_kernel's workgroup)
   const size_t shmem = sxstep::step_end_lds_bytes(nsig);
   const unsigned zb = (unsigned)sxstep::zero_blocks(max_bins, block);
   if (table && nsig <= SXMC_STEP_END_MEMBERS) {
-    hipLaunchKernelGGL(step_end_kernel<true>, dim3((unsigned)nvb + 1u), dim3(block), shmem, s, lookup_descs, hist_descs,
+    hipLaunchKernelGGL((step_end_kernel<true, W>), dim3((unsigned)nvb + 1u), dim3(block), shmem, s, lookup_descs, hist_descs,
                        nsig, npoints, weight, slots, last_good, sync, (unsigned)nvb, zb, a, *table);
   } else {
-    hipLaunchKernelGGL(step_end_kernel<false>, dim3((unsigned)nvb + 1u), dim3(block), shmem, s, lookup_descs, hist_descs,
+    hipLaunchKernelGGL((step_end_kernel<false, W>), dim3((unsigned)nvb + 1u), dim3(block), shmem, s, lookup_descs, hist_descs,
                        nsig, npoints, weight, slots, last_good, sync, (unsigned)nvb, zb, a, SxStepEndTable{});
   }
   return hipGetLastError();
@@ -932,6 +970,21 @@ hipError_t sx_launch_step_end2(const SxSignalDesc* lookup_a, const SxSignalDesc*
                      (unsigned)nvb, (unsigned)sxstep::zero_blocks(max_bins, block), norms_b, v_b, cap, a);
   return hipGetLastError();
 }
+
+#define SX_ROW_SUM_LAUNCHERS(W)                                                                                            \
+  template hipError_t sx_launch_eval_nll<W>(const SxSignalDesc*, int, unsigned long long, const W*, const double*,        \
+                                            const double*, const unsigned*, const short*, const unsigned*, double*, int,  \
+                                            int, hipStream_t);                                                            \
+  template hipError_t sx_launch_eval_nll_finish<W>(const SxSignalDesc*, int, unsigned long long, const W*, double*,       \
+                                                   unsigned*, const SxStepArgs&, int, int, hipStream_t);                  \
+  template hipError_t sx_launch_tail_step<W>(const SxSignalDesc*, int, unsigned long long, const W*, const SxStepArgs&,   \
+                                             hipStream_t);                                                                \
+  template hipError_t sx_launch_step_end<W>(const SxSignalDesc*, const SxSignalDesc*, int, int, unsigned long long,       \
+                                            const W*, unsigned long long*, double*, unsigned*, int, const SxStepArgs&,    \
+                                            hipStream_t, const SxStepEndTable*);
+SX_ROW_SUM_LAUNCHERS(unsigned)
+SX_ROW_SUM_LAUNCHERS(double)
+#undef SX_ROW_SUM_LAUNCHERS
 
 // Workgroups of the cooperative step end the device holds at once (the runtime's occupancy figure for step_end_kernel
 // with this launch's LDS x the CU count; 0: could not be asked) -- what the host's residency check counts against

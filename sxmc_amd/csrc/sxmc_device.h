@@ -118,8 +118,9 @@ inline unsigned sx_fill_w(const SxLaunchShape& sh) {
 }
 size_t sx_tail_args_bytes();
 void sx_tail_args_fill(void* image, const SxSignalDesc* lookup_descs, const SxSignalDesc* hist_descs, int nsig,
-                       int max_bins, unsigned long long npoints, const unsigned* weight, unsigned long long* slots,
-                       double* last_good, unsigned* sync, int nvb, const struct SxStepArgs& a);
+                       int max_bins, unsigned long long npoints, const unsigned* weight, const double* real_weight,
+                       unsigned long long* slots, double* last_good, unsigned* sync, int nvb, const struct SxStepArgs& a);
+// (real_weight: real event weights in `weight`'s place -- the roles' double instantiation; null: counts, or neither)
 
 // A fill kernel specialised at run time (sxmc_rtc.cpp): the template arguments of fill_body / fill_sparse_body.
 struct SxRtcSpec {
@@ -144,8 +145,11 @@ hipError_t sx_rtc_launch(void* fn, int grid, int threads, size_t lds_bytes, cons
                          void* ev_start = nullptr, void* ev_stop = nullptr);
 
 hipError_t sx_launch_zero(const SxSignalDesc* d_descs, int nsig, int max_bins, unsigned* ticket, hipStream_t s);
+// (the launchers of a row sum are templates over the row weight's type W: unsigned counts -- null: none --, or double
+//  event weights; both instantiated in pdfz_kernels.hip's unit)
+template <typename W>
 hipError_t sx_launch_step_end(const SxSignalDesc* lookup_descs, const SxSignalDesc* hist_descs, int nsig, int max_bins,
-                              unsigned long long npoints, const unsigned* weight, unsigned long long* slots,
+                              unsigned long long npoints, const W* weight, unsigned long long* slots,
                               double* last_good, unsigned* sync, int nvb, const SxStepArgs& a, hipStream_t s,
                               const SxStepEndTable* table = nullptr);   // (the lookup members by value, or null)
 hipError_t sx_launch_step_end2(const SxSignalDesc* lookup_a, const SxSignalDesc* lookup_b, const SxSignalDesc* hist_a,
@@ -158,8 +162,9 @@ int sx_step_end_resident_capacity(int nsig, int cus);
 hipError_t sx_launch_chain_ends(const SxChainEnds& e, int nchains, int nsig, int max_bins, int block, hipStream_t s);
 hipError_t sx_launch_finish_zero(const SxSignalDesc* d_descs, int nsig, int max_bins, size_t npartial,
                                  const double* sums, unsigned* ticket, const SxStepArgs& a, int block, hipStream_t s);
+template <typename W>
 hipError_t sx_launch_eval_nll_finish(const SxSignalDesc* d_descs, int nsig, unsigned long long npoints,
-                                      const unsigned* weight, double* sums, unsigned* ticket, const SxStepArgs& a,
+                                      const W* weight, double* sums, unsigned* ticket, const SxStepArgs& a,
                                       int grid, int block, hipStream_t s);
 hipError_t sx_launch_eval_nll2(const SxSignalDesc* descs_a, const SxSignalDesc* descs_b, int nsig,
                                unsigned long long npoints, const unsigned* weight_a, const unsigned* weight_b,
@@ -172,8 +177,9 @@ hipError_t sx_launch_finish2_zero(const SxSignalDesc* descs_a, const SxSignalDes
                                   double* v_b, const int* cap, const SxStepArgs& a, int block, hipStream_t s);
 hipError_t sx_launch_peek_next_proposal(int nparameters, const sxmc_rng_state* rng, const float* jump_width,
                                         const double* v_current, double* out, hipStream_t s);
+template <typename W>
 hipError_t sx_launch_tail_step(const SxSignalDesc* d_descs, int nsig, unsigned long long npoints,
-                               const unsigned* weight, const SxStepArgs& a, hipStream_t s);
+                               const W* weight, const SxStepArgs& a, hipStream_t s);
 hipError_t sx_launch_fill(const SxLaunchShape& shape, const SxSignalDesc* d_descs, const SxSegment* d_segs,
                           const unsigned* d_blk_off, hipStream_t s);
 hipError_t sx_launch_fill_sparse_runs(const SxLaunchShape& shape, const SxSignalDesc* d_descs, const SxSegment* d_segs,
@@ -221,8 +227,9 @@ hipError_t sx_hist_project(const unsigned* d_bins, unsigned long long total, uns
                            unsigned long long* d_out, unsigned max_blocks, hipStream_t s);
 hipError_t sx_launch_eval_pdf(const SxSignalDesc* d_descs, int nsig, unsigned long long max_points,
                               hipStream_t s);
+template <typename W>
 hipError_t sx_launch_eval_nll(const SxSignalDesc* d_descs, int nsig, unsigned long long npoints,
-                              const unsigned* weight, const double* pars, const double* nexpected, const unsigned* n_mc,
+                              const W* weight, const double* pars, const double* nexpected, const unsigned* n_mc,
                               const short* source_id, const unsigned* norms, double* sums,
                               int grid, int block, hipStream_t s);
 // The event sum over a mixed table (columns_kernels.hip): d_member_of[j] >= 0: column j is looked up from that member of

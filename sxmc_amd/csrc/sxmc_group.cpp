@@ -69,9 +69,20 @@ static sxmc_step_args pack_step_args(const double* d_means, const double* d_sigm
 }
 
 StepRows step_rows(const sxmc_group* g, bool sparse) {
-  if (g->cfg_lut) return {sparse ? g->d_descs_sparse.get() : g->d_descs.get(), nullptr, g->members[0]->npoints};
+  const bool real = !g->event_weights.empty();
+  if (g->cfg_lut) {
+    return {sparse ? g->d_descs_sparse.get() : g->d_descs.get(), nullptr, g->members[0]->npoints,
+            real ? g->d_event_weights.get() : nullptr};
+  }
   const sxmc_group::EventClasses& ec = g->ec[sparse ? 1 : 0];
-  return {ec.d_descs.get(), ec.d_weight.get(), ec.K};
+  return {ec.d_descs.get(), ec.d_weight.get(), ec.K, real ? ec.d_real_weight.get() : nullptr};
+}
+
+int ensure_step_rows(sxmc_group* g, bool sparse) {
+  if (!g->event_weights.empty() && (g->members.empty() || g->event_weights.size() != g->members[0]->npoints)) {
+    return fail(SXMC_ERR_STATE, "the group's event weights are not one per evaluation point of its members");
+  }
+  return g->cfg_lut ? SXMC_OK : ensure_event_classes(g, sparse);
 }
 
 void mark_cleared(sxmc_group* g, bool sparse) {
@@ -475,6 +486,29 @@ int sxmc_group_set_lut_output(sxmc_group_t g, int enable) {
   return SXMC_OK;
 }
 
+int sxmc_group_set_event_weights(sxmc_group_t g, const double* h_weights, size_t nevents) {
+  SX_REQUIRE(g, "null group");
+  SX_REQUIRE(h_weights || nevents == 0, "event weights: a null array of a positive length");
+  if (t_capturing) return fail(SXMC_ERR_STATE, "event weights cannot be set while recording a graph");
+  const long long bad = sxplan::first_bad_event_weight(h_weights, nevents);
+  if (bad >= 0) {
+    return fail(SXMC_ERR_INVALID, "event weight " + std::to_string(bad) + " is not a finite number >= 0");
+  }
+  if (nevents == 0 && g->event_weights.empty()) return SXMC_OK;   // (nothing set, nothing to clear: no wait, nothing invalidated)
+  SX_FLUSH();
+  if (g->built) SX_HIP(hipStreamSynchronize(g->last_stream));   // (a step in flight reads the weights replaced here)
+  if (nevents > g->d_event_weights.capacity()) SX_BUF(g->d_event_weights.grow(nevents));
+  if (nevents) {
+    SX_HIP(hipMemcpy(g->d_event_weights.get(), h_weights, sizeof(double) * nevents, hipMemcpyHostToDevice));
+    g->event_weights.assign(h_weights, h_weights + nevents);
+  } else {
+    g->event_weights.clear();
+  }
+  // (the classes' weight sums are made with their tables: out of date like after new points)
+  g->ec[0].tables_valid = g->ec[1].tables_valid = false;
+  return SXMC_OK;
+}
+
 int sxmc_group_set_proposal_factor(sxmc_group_t g, const double* d_factor) {
   SX_REQUIRE(g, "null group");
   g->proposal_factor = d_factor;   // (borrowed; read by sx_step_args at every step end the group launches)
@@ -544,22 +578,20 @@ int sxmc_group_eval_nll_async(sxmc_group_t g, sxmc_stream_t s, const double* d_p
   hipStream_t st = (hipStream_t)s;
   g->last_stream = st;
   const bool sparse = g->sparse_ready && g->cfg_sparse;
-  if (!g->cfg_lut) {
-    rc = ensure_event_classes(g, sparse);  // (may upload tables: before anything is launched)
-    if (rc) return rc;
-  }
+  rc = ensure_step_rows(g, sparse);  // (may upload tables: before anything is launched)
+  if (rc) return rc;
   rc = group_fill(g, st, sparse);
   if (rc) return rc;
   SX_REQUIRE(g->members.size() <= 1024, "too many members for the fused evaluation");
   // lookup table wanted: one pass over the events in order; otherwise over the distinct bin tuples
-  if (!g->cfg_lut) {
-    rc = ensure_event_classes(g, sparse);
-    if (rc) return rc;
-  }
+  rc = ensure_step_rows(g, sparse);
+  if (rc) return rc;
   const StepRows rows = step_rows(g, sparse);
   const int grid = step_sum_blocks(rows.ne);
-  SX_HIP(sx_launch_eval_nll(rows.descs, (int)g->members.size(), rows.ne, rows.weight, d_pars, d_nexpected, d_n_mc,
-                            d_source_id, d_norms, d_sums, grid, (int)sxstep::kStepSumRows, st));
+  SX_HIP(rows.with_weight([&](auto w) {
+    return sx_launch_eval_nll(rows.descs, (int)g->members.size(), rows.ne, w, d_pars, d_nexpected, d_n_mc, d_source_id,
+                              d_norms, d_sums, grid, (int)sxstep::kStepSumRows, st);
+  }));
   *npartial_out = grid;
   return SXMC_OK;
 }
@@ -587,20 +619,20 @@ int sxmc_group_mcmc_step_async(sxmc_group_t g, sxmc_stream_t s, const double* d_
   hipStream_t st = (hipStream_t)s;
   g->last_stream = st;
   const bool sparse = g->sparse_ready && g->cfg_sparse;
-  if (!g->cfg_lut) {
-    rc = ensure_event_classes(g, sparse);
-    if (rc) return rc;
-  }
+  rc = ensure_step_rows(g, sparse);
+  if (rc) return rc;
   const StepRows rows = step_rows(g, sparse);
   rc = group_fill(g, st, sparse);  // zero (also clears the ticket) + fill
   if (rc) return rc;
   const sxmc_step_args p = pack_step_args(d_means, d_sigmas, d_rng, d_nll_current, d_nll_proposed, d_v_current, d_v_proposed,
                                           d_accepted, d_counter, d_jump_buffer, nparameters, nsources, d_jump_width,
                                           d_nexpected, d_n_mc, d_source_id, d_norms, debug_mode);
-  SX_HIP(sx_launch_eval_nll_finish(rows.descs, (int)g->members.size(), rows.ne, rows.weight, g->d_step_sums.get(),
-                                   g->d_ticket.get() + sxstep::kTicket,
-                                   sx_step_args(p, g->members.size(), g->proposal_factor),
-                                   step_sum_blocks(rows.ne), (int)sxstep::kStepSumRows, st));
+  SX_HIP(rows.with_weight([&](auto w) {
+    return sx_launch_eval_nll_finish(rows.descs, (int)g->members.size(), rows.ne, w, g->d_step_sums.get(),
+                                     g->d_ticket.get() + sxstep::kTicket,
+                                     sx_step_args(p, g->members.size(), g->proposal_factor), step_sum_blocks(rows.ne),
+                                     (int)sxstep::kStepSumRows, st);
+  }));
   return SXMC_OK;
 }
 
@@ -652,6 +684,10 @@ int sxmc_group_eval_columns_nll_async(sxmc_group_t g, sxmc_stream_t s, const flo
   SX_REQUIRE(d_pars && d_nexpected && d_n_mc && d_source_id && d_norms && d_sums, "null argument");
   SX_REQUIRE(grid >= 1 && grid <= 65535 && block >= 1 && block <= 256, "grid must be 1 .. 65535, block 1 .. 256");
   if (g->col_member.empty()) return fail(SXMC_ERR_STATE, "eval_columns_nll before sxmc_group_set_columns");
+  if (!g->event_weights.empty()) {
+    return fail(SXMC_ERR_STATE, "the group has event weights set: the event sum with look-ups in place has no weighted form "
+                                "-- evaluate into the table and sum it with sxmc_launch_nll_event_chunks_weighted");
+  }
   SX_REQUIRE(d_lut || g->col_member.size() == g->members.size(), "null lookup table with dense columns");
   SX_REQUIRE(g->col_member.size() <= 1024, "too many columns for the mixed event sum");
   int rc = group_refresh(g);
@@ -784,7 +820,8 @@ int group_step_tail(sxmc_group* g, hipStream_t st, bool sparse, const StepRows& 
   // at config 2 (~2500 x 6) 16 us against 9, at the bench_pdfz shape (1000 x 1) 8 us against 7; config 1 (10 x 2)
   // gains 0.6 us of 14.7.  Only the smallest problems take it.
   if (step_end_takes_tail(g, sparse, rows.ne)) {
-    SX_HIP(sx_launch_tail_step(rows.descs, (int)g->members.size(), rows.ne, rows.weight, a, st));
+    SX_HIP(rows.with_weight(
+        [&](auto w) { return sx_launch_tail_step(rows.descs, (int)g->members.size(), rows.ne, w, a, st); }));
     g->last_step_launches += 1;
   } else if (step_end_is_cooperative(g, rows.ne)) {
     // ONE launch: the event sum's workgroups + a finisher that waits for them inside the kernel (step_end_kernel)
@@ -801,15 +838,19 @@ int group_step_tail(sxmc_group* g, hipStream_t st, bool sparse, const StepRows& 
       const std::vector<SxSignalDesc>& flavour = sparse ? g->h_descs_sparse : g->h_descs;
       if (sx_step_end_table_fill(own, flavour.data(), flavour.size())) table = &own;
     }
-    SX_HIP(sx_launch_step_end(rows.descs, sparse ? g->d_descs_sparse.get() : g->d_descs.get(), (int)g->members.size(),
-                              sparse ? g->max_bins_sparse : g->max_bins, rows.ne, rows.weight, g->d_coop_slots.get(),
-                              g->d_coop_last.get(), g->d_ticket.get(), nvb, a, st, table));
+    SX_HIP(rows.with_weight([&](auto w) {
+      return sx_launch_step_end(rows.descs, sparse ? g->d_descs_sparse.get() : g->d_descs.get(), (int)g->members.size(),
+                                sparse ? g->max_bins_sparse : g->max_bins, rows.ne, w, g->d_coop_slots.get(),
+                                g->d_coop_last.get(), g->d_ticket.get(), nvb, a, st, table);
+    }));
     g->last_step_launches += 1;
   } else {
     g->last_step_launches += 2;
     const int grid = step_sum_blocks(rows.ne);
-    SX_HIP(sx_launch_eval_nll(rows.descs, (int)g->members.size(), rows.ne, rows.weight, a.v_proposed, a.nexpected, a.n_mc,
-                              a.source_id, a.norms, g->d_step_sums.get(), grid, (int)sxstep::kStepSumRows, st));
+    SX_HIP(rows.with_weight([&](auto w) {
+      return sx_launch_eval_nll(rows.descs, (int)g->members.size(), rows.ne, w, a.v_proposed, a.nexpected, a.n_mc,
+                                a.source_id, a.norms, g->d_step_sums.get(), grid, (int)sxstep::kStepSumRows, st);
+    }));
     return finish_and_clear(g, st, sparse, (size_t)grid, g->d_step_sums.get(), a);
   }
   mark_cleared(g, sparse);
@@ -842,10 +883,8 @@ int sxmc_group_step_async(sxmc_group_t g, sxmc_stream_t s, const double* d_means
   hipStream_t st = (hipStream_t)s;
   g->last_stream = st;
   const bool sparse = g->sparse_ready && g->cfg_sparse;
-  if (!g->cfg_lut) {
-    rc = ensure_event_classes(g, sparse);  // (may upload tables: before anything is launched)
-    if (rc) return rc;
-  }
+  rc = ensure_step_rows(g, sparse);  // (may upload tables: before anything is launched)
+  if (rc) return rc;
   const StepRows rows = step_rows(g, sparse);
   const unsigned long long ne = rows.ne;
   const bool zero_launched = g->prezeroed != (sparse ? 2 : 1);   // (group_fill decides the same way, plus bookkeeping)
@@ -863,7 +902,7 @@ int sxmc_group_step_async(sxmc_group_t g, sxmc_stream_t s, const double* d_means
     const int nvb = step_sum_blocks(ne);
     g->h_tail.resize(sx_tail_args_bytes());   // (passed to the kernel by value: frozen at capture like every argument)
     sx_tail_args_fill(g->h_tail.data(), rows.descs, g->d_descs.get(), (int)g->members.size(), g->max_bins, ne, rows.weight,
-                      g->d_coop_slots.get(), g->d_coop_last.get(), g->d_ticket.get(), nvb, a);
+                      rows.real, g->d_coop_slots.get(), g->d_coop_last.get(), g->d_ticket.get(), nvb, a);
     c.shape.tail = g->h_tail.data();
     c.shape.tail_blocks = nvb + 1;
   }

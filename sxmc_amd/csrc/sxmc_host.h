@@ -56,6 +56,9 @@ hipError_t sx_nll_jump_decider(int, int, hipStream_t, sxmc_rng_state*, double*, 
                                const double*, unsigned, int*, int*, float*);
 hipError_t sx_nll_event_chunks(int, int, hipStream_t, const float*, const double*, size_t, size_t,
                                const double*, const unsigned*, const short*, const unsigned*, double*);
+hipError_t sx_nll_event_chunks_weighted(int, int, hipStream_t, const float*, const double*, size_t, size_t,
+                                        const double*, const unsigned*, const short*, const unsigned*, double*,
+                                        const double*);
 hipError_t sx_nll_event_reduce(int, hipStream_t, size_t, const double*, double*);
 hipError_t sx_nll_total(hipStream_t, size_t, const double*, size_t, size_t, const double*, const double*,
                         const double*, const double*, const unsigned*, const short*, const unsigned*, double*);
@@ -416,6 +419,7 @@ struct sxmc_group {
   struct EventClasses {
     sxhost::DeviceBuffer<int> d_rb;             // [nmembers][K] (grow-only, like d_weight)
     sxhost::DeviceBuffer<unsigned> d_weight;    // [K]
+    sxhost::DeviceBuffer<double> d_real_weight; // [K] with event weights set: the classes' weight sums (sxplan::class_weights)
     sxhost::DeviceBuffer<SxSignalDesc> d_descs; // member descriptors reading the class tables, no lookup-table output
     SxStepEndTable table;                       // the same descriptors as the cooperative step end takes them by value,
     bool has_table = false;                     // ... built with every upload of d_descs (up to 16 members)
@@ -424,6 +428,10 @@ struct sxmc_group {
     std::vector<unsigned long long> seen_points;
   };
   EventClasses ec[2];               // [0] dense, [1] sparse flavour
+  // sxmc_group_set_event_weights: one real weight per event (finite, >= 0), the host's copy and the device's; empty: every
+  // event counts once.  Rows that are classes carry the classes' sums (ec[].d_real_weight), rows that are events these.
+  std::vector<double> event_weights;
+  sxhost::DeviceBuffer<double> d_event_weights;
   std::vector<SxSignalDesc> h_descs_sparse;
   int cfg_lut = 1;
   // sxmc_group_set_columns: the lookup table of a mixed fit in signal order, per column the member looked up in place or
@@ -522,10 +530,17 @@ int proposal_factor_check(const double* factor, int nparameters, size_t nsignals
 // wanted, the events themselves.  ensure_event_classes comes first, before anything is launched: the caller's.
 struct StepRows {
   const SxSignalDesc* descs;
-  const unsigned* weight;
+  const unsigned* weight;   // events per class, or null: rows are events
   unsigned long long ne;
+  const double* real = nullptr;   // the group has event weights: one per row, in `weight`'s place
+  // f(the rows' weights, in their type): the launchers of a row sum are templates over it
+  template <typename F>
+  auto with_weight(F&& f) const { return real ? f(real) : f(weight); }
 };
 StepRows step_rows(const sxmc_group* g, bool sparse);
+// What an entry point does for its rows before anything is launched: the event weights' count against the members'
+// points, and without the lookup table the event classes (ensure_event_classes).
+int ensure_step_rows(sxmc_group* g, bool sparse);
 void mark_cleared(sxmc_group* g, bool sparse);   // a step end has cleared this flavour's histograms and normalisations
 bool step_end_takes_tail(const sxmc_group* g, bool sparse, unsigned long long ne);
 void note_stepping(sxmc_group* g);

@@ -1141,6 +1141,16 @@ int ensure_event_classes(sxmc_group* g, bool sparse) {
     if (std::max<size_t>(K, 1) > ec.d_weight.capacity()) SX_BUF(ec.d_weight.grow(K + K / 4 + 16));
     SX_HIP(hipMemcpy(ec.d_rb.get(), tables.data(), sizeof(int) * tables.size(), hipMemcpyHostToDevice));
     if (K) SX_HIP(hipMemcpy(ec.d_weight.get(), weight.data(), sizeof(unsigned) * K, hipMemcpyHostToDevice));
+    if (!g->event_weights.empty()) {
+      // real event weights (sxmc_group_set_event_weights: it drops these tables, as new points do): the classes' sums
+      if (g->event_weights.size() != E) {
+        return fail(SXMC_ERR_STATE, "the group's event weights are not one per evaluation point of its members");
+      }
+      std::vector<double> W;
+      sxplan::class_weights(arr, E, cls, g->event_weights.data(), W);
+      if (std::max<size_t>(K, 1) > ec.d_real_weight.capacity()) SX_BUF(ec.d_real_weight.grow(K + K / 4 + 16));
+      if (K) SX_HIP(hipMemcpy(ec.d_real_weight.get(), W.data(), sizeof(double) * K, hipMemcpyHostToDevice));
+    }
     ec.K = K;
     ec.seen_points.resize(S);
     for (size_t j = 0; j < S; j++) ec.seen_points[j] = g->members[j]->points_version;

@@ -129,6 +129,10 @@ int sxmc_multigroup_step_async(sxmc_multigroup_t mg, sxmc_stream_t s, const sxmc
       return fail(SXMC_ERR_STATE, "a member group has a proposal factor set: lockstep sets have no correlated step end "
                                   "-- step the chains one by one (sxmc_group_step_async)");
     }
+    if (!g->event_weights.empty()) {
+      return fail(SXMC_ERR_STATE, "a member group has event weights set: lockstep sets have no weighted step end "
+                                  "-- step the chains one by one (sxmc_group_step_async)");
+    }
   }
   // every chain's own plan first (may upload: before anything is launched)
   bool replan = mg->seen.size() != C;
@@ -243,6 +247,10 @@ int sxmc_multigroup_lookahead_step_async(sxmc_multigroup_t mg, sxmc_stream_t s, 
       return fail(SXMC_ERR_STATE, "a member group has a proposal factor set: the look-ahead pass has no correlated form "
                                   "-- walk sequentially (sxmc_group_lookahead_supported says so beforehand)");
     }
+    if (!g->event_weights.empty()) {
+      return fail(SXMC_ERR_STATE, "a member group has event weights set: the look-ahead pass has no weighted form "
+                                  "-- walk sequentially (sxmc_group_lookahead_supported says so beforehand)");
+    }
   }
   hipStream_t st = (hipStream_t)s;
   bool replan = mg->seen.size() != 2;
@@ -333,6 +341,7 @@ int sxmc_group_lookahead_supported(sxmc_group_t g, int* ok) {
   SX_REQUIRE(g && ok, "null argument");
   *ok = 0;
   if (g->proposal_factor) return SXMC_OK;   // (no correlated look-ahead pass; asked before the group is touched)
+  if (!g->event_weights.empty()) return SXMC_OK;   // (nor a weighted one)
   g->plan_cfg.box = 0;   // (the pass runs over the ordered form; the question could be asked of g->ordered and leave the setting alone)
   int rc = group_refresh(g);
   if (rc) return rc;

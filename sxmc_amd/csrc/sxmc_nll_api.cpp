@@ -58,6 +58,20 @@ int sxmc_launch_nll_event_chunks(int grid, int block, sxmc_stream_t s, const flo
   return SXMC_OK;
 }
 
+int sxmc_launch_nll_event_chunks_weighted(int grid, int block, sxmc_stream_t s, const float* d_lut, const double* d_pars,
+                                          size_t ne, size_t ns, const double* d_nexpected, const unsigned* d_n_mc,
+                                          const short* d_source_id, const unsigned* d_norms, double* d_sums,
+                                          const double* d_weights) {
+  SX_FLUSH();
+  SX_ORDER(s);
+  if (int rc = check_launch(grid, block)) return rc;
+  SX_REQUIRE(ns <= 4096, "too many signals");
+  SX_REQUIRE(d_weights || ne == 0, "nll_event_chunks_weighted: null weights");
+  SX_HIP(sx_nll_event_chunks_weighted(grid, block, (hipStream_t)s, d_lut, d_pars, ne, ns, d_nexpected, d_n_mc,
+                                      d_source_id, d_norms, d_sums, d_weights));
+  return SXMC_OK;
+}
+
 int sxmc_launch_nll_event_reduce(int grid, int block, sxmc_stream_t s, size_t nthreads, const double* d_sums,
                                  double* d_total_sum) {
   SX_FLUSH();

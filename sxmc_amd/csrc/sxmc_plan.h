@@ -443,6 +443,35 @@ inline void event_classes(const std::vector<const std::vector<int>*>& arr, size_
     for (size_t k = 0; k < o.K; k++) o.tables[j * o.K + k] = (*arr[j])[o.first[k]];
 }
 
+// Real event weights over the classes above: W[k] = the sum of w[i] over the events i of class k, in ASCENDING EVENT
+// INDEX, in double, added one by one from 0.0 -- the order is the law (tests/weighted_events_reference.py), not
+// event_classes' sort, which is not stable.  All weights 1.0 give W[k] == (double)weight[k] exactly; integer weights give
+// the multiplicities of the data set with event i repeated w[i] times.  `arr`, `E`: what `cls` was built from.
+inline void class_weights(const std::vector<const std::vector<int>*>& arr, size_t E, const EventClasses& cls,
+                          const double* w, std::vector<double>& W) {
+  W.assign(cls.K, 0.0);
+  // (the classes are in the sort's order of their keys: an event finds its own by bisection over their first events)
+  auto less = [&](unsigned a, unsigned b) {
+    for (const std::vector<int>* t : arr) {
+      const int x = (*t)[a], y = (*t)[b];
+      if (x != y) return x < y;
+    }
+    return false;
+  };
+  for (size_t i = 0; i < E; i++) {
+    const size_t k = (size_t)(std::lower_bound(cls.first.begin(), cls.first.end(), (unsigned)i, less) - cls.first.begin());
+    W[k] = W[k] + w[i];
+  }
+}
+
+// The first event weight that is not a finite double >= 0, or -1: sxmc_group_set_event_weights refuses by this index.
+inline long long first_bad_event_weight(const double* w, size_t n) {
+  for (size_t i = 0; i < n; i++) {
+    if (!(w[i] >= 0.0) || w[i] > 1.7976931348623157e308) return (long long)i;
+  }
+  return -1;
+}
+
 // ---------------------------------------------------------------------------------------------- mixed columns
 // sxmc_group_set_columns: the walk's columns in signal order, member_of_signal[j] >= 0 a member of the group, -1 a dense
 // column somebody else writes.  Valid: nothing below -1 or beyond the last member, every member exactly once.  Returns

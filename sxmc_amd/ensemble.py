@@ -148,6 +148,45 @@ def make_fake_dataset(rng, workload, evaluators, poisson=True):
     return np.concatenate(rows, axis=0).astype(np.float32), observed
 
 
+def make_asimov_dataset(workload, evaluators):
+    """The ASIMOV data set of the fit: one data set in which every bin holds its EXPECTED, non-integer content, as
+    weighted events (MCMC.walk(event_weights=...); one fit of it gives the median sensitivity).  Per histogram signal j,
+    evaluated at the nominal parameters exactly as get_efficiency does: nexp_j = nexpected_j * eff_j, and for every
+    non-empty bin b in flat index order (last observable fastest) one row at the bin's centre -- rounded with
+    sample_float so that SetEvalPoints looks it up into b -- of weight nexp_j * c_b / sum(c), in double, left to right.
+    Returns (rows in make_fake_dataset's layout, float64 weights, [nexp_j]).  Same rule as sxmc::make_asimov_dataset
+    (fake_data.h).  Kernel-density signals have no Asimov rule here: refused by name."""
+    w = workload
+    if w.nobs > 3:
+        raise ValueError("Cannot sample histograms of more than 3 dimensions")   # pdfz.cpp:499-501
+    syst_means = w.parameter_means()[w.nsources:]
+    nbins = np.asarray(w.nbins, np.int64)
+    lower, upper = np.asarray(w.lower, np.float64), np.asarray(w.upper, np.float64)
+    width = (upper - lower) / nbins
+    scale = nbins / (upper - lower)                      # the look-up's (pdfz.cpp:366-368)
+    rows, weights, nexp = [], [], []
+    for j, (sig, ev) in enumerate(zip(w.signals, evaluators)):
+        if isinstance(ev, pdfz.EvalKernel):
+            raise ValueError("make_asimov_dataset: signal %d is a kernel-density signal: the Asimov data set is built "
+                             "from histogram signals only" % j)
+        eff, bins, _ = get_efficiency(ev, w.nsyst_pars, syst_means, sig.n_mc, want_bins=True)
+        ne = float(sig.nexpected) * eff
+        nexp.append(ne)
+        bins = np.asarray(bins).reshape(-1)
+        total = float(int(bins.sum(dtype=np.uint64)))
+        flat = np.nonzero(bins)[0]
+        if flat.size == 0:
+            continue
+        idx = np.stack(np.unravel_index(flat, nbins), axis=1)
+        centre = lower + (idx + 0.5) * width
+        pts = [sample_float(centre[:, k], idx[:, k], lower[k], upper[k], scale[k]) for k in range(w.nobs)]
+        rows.append(np.stack(pts + [np.full(flat.size, np.float32(sig.dataset))], axis=1).astype(np.float32))
+        weights.append(ne * bins[flat].astype(np.float64) / total)
+    if not rows:
+        return np.zeros((0, w.nobs + 1), np.float32), np.zeros(0, np.float64), nexp
+    return np.concatenate(rows, axis=0), np.concatenate(weights), nexp
+
+
 # ------------------------------------------------------------------------------------ intervals
 def chisquare_quantile_1dof(cl):
     """TMath::ChisquareQuantile(cl, 1) = (Phi^-1((1 + cl) / 2))^2, by bisection on erf."""
@@ -354,12 +393,15 @@ def projection_interval(values, cl=0.9, nbins=100):
 
 # ------------------------------------------------------------------------------------ the ensemble
 def run_experiment(workload, seed, nsteps, burnin_fraction=0.1, cl=0.9, sync_interval=10000, mcmc=None,
-                   form="fused", graph_steps=0, lookahead=False, proposal="diagonal", proposal_shrinkage=0.05):
+                   form="fused", graph_steps=0, lookahead=False, proposal="diagonal", proposal_shrinkage=0.05,
+                   data=None, event_weights=None):
     """One iteration of the loop in sxmc.cpp:59-145: fake data -> MCMC -> intervals.
     Reuses `mcmc` (evaluators with the MC tables resident in HBM) across experiments when given.
     lookahead: walk with two evaluations per pass over the tables (MCMC.walk(lookahead=True): the same chain, about a
     quarter more steps per second when one experiment has the GPU to itself; `mcmc` then needs a created stream).
     proposal, proposal_shrinkage: MCMC.walk's ("covariance": the correlated proposal; it walks sequentially).
+    data, event_weights: fit this data set (with these event weights: MCMC.walk's) instead of a fake one -- the Asimov
+    data set of make_asimov_dataset, for instance.
     Returns (intervals float32 [P, 4], chain, accepted)."""
     rng = np.random.default_rng(seed)
     if mcmc is None:
@@ -367,15 +409,18 @@ def run_experiment(workload, seed, nsteps, burnin_fraction=0.1, cl=0.9, sync_int
                     lut_output=False, consume=True)
     else:
         mcmc.reseed(seed & 0xFFFFFFFF)
-    data, _ = make_fake_dataset(rng, workload, mcmc.pdfs, poisson=True)
+    if data is None:
+        if event_weights is not None:
+            raise ValueError("run_experiment: event_weights without the data they belong to")
+        data, _ = make_fake_dataset(rng, workload, mcmc.pdfs, poisson=True)
     chain, accepted = mcmc.walk(data, nsteps, burnin_fraction, sync_interval=sync_interval, graph_steps=graph_steps,
                                 lookahead=lookahead and mcmc.stream is not None and mcmc.consume, proposal=proposal,
-                                proposal_shrinkage=proposal_shrinkage)
+                                proposal_shrinkage=proposal_shrinkage, event_weights=event_weights)
     return contour_intervals(chain, cl), chain, accepted
 
 
 def run_experiments_in_lockstep(workload, seeds, nsteps, sets, burnin_fraction=0.1, cl=0.9, sync_interval=10000,
-                                graph_steps=0, timing=None, proposal="diagonal"):
+                                graph_steps=0, timing=None, proposal="diagonal", event_weights=None):
     """len(seeds) fake experiments at once on one GPU, the chains grouped into lockstep sets (mcmc.LockstepChains:
     the chains of a set share a stream and ONE fill pass per step; different sets run on different streams, so one
     set's step ends overlap another's fill).  Same schedule of re-tunings and flushes as a single walk; every
@@ -384,6 +429,9 @@ def run_experiments_in_lockstep(workload, seeds, nsteps, sets, burnin_fraction=0
     chain's set-up (fake data, evaluation points, first evaluation) to the last flush, re-tunings and flushes
     included -- which is what an experiment of BASELINE's 1e5 steps consists of."""
     import time
+    if event_weights is not None:
+        raise ValueError("lockstep sets have no weighted step end: weighted events (an Asimov data set) are fitted one "
+                         "experiment per chain (run_experiment)")
     if proposal != "diagonal":
         raise ValueError("lockstep sets have no correlated step end: proposal %r walks one experiment per chain "
                          "(run_experiment, run_experiments_concurrently)" % (proposal,))

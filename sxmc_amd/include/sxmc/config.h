@@ -682,6 +682,8 @@ struct FitConfig {
   std::string samples;   //!< fit.samples: a saved chain to take the intervals from INSTEAD of walking (sxmc.cpp:84-94)
   std::string proposal = "diagonal";   //!< fit.proposal: "diagonal" (the reference's) or "covariance" (mcmc.h: Proposal)
   double proposal_shrinkage = 0.05;    //!< fit.proposal_shrinkage in (0, 1]: only with "covariance"
+  bool asimov = false;                 //!< fit.asimov: fit exactly one data set, the Asimov one (fake_data.h:
+                                       //!< make_asimov_dataset); refused together with configured data sets
   std::vector<Observable> observables, cuts;
   std::vector<Systematic> systematics;            //!< union over the signals, parameters numbered in that order
   std::vector<Source> sources;
@@ -862,6 +864,15 @@ inline void fit_proposal_from_json(FitConfig& fc, const json::Value& fit) {
   if (!(v > 0 && v <= 1)) throw ConfigError("fit: \"proposal_shrinkage\" must be a number in (0, 1]");
   fc.proposal_shrinkage = v;
 }
+/** The fit's "asimov" (a boolean; absent: false): fit exactly one data set, the Asimov one (make_asimov_dataset).
+ *  Refused together with configured data sets.  A configuration without the key loads as before.  Same rules and
+ *  messages as sxmc_amd.io.fit_asimov. */
+inline void fit_asimov_from_json(FitConfig& fc, const json::Value& fit, bool has_data) {
+  fc.asimov = fit.isMember("asimov") ? fit["asimov"].asBool("asimov") : false;
+  if (fc.asimov && has_data) {
+    throw ConfigError("fit: \"asimov\" fits the expected data set: it cannot be combined with configured data sets");
+  }
+}
 }  // namespace detail
 
 inline FitConfig parse_config(const std::string& text, const std::string& base_dir, bool load_tables = true) {
@@ -998,6 +1009,11 @@ inline FitConfig parse_config(const std::string& text, const std::string& base_d
 
   // data sets, clipped to the PDF boundaries: observables act as cuts (config.cpp:260-296)
   const json::Value& data_params = root["data"];
+  {
+    bool has_data = false;
+    for (const auto& kv : data_params.members) has_data = has_data || !kv.second.items.empty();
+    detail::fit_asimov_from_json(fc, fit, has_data);
+  }
   for (const auto& kv : data_params.members) {
     const unsigned dataset = (unsigned)std::strtoul(kv.first.c_str(), nullptr, 10);
     std::vector<Observable> cc = fc.observables;

@@ -7,6 +7,7 @@
 #pragma once
 
 #include <chrono>
+#include <cstdio>
 #include <exception>
 #include <functional>
 #include <memory>
@@ -98,6 +99,10 @@ struct ExperimentOptions {
   SetupLock* device_exclusive = nullptr;
   Proposal proposal = Proposal::DIAGONAL;   //!< MCMC::proposal of every chain the runner builds (fit.proposal);
   double proposal_shrinkage = 0.05;         //!< ensemble_lockstep refuses COVARIANCE: its sets have no such step end
+  bool asimov = false;   //!< fit.asimov: fit exactly ONE data set, the Asimov one (make_asimov_dataset: weighted events) --
+                         //!< ensemble and ensemble_concurrent then run the first of `experiments` alone and say so through
+                         //!< the report; ensemble_lockstep and ensemble_multi_gpu refuse it (no weighted lockstep step
+                         //!< end; one fit needs one card)
 };
 
 /** Where an experiment runs when it is one of several in flight: all "none" for the one-at-a-time loop. */
@@ -135,10 +140,12 @@ struct Meeting {
       meet->arrive_and_wait(lanes);
     };
   }
-  Chain walk(MCMC& mcmc, std::vector<float>& data, unsigned nsteps, float burnin_fraction, unsigned sync_interval) {
+  Chain walk(MCMC& mcmc, std::vector<float>& data, unsigned nsteps, float burnin_fraction, unsigned sync_interval,
+             const std::vector<double>* event_weights = nullptr) {
     Chain chain;
     try {
-      chain = mcmc(data, nsteps, burnin_fraction, false, sync_interval);
+      chain = event_weights ? mcmc(data, *event_weights, nsteps, burnin_fraction, false, sync_interval)
+                            : mcmc(data, nsteps, burnin_fraction, false, sync_interval);
     } catch (...) {
       if (meet) meet->break_all();
       throw;
@@ -213,7 +220,26 @@ inline ExperimentResult run_experiment(unsigned k, unsigned long long base_seed,
   ExperimentResult r;
   r.index = k;
   PhaseClock::time_point t = PhaseClock::now();
-  std::vector<float> data = detail::experiment_data(k, rng, signals, systematics, observables);
+  std::vector<float> data;
+  std::vector<double> weights;
+  if (opt.asimov) {
+    if (lane.lockstep) {
+      throw pdfz::Error("run_experiment: a lockstep set has no weighted step end: fit the Asimov data set in a chain of its own");
+    }
+    AsimovDataset a = make_asimov_dataset(signals, systematics, observables);
+    data = std::move(a.events);
+    weights = std::move(a.weights);
+    if (report_sink()) {
+      double total = 0;
+      for (double w : weights) total += w;
+      char line[160];
+      std::snprintf(line, sizeof line, "Fitting the Asimov data set: %zu weighted rows, %.17g expected events\n",
+                    weights.size(), total);
+      report_sink()(k, line);
+    }
+  } else {
+    data = detail::experiment_data(k, rng, signals, systematics, observables);
+  }
   r.nevents = data.size() / (observables.size() + 1);
   r.phases.data = since(t);
   t = PhaseClock::now();
@@ -223,7 +249,7 @@ inline ExperimentResult run_experiment(unsigned k, unsigned long long base_seed,
   r.phases.construct = since(t);
   if (lane.exclusive) lock.unlock();   // the walk takes it itself
   t = PhaseClock::now();
-  const Chain chain = meeting.walk(*mcmc, data, nsteps, burnin_fraction, opt.sync_interval);
+  const Chain chain = meeting.walk(*mcmc, data, nsteps, burnin_fraction, opt.sync_interval, opt.asimov ? &weights : nullptr);
   r.phases.walk_setup = chain.setup_seconds;
   r.phases.steps = chain.steps_seconds;
   r.phases.walk_teardown = since(t) - chain.setup_seconds - chain.steps_seconds;
@@ -247,6 +273,7 @@ inline std::vector<ExperimentResult> ensemble(const std::vector<unsigned>& exper
   std::vector<ExperimentResult> out;
   for (unsigned k : experiments) {
     out.push_back(run_experiment(k, base_seed, sources, signals, systematics, observables, nsteps, burnin_fraction, opt));
+    if (opt.asimov) break;   // (exactly one data set, the expected one: every further experiment would fit it again)
   }
   return out;
 }
@@ -338,6 +365,9 @@ inline std::vector<ExperimentResult> ensemble_concurrent(const std::vector<unsig
                                                          std::vector<Observable>& observables, unsigned nsteps,
                                                          float burnin_fraction, unsigned nconcurrent,
                                                          const ExperimentOptions& opt) {
+  if (opt.asimov) {   // (one fit: nothing to run beside it)
+    return ensemble(experiments, base_seed, sources, signals, systematics, observables, nsteps, burnin_fraction, opt);
+  }
   PoolScope pool;   // the experiments' arrays recycle their blocks instead of allocating and freeing (device_array.h)
   const size_t lanes = std::max<size_t>(1, std::min<size_t>(nconcurrent, experiments.size()));
   std::vector<ExperimentResult> out(experiments.size());
@@ -395,6 +425,9 @@ inline std::vector<ExperimentResult> ensemble_lockstep(const std::vector<unsigne
   if (opt.proposal == Proposal::COVARIANCE) {
     throw pdfz::Error("ensemble_lockstep: a lockstep set has no correlated step end: run a COVARIANCE ensemble one "
                       "experiment per chain (ensemble, ensemble_concurrent)");
+  }
+  if (opt.asimov) {
+    throw pdfz::Error("ensemble_lockstep: a lockstep set has no weighted step end: fit the Asimov data set with ensemble");
   }
   PoolScope pool;   // the experiments' arrays recycle their blocks instead of allocating and freeing (device_array.h)
   const size_t L = std::max(2u, std::min(4u, chains_per_set)), S = std::max(1u, nsets), lanes = L * S;

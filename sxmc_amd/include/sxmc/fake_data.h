@@ -106,4 +106,57 @@ inline std::vector<float> make_fake_dataset(std::mt19937_64& rng, std::vector<Si
   return events;
 }
 
+/** The ASIMOV data set of a fit: one data set in which every bin holds its EXPECTED, non-integer content, as weighted
+ *  events (sxmc::MCMC's operator() with event weights; one fit of it gives the median sensitivity). */
+struct AsimovDataset {
+  std::vector<float> events;       //!< rows in make_fake_dataset's layout: the observables, then the dataset id
+  std::vector<double> weights;     //!< one per row
+  std::vector<double> nexpected;   //!< per signal: nexpected_j * eff_j, what its rows' weights sum to
+};
+
+/** Per histogram signal j, evaluated at the nominal parameters exactly as get_efficiency does: nexp_j = nexpected_j *
+ *  eff_j, and for every non-empty bin b in flat index order (last observable fastest) one row at the bin's centre --
+ *  rounded with sample_float so that SetEvalPoints looks it up into b -- of weight nexp_j * c_b / sum(c), in double, left
+ *  to right.  observables must be in field order.  Same rule as sxmc_amd.ensemble.make_asimov_dataset.  Kernel-density
+ *  signals have no Asimov rule here: refused by name. */
+inline AsimovDataset make_asimov_dataset(std::vector<Signal>& signals, std::vector<Systematic>& systematics,
+                                         std::vector<Observable>& observables) {
+  AsimovDataset out;
+  const size_t D = observables.size();
+  if (D > 3) throw pdfz::Error("Cannot EvalHist::CreateHistogram for dimensions greater than 3!");
+  for (size_t j = 0; j < signals.size(); j++) {
+    Signal& s = signals[j];
+    pdfz::EvalHist* h = dynamic_cast<pdfz::EvalHist*>(s.histogram);
+    if (!h) {
+      throw pdfz::Error("make_asimov_dataset: signal " + std::to_string(j) +
+                        " is a kernel-density signal: the Asimov data set is built from histogram signals only");
+    }
+    const double eff = get_efficiency(s, systematics);
+    const double ne = s.nexpected * eff;
+    out.nexpected.push_back(ne);
+    const std::vector<unsigned> bins = h->GetBins();
+    unsigned long long sum = 0;
+    for (unsigned c : bins) sum += c;
+    const double total = (double)sum;
+    for (size_t b = 0; b < bins.size(); b++) {
+      if (!bins[b]) continue;
+      size_t flat = b;
+      std::vector<size_t> idx(D);
+      for (size_t k = D; k-- > 0;) {
+        idx[k] = flat % observables[k].bins;
+        flat /= observables[k].bins;
+      }
+      for (size_t k = 0; k < D; k++) {
+        const double lower = (double)observables[k].lower, upper = (double)observables[k].upper;
+        const double width = (upper - lower) / (double)observables[k].bins;
+        const double scale = (int)observables[k].bins / (upper - lower);   // the look-up's (pdfz.cpp:366-368)
+        out.events.push_back(sample_float(lower + ((double)idx[k] + 0.5) * width, idx[k], lower, upper, scale));
+      }
+      out.events.push_back((float)h->Dataset());
+      out.weights.push_back(ne * (double)bins[b] / total);
+    }
+  }
+  return out;
+}
+
 }  // namespace sxmc

@@ -28,6 +28,7 @@
 // before the arrays die.  Handles are owned (Owned<>); record_graph is the one recorder of launches into a graph.
 #pragma once
 
+#include <limits>
 #include <algorithm>
 #include <atomic>
 #include <chrono>
@@ -472,8 +473,24 @@ class MCMC {
    *  Set up, choose the form of the steps, walk run by run, tear down: the parts are the members of Walk below. */
   Chain operator()(std::vector<float>& data, unsigned nsteps, float burnin_fraction,
                    const bool debug_mode = false, unsigned sync_interval = 10000) {
+    return walk(data, nullptr, nsteps, burnin_fraction, debug_mode, sync_interval);
+  }
+  /** The same over WEIGHTED data events: event_weights[i], a finite double >= 0, is row i's weight in the likelihood's
+   *  event term, sum_i w_i log(s_i) (include/sxmc_hip.h, sxmc_group_set_event_weights: the law).  Every sequential form
+   *  takes them -- reference_form and the MIXED form through sxmc_launch_nll_event_chunks_weighted over the whole table,
+   *  the batched and consuming forms through the group; asked with lookahead the walk goes sequentially.  Refused, with
+   *  pdfz::Error: a weight that is not finite and >= 0, a count that is not the data's, columns_in_place, a chain of a
+   *  lockstep set. */
+  Chain operator()(std::vector<float>& data, const std::vector<double>& event_weights, unsigned nsteps,
+                   float burnin_fraction, const bool debug_mode = false, unsigned sync_interval = 10000) {
+    return walk(data, &event_weights, nsteps, burnin_fraction, debug_mode, sync_interval);
+  }
+
+ protected:
+  Chain walk(std::vector<float>& data, const std::vector<double>* event_weights, unsigned nsteps, float burnin_fraction,
+             const bool debug_mode, unsigned sync_interval) {
     const std::chrono::steady_clock::time_point walk_t0 = std::chrono::steady_clock::now();
-    Walk w(*this, data, nsteps, burnin_fraction, debug_mode, sync_interval);
+    Walk w(*this, data, event_weights, nsteps, burnin_fraction, debug_mode, sync_interval);
     w.set_up();
     w.choose_form();
     const std::chrono::steady_clock::time_point steps_t0 = std::chrono::steady_clock::now();
@@ -482,6 +499,7 @@ class MCMC {
     return w.finish(steps_t0);
   }
 
+ public:
   size_t NumParameters() const { return nparameters; }
   /** The factor the last walk ended with, P x P doubles with L_ij at [j * P + i] (empty after a DIAGONAL walk), and
    *  the shrinkage it was built with (doubled where a pivot failed: sxmc_proposal_factor). */
@@ -506,12 +524,25 @@ class MCMC {
   }
 
  protected:
+  /** nll_event_chunks over the whole table in the reference's launch shape; weights (device, one per event): the
+   *  weighted launch point. */
+  void event_chunks(sxmc_stream_t s, const float* lut, size_t nevents, const double* v, const double* d_nexpected,
+                    const unsigned* d_n_mc, const short* d_source_id, const unsigned* norms, double* sums,
+                    const double* weights) {
+    if (weights) {
+      SXMC_KERNEL_LAUNCH(nll_event_chunks_weighted, nnllblocks, nllblocksize, 0, s, lut, v, nevents, nsignals,
+                         d_nexpected, d_n_mc, d_source_id, norms, sums, weights);
+    } else {
+      SXMC_KERNEL_LAUNCH(nll_event_chunks, nnllblocks, nllblocksize, 0, s, lut, v, nevents, nsignals, d_nexpected, d_n_mc,
+                         d_source_id, norms, sums);
+    }
+  }
+
   /** MCMC::nll (mcmc.cpp:390-415): three launches over an evaluated lookup table. */
   void nll(const float* lut, size_t nevents, const double* v, double* out, const unsigned* norms,
-           double* event_partial_sums, double* event_total_sum) {
-    SXMC_KERNEL_LAUNCH(nll_event_chunks, nnllblocks, nllblocksize, 0, stream, lut, v, nevents, nsignals,
-                       nexpected->readOnlyPtr(), n_mc->readOnlyPtr(), source_id->readOnlyPtr(), norms,
-                       event_partial_sums);
+           double* event_partial_sums, double* event_total_sum, const double* weights = nullptr) {
+    event_chunks(stream, lut, nevents, v, nexpected->readOnlyPtr(), n_mc->readOnlyPtr(), source_id->readOnlyPtr(), norms,
+                 event_partial_sums, weights);
     SXMC_KERNEL_LAUNCH(nll_event_reduce, 1, nreducethreads, nreducethreads * sizeof(double), stream,
                        (size_t)nnllthreads, event_partial_sums, event_total_sum);
     SXMC_KERNEL_LAUNCH(nll_total, 1, 1, 0, stream, nparameters, v, nsignals, nsources,
@@ -588,6 +619,8 @@ class MCMC {
     pdfz::Array<float> jump_buffer;
     pdfz::Array<double> current_nll, proposed_nll;
     pdfz::Array<float> jump_width, lut;
+    const std::vector<double>* const event_weights;   // the data's weights, one per event, or null
+    std::unique_ptr<pdfz::Array<double>> weights;     // ... on the device, for the weighted launch point
     const bool covariance;            // the walk's proposal is the correlated one
     std::unique_ptr<pdfz::Array<double>> factor;   // its factor, P x P: one device array for the walk's lifetime (none otherwise)
     std::unique_ptr<Shadow> shadow;   // look-ahead walk only
@@ -597,12 +630,13 @@ class MCMC {
     WalkForm form{};
     StepArgs d;
     const double* d_factor = nullptr; // the factor on the device, or null: resolved with d
+    const double* d_weights = nullptr; // the event weights on the device, or null: resolved with d
     bool two_forms = false;           // the plan holds a boxed and an ordered form of the fill (asked at every run)
     bool setup_announced = false;     // on_setup_done has been called
     bool torn_down = false;
 
-    Walk(MCMC& m_, std::vector<float>& data_, unsigned nsteps, float burnin_fraction, bool debug_mode_,
-         unsigned sync_interval)
+    Walk(MCMC& m_, std::vector<float>& data_, const std::vector<double>* event_weights_, unsigned nsteps,
+         float burnin_fraction, bool debug_mode_, unsigned sync_interval)
         : m(m_),
           excl(m_.exclusive ? std::unique_lock<SetupLock>(*m_.exclusive) : std::unique_lock<SetupLock>()),
           transfer_guard(m_.stream),
@@ -624,6 +658,7 @@ class MCMC {
           proposed_nll(1, true),
           jump_width(m_.nparameters, true),
           lut(nevents * m_.nsignals, true),
+          event_weights(event_weights_),
           covariance(m_.proposal == Proposal::COVARIANCE),
           factor(covariance ? new pdfz::Array<double>(m_.nparameters * m_.nparameters, true) : nullptr),
           strm(m_.stream) {
@@ -659,6 +694,27 @@ class MCMC {
         if (m.lockstep) throw pdfz::Error("MCMC: a lockstep set has no correlated step end: walk a COVARIANCE chain alone");
         rebuild_factor(nullptr, 0);   // (L = diag(w), through the re-tuning's own code)
       }
+      if (event_weights) {
+        if (event_weights->size() != nevents) {
+          throw pdfz::Error("MCMC: " + std::to_string(event_weights->size()) + " event weights for " +
+                            std::to_string(nevents) + " events");
+        }
+        for (size_t i = 0; i < nevents; i++) {   // (the group checks its copy too; a walk without a group has only this)
+          const double w = (*event_weights)[i];
+          if (!(w >= 0.0) || w > std::numeric_limits<double>::max()) {
+            throw pdfz::Error("MCMC: event weight " + std::to_string(i) + " is not a finite number >= 0");
+          }
+        }
+        if (m.lockstep) throw pdfz::Error("MCMC: a lockstep set has no weighted step end: walk a chain over weighted events alone");
+
+        if (m.columns_in_place) {
+          throw pdfz::Error("MCMC: columns_in_place has no weighted event sum: walk weighted events with the table materialised");
+        }
+        weights.reset(new pdfz::Array<double>(std::max<size_t>(nevents, 1), true));
+        for (size_t i = 0; i < nevents; i++) weights->writeOnlyHostPtr()[i] = (*event_weights)[i];
+      }
+      // (the group keeps a copy for its own event sums: this walk's, or none -- refuses what is not finite and >= 0)
+      if (m.group) check(sxmc_group_set_event_weights(m.group, event_weights ? event_weights->data() : nullptr, event_weights ? nevents : 0));
 
       // mcmc.cpp:230-242: bind, first evaluation at the current vector, then re-point at the proposal
       for (size_t i = 0; i < m.pdfs.size(); i++) {
@@ -672,7 +728,8 @@ class MCMC {
         p->SetParameterBuffer(&proposed_vector, (int)m.nsources);
       }
       m.nll(lut.readOnlyPtr(), nevents, current_vector.readOnlyPtr(), current_nll.writeOnlyPtr(),
-            normalizations.readOnlyPtr(), event_partial_sums.ptr(), event_total_sum.ptr());
+            normalizations.readOnlyPtr(), event_partial_sums.ptr(), event_total_sum.ptr(),
+            weights ? weights->readOnlyPtr() : nullptr);
       SXMC_KERNEL_LAUNCH(pick_new_vector, 1, 64, 0, m.stream, (int)m.nparameters, m.rngs->ptr(),
                          jump_width.readOnlyPtr(), current_vector.readOnlyPtr(), proposed_vector.writeOnlyPtr());
     }
@@ -680,7 +737,7 @@ class MCMC {
     /** The form of the steps (walk_plan.h: choose_form), narrowed by what the device says about the look-ahead pass;
      *  then what the form needs: the group bound and tuned, the shadow set, a stream to record on.  Lock: held. */
     void choose_form() {
-      form = sxmc::choose_form(covariance, WalkFlags{m.group != nullptr, m.reference_form,
+      form = sxmc::choose_form(covariance, event_weights != nullptr, WalkFlags{m.group != nullptr, m.reference_form,
                                          m.nsystematics > 0 && !m.systematics_fixed, m.consume, m.lut_output,
                                          m.lockstep != nullptr, m.lookahead || m.lookahead_auto, m.nparameters,
                                          m.graph_steps, !m.kernels.empty()});
@@ -787,6 +844,7 @@ class MCMC {
       // the factor like the widths: uploaded here, after a re-tuning wrote it, never under a recording; the address is
       // the same for the whole walk, so recorded steps survive a re-tuning
       d_factor = covariance ? factor->readOnlyPtr() : nullptr;
+      d_weights = weights ? weights->readOnlyPtr() : nullptr;
       if (m.group) check(sxmc_group_set_proposal_factor(m.group, d_factor));
     }
 
@@ -819,8 +877,8 @@ class MCMC {
           for (pdfz::Eval* p : m.pdfs) p->EvalAsync();
           for (pdfz::Eval* p : m.pdfs) p->EvalFinished();
         }
-        SXMC_KERNEL_LAUNCH(nll_event_chunks, m.nnllblocks, m.nllblocksize, 0, strm, d.lut, a.d_v_proposed, nevents,
-                           m.nsignals, a.d_nexpected, a.d_n_mc, a.d_source_id, a.d_norms, d.sums);
+        m.event_chunks(strm, d.lut, nevents, a.d_v_proposed, a.d_nexpected, a.d_n_mc, a.d_source_id, a.d_norms, d.sums,
+                       d_weights);
       }
       SXMC_KERNEL_LAUNCH(finish_nll_jump_pick_combo, 1, m.nreducethreads, m.nreducethreads * sizeof(double), strm,
                          (size_t)npartial, d.sums, m.nsignals, m.nsources, a.d_means, a.d_sigmas, a.d_rng,
@@ -854,8 +912,8 @@ class MCMC {
         }
       }
       if (!summed) {
-        SXMC_KERNEL_LAUNCH(nll_event_chunks, m.nnllblocks, m.nllblocksize, 0, strm, d.lut, a.d_v_proposed, nevents,
-                           m.nsignals, a.d_nexpected, a.d_n_mc, a.d_source_id, a.d_norms, d.sums);
+        m.event_chunks(strm, d.lut, nevents, a.d_v_proposed, a.d_nexpected, a.d_n_mc, a.d_source_id, a.d_norms, d.sums,
+                       d_weights);
       }
       if (m.group && form.reevaluate && m.consume) {
         check(sxmc_group_finish_columns_step_async(m.group, strm, (size_t)m.nnllthreads, d.sums, a.d_means, a.d_sigmas,

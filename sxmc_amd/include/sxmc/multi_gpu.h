@@ -317,6 +317,9 @@ inline MultiGpuEnsemble ensemble_multi_gpu(const std::vector<int>& devices, unsi
   PoolScope pool;   // (see ensemble(): blocks are pooled per device)
   const size_t G = devices.size();
   if (G == 0 || tables.size() != signals.size()) throw pdfz::Error("ensemble_multi_gpu: bad arguments");
+  if (opt.asimov) {
+    throw pdfz::Error("ensemble_multi_gpu: the Asimov data set is ONE fit, and one fit needs one card: run it with ensemble");
+  }
   size_t P = sources.size();
   for (const Systematic& s : systematics) P += s.npars;
   MultiGpuEnsemble out;

@@ -48,6 +48,15 @@ inline void nll_event_chunks(int grid, int block, size_t, sxmc_stream_t stream, 
                                      sums));
 }
 
+/** nll_event_chunks with one weight per event: the term is weights[i] * log(s_i) (sxmc_group_set_event_weights: the law) */
+inline void nll_event_chunks_weighted(int grid, int block, size_t, sxmc_stream_t stream, const float* lut,
+                                      const double* pars, const size_t ne, const size_t ns, const double* nexpected,
+                                      const unsigned* n_mc, const short* source_id, const unsigned* norms, double* sums,
+                                      const double* weights) {
+  check(sxmc_launch_nll_event_chunks_weighted(grid, block, stream, lut, pars, ne, ns, nexpected, n_mc, source_id, norms,
+                                              sums, weights));
+}
+
 /** nll_event_reduce (nll_kernels.h:126-127) */
 inline void nll_event_reduce(int grid, int block, size_t, sxmc_stream_t stream, const size_t nthreads,
                              const double* sums, double* total_sum) {

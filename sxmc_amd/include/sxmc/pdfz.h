@@ -133,6 +133,9 @@ class Eval {
     throw Error("Project is not implemented by this evaluator");
   }
 
+  /** The data set the evaluator's points are looked up for (the constructor's `dataset`). */
+  unsigned Dataset() const { return dataset; }
+
  protected:
   int nfields;
   int nobservables;

@@ -85,6 +85,9 @@ struct WalkFlags {
                            //!< evaluator of this library; has_group then says whether there are histogram members
   bool covariance_proposal = false;   //!< the proposal is the correlated one: every sequential form takes it, the
                                      //!< look-ahead pass and lockstep sets have no such step end
+  bool event_weights = false;         //!< the data events carry real weights: every sequential form takes them (the
+                                     //!< reference form and the MIXED form through the weighted launch point, the batched
+                                     //!< forms through the group); never LOOKAHEAD or LOCKSTEP
 };
 /** The form of the walk's steps, from the flags alone.  LOOKAHEAD is a candidate: two questions to the device (does the
  *  plan stream codes, is the pass offered for this shape) may still narrow it to CONSUMING, see narrowed(). */
@@ -114,8 +117,8 @@ inline WalkForm choose_form(const WalkFlags& f) {
   WalkForm::Step step = WalkForm::REFERENCE;
   if (fused && !f.consume) step = WalkForm::BATCHED;
   if (fused && f.consume) {
-    // (a correlated proposal: asked with lookahead, or given a lockstep set, the walk goes sequentially)
-    step = f.covariance_proposal ? WalkForm::CONSUMING
+    // (a correlated proposal, weighted events: asked with lookahead, or given a lockstep set, the walk goes sequentially)
+    step = (f.covariance_proposal || f.event_weights) ? WalkForm::CONSUMING
            : f.in_lockstep_set   ? WalkForm::LOCKSTEP
            : (f.lookahead_asked && !f.lut_output && f.nparameters <= 256) ? WalkForm::LOOKAHEAD
                                                                            : WalkForm::CONSUMING;
@@ -129,6 +132,11 @@ inline WalkForm choose_form(const WalkFlags& f) {
 inline WalkForm choose_form(bool covariance_proposal, WalkFlags f) {
   f.covariance_proposal = covariance_proposal;
   return choose_form(f);
+}
+/** ... and whose data events carry weights (the data's, named beside the proposal). */
+inline WalkForm choose_form(bool covariance_proposal, bool event_weights, WalkFlags f) {
+  f.event_weights = event_weights;
+  return choose_form(covariance_proposal, f);
 }
 
 }  // namespace sxmc

@@ -248,6 +248,25 @@ def fit_proposal(fit):
     return proposal, v
 
 
+ASIMOV_WITH_DATA = 'fit: "asimov" fits the expected data set: it cannot be combined with configured data sets'
+
+
+def fit_asimov(fit, has_data):
+    """The fit's "asimov" (a boolean; absent: false): fit exactly one data set, the Asimov one
+    (ensemble.make_asimov_dataset).  Refused together with configured data sets.  A configuration without the key loads
+    as before.  Same rules and messages as sxmc::detail::fit_asimov_from_json (config.h)."""
+    v = fit.get("asimov", False)
+    if isinstance(v, bool):
+        asimov = v
+    elif isinstance(v, (int, float)):
+        asimov = v != 0
+    else:
+        raise ValueError("asimov: not a boolean")
+    if asimov and has_data:
+        raise ValueError(ASIMOV_WITH_DATA)
+    return asimov
+
+
 def load_config(path_or_text, base_dir=None):
     if os.path.exists(path_or_text):
         base_dir = base_dir or os.path.dirname(os.path.abspath(path_or_text))
@@ -352,6 +371,7 @@ def load_config(path_or_text, base_dir=None):
             bandwidth_cutoff=signal_cutoff(name, c, pdf)))
     fc.data = {int(k): [dict(filename=row["filename"], title=row.get("title", "")) for row in rows]
                for k, rows in root.get("data", {}).items()}
+    fc.asimov = fit_asimov(fit, any(len(rows) > 0 for rows in fc.data.values()))
     fc.base_dir = base_dir or "."
     return fc
 
@@ -472,6 +492,9 @@ def run_config(path, out_dir=None, nexperiments=None, nsteps=None, report=None, 
             report.write(ensemble.format_best_fit(names, iv, np.asarray(chain, np.float32)[:, -1].min(), fc.confidence, one_sided))
             report.write(ensemble.format_correlations(names, ensemble.correlation_matrix(chain)))
     fc = load_config(path)
+    if fc.asimov and spectra_dir:
+        raise ValueError('run_config: fit spectra of weighted events are not built: "asimov" cannot be combined with '
+                         "spectra_dir")
     if fc.samples:                                               # sxmc.cpp:84-94: no walk, the saved likelihood space
         chain, names = read_table(os.path.join(fc.base_dir, fc.samples))
         assert names and names[-1] == "likelihood" and chain.shape[0] > 0
@@ -488,17 +511,23 @@ def run_config(path, out_dir=None, nexperiments=None, nsteps=None, report=None, 
     from .mcmc import MCMC
     w = build_workload(fc)
     m = MCMC(w, seed=fc.seed & 0xFFFFFFFF, fused=True, lut_output=False, consume=True)
-    nexp = nexperiments or fc.nexperiments
+    nexp = 1 if fc.asimov else (nexperiments or fc.nexperiments)   # ("asimov": exactly one data set, the expected one)
     nsteps = nsteps or fc.nsteps
     allint, limits = [], []
     for i in range(nexp):
         rng = np.random.default_rng((fc.seed << 20) + i)
         events = load_data(fc, w, i)                             # sxmc.cpp:71-80: file i of every configured data set
-        if events is None:
+        weights = None
+        if fc.asimov:
+            events, weights, _ = ensemble.make_asimov_dataset(w, m.pdfs)
+            if report is not None:
+                report.write("Fitting the Asimov data set: %d weighted rows, %.17g expected events\n"
+                             % (events.shape[0], float(np.sum(weights))))
+        elif events is None:
             events, _ = ensemble.make_fake_dataset(rng, w, m.pdfs, poisson=True)
         m.reseed(((fc.seed << 20) + i) & 0xFFFFFFFF)
         chain, _ = m.walk(events, nsteps, fc.burnin_fraction, debug_mode=fc.debug_mode, proposal=fc.proposal,
-                          proposal_shrinkage=fc.proposal_shrinkage)
+                          proposal_shrinkage=fc.proposal_shrinkage, event_weights=weights)
         if fc.error_type == "projection":                       # likelihood.cpp:104-137: the chosen estimator
             cols = [ensemble.projection_interval(chain[:, p], fc.confidence) for p in range(chain.shape[1] - 1)]
             iv = np.array([c[:4] for c in cols], np.float32)

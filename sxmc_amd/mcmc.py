@@ -124,6 +124,7 @@ class MCMC:
         self.proposal_factor = None
         self._factor_buffer = None
         self.proposal_shrinkage_used = None
+        self.event_weights = None               # setup(event_weights=...): one double per event on the device, or None
 
     # mcmc.cpp:198-228 (keeps the reference's `i < nsignals` test at :217)
     def initial_jump_widths(self, fixed=None):
@@ -148,14 +149,26 @@ class MCMC:
             out[i] = np.float32(0.1 * width * scale_factor)
         return out
 
-    def setup(self, data=None, sync_interval=10000, jump_width=None):
+    def setup(self, data=None, sync_interval=10000, jump_width=None, event_weights=None):
         """mcmc.cpp:186, 230-256: bind buffers, first evaluation at the current vector, NLL of it,
-        first proposal."""
+        first proposal.  event_weights: one finite weight >= 0 per event (the event term becomes sum_i w_i log s_i:
+        include/sxmc_hip.h, sxmc_group_set_event_weights), or None."""
         w = self.w
         data = w.events if data is None else data
         data = np.ascontiguousarray(data, dtype=np.float32).reshape(-1)
         self._graph = None                      # recorded steps hold the old evaluation-point tables
         self.nevents = data.size // (w.nobs + 1)
+        if event_weights is None:
+            self.event_weights = None
+            self.group.SetEventWeights(None)
+        else:
+            ew = np.ascontiguousarray(event_weights, np.float64).reshape(-1)
+            if ew.size != self.nevents:
+                raise ValueError("event_weights holds %d weights for %d events" % (ew.size, self.nevents))
+            if self.fused == "dropin":
+                raise ValueError("event weights: the drop-in form has no weighted event sum; walk in another form")
+            self.group.SetEventWeights(ew)      # (refuses NaN, infinite and negative weights by index)
+            self.event_weights = DeviceArray(ew)
         self.sync_interval = sync_interval
         self._since_flush = 0                   # steps launched since the jump buffer was last read back
         self.jump_buffer = DeviceArray.zeros(sync_interval * (self.nparameters + 1), np.float32)
@@ -177,11 +190,20 @@ class MCMC:
         self._adapt_pending = True               # (a plan with two forms of the fill: chosen at the first step)
         self._two_forms_cached = None
 
-    def nll(self, v, out):
-        """MCMC::nll (mcmc.cpp:390-415): three launches over an already evaluated lut."""
+    def _event_chunks(self, v):
+        """nll_event_chunks over the lut at v, weighted where the walk has event weights."""
+        if self.event_weights is not None:
+            nll.nll_event_chunks_weighted(NLL_BLOCKS, NLL_BLOCK_SIZE, self.stream, self.lut, v, self.nevents,
+                                          self.nsignals, self.nexpected, self.n_mc, self.source_id,
+                                          self.normalizations, self.event_partial_sums, self.event_weights)
+            return
         nll.nll_event_chunks(NLL_BLOCKS, NLL_BLOCK_SIZE, self.stream, self.lut, v, self.nevents, self.nsignals,
                              self.nexpected, self.n_mc, self.source_id, self.normalizations,
                              self.event_partial_sums)
+
+    def nll(self, v, out):
+        """MCMC::nll (mcmc.cpp:390-415): three launches over an already evaluated lut."""
+        self._event_chunks(v)
         nll.nll_event_reduce(1, REDUCE_THREADS, self.stream, self.nnllthreads, self.event_partial_sums,
                              self.event_total_sum)
         nll.nll_total(1, 1, self.stream, self.nparameters, v, self.nsignals, self.nsources,
@@ -225,9 +247,7 @@ class MCMC:
                                                self.source_id, self.normalizations, self.event_partial_sums)
         else:
             self.group.EvalAsync(True, self.stream)
-            nll.nll_event_chunks(NLL_BLOCKS, NLL_BLOCK_SIZE, self.stream, self.lut, self.proposed_vector,
-                                 self.nevents, self.nsignals, self.nexpected, self.n_mc, self.source_id,
-                                 self.normalizations, self.event_partial_sums)
+            self._event_chunks(self.proposed_vector)
             npartial = self.nnllthreads
         if self.consume:
             self.group.FinishStepAsync(self.stream, npartial, self.event_partial_sums, self.parameter_means,
@@ -261,7 +281,7 @@ class MCMC:
         self.rngs = nll.make_rngs(self.nparameters, seed, self.stream)
 
     def walk(self, data, nsteps, burnin_fraction, debug_mode=False, sync_interval=10000, graph_steps=0,
-             lookahead=False, proposal="diagonal", proposal_shrinkage=0.05):
+             lookahead=False, proposal="diagonal", proposal_shrinkage=0.05, event_weights=None):
         """MCMC::operator() (mcmc.cpp:143-387): start at the means, walk nsteps, re-tune the proposal
         widths from the chain's spread at burnin_steps and 2 * burnin_steps (dropping the steps so far
         unless debug_mode).  Returns (chain [nkept, P + 1] float32, accepted).
@@ -270,8 +290,11 @@ class MCMC:
         proposal="covariance": v_proposed = v_current + L z with L a lower-triangular factor rebuilt at the two
         re-tunings from the kept rows' correlations, shrunk towards the identity by proposal_shrinkage (README,
         "Correlated proposals"; include/sxmc_hip.h, sxmc_proposal_factor); every parameter's marginal width stays the
-        reference's.  Such a walk is always sequential: asked with lookahead it walks step by step."""
-        self.walk_begin(data, nsteps, burnin_fraction, debug_mode, sync_interval, proposal, proposal_shrinkage)
+        reference's.  Such a walk is always sequential: asked with lookahead it walks step by step.
+        event_weights: one weight per event (see setup); such a walk is sequential too -- there is no weighted look-ahead
+        pass (Group.LookaheadSupported answers no)."""
+        self.walk_begin(data, nsteps, burnin_fraction, debug_mode, sync_interval, proposal, proposal_shrinkage,
+                        event_weights)
         self.lookahead_passes = 0
         # (a shape the look-ahead pass is not offered for -- see Group.LookaheadSupported -- walks sequentially)
         if lookahead and self.group.LookaheadSupported():
@@ -356,7 +379,7 @@ class MCMC:
     # The same walk cut into per-step pieces, so that several chains can be advanced in turn and have
     # their kernels in flight together (one stream per chain).
     def walk_begin(self, data, nsteps, burnin_fraction, debug_mode=False, sync_interval=10000, proposal="diagonal",
-                   proposal_shrinkage=0.05):
+                   proposal_shrinkage=0.05, event_weights=None):
         w = self.w
         if proposal not in ("diagonal", "covariance"):
             raise ValueError('proposal must be "diagonal" or "covariance", not %r' % (proposal,))
@@ -368,7 +391,7 @@ class MCMC:
         self.current_vector.set(w.parameter_means().astype(np.float64))
         self.jump_counter.set(np.zeros(1, np.int32))
         self.accept_counter.set(np.zeros(1, np.int32))
-        self.setup(data, sync_interval=sync_interval)
+        self.setup(data, sync_interval=sync_interval, event_weights=event_weights)
         # mcmc.cpp:199: nfloat = the parameters that are not fixed (a fixed one carries jump width <= 0)
         nfloat = max(1, int(np.count_nonzero(self.jump_width.get() > 0)))
         self._scale_factor = np.float32(2.4 * 2.4 / nfloat)
@@ -604,7 +627,10 @@ class LockstepChains:
 
     def step(self, debug_mode=False):
         if not self._recording:
-            for c in self.chains:
+            for k, c in enumerate(self.chains):
+                if c.event_weights is not None:
+                    raise ValueError("chain %d of the lockstep set has event weights: lockstep sets have no weighted "
+                                     "step end; step that chain on its own" % k)
                 c._launching(1)      # (every chain's jump buffer must hold the run)
         self.mg.StepAsync(self.stream, debug_mode)
 

@@ -38,6 +38,12 @@ def nll_event_chunks(grid, block, stream, lut, pars, ne, ns, nexpected, n_mc, so
               ptr(nexpected), ptr(n_mc), ptr(source_id), ptr(norms), ptr(sums))
 
 
+def nll_event_chunks_weighted(grid, block, stream, lut, pars, ne, ns, nexpected, n_mc, source_id, norms, sums, weights):
+    """nll_event_chunks with one weight per event (a DeviceArray of ne doubles): the term is weights[i] * log(s_i)."""
+    capi.call("sxmc_launch_nll_event_chunks_weighted", grid, block, ptr(stream), ptr(lut), ptr(pars), int(ne), int(ns),
+              ptr(nexpected), ptr(n_mc), ptr(source_id), ptr(norms), ptr(sums), ptr(weights))
+
+
 def proposal_factor(rows, new_widths, shrinkage=0.05):
     """The re-tuning of a correlated proposal (sxmc_proposal_factor, host arithmetic only): rows [nrows, P + 1] float32
     kept rows of the chain, new_widths [P] float32 the re-tuned widths (<= 0: fixed).  Returns (factor, shrinkage used):
@@ -189,6 +195,15 @@ class EvalGroup:
         keep it alive; its contents may be rewritten between steps), or None for the diagonal proposal
         (sxmc_group_set_proposal_factor)."""
         capi.call("sxmc_group_set_proposal_factor", self._g, ptr(factor))
+
+    def SetEventWeights(self, weights):
+        """One real weight per event (host array of doubles, finite and >= 0; copied), or None: every event counts once
+        (sxmc_group_set_event_weights: the law, and which entries refuse a weighted group)."""
+        if weights is None:
+            capi.call("sxmc_group_set_event_weights", self._g, ptr(None), 0)
+            return
+        w = np.ascontiguousarray(weights, np.float64).reshape(-1)
+        capi.call("sxmc_group_set_event_weights", self._g, ptr(w), int(w.size))
 
     def SetLutOutput(self, enable):
         """False: EvalNllAsync / McmcStepAsync do not write the lookup table and sum over the distinct tuples
