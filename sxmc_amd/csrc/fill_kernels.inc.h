@@ -2221,6 +2221,9 @@ __device__ __forceinline__ void fill_ordered_body(SxChainDescs chains, const SxS
 // in the padded form with THAT observable as the outermost dimension of the LDS copy whatever its place in the real
 // histogram (the flush translates: a word (idx, hi * s + lo) is bin hi * s * nbins + idx * s + lo).
 // Slots: 0 the streamed observable, 1 the truth field, 2 the boxed observable (geometry at index 1).
+//   The interval rule below and granule_meta's verdict are restated in tests/boxed_reference.py and held, on granules
+// whose box corners are rows a hair from a bin edge, by tests/test_boxed_model_cpu.py (with planted wrong variants) and
+// tests/test_gpu_boxed_threshold.py.
 template <unsigned OPC, int XT>
 __device__ __forceinline__ void apply_box_interval(double& xl, double& xh, double tl, double th, bool& fin, const double* c) {
   constexpr int type = (int)(OPC & 15u), E = (int)((OPC >> 8) & 15u);
@@ -2394,7 +2397,19 @@ __device__ __forceinline__ void fill_boxed_body(const SxSignalDesc* __restrict__
       const double epsq = 0.5 * sum_abs * (1.0 + 0x1p-19);
       const double eps = epsq + mu * 0x1p-21 + (form[0].mag + __builtin_fabs(lo)) * sc * 0x1p-44;
       const bool ok = eps < 0.125;                       // (NaN fails)
-      const double e = eps * 1.01, slack = 0x1p-23;
+      // (this copy of the bound is held by tests/test_boxed_model_cpu.py -- restated in tests/boxed_reference.py -- and,
+      // on rows built to sit on the threshold, by tests/test_gpu_boxed_threshold.py and tests/boxed_margin_worker.py)
+      double e = eps * 1.01, slack = 0x1p-23;
+#if SXMC_MEASURE
+      // (measurement build: the scales of fill_ordered_body -- dbg bits 8-15 = 1 + 64 * the scale on everything but Q,
+      // bits 16-23 = 1 + 64 * a scale on the whole threshold; 0 = unscaled.  RESULTS ARE WRONG below the bound.)
+      {
+        const unsigned fr = (dbg >> 8) & 0xFFu, ft = (dbg >> 16) & 0xFFu;
+        const double rs = fr ? (double)(fr - 1u) / 64.0 : 1.0, ts = ft ? (double)(ft - 1u) / 64.0 : 1.0;
+        e = (epsq + rs * (e - epsq)) * ts;
+        slack = slack * rs * ts;
+      }
+#endif
       af = uniform_f((float)alpha);
       gf = uniform_f((float)(g + e));
       thr = uniform_f((float)(2.0 * e + slack));
