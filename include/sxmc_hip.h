@@ -735,6 +735,44 @@ int sxmc_group_set_event_weights(sxmc_group_t g, const double* h_weights, size_t
  * SXMC_ERR_INVALID: a null argument (rows may be null when nrows == 0), nparameters < 1, shrinkage outside (0, 1]. */
 int sxmc_proposal_factor(const float* rows, size_t nrows, int nparameters, const float* new_widths, double shrinkage,
                          double* factor, double* shrinkage_used);
+/* WEIGHTED MONTE CARLO SAMPLES (opt-in; an evaluator without multiplicities runs the kernels it ran before).  Histograms
+ * and normalisations are `unsigned` counts and every consumer is linear in them, so a row's weight enters as an integer
+ * MULTIPLICITY m_i, a fixed-point weight on a power-of-two scale 2^k; only the fill changes (it adds m_i where it added 1)
+ * and the scale cancels exactly wherever bins, norm and n_mc meet, since all three carry it.
+ * THE LAW of the quantiser, on the host (no device call; usable without a GPU; restated in
+ * tests/sample_weights_reference.py):
+ *   - a weight is a finite double >= 0 (-0.0 is 0); one that is negative or not finite is SXMC_ERR_INVALID and the
+ *     message names the first such row;
+ *   - max_total = 0 means 2^32 - 1; a larger value is SXMC_ERR_INVALID;
+ *   - for a candidate k, m_i = (unsigned) nearbyint(ldexp(w_i, k)), rounding half to even;
+ *   - k is the LARGEST integer in [-32, 24] for which every m_i <= 2^32 - 1 and sum m_i <= max_total;
+ *   - no such k, or sum m_i == 0 at the chosen one (no rows, every weight 0): SXMC_ERR_INVALID;
+ *   - *total = sum m_i, summed in 64 bits; *log2_scale = k (both optional).
+ * Consequences: non-negative integer weights that fit come back as m_i = w_i * 2^k exactly; all-ones weights come back all
+ * equal to 2^k.  m: n words, written (partly, on failure). */
+int sxmc_sample_multiplicities(const double* w, size_t n, unsigned long long max_total, unsigned* m, int* log2_scale,
+                               unsigned long long* total);
+/* The multiplicities of an evaluator's table rows, one word per row (nsamples must be sxmc_hist_nsamples'), from host or
+ * device memory; the library keeps its own device copy, padded with 0 to the columns' pitch (the float columns' row
+ * padding stays NaN).  THE DEVICE LAW: bins[b] = sum of m_i over the rows the reference's arithmetic puts into bin b;
+ * norm = sum of m_i over the rows that pass the domain test, the in-domain row whose index comes out one past the end
+ * included; nothing else about an evaluation changes.  All m_i == c give the unweighted evaluator's pdf values as bytes;
+ * m in {0, 1, 2, ...} gives the counts of the table with row i repeated m_i times.
+ * Allowed before the evaluator's first evaluation and before it joins a group: SXMC_ERR_STATE afterwards.  A total beyond
+ * 2^32 - 1: SXMC_ERR_INVALID.  Evaluators made from this one by sxmc_hist_create_shared share the column.
+ * A weighted member's fill streams the table as it is (no pre-binned column, no bucketed, ordered or boxed copy, no codes,
+ * no run-time specialisation: sxmc_group_launch_info says "weighted"), 20 bytes per row and float column where the rows
+ * form streams 16; the unweighted members of the same group keep the forms they plan alone.  A group with a weighted member
+ * evaluates in the dense flavour (no sparse event-bin counters).  With a weighted member sxmc_multigroup_step_async and
+ * sxmc_multigroup_lookahead_step_async return SXMC_ERR_STATE and sxmc_group_lookahead_supported answers 0 without touching
+ * the group; sxmc_group_set_fill_form on a group whose members are all weighted returns SXMC_ERR_STATE. */
+int sxmc_hist_set_sample_multiplicities(sxmc_hist_t h, const unsigned* m, size_t nsamples, int on_device);
+/* sum m_i, or the row count when no multiplicities are set: what n_mc is for either kind (sxmc_hist_nsamples stays the
+ * row count). */
+int sxmc_hist_sample_total(sxmc_hist_t h, unsigned long long* total);
+/* The multiplicities back on the host, n = the row count; all 1 when none are set (*is_set, optional, says which;
+ * h_m NULL with n 0 asks that question alone). */
+int sxmc_hist_get_sample_multiplicities(sxmc_hist_t h, unsigned* h_m, size_t n, int* is_set);
 int sxmc_group_eval_async(sxmc_group_t g, int do_eval_pdf, sxmc_stream_t s);
 /* As sxmc_group_eval_async(g, 1, s) followed by nll_event_chunks (nll_kernels.cpp:89-116) over
  * the members' lookup table, with the table lookup and the event sum fused in one kernel: the

@@ -96,6 +96,10 @@ SIGNATURES = {
     "sxmc_hist_bin_volume": [_vp, _pd],
     "sxmc_hist_nsamples": [_vp, _psz],
     "sxmc_hist_npoints": [_vp, _psz],
+    "sxmc_sample_multiplicities": [_vp, _sz, _ull, _vp, _pi, C.POINTER(C.c_ulonglong)],
+    "sxmc_hist_set_sample_multiplicities": [_vp, _vp, _sz, _i],
+    "sxmc_hist_sample_total": [_vp, C.POINTER(C.c_ulonglong)],
+    "sxmc_hist_get_sample_multiplicities": [_vp, _vp, _sz, _pi],
     "sxmc_hist_get_bins": [_vp, _vp, _sz],
     "sxmc_hist_get_read_bins": [_vp, _vp, _sz],
     "sxmc_hist_project": [_vp, _i, _vp, _sz],

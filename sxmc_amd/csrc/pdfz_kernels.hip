@@ -29,6 +29,7 @@
 #include "nll_device.h"
 
 #include "fill_kernels.inc.h"
+#include "fill_weighted.inc.h"
 
 #pragma clang fp contract(off)
 
@@ -318,6 +319,15 @@ hipError_t launch_fill_k(const SxLaunchShape& sh, const SxSignalDesc* descs, con
                      dbg);
 }
 
+// Rows with multiplicities (fill_weighted.inc.h): the program decoded at run time, never fused with the step end.
+template <int NOBS, int NSLOT, bool LDS_HIST>
+hipError_t launch_fill_weighted_k(const SxLaunchShape& sh, const SxSignalDesc* descs, const SxSegment* segs,
+                                  const unsigned* blk_off, hipStream_t s) {
+  if (sh.tail) return hipErrorInvalidValue;   // (the host asks sx_fill_has_step_form first)
+  return launch_fill(sh, fill_weighted_kernel<NOBS, NSLOT, LDS_HIST, DynamicProg>, sh.lds_bytes, false, s, descs, segs,
+                     blk_off, sx_fill_w(sh));
+}
+
 // entries per wave (keys + counts) of the per-wave LDS tables of the sparse counting over runs
 unsigned sparse_smax(const SxLaunchShape& sh) { return (unsigned)(sh.sparse_lds_bytes / 4 / (sh.threads / 64u) / 2); }
 template <int NOBS, int NSLOT, typename PROG>
@@ -427,7 +437,26 @@ FillLauncher program_launcher(int prog, int form, int lds_hist, int sparse_runs)
   return e.fn[sparse_runs ? 2 : lds_hist ? 0 : 1][own ? 0 : form];
 }
 
+// The one straight-line program of the WEIGHTED fill: BASELINE config 3's, over rows, histogram in LDS or beyond it.
+// (Measured at config 3's shape: the program decoded at run time is bound by the scalar unit, as it is unweighted.)
+template <bool LDS_HIST>
+hipError_t launch_fill_weighted_c3(const SxLaunchShape& sh, const SxSignalDesc* descs, const SxSegment* segs,
+                                   const unsigned* blk_off, hipStream_t s) {
+  using P = StaticProg<SX_SHIFT(1), SX_SCALE(0), SX_RES(0, 3)>;
+  if (sh.tail) return hipErrorInvalidValue;
+  return launch_fill(sh, fill_weighted_kernel<3, 4, LDS_HIST, P>, sh.lds_bytes, false, s, descs, segs, blk_off, sx_fill_w(sh));
+}
+FillLauncher weighted_program_launcher(int prog, int lds_hist) {
+  static const unsigned c3[3] = {SX_SHIFT(1), SX_SCALE(0), SX_RES(0, 3)};
+  if (prog < 0 || prog >= kNumPrograms) return nullptr;
+  const FillEntry& e = kPrograms[prog];
+  if (e.form != kFormRows || e.nobs != 3 || e.nslot != 4 || e.nops != 3 || !std::equal(c3, c3 + 3, e.ops)) return nullptr;
+  return lds_hist ? launch_fill_weighted_c3<true> : launch_fill_weighted_c3<false>;
+}
+
 }  // namespace
+
+bool sx_fill_weighted_supports(int prog, int lds_hist) { return weighted_program_launcher(prog, lds_hist) != nullptr; }
 
 bool sx_fill_has_specialization(int nobs, int nslot) {
   return nobs >= 1 && nobs <= 5 && nslot >= nobs && nslot <= nobs + 2;
@@ -449,6 +478,7 @@ bool sx_fill_supports(int prog, int form, int lds_hist, int sparse_runs) {
 
 // Does the launch described by `sh` also exist fused with the step end (see fill_step_kernel)?
 bool sx_fill_has_step_form(const SxLaunchShape& sh) {
+  if (sh.weighted) return false;   // (a weighted fill has no fused form: the step falls back to its separate step end)
   if (sh.rtc_fill || !sh.lds_hist || sh.grid <= 0 || !program_launcher(sh.static_prog, sh.form, 1, 0)) return false;
   return sh.form == kFormOrdered || (sx_form_prebinned(sh.form) && kPrograms[sh.static_prog].nops == 0);
 }
@@ -478,6 +508,28 @@ hipError_t sx_launch_prebin(const SxSignalDesc* d_desc, unsigned long long npad,
 hipError_t sx_launch_fill(const SxLaunchShape& sh, const SxSignalDesc* descs, const SxSegment* segs,
                           const unsigned* blk_off, hipStream_t s) {
   if (sh.grid <= 0) return hipSuccess;
+  if (sh.weighted) {
+    // the weighted kernels: rows form only, the program decoded at run time for this (nobs, nslot), else the generic one
+    if (sh.form != kFormRows || sh.rtc_fill) return hipErrorInvalidValue;
+    if (sh.static_prog >= 0) {   // (the planner asked sx_fill_weighted_supports)
+      const FillLauncher fn = weighted_program_launcher(sh.static_prog, sh.lds_hist);
+      return fn ? fn(sh, descs, segs, blk_off, s) : hipErrorInvalidValue;
+    }
+#define SX_CASE(NO, NS)                                                                                         \
+  if (sh.nobs == NO && sh.nslot == NS)                                                                          \
+    return (sh.lds_hist ? launch_fill_weighted_k<NO, NS, true> : launch_fill_weighted_k<NO, NS, false>)(sh, descs, segs, \
+                                                                                                          blk_off, s);
+    SX_CASE(1, 1) SX_CASE(1, 2) SX_CASE(1, 3)
+    SX_CASE(2, 2) SX_CASE(2, 3) SX_CASE(2, 4)
+    SX_CASE(3, 3) SX_CASE(3, 4) SX_CASE(3, 5)
+    SX_CASE(4, 4) SX_CASE(4, 5) SX_CASE(4, 6)
+    SX_CASE(5, 5) SX_CASE(5, 6) SX_CASE(5, 7)
+#undef SX_CASE
+    if (sh.tail) return hipErrorInvalidValue;
+    return sh.lds_hist ? launch_fill(sh, fill_weighted_kernel_generic<true>, sh.lds_bytes, false, s, descs, segs, blk_off,
+                                     sx_fill_w(sh))
+                       : launch_fill(sh, fill_weighted_kernel_generic<false>, (size_t)64, false, s, descs, segs, blk_off, 0u);
+  }
   if (sh.rtc_fill) {
     return sx_rtc_launch(sh.rtc_fill, sh.grid, sh.threads, sh.lds_bytes, descs, segs, blk_off, sx_fill_w(sh),
                          (unsigned)sh.debug_mode, s, sh.ev_start, sh.ev_stop);

@@ -326,6 +326,8 @@ int sxmc_hist_create_shared(sxmc_hist_t base, sxmc_hist_t* out) {
   h->cfg_threads = base->cfg_threads;
   h->cfg_bpc = base->cfg_bpc;
   h->want_optimize = base->want_optimize;
+  h->mult = base->mult;   // (the rows' multiplicities belong to the table: shared with it)
+  h->mult_total = base->mult_total;
   SX_HIP(hipStreamCreate(&h->stream));
   SX_BUF(h->d_bins.alloc((size_t)h->total_nbins));
   SX_HIP(hipMemset(h->d_bins.get(), 0, sizeof(unsigned) * (size_t)h->total_nbins));
@@ -556,6 +558,56 @@ int sxmc_hist_nsamples(sxmc_hist_t h, size_t* v) {
   *v = h->nsamples;
   return SXMC_OK;
 }
+// ------------------------------------------------------------------------------ sample multiplicities
+int sxmc_hist_set_sample_multiplicities(sxmc_hist_t h, const unsigned* m, size_t nsamples, int on_device) {
+  SX_REQUIRE(h && (m || nsamples == 0), "null argument");
+  SX_REQUIRE(nsamples == h->nsamples, "sample multiplicities: one word per row of the evaluator's table");
+  if (h->deferred) SX_FLUSH();   // (an evaluation asked for and not launched yet counts as one)
+  if (h->joined) {
+    return fail(SXMC_ERR_STATE, "sample multiplicities are set before the evaluator's first evaluation and before it joins "
+                                "a group: its launch plans and those of its groups are built for the table they found");
+  }
+  std::vector<unsigned> host(nsamples);
+  if (nsamples) {
+    if (on_device) SX_HIP(hipMemcpy(host.data(), m, sizeof(unsigned) * nsamples, hipMemcpyDeviceToHost));
+    else std::memcpy(host.data(), m, sizeof(unsigned) * nsamples);
+  }
+  unsigned long long total = 0;
+  for (unsigned v : host) total += v;   // (at most 2^32 rows of less than 2^32 each: no overflow of 64 bits)
+  if (total > 0xFFFFFFFFull) {
+    return fail(SXMC_ERR_INVALID, "sample multiplicities: their total " + std::to_string(total) +
+                                      " exceeds 4294967295, what the unsigned normalisation holds");
+  }
+  // the library's own copy, 0 in the padding up to the columns' pitch (the float columns' padding stays NaN)
+  auto column = std::make_shared<DeviceBuffer<unsigned>>();
+  SX_BUF(column->alloc(h->pitch));
+  SX_HIP(hipMemset(column->get(), 0, sizeof(unsigned) * h->pitch));
+  if (nsamples) SX_HIP(hipMemcpy(column->get(), host.data(), sizeof(unsigned) * nsamples, hipMemcpyHostToDevice));
+  h->mult = std::move(column);
+  h->mult_total = total;
+  h->version++;
+  return SXMC_OK;
+}
+
+int sxmc_hist_sample_total(sxmc_hist_t h, unsigned long long* total) {
+  SX_REQUIRE(h && total, "null argument");
+  *total = h->mult ? h->mult_total : (unsigned long long)h->nsamples;
+  return SXMC_OK;
+}
+
+int sxmc_hist_get_sample_multiplicities(sxmc_hist_t h, unsigned* out, size_t n, int* is_set) {
+  SX_REQUIRE(h && (out || n == 0), "null argument");
+  if (is_set) *is_set = h->mult ? 1 : 0;
+  if (!out && n == 0) return SXMC_OK;   // (the question alone: are any set?)
+  SX_REQUIRE(n == h->nsamples, "sample multiplicities buffer size mismatch");
+  if (!h->mult) {
+    std::fill(out, out + n, 1u);   // (none set: every row counts once)
+    return SXMC_OK;
+  }
+  if (n) SX_HIP(hipMemcpy(out, h->mult->get(), sizeof(unsigned) * n, hipMemcpyDeviceToHost));
+  return SXMC_OK;
+}
+
 int sxmc_hist_npoints(sxmc_hist_t h, size_t* v) {
   SX_REQUIRE(h && v, "null argument");
   *v = h->has_points ? h->npoints : 0;

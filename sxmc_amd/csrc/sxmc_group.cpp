@@ -120,6 +120,7 @@ int sxmc_group_create(const sxmc_hist_t* members, int nmembers, sxmc_group_t* ou
   SX_BUF(g->d_coop_slots.alloc(kCoopMaxWorkers));
   SX_BUF(g->d_coop_last.alloc(kCoopMaxWorkers));
   SX_HIP(sx_step_end_slots_init(g->d_coop_slots.get(), g->d_coop_last.get(), kCoopMaxWorkers));
+  for (sxmc_hist* h : g->members) h->joined = true;   // (sxmc_hist_set_sample_multiplicities: not from here on)
   *out = g.release();
   return SXMC_OK;
 }
@@ -294,6 +295,10 @@ int sxmc_group_set_box_limit(sxmc_group_t g, double bins) {
 int sxmc_group_set_fill_form(sxmc_group_t g, int form) {
   SX_REQUIRE(g && (form == 1 || form == 2), "form: 1 boxed, 2 ordered");
   SX_FLUSH();
+  if (!g->members.empty() && weighted_members(g) == g->members.size()) {
+    return fail(SXMC_ERR_STATE, "every member of the group has sample multiplicities set: the weighted fill streams the "
+                                "table as it is (rows), there is no boxed or ordered form to choose");
+  }
   int rc = group_refresh(g);
   if (rc) return rc;
   SX_REQUIRE(has_two_forms(g), "the group's plan has one form only");
@@ -465,7 +470,8 @@ int sxmc_group_launch_info(sxmc_group_t g, char* out, size_t n) {
   for (size_t i = 0; i < plan.classes.size(); i++) {
     const LaunchClass& c = plan.classes[i];
     char line[512];
-    const char* kind = c.shape.rtc_fill ? "runtime" : c.shape.static_prog >= 0 ? "builtin" : c.shape.nobs ? "decoded" : "generic";
+    const char* kind = c.shape.weighted ? (c.shape.static_prog >= 0 ? "builtin+weighted" : c.shape.nobs ? "decoded+weighted" : "generic+weighted")
+                       : c.shape.rtc_fill ? "runtime" : c.shape.static_prog >= 0 ? "builtin" : c.shape.nobs ? "decoded" : "generic";
     std::snprintf(line, sizeof line,
                   "launch %zu: members=%zu nobs=%d nslot=%d hist=%s program=%s table=%s%s threads=%d grid=%d partition=%d teams=%d lds=%zu layout=0x%08X\n",
                   i, c.member_idx.size(), c.shape.nobs, c.shape.nslot, c.shape.lds_hist ? "lds" : "global", kind,
@@ -1105,7 +1111,8 @@ static void algorithmic_bytes(const sxmc_group* g, const LaunchPlan& plan, doubl
                                                      : 4.0 * (double)(bk->fields.size() - (ord ? 1 : 0));
       fr += (double)bk->nkept * row_bytes + ((box ? 16.0 : ord ? 8.0 : 0.0) + (bk->runs > 1 ? 8.0 : 4.0)) * (double)bk->ngranules;
     } else {
-      fr += (double)h->nsamples * (4.0 * (d.nslot - pre_dims) + pre_w);
+      // (+ the 4 bytes per row of a weighted member's multiplicities)
+      fr += (double)h->nsamples * (4.0 * (d.nslot - pre_dims) + pre_w + (h->mult ? 4.0 : 0.0));
     }
     if (h->total_nbins <= kLdsMaxBins) {
       hb += 4.0 * (double)h->total_nbins;                       // LDS-private, flushed once

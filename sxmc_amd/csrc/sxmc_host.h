@@ -291,6 +291,12 @@ struct sxmc_hist {
   bool bins_valid = true;          // false after a sparse evaluation: the dense histogram was not filled
   const sxmc_group* cleared_by = nullptr;  // the group whose finish_step cleared this histogram and nothing has
                                            // counted into it since (any group's fill resets it)
+  // sxmc_hist_set_sample_multiplicities: one `unsigned` per table row, padded with 0 to `pitch` words (the weighted fill
+  // reads whole 4-row units); shared with the evaluators made from this one (sxmc_hist_create_shared).  Null: every row
+  // counts once.  Set before the evaluator joins a group (`joined`: any evaluation goes through one) and not afterwards.
+  std::shared_ptr<sxhost::DeviceBuffer<unsigned>> mult;
+  unsigned long long mult_total = 0;   // sum of the multiplicities (<= 2^32 - 1)
+  bool joined = false;
   // sxmc_hist_eval_async defers (see "deferred evaluations" below)
   std::shared_ptr<struct DeferredBatch> deferred;  // the host thread's batch of evaluations not launched yet it sits in
   std::shared_ptr<struct BatchInFlight> inflight;  // the batched launch the last sxmc_hist_eval_async went into
@@ -340,6 +346,7 @@ struct LaunchClass {
   int box_obs = -1, box_truth = -1;   // ... the boxed observable and its truth field, as slots of the members' full descriptors
   unsigned padded_rstride = 0;  // ... with the LDS histogram in the padded form: words between its replicas (0: not)
   int max_bins = 0;             // the largest histogram of the members
+  // (shape.weighted: the members carry sample multiplicities -- part of the class's key, find_class)
 };
 
 // The settings a group's launch plan depends on: a plan built with other values than these is out of date (group_refresh).
@@ -487,6 +494,12 @@ int group_refresh(sxmc_group* g);
 inline bool has_two_forms(const sxmc_group* g) { return !g->ordered.classes.empty(); }
 template <class Group>   // (sxmc_group or const sxmc_group)
 auto& active_plan(Group* g) { return has_two_forms(g) && g->fill_form == 2 ? g->ordered : g->plan; }
+// sample multiplicities among the group's members: how many carry them (0: none; members.size(): all)
+inline size_t weighted_members(const sxmc_group* g) {
+  size_t n = 0;
+  for (const sxmc_hist* h : g->members) n += h->mult ? 1 : 0;
+  return n;
+}
 int group_check_bound(sxmc_group* g, bool need_pdf);
 int ensure_event_classes(sxmc_group* g, bool sparse);
 int group_prepare_fill(sxmc_group* g, hipStream_t s, bool sparse);

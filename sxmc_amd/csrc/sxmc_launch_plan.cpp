@@ -540,7 +540,11 @@ int plan_bucketed(sxmc_group* g, const PlanConfig& cfg, LaunchPlan& plan, int i,
 }
 
 // The table as it is: rows, or with the observables no systematic writes pre-binned.
-MemberPlan plan_rows(sxmc_group* g, const PlanConfig& cfg, const SxSignalDesc& d, const sxplan::SystUse& use, int lds_hist) {
+// `weighted` (the member carries sample multiplicities): rows only, the weighted fill's own straight-line kernel where it
+// has one for the program, else the program decoded at run time by the weighted kernel of this (nobs, nslot) or the
+// shape-agnostic one -- no run-time specialisation, nothing pre-binned.
+MemberPlan plan_rows(sxmc_group* g, const PlanConfig& cfg, const SxSignalDesc& d, const sxplan::SystUse& use, int lds_hist,
+                     bool weighted = false) {
   MemberPlan mp{};
   LaunchClass& k = mp.cls;
   mp.desc = d;
@@ -549,6 +553,16 @@ MemberPlan plan_rows(sxmc_group* g, const PlanConfig& cfg, const SxSignalDesc& d
   k.shape.nobs = spec ? d.nobs : 0;
   k.shape.nslot = spec ? d.nslot : 0;
   k.prog = sxplan::prog_words(d);
+  if (weighted) {
+    // (the weighted fill's own straight-line kernels, where it has one for the program; the class is then keyed by it)
+    const int wsp = (spec && use.specialisable)
+                        ? sx_fill_find_program(kFormRows, k.shape.nobs, k.shape.nslot, (int)k.prog.size(), k.prog.data())
+                        : -1;
+    k.shape.weighted = 1;
+    k.prog_simple = sx_fill_weighted_supports(wsp, lds_hist);
+    k.shape.static_prog = k.prog_simple ? wsp : -1;
+    return mp;
+  }
   const int sp = (spec && use.specialisable)
                      ? sx_fill_find_program(kFormRows, k.shape.nobs, k.shape.nslot, (int)k.prog.size(), k.prog.data())
                      : -1;
@@ -571,6 +585,10 @@ int plan_member(sxmc_group* g, const PlanConfig& cfg, LaunchPlan& plan, const De
   const SxSignalDesc& d = g->h_descs[(size_t)i];
   const int lds_hist = h->total_nbins <= kLdsMaxBins ? 1 : 0;
   const sxplan::SystUse use = sxplan::syst_use(d);
+  if (h->mult) {   // (no bucketed, ordered or boxed table with a permuted multiplicity column, no codes: rows)
+    mp = plan_rows(g, cfg, d, use, lds_hist, true);
+    return SXMC_OK;
+  }
   if (cfg.bucket && d.nsyst > 0 && use.specialisable) {
     const bool runs_possible = !plan.order_blocked && h->has_points && h->d_table && (int)g->members.size() <= props.cus;
     const int ordered = sxplan::choose_ordered(d, use, cfg.order, lds_hist != 0, runs_possible);
@@ -598,7 +616,7 @@ LaunchClass& find_class(LaunchPlan& plan, MemberPlan& mp, int threads) {
     if (c.shape.nobs == k.shape.nobs && c.shape.nslot == k.shape.nslot && c.shape.lds_hist == k.shape.lds_hist &&
         c.prog_simple == k.prog_simple && (!k.prog_simple || c.prog == k.prog) && c.pre_mask == k.pre_mask &&
         c.shape.form == k.shape.form && c.runs_mode == k.runs_mode && c.shape.rtc_fill == k.shape.rtc_fill &&
-        c.shape.rtc_sparse == k.shape.rtc_sparse) {
+        c.shape.rtc_sparse == k.shape.rtc_sparse && c.shape.weighted == k.shape.weighted) {
       return c;
     }
   }
@@ -613,7 +631,9 @@ int build_sparse_descs(sxmc_group* g) {
   std::vector<SxSignalDesc> sparse_descs = g->h_descs;
   g->sparse_ready = false;
   g->max_bins_sparse = 0;
-  bool sparse_ok = true;
+  // (a member with sample multiplicities: the weighted fill counts into dense histograms only, so the whole group
+  // evaluates in the dense flavour -- same values at the events' bins, same norms)
+  bool sparse_ok = weighted_members(g) == 0;
   for (int i = 0; i < n; i++) {
     sxmc_hist* h = g->members[i];
     if (h->total_nbins > kLdsMaxBins) {
@@ -726,6 +746,7 @@ int class_tables(const sxmc_group* g, const PlanConfig& cfg, LaunchPlan& plan, c
       }
       d.pre = pre;
     }
+    if (c.shape.weighted) d.pre = h->mult->get();   // (the rows' multiplicities, padded with 0 to the pitch)
     if (is_bucketed(c)) {
       const int runs = c.runs_mode ? std::max(1, K[q]) * (c.shape.threads / 64) : 1;
       const SampleStore::Bucketed* bk = nullptr;

@@ -133,6 +133,10 @@ int sxmc_multigroup_step_async(sxmc_multigroup_t mg, sxmc_stream_t s, const sxmc
       return fail(SXMC_ERR_STATE, "a member group has event weights set: lockstep sets have no weighted step end "
                                   "-- step the chains one by one (sxmc_group_step_async)");
     }
+    if (weighted_members(g)) {
+      return fail(SXMC_ERR_STATE, "a member group has sample multiplicities set: lockstep sets have no weighted fill "
+                                  "-- step the chains one by one (sxmc_group_step_async)");
+    }
   }
   // every chain's own plan first (may upload: before anything is launched)
   bool replan = mg->seen.size() != C;
@@ -251,6 +255,10 @@ int sxmc_multigroup_lookahead_step_async(sxmc_multigroup_t mg, sxmc_stream_t s, 
       return fail(SXMC_ERR_STATE, "a member group has event weights set: the look-ahead pass has no weighted form "
                                   "-- walk sequentially (sxmc_group_lookahead_supported says so beforehand)");
     }
+    if (weighted_members(g)) {
+      return fail(SXMC_ERR_STATE, "a member group has sample multiplicities set: the look-ahead pass has no weighted fill "
+                                  "-- walk sequentially (sxmc_group_lookahead_supported says so beforehand)");
+    }
   }
   hipStream_t st = (hipStream_t)s;
   bool replan = mg->seen.size() != 2;
@@ -342,7 +350,8 @@ int sxmc_group_lookahead_supported(sxmc_group_t g, int* ok) {
   *ok = 0;
   if (g->proposal_factor) return SXMC_OK;   // (no correlated look-ahead pass; asked before the group is touched)
   if (!g->event_weights.empty()) return SXMC_OK;   // (nor a weighted one)
-  g->plan_cfg.box = 0;   // (the pass runs over the ordered form; the question could be asked of g->ordered and leave the setting alone)
+  if (weighted_members(g)) return SXMC_OK;         // (nor one over sample multiplicities)
+  g->plan_cfg.box = 0;  // (the pass runs over the ordered form; the question could be asked of g->ordered and leave the setting alone)
   int rc = group_refresh(g);
   if (rc) return rc;
   if (!g->same_points || g->cfg_lut || (g->sparse_ready && g->cfg_sparse) || g->members.empty()) return SXMC_OK;

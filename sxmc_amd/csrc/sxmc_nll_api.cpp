@@ -3,6 +3,7 @@
 #include "sxmc_host.h"
 
 #include "proposal_factor.h"
+#include "sample_multiplicities.h"
 
 using namespace sxhost;
 
@@ -141,6 +142,28 @@ int sxmc_proposal_factor(const float* rows, size_t nrows, int nparameters, const
   SX_REQUIRE(shrinkage > 0.0 && shrinkage <= 1.0, "the proposal shrinkage must lie in (0, 1]");
   const double used = sxproposal::proposal_factor(rows, nrows, (size_t)nparameters, new_widths, shrinkage, factor);
   if (shrinkage_used) *shrinkage_used = used;
+  return SXMC_OK;
+}
+
+// Real sample weights as integer multiplicities: host arithmetic only (sample_multiplicities.h), nothing of the device is touched.
+int sxmc_sample_multiplicities(const double* w, size_t n, unsigned long long max_total, unsigned* m, int* log2_scale,
+                               unsigned long long* total) {
+  SX_REQUIRE((w && m) || n == 0, "null argument");
+  const sxweights::Result r = sxweights::sample_multiplicities(w, n, max_total, m);
+  switch (r.status) {
+    case sxweights::Status::ok: break;
+    case sxweights::Status::bad_max_total:
+      return fail(SXMC_ERR_INVALID, "sample weights: max_total beyond 4294967295, what the unsigned normalisation holds");
+    case sxweights::Status::bad_weight:
+      return fail(SXMC_ERR_INVALID, "sample weights: the weight of row " + std::to_string(r.row) + " is negative or not finite");
+    case sxweights::Status::no_scale:
+      return fail(SXMC_ERR_INVALID, "sample weights: no scale 2^k, k in [-32, 24], keeps every multiplicity and their total "
+                                    "within the limit");
+    case sxweights::Status::zero_total:
+      return fail(SXMC_ERR_INVALID, "sample weights: the multiplicities' total is 0 (no rows, or every weight rounds to 0)");
+  }
+  if (log2_scale) *log2_scale = r.log2_scale;
+  if (total) *total = r.total;
   return SXMC_OK;
 }
 

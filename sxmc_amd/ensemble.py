@@ -120,6 +120,8 @@ def make_evaluators(workload):
                 ev.SetCutoff(s.bandwidth_cutoff)
         else:
             ev = pdfz.EvalHist(s.samples, s.nfields, w.nobs, w.lower, w.upper, w.nbins, dataset=s.dataset)
+            if getattr(s, "multiplicities", None) is not None:
+                ev.SetSampleMultiplicities(s.multiplicities)
         for d in w.systematics:
             ev.AddSystematic(make_systematic(d))
         out.append(ev)
@@ -435,6 +437,10 @@ def run_experiments_in_lockstep(workload, seeds, nsteps, sets, burnin_fraction=0
     if proposal != "diagonal":
         raise ValueError("lockstep sets have no correlated step end: proposal %r walks one experiment per chain "
                          "(run_experiment, run_experiments_concurrently)" % (proposal,))
+    for j, s in enumerate(workload.signals):
+        if getattr(s, "multiplicities", None) is not None:
+            raise ValueError("signal %d has sample multiplicities: lockstep sets have no weighted fill; weighted Monte Carlo "
+                             "is fitted one experiment per chain (run_experiment, run_experiments_concurrently)" % j)
     chains = [m for st in sets for m in st.chains]
     assert len(seeds) == len(chains)
     for st in sets:

@@ -533,7 +533,10 @@ inline std::vector<float> read_dataset_to_samples(const std::vector<float>& data
                                                   const std::vector<std::string>& dataset_fields, unsigned dataset_id,
                                                   const std::vector<std::string>& sample_fields,
                                                   const std::vector<Observable>& cuts,
-                                                  size_t required = (size_t)-1) {
+                                                  size_t required = (size_t)-1, std::vector<size_t>* kept = nullptr) {
+  // kept (optional): the rows of `dataset` that passed the cuts, ascending -- what a per-row column beside the table
+  // (a signal's multiplicities) is cut with
+  if (kept) kept->clear();
   const size_t nf = dataset_fields.size(), ns = sample_fields.size();
   if (ns == 0 || nf == 0) return {};
   std::vector<char> has_cut(nf, 0);
@@ -567,6 +570,7 @@ inline std::vector<float> read_dataset_to_samples(const std::vector<float>& data
       if (has_cut[j] && ((double)row[j] < lo[j] || (double)row[j] > hi[j])) valid = false;
     }
     if (!valid) continue;
+    if (kept) kept->push_back(r);
     for (size_t j = 0; j + 1 < ns; j++) out.push_back(map[j] < nf ? row[map[j]] : 0.0f);
     out.push_back((float)dataset_id);
   }
@@ -992,16 +996,49 @@ inline FitConfig parse_config(const std::string& text, const std::string& base_d
         s.source = src;
         break;
       }
+    // "weight_field": a field of the sample file holding one real weight per row (weighted Monte Carlo).  Not a sample
+    // field: it is quantised over ALL rows of the file into integer multiplicities (sxmc_sample_multiplicities) and cut
+    // with the rows.
+    const std::string weight_field = c.isMember("weight_field") ? c["weight_field"].asString("weight_field") : "";
+    if (!weight_field.empty()) {
+      if (s.pdf == "kernel") {
+        throw ConfigError("signal '" + name + "': \"weight_field\" is only for \"pdf\": \"hist\" (kernel-density weights are not built)");
+      }
+      if (std::find(fc.sample_fields.begin(), fc.sample_fields.end(), weight_field) != fc.sample_fields.end()) {
+        throw ConfigError("signal '" + name + "': weight_field '" + weight_field + "' is also an observable or a systematic's field");
+      }
+    }
     std::vector<float> table;
+    double weight_total = 0.0;   // the real weight total of the file's rows, sum m * 2^-k
     if (load_tables) {
       std::vector<float> raw;
       std::vector<std::string> fields, npy_fields;
       for (const json::Value& fv : c["fields"].items) npy_fields.push_back(fv.asString("fields[]"));
       read_table(detail::join_path(base_dir, s.filename), raw, fields, npy_fields);
       s.n_mc = fields.empty() ? 0 : raw.size() / fields.size();   // BEFORE cuts (signal.cpp:28)
-      table = read_dataset_to_samples(raw, fields, s.dataset, fc.sample_fields, fc.cuts);
+      std::vector<size_t> kept;
+      table = read_dataset_to_samples(raw, fields, s.dataset, fc.sample_fields, fc.cuts, (size_t)-1, &kept);
+      if (!weight_field.empty()) {
+        const size_t column = std::find(fields.begin(), fields.end(), weight_field) - fields.begin();
+        if (column >= fields.size()) {
+          throw ConfigError("signal '" + name + "': weight_field '" + weight_field + "' is not a field of " + s.filename);
+        }
+        const size_t rows = s.n_mc;
+        std::vector<double> w(rows);
+        for (size_t r = 0; r < rows; r++) w[r] = (double)raw[r * fields.size() + column];
+        std::vector<unsigned> m(rows);
+        unsigned long long total = 0;
+        if (sxmc_sample_multiplicities(w.data(), rows, 0, m.data(), &s.weight_log2_scale, &total) != SXMC_OK) {
+          throw ConfigError("signal '" + name + "': weight_field '" + weight_field + "': " + sxmc_last_error());
+        }
+        s.n_mc = (size_t)total;                                   // the multiplicities' total BEFORE cuts
+        weight_total = std::ldexp((double)total, -s.weight_log2_scale);
+        s.multiplicities.resize(kept.size());
+        for (size_t i = 0; i < kept.size(); i++) s.multiplicities[i] = m[kept[i]];
+      }
     }
-    if (nexpected < 0) nexpected *= -1.0 * (double)s.n_mc;          // signal.cpp:31-35
+    // signal.cpp:31-35; with weights, "scale" scales by the real weight total of the file
+    if (nexpected < 0) nexpected *= -1.0 * (weight_field.empty() ? (double)s.n_mc : weight_total);
     s.nexpected = nexpected;
     fc.signals.push_back(s);
     fc.tables.push_back(std::move(table));

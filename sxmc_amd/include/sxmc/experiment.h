@@ -429,7 +429,13 @@ inline std::vector<ExperimentResult> ensemble_lockstep(const std::vector<unsigne
   if (opt.asimov) {
     throw pdfz::Error("ensemble_lockstep: a lockstep set has no weighted step end: fit the Asimov data set with ensemble");
   }
-  PoolScope pool;   // the experiments' arrays recycle their blocks instead of allocating and freeing (device_array.h)
+  for (const Signal& s : signals) {
+    if (!s.multiplicities.empty()) {
+      throw pdfz::Error("ensemble_lockstep: signal '" + s.name + "' has sample multiplicities and a lockstep set has no "
+                        "weighted fill: run the ensemble one experiment per chain (ensemble, ensemble_concurrent)");
+    }
+  }
+  PoolScope pool;  // the experiments' arrays recycle their blocks instead of allocating and freeing (device_array.h)
   const size_t L = std::max(2u, std::min(4u, chains_per_set)), S = std::max(1u, nsets), lanes = L * S;
   const size_t usable = experiments.size() / lanes * lanes;
   std::vector<ExperimentResult> out(experiments.size());

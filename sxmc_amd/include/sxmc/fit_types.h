@@ -59,7 +59,11 @@ struct Signal {
   unsigned dataset = 0;
   Source source;
   double nexpected = 0;
-  size_t n_mc = 0;  //!< number of MC samples BEFORE cuts (signal.cpp:28); build_pdfz fills it in when it is 0
+  size_t n_mc = 0;  //!< number of MC samples BEFORE cuts (signal.cpp:28); build_pdfz fills it in when it is 0.  With
+                    //!< multiplicities: their total BEFORE cuts (bins, norm and n_mc all carry the scale 2^k: it cancels)
+  std::vector<unsigned> multiplicities;       //!< "hist": one per row of the table given to build_pdfz (after cuts), or empty:
+                                              //!< every row counts once (include/sxmc_hip.h, sxmc_sample_multiplicities)
+  int weight_log2_scale = 0;                  //!< ... the k of their scale 2^k: a row's weight is m * 2^-k
   std::string pdf = "hist";                   //!< "hist": pdfz::EvalHist; "kernel": pdfz::EvalKernel (kernel density)
   std::vector<double> bandwidth_scale;        //!< "kernel": one per fit observable, in fit-observable order (empty: 1.0)
   double bandwidth_sensitivity = 0.0;         //!< "kernel": alpha of the adaptive bandwidths in [0, 1]; 0: fixed
@@ -110,13 +114,30 @@ inline void build_pdfz(Signal& sig, const std::vector<float>& samples, int nfiel
     }
     if (sig.bandwidth_cutoff != 0.0) static_cast<pdfz::EvalKernel*>(h)->SetCutoff(sig.bandwidth_cutoff);
   } else if (sig.pdf == "hist") {
-    h = new pdfz::EvalHist(samples, nfields, (int)observables.size(), lower, upper, nbins, sig.dataset);
+    pdfz::EvalHist* hist = new pdfz::EvalHist(samples, nfields, (int)observables.size(), lower, upper, nbins, sig.dataset);
+    h = hist;
+    if (!sig.multiplicities.empty()) {
+      if (sig.multiplicities.size() != samples.size() / (size_t)nfields) {
+        delete hist;
+        throw pdfz::Error("signal '" + sig.name + "': " + std::to_string(sig.multiplicities.size()) + " multiplicities for " +
+                          std::to_string(samples.size() / (size_t)nfields) + " rows");
+      }
+      hist->SetSampleMultiplicities(sig.multiplicities);
+    }
   } else {
     throw pdfz::Error("signal '" + sig.name + "': unknown pdf \"" + sig.pdf + "\" (\"hist\" or \"kernel\")");
   }
   sig.histogram = h;
   // (a table loaded through load_config has been cut: n_mc is then the row count before the cuts, set by the loader)
-  if (sig.n_mc == 0) sig.n_mc = samples.size() / (size_t)nfields;
+  if (sig.pdf == "kernel" && !sig.multiplicities.empty()) {
+    delete h;
+    sig.histogram = nullptr;
+    throw pdfz::Error("signal '" + sig.name + "': sample multiplicities on a \"kernel\" signal (kernel-density weights are not built)");
+  }
+  if (sig.n_mc == 0) {
+    sig.n_mc = samples.size() / (size_t)nfields;
+    if (!sig.multiplicities.empty()) sig.n_mc = (size_t)static_cast<pdfz::EvalHist*>(h)->SampleTotal();
+  }
   for (Systematic& s : systematics) {
     auto pars = std::make_shared<pdfz::Array<short>>(s.npars, true);
     for (size_t i = 0; i < s.pidx.size(); i++) pars->writeOnlyHostPtr()[i] = s.pidx[i];

@@ -737,7 +737,16 @@ class MCMC {
     /** The form of the steps (walk_plan.h: choose_form), narrowed by what the device says about the look-ahead pass;
      *  then what the form needs: the group bound and tuned, the shadow set, a stream to record on.  Lock: held. */
     void choose_form() {
-      form = sxmc::choose_form(covariance, event_weights != nullptr, WalkFlags{m.group != nullptr, m.reference_form,
+      // weighted Monte Carlo samples (EvalHist::SetSampleMultiplicities): only the fill differs, every sequential form
+      // takes them; a lockstep set has no weighted fill and is refused by name, a walk asked with lookahead goes sequentially
+      bool sample_weights = false;
+      for (pdfz::Eval* p : m.pdfs)
+        if (pdfz::EvalHist* h = dynamic_cast<pdfz::EvalHist*>(p)) sample_weights = sample_weights || h->HasSampleMultiplicities();
+      if (sample_weights && m.lockstep) {
+        throw pdfz::Error("MCMC: a lockstep set has no weighted fill: walk a chain over signals with sample multiplicities alone");
+      }
+      form = sxmc::choose_form(covariance, event_weights != nullptr, sample_weights,
+                               WalkFlags{m.group != nullptr, m.reference_form,
                                          m.nsystematics > 0 && !m.systematics_fixed, m.consume, m.lut_output,
                                          m.lockstep != nullptr, m.lookahead || m.lookahead_auto, m.nparameters,
                                          m.graph_steps, !m.kernels.empty()});

@@ -307,6 +307,32 @@ class EvalHist : public detail::EvalOver<detail::HistApi> {
     return std::string(buf.data());
   }
 
+  /** WEIGHTED MONTE CARLO SAMPLES: one integer multiplicity per table row; the fill adds m_i where it added 1
+   *  (include/sxmc_hip.h, sxmc_hist_set_sample_multiplicities: the law).  Before the first evaluation and before the
+   *  evaluator joins a group (an MCMC, an ensemble); a total beyond 2^32 - 1 throws.  Share() shares the column. */
+  void SetSampleMultiplicities(const std::vector<unsigned>& m) {
+    throw_on(sxmc_hist_set_sample_multiplicities(handle, m.data(), m.size(), 0));
+  }
+  /** The multiplicities' total, or the row count when none are set: what n_mc is for either kind. */
+  unsigned long long SampleTotal() {
+    unsigned long long total = 0;
+    throw_on(sxmc_hist_sample_total(handle, &total));
+    return total;
+  }
+  bool HasSampleMultiplicities() {
+    int is_set = 0;
+    throw_on(sxmc_hist_get_sample_multiplicities(handle, nullptr, 0, &is_set));
+    return is_set != 0;
+  }
+  /** The multiplicities; all 1 when none are set. */
+  std::vector<unsigned> SampleMultiplicities() {
+    size_t n = 0;
+    throw_on(sxmc_hist_nsamples(handle, &n));
+    std::vector<unsigned> out(n);
+    throw_on(sxmc_hist_get_sample_multiplicities(handle, out.data(), out.size(), nullptr));
+    return out;
+  }
+
   /** pdfz.h:542-556 */
   void GetSamples(std::vector<float>& sv) {
     size_t n = 0;

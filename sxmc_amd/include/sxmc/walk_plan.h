@@ -88,6 +88,9 @@ struct WalkFlags {
   bool event_weights = false;         //!< the data events carry real weights: every sequential form takes them (the
                                      //!< reference form and the MIXED form through the weighted launch point, the batched
                                      //!< forms through the group); never LOOKAHEAD or LOCKSTEP
+  bool sample_weights = false;        //!< a histogram member carries sample multiplicities (weighted Monte Carlo): every
+                                     //!< sequential form takes it -- only the fill differs --; the look-ahead pass and
+                                     //!< lockstep sets have no weighted fill
 };
 /** The form of the walk's steps, from the flags alone.  LOOKAHEAD is a candidate: two questions to the device (does the
  *  plan stream codes, is the pass offered for this shape) may still narrow it to CONSUMING, see narrowed(). */
@@ -117,8 +120,9 @@ inline WalkForm choose_form(const WalkFlags& f) {
   WalkForm::Step step = WalkForm::REFERENCE;
   if (fused && !f.consume) step = WalkForm::BATCHED;
   if (fused && f.consume) {
-    // (a correlated proposal, weighted events: asked with lookahead, or given a lockstep set, the walk goes sequentially)
-    step = (f.covariance_proposal || f.event_weights) ? WalkForm::CONSUMING
+    // (a correlated proposal, weighted events, weighted Monte Carlo samples: asked with lookahead, or given a lockstep
+    // set, the walk goes sequentially)
+    step = (f.covariance_proposal || f.event_weights || f.sample_weights) ? WalkForm::CONSUMING
            : f.in_lockstep_set   ? WalkForm::LOCKSTEP
            : (f.lookahead_asked && !f.lut_output && f.nparameters <= 256) ? WalkForm::LOOKAHEAD
                                                                            : WalkForm::CONSUMING;
@@ -137,6 +141,11 @@ inline WalkForm choose_form(bool covariance_proposal, WalkFlags f) {
 inline WalkForm choose_form(bool covariance_proposal, bool event_weights, WalkFlags f) {
   f.event_weights = event_weights;
   return choose_form(covariance_proposal, f);
+}
+/** ... and whose histogram members carry sample multiplicities (the signals', named beside the data's weights). */
+inline WalkForm choose_form(bool covariance_proposal, bool event_weights, bool sample_weights, WalkFlags f) {
+  f.sample_weights = sample_weights;
+  return choose_form(covariance_proposal, event_weights, f);
 }
 
 }  // namespace sxmc

@@ -14,6 +14,7 @@ Config parsing and file formats are not compute; they exist so that a fit descri
 schema can be run end to end (run_config; `fit.samples` re-loads a saved chain instead of walking, as sxmc.cpp:84-94
 does).  Plots and ROOT files are not supported.
 """
+import ctypes as C
 import json
 import math
 import os
@@ -21,7 +22,7 @@ import re
 
 import numpy as np
 
-from . import workloads
+from . import capi, workloads
 
 TYPE_NAMES = ("shift", "scale", "ctscale", "resolution_scale")     # systematic.cpp:21-36
 
@@ -74,7 +75,18 @@ def write_table(path, matrix, fields):
     np.savez(path, **{f: np.asarray(matrix)[:, i] for i, f in enumerate(fields)})
 
 
-def read_dataset_to_samples(dataset, dataset_fields, dataset_id, sample_fields, cuts, required=None):
+def sample_multiplicities(weights, max_total=0):
+    """Real sample weights as integer multiplicities on a power-of-two scale (sxmc_sample_multiplicities, the library's
+    one implementation; host arithmetic only): (m uint32 [n], log2_scale, total).  Raises capi.SxmcError on a weight that
+    is negative or not finite, or when nothing fits."""
+    w = np.ascontiguousarray(weights, np.float64).reshape(-1)
+    m = np.zeros(w.size, np.uint32)
+    k, total = C.c_int(0), C.c_ulonglong(0)
+    capi.call("sxmc_sample_multiplicities", capi.ptr(w), w.size, int(max_total), capi.ptr(m), C.byref(k), C.byref(total))
+    return m, k.value, total.value
+
+
+def read_dataset_to_samples(dataset, dataset_fields, dataset_id, sample_fields, cuts, required=None, want_kept=False):
     """signal.cpp:50-109.  dataset: [n, len(dataset_fields)]; sample_fields ends with "DATASET";
     cuts: list of (field, lower, upper) -- an event is dropped when a cut field is < lower or > upper
     (bounds inclusive); when several cuts name one field the LAST one counts, as in the reference's lookup table
@@ -103,6 +115,8 @@ def read_dataset_to_samples(dataset, dataset_fields, dataset_id, sample_fields, 
         elif k < required:
             raise KeyError("sample field %r not in data set fields %r" % (f, dataset_fields))
     out[:, -1] = dataset_id
+    if want_kept:    # ... and which rows passed the cuts (what a per-row column beside the table is cut with)
+        return out, np.flatnonzero(keep)
     return out
 
 
@@ -358,7 +372,20 @@ def load_config(path_or_text, base_dir=None):
         assert ("rate" in c) != ("scale" in c)
         src_name = c.get("source", name)
         pdf, bandwidth_scale = signal_pdf(name, c, len(fc.observables))
+        # "weight_field": a field of the sample file holding one real weight per row (weighted Monte Carlo); not a
+        # sample field: quantised over ALL rows of the file (sxmc_sample_multiplicities) and cut with the rows
+        weight_field = c.get("weight_field", "")
+        if not isinstance(weight_field, str):
+            raise ValueError("weight_field: not a string")
+        if weight_field:
+            if pdf == "kernel":
+                raise ValueError("signal '%s': \"weight_field\" is only for \"pdf\": \"hist\" (kernel-density weights "
+                                 "are not built)" % name)
+            if weight_field in fc.sample_fields:
+                raise ValueError("signal '%s': weight_field '%s' is also an observable or a systematic's field"
+                                 % (name, weight_field))
         fc.signals.append(dict(
+            weight_field=weight_field,
             name=name, dataset=int(c["dataset"]), filename=c["filename"],
             # config.cpp:216-222: both go through a float
             rate=float(np.float32(c["rate"])) if "rate" in c else None,
@@ -387,10 +414,24 @@ def build_workload(fc):
     for s in fc.signals:
         table, fields = read_table(os.path.join(fc.base_dir, s["filename"]))
         n_mc = table.shape[0]                                    # before cuts (signal.cpp:28)
+        scale_by = float(n_mc)
+        samples, kept = read_dataset_to_samples(table, fields, s["dataset"], fc.sample_fields, cuts, want_kept=True)
+        multiplicities, log2_scale = None, 0
+        if s.get("weight_field"):
+            if s["weight_field"] not in fields:
+                raise ValueError("signal '%s': weight_field '%s' is not a field of %s"
+                                 % (s["name"], s["weight_field"], s["filename"]))
+            weights = table[:, fields.index(s["weight_field"])].astype(np.float64)
+            try:
+                m, log2_scale, total = sample_multiplicities(weights)
+            except capi.SxmcError as e:
+                raise ValueError("signal '%s': weight_field '%s': %s" % (s["name"], s["weight_field"], e.msg))
+            n_mc = total                                         # the multiplicities' total BEFORE cuts
+            scale_by = float(np.ldexp(float(total), -log2_scale))    # "scale": the real weight total of the file
+            multiplicities = m[kept]
         # config.cpp:221 keeps -1 / scale in a float, signal.cpp:31-35 multiplies it by -n_mc in double
         nexpected = s["rate"] if s["rate"] is not None else \
-            float(np.float32(-1.0) / np.float32(s["scale"])) * (-1.0 * n_mc)
-        samples = read_dataset_to_samples(table, fields, s["dataset"], fc.sample_fields, cuts)
+            float(np.float32(-1.0) / np.float32(s["scale"])) * (-1.0 * scale_by)
         # (bandwidth scales in the workload's observable order, that of lower / upper)
         scale = [s["bandwidth_scale"][i] for i in order] if s.get("bandwidth_scale") else None
         sig = workloads.Signal(samples, nfields, nexpected, s["source"]["index"], dataset=s["dataset"],
@@ -399,6 +440,7 @@ def build_workload(fc):
                                bandwidth_cv=s.get("bandwidth_cv"),
                                bandwidth_cutoff=s.get("bandwidth_cutoff", 0.0))
         sig.n_mc_total = n_mc
+        sig.multiplicities, sig.weight_log2_scale = multiplicities, log2_scale
         sig.name = s["name"]
         signals.append(sig)
     systs = [dict(type=s["type"], obs=s["observable_field_index"], true_obs=s["truth_field_index"],

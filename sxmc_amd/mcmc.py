@@ -92,7 +92,12 @@ class MCMC:
             ev = pdfz.EvalHist(src, s.nfields, w.nobs, w.lower, w.upper, w.nbins, dataset=s.dataset)
             for d in w.systematics:
                 ev.AddSystematic(make_systematic(d))
+            if getattr(s, "multiplicities", None) is not None:
+                ev.SetSampleMultiplicities(s.multiplicities)   # (before the evaluator joins the group below)
             self.pdfs.append(ev)
+        # weighted Monte Carlo samples: only the fill differs, every sequential walk takes them; the look-ahead pass is not
+        # offered (Group.LookaheadSupported answers no) and lockstep sets refuse such chains by name
+        self.sample_weights = any(getattr(s, "multiplicities", None) is not None for s in w.signals)
         self.group = nll.EvalGroup(self.pdfs)
         self.group.SetLutOutput(lut_output)
 
@@ -631,7 +636,10 @@ class LockstepChains:
                 if c.event_weights is not None:
                     raise ValueError("chain %d of the lockstep set has event weights: lockstep sets have no weighted "
                                      "step end; step that chain on its own" % k)
-                c._launching(1)      # (every chain's jump buffer must hold the run)
+                if getattr(c, "sample_weights", False):
+                    raise ValueError("chain %d of the lockstep set has sample multiplicities: lockstep sets have no "
+                                     "weighted fill; step that chain on its own" % k)
+                c._launching(1)     # (every chain's jump buffer must hold the run)
         self.mg.StepAsync(self.stream, debug_mode)
 
     def drop_graph(self):

@@ -227,6 +227,32 @@ class EvalHist(_Eval):
         total = int(counts.sum())
         return counts / float(total) if total else np.zeros(counts.size)
 
+    # -- weighted Monte Carlo samples: integer multiplicities (include/sxmc_hip.h) -------------
+    def SetSampleMultiplicities(self, m):
+        """One uint32 per table row: the fill adds m_i where it added 1 (sxmc_hist_set_sample_multiplicities).  Before the
+        first evaluation and before the evaluator joins a group; a total beyond 2^32 - 1 raises Error."""
+        if hasattr(m, "data_ptr"):
+            n, on_device = int(m.numel()), 1
+        else:
+            m = np.ascontiguousarray(m)
+            if m.dtype != np.uint32:
+                if m.size and (np.any(m < 0) or np.any(m > 0xFFFFFFFF) or np.any(m != np.floor(m))):
+                    raise Error("sample multiplicities are integers in [0, 2^32 - 1]")
+                m = m.astype(np.uint32)
+            m = m.reshape(-1)
+            n, on_device = m.size, 0
+        self._call("set_sample_multiplicities", capi.ptr(m), n, on_device)
+
+    def SampleTotal(self):
+        """The multiplicities' total, or the row count when none are set: n_mc for either kind."""
+        return self._get("sample_total", C.c_ulonglong)
+
+    def SampleMultiplicities(self):
+        """The multiplicities (uint32 [nsamples]); all 1 when none are set."""
+        out = np.empty(self.nsamples, dtype=np.uint32)
+        self._call("get_sample_multiplicities", capi.ptr(out), out.size, None)
+        return out
+
     # -- replaces Optimize*: analytic launch sizing, optionally overridden -------------------
     def SetLaunchConfig(self, bin_threads=0, bin_blocks_per_cu=0):
         self._call("set_launch_config", int(bin_threads), int(bin_blocks_per_cu))

@@ -30,10 +30,19 @@ class Signal:
         self.cv_report = None
         # "kernel": the cutoff radius of the pair sum in bandwidths (pdfz.EvalKernel.SetCutoff); 0: none
         self.bandwidth_cutoff = float(bandwidth_cutoff)
+        # "hist": weighted Monte Carlo -- one integer multiplicity per row of `samples` (uint32; None: every row counts
+        # once) on the scale 2^weight_log2_scale (include/sxmc_hip.h, sxmc_sample_multiplicities)
+        self.multiplicities = None
+        self.weight_log2_scale = 0
 
     @property
     def n_mc(self):
-        return self.samples.shape[0] if self.n_mc_total is None else self.n_mc_total
+        """Simulated events BEFORE cuts; with multiplicities their total (n_mc_total: the total before cuts)."""
+        if self.n_mc_total is not None:
+            return self.n_mc_total
+        if self.multiplicities is not None:
+            return int(np.asarray(self.multiplicities, dtype=np.uint64).sum())
+        return self.samples.shape[0]
 
 
 class Workload:
