@@ -760,7 +760,8 @@ int sxmc_sample_multiplicities(const double* w, size_t n, unsigned long long max
  * m in {0, 1, 2, ...} gives the counts of the table with row i repeated m_i times.
  * Allowed before the evaluator's first evaluation and before it joins a group: SXMC_ERR_STATE afterwards.  A total beyond
  * 2^32 - 1: SXMC_ERR_INVALID.  Evaluators made from this one by sxmc_hist_create_shared share the column.
- * A weighted member's fill streams the table as it is (no pre-binned column, no bucketed, ordered or boxed copy, no codes,
+ * A weighted member's fill (fill_body with PREW = kPreWeighted, sxmc_amd/csrc/fill_kernels.inc.h) streams the table as
+ * it is (no pre-binned column, no bucketed, ordered or boxed copy, no codes,
  * no run-time specialisation: sxmc_group_launch_info says "weighted"), 20 bytes per row and float column where the rows
  * form streams 16; the unweighted members of the same group keep the forms they plan alone.  A group with a weighted member
  * evaluates in the dense flavour (no sparse event-bin counters).  With a weighted member sxmc_multigroup_step_async and

@@ -327,7 +327,14 @@ __device__ __forceinline__ void sparse_count(const SxSignalDesc& d, gptr<unsigne
 // sees a lower-dimensional problem -- every observable it is given is binned here -- plus ONE word per
 // 256-sample granule: the granule's constant contribution to the flat bin index.  A wave reads exactly one
 // granule per step (units are 4 samples, a wave covers 64 consecutive units), so that word is wave-uniform.
+//
+// WEIGHTED ROWS (PREW = kPreWeighted; sxmc_hist_set_sample_multiplicities, include/sxmc_hip.h).  The rows form with ONE
+// more column streamed behind the float columns: the rows' integer multiplicities, one `unsigned` per row (one 16-byte
+// load per unit, PreVec<4>), padded with 0 to the columns' pitch -- the descriptor's `pre`, which a weighted class has
+// free: nothing is pre-binned.  20 bytes per row and streamed slot where the rows form streams 16.  Built into the
+// library only: a weighted launch class never asks for a run-time specialisation.
 constexpr int kPreGranule = kFormBucketed;   // (the names of sxmc_device_types.h, as the kernels spell them)
+constexpr int kPreWeighted = 4;              // (no form of table: the host marks a weighted class SxLaunchShape::weighted)
 template <int PREW> struct PreVec { typedef unsigned type; };
 template <> struct PreVec<2> { typedef unsigned type __attribute__((ext_vector_type(2))); };
 template <> struct PreVec<4> { typedef unsigned type __attribute__((ext_vector_type(4))); };
@@ -341,7 +348,7 @@ struct Columns {
 // slot k is streamed unless it is an observable that the pre-binned column covers
 template <int NOBS, int PREW, typename PROG>
 constexpr bool slot_loaded(int k) {
-  return PREW == 0 || PREW == kPreGranule || k >= NOBS || ((PROG::touched >> k) & 1u);
+  return PREW == 0 || PREW == kPreGranule || PREW == kPreWeighted || k >= NOBS || ((PROG::touched >> k) & 1u);
 }
 
 template <int PREW>
@@ -391,9 +398,18 @@ __device__ __forceinline__ void load_columns(Columns<NSLOT, PREW>& c, const gptr
 // = largest member), then 64 "trash" words, one per lane: a sample that is outside the domain
 // adds to its lane's trash word instead of being branched around, so the whole per-sample path
 // is unpredicated vector code (no exec-mask juggling on the scalar unit).
+//
+// The law with multiplicities (PREW = kPreWeighted): bins[b] = sum of m_i over the rows the arithmetic below puts into
+// bin b; norm = sum of m_i over the rows that pass the domain test, the in-domain row whose index comes out one past
+// the end included.  Without them every m_i is 1.  Counts are integers, integer atomics commute, and the host caps
+// sum m_i at 2^32 - 1, so no partial sum -- a lane's, a workgroup's LDS word, a bin -- can overflow.  A weighted launch
+// has its histogram in LDS or, beyond it, under dense global atomics (a group with a weighted member evaluates in the
+// dense flavour, sxmc_launch_plan.cpp build_sparse_descs): never the sparse counters.
 template <int NOBS, int NSLOT, bool LDS_HIST, typename PROG, int PREW>
 __device__ __forceinline__ void fill_body(const SxSignalDesc* __restrict__ descs, const SxSegment* __restrict__ segs,
                                           const unsigned* __restrict__ blk_off, unsigned hist_words, unsigned dbg_arg) {
+  constexpr bool kRowsWeighted = PREW == kPreWeighted;
+  constexpr bool kPrebinned = PREW != 0 && !kRowsWeighted;   // `pre` carries (part of) the flat bin index
   const unsigned dbg = sx_dbg(dbg_arg);   // (0 in the product build: see SXMC_MEASURE)
   extern __shared__ unsigned lds[];
   const unsigned tid = threadIdx.x;
@@ -415,7 +431,7 @@ __device__ __forceinline__ void fill_body(const SxSignalDesc* __restrict__ descs
     const unsigned long long v1 = sg.v1;
     const unsigned long long step = sg.step;
 
-    const bool sparse = !LDS_HIST && d.sparse_table != nullptr;
+    const bool sparse = !kRowsWeighted && !LDS_HIST && d.sparse_table != nullptr;
     const unsigned B = sparse ? (unsigned)d.sparse_real_nbins : (unsigned)d.total_nbins;
     gptr<unsigned> gbins = to_global(d.bins);
 
@@ -505,6 +521,11 @@ __device__ __forceinline__ void fill_body(const SxSignalDesc* __restrict__ descs
         }
       }
       typename PreVec<PREW>::type prebits = buf.pre;
+      unsigned mq[SXMC_VEC];   // (weighted) the unit's multiplicities: what each of its rows counts for
+      if constexpr (kRowsWeighted) {
+#pragma unroll
+        for (int q = 0; q < SXMC_VEC; q++) mq[q] = pre_value<PREW>(prebits, q);
+      }
       // Pin every widening BEFORE the buffer is re-loaded: if the compiler sinks one of them
       // below, that column's registers stay live across the reload, the reload lands in fresh
       // registers and the loop latch copies them back behind a vmcnt(0) that drains the ring.
@@ -515,11 +536,17 @@ __device__ __forceinline__ void fill_body(const SxSignalDesc* __restrict__ descs
           for (int q = 0; q < SXMC_VEC; q++) asm volatile("" : "+v"(f[k][q]));
         }
       }
-      if constexpr (PREW != 0) asm volatile("" : "+v"(prebits));
+      // (the multiplicities as four scalars)
+      if constexpr (kRowsWeighted) {
+#pragma unroll
+        for (int q = 0; q < SXMC_VEC; q++) asm volatile("" : "+v"(mq[q]));
+      } else if constexpr (PREW != 0) {
+        asm volatile("" : "+v"(prebits));
+      }
       // dbg: measurement hooks (libsxmc_hip_measure.so's sxmc_group_set_debug_mode), the constant 0 in the product:
       //   bit 1: every reload hits one cached address -> the kernel without its HBM stream
       //   bit 0: skip the arithmetic and the histogram -> the HBM stream alone
-      //   bit 2: skip only the histogram update
+      //   bit 2: skip only the histogram update (not in the weighted fill)
       const unsigned long long vl = vc + step;
       load_columns<NOBS, NSLOT, PREW, PROG>(buf, col, precol, (vl < v1 && !(dbg & 2u)) ? vl : vlast);
       if (dbg & 1u) {
@@ -528,7 +555,8 @@ __device__ __forceinline__ void fill_body(const SxSignalDesc* __restrict__ descs
 #pragma unroll
           for (int q = 0; q < SXMC_VEC; q++) cnt += (f[k][q] == 12345.678) ? 1u : 0u;
         }
-        if constexpr (PREW != 0) cnt += (pre_value<PREW>(prebits, 0) == 12345u) ? 1u : 0u;
+        if constexpr (kRowsWeighted) cnt += (mq[0] == 12345u) ? 1u : 0u;
+        if constexpr (kPrebinned) cnt += (pre_value<PREW>(prebits, 0) == 12345u) ? 1u : 0u;
         return;
       }
 
@@ -540,7 +568,8 @@ __device__ __forceinline__ void fill_body(const SxSignalDesc* __restrict__ descs
         run_static<NSLOT>(f, craw, PROG{}, typename MakeISeq<PROG::n>::type{});
       }
 
-      // lanes past the end of the slice hold clamped duplicates: count them as failures
+      // lanes past the end of the slice hold clamped duplicates: count them as failures (weighted: their m goes to the
+      // trash word)
       const unsigned dead = (vc < v1) ? 0u : 1u;
       unsigned okbin[SXMC_VEC];   // flat bin index of a sample to be counted, or all ones (non-LDS modes)
 #pragma unroll
@@ -549,7 +578,7 @@ __device__ __forceinline__ void fill_body(const SxSignalDesc* __restrict__ descs
         // add-with-carry, nothing on the scalar unit); the tests are written so that NaN fails.
         unsigned bad = dead;
         int bin = 0;
-        if constexpr (PREW != 0) {
+        if constexpr (kPrebinned) {
           const unsigned pv = pre_value<PREW>(prebits, q);
           if constexpr (PREW != kPreGranule) bad += (pv == pre_sentinel<PREW>()) ? 1u : 0u;
           bin = (int)pv;
@@ -569,19 +598,29 @@ __device__ __forceinline__ void fill_body(const SxSignalDesc* __restrict__ descs
             bin += idx * st[k];
           }
         }
-        const unsigned in_domain = (bad == 0u) ? 1u : 0u;
+        const unsigned in_domain = (bad == 0u) ? (kRowsWeighted ? mq[q] : 1u) : 0u;
         cnt += in_domain;
         // in domain but index out of range (the reference's one-past-the-end case) still counts in the
         // norm; it and every failure are not histogrammed
-        const bool store = (bad == 0u) && ((unsigned)bin < B) && !(dbg & 4u);
+        // (The weighted fill does without hook bit 2 and reads a row's m at each use.  With the third term the compiler
+        // lays the per-sample path out differently: the static 3-observable kernel takes 98 VGPRs for 78 and reloads the
+        // multiplicities into fresh registers, copied back behind a full wait.  With m read once per row the
+        // 5-observable kernels beyond LDS spill 8 and 4 bytes more.)
+        const bool store = kRowsWeighted ? (bad == 0u) && ((unsigned)bin < B)
+                                         : (bad == 0u) && ((unsigned)bin < B) && !(dbg & 4u);
         if (LDS_HIST) {
           const unsigned slot = store ? (unsigned)bin : trash;   // failures go to the lane's trash word
-          __hip_atomic_fetch_add(&hist[slot], 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+          __hip_atomic_fetch_add(&hist[slot], kRowsWeighted ? mq[q] : 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+        } else if constexpr (kRowsWeighted) {
+          // (dense only, and a row of multiplicity 0 sends no atomic to HBM)
+          if (store && mq[q] != 0u) {
+            __hip_atomic_fetch_add(&gbins[(unsigned)bin], mq[q], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+          }
         } else {
           okbin[q] = store ? (unsigned)bin : 0xFFFFFFFFu;
         }
       }
-      if (!LDS_HIST) {
+      if (!LDS_HIST && !kRowsWeighted) {
         if (sparse) {
           // all four filter words are requested before any is tested: one L2 round trip, not four
           // level 1: coarse filter in LDS, two bits per bin (passes ~3 % of the non-members at 1e5 event bins)

@@ -29,7 +29,6 @@
 #include "nll_device.h"
 
 #include "fill_kernels.inc.h"
-#include "fill_weighted.inc.h"
 
 #pragma clang fp contract(off)
 
@@ -54,8 +53,9 @@ __global__ __launch_bounds__(256) void zero_kernel(const SxSignalDesc* __restric
 
 // Shape-agnostic fallback (any nobs/nslot up to SXMC_MAX_NFIELDS): one sample per lane per
 // iteration, fields in a dynamically indexed array.  Correctness path for shapes without a
-// specialization; same arithmetic.
-template <bool LDS_HIST>
+// specialization; same arithmetic.  WEIGHTED: every row counts with its multiplicity (the descriptor's `pre`, one word
+// per row: fill_body's law), dense histograms only.
+template <bool LDS_HIST, bool WEIGHTED = false>
 __global__ __launch_bounds__(1024) void fill_kernel_generic(const SxSignalDesc* __restrict__ descs,
                                                             const SxSegment* __restrict__ segs,
                                                             const unsigned* __restrict__ blk_off,
@@ -75,9 +75,10 @@ __global__ __launch_bounds__(1024) void fill_kernel_generic(const SxSignalDesc* 
     const unsigned long long v0 = sg.v0;
     const unsigned long long v1 = sg.v1;
     const unsigned long long step = sg.step;
-    const bool sparse = !LDS_HIST && d.sparse_table != nullptr;
+    const bool sparse = !WEIGHTED && !LDS_HIST && d.sparse_table != nullptr;
     const unsigned B = sparse ? (unsigned)d.sparse_real_nbins : (unsigned)d.total_nbins;
     gptr<unsigned> gbins = to_global(d.bins);
+    gptr<const unsigned> mcol = to_global(reinterpret_cast<const unsigned*>(d.pre));
     if (!lds_clean) {
       // whole LDS histogram (sized for the largest member), once per workgroup
       if (LDS_HIST) {
@@ -94,6 +95,8 @@ __global__ __launch_bounds__(1024) void fill_kernel_generic(const SxSignalDesc* 
     for (unsigned long long c = v0; c < v1; c += step)
     for (unsigned long long i = c * SXMC_VEC + tid;
          i < (c + nthreads < v1 ? c + nthreads : v1) * SXMC_VEC; i += nthreads) {
+      unsigned m = 1u;
+      if constexpr (WEIGHTED) m = mcol[i];   // (the padding rows of the last unit: 0 here, NaN in the float columns)
       double f[SXMC_MAX_NFIELDS];
       for (int k = 0; k < nslot; k++) {
         f[k] = (double)to_global(d.cols)[(unsigned long long)d.slot_col[k] * d.col_pitch + i];
@@ -122,15 +125,15 @@ __global__ __launch_bounds__(1024) void fill_kernel_generic(const SxSignalDesc* 
         ok = (x >= d.lower[k]) && (x < d.upper[k]);
         if (ok) bin += (int)((x - d.lower[k]) * d.scale[k]) * d.bin_stride[k];
       }
-      if (ok) {
-        cnt += 1u;
+      if (ok && (!WEIGHTED || m != 0u)) {
+        cnt += m;
         if ((unsigned)bin < B) {
           if (LDS_HIST) {
-            __hip_atomic_fetch_add(&hist[bin], 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+            __hip_atomic_fetch_add(&hist[bin], m, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
           } else if (sparse) {
             sparse_count(d, gbins, (unsigned)bin);
           } else {
-            __hip_atomic_fetch_add(&gbins[bin], 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            __hip_atomic_fetch_add(&gbins[bin], m, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
           }
         }
       }
@@ -302,8 +305,9 @@ hipError_t launch_fill(const SxLaunchShape& sh, K k, size_t lds, bool fused, hip
 
 using FillLauncher = hipError_t (*)(const SxLaunchShape&, const SxSignalDesc*, const SxSegment*, const unsigned*, hipStream_t);
 
-// Rows, a pre-binned column or a bucketed table: fill_kernel.  Fused with the step end there are the ordered programs
-// (below) and, here, the LDS-histogram kernels of the EMPTY program over a pre-binned column (BASELINE config 2).
+// Rows, a pre-binned column, a bucketed table or rows with multiplicities (FORM = kPreWeighted): fill_kernel.  Fused with
+// the step end there are the ordered programs (below) and, here, the LDS-histogram kernels of the EMPTY program over a
+// pre-binned column (BASELINE config 2).
 template <int NOBS, int NSLOT, bool LDS_HIST, typename PROG, int FORM = kFormRows>
 hipError_t launch_fill_k(const SxLaunchShape& sh, const SxSignalDesc* descs, const SxSegment* segs,
                          const unsigned* blk_off, hipStream_t s) {
@@ -319,13 +323,22 @@ hipError_t launch_fill_k(const SxLaunchShape& sh, const SxSignalDesc* descs, con
                      dbg);
 }
 
-// Rows with multiplicities (fill_weighted.inc.h): the program decoded at run time, never fused with the step end.
-template <int NOBS, int NSLOT, bool LDS_HIST>
-hipError_t launch_fill_weighted_k(const SxLaunchShape& sh, const SxSignalDesc* descs, const SxSegment* segs,
-                                  const unsigned* blk_off, hipStream_t s) {
-  if (sh.tail) return hipErrorInvalidValue;   // (the host asks sx_fill_has_step_form first)
-  return launch_fill(sh, fill_weighted_kernel<NOBS, NSLOT, LDS_HIST, DynamicProg>, sh.lds_bytes, false, s, descs, segs,
-                     blk_off, sx_fill_w(sh));
+// The kernel that decodes the program at run time for this (nobs, nslot): over rows, or over rows with multiplicities.
+template <int NOBS, int NSLOT>
+FillLauncher decoded_launcher(bool lds_hist, bool weighted) {
+  if (weighted) {
+    return lds_hist ? launch_fill_k<NOBS, NSLOT, true, DynamicProg, kPreWeighted>
+                    : launch_fill_k<NOBS, NSLOT, false, DynamicProg, kPreWeighted>;
+  }
+  return lds_hist ? launch_fill_k<NOBS, NSLOT, true, DynamicProg> : launch_fill_k<NOBS, NSLOT, false, DynamicProg>;
+}
+
+template <bool WEIGHTED>
+hipError_t launch_fill_generic(const SxLaunchShape& sh, const SxSignalDesc* descs, const SxSegment* segs,
+                               const unsigned* blk_off, hipStream_t s) {
+  return sh.lds_hist ? launch_fill(sh, fill_kernel_generic<true, WEIGHTED>, sh.lds_bytes, false, s, descs, segs, blk_off,
+                                   sx_fill_w(sh))
+                     : launch_fill(sh, fill_kernel_generic<false, WEIGHTED>, (size_t)64, false, s, descs, segs, blk_off, 0u);
 }
 
 // entries per wave (keys + counts) of the per-wave LDS tables of the sparse counting over runs
@@ -361,13 +374,16 @@ struct FillEntry {
   int nobs, nslot, nops;
   unsigned ops[4];
   // [histogram in LDS / beyond it (dense global atomics or sparse event-bin counters) / bucketed table walked in runs, event
-  // bins counted in per-wave LDS tables][form: rows, pre-binned 1 / 2 bytes per sample, bucketed]; ordered and boxed: [0][0]
-  FillLauncher fn[3][4];
+  // bins counted in per-wave LDS tables][form: rows, pre-binned 1 / 2 bytes per sample, bucketed, rows with multiplicities];
+  // ordered and boxed: [0][0]
+  FillLauncher fn[3][5];
 };
-static_assert(kFormRows == 0 && kFormPre1 == 1 && kFormPre2 == 2 && kFormBucketed == 3, "fn is indexed by these forms");
+static_assert(kFormRows == 0 && kFormPre1 == 1 && kFormPre2 == 2 && kFormBucketed == 3 && kPreWeighted == 4,
+              "fn is indexed by these forms");
 // kPre: LDS histogram, observables no systematic writes pre-binned; kBeyond: histogram beyond LDS, rows and pre-binned;
-// kGran: bucketed table (every observable given is binned, + one offset per granule), histogram in LDS, beyond LDS, runs
-enum : unsigned { kPre = 1, kBeyond = 2, kGran = 4 };
+// kGran: bucketed table (every observable given is binned, + one offset per granule), histogram in LDS, beyond LDS, runs;
+// kWeighted: rows with multiplicities, histogram in LDS and beyond it
+enum : unsigned { kPre = 1, kBeyond = 2, kGran = 4, kWeighted = 8 };
 template <int FORM, unsigned HAS, int NO, int NS, unsigned... OPS>
 constexpr FillEntry fill_entry() {
   using P = StaticProg<OPS...>;
@@ -389,6 +405,10 @@ constexpr FillEntry fill_entry() {
       e.fn[0][kFormBucketed] = launch_fill_k<NO, NS, true, P, kFormBucketed>;
       e.fn[1][kFormBucketed] = launch_fill_k<NO, NS, false, P, kFormBucketed>;
       e.fn[2][kFormBucketed] = launch_fill_sparse_k<NO, NS, P>;
+    }
+    if constexpr (HAS & kWeighted) {
+      e.fn[0][kPreWeighted] = launch_fill_k<NO, NS, true, P, kPreWeighted>;
+      e.fn[1][kPreWeighted] = launch_fill_k<NO, NS, false, P, kPreWeighted>;
     }
   }
   return e;
@@ -416,7 +436,8 @@ const FillEntry kPrograms[] = {
     // 3-D (BASELINE config 3: shift(r) + scale(e) + resolution_scale(e | e_true))
     SX_PROG(kFormRows, kPre, 3, 3, SX_SHIFT(0)), SX_PROG(kFormRows, kPre, 3, 3, SX_SCALE(0)),
     SX_PROG(kFormRows, kPre, 3, 4, SX_RES(0, 3)), SX_PROG(kFormRows, kPre, 3, 4, SX_SCALE(0), SX_RES(0, 3)),
-    SX_PROG(kFormRows, kPre | kBeyond, 3, 4, SX_SHIFT(1), SX_SCALE(0), SX_RES(0, 3)),
+    // (the one straight-line program of the WEIGHTED fill: decoded at run time it is bound by the scalar unit at this shape)
+    SX_PROG(kFormRows, kPre | kBeyond | kWeighted, 3, 4, SX_SHIFT(1), SX_SCALE(0), SX_RES(0, 3)),
     // 5-D (BASELINE config 5: the same three systematics, histograms beyond LDS capacity)
     SX_PROG(kFormRows, kPre | kBeyond, 5, 6, SX_SHIFT(1), SX_SCALE(0), SX_RES(0, 5)),
     // ordered: one observable, one shift / scale (bench_sxmc pdfz): nothing is streamed but the granule words
@@ -428,35 +449,22 @@ const FillEntry kPrograms[] = {
 };
 constexpr int kNumPrograms = (int)(sizeof(kPrograms) / sizeof(kPrograms[0]));
 
-// The launcher of built-in program `prog` for this form of table and histogram mode, or null.
-FillLauncher program_launcher(int prog, int form, int lds_hist, int sparse_runs) {
+// The launcher of built-in program `prog` for this form of table and histogram mode, or null.  `weighted`: the rows carry
+// multiplicities (the rows form only).
+FillLauncher program_launcher(int prog, int form, int lds_hist, int sparse_runs, bool weighted = false) {
   if (prog < 0 || prog >= kNumPrograms) return nullptr;
   const FillEntry& e = kPrograms[prog];
   const bool own = sx_form_ordered(form);   // (an entry of that form, its one kernel in [0][0])
   if (e.form != (own ? form : kFormRows) || form < kFormRows || (!own && form > kFormBucketed)) return nullptr;
-  return e.fn[sparse_runs ? 2 : lds_hist ? 0 : 1][own ? 0 : form];
-}
-
-// The one straight-line program of the WEIGHTED fill: BASELINE config 3's, over rows, histogram in LDS or beyond it.
-// (Measured at config 3's shape: the program decoded at run time is bound by the scalar unit, as it is unweighted.)
-template <bool LDS_HIST>
-hipError_t launch_fill_weighted_c3(const SxLaunchShape& sh, const SxSignalDesc* descs, const SxSegment* segs,
-                                   const unsigned* blk_off, hipStream_t s) {
-  using P = StaticProg<SX_SHIFT(1), SX_SCALE(0), SX_RES(0, 3)>;
-  if (sh.tail) return hipErrorInvalidValue;
-  return launch_fill(sh, fill_weighted_kernel<3, 4, LDS_HIST, P>, sh.lds_bytes, false, s, descs, segs, blk_off, sx_fill_w(sh));
-}
-FillLauncher weighted_program_launcher(int prog, int lds_hist) {
-  static const unsigned c3[3] = {SX_SHIFT(1), SX_SCALE(0), SX_RES(0, 3)};
-  if (prog < 0 || prog >= kNumPrograms) return nullptr;
-  const FillEntry& e = kPrograms[prog];
-  if (e.form != kFormRows || e.nobs != 3 || e.nslot != 4 || e.nops != 3 || !std::equal(c3, c3 + 3, e.ops)) return nullptr;
-  return lds_hist ? launch_fill_weighted_c3<true> : launch_fill_weighted_c3<false>;
+  if (weighted && form != kFormRows) return nullptr;
+  return e.fn[sparse_runs ? 2 : lds_hist ? 0 : 1][own ? 0 : weighted ? kPreWeighted : form];
 }
 
 }  // namespace
 
-bool sx_fill_weighted_supports(int prog, int lds_hist) { return weighted_program_launcher(prog, lds_hist) != nullptr; }
+bool sx_fill_weighted_supports(int prog, int lds_hist) {
+  return program_launcher(prog, kFormRows, lds_hist, 0, true) != nullptr;
+}
 
 bool sx_fill_has_specialization(int nobs, int nslot) {
   return nobs >= 1 && nobs <= 5 && nslot >= nobs && nslot <= nobs + 2;
@@ -508,48 +516,27 @@ hipError_t sx_launch_prebin(const SxSignalDesc* d_desc, unsigned long long npad,
 hipError_t sx_launch_fill(const SxLaunchShape& sh, const SxSignalDesc* descs, const SxSegment* segs,
                           const unsigned* blk_off, hipStream_t s) {
   if (sh.grid <= 0) return hipSuccess;
-  if (sh.weighted) {
-    // the weighted kernels: rows form only, the program decoded at run time for this (nobs, nslot), else the generic one
-    if (sh.form != kFormRows || sh.rtc_fill) return hipErrorInvalidValue;
-    if (sh.static_prog >= 0) {   // (the planner asked sx_fill_weighted_supports)
-      const FillLauncher fn = weighted_program_launcher(sh.static_prog, sh.lds_hist);
-      return fn ? fn(sh, descs, segs, blk_off, s) : hipErrorInvalidValue;
-    }
-#define SX_CASE(NO, NS)                                                                                         \
-  if (sh.nobs == NO && sh.nslot == NS)                                                                          \
-    return (sh.lds_hist ? launch_fill_weighted_k<NO, NS, true> : launch_fill_weighted_k<NO, NS, false>)(sh, descs, segs, \
-                                                                                                          blk_off, s);
-    SX_CASE(1, 1) SX_CASE(1, 2) SX_CASE(1, 3)
-    SX_CASE(2, 2) SX_CASE(2, 3) SX_CASE(2, 4)
-    SX_CASE(3, 3) SX_CASE(3, 4) SX_CASE(3, 5)
-    SX_CASE(4, 4) SX_CASE(4, 5) SX_CASE(4, 6)
-    SX_CASE(5, 5) SX_CASE(5, 6) SX_CASE(5, 7)
-#undef SX_CASE
-    if (sh.tail) return hipErrorInvalidValue;
-    return sh.lds_hist ? launch_fill(sh, fill_weighted_kernel_generic<true>, sh.lds_bytes, false, s, descs, segs, blk_off,
-                                     sx_fill_w(sh))
-                       : launch_fill(sh, fill_weighted_kernel_generic<false>, (size_t)64, false, s, descs, segs, blk_off, 0u);
-  }
+  // rows with multiplicities: the rows form only, never specialised at run time, never fused with the step end (the host
+  // asks sx_fill_has_step_form first); its built-in program is the one the planner asked sx_fill_weighted_supports about
+  if (sh.weighted && (sh.form != kFormRows || sh.rtc_fill || sh.tail)) return hipErrorInvalidValue;
   if (sh.rtc_fill) {
     return sx_rtc_launch(sh.rtc_fill, sh.grid, sh.threads, sh.lds_bytes, descs, segs, blk_off, sx_fill_w(sh),
                          (unsigned)sh.debug_mode, s, sh.ev_start, sh.ev_stop);
   }
-  if (sx_form_ordered(sh.form) || (sh.static_prog >= 0 && sh.static_prog < kNumPrograms)) {
-    const FillLauncher fn = program_launcher(sh.static_prog, sh.form, sh.lds_hist, 0);
+  if (sx_form_ordered(sh.form) || (sh.static_prog >= 0 && (sh.weighted || sh.static_prog < kNumPrograms))) {
+    const FillLauncher fn = program_launcher(sh.static_prog, sh.form, sh.lds_hist, 0, sh.weighted);
     return fn ? fn(sh, descs, segs, blk_off, s) : hipErrorInvalidValue;
   }
-#define SX_CASE(NO, NS)                                                                                  \
-  if (sh.nobs == NO && sh.nslot == NS)                                                                   \
-    return (sh.lds_hist ? launch_fill_k<NO, NS, true, DynamicProg> : launch_fill_k<NO, NS, false, DynamicProg>)( \
-        sh, descs, segs, blk_off, s);
+#define SX_CASE(NO, NS) \
+  if (sh.nobs == NO && sh.nslot == NS) return decoded_launcher<NO, NS>(sh.lds_hist, sh.weighted)(sh, descs, segs, blk_off, s);
   SX_CASE(1, 1) SX_CASE(1, 2) SX_CASE(1, 3)
   SX_CASE(2, 2) SX_CASE(2, 3) SX_CASE(2, 4)
   SX_CASE(3, 3) SX_CASE(3, 4) SX_CASE(3, 5)
   SX_CASE(4, 4) SX_CASE(4, 5) SX_CASE(4, 6)
   SX_CASE(5, 5) SX_CASE(5, 6) SX_CASE(5, 7)
 #undef SX_CASE
-  return sh.lds_hist ? launch_fill(sh, fill_kernel_generic<true>, sh.lds_bytes, false, s, descs, segs, blk_off, sx_fill_w(sh))
-                     : launch_fill(sh, fill_kernel_generic<false>, (size_t)64, false, s, descs, segs, blk_off, 0u);
+  return sh.weighted ? launch_fill_generic<true>(sh, descs, segs, blk_off, s)
+                     : launch_fill_generic<false>(sh, descs, segs, blk_off, s);
 }
 
 hipError_t sx_launch_zero(const SxSignalDesc* d_descs, int nsig, int max_bins, unsigned* ticket, hipStream_t s) {

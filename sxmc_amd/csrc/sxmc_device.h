@@ -109,8 +109,8 @@ struct SxLaunchShape {
   // to the kernel by value) and the extra workgroups (finisher + workers) appended to the grid; null: the fill alone
   const void* tail = nullptr;
   int tail_blocks = 0;
-  // the members carry sample multiplicities (sxmc_hist_set_sample_multiplicities): fill_weighted_kernel over the rows form,
-  // its one built-in program (static_prog >= 0: sx_fill_weighted_supports), else the program decoded at run time or the
+  // the members carry sample multiplicities (sxmc_hist_set_sample_multiplicities): fill_kernel<..., kPreWeighted> over the rows
+  // form, its one built-in program (static_prog >= 0: sx_fill_weighted_supports), else the program decoded at run time or the
   // shape-agnostic kernel; no run-time specialisation, no form fused with the step end
   int weighted = 0;
 };
@@ -193,8 +193,8 @@ bool sx_fill_has_specialization(int nobs, int nslot);
 // `prog` has a kernel for this form and histogram mode (sparse_runs: the event-bin counters over a bucketed table's runs).
 int sx_fill_find_program(int form, int nobs, int nslot, int nops, const unsigned* ops);
 bool sx_fill_supports(int prog, int form, int lds_hist, int sparse_runs);
-// Has the WEIGHTED fill (fill_weighted.inc.h, rows form) a straight-line kernel for built-in program `prog`?  (One has:
-// BASELINE config 3's.)  Otherwise a weighted launch decodes its program at run time.
+// Has the WEIGHTED fill (fill_body with PREW = kPreWeighted, rows form) a straight-line kernel for built-in program `prog`?
+// (The registry says: one has, BASELINE config 3's.)  Otherwise a weighted launch decodes its program at run time.
 bool sx_fill_weighted_supports(int prog, int lds_hist);
 hipError_t sx_launch_prebin(const SxSignalDesc* d_desc, unsigned long long npad, unsigned mask, int width, void* out,
                             hipStream_t s);

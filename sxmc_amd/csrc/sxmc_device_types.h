@@ -82,7 +82,7 @@ struct SxSignalDesc {
   short coef_par[64];            // coefficient lane -> parameter index
   const void* pre;               // pre-binned column of the observables no systematic writes (or null); for a
                                  // bucketed table: one bin offset per 256-sample granule; for a WEIGHTED launch
-                                 // (fill_weighted.inc.h: rows form, nothing pre-binned): the rows' multiplicities, one
+                                 // (fill_body, PREW = kPreWeighted: rows form, nothing pre-binned): the rows' multiplicities, one
                                  // `unsigned` per row, 0 in the padding up to col_pitch
   const float* edges;           // bucketed table with an ORDERED observable (fill_ordered_kernel): per granule the
                                  // observable's value in the granule's first and last row; its geometry sits at

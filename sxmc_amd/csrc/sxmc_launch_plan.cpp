@@ -540,8 +540,8 @@ int plan_bucketed(sxmc_group* g, const PlanConfig& cfg, LaunchPlan& plan, int i,
 }
 
 // The table as it is: rows, or with the observables no systematic writes pre-binned.
-// `weighted` (the member carries sample multiplicities): rows only, the weighted fill's own straight-line kernel where it
-// has one for the program, else the program decoded at run time by the weighted kernel of this (nobs, nslot) or the
+// `weighted` (the member carries sample multiplicities): rows only, the straight-line kernel where the registry has a
+// weighted one for the program, else the program decoded at run time by the weighted kernel of this (nobs, nslot) or the
 // shape-agnostic one -- no run-time specialisation, nothing pre-binned.
 MemberPlan plan_rows(sxmc_group* g, const PlanConfig& cfg, const SxSignalDesc& d, const sxplan::SystUse& use, int lds_hist,
                      bool weighted = false) {
@@ -554,7 +554,7 @@ MemberPlan plan_rows(sxmc_group* g, const PlanConfig& cfg, const SxSignalDesc& d
   k.shape.nslot = spec ? d.nslot : 0;
   k.prog = sxplan::prog_words(d);
   if (weighted) {
-    // (the weighted fill's own straight-line kernels, where it has one for the program; the class is then keyed by it)
+    // (the registry's weighted straight-line kernels, where the program has them; the class is then keyed by it)
     const int wsp = (spec && use.specialisable)
                         ? sx_fill_find_program(kFormRows, k.shape.nobs, k.shape.nslot, (int)k.prog.size(), k.prog.data())
                         : -1;
