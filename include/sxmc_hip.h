@@ -325,6 +325,69 @@ int sxmc_kde_sensitivity(sxmc_kde_t k, double* sensitivity);
 /* lambda[0 .. nsamples): the factors fixed at creation, in table order; all 1.0 for a fixed-bandwidth evaluator.
  * n must be nsamples. */
 int sxmc_kde_local_factors(sxmc_kde_t k, double* lambda, size_t n);
+/* WEIGHTED MONTE CARLO SAMPLES in the kernel-density evaluator: sxmc_kde_create_adaptive with one integer MULTIPLICITY
+ * m_i per table row (host memory), the fixed-point weights sxmc_sample_multiplicities makes -- as for
+ * sxmc_hist_set_sample_multiplicities, the norm stays an `unsigned` (equal to a weighted histogram evaluator's, bit for
+ * bit) and the scale 2^k cancels wherever norm and n_mc meet.  multiplicities == NULL IS sxmc_kde_create_adaptive.  An
+ * evaluator without multiplicities launches the kernels it launched before they existed; with them only the prepass, the
+ * sampler's pick, the projection's preparation and the pilot's combine are siblings of their own, and the pair sum, the
+ * cutoff's gather and culled pair sum and the combine are the same code, because the multiplicity is folded into the
+ * row's weight.  THE LAWS (restated in numpy by tests/kde_weighted_reference.py):
+ *   construction  multiplicities are given here and cannot be set afterwards (bandwidths, pilot and padding are fixed
+ *                 here).  nmultiplicities must be the table's row count (SXMC_ERR_INVALID, by name); their total over
+ *                 all rows must be <= 2^32 - 1 (SXMC_ERR_INVALID).  The library keeps its own device copy, padded with 0
+ *                 to the padded row count; evaluators made by sxmc_kde_create_shared share it.
+ *   bandwidths    on the host in f64 before anything is allocated on the device (sxmc_amd/csrc/kde_weights.h; also
+ *                 sxmc_kde_weighted_bandwidths below), over the untransformed in-domain rows in table order, one
+ *                 rounding per operation, sums sequential:
+ *                   S1 = sum m_i, S2 = sum m_i^2 as exact integers (S2 in 128 bits), each converted to double once;
+ *                   n_eff = S1 * (S1 / S2)  (Kish);  mu_d = (sum (double)m_i * x_id) / S1;
+ *                   V_d = sum (double)m_i * (dx * dx), dx = x_id - mu_d;  sigma_d = sqrt(V_d / (S1 - S2 / S1));
+ *                   h_d = scale_d * sigma_d * pow(n_eff, -1/(D+4)).
+ *                 Refused by name (SXMC_ERR_INVALID): fewer than 2 in-domain rows with m > 0, S1 - S2 / S1 not positive,
+ *                 sigma_d == 0.  A power-of-two rescaling of every m gives the same bytes (all m == 8: the unweighted
+ *                 evaluator's); a bandwidth does not depend on the quantiser's k.
+ *   evaluation    norm = sum of m_i over the rows that pass the domain test after the systematics (integer atomics).
+ *                 The prepass stores the row's weight as (float)((double)m_i / mass_i), adaptive evaluators
+ *                 (float)((double)m_i / (mass_i * lambda_i^D)); 0 outside the domain or when m_i == 0 -- such a row then
+ *                 drops out of the cutoff's tile boxes and of the sampler's pool by the tests those make on the weight.
+ *                 pdf(x) = prefactor / norm * sum_i m_i w_i prod_d phi(...).  Point codes, NaN rules, do_eval_pdf = 0
+ *                 unchanged.  The four multiplicities of a lane's rows are one 16-byte load.
+ *   sampling      T = norm.  C_j: the inclusive prefix sums of the multiplicities of the in-domain rows with m > 0, in
+ *                 table order.  An attempt's first Philox word picks target = (word * T) >> 32 in 64 bits and the row
+ *                 picked is the first whose C_j exceeds target; everything after the pick is sxmc_kde_random_sample's.
+ *                 sxmc_kde_sample_pool answers the number of in-domain rows with m > 0.
+ *   projection    a row's reciprocal mass is multiplied by (double)m_i and m_i is counted:
+ *                 h_prob[j] = (1/norm) sum_i m_i [...]; the lane-per-bin kernel and the combine are unchanged.
+ *   pilot         f_i = prefactor / S1 * sum_j m_j w_j prod phi(...) over the in-domain rows in table order (the host
+ *                 hands m_j / mass_j as the row's weight and S1 in place of n); g = exp((sum (double)m_i * ln f_i) / S1)
+ *                 over the in-domain rows (a row with m_i == 0 adds nothing and its f_i is not read); lambda_i as for
+ *                 sxmc_kde_create_adaptive, for every row.
+ * Not built, refused by name: cross-validation of such an evaluator (sxmc_kde_cv_scores, sxmc_kde_cv_select:
+ * SXMC_ERR_STATE). */
+int sxmc_kde_create_weighted(const float* samples, size_t nsamples_floats, int samples_on_device,
+                             int nfields, int nobservables,
+                             const double* lower, size_t n_lower,
+                             const double* upper, size_t n_upper,
+                             const double* bandwidth_scale, size_t n_bandwidth_scale,
+                             unsigned dataset, double sensitivity,
+                             const unsigned* multiplicities, size_t nmultiplicities, sxmc_kde_t* out);
+/* sum m_i over all rows, or the row count when no multiplicities are set: what n_mc is for either kind. */
+int sxmc_kde_sample_total(sxmc_kde_t k, unsigned long long* total);
+/* The multiplicities back on the host, n = the row count; all 1 when none are set (*is_set, optional, says which;
+ * h_m NULL with n 0 asks that question alone). */
+int sxmc_kde_get_sample_multiplicities(sxmc_kde_t k, unsigned* h_m, size_t n, int* is_set);
+/* n_eff of the bandwidths, or the in-domain row count n when no multiplicities are set. */
+int sxmc_kde_effective_samples(sxmc_kde_t k, double* n_eff);
+/* The bandwidth law above on the host alone: no device call, usable without a GPU.  samples: the row-major table on the
+ * host; multiplicities NULL: every row counts once (the unweighted rule's bytes).  Outputs, each optional: h, sigma, mean
+ * [nobservables]; n_eff, s1, s2 (the two sums as doubles; written even when the table is then refused).  Validation and
+ * refusals as at creation. */
+int sxmc_kde_weighted_bandwidths(const float* samples, size_t nsamples_floats, int nfields, int nobservables,
+                                 const double* lower, size_t n_lower, const double* upper, size_t n_upper,
+                                 const double* bandwidth_scale, size_t n_bandwidth_scale,
+                                 const unsigned* multiplicities, size_t nmultiplicities,
+                                 double* h, double* sigma, double* mean, double* n_eff, double* s1, double* s2);
 /* A second evaluator over the SAME sample table as `base` (as sxmc_hist_create_shared: the table is shared and reference
  * counted, nothing is copied): systematics, bandwidths, prefactor and (adaptive) the sensitivity and the factors copied
  * from `base`, never recomputed; own rows, evaluation points, bindings, partial sums and stream.  For concurrent

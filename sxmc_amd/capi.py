@@ -112,6 +112,11 @@ SIGNATURES = {
     "sxmc_hist_launch_info": [_vp, C.c_char_p, _sz],
     "sxmc_kde_create": [_vp, _sz, _i, _i, _i, _vp, _sz, _vp, _sz, _vp, _sz, _u, _pvp],
     "sxmc_kde_create_adaptive": [_vp, _sz, _i, _i, _i, _vp, _sz, _vp, _sz, _vp, _sz, _u, _d, _pvp],
+    "sxmc_kde_create_weighted": [_vp, _sz, _i, _i, _i, _vp, _sz, _vp, _sz, _vp, _sz, _u, _d, _vp, _sz, _pvp],
+    "sxmc_kde_sample_total": [_vp, C.POINTER(C.c_ulonglong)],
+    "sxmc_kde_get_sample_multiplicities": [_vp, _vp, _sz, _pi],
+    "sxmc_kde_effective_samples": [_vp, _pd],
+    "sxmc_kde_weighted_bandwidths": [_vp, _sz, _i, _i, _vp, _sz, _vp, _sz, _vp, _sz, _vp, _sz, _vp, _vp, _vp, _pd, _pd, _pd],
     "sxmc_kde_sensitivity": [_vp, _pd],
     "sxmc_kde_local_factors": [_vp, _vp, _sz],
     "sxmc_kde_destroy": [_vp],

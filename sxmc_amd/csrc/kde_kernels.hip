@@ -30,6 +30,13 @@
 // A cutoff radius (sxmc_kde_set_cutoff, R > 0) puts kde_cutoff_gather between the prepass and the pair sum, replaces
 // the latter by kde_pairs_cutoff (both after kde_combine below; the pure parts in kde_cutoff.h) and gives kde_combine
 // the order of the sorted points.  At R = 0 neither runs and kde_combine takes no order.
+//
+// Weighted Monte Carlo samples (sxmc_kde_create_weighted: one integer multiplicity m_i per table row) fold m_i into the
+// row's weight in the prepass, so kde_pairs, kde_pairs_cutoff, kde_cutoff_gather and kde_combine are the same code for
+// them.  What reads multiplicities is an instantiation or a sibling of its own, made from the one source by a
+// compile-time WEIGHTED -- kde_prepass, kde_project_prep and kde_sample (with kde_mflag) over a KdeMult / KdePick,
+// kde_pilot_combine_weighted: an evaluator without multiplicities launches the kernels it launched before them,
+// instruction for instruction.
 #include <hip/hip_runtime.h>
 
 #include <type_traits>
@@ -70,8 +77,31 @@ hipError_t kde_for_dim_adapt(int D, bool adaptive, F&& f) {
   return kde_for_dim(D, [&](auto dim) { return adaptive ? f(dim, std::true_type{}) : f(dim, std::false_type{}); });
 }
 
-template <int NSLOT, bool ADAPT>
-__global__ __launch_bounds__(kKdeBlock) void kde_prepass_kernel(const SxSignalDesc d, const SxKdeArgs a) {
+// Weightedness is a compile-time fact of a kernel below, carried by a trailing argument pack: empty for an evaluator
+// without multiplicities -- whose instantiation then has the arguments, the kernel-argument layout and the instructions
+// it had before weights existed -- or one KdeMult (the sampler: one KdePick).  WEIGHTED = the pack is not empty.
+struct KdeMult {
+  const unsigned* __restrict__ p;   // [npad] the rows' multiplicities, 0 in the padding
+};
+template <class T>
+__device__ __forceinline__ const T& kde_only(const T& t) {
+  return t;
+}
+// ... and nothing else: no element, or exactly one of type T
+template <class T, class... PACK>
+constexpr bool kde_pack_is() {
+  return sizeof...(PACK) == 0 || (sizeof...(PACK) == 1 && (std::is_same<T, PACK>::value && ...));
+}
+
+// The prepass, written once.  WEIGHTED (sxmc_kde_create_weighted; `mult`: [npad] the rows' multiplicities, 0 in the
+// padding, else unused): a row counts m_i in the norm and its weight is (float)((double)m_i / mass) -- the multiplicity
+// folded into the number the pair sum multiplies by, so that nothing after the prepass knows of it.  The four
+// multiplicities of a lane's SXMC_VEC rows come in one 16-byte load.
+template <int NSLOT, bool ADAPT, class... MULT>
+__global__ __launch_bounds__(kKdeBlock) void kde_prepass_kernel(const SxSignalDesc d, const SxKdeArgs a,
+                                                                const MULT... mult) {
+  static_assert(kde_pack_is<KdeMult, MULT...>(), "the pack is empty or one KdeMult");
+  constexpr bool WEIGHTED = sizeof...(MULT) == 1;
   const unsigned tid = threadIdx.x;
   const unsigned lane = tid & (kWave - 1);
   const unsigned long long v = (unsigned long long)blockIdx.x * kKdeBlock + tid;
@@ -89,6 +119,17 @@ __global__ __launch_bounds__(kKdeBlock) void kde_prepass_kernel(const SxSignalDe
   for (int s = 0; s < d.nsyst; s++) apply_op<NSLOT>(f, pack_opword(d.syst[s]), coef);
 
   constexpr int D = NSLOT < SXMC_KDE_MAX_DIM ? NSLOT : SXMC_KDE_MAX_DIM;
+  unsigned mq[SXMC_VEC] = {0u, 0u, 0u, 0u};   // (WEIGHTED) what each of the lane's rows counts for
+  if constexpr (WEIGHTED) {
+    static_assert(SXMC_VEC == 4, "one 16-byte load of multiplicities per lane");
+    // (lanes past the padded rows read unit 0: their rows fail the domain test)
+    const unsigned long long vm = v < a.npad / SXMC_VEC ? v : 0ull;
+    const uint4 m4 = *reinterpret_cast<const uint4*>(kde_only(mult...).p + vm * SXMC_VEC);
+    mq[0] = m4.x;
+    mq[1] = m4.y;
+    mq[2] = m4.z;
+    mq[3] = m4.w;
+  }
   unsigned cnt = 0;
 #pragma unroll
   for (int q = 0; q < SXMC_VEC; q++) {
@@ -99,7 +140,8 @@ __global__ __launch_bounds__(kKdeBlock) void kde_prepass_kernel(const SxSignalDe
     for (int k = 0; k < D; k++) {
       if (k < d.nobs) in = in && (f[k][q] >= a.lower[k]) && (f[k][q] < a.upper[k]);
     }
-    cnt += in ? 1u : 0u;
+    if constexpr (WEIGHTED) cnt += in ? mq[q] : 0u;
+    else cnt += in ? 1u : 0u;
     if (i < a.npad) {
       double mass = 1.0;
       float* row = a.rows + i * (unsigned long long)(d.nobs + (ADAPT ? 2 : 1));
@@ -117,11 +159,13 @@ __global__ __launch_bounds__(kKdeBlock) void kde_prepass_kernel(const SxSignalDe
         mass = mass * sxkde::truncation_mass(x, a.lower[k], a.upper[k], r);
         row[k] = in ? (float)((x - a.lower[k]) * a.cscale[k]) : 0.0f;
       }
+      double one = 1.0;   // the numerator of the row's weight: (WEIGHTED) its multiplicity, 0 leaving the weight 0
+      if constexpr (WEIGHTED) one = (double)mq[q];
       if constexpr (ADAPT) {
         row[d.nobs] = (float)(1.0 / (lam * lam));
-        row[d.nobs + 1] = in ? (float)(1.0 / (mass * lam_pow)) : 0.0f;
+        row[d.nobs + 1] = in ? (float)(one / (mass * lam_pow)) : 0.0f;
       } else {
-        row[d.nobs] = in ? (float)(1.0 / mass) : 0.0f;
+        row[d.nobs] = in ? (float)(one / mass) : 0.0f;
       }
     }
   }
@@ -335,14 +379,22 @@ __global__ __launch_bounds__(kKdeBlock) void kde_pairs_cutoff_kernel(const float
 
 }  // namespace
 
-hipError_t sx_kde_prepass(const SxSignalDesc& d, const SxKdeArgs& a, hipStream_t s) {
+hipError_t sx_kde_prepass(const SxSignalDesc& d, const SxKdeArgs& a, const unsigned* mult, hipStream_t s) {
   const unsigned long long nvec = a.npad / SXMC_VEC;
   const unsigned grid = (unsigned)((nvec + kKdeBlock - 1) / kKdeBlock);
   if (grid == 0) return hipSuccess;
   return kde_for_range<7>(d.nslot, [&](auto nslot) {
     constexpr int N = decltype(nslot)::value;
-    if (a.lambda) hipLaunchKernelGGL((kde_prepass_kernel<N, true>), dim3(grid), dim3(kKdeBlock), 0, s, d, a);
-    else hipLaunchKernelGGL((kde_prepass_kernel<N, false>), dim3(grid), dim3(kKdeBlock), 0, s, d, a);
+    const dim3 g(grid), b(kKdeBlock);
+    if (mult) {
+      const KdeMult m{mult};
+      if (a.lambda) hipLaunchKernelGGL((kde_prepass_kernel<N, true, KdeMult>), g, b, 0, s, d, a, m);
+      else hipLaunchKernelGGL((kde_prepass_kernel<N, false, KdeMult>), g, b, 0, s, d, a, m);
+    } else if (a.lambda) {
+      hipLaunchKernelGGL((kde_prepass_kernel<N, true>), g, b, 0, s, d, a);
+    } else {
+      hipLaunchKernelGGL((kde_prepass_kernel<N, false>), g, b, 0, s, d, a);
+    }
     return hipGetLastError();
   });
 }
@@ -415,13 +467,37 @@ __global__ __launch_bounds__(kKdeBlock) void kde_scatter_kernel(const unsigned* 
 __device__ __forceinline__ double kde_phi(double z) { return 0.5 * erfc(-z * 0.70710678118654752); }
 __device__ __forceinline__ double kde_phi_inv(double p) { return -1.4142135623730950 * erfcinv(2.0 * p); }
 
-template <int D, bool ADAPT>
+// (WEIGHTED) the multiplicities' scan: one lane per row, m_i where the last evaluation left the row a weight > 0, else 0
+__global__ __launch_bounds__(kKdeBlock) void kde_mflag_kernel(const float* __restrict__ rows, int rowlen,
+                                                              unsigned long long npad,
+                                                              const unsigned* __restrict__ mult,
+                                                              unsigned* __restrict__ flag) {
+  const unsigned long long i = (unsigned long long)blockIdx.x * kKdeBlock + threadIdx.x;
+  if (i >= npad) return;
+  flag[i] = rows[i * (unsigned long long)rowlen + (unsigned long long)(rowlen - 1)] > 0.0f ? mult[i] : 0u;
+}
+
+// What a WEIGHTED sampler picks from (its trailing argument, as KdeMult above): cum = C, the inclusive prefix sum over
+// all npad rows of the live rows' multiplicities.
+struct KdePick {
+  const unsigned* __restrict__ cum;
+  unsigned npad;
+};
+
+// The sampler, written once.  Unweighted: idx lists the n in-domain rows and the first word picks place (word n) >> 32.
+// WEIGHTED: idx is unused and n is T, the last entry of C (the norm, <= 2^32 - 1: the 64-bit product cannot wrap);
+// target = (word T) >> 32 < T and the row picked is the first whose C exceeds target -- a live row, since C only grows
+// there.
+template <int D, bool ADAPT, class... PICK>
 __global__ __launch_bounds__(kKdeBlock) void kde_sample_kernel(const float* __restrict__ rows,
                                                                const double* __restrict__ lambda,
                                                                const unsigned* __restrict__ idx, unsigned n,
                                                                const SxKdeSampleArgs g, unsigned long long seed,
                                                                unsigned long long nevents, float* __restrict__ out,
-                                                               unsigned* __restrict__ exhausted) {
+                                                               unsigned* __restrict__ exhausted,
+                                                               const PICK... pick) {
+  static_assert(kde_pack_is<KdePick, PICK...>(), "the pack is empty or one KdePick");
+  constexpr bool WEIGHTED = sizeof...(PICK) == 1;
   const unsigned long long step = (unsigned long long)gridDim.x * kKdeBlock;
   for (unsigned long long e = (unsigned long long)blockIdx.x * kKdeBlock + threadIdx.x; e < nevents; e += step) {
     float x[D];
@@ -430,7 +506,20 @@ __global__ __launch_bounds__(kKdeBlock) void kde_sample_kernel(const float* __re
       const sxdev::Philox4 r0 = sxdev::philox4x32_10(e, 2ull * attempt, seed);
       const sxdev::Philox4 r1 = sxdev::philox4x32_10(e, 2ull * attempt + 1ull, seed);
       const unsigned u[4] = {r0.y, r0.z, r0.w, r1.x};
-      const unsigned i = idx[(unsigned)(((unsigned long long)r0.x * n) >> 32)];   // uniform over the n rows
+      unsigned i;
+      if constexpr (WEIGHTED) {
+        const unsigned target = (unsigned)(((unsigned long long)r0.x * n) >> 32);   // < T
+        const KdePick& c = kde_only(pick...);
+        unsigned lo = 0u, hi = c.npad - 1u;   // (C[npad - 1] = T > target: the search ends inside the table)
+        while (lo < hi) {
+          const unsigned mid = lo + (hi - lo) / 2u;
+          if (c.cum[mid] > target) hi = mid;
+          else lo = mid + 1u;
+        }
+        i = lo;
+      } else {
+        i = idx[(unsigned)(((unsigned long long)r0.x * n) >> 32)];   // uniform over the n rows
+      }
       const float* row = rows + (unsigned long long)i * (D + (ADAPT ? 2 : 1));
       double lam = 1.0;   // (ADAPT) the picked row's factor on every bandwidth
       if constexpr (ADAPT) lam = lambda[i];
@@ -503,6 +592,32 @@ hipError_t sx_kde_sample(int D, const float* rows, const double* lambda, const u
   });
 }
 
+// cum[0 .. npad): the inclusive prefix sum of the live rows' multiplicities, in table order
+hipError_t sx_kde_weighted_scan(const float* rows, int rowlen, unsigned long long npad, const unsigned* mult,
+                                unsigned* flag, unsigned* cum, void* temp, size_t temp_bytes, hipStream_t s) {
+  if (npad == 0) return hipSuccess;
+  const unsigned grid = (unsigned)((npad + kKdeBlock - 1) / kKdeBlock);
+  hipLaunchKernelGGL(kde_mflag_kernel, dim3(grid), dim3(kKdeBlock), 0, s, rows, rowlen, npad, mult, flag);
+  const hipError_t e = hipGetLastError();
+  if (e != hipSuccess) return e;
+  return sx_inclusive_sum_u32(flag, cum, (int)npad, temp, temp_bytes, s);
+}
+
+hipError_t sx_kde_sample_weighted(int D, const float* rows, const double* lambda, const unsigned* cum, unsigned total,
+                                  unsigned long long npad, const SxKdeSampleArgs& g, unsigned long long seed,
+                                  unsigned long long nevents, float* out, unsigned* exhausted, hipStream_t s) {
+  if (nevents == 0) return hipSuccess;
+  if (total == 0u || npad == 0 || npad > 0x7FFFFFFFull) return hipErrorInvalidValue;
+  const unsigned long long b = (nevents + kKdeBlock - 1) / kKdeBlock;
+  const dim3 grid((unsigned)(b < 4096 ? b : 4096));
+  return kde_for_dim_adapt(D, lambda != nullptr, [&](auto dim, auto adapt) {
+    const KdePick pick{cum, (unsigned)npad};
+    hipLaunchKernelGGL((kde_sample_kernel<decltype(dim)::value, decltype(adapt)::value, KdePick>), grid, dim3(kKdeBlock),
+                       0, s, rows, lambda, (const unsigned*)nullptr, total, g, seed, nevents, out, exhausted, pick);
+    return hipGetLastError();
+  });
+}
+
 // ------------------------------------------------------------------------------------ projection (sxmc_kde_project)
 // The share of the PDF of the last evaluation in each of nbins equal bins of one observable: the kernel of an in-domain
 // sample is a product of truncated Gaussians, the other observables integrate to their own truncation mass, and what is
@@ -517,11 +632,15 @@ namespace {
 
 // ADAPT (an adaptive evaluator): rows of D + 2 floats, and per sample three scratch doubles -- u, the reciprocal mass
 // taken at the sample's own bandwidth h lambda, and 1 / lambda, which scales every distance of the kernel below.
-template <bool ADAPT>
+// WEIGHTED (`mult`: [npad] the rows' multiplicities): a live row's reciprocal mass times (double)m_i, and m_i counted.
+template <bool ADAPT, class... MULT>
 __global__ __launch_bounds__(kKdeBlock) void kde_project_prep_kernel(const float* __restrict__ rows,
                                                                      const SxKdeProjectArgs a,
                                                                      double* __restrict__ scratch,
-                                                                     unsigned* __restrict__ count) {
+                                                                     unsigned* __restrict__ count,
+                                                                     const MULT... mult) {
+  static_assert(kde_pack_is<KdeMult, MULT...>(), "the pack is empty or one KdeMult");
+  constexpr bool WEIGHTED = sizeof...(MULT) == 1;
   const unsigned long long i = (unsigned long long)blockIdx.x * kKdeBlock + threadIdx.x;
   unsigned in = 0u;
   if (i < a.npad) {
@@ -535,6 +654,10 @@ __global__ __launch_bounds__(kKdeBlock) void kde_project_prep_kernel(const float
       const double T = (a.upper - a.lower) / a.h;
       if constexpr (ADAPT) inv = 1.0 / (kde_phi((T - u) * il) - kde_phi(-u * il));
       else inv = 1.0 / (kde_phi(T - u) - kde_phi(-u));
+      if constexpr (WEIGHTED) {
+        in = kde_only(mult...).p[i];
+        inv = inv * (double)in;
+      }
     }
     if constexpr (ADAPT) {
       scratch[3ull * i] = u;
@@ -601,8 +724,8 @@ __global__ __launch_bounds__(kKdeBlock) void kde_project_combine_kernel(const Sx
 
 }  // namespace
 
-hipError_t sx_kde_project(const float* rows, const SxKdeProjectArgs& a, double* scratch, unsigned* count, double* d_prob,
-                          hipStream_t s) {
+hipError_t sx_kde_project(const float* rows, const SxKdeProjectArgs& a, const unsigned* mult, double* scratch,
+                          unsigned* count, double* d_prob, hipStream_t s) {
   if (a.nbins < 1 || a.npad == 0 || a.obs < 0 || a.obs >= a.D || a.rows_per_split == 0 ||
       (unsigned long long)a.nsplit * a.rows_per_split < a.npad || a.pitch % SXMC_KDE_PROJ_LANES != 0 ||
       a.pitch < (unsigned long long)a.nbins) {
@@ -610,8 +733,16 @@ hipError_t sx_kde_project(const float* rows, const SxKdeProjectArgs& a, double* 
   }
   double* part = scratch + (a.lambda ? 3ull : 2ull) * a.npad;
   const dim3 prep((unsigned)((a.npad + kKdeBlock - 1) / kKdeBlock));
-  if (a.lambda) hipLaunchKernelGGL(kde_project_prep_kernel<true>, prep, dim3(kKdeBlock), 0, s, rows, a, scratch, count);
-  else hipLaunchKernelGGL(kde_project_prep_kernel<false>, prep, dim3(kKdeBlock), 0, s, rows, a, scratch, count);
+  const dim3 pb(kKdeBlock);
+  if (mult) {
+    const KdeMult m{mult};
+    if (a.lambda) hipLaunchKernelGGL((kde_project_prep_kernel<true, KdeMult>), prep, pb, 0, s, rows, a, scratch, count, m);
+    else hipLaunchKernelGGL((kde_project_prep_kernel<false, KdeMult>), prep, pb, 0, s, rows, a, scratch, count, m);
+  } else if (a.lambda) {
+    hipLaunchKernelGGL(kde_project_prep_kernel<true>, prep, pb, 0, s, rows, a, scratch, count);
+  } else {
+    hipLaunchKernelGGL(kde_project_prep_kernel<false>, prep, pb, 0, s, rows, a, scratch, count);
+  }
   hipError_t e = hipGetLastError();
   if (e != hipSuccess) return e;
   const dim3 grid((unsigned)(a.pitch / SXMC_KDE_PROJ_LANES), a.nsplit);
@@ -666,10 +797,22 @@ __global__ __launch_bounds__(kKdeBlock) void kde_pilot_combine_kernel(const SxKd
   f[i] = s * a.prefactor / (double)a.n;
 }
 
+// ... over weighted samples: the host hands m_j / mass_j as a row's weight and the multiplicities' total S1 stands in
+// place of n (a sibling of the combine above; kde_pilot_kernel is the same for both)
+__global__ __launch_bounds__(kKdeBlock) void kde_pilot_combine_weighted_kernel(const SxKdePilotArgs a,
+                                                                               const double* __restrict__ part,
+                                                                               double* __restrict__ f, double total) {
+  const unsigned long long i = (unsigned long long)blockIdx.x * kKdeBlock + threadIdx.x;
+  if (i >= a.pitch) return;
+  double s = 0.0;
+  for (unsigned k = 0; k < a.nsplit; k++) s += part[(unsigned long long)k * a.pitch + i];
+  f[i] = s * a.prefactor / total;
+}
+
 }  // namespace
 
-hipError_t sx_kde_pilot(const SxKdePilotArgs& a, const double* x, const double* s0, double* part, double* f,
-                        hipStream_t s) {
+hipError_t sx_kde_pilot(const SxKdePilotArgs& a, const double* x, const double* s0, double total, double* part,
+                        double* f, hipStream_t s) {
   if (a.pitch == 0 || a.pitch % kKdeBlock != 0 || a.n == 0 || a.per_split == 0 ||
       (unsigned long long)a.nsplit * a.per_split < a.n) {
     return hipErrorInvalidValue;
@@ -680,7 +823,9 @@ hipError_t sx_kde_pilot(const SxKdePilotArgs& a, const double* x, const double* 
     return hipGetLastError();
   });
   if (e != hipSuccess) return e;
-  hipLaunchKernelGGL(kde_pilot_combine_kernel, dim3((unsigned)(a.pitch / kKdeBlock)), dim3(kKdeBlock), 0, s, a, part, f);
+  const dim3 rows_grid((unsigned)(a.pitch / kKdeBlock));
+  if (total > 0.0) hipLaunchKernelGGL(kde_pilot_combine_weighted_kernel, rows_grid, dim3(kKdeBlock), 0, s, a, part, f, total);
+  else hipLaunchKernelGGL(kde_pilot_combine_kernel, rows_grid, dim3(kKdeBlock), 0, s, a, part, f);
   return hipGetLastError();
 }
 

@@ -268,7 +268,9 @@ struct SxKdeArgs {
   // same coordinates, 1 / lambda^2 and weight / lambda^D, the mass taken at h lambda.
   const double* lambda;
 };
-hipError_t sx_kde_prepass(const SxSignalDesc& d, const SxKdeArgs& a, hipStream_t s);
+// mult: [npad] the rows' multiplicities, 0 in the padding (sxmc_kde_create_weighted: a row counts m_i in the norm and
+// its weight is m_i / mass), or null: the kernels of an evaluator without them.
+hipError_t sx_kde_prepass(const SxSignalDesc& d, const SxKdeArgs& a, const unsigned* mult, hipStream_t s);
 // pts: [D][pitch] scaled point coordinates, pitch a multiple of 256; part: [nsplit][pitch]; adaptive: rows of D + 2
 // floats (an adaptive evaluator's prepass)
 hipError_t sx_kde_pairs(int D, bool adaptive, const float* pts, unsigned long long pitch, const float* rows,
@@ -311,6 +313,14 @@ hipError_t sx_inclusive_sum_u32(const unsigned* d_in, unsigned* d_out, int n, vo
 hipError_t sx_kde_sample(int D, const float* rows, const double* lambda, const unsigned* idx, unsigned n,
                          const SxKdeSampleArgs& g, unsigned long long seed, unsigned long long nevents, float* out,
                          unsigned* exhausted, hipStream_t s);
+// ... over weighted samples: cum = the inclusive prefix sum over all npad rows of m_i where the last evaluation left
+// row i a weight > 0 (flag: scratch, [npad]); total = cum[npad - 1] > 0; an event's first word picks
+// target = (word * total) >> 32 and the first row whose cum exceeds it.
+hipError_t sx_kde_weighted_scan(const float* rows, int rowlen, unsigned long long npad, const unsigned* mult,
+                                unsigned* flag, unsigned* cum, void* temp, size_t temp_bytes, hipStream_t s);
+hipError_t sx_kde_sample_weighted(int D, const float* rows, const double* lambda, const unsigned* cum, unsigned total,
+                                  unsigned long long npad, const SxKdeSampleArgs& g, unsigned long long seed,
+                                  unsigned long long nevents, float* out, unsigned* exhausted, hipStream_t s);
 // Projection onto one observable (sxmc_kde_project; the arithmetic is written out in include/sxmc_hip.h).  scratch:
 // [2 npad] doubles (u and the reciprocal mass of every sample row), then [nsplit][pitch] partial sums, pitch = the bins
 // rounded up to SXMC_KDE_PROJ_LANES; count: the in-domain rows, zero on entry.  rows_per_split sample rows to a
@@ -327,8 +337,9 @@ struct SxKdeProjectArgs {
   const double* lambda;     // an adaptive evaluator's factors, [npad], or null.  With them rows are D + 2 floats and
                             // the per-row scratch is [3 npad]: u, the reciprocal mass at h lambda, 1 / lambda
 };
-hipError_t sx_kde_project(const float* rows, const SxKdeProjectArgs& a, double* scratch, unsigned* count, double* d_prob,
-                          hipStream_t s);
+// mult: [npad] the rows' multiplicities (a live row's reciprocal mass times m_i, the count their sum), or null.
+hipError_t sx_kde_project(const float* rows, const SxKdeProjectArgs& a, const unsigned* mult, double* scratch,
+                          unsigned* count, double* d_prob, hipStream_t s);
 // The pilot of an adaptive evaluator (sxmc_kde_create_adaptive): the fixed-bandwidth PDF at zero systematics at every
 // table row, in f64.  x: [D][pitch] the rows' observables (pitch a multiple of 256, padded with anything finite);
 // s0: [n][D + 1] the in-domain samples and their truncation weights, in table order; part: [nsplit][pitch];
@@ -341,8 +352,10 @@ struct SxKdePilotArgs {
   double h[SXMC_KDE_MAX_DIM];
   double prefactor;         // 1 / ((2 pi)^(D/2) prod h)
 };
-hipError_t sx_kde_pilot(const SxKdePilotArgs& a, const double* x, const double* s0, double* part, double* f,
-                        hipStream_t s);
+// total: 0, or (weighted samples: s0's weights are m_j / mass_j) the multiplicities' total S1, which then divides in
+// place of n.
+hipError_t sx_kde_pilot(const SxKdePilotArgs& a, const double* x, const double* s0, double total, double* part,
+                        double* f, hipStream_t s);
 // One scan of likelihood cross-validation (sxmc_kde_cv_scores): K candidate bandwidth vectors scored on m rows in one
 // pass over the pairs.  KP: K rounded up to a count the pair kernel is built for (sx_kde_cv_padded; the padding weighs
 // 0).  x: [D][pitch] the m rows' observables (pitch a multiple of 256, zeros beyond m); s0: [m][D + KP] per sample its

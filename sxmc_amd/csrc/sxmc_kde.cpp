@@ -13,6 +13,11 @@
 // rows are D + 2 floats and every launch takes its adaptive form.  At sensitivity 0 d_lambda is null and every launch
 // is the fixed-bandwidth one.
 //
+// Weighted Monte Carlo samples (sxmc_kde_create_weighted; the host arithmetic in kde_weights.h): the rows' multiplicities
+// are given at creation, where the bandwidths and the pilot read them, and kept in d_mult, padded with 0 to npad and
+// shared with the table; with them the prepass, the sampler and the projection take their weighted forms.  Without,
+// d_mult is null and every launch is the one it was.
+//
 // A cutoff radius (sxmc_kde_set_cutoff; the pure parts in kde_cutoff.h): the spatial order of the table rows is made on
 // the host when a cutoff is first set and kept on the device (shared evaluators hold the same buffer); the points are
 // planned in the same order by set_eval_points, which keeps the caller's points so that a change of R can plan them
@@ -21,6 +26,7 @@
 #include "sxmc_kde_state.h"
 
 #include "kde_adaptive.h"
+#include "kde_weights.h"
 
 using namespace sxhost;
 
@@ -169,8 +175,12 @@ int plan_points(sxmc_kde* k) {
 
 // The factors of an adaptive evaluator that has its table, bandwidths and npad: the pilot on the device (kde_pilot),
 // then g and lambda on the host in f64 (kde_adaptive.h) and the upload of d_lambda.  rows: the untransformed table on
-// the host; inside: its in-domain rows in table order.
-int set_local_factors(sxmc_kde* k, const float* rows, int nfields, const std::vector<size_t>& inside) {
+// the host; inside: its in-domain rows in table order.  m: the rows' multiplicities or null -- with them a row's pilot
+// weight is m_j / mass_j, their in-domain total s1 divides in place of n, and g weighs ln f_i by m_i.  The law sums
+// "over the in-domain rows": a row of multiplicity 0 stays in s0 at weight 0 and adds +0.0 (pairs wasted at
+// construction, the split over workgroups -- from the in-domain count alone -- the same as without multiplicities).
+int set_local_factors(sxmc_kde* k, const float* rows, int nfields, const std::vector<size_t>& inside, const unsigned* m,
+                      double s1) {
   const int D = k->D;
   const size_t n = inside.size(), pitch = k->npad;
   SxKdePilotArgs a;
@@ -193,7 +203,7 @@ int set_local_factors(sxmc_kde* k, const float* rows, int nfields, const std::ve
       mass = mass * sxkde::truncation_mass(v, k->h->lower[(size_t)d], k->h->upper[(size_t)d], r);   // (as the prepass)
       s0[j * (size_t)(D + 1) + (size_t)d] = v;
     }
-    s0[j * (size_t)(D + 1) + (size_t)D] = 1.0 / mass;
+    s0[j * (size_t)(D + 1) + (size_t)D] = (m ? (double)m[inside[j]] : 1.0) / mass;
   }
   DeviceBuffer<double> dx, ds, dpart, df;   // (device memory of this call, freed when it returns)
   SX_BUF(dx.alloc(x.size()));
@@ -203,11 +213,11 @@ int set_local_factors(sxmc_kde* k, const float* rows, int nfields, const std::ve
   const hipStream_t s = k->h->stream;
   SX_HIP(hipMemcpyAsync(dx.get(), x.data(), sizeof(double) * x.size(), hipMemcpyHostToDevice, s));
   SX_HIP(hipMemcpyAsync(ds.get(), s0.data(), sizeof(double) * s0.size(), hipMemcpyHostToDevice, s));
-  SX_HIP(sx_kde_pilot(a, dx.get(), ds.get(), dpart.get(), df.get(), s));
+  SX_HIP(sx_kde_pilot(a, dx.get(), ds.get(), m ? s1 : 0.0, dpart.get(), df.get(), s));
   std::vector<double> f(pitch);
   SX_HIP(hipMemcpyAsync(f.data(), df.get(), sizeof(double) * pitch, hipMemcpyDeviceToHost, s));
   SX_HIP(hipStreamSynchronize(s));
-  const double g = sxkde::pilot_scale(f.data(), inside);
+  const double g = m ? sxkde::weighted_pilot_scale(f.data(), inside, m, s1) : sxkde::pilot_scale(f.data(), inside);
   std::vector<double> lam(pitch, 1.0);
   for (size_t i = 0; i < k->nsamples; i++) lam[i] = sxkde::local_factor(f[i], g, k->sensitivity);
   SX_BUF(k->d_lambda.alloc(pitch));
@@ -217,11 +227,11 @@ int set_local_factors(sxmc_kde* k, const float* rows, int nfields, const std::ve
   return SXMC_OK;
 }
 
-// sxmc_kde_create (sensitivity 0: nothing adaptive is allocated or run) and sxmc_kde_create_adaptive
-int kde_create(const float* samples, size_t nsamples_floats, int samples_on_device, int nfields, int nobservables,
-               const double* lower, size_t n_lower, const double* upper, size_t n_upper, const double* bandwidth_scale,
-               size_t n_bandwidth_scale, unsigned dataset, double sensitivity, sxmc_kde_t* out) {
-  // Eval::Eval validation, pdfz.cpp:64-82 (same order, same messages, as sxmc_hist_create)
+// The arguments every creation and sxmc_kde_weighted_bandwidths check alike.  Eval::Eval validation, pdfz.cpp:64-82
+// (same order, same messages, as sxmc_hist_create)
+int kde_check_arguments(const float* samples, size_t nsamples_floats, int nfields, int nobservables, const double* lower,
+                        size_t n_lower, const double* upper, size_t n_upper, const double* bandwidth_scale,
+                        size_t n_bandwidth_scale) {
   SX_REQUIRE(nfields > 0 && nsamples_floats % (size_t)nfields == 0,
              "Length of samples array is not divisible by number of fields.");
   SX_REQUIRE(nobservables != 0, "Number of observables in PDF is zero.");
@@ -242,6 +252,49 @@ int kde_create(const float* samples, size_t nsamples_floats, int samples_on_devi
     SX_REQUIRE(upper[d] > lower[d], "Upper bound must be greater than lower bound.");
   }
   SX_REQUIRE(nsamples_floats == 0 || samples, "null samples");
+  return SXMC_OK;
+}
+
+// The multiplicities' count and total, checked without a device.
+int kde_check_multiplicities(const unsigned* m, size_t nm, size_t nrows) {
+  SX_REQUIRE(nm == nrows, "EvalKernel sample multiplicities: " + std::to_string(nm) + " given for " + std::to_string(nrows) +
+                              " rows of the table (one word per row)");
+  unsigned long long total = 0;
+  for (size_t i = 0; i < nm; i++) total += m[i];   // (at most 2^32 rows of less than 2^32 each: no overflow of 64 bits)
+  if (total > 0xFFFFFFFFull) {
+    return fail(SXMC_ERR_INVALID, "EvalKernel sample multiplicities: their total " + std::to_string(total) +
+                                      " exceeds 4294967295, what the unsigned normalisation holds");
+  }
+  return SXMC_OK;
+}
+
+// What weighted_bandwidths refused, by name.
+int kde_bandwidth_refusal(const sxkde::WeightedBandwidths& wb, bool weighted) {
+  switch (wb.status) {
+    case sxkde::kWeightsTooFew:
+      if (!weighted) return fail(SXMC_ERR_INVALID, "EvalKernel needs at least 2 samples inside the domain to set its bandwidths.");
+      return fail(SXMC_ERR_INVALID, "EvalKernel needs at least 2 samples of multiplicity > 0 inside the domain to set its "
+                                    "bandwidths.");
+    case sxkde::kWeightsNoFreedom:
+      return fail(SXMC_ERR_INVALID, "EvalKernel sample multiplicities leave no degree of freedom (sum m - sum m^2 / sum m is "
+                                    "not positive): no bandwidth.");
+    case sxkde::kWeightsNoSpread:
+      return fail(SXMC_ERR_INVALID, "EvalKernel bandwidth is zero: observable " + std::to_string(wb.observable) +
+                                        " has no spread inside the domain.");
+    default: return SXMC_OK;
+  }
+}
+
+// sxmc_kde_create (sensitivity 0: nothing adaptive is allocated or run), sxmc_kde_create_adaptive and
+// sxmc_kde_create_weighted (m: one multiplicity per table row on the host, or null: none)
+int kde_create(const float* samples, size_t nsamples_floats, int samples_on_device, int nfields, int nobservables,
+               const double* lower, size_t n_lower, const double* upper, size_t n_upper, const double* bandwidth_scale,
+               size_t n_bandwidth_scale, unsigned dataset, double sensitivity, const unsigned* m, size_t nm,
+               sxmc_kde_t* out) {
+  if (int rc_ = kde_check_arguments(samples, nsamples_floats, nfields, nobservables, lower, n_lower, upper, n_upper,
+                                    bandwidth_scale, n_bandwidth_scale)) {
+    return rc_;
+  }
 
   // Scott's rule over the untransformed samples inside the domain, in f64 on the host (before anything is allocated on
   // the device: a table that cannot set its bandwidths is refused without a GPU)
@@ -256,21 +309,17 @@ int kde_create(const float* samples, size_t nsamples_floats, int samples_on_devi
   const size_t nrows = nsamples_floats / (size_t)nfields;
   const std::vector<size_t> inside = sxkde::rows_inside(rows, (size_t)nfields, 1, nrows, D, lower, upper);
   const size_t n = inside.size();
-  SX_REQUIRE(n >= 2, "EvalKernel needs at least 2 samples inside the domain to set its bandwidths.");
+  // (kde_weights.h: with multiplicities Kish's n_eff stands where n stood and the moments weigh every row by m; without,
+  // the same function gives the unweighted rule's bytes)
+  if (m) {
+    if (int rc_ = kde_check_multiplicities(m, nm, nrows)) return rc_;
+  }
+  const sxkde::WeightedBandwidths wb = sxkde::weighted_bandwidths(rows, (size_t)nfields, inside, D, bandwidth_scale, m);
+  if (int rc_ = kde_bandwidth_refusal(wb, m != nullptr)) return rc_;
   double bw[SXMC_KDE_MAX_DIM] = {0}, sigmas[SXMC_KDE_MAX_DIM] = {0}, prod_h = 1.0;
   for (int d = 0; d < D; d++) {
-    double mean = 0.0, ss = 0.0;
-    for (size_t i : inside) mean += rows[i * (size_t)nfields + (size_t)d];
-    mean /= (double)n;
-    for (size_t i : inside) {
-      const double dx = rows[i * (size_t)nfields + (size_t)d] - mean;
-      ss += dx * dx;
-    }
-    const double sigma = std::sqrt(ss / (double)(n - 1));
-    SX_REQUIRE(sigma > 0, "EvalKernel bandwidth is zero: observable " + std::to_string(d) +
-                              " has no spread inside the domain.");
-    bw[d] = bandwidth_scale[d] * sigma * std::pow((double)n, -1.0 / (D + 4));
-    sigmas[d] = sigma;
+    bw[d] = wb.h[d];
+    sigmas[d] = wb.sigma[d];
     prod_h *= bw[d];
   }
 
@@ -290,10 +339,24 @@ int kde_create(const float* samples, size_t nsamples_floats, int samples_on_devi
   }
   k->n_inside = n;
   k->prefactor = 1.0 / (std::pow(2.0 * M_PI, 0.5 * D) * prod_h);
+  k->n_eff = wb.n_eff;
   k->npad = std::max<size_t>(SXMC_KDE_TILE, (k->nsamples + SXMC_KDE_TILE - 1) / SXMC_KDE_TILE * SXMC_KDE_TILE);
+  if (m) {   // the library's own copy, 0 in the padding up to npad
+    auto column = std::make_shared<DeviceBuffer<unsigned>>();
+    SX_BUF(column->alloc(k->npad));
+    // (on the evaluator's own stream, which carries every later launch, and waited for: `m` is the caller's)
+    const hipStream_t s = k->h->stream;
+    SX_HIP(hipMemsetAsync(column->get(), 0, sizeof(unsigned) * k->npad, s));
+    if (nm) SX_HIP(hipMemcpyAsync(column->get(), m, sizeof(unsigned) * nm, hipMemcpyHostToDevice, s));
+    SX_HIP(hipStreamSynchronize(s));
+    k->d_mult = std::move(column);
+    k->mult = std::make_shared<const std::vector<unsigned>>(m, m + nm);
+    k->mult_total = 0;
+    for (size_t i = 0; i < nm; i++) k->mult_total += m[i];
+  }
   if (sensitivity > 0) {
     k->sensitivity = sensitivity;
-    rc = set_local_factors(k.get(), rows, nfields, inside);
+    rc = set_local_factors(k.get(), rows, nfields, inside, m, wb.s1);
     if (rc) return rc;
   }
   rc = cleared_rows(k.get());
@@ -314,7 +377,7 @@ int sxmc_kde_create(const float* samples, size_t nsamples_floats, int samples_on
   SX_REQUIRE(out, "null argument");
   *out = nullptr;
   return kde_create(samples, nsamples_floats, samples_on_device, nfields, nobservables, lower, n_lower, upper, n_upper,
-                    bandwidth_scale, n_bandwidth_scale, dataset, 0.0, out);
+                    bandwidth_scale, n_bandwidth_scale, dataset, 0.0, nullptr, 0, out);
 }
 
 int sxmc_kde_create_adaptive(const float* samples, size_t nsamples_floats, int samples_on_device, int nfields,
@@ -325,7 +388,47 @@ int sxmc_kde_create_adaptive(const float* samples, size_t nsamples_floats, int s
   *out = nullptr;
   SX_REQUIRE(sxkde::valid_sensitivity(sensitivity), "Bandwidth sensitivity must be a number in [0, 1].");
   return kde_create(samples, nsamples_floats, samples_on_device, nfields, nobservables, lower, n_lower, upper, n_upper,
-                    bandwidth_scale, n_bandwidth_scale, dataset, sensitivity, out);
+                    bandwidth_scale, n_bandwidth_scale, dataset, sensitivity, nullptr, 0, out);
+}
+
+int sxmc_kde_create_weighted(const float* samples, size_t nsamples_floats, int samples_on_device, int nfields,
+                             int nobservables, const double* lower, size_t n_lower, const double* upper,
+                             size_t n_upper, const double* bandwidth_scale, size_t n_bandwidth_scale, unsigned dataset,
+                             double sensitivity, const unsigned* multiplicities, size_t nmultiplicities,
+                             sxmc_kde_t* out) {
+  SX_REQUIRE(out, "null argument");
+  *out = nullptr;
+  SX_REQUIRE(sxkde::valid_sensitivity(sensitivity), "Bandwidth sensitivity must be a number in [0, 1].");
+  return kde_create(samples, nsamples_floats, samples_on_device, nfields, nobservables, lower, n_lower, upper, n_upper,
+                    bandwidth_scale, n_bandwidth_scale, dataset, sensitivity, multiplicities, nmultiplicities, out);
+}
+
+int sxmc_kde_weighted_bandwidths(const float* samples, size_t nsamples_floats, int nfields, int nobservables,
+                                 const double* lower, size_t n_lower, const double* upper, size_t n_upper,
+                                 const double* bandwidth_scale, size_t n_bandwidth_scale,
+                                 const unsigned* multiplicities, size_t nmultiplicities, double* h, double* sigma,
+                                 double* mean, double* n_eff, double* s1, double* s2) {
+  if (int rc_ = kde_check_arguments(samples, nsamples_floats, nfields, nobservables, lower, n_lower, upper, n_upper,
+                                    bandwidth_scale, n_bandwidth_scale)) {
+    return rc_;
+  }
+  const size_t nrows = nsamples_floats / (size_t)nfields;
+  if (multiplicities) {
+    if (int rc_ = kde_check_multiplicities(multiplicities, nmultiplicities, nrows)) return rc_;
+  }
+  const std::vector<size_t> inside = sxkde::rows_inside(samples, (size_t)nfields, 1, nrows, nobservables, lower, upper);
+  const sxkde::WeightedBandwidths wb =
+      sxkde::weighted_bandwidths(samples, (size_t)nfields, inside, nobservables, bandwidth_scale, multiplicities);
+  if (s1) *s1 = wb.s1;
+  if (s2) *s2 = wb.s2;
+  if (int rc_ = kde_bandwidth_refusal(wb, multiplicities != nullptr)) return rc_;
+  for (int d = 0; d < nobservables; d++) {
+    if (h) h[d] = wb.h[d];
+    if (sigma) sigma[d] = wb.sigma[d];
+    if (mean) mean[d] = wb.mean[d];
+  }
+  if (n_eff) *n_eff = wb.n_eff;
+  return SXMC_OK;
 }
 
 int sxmc_kde_create_shared(sxmc_kde_t base, sxmc_kde_t* out) {
@@ -345,6 +448,10 @@ int sxmc_kde_create_shared(sxmc_kde_t base, sxmc_kde_t* out) {
     k->scale[d] = base->scale[d];
   }
   k->n_inside = base->n_inside;
+  k->d_mult = base->d_mult;   // (the rows' multiplicities belong to the table: shared with it)
+  k->mult = base->mult;
+  k->mult_total = base->mult_total;
+  k->n_eff = base->n_eff;
   k->prefactor = base->prefactor;
   k->cus = base->cus;
   if (base->d_lambda) {   // the factors are copied, never recomputed
@@ -456,7 +563,7 @@ int kde_launch(sxmc_kde* k, int do_eval_pdf, hipStream_t s) {
   }
   a.lambda = k->d_lambda.get();
   SX_HIP(hipMemsetAsync(a.norm, 0, sizeof(unsigned), s));
-  SX_HIP(sx_kde_prepass(d, a, s));
+  SX_HIP(sx_kde_prepass(d, a, k->mult_ptr(), s));
   if (lookup) {
     const unsigned ntiles = (unsigned)(k->npad / SXMC_KDE_TILE);
     const bool adaptive = k->adaptive();
@@ -568,6 +675,25 @@ int sxmc_kde_local_factors(sxmc_kde_t k, double* lambda, size_t n) {
   SX_REQUIRE(k && (lambda || n == 0), "null argument");
   SX_REQUIRE(n == k->nsamples, "local factor buffer size mismatch");
   for (size_t i = 0; i < n; i++) lambda[i] = k->d_lambda ? k->lambda[i] : 1.0;
+  return SXMC_OK;
+}
+int sxmc_kde_sample_total(sxmc_kde_t k, unsigned long long* total) {
+  SX_REQUIRE(k && total, "null argument");
+  *total = k->weighted() ? k->mult_total : (unsigned long long)k->nsamples;
+  return SXMC_OK;
+}
+int sxmc_kde_get_sample_multiplicities(sxmc_kde_t k, unsigned* out, size_t n, int* is_set) {
+  SX_REQUIRE(k && (out || n == 0), "null argument");
+  if (is_set) *is_set = k->weighted() ? 1 : 0;
+  if (!out && n == 0) return SXMC_OK;   // (the question alone: are any set?)
+  SX_REQUIRE(n == k->nsamples, "sample multiplicities buffer size mismatch");
+  if (!k->weighted()) std::fill(out, out + n, 1u);   // (none set: every row counts once)
+  else std::copy(k->mult->begin(), k->mult->end(), out);
+  return SXMC_OK;
+}
+int sxmc_kde_effective_samples(sxmc_kde_t k, double* n_eff) {
+  SX_REQUIRE(k && n_eff, "null argument");
+  *n_eff = k->weighted() ? k->n_eff : (double)k->n_inside;
   return SXMC_OK;
 }
 int sxmc_kde_nsamples(sxmc_kde_t k, size_t* v) {

@@ -109,6 +109,14 @@ int cv_check_candidates(const sxmc_kde* k, const double* bw, int K) {
   return SXMC_OK;
 }
 
+// The leave-one-out score of a table with multiplicities is a law of its own (a row's own copies, its error bound): not
+// built, refused by name.
+int cv_refuse_weighted(sxmc_kde* k) {
+  if (!k->weighted()) return SXMC_OK;
+  return fail(SXMC_ERR_STATE, "EvalKernel: cross-validation of an evaluator with sample multiplicities is not built (the "
+                              "weighted leave-one-out score): choose the bandwidth scales on the unweighted table");
+}
+
 }  // namespace
 
 extern "C" {
@@ -123,6 +131,7 @@ int sxmc_kde_bandwidth_scale(sxmc_kde_t k, double* scale, size_t n) {
 int sxmc_kde_cv_scores(sxmc_kde_t k, const double* bandwidths, int ncandidates, size_t max_rows, double* scores,
                        size_t* rows_used) {
   SX_REQUIRE(k && bandwidths && scores, "null argument");
+  if (int rc_ = cv_refuse_weighted(k)) return rc_;
   if (int rc_ = cv_check_candidates(k, bandwidths, ncandidates)) return rc_;
   SX_REQUIRE(sxkde::cv_subset_size(k->n_inside, max_rows) >= 2, "Cross-validation needs at least 2 rows to score.");
   CvRows r;
@@ -137,6 +146,7 @@ int sxmc_kde_cv_select(sxmc_kde_t k, double lo, double hi, int steps, int per_ob
                        size_t* rows_used, int* nscans, double* scan_grid, double* scan_scores, int* scan_chosen) {
   SX_REQUIRE(k && scale_out, "null argument");
   SX_REQUIRE(n_scale == (size_t)k->D, "bandwidth scale buffer size mismatch");
+  if (int rc_ = cv_refuse_weighted(k)) return rc_;
   if (const char* why = sxkde::cv_grid_error(lo, hi, steps)) return fail(SXMC_ERR_INVALID, why);
   SX_REQUIRE(sxkde::cv_subset_size(k->n_inside, max_rows) >= 2, "Cross-validation needs at least 2 rows to score.");
   CvRows r;

@@ -9,9 +9,9 @@ using namespace sxhost;
 
 namespace {
 
-// Lists the in-domain rows of the last evaluation on the evaluator's stream and returns their count n (= the norm of
-// that evaluation): after it, d_flag + 2 npad holds their row numbers in table order.
-int kde_compact(sxmc_kde_t k, unsigned& n) {
+// What a look at the last evaluation's rows needs first: an evaluation, the caller's stream settled, d_flag and the
+// scan's scratch.
+int kde_draw_ready(sxmc_kde_t k) {
   if (!k->evaluated) {
     return fail(SXMC_ERR_STATE, "EvalKernel: nothing to draw from before an evaluation (EvalAsync first)");
   }
@@ -28,11 +28,34 @@ int kde_compact(sxmc_kde_t k, unsigned& n) {
     }
     SX_BUF(k->d_flag.alloc(3 * k->npad));
   }
+  return SXMC_OK;
+}
+
+// Lists the live rows of the last evaluation (weight > 0: inside the domain, and of multiplicity > 0 where there are
+// multiplicities) on the evaluator's stream and returns their count n (without multiplicities the norm of that
+// evaluation): after it, d_flag + 2 npad holds their row numbers in table order.
+int kde_compact(sxmc_kde_t k, unsigned& n) {
+  if (int rc_ = kde_draw_ready(k)) return rc_;
+  const hipStream_t s = k->h->stream;
   unsigned* flag = k->d_flag.get();
   unsigned* pos = flag + k->npad;
   unsigned* idx = pos + k->npad;
   SX_HIP(sx_kde_compact(k->d_rows.get(), k->rowlen(), k->npad, flag, pos, idx, k->d_scan_temp.get(), k->scan_temp_bytes, s));
   SX_HIP(hipMemcpyAsync(&n, pos + (k->npad - 1), sizeof(unsigned), hipMemcpyDeviceToHost, s));
+  SX_HIP(hipStreamSynchronize(s));
+  return SXMC_OK;
+}
+
+// With multiplicities: the inclusive prefix sum of the live rows' multiplicities over all npad rows, in table order, on
+// the evaluator's stream, and its last entry T (= the norm of the last evaluation): after it, d_flag + npad holds the sum.
+int kde_weighted_scan(sxmc_kde_t k, unsigned& total) {
+  if (int rc_ = kde_draw_ready(k)) return rc_;
+  const hipStream_t s = k->h->stream;
+  unsigned* flag = k->d_flag.get();
+  unsigned* cum = flag + k->npad;
+  SX_HIP(sx_kde_weighted_scan(k->d_rows.get(), k->rowlen(), k->npad, k->mult_ptr(), flag, cum, k->d_scan_temp.get(),
+                              k->scan_temp_bytes, s));
+  SX_HIP(hipMemcpyAsync(&total, cum + (k->npad - 1), sizeof(unsigned), hipMemcpyDeviceToHost, s));
   SX_HIP(hipStreamSynchronize(s));
   return SXMC_OK;
 }
@@ -58,8 +81,8 @@ int sxmc_kde_random_sample(sxmc_kde_t k, size_t nobserved, unsigned long long se
     return fail(SXMC_ERR_STATE, "EvalKernel: nothing to draw from before an evaluation (EvalAsync first)");
   }
   if (nobserved == 0) return SXMC_OK;
-  unsigned n = 0;
-  int rc = kde_compact(k, n);
+  unsigned n = 0;   // the in-domain rows, or (with multiplicities) their multiplicities' total
+  int rc = k->weighted() ? kde_weighted_scan(k, n) : kde_compact(k, n);
   if (rc) return rc;
   if (n == 0) {
     return fail(SXMC_ERR_STATE, "EvalKernel: the last evaluation left no sample inside the domain: nothing to draw from");
@@ -88,8 +111,13 @@ int sxmc_kde_random_sample(sxmc_kde_t k, size_t nobserved, unsigned long long se
   unsigned* d_exhausted = nullptr;
   rc = sample_buffer(k->h, nobserved, row, d_out, d_exhausted);   // (the histogram evaluator's, on the same stream)
   if (rc) return rc;
-  const unsigned* idx = k->d_flag.get() + 2 * k->npad;
-  SX_HIP(sx_kde_sample(D, k->d_rows.get(), k->d_lambda.get(), idx, n, g, seed, nobserved, d_out, d_exhausted, k->h->stream));
+  if (k->weighted()) {
+    SX_HIP(sx_kde_sample_weighted(D, k->d_rows.get(), k->d_lambda.get(), k->d_flag.get() + k->npad, n, k->npad, g, seed,
+                                  nobserved, d_out, d_exhausted, k->h->stream));
+  } else {
+    const unsigned* idx = k->d_flag.get() + 2 * k->npad;
+    SX_HIP(sx_kde_sample(D, k->d_rows.get(), k->d_lambda.get(), idx, n, g, seed, nobserved, d_out, d_exhausted, k->h->stream));
+  }
   return sample_read_back(k->h, nobserved, row, ": the cuts leave (almost) none of the kernel-density PDF's mass",
                           h_events);
 }
@@ -125,7 +153,7 @@ int sxmc_kde_project(sxmc_kde_t k, int obs, int nbins, double* h_prob) {
   double* d_prob = k->d_proj.get() + off_prob;
   unsigned* d_count = reinterpret_cast<unsigned*>(d_prob + nbins);
   SX_HIP(hipMemsetAsync(d_count, 0, sizeof(unsigned), s));
-  SX_HIP(sx_kde_project(k->d_rows.get(), a, k->d_proj.get(), d_count, d_prob, s));
+  SX_HIP(sx_kde_project(k->d_rows.get(), a, k->mult_ptr(), k->d_proj.get(), d_count, d_prob, s));
   SX_HIP(hipMemcpyAsync(h_prob, d_prob, sizeof(double) * (size_t)nbins, hipMemcpyDeviceToHost, s));
   SX_HIP(hipStreamSynchronize(s));
   return SXMC_OK;

@@ -45,6 +45,14 @@ struct sxmc_kde {
   double sensitivity = 0;
   sxhost::DeviceBuffer<double> d_lambda;   // [npad] the factors of the table rows, 1.0 in the padding; null when fixed
   std::vector<double> lambda;      // [nsamples] the same on the host
+  // weighted Monte Carlo samples (sxmc_kde_create_weighted): nothing of it is set or read without multiplicities.  The
+  // column belongs to the table: evaluators made by sxmc_kde_create_shared hold the same buffers.
+  std::shared_ptr<sxhost::DeviceBuffer<unsigned>> d_mult;   // [npad] the rows' multiplicities, 0 in the padding; null: none
+  std::shared_ptr<const std::vector<unsigned>> mult;        // [nsamples] the same on the host
+  unsigned long long mult_total = 0;                        // their sum over ALL rows (<= 2^32 - 1)
+  double n_eff = 0;                // Kish's effective sample count of the in-domain rows (n_inside without multiplicities)
+  bool weighted() const { return d_mult != nullptr; }
+  const unsigned* mult_ptr() const { return d_mult ? d_mult->get() : nullptr; }
   bool adaptive() const { return d_lambda.get() != nullptr; }
   int rowlen() const { return D + (adaptive() ? 2 : 1); }
   // evaluation points
@@ -76,7 +84,9 @@ struct sxmc_kde {
   // sampling (sxmc_kde_random_sample): the rows hold an evaluation once one has been launched
   bool evaluated = false;
   sxhost::DeviceBuffer<unsigned> d_flag;   // [npad] in-domain flags, then [npad] their inclusive prefix sum, then [npad] the
-                                           // in-domain row numbers (one allocation, made at the first draw)
+                                           // in-domain row numbers (one allocation, made at the first draw); with
+                                           // multiplicities a draw leaves [npad] m_i of the live rows, then [npad] their
+                                           // inclusive prefix sum, which the sampler searches
   sxhost::DeviceBuffer<void> d_scan_temp;
   size_t scan_temp_bytes = 0;
   // projection (sxmc_kde_project): per-row scratch, partial sums, the result and the in-domain count (grow-only)

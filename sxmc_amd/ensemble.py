@@ -103,6 +103,11 @@ def make_evaluators(workload):
     for s in w.signals:
         if getattr(s, "pdf", "hist") == "kernel":
             alpha = getattr(s, "bandwidth_sensitivity", 0.0)
+            mult = getattr(s, "multiplicities", None)
+            if getattr(s, "bandwidth_cv", None) is not None and mult is not None:
+                raise pdfz.Error("signal %r: \"bandwidth_scale\": \"cv\" with sample multiplicities: cross-validation "
+                                 "of a weighted kernel-density evaluator is not built (the weighted leave-one-out score)"
+                                 % getattr(s, "name", "?"))
             if getattr(s, "bandwidth_cv", None) is not None:
                 # "bandwidth_scale": "cv": chosen once, here; from now on the signal carries the numbers, so that
                 # every later evaluator of it is built with them typed in and nothing is searched again
@@ -115,7 +120,7 @@ def make_evaluators(workload):
             else:
                 scale = s.bandwidth_scale if s.bandwidth_scale is not None else [1.0] * w.nobs
                 ev = pdfz.EvalKernel(s.samples, s.nfields, w.nobs, w.lower, w.upper, scale, dataset=s.dataset,
-                                     bandwidth_sensitivity=alpha)
+                                     bandwidth_sensitivity=alpha, multiplicities=mult)
             if getattr(s, "bandwidth_cutoff", 0.0) != 0.0:
                 ev.SetCutoff(s.bandwidth_cutoff)
         else:

@@ -61,7 +61,7 @@ struct Signal {
   double nexpected = 0;
   size_t n_mc = 0;  //!< number of MC samples BEFORE cuts (signal.cpp:28); build_pdfz fills it in when it is 0.  With
                     //!< multiplicities: their total BEFORE cuts (bins, norm and n_mc all carry the scale 2^k: it cancels)
-  std::vector<unsigned> multiplicities;       //!< "hist": one per row of the table given to build_pdfz (after cuts), or empty:
+  std::vector<unsigned> multiplicities;       //!< either pdf: one per row of the table given to build_pdfz (after cuts), or empty:
                                               //!< every row counts once (include/sxmc_hip.h, sxmc_sample_multiplicities)
   int weight_log2_scale = 0;                  //!< ... the k of their scale 2^k: a row's weight is m * 2^-k
   std::string pdf = "hist";                   //!< "hist": pdfz::EvalHist; "kernel": pdfz::EvalKernel (kernel density)
@@ -99,7 +99,19 @@ inline void build_pdfz(Signal& sig, const std::vector<float>& samples, int nfiel
     }
     std::vector<double> scale(D, 1.0);
     for (size_t i = 0; i < D && !sig.bandwidth_scale.empty(); i++) scale.at(observables[i].field_index) = sig.bandwidth_scale[i];
-    if (sig.bandwidth_cv) {
+    if (!sig.multiplicities.empty()) {
+      // weighted Monte Carlo samples: the same row-count check as for histograms; the evaluator takes them at construction
+      if (sig.multiplicities.size() != samples.size() / (size_t)nfields) {
+        throw pdfz::Error("signal '" + sig.name + "': " + std::to_string(sig.multiplicities.size()) + " multiplicities for " +
+                          std::to_string(samples.size() / (size_t)nfields) + " rows");
+      }
+      if (sig.bandwidth_cv) {
+        throw pdfz::Error("signal '" + sig.name + "': \"bandwidth_scale\": \"cv\" with sample multiplicities: cross-validation "
+                          "of a weighted kernel-density evaluator is not built (the weighted leave-one-out score)");
+      }
+      h = new pdfz::EvalKernel(samples, nfields, (int)D, lower, upper, scale, sig.multiplicities, sig.dataset,
+                               sig.bandwidth_sensitivity);
+    } else if (sig.bandwidth_cv) {
       // "bandwidth_scale": "cv": chosen once, here; from now on the signal carries the numbers, so that every later
       // evaluator of it (another device's, a shared one) is built with them typed in and nothing is searched again
       pdfz::EvalKernel* k = pdfz::EvalKernel::CrossValidated(samples, nfields, (int)D, lower, upper, sig.cv, sig.dataset,
@@ -129,14 +141,12 @@ inline void build_pdfz(Signal& sig, const std::vector<float>& samples, int nfiel
   }
   sig.histogram = h;
   // (a table loaded through load_config has been cut: n_mc is then the row count before the cuts, set by the loader)
-  if (sig.pdf == "kernel" && !sig.multiplicities.empty()) {
-    delete h;
-    sig.histogram = nullptr;
-    throw pdfz::Error("signal '" + sig.name + "': sample multiplicities on a \"kernel\" signal (kernel-density weights are not built)");
-  }
   if (sig.n_mc == 0) {
     sig.n_mc = samples.size() / (size_t)nfields;
-    if (!sig.multiplicities.empty()) sig.n_mc = (size_t)static_cast<pdfz::EvalHist*>(h)->SampleTotal();
+    if (!sig.multiplicities.empty()) {
+      sig.n_mc = sig.pdf == "kernel" ? (size_t)static_cast<pdfz::EvalKernel*>(h)->SampleTotal()
+                                     : (size_t)static_cast<pdfz::EvalHist*>(h)->SampleTotal();
+    }
   }
   for (Systematic& s : systematics) {
     auto pars = std::make_shared<pdfz::Array<short>>(s.npars, true);

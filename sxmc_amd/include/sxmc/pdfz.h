@@ -620,9 +620,56 @@ class EvalKernel : public detail::EvalOver<detail::KernelApi> {
                                       lower.size(), upper.data(), upper.size(), bandwidth_scale.data(),
                                       bandwidth_scale.size(), dataset, bandwidth_sensitivity, &handle));
   }
+  /** WEIGHTED MONTE CARLO SAMPLES: the same with one integer multiplicity per table row (sxmc_sample_multiplicities'
+   *  fixed-point weights; the laws are written out at sxmc_kde_create_weighted in include/sxmc_hip.h).  Given here and
+   *  never set afterwards: the bandwidths (Kish's n_eff = (sum m)^2 / sum m^2 where n stood, moments weighted by m), the
+   *  pilot and the padding are fixed at construction.  The norm is sum m_i over the in-domain rows (a weighted
+   *  EvalHist's, bit for bit); a row's weight is m_i / mass_i, so the pair sum, its cutoff and the combine are the code
+   *  they were; SampleEvents picks a row with probability m_i / norm; Project weighs a row by m_i.  A count that is not
+   *  the row count, or a total beyond 2^32 - 1, throws.  All m equal to a power of two give the unweighted evaluator's
+   *  bytes.  An empty vector is NOT "no multiplicities": it is a count mismatch unless the table is empty.
+   *  Cross-validation of such an evaluator (CvScores, SelectBandwidthScale) throws: not built.  Share() shares the column. */
+  EvalKernel(const std::vector<float>& samples, int nfields, int nobservables, const std::vector<double>& lower,
+             const std::vector<double>& upper, const std::vector<double>& bandwidth_scale,
+             const std::vector<unsigned>& multiplicities, unsigned dataset = 0, double bandwidth_sensitivity = 0.0)
+      : EvalOver(nfields, nobservables, dataset) {
+    const unsigned none = 0;
+    throw_on(sxmc_kde_create_weighted(samples.data(), samples.size(), 0, nfields, nobservables, lower.data(),
+                                      lower.size(), upper.data(), upper.size(), bandwidth_scale.data(),
+                                      bandwidth_scale.size(), dataset, bandwidth_sensitivity,
+                                      multiplicities.empty() ? &none : multiplicities.data(), multiplicities.size(),
+                                      &handle));
+  }
   EvalKernel(const EvalKernel& base, SharedSamples s)
       : EvalOver(base, s), cv_report(base.cv_report), cross_validated(base.cross_validated) {}
   Eval* Share() const override { return new EvalKernel(*this, SharedSamples{}); }
+
+  /** The multiplicities' total, or the row count when none are set: what n_mc is for either kind. */
+  unsigned long long SampleTotal() const {
+    unsigned long long total = 0;
+    throw_on(sxmc_kde_sample_total(handle, &total));
+    return total;
+  }
+  bool HasSampleMultiplicities() const {
+    int is_set = 0;
+    throw_on(sxmc_kde_get_sample_multiplicities(handle, nullptr, 0, &is_set));
+    return is_set != 0;
+  }
+  /** The multiplicities; all 1 when none are set. */
+  std::vector<unsigned> SampleMultiplicities() const {
+    size_t n = 0;
+    throw_on(sxmc_kde_nsamples(handle, &n));
+    std::vector<unsigned> out(n);
+    unsigned none = 0;
+    throw_on(sxmc_kde_get_sample_multiplicities(handle, n ? out.data() : &none, n, nullptr));
+    return out;
+  }
+  /** Kish's n_eff of the bandwidth rule; the in-domain row count when no multiplicities are set. */
+  double EffectiveSamples() const {
+    double n_eff = 0.0;
+    throw_on(sxmc_kde_effective_samples(handle, &n_eff));
+    return n_eff;
+  }
 
   /** The alpha this evaluator was constructed with (a shared evaluator: its base's). */
   double BandwidthSensitivity() const {

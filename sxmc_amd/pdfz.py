@@ -284,6 +284,35 @@ class EvalHist(_Eval):
         return out
 
 
+def _multiplicities(m):
+    """One uint32 per table row from anything array-like of non-negative integers; Error otherwise."""
+    m = np.ascontiguousarray(m)
+    if m.dtype != np.uint32:
+        if m.size and (np.any(m < 0) or np.any(m > 0xFFFFFFFF) or np.any(m != np.floor(m))):
+            raise Error("sample multiplicities are integers in [0, 2^32 - 1]")
+        m = m.astype(np.uint32)
+    return m.reshape(-1)
+
+
+def kde_weighted_bandwidths(samples, nfields, nobservables, lower, upper, bandwidth_scale, multiplicities=None):
+    """sxmc_kde_weighted_bandwidths: the bandwidth law of an EvalKernel over weighted samples on the host alone (no
+    device is touched).  Returns a dict of h, sigma, mean (float64 [nobservables]), n_eff, s1, s2; raises Error where
+    the constructor would."""
+    samples = np.ascontiguousarray(samples, dtype=np.float32).reshape(-1)
+    lower = np.ascontiguousarray(lower, dtype=np.float64)
+    upper = np.ascontiguousarray(upper, dtype=np.float64)
+    scale = np.ascontiguousarray(bandwidth_scale, dtype=np.float64).reshape(-1)
+    m = None if multiplicities is None else _multiplicities(multiplicities)
+    D = max(int(nobservables), 0)
+    h, sigma, mean = np.zeros(D), np.zeros(D), np.zeros(D)
+    n_eff, s1, s2 = C.c_double(0), C.c_double(0), C.c_double(0)
+    _raise(capi.load().sxmc_kde_weighted_bandwidths(
+        capi.ptr(samples), samples.size, int(nfields), int(nobservables), capi.ptr(lower), lower.size, capi.ptr(upper),
+        upper.size, capi.ptr(scale), scale.size, capi.ptr(m), 0 if m is None else m.size, capi.ptr(h), capi.ptr(sigma),
+        capi.ptr(mean), C.byref(n_eff), C.byref(s1), C.byref(s2)))
+    return {"h": h, "sigma": sigma, "mean": mean, "n_eff": n_eff.value, "s1": s1.value, "s2": s2.value}
+
+
 class CvOptions:
     """The grid and the search of EvalKernel's cross-validation (sxmc_amd/csrc/kde_cv.h): multipliers
     lo (hi/lo)^(k/(steps-1)) of Scott's rule, a common scan and (per_observable) one coordinate scan per observable,
@@ -323,21 +352,50 @@ class EvalKernel(_Eval):
     Same method names as EvalHist (RandomSample and Shared included), plus Bandwidths(); at most 4 observables;
     O(points x samples) per evaluation.  bandwidth_sensitivity in [0, 1] (alpha) turns on Abramson's adaptive
     bandwidths h_d * lambda_i, lambda_i fixed per table row at construction (LocalFactors()); 0.0, the default, is the
-    fixed-bandwidth evaluator, the same kernels and bits as before the keyword existed."""
+    fixed-bandwidth evaluator, the same kernels and bits as before the keyword existed.
+    multiplicities (one non-negative integer per table row, host memory; None: none) makes it an evaluator over
+    weighted Monte Carlo samples (sxmc_kde_create_weighted, the laws in include/sxmc_hip.h): given here, never set
+    afterwards; SampleTotal(), SampleMultiplicities() and EffectiveSamples() read them back.  Cross-validation of such
+    an evaluator is refused."""
 
     _prefix = "sxmc_kde_"
 
     def __init__(self, samples, nfields, nobservables, lower, upper, bandwidth_scale, dataset=0,
-                 bandwidth_sensitivity=0.0):
+                 bandwidth_sensitivity=0.0, multiplicities=None):
         scale = np.ascontiguousarray(bandwidth_scale, dtype=np.float64).reshape(-1)
         alpha = float(bandwidth_sensitivity)
         lib = capi.load()
-        if alpha == 0.0:
+        if multiplicities is not None:
+            m = _multiplicities(multiplicities)
+
+            def create(*a):
+                return lib.sxmc_kde_create_weighted(*a[:-1], alpha, capi.ptr(m), m.size, a[-1])
+        elif alpha == 0.0:
             create = lib.sxmc_kde_create
         else:
             def create(*a):
                 return lib.sxmc_kde_create_adaptive(*a[:-1], alpha, a[-1])
         self._create(create, samples, nfields, nobservables, lower, upper, scale, dataset)
+
+    def SampleTotal(self):
+        """The multiplicities' total, or the row count when none are set: n_mc for either kind."""
+        return self._get("sample_total", C.c_ulonglong)
+
+    def SampleMultiplicities(self):
+        """The multiplicities (uint32 [nsamples]); all 1 when none are set."""
+        out = np.empty(self.nsamples, dtype=np.uint32)
+        self._call("get_sample_multiplicities", capi.ptr(out), out.size, None)
+        return out
+
+    def HasSampleMultiplicities(self):
+        is_set = C.c_int(0)
+        self._call("get_sample_multiplicities", None, 0, C.byref(is_set))
+        return bool(is_set.value)
+
+    def EffectiveSamples(self):
+        """Kish's n_eff = (sum m)^2 / sum m^2 over the in-domain rows, which stands where n stood in the bandwidth rule;
+        the in-domain row count when no multiplicities are set."""
+        return self._get("effective_samples", C.c_double)
 
     @classmethod
     def CrossValidated(cls, samples, nfields, nobservables, lower, upper, options=None, dataset=0,

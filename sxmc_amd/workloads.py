@@ -30,8 +30,9 @@ class Signal:
         self.cv_report = None
         # "kernel": the cutoff radius of the pair sum in bandwidths (pdfz.EvalKernel.SetCutoff); 0: none
         self.bandwidth_cutoff = float(bandwidth_cutoff)
-        # "hist": weighted Monte Carlo -- one integer multiplicity per row of `samples` (uint32; None: every row counts
-        # once) on the scale 2^weight_log2_scale (include/sxmc_hip.h, sxmc_sample_multiplicities)
+        # weighted Monte Carlo, "hist" and "kernel" alike -- one integer multiplicity per row of `samples` (uint32; None:
+        # every row counts once) on the scale 2^weight_log2_scale (include/sxmc_hip.h, sxmc_sample_multiplicities; a
+        # kernel-density evaluator takes them at construction, sxmc_kde_create_weighted)
         self.multiplicities = None
         self.weight_log2_scale = 0
 
