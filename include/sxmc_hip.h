@@ -28,7 +28,7 @@ extern "C" {
 #define SXMC_ERR_INVALID 1 /* argument validation failed: where the reference throws pdfz::Error */
 #define SXMC_ERR_HIP 2     /* a HIP runtime call failed (reference: checkCuda) */
 #define SXMC_ERR_STATE 3   /* call sequence error, e.g. eval before the buffers are bound */
-#define SXMC_ERR_SHAPE 4   /* a shape the requested form has no kernel for (a proposal factor beyond 256 parameters) */
+#define SXMC_ERR_SHAPE 4   /* a shape the requested form has no kernel for (a proposal factor or whitening matrix beyond 256 parameters) */
 
 #define SXMC_MAX_NFIELDS 10   /* pdfz.cpp:17 MAX_NFIELDS */
 #define SXMC_MAX_SYST 16      /* systematics per evaluator (reference: unbounded array, pdfz.cpp:126-132) */
@@ -798,6 +798,40 @@ int sxmc_group_set_event_weights(sxmc_group_t g, const double* h_weights, size_t
  * SXMC_ERR_INVALID: a null argument (rows may be null when nrows == 0), nparameters < 1, shrinkage outside (0, 1]. */
 int sxmc_proposal_factor(const float* rows, size_t nrows, int nparameters, const float* new_widths, double shrinkage,
                          double* factor, double* shrinkage_used);
+/* CORRELATED GAUSSIAN CONSTRAINTS (opt-in; NULL, the default, is the reference's one independent Gaussian per parameter,
+ * bit for bit).  With a whitening matrix W set, every step end this group launches (the same list as for the proposal
+ * factor above) replaces the constraint terms of nll_total by those of the whitened residuals.  Per evaluation:
+ *     x_i   = (p_i - mean_i) / sigma_i   for sigma_i > 0 (exactly the division made without W), otherwise x_i = 0;
+ *     r_i   = 0, then for j = 0 .. i ascending  r_i = fma(W_ij, x_j, r_i)   (one fused multiply-add in double per term);
+ *     pen_i = 0.5 * r_i * r_i             for sigma_i > 0, otherwise -0.0 (which changes no sum);
+ * pen_i takes THE SLOT constraint i has without W: nll_total adds the same number of terms in the same order, the
+ * negative-rate and NaN rules (1e18) unchanged.  Mathematically sum pen_i = 0.5 x^T rho^-1 x for W = T^-1, T the
+ * Cholesky factor of the correlation matrix rho (sxmc_constraint_whitening below).  Two exact consequences: with W = I,
+ * r_i = fma(1, x_i, 0) = x_i and every chain is the uncorrelated chain's bytes; a block-diagonal rho gives inside each
+ * block the bytes that block gives alone.  A fixed parameter may take part: its x is constant.
+ * LAYOUT: d_whitening holds P x P doubles (P = nparameters), COLUMN-major: W_ij at d_whitening[j * P + i]; only j <= i is
+ * read.  The pointer is BORROWED: it must stay valid while steps are in flight or recorded in a graph.  The product is
+ * formed before the step end waits for the event sums.  At step time SXMC_ERR_SHAPE beyond 256 parameters or 256
+ * signals.  The look-ahead pass and lockstep sets have no such form: with a matrix set on a member group
+ * sxmc_multigroup_step_async and sxmc_multigroup_lookahead_step_async return SXMC_ERR_STATE, and
+ * sxmc_group_lookahead_supported answers 0 without touching the group. */
+int sxmc_group_set_constraint_whitening(sxmc_group_t g, const double* d_whitening);
+/* The whitening matrix of a correlation matrix, on the host (no device call; usable without a GPU).  rho: P x P doubles
+ * (symmetric, so either major order) over the parameter vector in the walk's order (sources, then <systematic>_<j>);
+ * sigmas: the P constraint widths (<= 0: no constraint); W: P x P doubles in sxmc_group_set_constraint_whitening's layout,
+ * all of them written on success (zeros above the diagonal).
+ * SXMC_ERR_INVALID, the message naming row and column, when rho has an entry that is not finite or lies outside
+ * [-1, 1], a diagonal entry that is not exactly 1, is not exactly symmetric, or gives a parameter with sigma_i <= 0 a
+ * non-zero off-diagonal entry -- checked in that order, each over the rows ascending.
+ * Every operation is one double operation rounded once:
+ *   T = the Cholesky factor of rho, row by row: for i, for j = 0 .. i:  s = rho_ij;  for k = 0 .. j-1 ascending
+ *       s = s - T_ik * T_jk;  j == i: a pivot s that is not > 0 is SXMC_ERR_INVALID "not positive definite at parameter
+ *       i" (no shrinkage: the user's matrix is the model), T_ii = sqrt(s);  j < i: T_ij = s / T_jj.
+ *   W = T^-1 by forward substitution, row by row: W_ii = 1 / T_ii;  for j = 0 .. i-1:  s = 0;  for k = j .. i-1
+ *       ascending  s = s + T_ik * W_kj;  W_ij = -(s * W_ii).
+ *   A product whose T_ik is exactly zero is skipped in both loops, and a W_ij all of whose products were skipped is +0:
+ *   a parameter outside every correlated group has W_ii = 1 and +0 in the rest of its row. */
+int sxmc_constraint_whitening(const double* rho, const double* sigmas, int P, double* W);
 /* WEIGHTED MONTE CARLO SAMPLES (opt-in; an evaluator without multiplicities runs the kernels it ran before).  Histograms
  * and normalisations are `unsigned` counts and every consumer is linear in them, so a row's weight enters as an integer
  * MULTIPLICITY m_i, a fixed-point weight on a power-of-two scale 2^k; only the fill changes (it adds m_i where it added 1)
@@ -1100,6 +1134,14 @@ int sxmc_launch_nll_total(int grid, int block, sxmc_stream_t s, size_t nparamete
                           const double* d_events_total, const double* d_nexpected,
                           const unsigned* d_n_mc, const short* d_source_id,
                           const unsigned* d_norms, double* d_nll);
+/* The same with correlated constraints (sxmc_group_set_constraint_whitening: law and layout).  d_whitening == NULL:
+ * exactly the launch above.  One thread, no staging: any number of parameters. */
+int sxmc_launch_nll_total_whitened(int grid, int block, sxmc_stream_t s, size_t nparameters,
+                                   const double* d_pars, size_t nsignals, size_t nsources,
+                                   const double* d_means, const double* d_sigmas,
+                                   const double* d_events_total, const double* d_nexpected,
+                                   const unsigned* d_n_mc, const short* d_source_id,
+                                   const unsigned* d_norms, double* d_nll, const double* d_whitening);
 /* finish_nll_jump_pick_combo (nll_kernels.cpp:230-271); grid must be 1 */
 int sxmc_launch_finish_nll_jump_pick_combo(int grid, int block, sxmc_stream_t s,
                                            size_t npartial_sums, const double* d_sums,
@@ -1128,6 +1170,22 @@ int sxmc_launch_finish_nll_jump_pick_combo_factor(int grid, int block, sxmc_stre
                                                   const double* d_nexpected, const unsigned* d_n_mc,
                                                   const short* d_source_id, const unsigned* d_norms,
                                                   int debug_mode, const double* d_factor);
+/* The same with a proposal factor and a constraint whitening matrix (sxmc_group_set_constraint_whitening: law and
+ * layout); either may be NULL, both NULL is exactly the first launch.  SXMC_ERR_SHAPE with either set and more than 256
+ * parameters or signals. */
+int sxmc_launch_finish_nll_jump_pick_combo_constrained(int grid, int block, sxmc_stream_t s,
+                                                       size_t npartial_sums, const double* d_sums,
+                                                       size_t nsignals, size_t nsources,
+                                                       const double* d_means, const double* d_sigmas,
+                                                       sxmc_rng_state* d_rng, double* d_nll_current,
+                                                       double* d_nll_proposed, double* d_v_current,
+                                                       double* d_v_proposed, int* d_accepted,
+                                                       int* d_counter, float* d_jump_buffer,
+                                                       int nparameters, const float* d_jump_width,
+                                                       const double* d_nexpected, const unsigned* d_n_mc,
+                                                       const short* d_source_id, const unsigned* d_norms,
+                                                       int debug_mode, const double* d_factor,
+                                                       const double* d_whitening);
 
 /* ---------------------------------------------------------------- multi-GPU exchange (RCCL) ----- */
 /* Fake experiments shard over the GPUs of a node one experiment per rank with NO data-path collective

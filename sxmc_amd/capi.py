@@ -169,6 +169,8 @@ SIGNATURES = {
     "sxmc_group_launch_info": [_vp, C.c_char_p, _sz],
     "sxmc_group_set_lut_output": [_vp, _i],
     "sxmc_group_set_proposal_factor": [_vp, _vp],
+    "sxmc_group_set_constraint_whitening": [_vp, _vp],
+    "sxmc_constraint_whitening": [_vp, _vp, _i, _vp],
     "sxmc_group_set_event_weights": [_vp, _vp, _sz],
     "sxmc_proposal_factor": [_vp, _sz, _i, _vp, _d, _vp, _pd],
     "sxmc_group_eval_async": [_vp, _i, _vp],
@@ -208,10 +210,13 @@ SIGNATURES = {
     "sxmc_launch_nll_event_chunks_weighted": [_i, _i, _vp, _vp, _vp, _sz, _sz, _vp, _vp, _vp, _vp, _vp, _vp],
     "sxmc_launch_nll_event_reduce": [_i, _i, _vp, _sz, _vp, _vp],
     "sxmc_launch_nll_total": [_i, _i, _vp, _sz, _vp, _sz, _sz, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp],
+    "sxmc_launch_nll_total_whitened": [_i, _i, _vp, _sz, _vp, _sz, _sz, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp],
     "sxmc_launch_finish_nll_jump_pick_combo": [_i, _i, _vp, _sz, _vp, _sz, _sz, _vp, _vp, _vp, _vp, _vp,
                                                _vp, _vp, _vp, _vp, _vp, _i, _vp, _vp, _vp, _vp, _vp, _i],
     "sxmc_launch_finish_nll_jump_pick_combo_factor": [_i, _i, _vp, _sz, _vp, _sz, _sz, _vp, _vp, _vp, _vp, _vp,
                                                       _vp, _vp, _vp, _vp, _vp, _i, _vp, _vp, _vp, _vp, _vp, _i, _vp],
+    "sxmc_launch_finish_nll_jump_pick_combo_constrained": [_i, _i, _vp, _sz, _vp, _sz, _sz, _vp, _vp, _vp, _vp, _vp,
+                                                           _vp, _vp, _vp, _vp, _vp, _i, _vp, _vp, _vp, _vp, _vp, _i, _vp, _vp],
     "sxmc_comm_init_all": [_vp, _i, _pvp],
     "sxmc_comm_unique_id": [C.c_char_p, _sz],
     "sxmc_comm_init_rank": [C.c_char_p, _sz, _i, _i, _pvp],

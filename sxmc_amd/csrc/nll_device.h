@@ -97,7 +97,7 @@ __device__ __forceinline__ void nll_total_device(size_t nparameters, size_t nsig
                                                  const double* sigmas, const double* events_total,
                                                  const double* nexpected, const unsigned* n_mc,
                                                  const short* source_id, const unsigned* norms,
-                                                 double* nll) {
+                                                 double* nll, const double* whitening = nullptr) {
   double sum = -events_total[0];
   if (isnan(sum)) {
     nll[0] = 1e18;
@@ -113,7 +113,18 @@ __device__ __forceinline__ void nll_total_device(size_t nparameters, size_t nsig
       return;
     }
     if (sigmas[i] > 0) {
-      const double x = (pars[i] - means[i]) / sigmas[i];
+      double x = (pars[i] - means[i]) / sigmas[i];
+      if (whitening != nullptr) {
+        // correlated constraints (include/sxmc_hip.h, sxmc_group_set_constraint_whitening): the whitened residual
+        // r_i = sum over j <= i of W_ij x_j, ascending, one fma per term, in the slot constraint i has.  This sequential
+        // form keeps no vector: every x_j is formed again, by the same division.
+        double r = 0.0;
+        for (unsigned j = 0; j <= i; j++) {
+          const double xj = sigmas[j] > 0 ? (pars[j] - means[j]) / sigmas[j] : 0.0;
+          r = __fma_rn(whitening[(size_t)j * nparameters + i], xj, r);
+        }
+        x = r;
+      }
       sum += 0.5 * x * x;
     }
   }
@@ -192,10 +203,12 @@ __device__ __forceinline__ bool finish_step_device_w(size_t npartial_sums, const
                                                      int nparameters, const float* jump_width,
                                                      const double* nexpected, const unsigned* n_mc,
                                                      const short* source_id, const unsigned* norms,
-                                                     const double* factor, bool debug_mode, Wait&& wait) {
+                                                     const double* factor, const double* whitening,
+                                                     bool debug_mode, Wait&& wait) {
   __shared__ double s_wave[17];
   __shared__ double s_vprop[kStage], s_vcur[kStage], s_z[kStage];
   __shared__ double s_d[kStage];            // with a factor: the next proposal's displacement (L z)_i, formed in phase A
+                                            // (ahead of that, with a whitening matrix: the constraints' residuals x)
   __shared__ double s_add[2 * kStage];      // phase B's addends in its order: the signals' terms, then the constraints'
   __shared__ float s_jw[kStage];
   __shared__ unsigned s_badw[16];           // per wave: one of its parameters is a negative source rate
@@ -209,7 +222,7 @@ __device__ __forceinline__ bool finish_step_device_w(size_t npartial_sums, const
     double total_sum = block_sum<BD>(npartial_sums, sums, s_wave);
     if (threadIdx.x == 0) {
       nll_total_device(nparameters, nsignals, nsources, v_proposed, means, sigmas, &total_sum, nexpected, n_mc,
-                       source_id, norms, nll_proposed);
+                       source_id, norms, nll_proposed, whitening);
       jump_decider_device(rng, nll_current, nll_proposed, v_current, v_proposed, nparameters, accepted, counter,
                           jump_buffer, debug_mode);
     }
@@ -247,10 +260,12 @@ __device__ __forceinline__ bool finish_step_device_w(size_t npartial_sums, const
     // (a parameter without a constraint adds -0.0, which leaves every sum as it is, bit for bit: x + -0.0 == x for
     //  every x, both zeros and NaN included)
     double pen = -0.0;
+    double x = 0.0;
     if (sigma > 0) {  // nll_kernels.cpp:181-184
-      const double x = (p - mean) / sigma;
+      x = (p - mean) / sigma;
       pen = 0.5 * x * x;
     }
+    if (whitening != nullptr) s_d[i] = x;   // (an unconstrained parameter's residual is 0: the product reads every x_j)
     if ((size_t)i < nsources && p < 0) negative_rate = true;  // :176-179
     s_pen[i] = pen;
     if (i == 0 || jw > 0) {
@@ -271,6 +286,33 @@ __device__ __forceinline__ bool finish_step_device_w(size_t npartial_sums, const
     if ((threadIdx.x & (kWave - 1)) == 0) s_badw[threadIdx.x / kWave] = any_negative != 0ull ? 1u : 0u;
   }
   __syncthreads();
+  // Correlated constraints (include/sxmc_hip.h, sxmc_group_set_constraint_whitening): lane i's whitened residual
+  // r_i = sum over j <= i of W_ij x_j, ascending in j, one fma per term, and 0.5 r_i^2 in the slot constraint i has in
+  // s_pen -- the sum below keeps its length and its order.  Here, behind the barrier that published x (in s_d, which
+  // nothing else uses yet) and ahead of the wait, so that it runs under the other workgroups' event sums.  W_ij stands
+  // at whitening[j * P + i]: consecutive doubles across a wave for a fixed j, x_j one LDS word for all its lanes; the
+  // loads do not depend on the chain of fmas and eight are in flight at a time.  The barrier behind it completes s_pen
+  // before any lane takes its addends, and lets the factor's loop reuse s_d.  The branch is uniform (a kernel argument).
+  if (whitening != nullptr) {
+    for (int i = threadIdx.x; i < nparameters; i += (int)bdim) {
+      if (sigmas[i] > 0) {   // (an unconstrained parameter keeps its -0.0)
+        const double* col = whitening + i;
+        const size_t P = (size_t)nparameters;
+        double r = 0.0;
+        int j = 0;
+        for (; j + 8 <= i + 1; j += 8) {
+          double w[8];
+#pragma unroll
+          for (int k = 0; k < 8; k++) w[k] = col[(size_t)(j + k) * P];
+#pragma unroll
+          for (int k = 0; k < 8; k++) r = __fma_rn(w[k], s_d[j + k], r);
+        }
+        for (; j <= i; j++) r = __fma_rn(col[(size_t)j * P], s_d[j], r);
+        s_pen[i] = 0.5 * r * r;
+      }
+    }
+    __syncthreads();
+  }
   // Everything phase B adds is known now.  EVERY lane takes it into registers before the wait (the first kRegAdd addends,
   // fetched together; all lanes read the same words), so that what follows the partial sums' reduction is a chain of
   // additions, the exp and the stores: no LDS round trip per addend, and no broadcast of the decision with its barrier --
@@ -363,10 +405,11 @@ __device__ __forceinline__ bool finish_step_device(size_t npartial_sums, const d
                                                    int nparameters, const float* jump_width,
                                                    const double* nexpected, const unsigned* n_mc,
                                                    const short* source_id, const unsigned* norms,
-                                                   const double* factor, bool debug_mode) {
+                                                   const double* factor, const double* whitening,
+                                                   bool debug_mode) {
   return finish_step_device_w<0, R>(npartial_sums, sums, nsignals, nsources, means, sigmas, rng, nll_current, nll_proposed,
                               v_current, v_proposed, accepted, counter, jump_buffer, nparameters, jump_width, nexpected,
-                              n_mc, source_id, norms, factor, debug_mode, [] {});
+                              n_mc, source_id, norms, factor, whitening, debug_mode, [] {});
 }
 
 // What the NEXT call of finish_step_device would propose if the step it decides were rejected -- i.e. from the

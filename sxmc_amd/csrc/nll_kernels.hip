@@ -148,10 +148,10 @@ __global__ void nll_event_reduce_kernel(size_t nthreads, const double* sums, dou
 __global__ void nll_total_kernel(size_t npars, const double* pars, size_t nsignals, size_t nsources,
                                  const double* means, const double* sigmas, const double* events_total,
                                  const double* nexpected, const unsigned* n_mc, const short* source_id,
-                                 const unsigned* norms, double* nll) {
+                                 const unsigned* norms, double* nll, const double* whitening) {
   if (blockIdx.x == 0 && threadIdx.x == 0) {
     nll_total_device(npars, nsignals, nsources, pars, means, sigmas, events_total, nexpected, n_mc,
-                     source_id, norms, nll);
+                     source_id, norms, nll, whitening);
   }
 }
 
@@ -163,10 +163,11 @@ __global__ void finish_nll_jump_pick_combo_kernel(size_t npartial_sums, const do
                                                   int nparameters, const float* jump_width,
                                                   const double* nexpected, const unsigned* n_mc,
                                                   const short* source_id, const unsigned* norms,
-                                                  const double* factor, bool debug_mode) {
+                                                  const double* factor, const double* whitening,
+                                                  bool debug_mode) {
   finish_step_device(npartial_sums, sums, nsignals, nsources, means, sigmas, rng, nll_current, nll_proposed,
                      v_current, v_proposed, accepted, counter, jump_buffer, nparameters, jump_width, nexpected,
-                     n_mc, source_id, norms, factor, debug_mode);
+                     n_mc, source_id, norms, factor, whitening, debug_mode);
 }
 
 }  // namespace
@@ -225,9 +226,9 @@ hipError_t sx_nll_event_reduce(int block, hipStream_t s, size_t n, const double*
 hipError_t sx_nll_total(hipStream_t s, size_t npars, const double* pars, size_t nsignals, size_t nsources,
                         const double* means, const double* sigmas, const double* events_total,
                         const double* nexpected, const unsigned* n_mc, const short* source_id,
-                        const unsigned* norms, double* nll) {
+                        const unsigned* norms, double* nll, const double* whitening) {
   hipLaunchKernelGGL(nll_total_kernel, dim3(1), dim3(64), 0, s, npars, pars, nsignals, nsources, means, sigmas,
-                     events_total, nexpected, n_mc, source_id, norms, nll);
+                     events_total, nexpected, n_mc, source_id, norms, nll, whitening);
   return hipGetLastError();
 }
 
@@ -237,11 +238,11 @@ hipError_t sx_nll_finish_combo(int block, hipStream_t s, size_t npartial, const 
                                int* accepted, int* counter, float* jump_buffer, int nparameters,
                                const float* jump_width, const double* nexpected, const unsigned* n_mc,
                                const short* source_id, const unsigned* norms, const double* factor,
-                               bool debug_mode) {
+                               const double* whitening, bool debug_mode) {
   hipLaunchKernelGGL(finish_nll_jump_pick_combo_kernel, dim3(1), dim3(block), 0, s, npartial, sums, nsignals,
                      nsources, means, sigmas, rng, nll_current, nll_proposed, v_current, v_proposed, accepted,
                      counter, jump_buffer, nparameters, jump_width, nexpected, n_mc, source_id, norms, factor,
-                     debug_mode);
+                     whitening, debug_mode);
   return hipGetLastError();
 }
 

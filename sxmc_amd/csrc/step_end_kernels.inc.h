@@ -272,7 +272,7 @@ __device__ __forceinline__ bool finish_step_w(size_t npartial, const double* sum
   return sxdev::finish_step_device_w<BD, R>(npartial, sums, a.nsignals, a.nsources, a.means, a.sigmas, a.rng,
                                             a.nll_current, a.nll_proposed, a.v_current, a.v_proposed, a.accepted,
                                             a.counter, a.jump_buffer, a.nparameters, a.jump_width, a.nexpected, a.n_mc,
-                                            a.source_id, norms, a.factor, a.debug_mode != 0, wait);
+                                            a.source_id, norms, a.factor, a.whitening, a.debug_mode != 0, wait);
 }
 template <int R = 32>
 __device__ __forceinline__ bool finish_step(size_t npartial, const double* sums, const SxStepArgs& a,

@@ -39,6 +39,10 @@ struct SxStepArgs {
   // proposal (include/sxmc_hip.h, sxmc_group_set_proposal_factor).  Staged step ends only (at most 256 parameters and
   // signals); the look-ahead pass and the lockstep sets' joint ends never get one.
   const double* factor = nullptr;
+  // correlated constraints' whitening matrix, P x P doubles, lower triangular with W_ij at [j * P + i], or null: one
+  // independent Gaussian per parameter (include/sxmc_hip.h, sxmc_group_set_constraint_whitening).  Staged step ends only,
+  // as the factor.
+  const double* whitening = nullptr;
 };
 
 // The cooperative step end's look-up pointers BY VALUE (step_end_kernel<true>): per member the two tables a worker's

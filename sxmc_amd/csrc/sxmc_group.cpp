@@ -14,9 +14,18 @@ int proposal_factor_check(const double* factor, int nparameters, size_t nsignals
   return SXMC_OK;
 }
 
-SxStepArgs sx_step_args(const sxmc_step_args& p, size_t nsignals, const double* factor) {
+int constraint_whitening_check(const double* whitening, int nparameters, size_t nsignals) {
+  if (whitening && (nparameters > 256 || nsignals > 256)) {
+    return fail(SXMC_ERR_SHAPE,
+                "a constraint whitening matrix needs the staged step end: at most 256 parameters and 256 signals");
+  }
+  return SXMC_OK;
+}
+
+SxStepArgs sx_step_args(const sxmc_step_args& p, size_t nsignals, const double* factor, const double* whitening) {
   SxStepArgs a;   // (the measurement build's gate keeps its defaults)
   a.factor = factor;
+  a.whitening = whitening;
   a.nsignals = nsignals;
   a.nsources = p.nsources;
   a.means = p.d_means;
@@ -515,6 +524,12 @@ int sxmc_group_set_event_weights(sxmc_group_t g, const double* h_weights, size_t
   return SXMC_OK;
 }
 
+int sxmc_group_set_constraint_whitening(sxmc_group_t g, const double* d_whitening) {
+  SX_REQUIRE(g, "null group");
+  g->constraint_whitening = d_whitening;   // (borrowed; read by sx_step_args at every step end the group launches)
+  return SXMC_OK;
+}
+
 int sxmc_group_set_proposal_factor(sxmc_group_t g, const double* d_factor) {
   SX_REQUIRE(g, "null group");
   g->proposal_factor = d_factor;   // (borrowed; read by sx_step_args at every step end the group launches)
@@ -616,6 +631,7 @@ int sxmc_group_mcmc_step_async(sxmc_group_t g, sxmc_stream_t s, const double* d_
              "null argument");
   SX_REQUIRE(nparameters > 0, "nparameters must be positive");
   if (int bad = proposal_factor_check(g->proposal_factor, nparameters, g->members.size())) return bad;
+  if (int bad = constraint_whitening_check(g->constraint_whitening, nparameters, g->members.size())) return bad;
   int rc = group_refresh(g);
   if (rc) return rc;
   rc = group_check_bound(g, true);
@@ -636,7 +652,8 @@ int sxmc_group_mcmc_step_async(sxmc_group_t g, sxmc_stream_t s, const double* d_
   SX_HIP(rows.with_weight([&](auto w) {
     return sx_launch_eval_nll_finish(rows.descs, (int)g->members.size(), rows.ne, w, g->d_step_sums.get(),
                                      g->d_ticket.get() + sxstep::kTicket,
-                                     sx_step_args(p, g->members.size(), g->proposal_factor), step_sum_blocks(rows.ne),
+                                     sx_step_args(p, g->members.size(), g->proposal_factor, g->constraint_whitening),
+                                     step_sum_blocks(rows.ne),
                                      (int)sxstep::kStepSumRows, st);
   }));
   return SXMC_OK;
@@ -661,8 +678,9 @@ int sxmc_group_finish_step_async(sxmc_group_t g, sxmc_stream_t s, size_t npartia
                                           d_accepted, d_counter, d_jump_buffer, nparameters, nsources, d_jump_width,
                                           d_nexpected, d_n_mc, d_source_id, d_norms, debug_mode);
   if (int rc = proposal_factor_check(g->proposal_factor, nparameters, g->members.size())) return rc;
+  if (int rc = constraint_whitening_check(g->constraint_whitening, nparameters, g->members.size())) return rc;
   return finish_and_clear(g, (hipStream_t)s, g->last_sparse, npartial_sums, d_sums,
-                          sx_step_args(p, g->members.size(), g->proposal_factor));
+                          sx_step_args(p, g->members.size(), g->proposal_factor, g->constraint_whitening));
 }
 
 // ------------------------------------------------------------------------------ mixed fits
@@ -739,8 +757,9 @@ int sxmc_group_finish_columns_step_async(sxmc_group_t g, sxmc_stream_t s, size_t
                                           d_nexpected, d_n_mc, d_source_id, d_norms, debug_mode);
   // (the step end runs over every column; the clearing over the members)
   if (int rc = proposal_factor_check(g->proposal_factor, nparameters, g->col_member.size())) return rc;
+  if (int rc = constraint_whitening_check(g->constraint_whitening, nparameters, g->col_member.size())) return rc;
   const int rc = finish_and_clear(g, (hipStream_t)s, g->last_sparse, npartial_sums, d_sums,
-                                  sx_step_args(p, g->col_member.size(), g->proposal_factor));
+                                  sx_step_args(p, g->col_member.size(), g->proposal_factor, g->constraint_whitening));
   if (rc == SXMC_OK) g->last_stream = (hipStream_t)s;
   return rc;
 }
@@ -879,6 +898,7 @@ int sxmc_group_step_async(sxmc_group_t g, sxmc_stream_t s, const double* d_means
              "null argument");
   SX_REQUIRE(nparameters > 0, "nparameters must be positive");
   if (int bad = proposal_factor_check(g->proposal_factor, nparameters, g->members.size())) return bad;
+  if (int bad = constraint_whitening_check(g->constraint_whitening, nparameters, g->members.size())) return bad;
   int rc = group_refresh(g);
   if (rc) return rc;
   rc = group_check_bound(g, true);
@@ -897,7 +917,7 @@ int sxmc_group_step_async(sxmc_group_t g, sxmc_stream_t s, const double* d_means
   const sxmc_step_args p = pack_step_args(d_means, d_sigmas, d_rng, d_nll_current, d_nll_proposed, d_v_current, d_v_proposed,
                                           d_accepted, d_counter, d_jump_buffer, nparameters, nsources, d_jump_width,
                                           d_nexpected, d_n_mc, d_source_id, d_norms, debug_mode);
-  SxStepArgs a = sx_step_args(p, g->members.size(), g->proposal_factor);
+  SxStepArgs a = sx_step_args(p, g->members.size(), g->proposal_factor, g->constraint_whitening);
   // THE WHOLE STEP IN ONE LAUNCH where the fill has that form (fill_step_kernel: the fill's workgroups, then a finisher
   // and the event sum's workers as later blocks of the same grid) -- not for a launch whose fill is being timed
   // (sxmc_group_profile: the fill alone is what the roofline figures are about, so profiled steps stay two launches)

@@ -61,11 +61,12 @@ hipError_t sx_nll_event_chunks_weighted(int, int, hipStream_t, const float*, con
                                         const double*);
 hipError_t sx_nll_event_reduce(int, hipStream_t, size_t, const double*, double*);
 hipError_t sx_nll_total(hipStream_t, size_t, const double*, size_t, size_t, const double*, const double*,
-                        const double*, const double*, const unsigned*, const short*, const unsigned*, double*);
+                        const double*, const double*, const unsigned*, const short*, const unsigned*, double*,
+                        const double*);
 hipError_t sx_nll_finish_combo(int, hipStream_t, size_t, const double*, size_t, size_t, const double*,
                                const double*, sxmc_rng_state*, double*, double*, double*, double*, int*, int*,
                                float*, int, const float*, const double*, const unsigned*, const short*,
-                               const unsigned*, const double*, bool);
+                               const unsigned*, const double*, const double*, bool);
 }
 
 
@@ -410,6 +411,7 @@ struct sxmc_group {
   unsigned long long plan_generation = 0;          // counts launch plans built (a multigroup re-validates on change)
   int debug_mode = 0;
   const double* proposal_factor = nullptr;         // sxmc_group_set_proposal_factor: borrowed, P x P doubles, or null (diagonal)
+  const double* constraint_whitening = nullptr;    // sxmc_group_set_constraint_whitening: borrowed, P x P doubles, or null (independent)
   // measurement build only (the gated step): the stream this group's NEXT step puts its fill on, beside the step end of
   // the step before (null: the step is launched on one stream, as always), and the step's index inside its recording
   hipStream_t split_fill_stream = nullptr;
@@ -536,9 +538,12 @@ extern std::atomic<int> g_stepping_groups;       // groups of this process that 
 using sxstep::kCoopMaxWorkers;
 using sxstep::step_sum_blocks;
 // the kernels' argument pack from the public one; nsignals: the columns finish_nll_jump_pick_combo runs over
-SxStepArgs sx_step_args(const sxmc_step_args& p, size_t nsignals, const double* factor = nullptr);
+SxStepArgs sx_step_args(const sxmc_step_args& p, size_t nsignals, const double* factor = nullptr,
+                        const double* whitening = nullptr);
 // SXMC_ERR_SHAPE where a step end over these many parameters and signals cannot take the factor (its unstaged form)
 int proposal_factor_check(const double* factor, int nparameters, size_t nsignals);
+// the same for the correlated constraints' whitening matrix
+int constraint_whitening_check(const double* whitening, int nparameters, size_t nsignals);
 // The rows a step end walks: the event classes (their descriptors, events per class, K) or, with the lookup table
 // wanted, the events themselves.  ensure_event_classes comes first, before anything is launched: the caller's.
 struct StepRows {

@@ -138,6 +138,12 @@ int sxmc_multigroup_step_async(sxmc_multigroup_t mg, sxmc_stream_t s, const sxmc
                                   "-- step the chains one by one (sxmc_group_step_async)");
     }
   }
+  for (const sxmc_group* g : mg->groups) {
+    if (g->constraint_whitening) {
+      return fail(SXMC_ERR_STATE, "a member group has a constraint whitening matrix set: lockstep sets have no step end "
+                                  "with correlated constraints -- step the chains one by one (sxmc_group_step_async)");
+    }
+  }
   // every chain's own plan first (may upload: before anything is launched)
   bool replan = mg->seen.size() != C;
   for (size_t c = 0; c < C; c++) {
@@ -260,6 +266,13 @@ int sxmc_multigroup_lookahead_step_async(sxmc_multigroup_t mg, sxmc_stream_t s, 
                                   "-- walk sequentially (sxmc_group_lookahead_supported says so beforehand)");
     }
   }
+  for (const sxmc_group* g : mg->groups) {
+    if (g->constraint_whitening) {
+      return fail(SXMC_ERR_STATE, "a member group has a constraint whitening matrix set: the look-ahead pass has no form "
+                                  "with correlated constraints -- walk sequentially (sxmc_group_lookahead_supported "
+                                  "says so beforehand)");
+    }
+  }
   hipStream_t st = (hipStream_t)s;
   bool replan = mg->seen.size() != 2;
   for (size_t c = 0; c < 2; c++) {
@@ -349,6 +362,7 @@ int sxmc_group_lookahead_supported(sxmc_group_t g, int* ok) {
   SX_REQUIRE(g && ok, "null argument");
   *ok = 0;
   if (g->proposal_factor) return SXMC_OK;   // (no correlated look-ahead pass; asked before the group is touched)
+  if (g->constraint_whitening) return SXMC_OK;   // (nor one with correlated constraints)
   if (!g->event_weights.empty()) return SXMC_OK;   // (nor a weighted one)
   if (weighted_members(g)) return SXMC_OK;         // (nor one over sample multiplicities)
   g->plan_cfg.box = 0;  // (the pass runs over the ordered form; the question could be asked of g->ordered and leave the setting alone)

@@ -2,6 +2,7 @@
 // the test hooks.
 #include "sxmc_host.h"
 
+#include "constraint_whitening.h"
 #include "proposal_factor.h"
 #include "sample_multiplicities.h"
 
@@ -91,7 +92,20 @@ int sxmc_launch_nll_total(int grid, int block, sxmc_stream_t s, size_t nparamete
   SX_ORDER(s);
   if (int rc = check_launch(grid, block)) return rc;
   SX_HIP(sx_nll_total((hipStream_t)s, nparameters, d_pars, nsignals, nsources, d_means, d_sigmas, d_events_total,
-                      d_nexpected, d_n_mc, d_source_id, d_norms, d_nll));
+                      d_nexpected, d_n_mc, d_source_id, d_norms, d_nll, nullptr));
+  return SXMC_OK;
+}
+
+int sxmc_launch_nll_total_whitened(int grid, int block, sxmc_stream_t s, size_t nparameters, const double* d_pars,
+                                   size_t nsignals, size_t nsources, const double* d_means, const double* d_sigmas,
+                                   const double* d_events_total, const double* d_nexpected, const unsigned* d_n_mc,
+                                   const short* d_source_id, const unsigned* d_norms, double* d_nll,
+                                   const double* d_whitening) {
+  SX_FLUSH();
+  SX_ORDER(s);
+  if (int rc = check_launch(grid, block)) return rc;
+  SX_HIP(sx_nll_total((hipStream_t)s, nparameters, d_pars, nsignals, nsources, d_means, d_sigmas, d_events_total,
+                      d_nexpected, d_n_mc, d_source_id, d_norms, d_nll, d_whitening));
   return SXMC_OK;
 }
 
@@ -110,7 +124,7 @@ int sxmc_launch_finish_nll_jump_pick_combo(int grid, int block, sxmc_stream_t s,
   SX_HIP(sx_nll_finish_combo(block, (hipStream_t)s, npartial_sums, d_sums, nsignals, nsources, d_means, d_sigmas,
                              d_rng, d_nll_current, d_nll_proposed, d_v_current, d_v_proposed, d_accepted,
                              d_counter, d_jump_buffer, nparameters, d_jump_width, d_nexpected, d_n_mc, d_source_id,
-                             d_norms, nullptr, debug_mode != 0));
+                             d_norms, nullptr, nullptr, debug_mode != 0));
   return SXMC_OK;
 }
 
@@ -131,7 +145,45 @@ int sxmc_launch_finish_nll_jump_pick_combo_factor(int grid, int block, sxmc_stre
   SX_HIP(sx_nll_finish_combo(block, (hipStream_t)s, npartial_sums, d_sums, nsignals, nsources, d_means, d_sigmas,
                              d_rng, d_nll_current, d_nll_proposed, d_v_current, d_v_proposed, d_accepted,
                              d_counter, d_jump_buffer, nparameters, d_jump_width, d_nexpected, d_n_mc, d_source_id,
-                             d_norms, d_factor, debug_mode != 0));
+                             d_norms, d_factor, nullptr, debug_mode != 0));
+  return SXMC_OK;
+}
+
+int sxmc_launch_finish_nll_jump_pick_combo_constrained(int grid, int block, sxmc_stream_t s, size_t npartial_sums,
+                                                       const double* d_sums, size_t nsignals, size_t nsources,
+                                                       const double* d_means, const double* d_sigmas,
+                                                       sxmc_rng_state* d_rng, double* d_nll_current,
+                                                       double* d_nll_proposed, double* d_v_current,
+                                                       double* d_v_proposed, int* d_accepted, int* d_counter,
+                                                       float* d_jump_buffer, int nparameters,
+                                                       const float* d_jump_width, const double* d_nexpected,
+                                                       const unsigned* d_n_mc, const short* d_source_id,
+                                                       const unsigned* d_norms, int debug_mode, const double* d_factor,
+                                                       const double* d_whitening) {
+  SX_FLUSH();
+  SX_ORDER(s);
+  if (int rc = check_launch(grid, block)) return rc;
+  SX_REQUIRE(grid == 1, "finish_nll_jump_pick_combo runs in one workgroup");
+  if (int rc = proposal_factor_check(d_factor, nparameters, nsignals)) return rc;
+  if (int rc = constraint_whitening_check(d_whitening, nparameters, nsignals)) return rc;
+  SX_HIP(sx_nll_finish_combo(block, (hipStream_t)s, npartial_sums, d_sums, nsignals, nsources, d_means, d_sigmas,
+                             d_rng, d_nll_current, d_nll_proposed, d_v_current, d_v_proposed, d_accepted,
+                             d_counter, d_jump_buffer, nparameters, d_jump_width, d_nexpected, d_n_mc, d_source_id,
+                             d_norms, d_factor, d_whitening, debug_mode != 0));
+  return SXMC_OK;
+}
+
+// The whitening matrix of correlated constraints: host arithmetic only (constraint_whitening.h), nothing of the device
+// is touched.
+int sxmc_constraint_whitening(const double* rho, const double* sigmas, int P, double* W) {
+  SX_REQUIRE(rho && sigmas && W && P >= 1, "bad arguments");
+  const std::string why = sxconstraint::check_correlation(rho, sigmas, (size_t)P);
+  if (!why.empty()) return fail(SXMC_ERR_INVALID, why);
+  const long pivot = sxconstraint::whitening(rho, (size_t)P, W);
+  if (pivot >= 0) {
+    return fail(SXMC_ERR_INVALID,
+                "constraint correlation: not positive definite at parameter " + std::to_string(pivot));
+  }
   return SXMC_OK;
 }
 

@@ -401,12 +401,13 @@ def projection_interval(values, cl=0.9, nbins=100):
 # ------------------------------------------------------------------------------------ the ensemble
 def run_experiment(workload, seed, nsteps, burnin_fraction=0.1, cl=0.9, sync_interval=10000, mcmc=None,
                    form="fused", graph_steps=0, lookahead=False, proposal="diagonal", proposal_shrinkage=0.05,
-                   data=None, event_weights=None):
+                   data=None, event_weights=None, constraint_correlation=None):
     """One iteration of the loop in sxmc.cpp:59-145: fake data -> MCMC -> intervals.
     Reuses `mcmc` (evaluators with the MC tables resident in HBM) across experiments when given.
     lookahead: walk with two evaluations per pass over the tables (MCMC.walk(lookahead=True): the same chain, about a
     quarter more steps per second when one experiment has the GPU to itself; `mcmc` then needs a created stream).
     proposal, proposal_shrinkage: MCMC.walk's ("covariance": the correlated proposal; it walks sequentially).
+    constraint_correlation: MCMC.walk's (correlated Gaussian constraints; such a walk is sequential too).
     data, event_weights: fit this data set (with these event weights: MCMC.walk's) instead of a fake one -- the Asimov
     data set of make_asimov_dataset, for instance.
     Returns (intervals float32 [P, 4], chain, accepted)."""
@@ -422,12 +423,14 @@ def run_experiment(workload, seed, nsteps, burnin_fraction=0.1, cl=0.9, sync_int
         data, _ = make_fake_dataset(rng, workload, mcmc.pdfs, poisson=True)
     chain, accepted = mcmc.walk(data, nsteps, burnin_fraction, sync_interval=sync_interval, graph_steps=graph_steps,
                                 lookahead=lookahead and mcmc.stream is not None and mcmc.consume, proposal=proposal,
-                                proposal_shrinkage=proposal_shrinkage, event_weights=event_weights)
+                                proposal_shrinkage=proposal_shrinkage, event_weights=event_weights,
+                                constraint_correlation=constraint_correlation)
     return contour_intervals(chain, cl), chain, accepted
 
 
 def run_experiments_in_lockstep(workload, seeds, nsteps, sets, burnin_fraction=0.1, cl=0.9, sync_interval=10000,
-                                graph_steps=0, timing=None, proposal="diagonal", event_weights=None):
+                                graph_steps=0, timing=None, proposal="diagonal", event_weights=None,
+                                constraint_correlation=None):
     """len(seeds) fake experiments at once on one GPU, the chains grouped into lockstep sets (mcmc.LockstepChains:
     the chains of a set share a stream and ONE fill pass per step; different sets run on different streams, so one
     set's step ends overlap another's fill).  Same schedule of re-tunings and flushes as a single walk; every
@@ -439,6 +442,9 @@ def run_experiments_in_lockstep(workload, seeds, nsteps, sets, burnin_fraction=0
     if event_weights is not None:
         raise ValueError("lockstep sets have no weighted step end: weighted events (an Asimov data set) are fitted one "
                          "experiment per chain (run_experiment)")
+    if constraint_correlation is not None:
+        raise ValueError("lockstep sets have no step end with correlated constraints: constraint_correlation walks one "
+                         "experiment per chain (run_experiment, run_experiments_concurrently)")
     if proposal != "diagonal":
         raise ValueError("lockstep sets have no correlated step end: proposal %r walks one experiment per chain "
                          "(run_experiment, run_experiments_concurrently)" % (proposal,))
@@ -482,7 +488,8 @@ def run_experiments_in_lockstep(workload, seeds, nsteps, sets, burnin_fraction=0
 
 
 def run_experiments_concurrently(workload, seeds, nsteps, chains, burnin_fraction=0.1, cl=0.9, sync_interval=10000,
-                                 graph_steps=0, proposal="diagonal", proposal_shrinkage=0.05):
+                                 graph_steps=0, proposal="diagonal", proposal_shrinkage=0.05,
+                                 constraint_correlation=None):
     """len(chains) fake experiments at once on one GPU (BASELINE config 4: one experiment per stream):
     the chains share one resident copy of the MC tables (MCMC(..., share_with=...), own non-blocking
     streams) and are advanced in turn, so one experiment's small kernels overlap another's fill.
@@ -494,7 +501,7 @@ def run_experiments_concurrently(workload, seeds, nsteps, chains, burnin_fractio
         m.reseed(seed & 0xFFFFFFFF)
         data, _ = make_fake_dataset(rng, workload, m.pdfs, poisson=True)
         m.walk_begin(data, nsteps, burnin_fraction, sync_interval=sync_interval, proposal=proposal,
-                     proposal_shrinkage=proposal_shrinkage)
+                     proposal_shrinkage=proposal_shrinkage, constraint_correlation=constraint_correlation)
     if graph_steps <= 0:
         for i in range(nsteps):
             for m in chains:

@@ -686,6 +686,9 @@ struct FitConfig {
   std::string samples;   //!< fit.samples: a saved chain to take the intervals from INSTEAD of walking (sxmc.cpp:84-94)
   std::string proposal = "diagonal";   //!< fit.proposal: "diagonal" (the reference's) or "covariance" (mcmc.h: Proposal)
   double proposal_shrinkage = 0.05;    //!< fit.proposal_shrinkage in (0, 1]: only with "covariance"
+  std::vector<double> constraint_correlation;   //!< fit.constraint_correlations scattered into the P x P correlation
+                                       //!< matrix over the walk's parameter vector (row-major), validated by
+                                       //!< sxmc_constraint_whitening; empty without the key (mcmc.h: constraint_correlation)
   bool asimov = false;                 //!< fit.asimov: fit exactly one data set, the Asimov one (fake_data.h:
                                        //!< make_asimov_dataset); refused together with configured data sets
   std::vector<Observable> observables, cuts;
@@ -879,6 +882,71 @@ inline void fit_asimov_from_json(FitConfig& fc, const json::Value& fit, bool has
 }
 }  // namespace detail
 
+namespace detail {
+/** The fit's "constraint_correlations": a list of groups {"parameters": [names], "matrix": [[...]]} that tie the Gaussian
+ *  constraints of the named parameters together.  Names are the walk's parameter names (sources, then
+ *  <systematic>_<j>); groups are disjoint; each matrix is square, of its group's size.  The groups are scattered into the
+ *  P x P identity and the whole is validated by sxmc_constraint_whitening (symmetric, unit diagonal, entries in [-1, 1],
+ *  positive definite, no correlated parameter without a sigma).  A configuration without the key loads as before
+ *  (fc.constraint_correlation stays empty).  Same rules and messages as sxmc_amd.io.fit_constraint_correlations. */
+inline void fit_constraint_correlations_from_json(FitConfig& fc, const json::Value& fit) {
+  fc.constraint_correlation.clear();
+  if (!fit.isMember("constraint_correlations")) return;
+  const json::Value& groups = fit["constraint_correlations"];
+  if (groups.kind != json::Value::Array) throw ConfigError("fit: \"constraint_correlations\" is not a list of groups");
+  std::vector<std::string> names;
+  std::vector<double> sigmas;
+  for (const Source& s : fc.sources) {
+    names.push_back(s.name);
+    sigmas.push_back((double)s.sigma);
+  }
+  for (const Systematic& s : fc.systematics) {
+    for (size_t j = 0; j < s.npars; j++) {
+      names.push_back(s.name + "_" + std::to_string(j));
+      sigmas.push_back(s.sigmas[j]);
+    }
+  }
+  const size_t P = names.size();
+  std::vector<double> rho(P * P, 0.0);
+  for (size_t i = 0; i < P; i++) rho[i * P + i] = 1.0;
+  std::vector<char> taken(P, 0);
+  for (size_t g = 0; g < groups.items.size(); g++) {
+    const std::string where = "fit: constraint_correlations[" + std::to_string(g) + "]: ";
+    const json::Value& grp = groups.items[g];
+    const json::Value& pars = grp["parameters"];
+    const json::Value& matrix = grp["matrix"];
+    if (grp.kind != json::Value::Object || pars.kind != json::Value::Array || matrix.kind != json::Value::Array) {
+      throw ConfigError(where + "a group is {\"parameters\": [names], \"matrix\": [[...]]}");
+    }
+    std::vector<size_t> index;
+    for (const json::Value& nv : pars.items) {
+      const std::string& name = nv.asString("parameters[]");
+      const size_t at = std::find(names.begin(), names.end(), name) - names.begin();
+      if (at >= P) throw ConfigError(where + "unknown parameter \"" + name + "\"");
+      if (taken[at]) throw ConfigError(where + "parameter \"" + name + "\" is already in a group");
+      taken[at] = 1;
+      index.push_back(at);
+    }
+    const size_t n = index.size();
+    bool square = matrix.items.size() == n;
+    for (size_t r = 0; square && r < n; r++) {
+      square = matrix.items[r].kind == json::Value::Array && matrix.items[r].items.size() == n;
+    }
+    if (!square) {
+      throw ConfigError(where + "\"matrix\" must be " + std::to_string(n) + " x " + std::to_string(n) + " for its " +
+                        std::to_string(n) + " parameters");
+    }
+    for (size_t r = 0; r < n; r++)
+      for (size_t c = 0; c < n; c++) rho[index[r] * P + index[c]] = matrix.items[r].items[c].asDouble("matrix[][]");
+  }
+  std::vector<double> W(P * P);
+  if (P == 0 || sxmc_constraint_whitening(rho.data(), sigmas.data(), (int)P, W.data()) != SXMC_OK) {
+    throw ConfigError(std::string("fit: constraint_correlations: ") + (P == 0 ? "no parameters" : sxmc_last_error()));
+  }
+  fc.constraint_correlation = rho;
+}
+}  // namespace detail
+
 inline FitConfig parse_config(const std::string& text, const std::string& base_dir, bool load_tables = true) {
   const json::Value root = json::parse(text);
   const json::Value& fit = root["fit"];
@@ -954,6 +1022,8 @@ inline FitConfig parse_config(const std::string& text, const std::string& base_d
                                   sc.get("fixed", false)));
     }
   }
+
+  detail::fit_constraint_correlations_from_json(fc, fit);   // (the parameter vector's layout is known now)
 
   // order of the sampled fields: observables, extra truth fields, DATASET (config.cpp:153-194)
   for (Observable& o : fc.observables) o.field_index = detail::index_with_append(fc.sample_fields, o.field);

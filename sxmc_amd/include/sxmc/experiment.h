@@ -99,6 +99,8 @@ struct ExperimentOptions {
   SetupLock* device_exclusive = nullptr;
   Proposal proposal = Proposal::DIAGONAL;   //!< MCMC::proposal of every chain the runner builds (fit.proposal);
   double proposal_shrinkage = 0.05;         //!< ensemble_lockstep refuses COVARIANCE: its sets have no such step end
+  std::vector<double> constraint_correlation = {};   //!< MCMC::constraint_correlation of every chain the runner builds (the
+                                            //!< fit's constraint_correlations, scattered); ensemble_lockstep refuses it
   bool asimov = false;   //!< fit.asimov: fit exactly ONE data set, the Asimov one (make_asimov_dataset: weighted events) --
                          //!< ensemble and ensemble_concurrent then run the first of `experiments` alone and say so through
                          //!< the report; ensemble_lockstep and ensemble_multi_gpu refuse it (no weighted lockstep step
@@ -174,6 +176,7 @@ inline std::unique_ptr<MCMC> experiment_chain(std::vector<Source>& sources, std:
   mcmc->graph_steps = opt.graph_steps;
   mcmc->proposal = opt.proposal;
   mcmc->proposal_shrinkage = opt.proposal_shrinkage;
+  mcmc->constraint_correlation = opt.constraint_correlation;
   mcmc->exclusive = lane.exclusive;
   mcmc->lockstep = lane.lockstep;
   mcmc->lockstep_index = lane.lockstep_index;
@@ -422,6 +425,10 @@ inline std::vector<ExperimentResult> ensemble_lockstep(const std::vector<unsigne
                                                        std::vector<Observable>& observables, unsigned nsteps,
                                                        float burnin_fraction, unsigned chains_per_set, unsigned nsets,
                                                        const ExperimentOptions& opt) {
+  if (!opt.constraint_correlation.empty()) {
+    throw pdfz::Error("ensemble_lockstep: a lockstep set has no step end with correlated constraints: run an ensemble "
+                      "with a constraint_correlation one experiment per chain (ensemble, ensemble_concurrent)");
+  }
   if (opt.proposal == Proposal::COVARIANCE) {
     throw pdfz::Error("ensemble_lockstep: a lockstep set has no correlated step end: run a COVARIANCE ensemble one "
                       "experiment per chain (ensemble, ensemble_concurrent)");

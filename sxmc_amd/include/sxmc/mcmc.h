@@ -307,6 +307,13 @@ class MCMC {
                                             //!< form takes it; asked with lookahead the walk goes sequentially; a chain
                                             //!< of a lockstep set refuses it
   double proposal_shrinkage = 0.05;         //!< in (0, 1]: the correlations are shrunk towards the identity by this much
+  std::vector<double> constraint_correlation;   //!< empty: one independent Gaussian constraint per parameter.  Otherwise
+                                            //!< P x P, a correlation matrix over the parameter vector (sources, then the
+                                            //!< systematics' parameters) that ties the constraints together: the NLL's
+                                            //!< constraint terms become 0.5 r_i^2 of the whitened residuals r = W x
+                                            //!< (README, "Correlated constraints"; sxmc_constraint_whitening validates and
+                                            //!< whitens).  Every sequential form takes it; asked with lookahead the walk
+                                            //!< goes sequentially; a chain of a lockstep set refuses it
   LockstepSet* lockstep = nullptr;  //!< set: this chain steps together with the other chains of the set (same
   size_t lockstep_index = 0;        //!< sample tables, same systematics, the set's stream); every run of steps is
                                     //!< launched (graph replays of graph_steps steps) by the chain that arrives last
@@ -507,6 +514,9 @@ class MCMC {
     if (shrinkage_used) *shrinkage_used = last_shrinkage;
     return last_factor;
   }
+  /** The whitening matrix the last walk's constraints went through, P x P doubles with W_ij at [j * P + i]; empty
+   *  after a walk without constraint_correlation. */
+  const std::vector<double>& ConstraintWhitening() const { return last_whitening; }
   /** The form the steps of the last walk took (walk_plan.h: WalkForm::Step), valid after a walk: "reference", "batched",
    *  "consuming", "lockstep", "lookahead" or "mixed". */
   const char* WalkFormName() const { return form_name; }
@@ -540,14 +550,15 @@ class MCMC {
 
   /** MCMC::nll (mcmc.cpp:390-415): three launches over an evaluated lookup table. */
   void nll(const float* lut, size_t nevents, const double* v, double* out, const unsigned* norms,
-           double* event_partial_sums, double* event_total_sum, const double* weights = nullptr) {
+           double* event_partial_sums, double* event_total_sum, const double* weights = nullptr,
+           const double* whitening = nullptr) {
     event_chunks(stream, lut, nevents, v, nexpected->readOnlyPtr(), n_mc->readOnlyPtr(), source_id->readOnlyPtr(), norms,
                  event_partial_sums, weights);
     SXMC_KERNEL_LAUNCH(nll_event_reduce, 1, nreducethreads, nreducethreads * sizeof(double), stream,
                        (size_t)nnllthreads, event_partial_sums, event_total_sum);
     SXMC_KERNEL_LAUNCH(nll_total, 1, 1, 0, stream, nparameters, v, nsignals, nsources,
                        parameter_means->readOnlyPtr(), parameter_sigma->readOnlyPtr(), event_total_sum,
-                       nexpected->readOnlyPtr(), n_mc->readOnlyPtr(), source_id->readOnlyPtr(), norms, out);
+                       nexpected->readOnlyPtr(), n_mc->readOnlyPtr(), source_id->readOnlyPtr(), norms, out, whitening);
   }
 
   static double column_stddev(const Chain& c, size_t col) {
@@ -623,6 +634,8 @@ class MCMC {
     std::unique_ptr<pdfz::Array<double>> weights;     // ... on the device, for the weighted launch point
     const bool covariance;            // the walk's proposal is the correlated one
     std::unique_ptr<pdfz::Array<double>> factor;   // its factor, P x P: one device array for the walk's lifetime (none otherwise)
+    const bool constrained;           // the walk's constraints are correlated
+    std::unique_ptr<pdfz::Array<double>> whitening;   // their whitening matrix, P x P, on the device (none otherwise)
     std::unique_ptr<Shadow> shadow;   // look-ahead walk only
     OwnedGraph graph;
     OwnedStream own_stream;           // recorded steps need a created stream: the walk's own when it was given none
@@ -631,6 +644,7 @@ class MCMC {
     StepArgs d;
     const double* d_factor = nullptr; // the factor on the device, or null: resolved with d
     const double* d_weights = nullptr; // the event weights on the device, or null: resolved with d
+    const double* d_whitening = nullptr; // the constraints' whitening matrix on the device, or null: resolved with d
     bool two_forms = false;           // the plan holds a boxed and an ordered form of the fill (asked at every run)
     bool setup_announced = false;     // on_setup_done has been called
     bool torn_down = false;
@@ -661,6 +675,8 @@ class MCMC {
           event_weights(event_weights_),
           covariance(m_.proposal == Proposal::COVARIANCE),
           factor(covariance ? new pdfz::Array<double>(m_.nparameters * m_.nparameters, true) : nullptr),
+          constrained(!m_.constraint_correlation.empty()),
+          whitening(constrained ? new pdfz::Array<double>(m_.nparameters * m_.nparameters, true) : nullptr),
           strm(m_.stream) {
       std::memset(&d, 0, sizeof d);
       chain.names = m.parameter_names;
@@ -693,6 +709,21 @@ class MCMC {
       if (covariance) {
         if (m.lockstep) throw pdfz::Error("MCMC: a lockstep set has no correlated step end: walk a COVARIANCE chain alone");
         rebuild_factor(nullptr, 0);   // (L = diag(w), through the re-tuning's own code)
+      }
+      m.last_whitening.clear();
+      if (constrained) {
+        if (m.constraint_correlation.size() != m.nparameters * m.nparameters) {
+          throw pdfz::Error("MCMC: constraint_correlation holds " + std::to_string(m.constraint_correlation.size()) +
+                            " entries for " + std::to_string(m.nparameters) + " x " + std::to_string(m.nparameters));
+        }
+        if (m.lockstep) {
+          throw pdfz::Error("MCMC: a lockstep set has no step end with correlated constraints: walk a chain with a "
+                            "constraint_correlation alone");
+        }
+        // (validated and whitened by the library's one implementation; a refusal names the entry or the pivot)
+        check(sxmc_constraint_whitening(m.constraint_correlation.data(), m.parameter_sigma->readOnlyHostPtr(),
+                                        (int)m.nparameters, whitening->writeOnlyHostPtr()));
+        m.last_whitening.assign(whitening->readOnlyHostPtr(), whitening->readOnlyHostPtr() + m.nparameters * m.nparameters);
       }
       if (event_weights) {
         if (event_weights->size() != nevents) {
@@ -729,7 +760,7 @@ class MCMC {
       }
       m.nll(lut.readOnlyPtr(), nevents, current_vector.readOnlyPtr(), current_nll.writeOnlyPtr(),
             normalizations.readOnlyPtr(), event_partial_sums.ptr(), event_total_sum.ptr(),
-            weights ? weights->readOnlyPtr() : nullptr);
+            weights ? weights->readOnlyPtr() : nullptr, whitening ? whitening->readOnlyPtr() : nullptr);
       SXMC_KERNEL_LAUNCH(pick_new_vector, 1, 64, 0, m.stream, (int)m.nparameters, m.rngs->ptr(),
                          jump_width.readOnlyPtr(), current_vector.readOnlyPtr(), proposed_vector.writeOnlyPtr());
     }
@@ -745,7 +776,7 @@ class MCMC {
       if (sample_weights && m.lockstep) {
         throw pdfz::Error("MCMC: a lockstep set has no weighted fill: walk a chain over signals with sample multiplicities alone");
       }
-      form = sxmc::choose_form(covariance, event_weights != nullptr, sample_weights,
+      form = sxmc::choose_form(covariance, event_weights != nullptr, sample_weights, constrained,
                                WalkFlags{m.group != nullptr, m.reference_form,
                                          m.nsystematics > 0 && !m.systematics_fixed, m.consume, m.lut_output,
                                          m.lockstep != nullptr, m.lookahead || m.lookahead_auto, m.nparameters,
@@ -854,7 +885,9 @@ class MCMC {
       // the same for the whole walk, so recorded steps survive a re-tuning
       d_factor = covariance ? factor->readOnlyPtr() : nullptr;
       d_weights = weights ? weights->readOnlyPtr() : nullptr;
+      d_whitening = whitening ? whitening->readOnlyPtr() : nullptr;
       if (m.group) check(sxmc_group_set_proposal_factor(m.group, d_factor));
+      if (m.group) check(sxmc_group_set_constraint_whitening(m.group, d_whitening));
     }
 
     /** One step of the sequential walk, in the form's launches. */
@@ -893,7 +926,7 @@ class MCMC {
                          (size_t)npartial, d.sums, m.nsignals, m.nsources, a.d_means, a.d_sigmas, a.d_rng,
                          a.d_nll_current, a.d_nll_proposed, a.d_v_current, a.d_v_proposed, a.d_accepted, a.d_counter,
                          a.d_jump_buffer, a.nparameters, a.d_jump_width, a.d_nexpected, a.d_n_mc, a.d_source_id,
-                         a.d_norms, debug_mode, d_factor);
+                         a.d_norms, debug_mode, d_factor, d_whitening);
     }
 
     /** One step of a MIXED walk, every launch on the walk's stream and none of them a wait, a copy or an allocation (so
@@ -936,7 +969,7 @@ class MCMC {
                          (size_t)m.nnllthreads, d.sums, m.nsignals, m.nsources, a.d_means, a.d_sigmas, a.d_rng,
                          a.d_nll_current, a.d_nll_proposed, a.d_v_current, a.d_v_proposed, a.d_accepted, a.d_counter,
                          a.d_jump_buffer, a.nparameters, a.d_jump_width, a.d_nexpected, a.d_n_mc, a.d_source_id,
-                         a.d_norms, debug_mode, d_factor);
+                         a.d_norms, debug_mode, d_factor, d_whitening);
     }
 
     /** The run of steps that starts at step i: what the host does before it (re-tuning, the form of the fill), the
@@ -1145,6 +1178,7 @@ class MCMC {
           for (const KernelMember& k : m.kernels) k.eval->EvalFinished();
         for (pdfz::Eval* p : m.pdfs) p->ForgetBuffers();
         if (m.group) (void)sxmc_group_set_proposal_factor(m.group, nullptr);   // (it borrowed this walk's factor)
+        if (m.group) (void)sxmc_group_set_constraint_whitening(m.group, nullptr);   // (and its whitening matrix)
         if (shadow)
           for (auto& p : shadow->evaluators) p->ForgetBuffers();
         // (before the lock is re-taken: the set's launcher takes the two in the other order)
@@ -1185,6 +1219,7 @@ class MCMC {
   const char* form_name = "reference";
   std::vector<double> last_factor;     //!< ProposalFactor(): the last COVARIANCE walk's factor, as the device read it
   double last_shrinkage = 0;
+  std::vector<double> last_whitening;  //!< ConstraintWhitening(): the last constrained walk's matrix, as the device read it
   bool optimized = false;
   size_t ahead_passes = 0, ahead_passes_seen = 0;   //!< look-ahead walk: passes launched / counted in the rate below
   double ahead_steps_seen = 0;

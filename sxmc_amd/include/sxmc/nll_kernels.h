@@ -72,6 +72,17 @@ inline void nll_total(int grid, int block, size_t, sxmc_stream_t stream, const s
                               events_total, nexpected, n_mc, source_id, norms, nll));
 }
 
+/** The same with correlated constraints' whitening matrix behind nll (include/sxmc_hip.h,
+ *  sxmc_group_set_constraint_whitening: the law and the layout; null: the launch above). */
+inline void nll_total(int grid, int block, size_t, sxmc_stream_t stream, const size_t nparameters,
+                      const double* pars, const size_t nsignals, const size_t nsources, const double* means,
+                      const double* sigmas, const double* events_total, const double* nexpected,
+                      const unsigned* n_mc, const short* source_id, const unsigned* norms, double* nll,
+                      const double* whitening) {
+  check(sxmc_launch_nll_total_whitened(grid, block, stream, nparameters, pars, nsignals, nsources, means, sigmas,
+                                       events_total, nexpected, n_mc, source_id, norms, nll, whitening));
+}
+
 /** finish_nll_jump_pick_combo (nll_kernels.h:190-207) */
 inline void finish_nll_jump_pick_combo(int grid, int block, size_t, sxmc_stream_t stream,
                                        const size_t npartial_sums, const double* sums, const size_t nsignals,
@@ -103,6 +114,24 @@ inline void finish_nll_jump_pick_combo(int grid, int block, size_t, sxmc_stream_
                                                       v_proposed, accepted, counter, jump_buffer, nparameters,
                                                       jump_width, nexpected, n_mc, source_id, norms,
                                                       debug_mode ? 1 : 0, factor));
+}
+
+/** ... and with correlated constraints' whitening matrix behind the factor (sxmc_group_set_constraint_whitening; either
+ *  may be null). */
+inline void finish_nll_jump_pick_combo(int grid, int block, size_t, sxmc_stream_t stream,
+                                       const size_t npartial_sums, const double* sums, const size_t nsignals,
+                                       const size_t nsources, const double* means, const double* sigmas,
+                                       RNGState* rng, double* nll_current, double* nll_proposed,
+                                       double* v_current, double* v_proposed, int* accepted, int* counter,
+                                       float* jump_buffer, int nparameters, const float* jump_width,
+                                       const double* nexpected, const unsigned* n_mc, const short* source_id,
+                                       const unsigned* norms, const bool debug_mode, const double* factor,
+                                       const double* whitening) {
+  check(sxmc_launch_finish_nll_jump_pick_combo_constrained(grid, block, stream, npartial_sums, sums, nsignals,
+                                                           nsources, means, sigmas, rng, nll_current, nll_proposed,
+                                                           v_current, v_proposed, accepted, counter, jump_buffer,
+                                                           nparameters, jump_width, nexpected, n_mc, source_id, norms,
+                                                           debug_mode ? 1 : 0, factor, whitening));
 }
 
 }  // namespace launch

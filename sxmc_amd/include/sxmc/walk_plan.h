@@ -91,6 +91,8 @@ struct WalkFlags {
   bool sample_weights = false;        //!< a histogram member carries sample multiplicities (weighted Monte Carlo): every
                                      //!< sequential form takes it -- only the fill differs --; the look-ahead pass and
                                      //!< lockstep sets have no weighted fill
+  bool correlated_constraints = false;   //!< the Gaussian constraints are tied by a correlation matrix: every sequential
+                                        //!< form takes its whitening matrix in the step end; never LOOKAHEAD or LOCKSTEP
 };
 /** The form of the walk's steps, from the flags alone.  LOOKAHEAD is a candidate: two questions to the device (does the
  *  plan stream codes, is the pass offered for this shape) may still narrow it to CONSUMING, see narrowed(). */
@@ -120,9 +122,10 @@ inline WalkForm choose_form(const WalkFlags& f) {
   WalkForm::Step step = WalkForm::REFERENCE;
   if (fused && !f.consume) step = WalkForm::BATCHED;
   if (fused && f.consume) {
-    // (a correlated proposal, weighted events, weighted Monte Carlo samples: asked with lookahead, or given a lockstep
-    // set, the walk goes sequentially)
-    step = (f.covariance_proposal || f.event_weights || f.sample_weights) ? WalkForm::CONSUMING
+    // (a correlated proposal, weighted events, weighted Monte Carlo samples, correlated constraints: asked with lookahead,
+    // or given a lockstep set, the walk goes sequentially)
+    step = (f.covariance_proposal || f.event_weights || f.sample_weights || f.correlated_constraints)
+               ? WalkForm::CONSUMING
            : f.in_lockstep_set   ? WalkForm::LOCKSTEP
            : (f.lookahead_asked && !f.lut_output && f.nparameters <= 256) ? WalkForm::LOOKAHEAD
                                                                            : WalkForm::CONSUMING;
@@ -146,6 +149,12 @@ inline WalkForm choose_form(bool covariance_proposal, bool event_weights, WalkFl
 inline WalkForm choose_form(bool covariance_proposal, bool event_weights, bool sample_weights, WalkFlags f) {
   f.sample_weights = sample_weights;
   return choose_form(covariance_proposal, event_weights, f);
+}
+/** ... and whose constraints are correlated (the walk's, named beside the signals' weights). */
+inline WalkForm choose_form(bool covariance_proposal, bool event_weights, bool sample_weights, bool correlated_constraints,
+                            WalkFlags f) {
+  f.correlated_constraints = correlated_constraints;
+  return choose_form(covariance_proposal, event_weights, sample_weights, f);
 }
 
 }  // namespace sxmc

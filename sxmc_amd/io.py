@@ -262,6 +262,67 @@ def fit_proposal(fit):
     return proposal, v
 
 
+def fit_constraint_correlations(fit, names, sigmas):
+    """The fit's "constraint_correlations": a list of groups {"parameters": [names], "matrix": [[...]]} that tie the
+    Gaussian constraints of the named parameters together.  names, sigmas: the walk's parameter names (sources, then
+    <systematic>_<j>) and constraint widths.  Groups are disjoint; each matrix is square, of its group's size.  The groups
+    are scattered into the P x P identity and the whole is validated by sxmc_constraint_whitening (symmetric, unit
+    diagonal, entries in [-1, 1], positive definite, no correlated parameter without a sigma).  -> rho [P, P] float64,
+    or None without the key: such a configuration loads as before.  Same rules and messages as
+    sxmc::detail::fit_constraint_correlations_from_json (config.h)."""
+    if "constraint_correlations" not in fit:
+        return None
+    groups = fit["constraint_correlations"]
+    if not isinstance(groups, list):
+        raise ValueError('fit: "constraint_correlations" is not a list of groups')
+    names = list(names)
+    P = len(names)
+    rho = np.eye(P)
+    taken = [False] * P
+    for g, grp in enumerate(groups):
+        where = "fit: constraint_correlations[%d]: " % g
+        if (not isinstance(grp, dict) or not isinstance(grp.get("parameters"), list)
+                or not isinstance(grp.get("matrix"), list)):
+            raise ValueError(where + 'a group is {"parameters": [names], "matrix": [[...]]}')
+        index = []
+        for name in grp["parameters"]:
+            if not isinstance(name, str):
+                raise ValueError("parameters[]: not a string")
+            if name not in names:
+                raise ValueError(where + 'unknown parameter "%s"' % name)
+            at = names.index(name)
+            if taken[at]:
+                raise ValueError(where + 'parameter "%s" is already in a group' % name)
+            taken[at] = True
+            index.append(at)
+        n = len(index)
+        matrix = grp["matrix"]
+        if len(matrix) != n or any(not isinstance(row, list) or len(row) != n for row in matrix):
+            raise ValueError(where + '"matrix" must be %d x %d for its %d parameters' % (n, n, n))
+        for r in range(n):
+            for c in range(n):
+                rho[index[r], index[c]] = _number(matrix[r][c], "matrix[][]")
+    if P == 0:
+        raise ValueError("fit: constraint_correlations: no parameters")
+    from . import capi, nll
+    try:
+        nll.constraint_whitening(rho, np.asarray(sigmas, np.float64))
+    except capi.SxmcError as e:
+        raise ValueError("fit: constraint_correlations: " + e.msg) from None
+    return rho
+
+
+def parameter_names_and_sigmas(fc):
+    """The walk's parameter vector as the loaders know it: sources, then <systematic>_<j> (mcmc.cpp:53-98)."""
+    names = [s["name"] for s in fc.sources]
+    sigmas = [float(s["sigma"]) for s in fc.sources]
+    for s in fc.systematics:
+        for j in range(s["npars"]):
+            names.append("%s_%d" % (s["name"], j))
+            sigmas.append(float(s["sigmas"][j]))
+    return names, sigmas
+
+
 ASIMOV_WITH_DATA = 'fit: "asimov" fits the expected data set: it cannot be combined with configured data sets'
 
 
@@ -349,6 +410,8 @@ def load_config(path_or_text, base_dir=None):
         else:                                                   # the signal is a source for itself
             fc.sources.append(dict(name=sname, index=len(fc.sources), mean=np.float32(sconf.get("mean", 1.0)),
                                    sigma=np.float32(sconf.get("sigma", 0.0)), fixed=bool(sconf.get("fixed", False))))
+
+    fc.constraint_correlation = fit_constraint_correlations(fit, *parameter_names_and_sigmas(fc))
 
     # order of the sampled fields: observables, then extra truth fields, then DATASET (config.cpp:153-194)
     fc.sample_fields = []
@@ -569,7 +632,8 @@ def run_config(path, out_dir=None, nexperiments=None, nsteps=None, report=None, 
             events, _ = ensemble.make_fake_dataset(rng, w, m.pdfs, poisson=True)
         m.reseed(((fc.seed << 20) + i) & 0xFFFFFFFF)
         chain, _ = m.walk(events, nsteps, fc.burnin_fraction, debug_mode=fc.debug_mode, proposal=fc.proposal,
-                          proposal_shrinkage=fc.proposal_shrinkage, event_weights=weights)
+                          proposal_shrinkage=fc.proposal_shrinkage, event_weights=weights,
+                          constraint_correlation=fc.constraint_correlation)
         if fc.error_type == "projection":                       # likelihood.cpp:104-137: the chosen estimator
             cols = [ensemble.projection_interval(chain[:, p], fc.confidence) for p in range(chain.shape[1] - 1)]
             iv = np.array([c[:4] for c in cols], np.float32)

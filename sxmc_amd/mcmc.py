@@ -130,6 +130,10 @@ class MCMC:
         self._factor_buffer = None
         self.proposal_shrinkage_used = None
         self.event_weights = None               # setup(event_weights=...): one double per event on the device, or None
+        # correlated constraints (walk(constraint_correlation=...)): the whitening matrix W on the device, P x P doubles
+        # with W_ij at [j * P + i], or None: one independent Gaussian per parameter
+        self.constraint_whitening = None
+        self._whitening_host = None
 
     # mcmc.cpp:198-228 (keeps the reference's `i < nsignals` test at :217)
     def initial_jump_widths(self, fixed=None):
@@ -213,7 +217,7 @@ class MCMC:
                              self.event_total_sum)
         nll.nll_total(1, 1, self.stream, self.nparameters, v, self.nsignals, self.nsources,
                       self.parameter_means, self.parameter_sigma, self.event_total_sum, self.nexpected,
-                      self.n_mc, self.source_id, self.normalizations, out)
+                      self.n_mc, self.source_id, self.normalizations, out, whitening=self.constraint_whitening)
 
     def step(self, debug_mode=False):
         """One pass of the hot path = one NLL evaluation at the proposed vector + the fused
@@ -268,7 +272,7 @@ class MCMC:
                                        self.current_vector, self.proposed_vector, self.accept_counter,
                                        self.jump_counter, self.jump_buffer, self.nparameters, self.jump_width,
                                        self.nexpected, self.n_mc, self.source_id, self.normalizations,
-                                       debug_mode, factor=self.proposal_factor)
+                                       debug_mode, factor=self.proposal_factor, whitening=self.constraint_whitening)
 
     def _launching(self, n):
         """Every step appends a row to the jump buffer (sync_interval rows, jump_decider nll_kernels.cpp:78-84, which
@@ -286,7 +290,8 @@ class MCMC:
         self.rngs = nll.make_rngs(self.nparameters, seed, self.stream)
 
     def walk(self, data, nsteps, burnin_fraction, debug_mode=False, sync_interval=10000, graph_steps=0,
-             lookahead=False, proposal="diagonal", proposal_shrinkage=0.05, event_weights=None):
+             lookahead=False, proposal="diagonal", proposal_shrinkage=0.05, event_weights=None,
+             constraint_correlation=None):
         """MCMC::operator() (mcmc.cpp:143-387): start at the means, walk nsteps, re-tune the proposal
         widths from the chain's spread at burnin_steps and 2 * burnin_steps (dropping the steps so far
         unless debug_mode).  Returns (chain [nkept, P + 1] float32, accepted).
@@ -297,9 +302,14 @@ class MCMC:
         "Correlated proposals"; include/sxmc_hip.h, sxmc_proposal_factor); every parameter's marginal width stays the
         reference's.  Such a walk is always sequential: asked with lookahead it walks step by step.
         event_weights: one weight per event (see setup); such a walk is sequential too -- there is no weighted look-ahead
-        pass (Group.LookaheadSupported answers no)."""
+        pass (Group.LookaheadSupported answers no).
+        constraint_correlation: a [P, P] correlation matrix over the parameter vector (sources, then the systematics'
+        parameters) that ties the Gaussian constraints together, or None: one independent Gaussian per parameter.  The
+        NLL's constraint terms become 0.5 r_i^2 of the whitened residuals r = W x, W the inverse Cholesky factor
+        (README, "Correlated constraints"; include/sxmc_hip.h, sxmc_constraint_whitening, which validates the matrix).
+        Such a walk is sequential too."""
         self.walk_begin(data, nsteps, burnin_fraction, debug_mode, sync_interval, proposal, proposal_shrinkage,
-                        event_weights)
+                        event_weights, constraint_correlation)
         self.lookahead_passes = 0
         # (a shape the look-ahead pass is not offered for -- see Group.LookaheadSupported -- walks sequentially)
         if lookahead and self.group.LookaheadSupported():
@@ -384,7 +394,7 @@ class MCMC:
     # The same walk cut into per-step pieces, so that several chains can be advanced in turn and have
     # their kernels in flight together (one stream per chain).
     def walk_begin(self, data, nsteps, burnin_fraction, debug_mode=False, sync_interval=10000, proposal="diagonal",
-                   proposal_shrinkage=0.05, event_weights=None):
+                   proposal_shrinkage=0.05, event_weights=None, constraint_correlation=None):
         w = self.w
         if proposal not in ("diagonal", "covariance"):
             raise ValueError('proposal must be "diagonal" or "covariance", not %r' % (proposal,))
@@ -396,12 +406,36 @@ class MCMC:
         self.current_vector.set(w.parameter_means().astype(np.float64))
         self.jump_counter.set(np.zeros(1, np.int32))
         self.accept_counter.set(np.zeros(1, np.int32))
+        self.set_constraint_correlation(constraint_correlation)   # (before the first NLL, which has the constraints)
         self.setup(data, sync_interval=sync_interval, event_weights=event_weights)
         # mcmc.cpp:199: nfloat = the parameters that are not fixed (a fixed one carries jump width <= 0)
         nfloat = max(1, int(np.count_nonzero(self.jump_width.get() > 0)))
         self._scale_factor = np.float32(2.4 * 2.4 / nfloat)
         self._set_proposal(proposal)
         self._rows, self._accepted = [np.zeros((0, self.nparameters + 1), np.float32)], 0
+
+    def set_constraint_correlation(self, rho):
+        """Correlated Gaussian constraints from now on: rho, a [P, P] correlation matrix (validated and whitened by
+        sxmc_constraint_whitening, whose refusals name the entry), or None to go back to independent ones.  Handed to the
+        group (its step ends) and to the group-less launch points (nll(), step()).  Call it before setup()."""
+        if self._graph is not None:
+            graph, self._graph = self._graph, None          # (recorded steps hold the other law's arguments)
+            if hasattr(graph, "close"):
+                graph.close()
+        if rho is None:
+            self.constraint_whitening, self._whitening_host = None, None
+        else:
+            W = nll.constraint_whitening(rho, self.w.parameter_sigmas().astype(np.float64))
+            self._whitening_host = W
+            self.constraint_whitening = DeviceArray(W)
+        self.group.SetConstraintWhitening(self.constraint_whitening)
+
+    def ConstraintWhitening(self):
+        """The whitening matrix in use as [P, P] (W[i, j]), or None without correlated constraints."""
+        if self._whitening_host is None:
+            return None
+        P = self.nparameters
+        return self._whitening_host.reshape(P, P).T.copy()
 
     def _set_proposal(self, proposal):
         """Diagonal: no factor anywhere.  Covariance: L = diag(w) through the re-tuning's own code path (no rows), in the

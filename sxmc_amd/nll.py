@@ -58,12 +58,34 @@ def proposal_factor(rows, new_widths, shrinkage=0.05):
     return out, used.value
 
 
+def constraint_whitening(rho, sigmas):
+    """The whitening matrix of correlated Gaussian constraints (sxmc_constraint_whitening, host arithmetic only): rho
+    [P, P] float64 the correlation matrix over the parameter vector, sigmas [P] the constraint widths (<= 0: none).
+    Returns W as [P * P] float64 in the device's layout, W_ij at [j * P + i].  A refused matrix raises capi.SxmcError
+    with the library's message, which names the entry or the pivot."""
+    sg = np.ascontiguousarray(sigmas, np.float64).reshape(-1)
+    P = sg.size
+    r = np.ascontiguousarray(rho, np.float64)
+    if r.shape != (P, P):
+        raise ValueError("constraint correlation: a %d x %d matrix is needed, not one of shape %r" % (P, P, r.shape))
+    out = np.zeros(P * P, np.float64)
+    capi.call("sxmc_constraint_whitening", ptr(r), ptr(sg), int(P), ptr(out))
+    return out
+
+
 def nll_event_reduce(grid, block, stream, nthreads, sums, total_sum):
     capi.call("sxmc_launch_nll_event_reduce", grid, block, ptr(stream), int(nthreads), ptr(sums), ptr(total_sum))
 
 
 def nll_total(grid, block, stream, nparameters, pars, nsignals, nsources, means, sigmas, events_total,
-              nexpected, n_mc, source_id, norms, nll):
+              nexpected, n_mc, source_id, norms, nll, whitening=None):
+    """whitening: correlated constraints' P x P whitening matrix on the device (sxmc_group_set_constraint_whitening in
+    include/sxmc_hip.h has the law and the layout), or None: the reference's launch point."""
+    if whitening is not None:
+        capi.call("sxmc_launch_nll_total_whitened", grid, block, ptr(stream), int(nparameters), ptr(pars),
+                  int(nsignals), int(nsources), ptr(means), ptr(sigmas), ptr(events_total), ptr(nexpected), ptr(n_mc),
+                  ptr(source_id), ptr(norms), ptr(nll), ptr(whitening))
+        return
     capi.call("sxmc_launch_nll_total", grid, block, ptr(stream), int(nparameters), ptr(pars), int(nsignals),
               int(nsources), ptr(means), ptr(sigmas), ptr(events_total), ptr(nexpected), ptr(n_mc),
               ptr(source_id), ptr(norms), ptr(nll))
@@ -72,9 +94,17 @@ def nll_total(grid, block, stream, nparameters, pars, nsignals, nsources, means,
 def finish_nll_jump_pick_combo(grid, block, stream, npartial_sums, sums, nsignals, nsources, means, sigmas,
                                rng, nll_current, nll_proposed, v_current, v_proposed, accepted, counter,
                                jump_buffer, nparameters, jump_width, nexpected, n_mc, source_id, norms,
-                               debug_mode=False, factor=None):
+                               debug_mode=False, factor=None, whitening=None):
     """factor: a correlated proposal's P x P factor on the device (sxmc_group_set_proposal_factor in include/sxmc_hip.h
-    has the law and the layout), or None: the diagonal proposal through the reference-shaped launch point."""
+    has the law and the layout), or None: the diagonal proposal through the reference-shaped launch point.
+    whitening: correlated constraints' whitening matrix on the device (sxmc_group_set_constraint_whitening), or None."""
+    if whitening is not None:
+        capi.call("sxmc_launch_finish_nll_jump_pick_combo_constrained", grid, block, ptr(stream), int(npartial_sums),
+                  ptr(sums), int(nsignals), int(nsources), ptr(means), ptr(sigmas), ptr(rng), ptr(nll_current),
+                  ptr(nll_proposed), ptr(v_current), ptr(v_proposed), ptr(accepted), ptr(counter),
+                  ptr(jump_buffer), int(nparameters), ptr(jump_width), ptr(nexpected), ptr(n_mc), ptr(source_id),
+                  ptr(norms), int(bool(debug_mode)), ptr(factor), ptr(whitening))
+        return
     if factor is not None:
         capi.call("sxmc_launch_finish_nll_jump_pick_combo_factor", grid, block, ptr(stream), int(npartial_sums),
                   ptr(sums), int(nsignals), int(nsources), ptr(means), ptr(sigmas), ptr(rng), ptr(nll_current),
@@ -204,6 +234,12 @@ class EvalGroup:
             return
         w = np.ascontiguousarray(weights, np.float64).reshape(-1)
         capi.call("sxmc_group_set_event_weights", self._g, ptr(w), int(w.size))
+
+    def SetConstraintWhitening(self, whitening):
+        """Correlated Gaussian constraints for every step end this group launches: whitening, a DeviceArray of P x P
+        doubles (borrowed: keep it alive), or None for one independent Gaussian per parameter
+        (sxmc_group_set_constraint_whitening)."""
+        capi.call("sxmc_group_set_constraint_whitening", self._g, ptr(whitening))
 
     def SetLutOutput(self, enable):
         """False: EvalNllAsync / McmcStepAsync do not write the lookup table and sum over the distinct tuples
